@@ -31,6 +31,11 @@ every step, a pass of its own), and `dropin` is the reference-shaped call patter
 Halo, set_redshift(z) + power_mm(k) per redshift, host arrays in and out.
 
 --workload c3 | c4 | c5 runs one of the other configs as the headline instead.
+
+--dump-outputs DIR writes what the headline's last timed step computed -- the arrays a caller of
+that path receives: the P(k, z) grid (c2, c3, batch), w(theta) and C_l (c4, c5) -- as
+DIR/<name>.npy in float64, so that two builds can be compared output for output (the inputs are
+fixed by the arguments).
 """
 import argparse
 import json
@@ -52,6 +57,7 @@ N_THETA, N_ELL = 1024, 2048
 STAGE_K_COUNTER_FILES = ("round4_stage_k_counters.json", "round3_stage_k_counters.json",
                          "round2_stage_k_counters.json")
 PROFILE_ROUND = "round4"
+DUMP_BYTES_MAX = 64 << 20
 
 
 # ---------------------------------------------------------------------------
@@ -294,14 +300,15 @@ def batch_cosmologies(n, draws, seed):
     return out
 
 
-def batch_leg(D, n, distinct, steps, warmup, stream, which="power_mm", mf="st"):
+def batch_leg(D, n, distinct, steps, warmup, stream, which="power_mm", mf="st", outputs=None):
     """SURVEY 8(f) rank 1, the batch-over-parameters axis (simulation_design.py:116-155, the MCMC
     loop of examples/example_script.py:141-143): n epochs (z = linspace(0, 1.5, n)) x 4096 k per
     step.  distinct=False: one cosmology for all (configs[1] made longer; the cosmology-only work
     is shared and no parameter changes between steps).  distinct=True: every epoch its own
     cosmology AND a fresh draw every step (a pool of 4 pre-packed draws taken in turn, so that
     every step's block differs from what the device holds: no upload is skipped, the host packs
-    nothing inside the step).  Returns the result dict of one batch_scaling entry."""
+    nothing inside the step).  Returns the result dict of one batch_scaling entry; `outputs`
+    (a dict), if given, receives the last timed step's grid on the host."""
     import torch
     from chomp_amd import grid
     z = numpy.linspace(0.0, Z_MAX, n)
@@ -332,6 +339,8 @@ def batch_leg(D, n, distinct, steps, warmup, stream, which="power_mm", mf="st"):
     D.fence()
     elapsed = time.perf_counter() - t0
     assert bool(torch.isfinite(out).all())
+    if outputs is not None:
+        outputs[which] = out.cpu().numpy()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     reps = max(3, steps // 2)
     ev0.record(stream)
@@ -371,12 +380,13 @@ def batch_leg(D, n, distinct, steps, warmup, stream, which="power_mm", mf="st"):
     return res
 
 
-def projection_leg(D, ggl, steps, warmup):
+def projection_leg(D, ggl, steps, warmup, outputs=None):
     """configs[3] (c4: gal-gal clustering, J0, P_gg) and configs[4] (c5: galaxy-galaxy
     lensing, J2, HaloFit P_gm): a step = the whole projection path -- MultiEpoch chi(z),
     both windows, the 50-knot Bessel kernel and z_bar, the halo tables at z_bar, then
     w(theta) at 1024 theta and C_l at 2048 l -- with theta / l sharded over the ranks
-    (set-up replicated, as SURVEY 8(e) prescribes) and one all-gather each."""
+    (set-up replicated, as SURVEY 8(e) prescribes) and one all-gather each.  `outputs` (a
+    dict), if given, receives the last timed step's w(theta) and C_l on the host."""
     import contextlib
     import torch
     from chomp_amd import cosmology, correlation, halo, kernel, grid
@@ -434,6 +444,10 @@ def projection_leg(D, ggl, steps, warmup):
         elapsed = D.max_over_ranks(time.perf_counter() - t0)
         assert w.numel() == N_THETA and c.numel() == N_ELL
         assert bool(torch.isfinite(w).all()) and bool((c > 0).all())
+        if outputs is not None:
+            # (the graph replay below becomes the headline only if it equals this step bit for bit)
+            outputs["wtheta"] = w.cpu().numpy()
+            outputs["cell"] = c.cpu().numpy()
         dist = None
         if D.world == 1:
             dist = step_distribution(step, steps, torch.cuda.current_stream(D.dev), D.dev)
@@ -505,6 +519,26 @@ def stage_k_roofline(stage_k_seconds, workload):
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each host array as path/<name>.npy in float64.  An array larger than
+    its share of DUMP_BYTES_MAX (only a --batch-n far above the default gets there) is replaced by
+    a fixed, seeded sample of its flattened elements, in index order.  Returns what was written."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // len(arrays)
+    info = {}
+    for name, a in arrays.items():
+        a = numpy.ascontiguousarray(a, dtype=numpy.float64)
+        entry = {"shape": list(a.shape), "dtype": "float64"}
+        n_max = share // a.itemsize
+        if a.size > n_max:
+            entry["sample"] = "%d of %d elements, flat index order (seed 0)" % (n_max, a.size)
+            idx = numpy.sort(numpy.random.default_rng(0).choice(a.size, n_max, replace=False))
+            a = a.reshape(-1)[idx]
+        numpy.save(os.path.join(path, name + ".npy"), a)
+        info[name] = entry
+    return info
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (one per GPU)
     with torch.distributed.run as CHILDREN of this process -- which never initialises the GPU
@@ -561,7 +595,12 @@ def main():
     ap.add_argument("--rehearse", action="store_true",
                     help="test-only: run the N > 1 path on ONE GPU (every rank on device 0, "
                          "gloo all-gather through host memory); the numbers mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has not
@@ -618,8 +657,13 @@ def main():
     if args.rehearse and world > 1:
         rehearsal_gathers()
 
+    # --dump-outputs: the headline leg fills this right after its timed region; rank 0 writes it
+    outputs = {} if args.dump_outputs and rank == 0 else None
+
     def finish(res):
         if rank == 0:
+            if outputs:
+                res["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(res))
         if world > 1:
             dist.barrier()
@@ -628,7 +672,8 @@ def main():
     # ---- the batch-over-parameters axis as the headline (profiling runs: tools/prof.sh sq)
     if args.workload == "batch":
         assert world == 1, "--workload batch is a one-GPU measurement"
-        b = batch_leg(D, args.batch_n, bool(args.batch_distinct), args.steps, args.warmup, stream)
+        b = batch_leg(D, args.batch_n, bool(args.batch_distinct), args.steps, args.warmup, stream,
+                      outputs=outputs)
         return finish({"metric": "halo-model P(k,z) samples/sec (batch over parameters)",
                        "value": b["samples_per_s"], "unit": "samples/s", "n_gpus": 1,
                        "steps": args.steps, "warmup": args.warmup, "ms_per_step": b["ms_per_step"],
@@ -642,7 +687,7 @@ def main():
     # ---- projection workloads as the headline
     if proj:
         ggl = args.workload == "c5"
-        elapsed, pdist, pgraph = projection_leg(D, ggl, args.steps, args.warmup)
+        elapsed, pdist, pgraph = projection_leg(D, ggl, args.steps, args.warmup, outputs)
         res = {"metric": "Limber w(theta) + C_l samples/sec (projection and halo set-up included)",
                "value": (N_THETA + N_ELL) * args.steps / elapsed, "unit": "samples/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -687,6 +732,8 @@ def main():
     #  -- so that a scaling run's N = 1 line equals the plain bench line)
     head = args.scaling or ("weak" if world == 1 else "strong")
     elapsed, hg, k, out = grid_leg(D, which, mf, nz_of[head], args.steps, args.warmup, stream)
+    if outputs is not None:
+        outputs[which] = out.cpu().numpy()      # (the next steps reuse the gather buffers)
     head_dist = step_distribution(hg.bench_step, args.steps, stream, dev)
     nz = nz_of[head]
     ms_per_step = 1e3 * elapsed / args.steps
