@@ -113,9 +113,10 @@ ST_MASS_MIN_SATURATED, ST_MASS_MAX_SATURATED, ST_MASS_SEARCH_EXHAUSTED, ST_SIGMA
 ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000}
 ST_NONFINITE = 0x10000
 ST_SATURATED = ST_MASS_MIN_SATURATED | ST_MASS_MAX_SATURATED
-TUNE_E_STREAM_MIN, TUNE_E_ROWS, TUNE_DEEP_LITERAL, TUNE_ROCTX, TUNE_WTHETA_DIRECT = 0, 1, 2, 3, 4
+TUNE_E_STREAM_MIN, TUNE_DEEP_LITERAL, TUNE_ROCTX, TUNE_WTHETA_DIRECT = 0, 2, 3, 4
 TUNE_CELL_ONE_KERNEL = 5
-TUNE_DEEP_TOL, TUNE_DEEP_MAX_BREAKS, TUNE_DEEP_MAX_FINE, TUNE_HOD_CAP, TUNE_DEEP_SLOTS = 6, 7, 8, 9, 10
+TUNE_DEEP_TOL, TUNE_DEEP_MAX_BREAKS, TUNE_DEEP_MAX_FINE, TUNE_DEEP_SLOTS = 6, 7, 8, 10
+TUNE_COUNT = 11   # (1 and 9: retired knobs, refused like any unknown number)
 
 
 class ChompAccuracyWarning(UserWarning):
@@ -198,8 +199,8 @@ def built_hash():
 def build(force=False, verbose=False, extra_flags=(), out=None):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a
     GPU).  Rebuilds when the sources differ from the ones the .so was built from (their
-    hash is kept beside it).  extra_flags / out: a development build somewhere else (e.g.
-    -DCHOMP_STAMPS into build_exp/), leaving the product library alone."""
+    hash is kept beside it).  extra_flags / out: a development build with other compiler flags
+    somewhere else (e.g. build_exp/), leaving the product library alone."""
     want = source_hash()
     if out is None and not force and os.path.exists(LIB_PATH):
         try:

@@ -154,10 +154,9 @@ struct chomp_ctx {
     int bao = 0, parity = 0, n_slow = -1;
   } plan;
   int slow_parity = 0;
-  // opt-ins for more than 64 KiB of dynamic LDS, done once per context (hipFuncSetAttribute
-  // applies to the current device: a process-wide flag would skip a second device)
-  bool lds_knots_set = false, lds_lns_set = false;
-  unsigned lds_cell_mask = 0;      // k_cell_deep<HF, BAO>: bit 2 HF + BAO
+  // kernel -> the dynamic LDS it has been opted in to (lds_opt_in; per context: hipFuncSetAttribute
+  // applies to the current device, so a process-wide record would skip a second device)
+  std::unordered_map<const void*, int> lds_limit;
   bool slow_by_memset = false;     // set once a Stage E call has been captured into a HIP graph
   int precision = CHOMP_PREC_F64;  // chomp_set_precision
   int with_bao = 0;                // chomp_set_transfer
@@ -345,6 +344,18 @@ int ensure(chomp_ctx* ctx, T** p, size_t* cap, size_t n) {
   *p = nullptr;
   HIPCHK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
   *cap = n;
+  return CHOMP_OK;
+}
+
+// Before a launch with more than 64 KiB of dynamic LDS: opt `kernel` in to `bytes`, once per
+// context and kernel.
+template <class Kernel>
+int lds_opt_in(chomp_ctx* ctx, Kernel* kernel, int bytes) {
+  int& have = ctx->lds_limit[reinterpret_cast<const void*>(kernel)];
+  if (have >= bytes) return CHOMP_OK;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  have = bytes;
   return CHOMP_OK;
 }
 
@@ -620,28 +631,11 @@ int chomp_sync(chomp_ctx* ctx) {
   return CHOMP_OK;
 }
 
-#ifdef CHOMP_STAMPS
-// (development builds only: read / clear the stamps of k_halo_knots_fast)
-int chomp_debug_ks(long long* out, int n, int clear) {
-  if (clear) {
-    static long long z[kStampBlocks * kStampSlots];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(chomp::g_ks), z, sizeof(z));
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(chomp::g_ks), (size_t)n * sizeof(long long));
-}
-// (... and of k_mass_nodes)
-int chomp_debug_ms(long long* out, int n, int clear) {
-  if (clear) {
-    static long long z[64 * 16 * kMStampSlots];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(chomp::g_ms), z, sizeof(z));
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(chomp::g_ms), (size_t)n * sizeof(long long));
-}
-#endif
-
 int chomp_set_tuning(chomp_ctx* ctx, int what, long long value) {
   if (!ctx) return CHOMP_ERR_ARG;
-  if (what < 0 || what >= CHOMP_TUNE_COUNT) return fail(ctx, CHOMP_ERR_ARG, "set_tuning: unknown knob");
+  // (1 and 9 are the numbers of retired knobs: refused like any unknown one)
+  if (what < 0 || what >= CHOMP_TUNE_COUNT || what == 1 || what == 9)
+    return fail(ctx, CHOMP_ERR_ARG, "set_tuning: unknown knob");
   ctx->tune[what] = value < 0 ? -1 : value;
   if (what == CHOMP_TUNE_ROCTX) {
     if (value > 0) {
@@ -890,44 +884,34 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   // (one cosmology or a few: most blocks, shortest launch; a batch of many: four nodes per
   //  thread and the ln S integrals one per wavefront -- see k_sigma_nodes)
   const unsigned gy = (unsigned)(n_slots + (n_epoch + 255) / 256);
-#define CHOMP_SIGMA_NODES(BAO, NPT)                                                              \
-  hipLaunchKernelGGL((k_sigma_nodes<BAO, NPT>),                                                   \
-                     dim3(sigma_node_blocks<NPT>() + sigma_lns_blocks<NPT>() + sigma_gtab_blocks<NPT>(), gy), \
-                     dim3(256), 0, ctx->stream, ctx->cfg, ctx->d_cosmo, ctx->d_z, ctx->d_first,    \
-                     ctx->d_slot, (int)n_slots, (int)n_epoch, ctx->d_epochs, ctx->d_snodes,         \
-                     ctx->d_status)
-  if (n_slots >= 16) {
-    if (ctx->with_bao) CHOMP_SIGMA_NODES(true, 4); else CHOMP_SIGMA_NODES(false, 4);
-    // ... and the aiming tables behind them (the g table of a cosmology staged in LDS)
-    const size_t shl = (size_t)kGTabCount * sizeof(double);
-    if (!ctx->lds_lns_set) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sigma_lns<false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shl));
-      ctx->lds_lns_set = true;
+  rc = with_flag(ctx->with_bao, n_slots >= 16, [&](auto BAO, auto MANY) {
+    constexpr int NPT = MANY ? 4 : 1;
+    hipLaunchKernelGGL((k_sigma_nodes<BAO, NPT>),
+                       dim3(sigma_node_blocks<NPT>() + sigma_lns_blocks<NPT>() + sigma_gtab_blocks<NPT>(), gy),
+                       dim3(256), 0, ctx->stream, ctx->cfg, ctx->d_cosmo, ctx->d_z, ctx->d_first,
+                       ctx->d_slot, (int)n_slots, (int)n_epoch, ctx->d_epochs, ctx->d_snodes,
+                       ctx->d_status);
+    if (!MANY) return CHOMP_OK;
+    // ... and the aiming tables behind them (the g table of a cosmology staged in LDS; the
+    // instance with BAO stages none)
+    const size_t shl = BAO ? 0 : (size_t)kGTabCount * sizeof(double);
+    if constexpr (!BAO) {
+      const int rcl = lds_opt_in(ctx, &k_sigma_lns<BAO>, (int)shl);
+      if (rcl) return rcl;
     }
-    if (ctx->with_bao)
-      hipLaunchKernelGGL(k_sigma_lns<true>, dim3((unsigned)n_slots), dim3(kLnsThreads), 0, ctx->stream,
-                         ctx->cfg, ctx->d_cosmo, ctx->d_z, ctx->d_first, ctx->d_snodes);
-    else
-      hipLaunchKernelGGL(k_sigma_lns<false>, dim3((unsigned)n_slots), dim3(kLnsThreads), shl, ctx->stream,
-                         ctx->cfg, ctx->d_cosmo, ctx->d_z, ctx->d_first, ctx->d_snodes);
-  } else {
-    if (ctx->with_bao) CHOMP_SIGMA_NODES(true, 1); else CHOMP_SIGMA_NODES(false, 1);
-  }
-#undef CHOMP_SIGMA_NODES
+    hipLaunchKernelGGL(k_sigma_lns<BAO>, dim3((unsigned)n_slots), dim3(kLnsThreads), shl, ctx->stream,
+                       ctx->cfg, ctx->d_cosmo, ctx->d_z, ctx->d_first, ctx->d_snodes);
+    return CHOMP_OK;
+  });
+  if (rc) return rc;
   // (k_epoch_probe lives in chomp_probe.hip: the one kernel that is faster WITH machine LICM --
   //  but for the probing phase of a large batch, one wavefront per probe, compiled here)
-  if (n_epoch >= 128) {
-    const dim3 pgrid((unsigned)n_epoch, 2 * kProbes);
-    if (ctx->with_bao)
-      hipLaunchKernelGGL((k_epoch_probe<true, 1, 1>), pgrid, dim3(64), 0, ctx->stream, ctx->cfg,
-                         ctx->d_epochs, ctx->d_search, ctx->d_cand, ctx->d_snodes, ctx->d_probe,
-                         ctx->d_count, ctx->d_status);
-    else
-      hipLaunchKernelGGL((k_epoch_probe<false, 1, 1>), pgrid, dim3(64), 0, ctx->stream, ctx->cfg,
-                         ctx->d_epochs, ctx->d_search, ctx->d_cand, ctx->d_snodes, ctx->d_probe,
-                         ctx->d_count, ctx->d_status);
-  }
+  if (n_epoch >= 128)
+    with_flag(ctx->with_bao, [&](auto BAO) {
+      hipLaunchKernelGGL((k_epoch_probe<BAO, 1, 1>), dim3((unsigned)n_epoch, 2 * kProbes), dim3(64), 0,
+                         ctx->stream, ctx->cfg, ctx->d_epochs, ctx->d_search, ctx->d_cand, ctx->d_snodes,
+                         ctx->d_probe, ctx->d_count, ctx->d_status);
+    });
   chomp::launch_epoch_probe(ctx->with_bao != 0, (unsigned)n_epoch, ctx->stream, ctx->cfg,
                             ctx->d_epochs, ctx->d_search, ctx->d_cand, ctx->d_snodes,
                             ctx->d_probe, ctx->d_count, ctx->d_status);
@@ -994,16 +978,13 @@ static int launch_nu_mass(chomp_ctx* ctx, int mf_kind, const HaloPlan* plan) {
   //  a cosmology per epoch: an epoch's masses side by side -- see k_nu_table)
   //  (the epochs as the grid's y axis: at most 65535 of them)
   const int ef = (ctx->n_slots < 16 || n > 65535) ? 1 : 0;
-#define CHOMP_NU_TABLE(BAO, NW)                                                                 \
-  hipLaunchKernelGGL((k_nu_table<BAO, NW>), ef ? dim3((unsigned)n, L.NM) : dim3(L.NM, (unsigned)n), \
-                     dim3(64 * NW), 0, ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_search,   \
-                     ctx->d_snodes, ctx->d_tab, ctx->d_status, ef)
-  if ((size_t)L.NM * n <= 512) {      // (fewer integrals than SIMDs to put them on)
-    if (ctx->with_bao) CHOMP_NU_TABLE(true, 4); else CHOMP_NU_TABLE(false, 4);
-  } else {
-    if (ctx->with_bao) CHOMP_NU_TABLE(true, 1); else CHOMP_NU_TABLE(false, 1);
-  }
-#undef CHOMP_NU_TABLE
+  // (fewer integrals than SIMDs to put them on: four wavefronts to an integral)
+  with_flag(ctx->with_bao, (size_t)L.NM * n <= 512, [&](auto BAO, auto FEW) {
+    constexpr int NW = FEW ? 4 : 1;
+    hipLaunchKernelGGL((k_nu_table<BAO, NW>), ef ? dim3((unsigned)n, L.NM) : dim3(L.NM, (unsigned)n),
+                       dim3(64 * NW), 0, ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_search,
+                       ctx->d_snodes, ctx->d_tab, ctx->d_status, ef);
+  });
   const size_t sh = (size_t)mass_lds_doubles(L.NM) * sizeof(double);
   const int ng = plan && plan->ng > 0 ? plan->ng : 1;
   // (node-table chunks: as many blocks per (epoch, group) as keep the launch under ~2 blocks
@@ -1021,6 +1002,32 @@ static int launch_nu_mass(chomp_ctx* ctx, int mf_kind, const HaloPlan* plan) {
   HIPCHK(hipGetLastError());
   return CHOMP_OK;
 }
+
+// The launches of k_halo_knots_fast in a halo set-up (launch_halo_knots): what they share, and
+// one launch on the listed knots in the sample buffer's slots [lo, hi) of round `round`
+// (from_eval: on the knots the lean instance handed on).
+extern "C++" struct KnotsFast {
+  chomp_ctx* ctx;
+  const HaloPlan& P;
+  size_t lds;                      // dynamic LDS of every instance
+  int all_literal;
+  double deep_tol;
+  int max_rough, max_fine, parts;
+  template <int NT, bool SELF, bool EVAL, bool LIT = false>
+  int launch(unsigned grid, int round, int lo, int hi, int from_eval) const {
+    if (lds > 64 * 1024) {
+      const int rc = lds_opt_in(ctx, &k_halo_knots_fast<kDeepCoarse, NT, SELF, EVAL, LIT>, 80 * 1024);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL((k_halo_knots_fast<kDeepCoarse, NT, SELF, EVAL, LIT>), dim3(grid), dim3(NT), lds,
+                       ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, ctx->d_tab, ctx->d_sici, P.groups[0],
+                       P.groups[1], P.groups[2], P.kmask, (int)ctx->n_epoch, ctx->d_pending, ctx->d_npend,
+                       ctx->d_epochs, P.fam, ctx->d_status, ctx->d_deepw, all_literal, deep_tol, max_rough,
+                       max_fine, ctx->d_deepstat, ctx->d_samples, ctx->d_psum, parts, round, lo, hi,
+                       from_eval, reinterpret_cast<const DeepPlan*>(ctx->d_plan), ctx->d_profile, ctx->d_hod);
+    return CHOMP_OK;
+  }
+};
 
 // The knot integrals and everything after them (k_halo_knots, k_halo_knots_fast with the
 // per-epoch finalisation).
@@ -1062,10 +1069,9 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
   // (a set-up of one or a few epochs -- every launch lasts as long as its slowest unit -- leaves
   //  the table at level 9; a batch, where the ~11 % of knots that converge AT level 10 would each
   //  take a slot, a sampling work item and a summing block, walks the whole table: 888 against
-  //  1001 listed knots and -6.6 us per configs[2] step, tools/scratch/hod_cap.py)
-  int hod_cap = ctx->tune[CHOMP_TUNE_HOD_CAP] >= 0 ? (int)ctx->tune[CHOMP_TUNE_HOD_CAP]
-                : ((size_t)L.NK * n * ng <= 768 ? kHodCapLevel : kNodeLevel);
-  if (hod_cap < 6) hod_cap = 6;
+  //  1001 listed knots and -6.6 us per configs[2] step)
+  const bool few = (size_t)L.NK * n * ng <= 768;
+  const int hod_cap = few ? kHodCapLevel : kNodeLevel;
   // chomp_set_tuning: the checker (every listed knot by literal evaluation) and the two
   // thresholds at which a knot leaves the fast path by itself
   const int all_literal = ctx->tune[CHOMP_TUNE_DEEP_LITERAL] > 0 ? 1 : 0;
@@ -1083,15 +1089,15 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
     const int rcp = ensure(ctx, &ctx->d_plan, &ctx->cap_plan, n * 3 * sizeof(DeepPlan));
     if (rcp) return rcp;
   }
-#define CHOMP_KNOTS(KNW)                                                                          \
-  hipLaunchKernelGGL((k_halo_knots<KNW>), dim3((unsigned)n, kb + (P.want_nbar ? 1u : 0u) + (unsigned)want_plan, (unsigned)ng), \
-                     dim3(KNW == 0 ? 64 : 256), shk, ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_tab,        \
-                     ctx->d_profile, ctx->d_hod, ctx->d_sici, ctx->d_nodes, ctx->d_endp,          \
-                     P.groups[0], P.groups[1], P.groups[2], P.kmask, P.want_nbar, ctx->d_pending, \
-                     ctx->d_npend, ctx->d_status, hod_cap, want_plan, max_rough, max_fine,           \
-                     reinterpret_cast<DeepPlan*>(ctx->d_plan))
-  if (wide) CHOMP_KNOTS(4); else if (lone) CHOMP_KNOTS(0); else CHOMP_KNOTS(1);
-#undef CHOMP_KNOTS
+  auto knots = [&](auto KNW) {
+    hipLaunchKernelGGL((k_halo_knots<KNW>), dim3((unsigned)n, kb + (P.want_nbar ? 1u : 0u) + (unsigned)want_plan, (unsigned)ng),
+                       dim3(KNW == 0 ? 64 : 256), shk, ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_tab,
+                       ctx->d_profile, ctx->d_hod, ctx->d_sici, ctx->d_nodes, ctx->d_endp,
+                       P.groups[0], P.groups[1], P.groups[2], P.kmask, P.want_nbar, ctx->d_pending,
+                       ctx->d_npend, ctx->d_status, hod_cap, want_plan, max_rough, max_fine,
+                       reinterpret_cast<DeepPlan*>(ctx->d_plan));
+  };
+  if (wide) knots(int_c<4>{}); else if (lone) knots(int_c<0>{}); else knots(int_c<1>{});
   // blocks 0..n-1 take the epochs' tokens; with integrands that can run beyond the node
   // tables (the HOD ones) enough further blocks to fill the chip draw from the list
   unsigned gd = (unsigned)n;
@@ -1101,93 +1107,59 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
     //  stages its tables to find nothing left)
     // (three of 256 threads -- the lean instance: 164 registers, 51 KB of LDS -- or one of 512)
     unsigned want = (unsigned)(L.NK * n * ng);
-    const unsigned resident = (size_t)L.NK * n * ng <= 768 ? 256u : (P.eval ? 512u : 768u);
+    const unsigned resident = few ? 256u : (P.eval ? 512u : 768u);
     if (want > resident) want = resident;
     if (want > gd) gd = want;
   }
   size_t shf = deep_fast_lds<kDeepCoarse>(L.NM, ctx->cfg.divmax);
   if (shf < (size_t)finalize_lds_doubles(L.NK) * sizeof(double))
     shf = (size_t)finalize_lds_doubles(L.NK) * sizeof(double);
-#define CHOMP_KNOTS_FAST(NT, SELF, EVAL, GRID, ROUND, LO, HI, FROM) \
-  CHOMP_KNOTS_FAST_L(NT, SELF, EVAL, false, GRID, ROUND, LO, HI, FROM)
-#define CHOMP_KNOTS_FAST_L(NT, SELF, EVAL, LIT, GRID, ROUND, LO, HI, FROM)                                         \
-  hipLaunchKernelGGL((k_halo_knots_fast<kDeepCoarse, NT, SELF, EVAL, LIT>), dim3(GRID), dim3(NT), shf, ctx->stream, \
-                     ctx->cfg, L, ctx->d_epochs, ctx->d_tab, ctx->d_sici, P.groups[0], P.groups[1], \
-                     P.groups[2], P.kmask, (int)n, ctx->d_pending, ctx->d_npend, ctx->d_epochs,     \
-                     P.fam, ctx->d_status, ctx->d_deepw, all_literal, deep_tol, max_rough, max_fine, \
-                     ctx->d_deepstat, ctx->d_samples, ctx->d_psum, parts, ROUND, LO, HI, FROM,      \
-                     reinterpret_cast<const DeepPlan*>(ctx->d_plan), ctx->d_profile, ctx->d_hod)
-#define CHOMP_KNOTS_SAMPLES(GRID, LO, HI)                                                        \
-  hipLaunchKernelGGL((k_halo_knots_samples<kDeepCoarse>), dim3(GRID), dim3(256), 0, ctx->stream,   \
-                     ctx->cfg, L, ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.kmask,      \
-                     (int)n, ctx->d_pending, ctx->d_nodes, ctx->d_endp, ctx->d_samples, ctx->d_psum, \
-                     parts, LO, HI)
-#define CHOMP_KNOTS_LITERAL(NT, GRID)                                                            \
-  hipLaunchKernelGGL((k_halo_knots_literal<NT>), dim3(GRID), dim3(NT), shl, ctx->stream, ctx->cfg,  \
-                     L, ctx->d_epochs, ctx->d_tab, ctx->d_profile, ctx->d_hod, ctx->d_sici,         \
-                     P.groups[0], P.groups[1], P.groups[2], P.kmask, (int)n, ctx->d_pending,        \
-                     ctx->d_npend, ctx->d_epochs, P.fam, ctx->d_status, ctx->d_deepstat)
-  if (shf > 64 * 1024) {            // (more than 64 KiB of dynamic LDS: opt in, once per context)
-    if (!ctx->lds_knots_set) {       // (per context: the attribute belongs to the current device)
-#define CHOMP_LDS_OPT_IN(NT, SELF, EVAL)                                                   \
-      HIPCHK(hipFuncSetAttribute(                                                          \
-          reinterpret_cast<const void*>(&k_halo_knots_fast<kDeepCoarse, NT, SELF, EVAL>), \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024))
-      CHOMP_LDS_OPT_IN(kDeepThreadsFew, false, false);
-      CHOMP_LDS_OPT_IN(kDeepThreads, false, false);
-      CHOMP_LDS_OPT_IN(kDeepThreads, false, true);
-      CHOMP_LDS_OPT_IN(kDeepThreadsFew, false, true);
-      CHOMP_LDS_OPT_IN(kDeepThreads, true, true);
-      HIPCHK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&k_halo_knots_fast<kDeepCoarse, kDeepThreads, false, true, true>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-#undef CHOMP_LDS_OPT_IN
-      ctx->lds_knots_set = true;
-    }
-  }
-  const bool few = (size_t)L.NK * n * ng <= 768;
   // (the sampling launch: a listed knot's 2^11 + 1 samples in `parts` work items -- the fewer
   //  knots there can be, the finer, so that a single epoch's handful still spreads over the chip)
   const int parts = few ? 8 : ((size_t)L.NK * n * ng <= 8192 ? 4 : 2);
+  const KnotsFast fast{ctx, P, shf, all_literal, deep_tol, max_rough, max_fine, parts};
+  constexpr int NT = kDeepThreads, NF = kDeepThreadsFew;
+  int rc = CHOMP_OK;
   if (!hod_groups) {                // (group 0 alone: listed knots are done in the same launch)
-    CHOMP_KNOTS_FAST(kDeepThreads, true, true, gd, 0, 0, 0x7fffffff, 0);
+    rc = fast.launch<NT, true, true>(gd, 0, 0, 0x7fffffff, 0);
   } else if (!deep_route) {         // (divmax within the node tables: nothing is ever listed)
-    if (few) CHOMP_KNOTS_FAST(kDeepThreadsFew, false, false, gd, 0, 0, 0, 0);
-    else CHOMP_KNOTS_FAST(kDeepThreads, false, false, gd, 0, 0, 0, 0);
+    rc = few ? fast.launch<NF, false, false>(gd, 0, 0, 0, 0) : fast.launch<NT, false, false>(gd, 0, 0, 0, 0);
   } else {
-    for (int r = 0; r < rounds; ++r) {
+    for (int r = 0; r < rounds && !rc; ++r) {
       const int lo = (int)((size_t)r * slots), hi = (int)((size_t)(r + 1) * slots);
       size_t gs = slots * (size_t)parts;
       if (gs > 1536) gs = 1536;
-      CHOMP_KNOTS_SAMPLES((unsigned)gs, lo, hi);
+      hipLaunchKernelGGL((k_halo_knots_samples<kDeepCoarse>), dim3((unsigned)gs), dim3(256), 0, ctx->stream,
+                         ctx->cfg, L, ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.kmask,
+                         (int)n, ctx->d_pending, ctx->d_nodes, ctx->d_endp, ctx->d_samples, ctx->d_psum,
+                         parts, lo, hi);
       const unsigned g = r == 0 ? gd : (gd < 512u ? gd : 512u);
       if (P.eval) {
-        if (few) CHOMP_KNOTS_FAST(kDeepThreadsFew, false, true, (g < 256u ? g : 256u), r, lo, hi, 0);
-        else CHOMP_KNOTS_FAST(kDeepThreads, false, true, (g < 512u ? g : 512u), r, lo, hi, 0);
+        rc = few ? fast.launch<NF, false, true>(g < 256u ? g : 256u, r, lo, hi, 0)
+                 : fast.launch<NT, false, true>(g < 512u ? g : 512u, r, lo, hi, 0);
       } else {
         // (the lean instance, and behind it ONE launch for what it hands on: the knots that
         //  need node evaluations -- few and long: 512 threads each -- and, in the last round,
         //  those that go to the literal evaluation)
         const bool last_round = r == rounds - 1;
         const unsigned ge = all_literal ? g : (g < 256u ? g : 256u);
-        if (few) CHOMP_KNOTS_FAST(kDeepThreadsFew, false, false, g, r, lo, hi, 0);
-        else CHOMP_KNOTS_FAST(kDeepThreads, false, false, g, r, lo, hi, 0);
-        if (last_round) CHOMP_KNOTS_FAST_L(kDeepThreads, false, true, true, ge, r, lo, hi, 1);
-        else CHOMP_KNOTS_FAST(kDeepThreads, false, true, ge, r, lo, hi, 1);
+        rc = few ? fast.launch<NF, false, false>(g, r, lo, hi, 0) : fast.launch<NT, false, false>(g, r, lo, hi, 0);
+        if (!rc)
+          rc = last_round ? fast.launch<NT, false, true, true>(ge, r, lo, hi, 1)
+                          : fast.launch<NT, false, true>(ge, r, lo, hi, 1);
       }
     }
   }
+  if (rc) return rc;
   // knots can only be handed on when some HOD Romberg may run beyond the node tables
   if (deep_route && P.eval) {       // (alpha != 1: no launch behind the fast sums that could take the list)
-    const size_t shl = deep_literal_lds(L.NM, L.NK);
     // (an empty list is the rule: few blocks, each returns after one read)
     const unsigned gl = all_literal ? gd : (gd < 256u ? gd : 256u);
-    CHOMP_KNOTS_LITERAL(kDeepThreads, gl);
+    hipLaunchKernelGGL((k_halo_knots_literal<NT>), dim3(gl), dim3(NT), deep_literal_lds(L.NM, L.NK),
+                       ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_tab, ctx->d_profile, ctx->d_hod,
+                       ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.kmask, (int)n, ctx->d_pending,
+                       ctx->d_npend, ctx->d_epochs, P.fam, ctx->d_status, ctx->d_deepstat);
   }
-#undef CHOMP_KNOTS_FAST
-#undef CHOMP_KNOTS_FAST_L
-#undef CHOMP_KNOTS_SAMPLES
-#undef CHOMP_KNOTS_LITERAL
   HIPCHK(hipGetLastError());
   ctx->have_halo = true;
   ctx->fam_mask |= P.fam;
@@ -1313,12 +1285,10 @@ static int prepare_extrapolation(chomp_ctx* ctx, int which, size_t epoch0, size_
   const int w = which & 15;
   if (!(which & CHOMP_P_EXTRAPOLATE) || (which & CHOMP_P_HALOFIT) || w == CHOMP_P_LIN)
     return CHOMP_OK;
-  if (ctx->with_bao)
-    hipLaunchKernelGGL(k_power_extrap<true>, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->cfg,
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_power_extrap<BAO>, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->cfg,
                        ctx->L, ctx->d_epochs, ctx->d_tab, w, (int)epoch0);
-  else
-    hipLaunchKernelGGL(k_power_extrap<false>, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->cfg,
-                       ctx->L, ctx->d_epochs, ctx->d_tab, w, (int)epoch0);
+  });
   HIPCHK(hipGetLastError());
   return CHOMP_OK;
 }
@@ -1353,14 +1323,11 @@ static int stage_e_prep(chomp_ctx* ctx, size_t epoch0, int w, const double* dk, 
   if (rc) return rc;
   rc = ensure(ctx, &ctx->d_ktab, &ctx->cap_ktab, (size_t)gx8 * 1024);
   if (rc) return rc;
-  if (ctx->with_bao)
-    hipLaunchKernelGGL(k_power_prep<true>, dim3(gx8), dim3(256), 0, ctx->stream, ctx->cfg, L,
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_power_prep<BAO>, dim3(gx8), dim3(256), 0, ctx->stream, ctx->cfg, L,
                        ctx->d_epochs, (int)epoch0, w, dk, nk, ctx->d_ktab, ctx->d_winfo,
                        ctx->d_slow, *parity);
-  else
-    hipLaunchKernelGGL(k_power_prep<false>, dim3(gx8), dim3(256), 0, ctx->stream, ctx->cfg, L,
-                       ctx->d_epochs, (int)epoch0, w, dk, nk, ctx->d_ktab, ctx->d_winfo,
-                       ctx->d_slow, *parity);
+  });
   HIPCHK(hipGetLastError());
   return CHOMP_OK;
 }
@@ -1463,22 +1430,12 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
       }
       if (timed) HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
       const unsigned gx8 = (gx + 7) / 8 * 8;
-      int per = n % 2 == 0 ? 2 : 1;
-      // (chomp_set_tuning: rows per block of the streaming kernel; 2 measured best on MI355X)
-      {
-        const long long v = ctx->tune[CHOMP_TUNE_E_ROWS];
-        if ((v == 1 || v == 2 || v == 4) && n % (size_t)v == 0) per = (int)v;
-      }
-      const unsigned gy = (unsigned)(n / per);
-#define CHOMP_STREAM(P)                                                                   \
-      hipLaunchKernelGGL(k_power_stream<P>, dim3(gx8, gy), dim3(256), 0, ctx->stream, L,  \
-                         ctx->d_tab, w, (int)epoch0, ctx->d_ktab, ctx->d_winfo, nk, dout)
-      switch (per) {
-        case 1: CHOMP_STREAM(1); break;
-        case 4: CHOMP_STREAM(4); break;
-        default: CHOMP_STREAM(2); break;
-      }
-#undef CHOMP_STREAM
+      // (two rows per block of the streaming kernel where the rows pair up: measured best on MI355X)
+      with_flag(n % 2 == 0, [&](auto PAIRS) {
+        constexpr int PER = PAIRS ? 2 : 1;
+        hipLaunchKernelGGL(k_power_stream<PER>, dim3(gx8, (unsigned)(n / PER)), dim3(256), 0, ctx->stream,
+                           L, ctx->d_tab, w, (int)epoch0, ctx->d_ktab, ctx->d_winfo, nk, dout);
+      });
       if (timed) {
         HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
         ctx->timing_valid = true;
@@ -1489,39 +1446,30 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
       if (gy > n) gy = (unsigned)n;
       const int epy = (int)((n + gy - 1) / gy);
       gy = (unsigned)((n + epy - 1) / epy);
-      if (ctx->with_bao)
-        hipLaunchKernelGGL(k_power_grid<true>, dim3(gx, gy), dim3(256), 0, ctx->stream, ctx->cfg, L,
+      with_flag(ctx->with_bao, [&](auto BAO) {
+        hipLaunchKernelGGL(k_power_grid<BAO>, dim3(gx, gy), dim3(256), 0, ctx->stream, ctx->cfg, L,
                            ctx->d_epochs, ctx->d_tab, w, (int)epoch0, (int)n, epy, 1, dk, nk,
                            dout, ctx->d_slow, parity, 1, extrap);
-      else
-        hipLaunchKernelGGL(k_power_grid<false>, dim3(gx, gy), dim3(256), 0, ctx->stream, ctx->cfg, L,
-                           ctx->d_epochs, ctx->d_tab, w, (int)epoch0, (int)n, epy, 1, dk, nk,
-                           dout, ctx->d_slow, parity, 1, extrap);
+      });
       streaming = false;
     }
     // per-lane pass over the listed k groups (streaming shape only; a planned grid knows
     // whether it has any)
-    if (streaming && lanes_needed) {
-      if (ctx->with_bao)
-        hipLaunchKernelGGL(k_power_grid_lanes<true>, dim3(1024), dim3(256), 0, ctx->stream, ctx->cfg,
+    if (streaming && lanes_needed)
+      with_flag(ctx->with_bao, [&](auto BAO) {
+        hipLaunchKernelGGL(k_power_grid_lanes<BAO>, dim3(1024), dim3(256), 0, ctx->stream, ctx->cfg,
                            L, ctx->d_epochs, ctx->d_tab, w, extrap, (int)epoch0, (int)n, dk, nk, dout,
                            ctx->d_slow, parity);
-      else
-        hipLaunchKernelGGL(k_power_grid_lanes<false>, dim3(1024), dim3(256), 0, ctx->stream, ctx->cfg,
-                           L, ctx->d_epochs, ctx->d_tab, w, extrap, (int)epoch0, (int)n, dk, nk, dout,
-                           ctx->d_slow, parity);
-    }
+      });
     if (ctx->timing_valid) HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   } else {
     unsigned gx = (unsigned)((nk + 255) / 256);
     if (gx > 2048) gx = 2048;
     const size_t sh = (size_t)(12 * (L.NK - 1)) * sizeof(double);
-    if (ctx->with_bao)
-      hipLaunchKernelGGL(k_power<true>, dim3(gx, (unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+    with_flag(ctx->with_bao, [&](auto BAO) {
+      hipLaunchKernelGGL(k_power<BAO>, dim3(gx, (unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
                          L, ctx->d_epochs, ctx->d_tab, which, (int)epoch0, dk, nk, dout);
-    else
-      hipLaunchKernelGGL(k_power<false>, dim3(gx, (unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
-                         L, ctx->d_epochs, ctx->d_tab, which, (int)epoch0, dk, nk, dout);
+    });
   }
   HIPCHK(hipGetLastError());
   if (mem == CHOMP_HOST) {
@@ -1548,12 +1496,10 @@ int chomp_sigma_r(chomp_ctx* ctx, size_t epoch, const double* scale, size_t n, d
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(ctx->d_stage_in, scale, n * sizeof(double), hipMemcpyHostToDevice,
                         ctx->stream));
-  if (ctx->with_bao)
-    hipLaunchKernelGGL(k_sigma_r<true>, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg,
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_sigma_r<BAO>, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg,
                        ctx->d_epochs, (int)epoch, ctx->d_stage_in, ctx->d_snodes, ctx->d_stage_out);
-  else
-    hipLaunchKernelGGL(k_sigma_r<false>, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg,
-                       ctx->d_epochs, (int)epoch, ctx->d_stage_in, ctx->d_snodes, ctx->d_stage_out);
+  });
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost,
                         ctx->stream));

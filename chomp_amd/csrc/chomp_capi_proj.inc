@@ -32,12 +32,10 @@ static int stage_out(chomp_ctx* ctx, double* out, size_t n, int mem, const Stage
 static int halofit_launch(chomp_ctx* ctx, size_t dst, size_t src, double f_1, double f_2,
                           double f_3, double omega_l, double w) {
   const TabLayout& L = ctx->L;
-  if (ctx->with_bao)
-    hipLaunchKernelGGL(k_halofit_sigma<true>, dim3(L.NK), dim3(256), 0, ctx->stream, ctx->cfg, L,
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_halofit_sigma<BAO>, dim3(L.NK), dim3(256), 0, ctx->stream, ctx->cfg, L,
                        ctx->d_epochs, (int)src, ctx->d_tab);
-  else
-    hipLaunchKernelGGL(k_halofit_sigma<false>, dim3(L.NK), dim3(256), 0, ctx->stream, ctx->cfg, L,
-                       ctx->d_epochs, (int)src, ctx->d_tab);
+  });
   hipLaunchKernelGGL(k_halofit_finalize, dim3(1), dim3(64),
                      (size_t)(25 * L.NK + 64) * sizeof(double), ctx->stream, L, ctx->d_epochs,
                      (int)dst, (int)src, ctx->d_tab, f_1, f_2, f_3, omega_l, w, ctx->d_hf_ainv);
@@ -403,78 +401,54 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
   if (rc) return rc;
   const ProjLayout& L = ctx->proj.L;
   const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
-#define CHOMP_WTHETA(KERNEL, THREADS)                                                         \
-  hipLaunchKernelGGL(KERNEL, dim3((unsigned)n), dim3(THREADS), sh, ctx->stream, ctx->cfg,     \
-                     ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd, \
-                     ctx->proj.d_tab, k_min, k_max, D_z, s.in, s.out)
-  // fp64 path: the theta-independent factor of the integrand on the Romberg nodes first
   const int LT = ctx->cfg.divmax < kWthetaTabLevel ? ctx->cfg.divmax : kWthetaTabLevel;
   const size_t n_nodes = ((size_t)1 << LT) + 1;
-#define CHOMP_WTHETA_TAB(HF, BAO)                                                             \
-  do {                                                                                        \
-    hipLaunchKernelGGL((k_wtheta_nodes<HF, BAO>),                                             \
-                       dim3((unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread))), \
-                       dim3(256), (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double),            \
-                       ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab,  \
-                       which, k_min, k_max, D_z, LT, ctx->d_wnodes);                          \
-    hipLaunchKernelGGL((k_wtheta<HF, BAO>), dim3((unsigned)n), dim3(64 * kWthetaNW), sh,      \
-                       ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,           \
-                       ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, D_z, \
-                       s.in, s.out, ctx->d_wnodes, LT);                                       \
-  } while (0)
-  switch (ctx->precision) {
-    case CHOMP_PREC_F32_EVAL: CHOMP_WTHETA(k_wtheta_mixed<CHOMP_PREC_F32_EVAL>, 256); break;
-    case CHOMP_PREC_F32_TABLES: CHOMP_WTHETA(k_wtheta_mixed<CHOMP_PREC_F32_TABLES>, 256); break;
-    case CHOMP_PREC_F32_ALL: CHOMP_WTHETA(k_wtheta_mixed<CHOMP_PREC_F32_ALL>, 256); break;
-    default: {
-      // The moment route (k_wtheta_moments + k_wtheta_fast): every level within the node table,
-      // segments about as wide as (never narrower than) a piece of the kernel spline.
-      const double dxK = (ctx->proj.host.ln_kt_max - ctx->proj.host.ln_kt_min) / (double)(L.NKT - 1);
-      int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
-      nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
-      const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
-                        ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
-      // node table, then (fast route) the moment records and the segments' totals
-      const size_t n_rec = 4 * wth_rec_count(LT), n_tot = 4 * (size_t)(LT + 1) * (size_t)nseg;
-      rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes,
-                  n_nodes + 1 + (fast ? n_rec + n_tot + 2 : 0));
-      if (rc) return rc;
-      if (fast) {
-        double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // 16-byte aligned records
-        double* segtot = rec + n_rec;
-        const dim3 gn((unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread)));
-        const size_t shn = (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double);
-#define CHOMP_WNODES(HF, BAO)                                                                  \
-        hipLaunchKernelGGL((k_wtheta_nodes<HF, BAO>), gn, dim3(256), shn, ctx->stream, ctx->cfg, \
-                           ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, k_min, k_max,  \
-                           D_z, LT, ctx->d_wnodes)
-        if (which & CHOMP_P_HALOFIT) {
-          if (ctx->with_bao) CHOMP_WNODES(true, true); else CHOMP_WNODES(true, false);
-        } else {
-          if (ctx->with_bao) CHOMP_WNODES(false, true); else CHOMP_WNODES(false, false);
-        }
-#undef CHOMP_WNODES
-        hipLaunchKernelGGL(k_wtheta_moments, dim3((unsigned)nseg, (unsigned)LT, kWthParts), dim3(256), 0,
-                           ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min), std::log(k_max),
-                           rec, segtot);
-        hipLaunchKernelGGL(k_wtheta_fast, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg,
-                           L, ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, s.in, s.out,
-                           ctx->d_wnodes, rec, segtot, LT, nseg);
-        break;
-      }
-      if (which & CHOMP_P_HALOFIT) {
-        if (ctx->with_bao) CHOMP_WTHETA_TAB(true, true);
-        else CHOMP_WTHETA_TAB(true, false);
-      } else if (ctx->with_bao) {
-        CHOMP_WTHETA_TAB(false, true);
-      } else {
-        CHOMP_WTHETA_TAB(false, false);
-      }
-      break;
+  if (ctx->precision != CHOMP_PREC_F64) {
+    auto mixed = [&](auto PREC) {
+      hipLaunchKernelGGL(k_wtheta_mixed<PREC>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+                         ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd,
+                         ctx->proj.d_tab, k_min, k_max, D_z, s.in, s.out);
+    };
+    switch (ctx->precision) {
+      case CHOMP_PREC_F32_EVAL: mixed(int_c<CHOMP_PREC_F32_EVAL>{}); break;
+      case CHOMP_PREC_F32_TABLES: mixed(int_c<CHOMP_PREC_F32_TABLES>{}); break;
+      default: mixed(int_c<CHOMP_PREC_F32_ALL>{}); break;
     }
+    return stage_out(ctx, out, n, mem, s);
   }
-#undef CHOMP_WTHETA_TAB
-#undef CHOMP_WTHETA
+  // fp64: the theta-independent factor of the integrand on the Romberg nodes first, then the
+  // moment route (k_wtheta_moments + k_wtheta_fast: every level within the node table, segments
+  // about as wide as -- never narrower than -- a piece of the kernel spline) or k_wtheta
+  const double dxK = (ctx->proj.host.ln_kt_max - ctx->proj.host.ln_kt_min) / (double)(L.NKT - 1);
+  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
+  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
+  const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
+                    ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
+  // node table, then (fast route) the moment records and the segments' totals
+  const size_t n_rec = 4 * wth_rec_count(LT), n_tot = 4 * (size_t)(LT + 1) * (size_t)nseg;
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, n_nodes + 1 + (fast ? n_rec + n_tot + 2 : 0));
+  if (rc) return rc;
+  double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // 16-byte aligned records
+  double* segtot = rec + n_rec;
+  with_flag(which & CHOMP_P_HALOFIT, ctx->with_bao, [&](auto HF, auto BAO) {
+    hipLaunchKernelGGL((k_wtheta_nodes<HF, BAO>),
+                       dim3((unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread))),
+                       dim3(256), (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                       ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, k_min, k_max, D_z, LT,
+                       ctx->d_wnodes);
+    if (fast) {
+      hipLaunchKernelGGL(k_wtheta_moments, dim3((unsigned)nseg, (unsigned)LT, kWthParts), dim3(256), 0,
+                         ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min), std::log(k_max), rec,
+                         segtot);
+      hipLaunchKernelGGL(k_wtheta_fast, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg, L,
+                         ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, s.in, s.out, ctx->d_wnodes, rec,
+                         segtot, LT, nseg);
+    } else {
+      hipLaunchKernelGGL((k_wtheta<HF, BAO>), dim3((unsigned)n), dim3(64 * kWthetaNW), sh, ctx->stream,
+                         ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd,
+                         ctx->proj.d_tab, k_min, k_max, D_z, s.in, s.out, ctx->d_wnodes, LT);
+    }
+  });
   return stage_out(ctx, out, n, mem, s);
 }
 
@@ -491,14 +465,11 @@ int chomp_xi3d(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_m
   rc = stage_in(ctx, r, n, out, mem, &s);
   if (rc) return rc;
   const size_t sh = (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double);
-  if (ctx->with_bao)
-    hipLaunchKernelGGL(k_xi3d<true>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_xi3d<BAO>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
                        ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->d_j0, k_min,
                        k_max, s.in, s.out);
-  else
-    hipLaunchKernelGGL(k_xi3d<false>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
-                       ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->d_j0, k_min,
-                       k_max, s.in, s.out);
+  });
   return stage_out(ctx, out, n, mem, s);
 }
 
@@ -545,14 +516,17 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   int rc = check_power(ctx, which, epoch, 1);
   if (rc) return rc;
   if (!(D_z > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "cell: D_z");
+  const ProjLayout& L = ctx->proj.L;
+  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
+  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);   // (k_cell_deep)
+  constexpr int kDeepLds = 160 * 1024 - 4096;
+  if (shd > kDeepLds) return fail(ctx, CHOMP_ERR_ARG, "cell: halo_npoints too large for k_cell_deep");
   HIPCHK(hipSetDevice(ctx->device));
   rc = prepare_extrapolation(ctx, which, epoch, 1);
   if (rc) return rc;
   Staged s;
   rc = stage_in(ctx, ell, n, out, mem, &s);
   if (rc) return rc;
-  const ProjLayout& L = ctx->proj.L;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
   // the chi-only factors of the integrand on the Romberg nodes first
   const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
   const size_t n_nodes = ((size_t)1 << LT) + 1;
@@ -571,49 +545,35 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   // levels beyond kCellSplitLevel by k_cell_deep (CHOMP_TUNE_CELL_ONE_KERNEL: all in k_cell)
   const int split = (ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL] > 0 || ctx->cfg.divmax <= kCellSplitLevel)
                         ? ctx->cfg.divmax : kCellSplitLevel;
-  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);
   const unsigned gdeep = (unsigned)(n < 512 ? n : 512);
-#define CHOMP_CELL(HF, BAO)                                                                     \
-  do {                                                                                          \
-    if (pk_tab)                                                                                 \
-      hipLaunchKernelGGL((k_cell_ptab<HF, BAO>), dim3((kPTabN + 256) / 256), dim3(256),         \
-                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg, \
-                         ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, pk_tab);         \
-    if (split <= LT && split >= 6 && n >= 16)   /* (four multipoles to a block) */            \
-      hipLaunchKernelGGL((k_cell4<HF, BAO>), dim3((unsigned)((n + 3) / 4)), dim3(256), sh,      \
-                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,           \
-                         ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, (int)n, \
-                         s.out, ctx->d_cnodes, LT, pk_tab, split, deep, state);                 \
-    else if (split <= LT)   /* (no level beyond the node table in k_cell: the lean instance) */ \
-      hipLaunchKernelGGL((k_cell<HF, BAO, false>), dim3((unsigned)n), dim3(256), sh, ctx->stream, \
-                         ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which,     \
-                         ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out, ctx->d_cnodes, LT,  \
-                         pk_tab, split, deep, state);                                           \
-    else                                                                                        \
-      hipLaunchKernelGGL((k_cell<HF, BAO, true>), dim3((unsigned)n), dim3(256), sh, ctx->stream, \
-                         ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which,     \
-                         ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out, ctx->d_cnodes, LT,  \
-                         pk_tab, split, deep, state);                                           \
-    if (split < ctx->cfg.divmax) {                                                              \
-      const unsigned lds_bit = 1u << (2 * (HF ? 1 : 0) + (BAO ? 1 : 0));                        \
-      if (!(ctx->lds_cell_mask & lds_bit)) { /* (> 64 KiB of dynamic LDS: opt in, per context) */ \
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cell_deep<HF, BAO>),        \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096)); \
-        ctx->lds_cell_mask |= lds_bit;                                                          \
-      }                                                                                         \
-      hipLaunchKernelGGL((k_cell_deep<HF, BAO>), dim3(gdeep), dim3(kCellDeepThreads), shd,      \
-                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,           \
-                         ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out,  \
-                         ctx->d_cnodes, LT, pk_tab, split, deep, state);                        \
-    }                                                                                           \
-  } while (0)
-  if (shd > 160 * 1024 - 4096) return fail(ctx, CHOMP_ERR_ARG, "cell: halo_npoints too large for k_cell_deep");
-  if (which & CHOMP_P_HALOFIT) {
-    if (ctx->with_bao) CHOMP_CELL(true, true); else CHOMP_CELL(true, false);
-  } else {
-    if (ctx->with_bao) CHOMP_CELL(false, true); else CHOMP_CELL(false, false);
-  }
-#undef CHOMP_CELL
+  rc = with_flag(which & CHOMP_P_HALOFIT, ctx->with_bao, [&](auto HF, auto BAO) {
+    if (pk_tab)
+      hipLaunchKernelGGL((k_cell_ptab<HF, BAO>), dim3((kPTabN + 256) / 256), dim3(256),
+                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                         ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, pk_tab);
+    if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
+      hipLaunchKernelGGL((k_cell4<HF, BAO>), dim3((unsigned)((n + 3) / 4)), dim3(256), sh,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,
+                         ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, (int)n,
+                         s.out, ctx->d_cnodes, LT, pk_tab, split, deep, state);
+    } else {   // (no level beyond the node table in k_cell: the lean instance)
+      with_flag(split > LT, [&](auto BEYOND) {
+        hipLaunchKernelGGL((k_cell<HF, BAO, BEYOND>), dim3((unsigned)n), dim3(256), sh, ctx->stream,
+                           ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which,
+                           ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out, ctx->d_cnodes, LT,
+                           pk_tab, split, deep, state);
+      });
+    }
+    if (split >= ctx->cfg.divmax) return CHOMP_OK;
+    const int rcl = lds_opt_in(ctx, &k_cell_deep<HF, BAO>, kDeepLds);
+    if (rcl) return rcl;
+    hipLaunchKernelGGL((k_cell_deep<HF, BAO>), dim3(gdeep), dim3(kCellDeepThreads), shd,
+                       ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,
+                       ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out,
+                       ctx->d_cnodes, LT, pk_tab, split, deep, state);
+    return CHOMP_OK;
+  });
+  if (rc) return rc;
   return stage_out(ctx, out, n, mem, s);
 }
 
@@ -685,14 +645,11 @@ int chomp_covariance_table(chomp_ctx* ctx, int which, size_t epoch, double D_z, 
   P.cov_ready = false;
   if (!P.d_cov) HIPCHK(hipMalloc(&P.d_cov, (size_t)C.total * sizeof(double)));
   const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
-  if (ctx->with_bao)
-    hipLaunchKernelGGL(k_cov_proj_knots<true>, dim3((unsigned)C.N), dim3(256), sh, ctx->stream,
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_cov_proj_knots<BAO>, dim3((unsigned)C.N), dim3(256), sh, ctx->stream,
                        ctx->cfg, ctx->L, L, C, ctx->d_epochs, (int)epoch, ctx->d_tab, which,
                        P.d_pd, P.d_tab, D_z, P.d_cov);
-  else
-    hipLaunchKernelGGL(k_cov_proj_knots<false>, dim3((unsigned)C.N), dim3(256), sh, ctx->stream,
-                       ctx->cfg, ctx->L, L, C, ctx->d_epochs, (int)epoch, ctx->d_tab, which,
-                       P.d_pd, P.d_tab, D_z, P.d_cov);
+  });
   hipLaunchKernelGGL(k_cov_spline, dim3(1), dim3(64), 0, ctx->stream, C, P.d_cov);
   HIPCHK(hipGetLastError());
   P.cov_ready = true;

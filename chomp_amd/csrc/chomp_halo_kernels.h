@@ -461,7 +461,6 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
   const bool first = blockIdx.y == 0 && blockIdx.z == 0;
   __shared__ unsigned scratch_status;
   __shared__ int scratch_npend;
-  MSTAMP(0);
   copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
                kEpochDoubles);
   if (do_nodes)
@@ -473,14 +472,12 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
   const int n_search = (int)(search[(e * 2 + 0) * 2 + 1] + search[(e * 2 + 1) * 2 + 1]);
   mass_setup_block(cfg, L, E, epochs, e, first, search[(e * 2 + 0) * 2], search[(e * 2 + 1) * 2],
                    n_search, tab + (size_t)e * L.stride, mass_par[e], mf_kind, tinker, gl16, M);
-  MSTAMP(5);
   if (!do_nodes) return;
   if (threadIdx.x < 64)
     halo_epoch_begin(E, profile[e], hod[e], M.c_nu, M.x_lnm[0], L.NM,
                      first ? &status[e] : &scratch_status, first ? &npend[e] : &scratch_npend,
                      pending, first && e == 0);
   __syncthreads();
-  MSTAMP(6);
   if (first)
     copy_doubles(reinterpret_cast<double*>(&epochs[e]), reinterpret_cast<const double*>(&E),
                  kEpochDoubles);
@@ -490,7 +487,6 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
                    nodes + ((size_t)e * 3 + group) * kNodeStride,
                    endp + ((size_t)e * 3 + group) * 2 * L.NK, (mask & kMaskDeepNodes) != 0,
                    (int)blockIdx.z, (int)gridDim.z);
-  MSTAMP(7);
 }
 
 // Halo.calculate_bias / calculate_m_eff / calculate_f_sat (halo.py:709-838): grid (3, n),
@@ -1154,7 +1150,7 @@ __device__ __forceinline__ void deep_plan_block(const Epoch& E, const double* nu
 // the break-point plan of its (epoch, group) for k_halo_knots_fast (DeepPlan).
 // The epochs are the FASTEST grid axis: blocks are dispatched in linear order, a (k, z) grid's
 // launch is 900 blocks for 512-768 resident ones, and with the epochs slowest the last epochs'
-// deepest knots entered the chip 11-15 us into the launch (tools/dev_knots_stamps2.py).
+// deepest knots entered the chip 11-15 us into the launch (per-block time stamps).
 // KNW = 1 (a batch of a few dozen epochs): four knots to a block up to level 7, then the
 // block's knots that go on are walked by all four wavefronts together (below), capped at three
 // wavefronts per SIMD (168 registers, 4 spills: every block of a 64-epoch launch but the last
@@ -1180,7 +1176,6 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
   const int NK = L.NK;
   const int e = blockIdx.x, n_epoch = (int)gridDim.x;
   const int kb = KNW == 1 ? (NK + 3) / 4 : NK;     // knot blocks
-  KNSTAMP(0, __builtin_amdgcn_s_memrealtime());
   // Blocks are dispatched x (the epochs) fastest, z slowest: the long units of EVERY epoch first
   // -- the n_bar integrals, the highest k (the deepest Romberg), the HOD groups (plan slots 1, 2)
   // before the smooth one -- so that the launch ends with the knots that stop at level 6.
@@ -1218,7 +1213,6 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
   // KNW = 1 with the cooperative tail (below): wavefront w of block bx takes knot bx + kb w --
   // the knots that run deep are the highest k, and this way a block holds one of them at most
   const int ik = KNW == 1 ? (kCoop ? bx + kb * (int)(threadIdx.x >> 6) : bx * 4 + (int)(threadIdx.x >> 6)) : bx;
-  KNSTAMP(1, __builtin_amdgcn_s_memrealtime());
   const bool have = ik < NK;
   if (!kCoop && !have) return;     // (no barrier below unless kCoop: the wavefronts are independent)
   const double* node = nodes + ((size_t)e * 3 + group) * kNodeStride;
@@ -1330,8 +1324,6 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
     (void)fb;
     r = romberg_group<KNW, 2>(f, a, b, cfg.global_precision, cfg.halo_precision, dmax, sm);
   }
-  KNSTAMP(2, __builtin_amdgcn_s_memrealtime());
-  KNSTAMP(3, (r.level[0] > r.level[1] ? r.level[0] : r.level[1]) + 100 * ik);
   if ((KNW <= 1 ? (threadIdx.x & 63) : threadIdx.x) == 0) {
     double* lev = t + L.off_levels;
     const int fa = group_fa(group), fb_ = group_fb(group);
@@ -1506,32 +1498,6 @@ inline size_t deep_literal_lds(int NM, int NK) {
   return d * sizeof(double);
 }
 
-// Development stamps (tools/dev_knot_stamps.py builds with -DCHOMP_STAMPS; absent from the
-// product build): s_memtime at the phase boundaries of the first knot each block draws.
-#ifdef CHOMP_STAMPS
-constexpr int kStampBlocks = 2048, kStampSlots = 24;
-__device__ long long g_ks[kStampBlocks * kStampSlots];
-#define KSTAMP(k)                                                                     \
-  do {                                                                                \
-    if (first_item && threadIdx.x == 0 && blockIdx.x < kStampBlocks && !from_eval)    \
-      g_ks[blockIdx.x * kStampSlots + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
-  } while (0)
-#define KSTAMP_VALUE(k, v)                                                            \
-  do {                                                                                \
-    if (first_item && threadIdx.x == 0 && blockIdx.x < kStampBlocks && !from_eval)    \
-      g_ks[blockIdx.x * kStampSlots + (k)] = (long long)(v);                          \
-  } while (0)
-#define KSTAMP_BLOCK(k, v)                                                            \
-  do {                                                                                \
-    if (threadIdx.x == 0 && blockIdx.x < kStampBlocks && !from_eval)                  \
-      g_ks[blockIdx.x * kStampSlots + (k)] = (long long)(v);                          \
-  } while (0)
-#else
-#define KSTAMP_BLOCK(k, v) do { } while (0)
-#define KSTAMP(k) do { } while (0)
-#define KSTAMP_VALUE(k, v) do { } while (0)
-#endif
-
 // One more arrival at epoch e (its token, or one of its listed knots done) by a whole block:
 // whoever brings npend[e] to zero finalises the epoch.  fences: knots were written by other
 // blocks of this or the previous launch's kernels since the counter was armed.
@@ -1634,7 +1600,6 @@ __device__ __forceinline__ void deep_fast_body(
   const int NK = L.NK;
   const int tid = threadIdx.x;
   const int wv = tid >> 6, ln = tid & 63;
-  KSTAMP_BLOCK(18, __builtin_amdgcn_s_memtime());
   const int count_front = pending[0], count = count_front + pending[2];
   // (with an empty list no block of this launch writes a knot: every value the finalisation
   //  reads comes from the previous launch, and no fence is needed)
@@ -1670,10 +1635,6 @@ __device__ __forceinline__ void deep_fast_body(
     copy_doubles(reinterpret_cast<double*>(&S), reinterpret_cast<const double*>(sici_g),
                  (int)(sizeof(SiCiTab) / sizeof(double)));
   stage_weights();
-#ifdef CHOMP_STAMPS
-  bool first_item = true;
-  int n_items = 0;
-#endif
   // (drawing the next knot while the current one is worked on -- the atomic's round trip off the
   //  chain -- was measured and is worse: the blocks that start first, on the deepest knots, then
   //  also hold the first of the knots left over, 100 against 88 us per configs[2] launch; and a
@@ -1683,9 +1644,6 @@ __device__ __forceinline__ void deep_fast_body(
   //  is the dispatch order of the blocks anyway; the knots beyond the grid are drawn)
   bool own_first = !from_eval;
   for (;;) {
-#ifdef CHOMP_STAMPS
-    first_item = (n_items++ == 0);
-#endif
     __syncthreads();               // (previous item done with E, sm)
     if (tid == 0) {
       if (from_eval) {
@@ -1700,10 +1658,6 @@ __device__ __forceinline__ void deep_fast_body(
     own_first = false;
     __syncthreads();
     if (item_sh >= item_hi) {      // block-uniform
-      KSTAMP_BLOCK(19, __builtin_amdgcn_s_memtime());
-#ifdef CHOMP_STAMPS
-      KSTAMP_BLOCK(20, n_items - 1);
-#endif
       return;
     }
     const int item_raw = item_sh < count_front
@@ -1758,7 +1712,6 @@ __device__ __forceinline__ void deep_fast_body(
       if (tid == 0) lit_items[atomicAdd(&pending[4], 1)] = item;
       continue;
     }
-    KSTAMP(0);
     // (the sampling launch's level sums, its chunks in order: on their way while the samples are copied)
     double lsum_pre = 0.0;
     if (tid < 2 * (LC + 1) && tid % (LC + 1) >= 1) {
@@ -1792,8 +1745,6 @@ __device__ __forceinline__ void deep_fast_body(
       for (int i = tid; i < kDeepF; i += NT) dst[i] = src[i];              // F0 and F1
     }
     __syncthreads();
-    KSTAMP(1);
-    KSTAMP(2);
     if (PL.flag != 0) {              // block-uniform: too many break points / intervals
       if (tid == 0) {
         lit_items[atomicAdd(&pending[4], 1)] = item;
@@ -1824,7 +1775,6 @@ __device__ __forceinline__ void deep_fast_body(
                            0.5 * (F0[0] + F0[deep_pos(NC)]), 0.5 * (F1[0] + F1[deep_pos(NC)]),
                            lsum, lsum + LC + 1, pa, pb);
       }
-      KSTAMP(3);
       const int nf_all = PL.n_fine, ns = PL.n_seg;
       if (!R.all_done()) {
         // ---- a break-point interval between two smooth segments: on either side of the
@@ -1892,7 +1842,6 @@ __device__ __forceinline__ void deep_fast_body(
           seg_sum[f][sgi] = v;
         }
         // (visible to the rounds below: the self-check's exchanges carry barriers)
-        KSTAMP(4);
         // ---- self-check: the same machinery one level up.  Every odd sample is predicted
         // from the even ones (stencils of twice the spacing, shifted at segment ends
         // exactly as below) and compared with its true value; at the spacing actually
@@ -1948,8 +1897,6 @@ __device__ __forceinline__ void deep_fast_body(
         if (tid == 0) ev_items[atomicAdd(&pending[kPendingEvCount + round], 1)] = item_sh;
         continue;
       }
-      KSTAMP(5);
-      KSTAMP_VALUE(22, nf_all);
       {
         // ---- deeper levels, kDeepRound at a time (their sums are independent; what a level
         // costs here is latency -- a handful of node-by-node evaluations and two reductions --
@@ -2007,7 +1954,6 @@ __device__ __forceinline__ void deep_fast_body(
                 if (gg == g) { s0[gg] += v0; s1[gg] += v1; }
             }
           }
-          if (lv0 == LC + 1) KSTAMP(10);
           // the break-point intervals: level lv0 + g has n0 << g nodes in each
           const int n0 = 1 << (lv0 - 1 - LC);
           const int per0 = nf * n0;                            // nodes of the round's first level
@@ -2041,7 +1987,6 @@ __device__ __forceinline__ void deep_fast_body(
             for (int gg = 0; gg < kDeepRound; ++gg)
               if (gg == g) { s0[gg] += o[0]; s1[gg] += o[1]; }
           }
-          if (lv0 == LC + 1) KSTAMP(11);
           // one exchange for the 2 ng sums
           {
             double* slot = red + (flip ? 2 * kDeepRound * NWV : 0);
@@ -2066,7 +2011,6 @@ __device__ __forceinline__ void deep_fast_body(
             }
             flip ^= 1;
           }
-          if (lv0 == LC + 1) KSTAMP(12);
           if constexpr (!EVAL) {
             // (read behind the exchange's barrier: block-uniform; cannot happen while the
             //  pre-check above sends every knot with such an interval on, kept as the guard)
@@ -2076,7 +2020,6 @@ __device__ __forceinline__ void deep_fast_body(
 #pragma unroll
           for (int g = 0; g < kDeepRound; ++g)
             if (g < ng && !R.all_done()) R.advance(lv0 + g, s0[g], s1[g]);
-          KSTAMP(5 + (lv0 - LC - 1) / kDeepRound + 1);
         }
       }
       if (to_eval) {               // (!EVAL only) still counted in npend[e]
@@ -2087,8 +2030,6 @@ __device__ __forceinline__ void deep_fast_body(
         continue;
       }
     }
-    KSTAMP(16);
-    KSTAMP_VALUE(23, R.level[0] > R.level[1] ? R.level[0] : R.level[1]);
     if (tid == 0) {
       if (pa) { knot_store(&t[L.off_knot[fa] + ik], R.value[0]); knot_store(&levs[fa * NK + ik], (double)R.level[0]); }
       if (pb) { knot_store(&t[L.off_knot[fb] + ik], R.value[1]); knot_store(&levs[fb * NK + ik], (double)R.level[1]); }
@@ -2100,7 +2041,6 @@ __device__ __forceinline__ void deep_fast_body(
     }
     deep_arrive(cfg, L, epochs_rw, tab, e, fam_mask, status, npend, fences, &last_sh, sm,
                 kArriveThrough);
-    KSTAMP(17);
     if (!w_safe) { __syncthreads(); stage_weights(); }
   }   // next item
 }

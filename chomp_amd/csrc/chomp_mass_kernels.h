@@ -21,6 +21,8 @@
 // No MFMA: there is no dense contraction anywhere on this path.
 #pragma once
 
+#include <type_traits>
+
 #include <hip/hip_runtime.h>
 
 #include "../../include/chomp_mi355x.h"
@@ -118,51 +120,6 @@ constexpr unsigned kStNonfinite = CHOMP_ST_NONFINITE;
 constexpr unsigned kStHaloBits = (31u * CHOMP_ST_HALO_DIVMAX_H_M) | CHOMP_ST_NONFINITE;
 
 // Cooperative copy of POD blocks as doubles.
-// Development stamps (-DCHOMP_STAMPS, absent from the product build): s_memtime at the phase
-// boundaries of every block of k_mass_nodes (tools/dev_mass_stamps.py; block (x, 0, z) < (64, 1, 8))
-// or, with -DCHOMP_STAMPS=2, of k_halo_knots<1> (block (x, y, 0) < (64, 14, 1)).
-#ifdef CHOMP_STAMPS
-constexpr int kMStampSlots = 16;
-static __device__ long long g_ms[64 * 16 * kMStampSlots];
-#endif
-#if defined(CHOMP_STAMPS) && CHOMP_STAMPS == 3   /* k_nu_table<., 1>, block (x, y) < (64, 50) */
-#define NUSTAMP(k, v)                                                                          \
-  do {                                                                                         \
-    if (threadIdx.x == 0 && blockIdx.x < 64 && blockIdx.y < 50)                                \
-      g_ms[(blockIdx.x * 50 + blockIdx.y) * 4 + (k)] = (long long)(v);                         \
-  } while (0)
-#else
-#define NUSTAMP(k, v) do { } while (0)
-#endif
-#if defined(CHOMP_STAMPS) && CHOMP_STAMPS == 4   /* k_epoch_probe<., 0>, block (x, y) < (64, 8) */
-#define PSTAMP(k)                                                                              \
-  do {                                                                                         \
-    if (threadIdx.x == 0 && blockIdx.x < 64 && blockIdx.y < 8)                                 \
-      g_ms[(blockIdx.x * 8 + blockIdx.y) * 8 + (k)] = (long long)__builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define PSTAMP(k) do { } while (0)
-#endif
-#if defined(CHOMP_STAMPS) && CHOMP_STAMPS == 1
-#define MSTAMP(k)                                                                              \
-  do {                                                                                         \
-    if (threadIdx.x == 0 && blockIdx.x < 64 && blockIdx.y == 0 && blockIdx.z < 8)              \
-      g_ms[(blockIdx.x * 8 + blockIdx.z) * kMStampSlots + (k)] =                               \
-          (long long)__builtin_amdgcn_s_memtime();                                             \
-  } while (0)
-#else
-#define MSTAMP(k) do { } while (0)
-#endif
-#if defined(CHOMP_STAMPS) && CHOMP_STAMPS == 2
-#define KNSTAMP(k, v)                                                                          \
-  do {                                                                                         \
-    if ((threadIdx.x & 63) == 0 && blockIdx.y < 14 && blockIdx.x < 64 && blockIdx.z == 0)      \
-      g_ms[((blockIdx.x * 14 + blockIdx.y) * 4 + (threadIdx.x >> 6)) * 4 + (k)] = (long long)(v); \
-  } while (0)
-#else
-#define KNSTAMP(k, v) do { } while (0)
-#endif
-
 __device__ __forceinline__ void copy_doubles(double* dst, const double* src, int n) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
@@ -1012,6 +969,20 @@ __device__ __forceinline__ SidePlan plan_side(const Epoch& E, const double* lns,
   return P;
 }
 
+// Host side of the launches: a run-time flag as a template argument.  f is called with
+// std::true_type or std::false_type, which convert to bool in a constant expression
+// (k<flag>); two flags give f both, for the HF x BAO instances.
+template <class F>
+decltype(auto) with_flag(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>
+decltype(auto) with_flag(bool a, bool b, F&& f) {
+  return with_flag(a, [&](auto A) { return with_flag(b, [&](auto B) { return f(A, B); }); });
+}
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
 // k_epoch_probe (chomp_probe_kernel.h) is compiled in its own translation unit, chomp_probe.hip
 // -- WITH LLVM's machine LICM, which every other kernel of the library is faster without
 // (chomp_amd/_lib.py: HIPCC_FLAGS): 38.5 against 41.8 us per C2 launch.  This is its launcher.
@@ -1064,7 +1035,7 @@ __global__ __launch_bounds__(64 * NW) void k_nu_table(chomp_config cfg, TabLayou
     // MIDDLE of the table.  Blocks go to the SIMDs round-robin (1024 of them: a SIMD gets linear
     // blocks b, b + 1024, b + 2048, ...), a 64-epoch launch is 3200 wavefronts, so the SIMDs of
     // the first two rows get a fourth one from the last two; the SIMDs run at their VALU issue
-    // rate from the first microsecond to the last (tools/dev_nu_stamps3.py), so the launch lasts
+    // rate from the first microsecond to the last (per-block time stamps), so the launch lasts
     // as long as the most loaded of them -- and the largest masses (Romberg level 12) are the
     // longest integrals, the middle ones (level 10-11 on the node table) the shortest.
     const int NM = (int)gridDim.y, y = (int)blockIdx.y, m0 = NM / 2 - 1;
@@ -1073,26 +1044,15 @@ __global__ __launch_bounds__(64 * NW) void k_nu_table(chomp_config cfg, TabLayou
     else if (y >= NM - 2) i = m0 + 2 + (y - (NM - 2));
     else { i = NM - 1 - (y - 2); if (i <= m0 + 3) i -= 4; }
   }
-  NUSTAMP(0, __builtin_amdgcn_s_memrealtime());
   copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
                kEpochDoubles);
   __syncthreads();
-  NUSTAMP(1, __builtin_amdgcn_s_memrealtime());
   const double* snode = snodes + (size_t)E.cosmo_slot * kSigmaStride;
   const double ln_lo = search[(e * 2 + 0) * 2], ln_hi = search[(e * 2 + 1) * 2];
   const double lnm = linspace_at(ln_lo, ln_hi, L.NM, i);
   bool conv = true;
-#if defined(CHOMP_STAMPS) && CHOMP_STAMPS == 3
-  int lev_dbg = 0;
-  const double nu = nu_of_mass_block<NW, 1, BAO>(E, snode, exp(lnm), cfg, cfg.cosmo_precision,
-                                                 red, &conv, nullptr, &lev_dbg);
-  NUSTAMP(1, lev_dbg);
-#else
   const double nu = nu_of_mass_block<NW, 1, BAO>(E, snode, exp(lnm), cfg, cfg.cosmo_precision,
                                                  red, &conv);
-#endif
-  NUSTAMP(2, __builtin_amdgcn_s_memrealtime());
-  NUSTAMP(3, (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32));   // HW_ID, XCC_ID
   if (threadIdx.x == 0) {
     double* t = tab + (size_t)e * L.stride;
     t[L.off_ln_mass + i] = lnm;
@@ -1168,18 +1128,16 @@ __device__ __forceinline__ void mass_setup_block(
   copy_doubles(M.y_nu, t + L.off_nu, NM);
   copy_doubles(M.gl, gl16, 32);
   __syncthreads();
-  MSTAMP(1);
   {   // nu(ln M) on threads 0..127, ln M(nu) on threads 128..255, in lockstep
     const int sys = threadIdx.x >> 7, tid = threadIdx.x & 127;
     spline_build_pcr(sys == 0 ? M.x_lnm : M.y_nu, sys == 0 ? M.y_nu : M.x_lnm, NM,
                      sys == 0 ? M.c_nu : M.c_lnm, M.work + sys * 9 * NM, tid, 128, true);
   }
-  MSTAMP(2);
   if (threadIdx.x < 64) {
     // (one wavefront: the five Tinker parameters -- a look-up in the 9-row table from global
     //  memory and a power of 1 + z each, mass_function.py:547-564 -- in five lanes at once, m_star
     //  in a sixth: done one after the other by thread 0 they were 6.7 us of every block's chain
-    //  on a Tinker set-up (tools/dev_mass_stamps.py).  Same calls on the same arguments.)
+    //  on a Tinker set-up (per-block time stamps).  Same calls on the same arguments.)
     const int lane = (int)threadIdx.x;
     const double mf_delta_v = (hp.delta_v == -1.0) ? E.delta_v : hp.delta_v;
     double mine = 0.0;
@@ -1221,7 +1179,6 @@ __device__ __forceinline__ void mass_setup_block(
     }
   }
   __syncthreads();
-  MSTAMP(3);
   // Normalisations (mass_function.py:225-241; Tinker: bias only, :532-545).  The
   // reference integrates in linear nu with Romberg to rtol 1.48e-8 (8193 nodes);
   // the integrand is analytic, so 8 x 16 Gauss-Legendre nodes in ln nu give the
@@ -1272,7 +1229,6 @@ __device__ __forceinline__ void mass_setup_block(
     }
     __syncthreads();
   }
-  MSTAMP(4);
   if (!publish) return;
   copy_doubles(reinterpret_cast<double*>(&epochs[e]), reinterpret_cast<const double*>(&E),
                kEpochDoubles);

@@ -43,7 +43,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
   const int side = role / kProbes, p = role % kProbes;
   const bool fixed = cfg.mass_min > 0.0 && cfg.mass_max > 0.0;     // mass_function.py:163-170
   if (fixed && !chi_role) return;
-  PSTAMP(0);
   copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
                kEpochDoubles);
   __syncthreads();
@@ -56,7 +55,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
   }
   __syncthreads();
   double* pr = probe + (size_t)e * kProbeStride;
-  PSTAMP(1);
   if (chi_role) {                  // comoving distance, cosmology.py:106-110
     EIntegrand f{E.om0, E.ol0, E.or0, E.H0};
     const double chi = romberg1<NW>(f, 0.0, E.z, cfg.global_precision,
@@ -82,9 +80,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
   }
   if constexpr (PHASE != 2) {
     // ---- this block's probe: candidate j - 2 + p of its side
-    PSTAMP(2);
     const SidePlan plan = plan_side(E, lns, side, cand, &sh_j);
-    PSTAMP(3);
     const SideThresholds T = side_thresholds(side, cand);
     double nu_mine = NAN;
     if (plan.ok && plan.dir != 0) {
@@ -112,7 +108,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
       }
     }
   }
-  PSTAMP(4);
   if constexpr (PHASE != 1) {
   if constexpr (PHASE == 0) {
     if (threadIdx.x == 0) {
@@ -120,7 +115,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
       last = atomicAdd(&count[e], 1) == 2 * kProbes - 1 ? 1 : 0;
     }
     __syncthreads();
-    PSTAMP(5);
     if (!last) return;
     // (no fence on this side: everything the last block reads of the others -- the probe record
     //  -- is read with agent-scope loads, issued behind the arrival count's return)
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
   // The epoch's probe record -- written by the other seven blocks -- is fetched by 24 lanes at
   // once, one agent-scope load each, and the logic reads the copy in LDS: read where they are
   // used, the ~20 loads were a chain of dependent round trips, 9 of the launch's 38 us
-  // (tools/dev_probe_stamps4.py: arrival at 25 us, end at 34.5).
+  // (per-block time stamps: arrival at 25 us, end at 34.5).
   __shared__ double rec[kProbeStride];
   if (threadIdx.x < kProbeStride)
     rec[threadIdx.x] = __hip_atomic_load(pr + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -237,7 +231,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
   __syncthreads();
   copy_doubles(reinterpret_cast<double*>(&epochs[e]), reinterpret_cast<const double*>(&E),
                kEpochDoubles);
-  PSTAMP(6);
   }  // (PHASE != 1)
 }
 

@@ -309,9 +309,9 @@ int chomp_status_post(chomp_ctx* ctx);
 int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
 
 /* Test / tuning hooks (no counterpart in the reference; not needed by a caller): override a
- * launch-shape decision of this context.  value < 0 restores the default.
+ * launch-shape decision of this context.  value < 0 restores the default.  Numbers 1 and 9
+ * belonged to retired knobs and are refused (CHOMP_ERR_ARG) like any unknown one.
  *   CHOMP_TUNE_E_STREAM_MIN  samples from which chomp_power takes the streaming launch shape
- *   CHOMP_TUNE_E_ROWS        rows per block of the streaming kernel (1, 2 or 4)
  *   CHOMP_TUNE_DEEP_LITERAL  1: knots beyond the node tables by literal evaluation of every
  *                            Romberg node (the checker of the fast deep-level sums)
  *   CHOMP_TUNE_DEEP_TOL      self-check threshold of the fast deep-level sums, in units of 1e-15
@@ -325,10 +325,6 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
  *                            the margin above a singular satellite onset, segments shorter
  *                            than a stencil) and still take the fast sums (default and
  *                            maximum 64)
- *   CHOMP_TUNE_HOD_CAP       Romberg level (6..10; default 9 for a set-up of one or a few
- *                            epochs, 10 for a batch) up to which a knot of the HOD integrands
- *                            walks the node table before it is listed for the fast deep-level
- *                            sums (10: the whole table, as for the smooth pair)
  *   CHOMP_TUNE_DEEP_SLOTS    slots of the sample buffer of the listed knots (default: one per
  *                            knot that can be listed, up to 1 GiB): with fewer slots than
  *                            listed knots the sampling and summing launches work the list off
@@ -343,7 +339,6 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
  *                            the kernels they queued).  The marker library is looked up with
  *                            dlopen; CHOMP_ERR_STATE if none is installed. */
 #define CHOMP_TUNE_E_STREAM_MIN 0
-#define CHOMP_TUNE_E_ROWS 1
 #define CHOMP_TUNE_DEEP_LITERAL 2
 #define CHOMP_TUNE_ROCTX 3
 #define CHOMP_TUNE_WTHETA_DIRECT 4
@@ -351,7 +346,6 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
 #define CHOMP_TUNE_DEEP_TOL 6
 #define CHOMP_TUNE_DEEP_MAX_BREAKS 7
 #define CHOMP_TUNE_DEEP_MAX_FINE 8
-#define CHOMP_TUNE_HOD_CAP 9
 #define CHOMP_TUNE_DEEP_SLOTS 10
 #define CHOMP_TUNE_COUNT 11
 int chomp_set_tuning(chomp_ctx* ctx, int what, long long value);

@@ -766,9 +766,14 @@ def test_power_plan_reuses_the_k_table(torch_mod):
 
 def test_roctx_ranges_switch_on_and_off():
     """CHOMP_TUNE_ROCTX: the stage ranges (roctxRangePush / Pop through a dlopen'ed marker
-    library) can be switched on and off around a step without changing a result."""
+    library) can be switched on and off around a step without changing a result.  A number that
+    names no knob (the two retired ones, CHOMP_TUNE_COUNT) is refused: CHOMP_ERR_ARG, which the
+    binding raises as ValueError."""
     from chomp_amd import grid, _lib
     hg = grid.HaloGrid(numpy.array([0.0, 0.7]))
+    for what in (1, 9, _lib.TUNE_COUNT):
+        with pytest.raises(ValueError, match="unknown knob"):
+            hg.ctx.set_tuning(what, 1)
     k = numpy.logspace(-2, 1, 16)
     ref = hg.power("power_mm", k)
     hg.ctx.set_tuning(_lib.TUNE_ROCTX, 1)
