@@ -19,9 +19,12 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_SCOPE = 0, -1, -2, -3, -4
 HOST, DEVICE = 0, 1
 MF_ST, MF_TINKER = 0, 1
 T_H_M, T_PP_MM, T_H_G, T_PP_GM, T_PP_GG = 1, 2, 4, 8, 16
+T_I_1_2 = 32
 T_EXCLUSION = 64
 FAM_MM, FAM_GM, FAM_GG = T_H_M | T_PP_MM, T_H_M | T_H_G | T_PP_GM, T_H_G | T_PP_GG
+FAM_SSC = FAM_MM | T_I_1_2
 P_LIN, P_MM, P_GM, P_GG, P_HALOFIT, P_EXTRAPOLATE = 0, 1, 2, 3, 16, 32
+P_SSC_RESPONSE, P_MM_SSC = 4, 5
 PREC_F64, PREC_F32_EVAL, PREC_F32_TABLES, PREC_F32_ALL = 0, 1, 2, 3
 DNDZ_MAGLIM, DNDZ_GAUSSIAN, DNDZ_BOXCAR, DNDZ_PPOLY = 0, 1, 2, 3
 WINDOW_GALAXY, WINDOW_CONVERGENCE, WINDOW_FLAT_CONVERGENCE, WINDOW_CONVERGENCE_DELTA = 0, 1, 2, 3
@@ -34,7 +37,7 @@ SC = {name: i for i, name in enumerate([
     "growth_norm", "delta_H", "hf_k_s", "hf_n_eff", "hf_C"])}
 SC_COUNT = 30
 TAB = {"ln_mass": 0, "nu": 1, "h_m": 2, "pp_mm": 3, "h_g": 4, "pp_gm": 5,
-       "pp_gg": 6, "levels": 7, "hf_ln_sigma2": 8}
+       "pp_gg": 6, "levels": 7, "hf_ln_sigma2": 8, "i_1_2": 9, "levels_i_1_2": 10}
 EV = {"nu_of_mass": 0, "ln_mass_of_nu": 1, "f_nu": 2, "bias_nu": 3,
       "hod_first": 4, "hod_second": 5, "hod_central": 6, "hod_satellite": 7,
       "virial_radius": 8, "concentration": 9, "delta_k": 10}
@@ -105,12 +108,13 @@ EXPORTS = [
     "chomp_set_timing", "chomp_get_timing", "chomp_get_status", "chomp_status_post",
     "chomp_status_wait", "chomp_set_tuning",
     "chomp_get_deep_stats", "chomp_stage_k", "chomp_power_plan", "chomp_get_stream",
-    "chomp_wtheta_cell", "chomp_stage_k_halofit",
+    "chomp_wtheta_cell", "chomp_stage_k_halofit", "chomp_set_delta_b", "chomp_put_table",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
 ST_MASS_MIN_SATURATED, ST_MASS_MAX_SATURATED, ST_MASS_SEARCH_EXHAUSTED, ST_SIGMA_DIVMAX = 1, 2, 4, 8
-ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000}
+ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000,
+                  "i_1_2": 0x2000}
 ST_NONFINITE = 0x10000
 ST_SATURATED = ST_MASS_MIN_SATURATED | ST_MASS_MAX_SATURATED
 TUNE_E_STREAM_MIN, TUNE_DEEP_LITERAL, TUNE_ROCTX, TUNE_WTHETA_DIRECT = 0, 2, 3, 4
@@ -322,6 +326,8 @@ def lib():
         L.chomp_y_nfw.argtypes = [vp, sz, c_double_p, c_double_p, sz, c_double_p]
         L.chomp_get_scalars.argtypes = [vp, sz, c_double_p]
         L.chomp_get_table.argtypes = [vp, sz, i, c_double_p, sz]
+        L.chomp_put_table.argtypes = [vp, sz, i, c_double_p, sz]
+        L.chomp_set_delta_b.argtypes = [vp, sz, sz, vp, i]
         L.chomp_eval.argtypes = [vp, sz, i, vp, sz, vp, i]
         L.chomp_halofit_get.argtypes = [vp, sz, c_double_p]
         L.chomp_halofit_put.argtypes = [vp, sz, c_double_p]
@@ -642,6 +648,28 @@ class Context(object):
         self._check(self._L.chomp_get_table(self._h, epoch, TAB[name],
                                             out.ctypes.data_as(c_double_p), n))
         return out
+
+    def put_table(self, name, values, epoch=0):
+        """Install the knots of one knot table ("h_m" .. "pp_gg", "i_1_2") and rebuild its
+        spline (chomp_put_table): get -> put leaves every spectrum bit for bit as it was."""
+        v = numpy.ascontiguousarray(values, dtype=numpy.float64).ravel()
+        self._check(self._L.chomp_put_table(self._h, epoch, TAB[name],
+                                            v.ctypes.data_as(c_double_p), v.size))
+
+    def set_delta_b(self, delta_b, epoch0=0):
+        """HaloSuperSampleCovariance._delta_b of epochs [epoch0, epoch0 + len) (chomp_set_delta_b);
+        numpy array / sequence (host) or torch cuda tensor (device, async on the stream)."""
+        if _is_torch(delta_b):
+            import torch
+            assert delta_b.is_cuda and delta_b.dtype == torch.float64 and delta_b.is_contiguous()
+            pair = self._torch_enter()
+            self._check(self._L.chomp_set_delta_b(self._h, epoch0, delta_b.numel(),
+                                                  ctypes.c_void_p(delta_b.data_ptr()), DEVICE))
+            self._torch_leave(pair)
+            return
+        v = numpy.ascontiguousarray(numpy.atleast_1d(delta_b), dtype=numpy.float64).ravel()
+        self._check(self._L.chomp_set_delta_b(self._h, epoch0, v.size,
+                                              ctypes.c_void_p(v.ctypes.data), HOST))
 
     def eval(self, what, x, epoch=0):
         """Element-wise lookup; x numpy (any shape) or torch cuda tensor."""

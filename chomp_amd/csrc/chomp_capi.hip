@@ -106,7 +106,15 @@ struct chomp_ctx {
   int* d_npend = nullptr;          // per epoch: listed knots + 1 token (k_halo_knots_fast)
   long long tune[CHOMP_TUNE_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // chomp_set_tuning
   bool have_epochs = false, have_mass = false, have_halo = false;
-  unsigned fam_mask = 0;          // families (F_* bits) with valid splines
+  unsigned fam_mask = 0;          // families (F_* bits) with valid splines in every epoch (set-ups)
+  std::vector<unsigned> put_mask;  // per epoch: families installed by chomp_put_table since epochs_set
+  // HaloSuperSampleCovariance._delta_b per epoch (chomp_set_delta_b), read by CHOMP_P_MM_SSC.
+  // chomp_epochs_set only raises delta_b_zero: the buffer is cleared when something next needs
+  // it, so that a batch that never asks for the super-sample codes queues nothing for them.
+  double* d_delta_b = nullptr;
+  size_t cap_delta_b = 0;
+  StagedBlock sh_delta_b;
+  bool delta_b_zero = true;
   std::vector<char> have_halofit;
   StagedBlock sh_cosmo, sh_z, sh_mass, sh_profile, sh_hod, sh_slot, sh_first;
   StagedBlock sh_proj, sh_pp[2];   // projection scalars, tabulated redshift distributions
@@ -475,14 +483,17 @@ int alloc_epochs(chomp_ctx* ctx, size_t n) {
   HIPCHK(hipMemsetAsync(ctx->d_count, 0, n * sizeof(int), ctx->stream));
   HIPCHK(hipMalloc(&ctx->d_pending, pending_ints(n, ctx->L.NK) * sizeof(int)));
   HIPCHK(hipMemsetAsync(ctx->d_pending, 0, kPendingHead * sizeof(int), ctx->stream));
-  HIPCHK(hipMalloc(&ctx->d_endp, n * 3 * 2 * (size_t)ctx->L.NK * sizeof(double)));
+  HIPCHK(hipMalloc(&ctx->d_endp, n * kGroups * 2 * (size_t)ctx->L.NK * sizeof(double)));
   HIPCHK(hipMalloc(&ctx->d_npend, n * sizeof(int)));
   HIPCHK(hipMemsetAsync(ctx->d_npend, 0, n * sizeof(int), ctx->stream));
   HIPCHK(hipMalloc(&ctx->d_tab, n * (size_t)ctx->L.stride * sizeof(double)));
+  // (rows of the levels table and knot tables no set-up has written read back as 0, not as
+  //  whatever the allocation held: the same for every context)
+  HIPCHK(hipMemsetAsync(ctx->d_tab, 0, n * (size_t)ctx->L.stride * sizeof(double), ctx->stream));
   HIPCHK(hipMalloc(&ctx->d_mass_par, n * sizeof(chomp_halo_par)));
   HIPCHK(hipMalloc(&ctx->d_profile, n * sizeof(chomp_halo_par)));
   HIPCHK(hipMalloc(&ctx->d_hod, n * sizeof(HodDev)));
-  HIPCHK(hipMalloc(&ctx->d_nodes, n * 3 * (size_t)kNodeStride * sizeof(double)));
+  HIPCHK(hipMalloc(&ctx->d_nodes, n * kGroups * (size_t)kNodeStride * sizeof(double)));
   HIPCHK(hipMalloc(&ctx->d_snodes, n * (size_t)kSigmaStride * sizeof(double)));
   // (holds the arrival counters of k_sigma_nodes: zero once, the kernel resets them)
   HIPCHK(hipMemsetAsync(ctx->d_snodes, 0, n * (size_t)kSigmaStride * sizeof(double), ctx->stream));
@@ -565,13 +576,13 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_cand, ctx->d_cosmo, ctx->d_z, ctx->d_epochs, ctx->d_search, ctx->d_probe, ctx->d_count, ctx->d_pending,
                   ctx->d_tab, ctx->d_mass_par, ctx->d_profile, ctx->d_hod, ctx->d_nodes, ctx->d_snodes, ctx->d_slot, ctx->d_first, ctx->d_status, ctx->d_endp, ctx->d_npend,
                   ctx->d_stage_in, ctx->d_stage_in2, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
-                  ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv};
+                  ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
   for (void* p : ctx->host_graveyard) (void)hipHostFree(p);
   for (StagedBlock* b : {&ctx->sh_cosmo, &ctx->sh_z, &ctx->sh_mass, &ctx->sh_profile, &ctx->sh_hod,
-                         &ctx->sh_slot, &ctx->sh_first, &ctx->sh_proj, &ctx->sh_pp[0],
+                         &ctx->sh_slot, &ctx->sh_first, &ctx->sh_delta_b, &ctx->sh_proj, &ctx->sh_pp[0],
                          &ctx->sh_pp[1]})
     b->release();
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
@@ -842,6 +853,8 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   { const int rch = ensure_hstatus(ctx); if (rch) return rch; }
   ctx->have_mass = ctx->have_halo = false;
   ctx->fam_mask = 0;
+  ctx->put_mask.assign(n_epoch, 0u);
+  ctx->delta_b_zero = true;
   ctx->have_halofit.assign(n_epoch, 0);
   rc = upload(ctx, ctx->d_cosmo, cosmo, n_epoch * sizeof(chomp_cosmo), ctx->sh_cosmo);
   if (rc) return rc;
@@ -925,10 +938,14 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
 // families need.
 struct HaloPlan {
   unsigned fam = 0, kmask = 0;
-  int groups[3] = {-1, -1, -1};
+  int groups[4] = {-1, -1, -1, -1};
   int ng = 0;
   int want_nbar = 1;
   bool eval = false;     // some epoch's HOD has alpha != 1: the deep-level sums evaluate nodes
+  bool has_hod() const {
+    return group_hod(groups[0]) || group_hod(groups[1]) || group_hod(groups[2]) ||
+           group_hod(groups[3]);
+  }
 };
 static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const chomp_hod_par* hod,
                         unsigned tables, HaloPlan* P) {
@@ -957,14 +974,15 @@ static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const cho
   rcu = upload(ctx, ctx->d_hod, hd.data(), n * sizeof(HodDev), ctx->sh_hod);
   if (rcu) return rcu;
   // header bits CHOMP_T_* are (1 << F_*) by construction
-  P->fam = tables & 31u;
+  P->fam = tables & ((1u << kFamilies) - 1u);
   P->kmask = P->fam | ((tables & CHOMP_T_EXCLUSION) ? kMaskExclusion : 0u);
   P->ng = 0;
   if (P->fam & ((1u << F_HM) | (1u << F_PPMM))) P->groups[P->ng++] = 0;
   if (P->fam & ((1u << F_HG) | (1u << F_PPGM))) P->groups[P->ng++] = 1;
   if (P->fam & (1u << F_PPGG)) P->groups[P->ng++] = 2;
+  if (P->fam & (1u << F_I12)) P->groups[P->ng++] = 3;
   // integrands that can run beyond the node tables (the HOD ones): one level more in the tables
-  if ((P->groups[0] > 0 || P->groups[1] > 0 || P->groups[2] > 0) && ctx->cfg.divmax > kNodeLevel)
+  if (P->has_hod() && ctx->cfg.divmax > kNodeLevel)
     P->kmask |= kMaskDeepNodes;
   return CHOMP_OK;
 }
@@ -998,7 +1016,7 @@ static int launch_nu_mass(chomp_ctx* ctx, int mf_kind, const HaloPlan* plan) {
                      ctx->d_tinker, ctx->d_gl16, plan ? 1 : 0, ctx->d_profile, ctx->d_hod,
                      ctx->d_sici, ctx->d_nodes, ctx->d_endp, plan ? plan->groups[0] : -1,
                      plan ? plan->groups[1] : -1, plan ? plan->groups[2] : -1,
-                     plan ? plan->kmask : 0u, ctx->d_status, ctx->d_npend, ctx->d_pending);
+                     plan ? plan->groups[3] : -1, plan ? plan->kmask : 0u, ctx->d_status, ctx->d_npend, ctx->d_pending);
   HIPCHK(hipGetLastError());
   return CHOMP_OK;
 }
@@ -1021,7 +1039,7 @@ extern "C++" struct KnotsFast {
     }
     hipLaunchKernelGGL((k_halo_knots_fast<kDeepCoarse, NT, SELF, EVAL, LIT>), dim3(grid), dim3(NT), lds,
                        ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, ctx->d_tab, ctx->d_sici, P.groups[0],
-                       P.groups[1], P.groups[2], P.kmask, (int)ctx->n_epoch, ctx->d_pending, ctx->d_npend,
+                       P.groups[1], P.groups[2], P.groups[3], P.kmask, (int)ctx->n_epoch, ctx->d_pending, ctx->d_npend,
                        ctx->d_epochs, P.fam, ctx->d_status, ctx->d_deepw, all_literal, deep_tol, max_rough,
                        max_fine, ctx->d_deepstat, ctx->d_samples, ctx->d_psum, parts, round, lo, hi,
                        from_eval, reinterpret_cast<const DeepPlan*>(ctx->d_plan), ctx->d_profile, ctx->d_hod);
@@ -1048,7 +1066,7 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
   // listed knot gets a slot of the sample buffer (k_halo_knots_samples fills it, k_halo_knots_fast
   // sums the knot's levels from it).  The buffer holds every knot that CAN be listed while that
   // stays under the budget; beyond it the two kernels work the list off in rounds of `slots`.
-  const bool hod_groups = P.groups[0] > 0 || P.groups[1] > 0 || P.groups[2] > 0;
+  const bool hod_groups = P.has_hod();
   const bool deep_route = hod_groups && ctx->cfg.divmax > kNodeLevel;
   size_t slots = 0;
   int rounds = 1;
@@ -1086,14 +1104,14 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
   // (the break-point plans of the (epoch, group)s: an extra block row of k_halo_knots)
   const int want_plan = deep_route ? 1 : 0;
   if (want_plan) {
-    const int rcp = ensure(ctx, &ctx->d_plan, &ctx->cap_plan, n * 3 * sizeof(DeepPlan));
+    const int rcp = ensure(ctx, &ctx->d_plan, &ctx->cap_plan, n * kGroups * sizeof(DeepPlan));
     if (rcp) return rcp;
   }
   auto knots = [&](auto KNW) {
     hipLaunchKernelGGL((k_halo_knots<KNW>), dim3((unsigned)n, kb + (P.want_nbar ? 1u : 0u) + (unsigned)want_plan, (unsigned)ng),
                        dim3(KNW == 0 ? 64 : 256), shk, ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_tab,
                        ctx->d_profile, ctx->d_hod, ctx->d_sici, ctx->d_nodes, ctx->d_endp,
-                       P.groups[0], P.groups[1], P.groups[2], P.kmask, P.want_nbar, ctx->d_pending,
+                       P.groups[0], P.groups[1], P.groups[2], P.groups[3], P.kmask, P.want_nbar, ctx->d_pending,
                        ctx->d_npend, ctx->d_status, hod_cap, want_plan, max_rough, max_fine,
                        reinterpret_cast<DeepPlan*>(ctx->d_plan));
   };
@@ -1130,7 +1148,7 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
       size_t gs = slots * (size_t)parts;
       if (gs > 1536) gs = 1536;
       hipLaunchKernelGGL((k_halo_knots_samples<kDeepCoarse>), dim3((unsigned)gs), dim3(256), 0, ctx->stream,
-                         ctx->cfg, L, ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.kmask,
+                         ctx->cfg, L, ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.groups[3], P.kmask,
                          (int)n, ctx->d_pending, ctx->d_nodes, ctx->d_endp, ctx->d_samples, ctx->d_psum,
                          parts, lo, hi);
       const unsigned g = r == 0 ? gd : (gd < 512u ? gd : 512u);
@@ -1157,7 +1175,7 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
     const unsigned gl = all_literal ? gd : (gd < 256u ? gd : 256u);
     hipLaunchKernelGGL((k_halo_knots_literal<NT>), dim3(gl), dim3(NT), deep_literal_lds(L.NM, L.NK),
                        ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_tab, ctx->d_profile, ctx->d_hod,
-                       ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.kmask, (int)n, ctx->d_pending,
+                       ctx->d_sici, P.groups[0], P.groups[1], P.groups[2], P.groups[3], P.kmask, (int)n, ctx->d_pending,
                        ctx->d_npend, ctx->d_epochs, P.fam, ctx->d_status, ctx->d_deepstat);
   }
   HIPCHK(hipGetLastError());
@@ -1203,7 +1221,7 @@ int chomp_halo_setup(chomp_ctx* ctx, const chomp_halo_par* profile,
   hipLaunchKernelGGL(k_halo_nodes, dim3((unsigned)n, ngy, nchunks), dim3(256), sh,
                      ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_tab, ctx->d_profile,
                      ctx->d_hod, ctx->d_sici, ctx->d_nodes, ctx->d_endp, P.groups[0], P.groups[1],
-                     P.groups[2], P.kmask, ctx->d_status, ctx->d_npend, ctx->d_pending);
+                     P.groups[2], P.groups[3], P.kmask, ctx->d_status, ctx->d_npend, ctx->d_pending);
   return launch_halo_knots(ctx, P);
 }
 
@@ -1234,6 +1252,7 @@ int chomp_set_transfer(chomp_ctx* ctx, int kind) {
     ctx->with_bao = kind == CHOMP_TRANSFER_EH_BAO;
     ctx->have_epochs = ctx->have_mass = ctx->have_halo = false;   // every table depends on T(k)
     ctx->fam_mask = 0;
+    ctx->put_mask.assign(ctx->put_mask.size(), 0u);
   }
   return CHOMP_OK;
 }
@@ -1257,21 +1276,32 @@ int chomp_hod_stats(chomp_ctx* ctx, size_t epoch0, size_t n, double* out) {
   return CHOMP_OK;
 }
 
-static int check_power(chomp_ctx* ctx, int which, size_t epoch0, size_t n) {
+// ssc: the caller serves the super-sample codes (chomp_power / chomp_power_range; the projections
+// take the spectra of Halo / HaloFit only).
+static int check_power(chomp_ctx* ctx, int which, size_t epoch0, size_t n, bool ssc = false) {
   if (!ctx) return CHOMP_ERR_ARG;
   if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "power before epochs_set");
   if (epoch0 + n > ctx->n_epoch || n == 0) return fail(ctx, CHOMP_ERR_ARG, "power: epoch range");
   const int w = which & 15;
   const bool hf = (which & CHOMP_P_HALOFIT) != 0;
-  if (w < CHOMP_P_LIN || w > CHOMP_P_GG) return fail(ctx, CHOMP_ERR_ARG, "power: unknown spectrum");
+  const bool w_ssc = w == CHOMP_P_SSC_RESPONSE || w == CHOMP_P_MM_SSC;
+  if (w < CHOMP_P_LIN || w > (ssc ? CHOMP_P_MM_SSC : CHOMP_P_GG)) return fail(ctx, CHOMP_ERR_ARG, "power: unknown spectrum");
   if (hf && w == CHOMP_P_LIN) return fail(ctx, CHOMP_ERR_ARG, "power: halofit|lin");
+  // HaloSuperSampleCovariance is a Halo that never extrapolates (halo.py:1102-1108) and no HaloFit
+  if (w_ssc && (which & (CHOMP_P_HALOFIT | CHOMP_P_EXTRAPOLATE)))
+    return fail(ctx, CHOMP_ERR_ARG, "power: the super-sample spectra take no HALOFIT / EXTRAPOLATE");
   unsigned need = 0;
+  if (w_ssc) need = (1u << F_HM) | (1u << F_PPMM) | (1u << F_I12);
   if (w == CHOMP_P_MM && !hf) need = (1u << F_HM) | (1u << F_PPMM);
   if (w == CHOMP_P_GM) need = (1u << F_HM) | (1u << F_HG) | (1u << F_PPGM);
   if (w == CHOMP_P_GG) need = (1u << F_HG) | (1u << F_PPGG);
+  // (a set-up builds a family for every epoch; chomp_put_table for the one epoch it is given)
   if ((ctx->fam_mask & need) != need)
-    return fail(ctx, CHOMP_ERR_STATE, "power: knot tables of this spectrum were not built "
-                                      "(chomp_halo_setup families)");
+    for (size_t i = epoch0; i < epoch0 + n; ++i)
+      if (((ctx->fam_mask | ctx->put_mask[i]) & need) != need)
+        return fail(ctx, CHOMP_ERR_STATE, "power: knot tables of this spectrum were not built "
+                                          "(chomp_halo_setup families, or chomp_put_table) for "
+                                          "every epoch of the range");
   if (hf)
     for (size_t i = epoch0; i < epoch0 + n; ++i)
       if (!ctx->have_halofit[i])
@@ -1332,6 +1362,40 @@ static int stage_e_prep(chomp_ctx* ctx, size_t epoch0, int w, const double* dk, 
   return CHOMP_OK;
 }
 
+// The per-epoch delta_b buffer, cleared if chomp_epochs_set has been called since it was last
+// written.
+static int ensure_delta_b(chomp_ctx* ctx) {
+  const size_t had = ctx->cap_delta_b;
+  const int rc = ensure(ctx, &ctx->d_delta_b, &ctx->cap_delta_b, ctx->n_epoch);
+  if (rc) return rc;
+  if (ctx->delta_b_zero || ctx->cap_delta_b != had) {
+    HIPCHK(hipMemsetAsync(ctx->d_delta_b, 0, ctx->cap_delta_b * sizeof(double), ctx->stream));
+    ctx->delta_b_zero = false;
+  }
+  return CHOMP_OK;
+}
+
+int chomp_set_delta_b(chomp_ctx* ctx, size_t epoch0, size_t n, const double* delta_b, int mem) {
+  if (!ctx || !delta_b || n == 0 || (mem != CHOMP_HOST && mem != CHOMP_DEVICE))
+    return fail(ctx, CHOMP_ERR_ARG, "set_delta_b: bad args");
+  if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "set_delta_b before epochs_set");
+  if (epoch0 + n > ctx->n_epoch) return fail(ctx, CHOMP_ERR_ARG, "set_delta_b: epoch range");
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = ensure_delta_b(ctx);
+  if (rc) return rc;
+  if (mem == CHOMP_DEVICE) {
+    HIPCHK(hipMemcpyAsync(ctx->d_delta_b + epoch0, delta_b, n * sizeof(double),
+                          hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    // (through the pinned staging pair, no host synchronisation; every call uploads -- the
+    //  shadow cannot know what chomp_epochs_set has cleared since)
+    ctx->sh_delta_b.reset();
+    rc = upload(ctx, ctx->d_delta_b + epoch0, delta_b, n * sizeof(double), ctx->sh_delta_b);
+    if (rc) return rc;
+  }
+  return CHOMP_OK;
+}
+
 static bool plan_matches(chomp_ctx* ctx, size_t epoch0, const double* dk, size_t nk) {
   const chomp_ctx::PowerPlan& P = ctx->plan;
   if (!P.valid || P.k != dk || P.nk != nk || P.bao != ctx->with_bao) return false;
@@ -1367,10 +1431,15 @@ int chomp_power_plan(chomp_ctx* ctx, size_t epoch0, const double* k, size_t nk) 
 int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const double* k,
                       size_t nk, double* out, int mem) {
   StageRange range_(ctx, "chomp:power (Stage E)");
-  int rc = check_power(ctx, which, epoch0, n);
+  int rc = check_power(ctx, which, epoch0, n, true);
   if (rc) return rc;
   if (!k || !out || nk == 0) return fail(ctx, CHOMP_ERR_ARG, "power: null buffer");
   HIPCHK(hipSetDevice(ctx->device));
+  const bool ssc = (which & 15) == CHOMP_P_SSC_RESPONSE || (which & 15) == CHOMP_P_MM_SSC;
+  if (ssc) {
+    rc = ensure_delta_b(ctx);
+    if (rc) return rc;
+  }
   rc = prepare_extrapolation(ctx, which, epoch0, n);
   if (rc) return rc;
   const bool extrap = (which & CHOMP_P_EXTRAPOLATE) && !(which & CHOMP_P_HALOFIT);
@@ -1431,10 +1500,11 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
       if (timed) HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
       const unsigned gx8 = (gx + 7) / 8 * 8;
       // (two rows per block of the streaming kernel where the rows pair up: measured best on MI355X)
-      with_flag(n % 2 == 0, [&](auto PAIRS) {
+      with_flag(n % 2 == 0, ssc, [&](auto PAIRS, auto SSC) {
         constexpr int PER = PAIRS ? 2 : 1;
-        hipLaunchKernelGGL(k_power_stream<PER>, dim3(gx8, (unsigned)(n / PER)), dim3(256), 0, ctx->stream,
-                           L, ctx->d_tab, w, (int)epoch0, ctx->d_ktab, ctx->d_winfo, nk, dout);
+        hipLaunchKernelGGL((k_power_stream<PER, SSC>), dim3(gx8, (unsigned)(n / PER)), dim3(256), 0,
+                           ctx->stream, L, ctx->d_tab, w, (int)epoch0, ctx->d_ktab, ctx->d_winfo, nk,
+                           dout, ctx->d_delta_b);
       });
       if (timed) {
         HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
@@ -1446,20 +1516,20 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
       if (gy > n) gy = (unsigned)n;
       const int epy = (int)((n + gy - 1) / gy);
       gy = (unsigned)((n + epy - 1) / epy);
-      with_flag(ctx->with_bao, [&](auto BAO) {
-        hipLaunchKernelGGL(k_power_grid<BAO>, dim3(gx, gy), dim3(256), 0, ctx->stream, ctx->cfg, L,
-                           ctx->d_epochs, ctx->d_tab, w, (int)epoch0, (int)n, epy, 1, dk, nk,
-                           dout, ctx->d_slow, parity, 1, extrap);
+      with_flag(ctx->with_bao, ssc, [&](auto BAO, auto SSC) {
+        hipLaunchKernelGGL((k_power_grid<BAO, SSC>), dim3(gx, gy), dim3(256), 0, ctx->stream, ctx->cfg,
+                           L, ctx->d_epochs, ctx->d_tab, w, (int)epoch0, (int)n, epy, 1, dk, nk,
+                           dout, ctx->d_slow, parity, 1, extrap, ctx->d_delta_b);
       });
       streaming = false;
     }
     // per-lane pass over the listed k groups (streaming shape only; a planned grid knows
     // whether it has any)
     if (streaming && lanes_needed)
-      with_flag(ctx->with_bao, [&](auto BAO) {
-        hipLaunchKernelGGL(k_power_grid_lanes<BAO>, dim3(1024), dim3(256), 0, ctx->stream, ctx->cfg,
-                           L, ctx->d_epochs, ctx->d_tab, w, extrap, (int)epoch0, (int)n, dk, nk, dout,
-                           ctx->d_slow, parity);
+      with_flag(ctx->with_bao, ssc, [&](auto BAO, auto SSC) {
+        hipLaunchKernelGGL((k_power_grid_lanes<BAO, SSC>), dim3(1024), dim3(256), 0, ctx->stream,
+                           ctx->cfg, L, ctx->d_epochs, ctx->d_tab, w, extrap, (int)epoch0, (int)n, dk,
+                           nk, dout, ctx->d_slow, parity, ctx->d_delta_b);
       });
     if (ctx->timing_valid) HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   } else {
@@ -1468,7 +1538,8 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
     const size_t sh = (size_t)(12 * (L.NK - 1)) * sizeof(double);
     with_flag(ctx->with_bao, [&](auto BAO) {
       hipLaunchKernelGGL(k_power<BAO>, dim3(gx, (unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
-                         L, ctx->d_epochs, ctx->d_tab, which, (int)epoch0, dk, nk, dout);
+                         L, ctx->d_epochs, ctx->d_tab, which, (int)epoch0, dk, nk, dout,
+                         ctx->d_delta_b);
     });
   }
   HIPCHK(hipGetLastError());
@@ -1633,9 +1704,14 @@ int chomp_get_table(chomp_ctx* ctx, size_t epoch, int table, double* out, size_t
       if (!ctx->fam_mask) return fail(ctx, CHOMP_ERR_STATE, "get_table: no knot table built yet");
       break;
     case CHOMP_TAB_HF_LN_SIGMA2: off = L.off_hf_lns2; len = L.NK; need_hf = true; break;
+    case CHOMP_TAB_I_1_2: off = L.off_knot[F_I12]; len = L.NK; need = 1u << F_I12; break;
+    case CHOMP_TAB_LEVELS_I_1_2:
+      off = L.off_levels + F_I12 * L.NK; len = L.NK; need = 1u << F_I12; break;
     default: return fail(ctx, CHOMP_ERR_ARG, "get_table: unknown table");
   }
-  if ((ctx->fam_mask & need) != need)
+  // (the levels rows come from a set-up only: chomp_put_table installs knots, not levels)
+  const bool levels = table == CHOMP_TAB_LEVELS_I_1_2;
+  if (((ctx->fam_mask | (levels ? 0u : ctx->put_mask[epoch])) & need) != need)
     return fail(ctx, CHOMP_ERR_STATE, "get_table: this knot table was not built (chomp_halo_setup)");
   if (need_hf && !ctx->have_halofit[epoch])
     return fail(ctx, CHOMP_ERR_STATE, "get_table: chomp_halofit_setup not called for this epoch");
@@ -1644,6 +1720,34 @@ int chomp_get_table(chomp_ctx* ctx, size_t epoch, int table, double* out, size_t
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(out, ctx->d_tab + epoch * (size_t)L.stride + off, len * sizeof(double),
                    hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
+int chomp_put_table(chomp_ctx* ctx, size_t epoch, int table, const double* in, size_t n) {
+  if (!ctx || !in) return fail(ctx, CHOMP_ERR_ARG, "put_table: bad args");
+  if (!ctx->have_mass || epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "put_table before mass_setup");
+  int f = -1;
+  switch (table) {
+    case CHOMP_TAB_H_M: f = F_HM; break;
+    case CHOMP_TAB_PP_MM: f = F_PPMM; break;
+    case CHOMP_TAB_H_G: f = F_HG; break;
+    case CHOMP_TAB_PP_GM: f = F_PPGM; break;
+    case CHOMP_TAB_PP_GG: f = F_PPGG; break;
+    case CHOMP_TAB_I_1_2: f = F_I12; break;
+    default: return fail(ctx, CHOMP_ERR_ARG, "put_table: not a knot table");
+  }
+  const TabLayout& L = ctx->L;
+  if (n != (size_t)L.NK) return fail(ctx, CHOMP_ERR_ARG, "put_table: length mismatch");
+  if (capturing(ctx))
+    return fail(ctx, CHOMP_ERR_STATE, "put_table: synchronises the host; not while the stream is being captured");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(ctx->d_tab + epoch * (size_t)L.stride + L.off_knot[f], in, n * sizeof(double),
+                   hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_put_spline, dim3(1), dim3(64), (size_t)(11 * L.NK) * sizeof(double), ctx->stream,
+                     ctx->cfg, L, ctx->d_tab, (int)epoch, f);
+  HIPCHK(hipGetLastError());
+  ctx->put_mask[epoch] |= 1u << f;
   return CHOMP_OK;
 }
 

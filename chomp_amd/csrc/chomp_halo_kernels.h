@@ -44,15 +44,26 @@ constexpr int kPendingRounds = 32;
 constexpr int kPendingEvCount = kPendingDraw + kPendingRounds;
 constexpr int kPendingEvDraw = kPendingEvCount + kPendingRounds;
 constexpr int kPendingHead = kPendingEvDraw + kPendingRounds;
+// Integration groups (a pair of integrals, or one, sharing the nodes of one range): 0: h_m +
+// pp_mm, 1: h_g + pp_gm, 2: pp_gg, 3: I_1^2 (HaloSuperSampleCovariance, halo.py:1176-1199).
+// Node tables, end points and plans are per (epoch, group), kGroups to an epoch.
+constexpr int kGroups = 4;
 __host__ __device__ inline size_t pending_literal_base(size_t n_epoch, int NK) {
-  return (size_t)kPendingHead + 3 * n_epoch * (size_t)NK;
+  return (size_t)kPendingHead + kGroups * n_epoch * (size_t)NK;
 }
 __host__ __device__ inline size_t pending_eval_base(size_t n_epoch, int NK) {
-  return (size_t)kPendingHead + 2 * 3 * n_epoch * (size_t)NK;
+  return (size_t)kPendingHead + 2 * kGroups * n_epoch * (size_t)NK;
 }
 __host__ __device__ inline size_t pending_ints(size_t n_epoch, int NK) {
-  return (size_t)kPendingHead + 3 * 3 * n_epoch * (size_t)NK;
+  return (size_t)kPendingHead + 3 * kGroups * n_epoch * (size_t)NK;
 }
+__host__ __device__ inline int pick_group(int z, int g0, int g1, int g2, int g3) {
+  return z == 0 ? g0 : (z == 1 ? g1 : (z == 2 ? g2 : g3));
+}
+// the groups whose integrand is a single integral (out[1] of the pair; out[0] is zero)
+__host__ __device__ inline bool group_single(int group) { return group == 2 || group == 3; }
+// the groups whose integrands carry the HOD (break points, the deep-level sums)
+__host__ __device__ inline bool group_hod(int group) { return group == 1 || group == 2; }
 constexpr int kItemOpenA = 1 << 29, kItemOpenB = 1 << 30;   // flags of a listed item: see k_halo_knots
 constexpr int kItemIndex = kItemOpenA - 1;                  // ... and the mask of its index
 constexpr unsigned kMaskExclusion = 1u << 8;   // bit of the kernels' family mask: HaloExclusion
@@ -83,6 +94,18 @@ struct IntegrandMM {       // out[0] = h_m, out[1] = pp_mm (x rho_bar)
     mf_node(*c.e, nu, ln_nu, true, &nf, &b);
     out[0] = nf * b * y * c.window(lnm);
     out[1] = nf * exp(lnm) * y * y;
+  }
+};
+
+struct IntegrandI12 {      // out[0] = I_1^2 (x rho_bar), halo.py:1194-1199
+  HaloCtx c;
+  __device__ __forceinline__ void operator()(double ln_nu, double (&out)[1]) const {
+    const double nu = exp(ln_nu);
+    const double lnm = spline_eval(c.nu_knots, c.lnm_pp, c.NM, nu);
+    const double y = y_nfw(*c.e, *c.sici, c.ln_k, lnm);
+    double nf, b;
+    mf_node(*c.e, nu, ln_nu, true, &nf, &b);
+    out[0] = nf * b * exp(lnm) * y * y;
   }
 };
 
@@ -221,10 +244,11 @@ __device__ __forceinline__ void apply_halo_hod_wave(Epoch& E, const chomp_halo_p
   }
 }
 
-// Lower limit of group g's integrals: 0: nu_min; 1: nu(first_moment_zero); 2:
-// nu(second_moment_zero) (halo.py:909-911, 935-939, 1002-1006).
+// Lower limit of group g's integrals: 0, 3: nu_min; 1: nu(first_moment_zero); 2:
+// nu(second_moment_zero) (halo.py:909-911, 935-939, 1002-1006, 1183).
 __device__ __forceinline__ double group_lower(const Epoch& E, int group) {
-  return group == 0 ? log(E.nu_min) : (group == 1 ? E.ln_nu_lo_first : E.ln_nu_lo_second);
+  return (group == 0 || group == 3) ? log(E.nu_min)
+                                    : (group == 1 ? E.ln_nu_lo_first : E.ln_nu_lo_second);
 }
 
 // Stage what every halo-integral block needs into LDS (all threads call; ends with a
@@ -275,6 +299,9 @@ __device__ __forceinline__ void halo_node_fields(const Epoch& E, const double* n
   if (group == 0) {
     wA = nf * bias;
     wB = nf * mass;
+  } else if (group == 3) {   // I_1^2: one integral, nf b M y^2 (state 0: the y^2 branch)
+    wA = 0.0;
+    wB = nf * bias * mass;
   } else {
     double n1, n2;
     zheng_node(E, mass, lnm, &n1, &n2);
@@ -409,13 +436,13 @@ __global__ __launch_bounds__(256) void k_halo_nodes(
     chomp_config cfg, TabLayout L, Epoch* __restrict__ epochs, const double* __restrict__ tab,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod,
     const SiCiTab* __restrict__ sici_g, double* __restrict__ nodes, double* __restrict__ endp,
-    int g0, int g1, int g2, unsigned mask, unsigned* __restrict__ status,
+    int g0, int g1, int g2, int g3, unsigned mask, unsigned* __restrict__ status,
     int* __restrict__ npend, int* __restrict__ pending) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   __shared__ SiCiTab S;
   const int e = blockIdx.x;
-  const int group = blockIdx.y == 0 ? g0 : (blockIdx.y == 1 ? g1 : g2);
+  const int group = pick_group((int)blockIdx.y, g0, g1, g2, g3);
   HaloLds H;
   H.stage(L, E, S, epochs, e, tab + (size_t)e * L.stride, profile, hod, sici_g, sm);
   __shared__ unsigned scratch_status;
@@ -431,10 +458,10 @@ __global__ __launch_bounds__(256) void k_halo_nodes(
   if (blockIdx.y == 0 && blockIdx.z == 0)
     copy_doubles(reinterpret_cast<double*>(&epochs[e]), reinterpret_cast<const double*>(&E),
                  kEpochDoubles);
-  if (group < 0 || group > 2) return;            // n_bar only: the record is all it needs
+  if (group < 0 || group > 3) return;            // n_bar only: the record is all it needs
   halo_nodes_block(cfg, L, E, S, H.nu_knots, H.lnm_pp, group, (mask & kMaskExclusion) != 0,
-                   nodes + ((size_t)e * 3 + group) * kNodeStride,
-                   endp + ((size_t)e * 3 + group) * 2 * L.NK, (mask & kMaskDeepNodes) != 0,
+                   nodes + ((size_t)e * kGroups + group) * kNodeStride,
+                   endp + ((size_t)e * kGroups + group) * 2 * L.NK, (mask & kMaskDeepNodes) != 0,
                    (int)blockIdx.z, (int)gridDim.z);
 }
 
@@ -452,7 +479,7 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
     const TinkerTab* __restrict__ tinker, const double* __restrict__ gl16, int do_nodes,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod,
     const SiCiTab* __restrict__ sici_g, double* __restrict__ nodes, double* __restrict__ endp,
-    int g0, int g1, int g2, unsigned mask, unsigned* __restrict__ status,
+    int g0, int g1, int g2, int g3, unsigned mask, unsigned* __restrict__ status,
     int* __restrict__ npend, int* __restrict__ pending) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
@@ -481,11 +508,11 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
   if (first)
     copy_doubles(reinterpret_cast<double*>(&epochs[e]), reinterpret_cast<const double*>(&E),
                  kEpochDoubles);
-  const int group = blockIdx.y == 0 ? g0 : (blockIdx.y == 1 ? g1 : g2);
-  if (group < 0 || group > 2) return;            // n_bar only: the record is all it needs
+  const int group = pick_group((int)blockIdx.y, g0, g1, g2, g3);
+  if (group < 0 || group > 3) return;            // n_bar only: the record is all it needs
   halo_nodes_block(cfg, L, E, S, M.y_nu, M.c_lnm, group, (mask & kMaskExclusion) != 0,
-                   nodes + ((size_t)e * 3 + group) * kNodeStride,
-                   endp + ((size_t)e * 3 + group) * 2 * L.NK, (mask & kMaskDeepNodes) != 0,
+                   nodes + ((size_t)e * kGroups + group) * kNodeStride,
+                   endp + ((size_t)e * kGroups + group) * 2 * L.NK, (mask & kMaskDeepNodes) != 0,
                    (int)blockIdx.z, (int)gridDim.z);
 }
 
@@ -528,7 +555,7 @@ struct NodeIntegrand {
 
 __device__ __forceinline__ int group_fa(int group) { return group == 0 ? F_HM : F_HG; }
 __device__ __forceinline__ int group_fb(int group) {
-  return group == 0 ? F_PPMM : (group == 1 ? F_PPGM : F_PPGG);
+  return group == 0 ? F_PPMM : (group == 1 ? F_PPGM : (group == 2 ? F_PPGG : F_I12));
 }
 
 // ---------------------------------------------------------------------------
@@ -537,7 +564,7 @@ __device__ __forceinline__ int group_fb(int group) {
 // splines over ln k (the builds run in lockstep, one wavefront each, parallel cyclic
 // reduction), the Stage-E record, n_bar into the epoch record.  sm: 51 NK doubles.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline int finalize_lds_doubles(int NK) { return 42 * NK; }
+__host__ __device__ inline int finalize_lds_doubles(int NK) { return (1 + kFamilies + 36) * NK; }
 // through: the knot values were (in part) written by other blocks of this launch, with agent
 // scope: they are read with agent-scope loads, and the caller needs no fence in front.
 __device__ __forceinline__ void halo_finalize_block(const chomp_config& cfg, const TabLayout& L,
@@ -548,8 +575,8 @@ __device__ __forceinline__ void halo_finalize_block(const chomp_config& cfg, con
                                                     bool through = false) {
   const int NK = L.NK;
   double* xk = sm;                      // [NK]
-  double* yk = xk + NK;                 // [5][NK]
-  double* work = yk + 5 * NK;           // [4][9 NK]
+  double* yk = xk + NK;                 // [kFamilies][NK]
+  double* work = yk + kFamilies * NK;   // [4][9 NK]
   double* t = tab + (size_t)e * L.stride;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const double nbr = t[L.off_misc];                    // n_bar / rho_bar
@@ -564,14 +591,14 @@ __device__ __forceinline__ void halo_finalize_block(const chomp_config& cfg, con
     epochs[e].n_bar_over_rho_bar = nbr;                // halo.py:692-700
     epochs[e].n_bar = nbr * rho_bar;
   }
-  const int rounds = (fam_mask >> 4) ? 2 : 1;          // (family 4 = pp_gg is the only one of round 1)
+  const int rounds = (fam_mask >> 4) ? 2 : 1;          // (families 4, 5 = pp_gg, I_1^2: round 1)
   for (int round = 0; round < rounds; ++round) {
     const int f = wave + 4 * round;                      // (wavefronts beyond the fourth only keep
-    const bool active = wave < 4 && f < 5 && ((fam_mask >> f) & 1u);   //  the barriers company)
+    const bool active = wave < 4 && f < kFamilies && ((fam_mask >> f) & 1u);   //  the barriers company)
     if (active) {
       const double n_bar = nbr * rho_bar;
       double scale = 1.0;
-      if (f == F_PPMM) scale = 1.0 / rho_bar;                       // halo.py:983
+      if (f == F_PPMM || f == F_I12) scale = 1.0 / rho_bar;         // halo.py:983, 1190
       else if (f == F_HG) scale = 1.0 / nbr;                        // :959
       else if (f == F_PPGM) scale = 1.0 / n_bar;                    // :1072
       else if (f == F_PPGG) scale = rho_bar / (n_bar * n_bar);      // :1026
@@ -691,6 +718,12 @@ __device__ __forceinline__ void halo_eval_coded(int group, const HaloCtx& c, dou
     *code = 0;
     return;
   }
+  if (group == 3) {
+    out[0] = 0.0;
+    out[1] = nf * b * exp(lnm) * y * y;
+    *code = 0;
+    return;
+  }
   const double mass = exp(lnm);
   double n1, n2;
   zheng_node(E, mass, lnm, &n1, &n2);
@@ -711,6 +744,7 @@ __device__ __forceinline__ void halo_eval_coded(int group, const HaloCtx& c, dou
 // The discrete state alone (halo_eval_coded's code) at a node: everything of the integrand
 // that does not depend on k and decides its branch -- no NFW transform, no mass function.
 __device__ __forceinline__ int halo_state_at(int group, const HaloCtx& c, double ln_nu) {
+  if (group == 0 || group == 3) return 0;
   const Epoch& E = *c.e;
   const double nu = exp(ln_nu);
   const double lnm = spline_eval(c.nu_knots, c.lnm_pp, c.NM, nu);
@@ -908,6 +942,12 @@ __device__ __forceinline__ void deep_literal(const chomp_config& cfg, const Halo
                                                 cfg.divmax, red);
     val[0] = r.value[0]; val[1] = r.value[1]; lev[0] = r.level[0]; lev[1] = r.level[1];
     conv[0] = r.converged[0]; conv[1] = r.converged[1];
+  } else if (group == 3) {
+    IntegrandI12 f{c};
+    const RombergOut<1> r = romberg_group<NW, 1>(f, group_lower(E, 3), ln_nu_max,
+                                                cfg.global_precision, cfg.halo_precision,
+                                                cfg.divmax, red);
+    val[1] = r.value[0]; lev[1] = r.level[0]; conv[1] = r.converged[0];
   } else {
     IntegrandGG f{c};
     const RombergOut<1> r = romberg_group<NW, 1>(f, group_lower(E, 2), ln_nu_max,
@@ -1167,7 +1207,7 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs, double* __restrict__ tab,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod,
     const SiCiTab* __restrict__ sici_g, const double* __restrict__ nodes,
-    const double* __restrict__ endp, int g0, int g1, int g2, unsigned mask, int want_nbar,
+    const double* __restrict__ endp, int g0, int g1, int g2, int g3, unsigned mask, int want_nbar,
     int* __restrict__ pending, int* __restrict__ npend, unsigned* __restrict__ status,
     int hod_cap, int want_plan, int max_rough, int max_fine, DeepPlan* __restrict__ plans) {
   extern __shared__ __align__(16) double sm[];
@@ -1182,7 +1222,7 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
   const int bx = (int)gridDim.y - 1 - (int)blockIdx.y, bz = (int)gridDim.z - 1 - (int)blockIdx.z;
   if (bx >= kb) {                  // ---- the extra blocks: n_bar, the groups' break-point plans
     const int ex = bx - kb;
-    const int gx = bz == 0 ? g0 : (bz == 1 ? g1 : g2);
+    const int gx = pick_group(bz, g0, g1, g2, g3);
     const bool nbar_block = want_nbar && ex == 0 && bz == 0;
     const bool plan_block = want_plan && ex == (want_nbar ? 1 : 0) && gx >= 0 && gx <= 2;
     if (!nbar_block && !plan_block) return;
@@ -1200,12 +1240,12 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
     // (what the listed knots of (e, gx) share: see DeepPlan)
     __shared__ DeepPlanLds<kNodeTabLevel> plan_lds;
     deep_plan_block<kNodeTabLevel>(E, H.nu_knots, H.lnm_pp, L.NM, gx,
-                                   nodes + ((size_t)e * 3 + gx) * kNodeStride, max_rough, max_fine,
-                                   cfg.divmax, plan_lds, plans + (size_t)e * 3 + gx);
+                                   nodes + ((size_t)e * kGroups + gx) * kNodeStride, max_rough, max_fine,
+                                   cfg.divmax, plan_lds, plans + (size_t)e * kGroups + gx);
     return;
   }
-  const int group = bz == 0 ? g0 : (bz == 1 ? g1 : g2);
-  if (group < 0 || group > 2) return;
+  const int group = pick_group(bz, g0, g1, g2, g3);
+  if (group < 0 || group > 3) return;
   copy_doubles(reinterpret_cast<double*>(&S), reinterpret_cast<const double*>(sici_g),
                (int)(sizeof(SiCiTab) / sizeof(double)));
   __syncthreads();
@@ -1215,9 +1255,9 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
   const int ik = KNW == 1 ? (kCoop ? bx + kb * (int)(threadIdx.x >> 6) : bx * 4 + (int)(threadIdx.x >> 6)) : bx;
   const bool have = ik < NK;
   if (!kCoop && !have) return;     // (no barrier below unless kCoop: the wavefronts are independent)
-  const double* node = nodes + ((size_t)e * 3 + group) * kNodeStride;
+  const double* node = nodes + ((size_t)e * kGroups + group) * kNodeStride;
   const double a = node[kNodeFields * kNodeCount], b = node[kNodeFields * kNodeCount + 1];
-  const double* ep = endp + ((size_t)e * 3 + group) * 2 * NK + 2 * (have ? ik : 0);
+  const double* ep = endp + ((size_t)e * kGroups + group) * 2 * NK + 2 * (have ? ik : 0);
   const double fb[2] = {ep[0], ep[1]};
   double* t = tab + (size_t)e * L.stride;
   const double ln_k0 = node[kNodeFields * kNodeCount + 2], ln_k1 = node[kNodeFields * kNodeCount + 3];
@@ -1229,7 +1269,7 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
   // node of the table for them anyway: what such a knot sums here beyond level hod_cap is
   // done twice (at the default HOD the pairs either stop at levels 8-9 or run to 11..20, so
   // level 10 -- half the table's nodes, on one wavefront -- is evaluated for the listed only).
-  const int top = (group > 0 && (mask & kMaskDeepNodes) && hod_cap < kNodeLevel) ? hod_cap : kNodeLevel;
+  const int top = (group_hod(group) && (mask & kMaskDeepNodes) && hod_cap < kNodeLevel) ? hod_cap : kNodeLevel;
   const int dmax = cfg.divmax < top ? cfg.divmax : top;
   RombergOut<2> r;
   if constexpr (kCoop) {
@@ -1328,12 +1368,12 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
     double* lev = t + L.off_levels;
     const int fa = group_fa(group), fb_ = group_fb(group);
     const bool more = cfg.divmax > top;
-    if (group != 2 && (mask & (1u << fa))) {
+    if (!group_single(group) && (mask & (1u << fa))) {
       t[L.off_knot[fa] + ik] = r.value[0];
       lev[fa * NK + ik] = (!r.converged[0] && more) ? kPendingLevel : (double)r.level[0];
     }
     bool any = false, need_a = false, need_b = false;
-    if (group != 2 && (mask & (1u << fa))) need_a = !r.converged[0] && more;
+    if (!group_single(group) && (mask & (1u << fa))) need_a = !r.converged[0] && more;
     if (mask & (1u << fb_)) {
       t[L.off_knot[fb_] + ik] = r.value[1];
       lev[fb_ * NK + ik] = (!r.converged[1] && more) ? kPendingLevel : (double)r.level[1];
@@ -1343,7 +1383,7 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
     // divmax within the node tables: scipy returns the last row with an AccuracyWarning
     if (!more) {
       unsigned st = 0u;
-      if (group != 2 && (mask & (1u << fa)) && !r.converged[0]) st |= kStHaloDivmax0 << fa;
+      if (!group_single(group) && (mask & (1u << fa)) && !r.converged[0]) st |= kStHaloDivmax0 << fa;
       if ((mask & (1u << fb_)) && !r.converged[1]) st |= kStHaloDivmax0 << fb_;
       if (st) atomicOr(&status[e], st);
     }
@@ -1355,7 +1395,7 @@ __global__ __launch_bounds__(KNW == 0 ? 64 : 256, KNW == 1 ? 3 : 1) void k_halo_
       //  the levels table -- a dependent round trip at the front of every listed knot)
       const int item = (int)((bz * n_epoch + e) * NK + ik) | (need_a ? kItemOpenA : 0) |
                        (need_b ? kItemOpenB : 0);
-      const int cap = 3 * n_epoch * NK;
+      const int cap = kGroups * n_epoch * NK;
       if (4 * ik >= 3 * NK) pending[kPendingHead + atomicAdd(&pending[0], 1)] = item;
       else pending[kPendingHead + cap - 1 - atomicAdd(&pending[2], 1)] = item;
     }
@@ -1400,7 +1440,7 @@ __host__ __device__ inline int deep_f_off(int NM) { return (NM + 8 * (NM - 1) + 
 constexpr int kDeepChunks = 8;
 template <int LC>
 __global__ __launch_bounds__(256) void k_halo_knots_samples(
-    chomp_config cfg, TabLayout L, const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2,
+    chomp_config cfg, TabLayout L, const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, int g3,
     unsigned mask, int n_epoch, const int* __restrict__ pending, const double* __restrict__ nodes,
     const double* __restrict__ endp, double* __restrict__ samples, double* __restrict__ psum,
     int parts, int slot_lo, int slot_hi) {
@@ -1423,11 +1463,11 @@ __global__ __launch_bounds__(256) void k_halo_knots_samples(
     const int li = slot_lo + w / parts, part = w % parts;
     const int item = kItemIndex & (li < count_front
                                        ? pending[kPendingHead + li]
-                                       : pending[kPendingHead + 3 * n_epoch * NK - 1 - (li - count_front)]);
+                                       : pending[kPendingHead + kGroups * n_epoch * NK - 1 - (li - count_front)]);
     const int ik = item % NK, e = (item / NK) % n_epoch, zg = item / (NK * n_epoch);
-    const int group = zg == 0 ? g0 : (zg == 1 ? g1 : g2);
-    if (group < 0 || group > 2) continue;          // (never listed)
-    const double* nd = nodes + ((size_t)e * 3 + group) * kNodeStride;
+    const int group = pick_group(zg, g0, g1, g2, g3);
+    if (group < 0 || group > 3) continue;          // (never listed)
+    const double* nd = nodes + ((size_t)e * kGroups + group) * kNodeStride;
     const KnotK kk = KnotK::uniform(linspace_at(log(cfg.k_min), log(cfg.k_max), NK, ik));
     double* slot = samples + (size_t)(li - slot_lo) * kDeepSlot;
     for (int c = part * per; c < (part + 1) * per; ++c) {
@@ -1447,7 +1487,7 @@ __global__ __launch_bounds__(256) void k_halo_knots_samples(
       slot[at] = o[0];
       slot[kDeepF + at] = o[1];
       if (c == 0 && tid == 0) {                    // the upper end point (node 1 of the table)
-        const double* ep = endp + ((size_t)e * 3 + group) * 2 * NK + 2 * ik;
+        const double* ep = endp + ((size_t)e * kGroups + group) * 2 * NK + 2 * ik;
         slot[deep_pos(NC)] = ep[0];
         slot[kDeepF + deep_pos(NC)] = ep[1];
         o[0] = 0.0;                                // (an end point: in no level's sum)
@@ -1567,14 +1607,14 @@ template <int NT>
 __device__ __forceinline__ void deep_literal_loop(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs, double* __restrict__ tab,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod,
-    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, unsigned mask, int n_epoch,
+    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, int g3, unsigned mask, int n_epoch,
     int* __restrict__ pending, int* __restrict__ npend, Epoch* __restrict__ epochs_rw,
     unsigned fam_mask, unsigned* __restrict__ status, int* __restrict__ stats);
 
 template <int LC, int NT, bool SELF, bool EVAL>
 __device__ __forceinline__ void deep_fast_body(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs, double* __restrict__ tab,
-    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, unsigned mask, int n_epoch,
+    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, int g3, unsigned mask, int n_epoch,
     int* __restrict__ pending, int* __restrict__ npend, Epoch* __restrict__ epochs_rw,
     unsigned fam_mask, unsigned* __restrict__ status, const double* __restrict__ deepw,
     int all_literal, double tol, int max_rough, int max_fine, int* __restrict__ stats,
@@ -1662,17 +1702,17 @@ __device__ __forceinline__ void deep_fast_body(
     }
     const int item_raw = item_sh < count_front
                              ? pending[kPendingHead + item_sh]
-                             : pending[kPendingHead + 3 * n_epoch * NK - 1 - (item_sh - count_front)];
+                             : pending[kPendingHead + kGroups * n_epoch * NK - 1 - (item_sh - count_front)];
     const int item = item_raw & kItemIndex;
     const int ik = item % NK, e = (item / NK) % n_epoch, zg = item / (NK * n_epoch);
-    const int group = zg == 0 ? g0 : (zg == 1 ? g1 : g2);
+    const int group = pick_group(zg, g0, g1, g2, g3);
     double* t = tab + (size_t)e * L.stride;
     double* levs = t + L.off_levels;
     const int fa = group_fa(group < 0 ? 0 : group), fb = group_fb(group < 0 ? 0 : group);
     // (which of the pair is open: from the item's flags -- the lister's levels[] == pending marks)
-    const bool pa = group >= 0 && group <= 2 && group != 2 && (mask & (1u << fa)) &&
+    const bool pa = group >= 0 && group <= 3 && !group_single(group) && (mask & (1u << fa)) &&
                     (item_raw & kItemOpenA) != 0;
-    const bool pb = group >= 0 && group <= 2 && (mask & (1u << fb)) && (item_raw & kItemOpenB) != 0;
+    const bool pb = group >= 0 && group <= 3 && (mask & (1u << fb)) && (item_raw & kItemOpenB) != 0;
     if (!pa && !pb) {              // (never listed; keep the count right)
       deep_arrive(cfg, L, epochs_rw, tab, e, fam_mask, status, npend, fences, &last_sh, sm,
                   kArriveNothing);
@@ -1680,7 +1720,8 @@ __device__ __forceinline__ void deep_fast_body(
       continue;
     }
     if constexpr (SELF) {
-      // (group 0 only; the block-wide literal Romberg on the smooth h_m / pp_mm pair)
+      // (groups 0 and 3 only; the block-wide literal Romberg on the smooth h_m / pp_mm pair or
+      //  on I_1^2)
       double* nu_knots = sm;
       double* lnm_pp = nu_knots + L.NM;
       copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
@@ -1690,10 +1731,19 @@ __device__ __forceinline__ void deep_fast_body(
       __syncthreads();
       HaloCtx c{&E, &S, nu_knots, lnm_pp, L.NM,
                 linspace_at(log(cfg.k_min), log(cfg.k_max), NK, ik), (mask & kMaskExclusion) != 0};
-      IntegrandMM f{c};
-      const RombergOut<2> r = romberg_group<NWV, 2>(f, group_lower(E, 0), log(E.nu_max),
-                                                   cfg.global_precision, cfg.halo_precision,
-                                                   cfg.divmax, sm + L.NM + 8 * (L.NM - 1));
+      RombergOut<2> r;
+      if (group == 3) {
+        IntegrandI12 f{c};
+        const RombergOut<1> r1 = romberg_group<NWV, 1>(f, group_lower(E, 3), log(E.nu_max),
+                                                      cfg.global_precision, cfg.halo_precision,
+                                                      cfg.divmax, sm + L.NM + 8 * (L.NM - 1));
+        r.value[0] = 0.0; r.level[0] = 0; r.converged[0] = true;
+        r.value[1] = r1.value[0]; r.level[1] = r1.level[0]; r.converged[1] = r1.converged[0];
+      } else {
+        IntegrandMM f{c};
+        r = romberg_group<NWV, 2>(f, group_lower(E, 0), log(E.nu_max), cfg.global_precision,
+                                  cfg.halo_precision, cfg.divmax, sm + L.NM + 8 * (L.NM - 1));
+      }
       if (tid == 0) {
         if (pa) { t[L.off_knot[fa] + ik] = r.value[0]; levs[fa * NK + ik] = (double)r.level[0]; }
         if (pb) { t[L.off_knot[fb] + ik] = r.value[1]; levs[fb * NK + ik] = (double)r.level[1]; }
@@ -1707,8 +1757,9 @@ __device__ __forceinline__ void deep_fast_body(
       if (!w_safe) { __syncthreads(); stage_weights(); }
       continue;
     }
-    // hand the knot on where this scheme does not apply at all
-    if (all_literal || cfg.divmax <= LC || !(mask & kMaskDeepNodes)) {
+    // hand the knot on where this scheme does not apply at all (I_1^2: a smooth integrand with
+    // no break-point plan, literal as in the SELF instance)
+    if (all_literal || cfg.divmax <= LC || !(mask & kMaskDeepNodes) || group == 3) {
       if (tid == 0) lit_items[atomicAdd(&pending[4], 1)] = item;
       continue;
     }
@@ -1721,7 +1772,7 @@ __device__ __forceinline__ void deep_fast_body(
     }
     // ---- the (epoch, group)'s break-point plan (k_halo_knots' extra block built it)
     copy_doubles(reinterpret_cast<double*>(&PL),
-                 reinterpret_cast<const double*>(plans + (size_t)e * 3 + group), kDeepPlanDoubles);
+                 reinterpret_cast<const double*>(plans + (size_t)e * kGroups + group), kDeepPlanDoubles);
     double* nu_knots = sm;
     double* lnm_pp = nu_knots + L.NM;
     if constexpr (EVAL) {            // (the integrand's tables: only where nodes are evaluated)
@@ -2056,20 +2107,20 @@ template <int LC, int NT, bool SELF, bool EVAL, bool LIT = false>
 //  that only see the rare hand-overs -- SELF, LIT -- uncapped and free of scratch)
 __global__ __launch_bounds__(NT, (SELF || LIT) ? 1 : (EVAL ? 512 / NT : (NT == 256 ? 3 : 1))) void k_halo_knots_fast(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs, double* __restrict__ tab,
-    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, unsigned mask, int n_epoch,
+    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, int g3, unsigned mask, int n_epoch,
     int* __restrict__ pending, int* __restrict__ npend, Epoch* __restrict__ epochs_rw,
     unsigned fam_mask, unsigned* __restrict__ status, const double* __restrict__ deepw,
     int all_literal, double tol, int max_rough, int max_fine, int* __restrict__ stats,
     const double* __restrict__ samples, const double* __restrict__ psum, int parts,
     int round, int slot_lo, int slot_hi, int from_eval, const DeepPlan* __restrict__ plans,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod) {
-  deep_fast_body<LC, NT, SELF, EVAL>(cfg, L, epochs, tab, sici_g, g0, g1, g2, mask, n_epoch, pending,
+  deep_fast_body<LC, NT, SELF, EVAL>(cfg, L, epochs, tab, sici_g, g0, g1, g2, g3, mask, n_epoch, pending,
                                      npend, epochs_rw, fam_mask, status, deepw, all_literal, tol,
                                      max_rough, max_fine, stats, samples, psum, parts, round,
                                      slot_lo, slot_hi, from_eval, plans);
   if constexpr (LIT) {
     __syncthreads();
-    deep_literal_loop<NT>(cfg, L, epochs, tab, profile, hod, sici_g, g0, g1, g2, mask, n_epoch,
+    deep_literal_loop<NT>(cfg, L, epochs, tab, profile, hod, sici_g, g0, g1, g2, g3, mask, n_epoch,
                           pending, npend, epochs_rw, fam_mask, status, stats);
   }
 }
@@ -2083,7 +2134,7 @@ template <int NT>
 __device__ __forceinline__ void deep_literal_loop(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs, double* __restrict__ tab,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod,
-    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, unsigned mask, int n_epoch,
+    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, int g3, unsigned mask, int n_epoch,
     int* __restrict__ pending, int* __restrict__ npend, Epoch* __restrict__ epochs_rw,
     unsigned fam_mask, unsigned* __restrict__ status, int* __restrict__ stats) {
   constexpr int NWV = NT / 64;
@@ -2103,11 +2154,11 @@ __device__ __forceinline__ void deep_literal_loop(
     if (item_sh >= count) return;  // block-uniform
     const int item = items[item_sh];
     const int ik = item % NK, e = (item / NK) % n_epoch, zg = item / (NK * n_epoch);
-    const int group = zg == 0 ? g0 : (zg == 1 ? g1 : g2);
+    const int group = pick_group(zg, g0, g1, g2, g3);
     double* t = tab + (size_t)e * L.stride;
     double* levs = t + L.off_levels;
     const int fa = group_fa(group), fb = group_fb(group);
-    const bool pa = group != 2 && (mask & (1u << fa)) && levs[fa * NK + ik] == kPendingLevel;
+    const bool pa = !group_single(group) && (mask & (1u << fa)) && levs[fa * NK + ik] == kPendingLevel;
     const bool pb = (mask & (1u << fb)) && levs[fb * NK + ik] == kPendingLevel;
     HaloLds H;
     H.stage(L, E, S, epochs, e, t, profile, hod, sici_g, sm);
@@ -2134,11 +2185,30 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_halo_knots_literal(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs, double* __restrict__ tab,
     const chomp_halo_par* __restrict__ profile, const HodDev* __restrict__ hod,
-    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, unsigned mask, int n_epoch,
+    const SiCiTab* __restrict__ sici_g, int g0, int g1, int g2, int g3, unsigned mask, int n_epoch,
     int* __restrict__ pending, int* __restrict__ npend, Epoch* __restrict__ epochs_rw,
     unsigned fam_mask, unsigned* __restrict__ status, int* __restrict__ stats) {
-  deep_literal_loop<NT>(cfg, L, epochs, tab, profile, hod, sici_g, g0, g1, g2, mask, n_epoch,
+  deep_literal_loop<NT>(cfg, L, epochs, tab, profile, hod, sici_g, g0, g1, g2, g3, mask, n_epoch,
                         pending, npend, epochs_rw, fam_mask, status, stats);
+}
+
+// chomp_put_table: the not-a-knot spline of family f of epoch e rebuilt from the knot values just
+// installed, by halo_finalize_block's routine on the same abscissae with the same 64 lanes (the same
+// coefficients, bit for bit, for the same knots).  grid 1, block 64, LDS 11 NK doubles.
+__global__ __launch_bounds__(64) void k_put_spline(chomp_config cfg, TabLayout L,
+                                                   double* __restrict__ tab, int e, int f) {
+  extern __shared__ __align__(16) double sm[];
+  const int NK = L.NK;
+  double* xk = sm;
+  double* yk = xk + NK;
+  double* work = yk + NK;                 // [9 NK]
+  double* t = tab + (size_t)e * L.stride;
+  for (int i = threadIdx.x; i < NK; i += 64) {
+    xk[i] = linspace_at(log(cfg.k_min), log(cfg.k_max), NK, i);
+    yk[i] = t[L.off_knot[f] + i];
+  }
+  __syncthreads();
+  spline_build_pcr(xk, yk, NK, t + L.off_kpp[f], work, (int)threadIdx.x, 64, true);
 }
 
 }  // namespace chomp

@@ -31,11 +31,16 @@
 
 namespace chomp {
 
+// Families: index into off_knot / off_kpp (and rows of the levels table).  F_I12 is the
+// I_1^2 table of HaloSuperSampleCovariance (halo.py:1176-1199).
+enum { F_HM = 0, F_PPMM = 1, F_HG = 2, F_PPGM = 3, F_PPGG = 4, F_I12 = 5 };
+constexpr int kFamilies = 6;
+
 // Per-epoch table block (doubles), offsets fixed by the context's point counts.
 struct TabLayout {
   int NM, NK;
   int off_ln_mass, off_nu, off_nu_pp, off_lnm_pp;
-  int off_knot[5], off_kpp[5];
+  int off_knot[6], off_kpp[6];             // families F_*
   int off_levels, off_hf_lns2, off_misc;   // misc[0] = n_bar / rho_bar (raw integral)
   int stride;
   // pinned host words (device-accessible) the block that finalises an epoch's halo set-up
@@ -55,9 +60,9 @@ inline TabLayout make_layout(int NM, int NK) {
   L.off_nu = o; o += NM;
   L.off_nu_pp = o; o += 4 * (NM - 1);
   L.off_lnm_pp = o; o += 4 * (NM - 1);
-  for (int f = 0; f < 5; ++f) { L.off_knot[f] = o; o += NK; }
-  for (int f = 0; f < 5; ++f) { L.off_kpp[f] = o; o += 4 * (NK - 1); }
-  L.off_levels = o; o += 5 * NK;
+  for (int f = 0; f < kFamilies; ++f) { L.off_knot[f] = o; o += NK; }
+  for (int f = 0; f < kFamilies; ++f) { L.off_kpp[f] = o; o += 4 * (NK - 1); }
+  L.off_levels = o; o += kFamilies * NK;
   L.off_hf_lns2 = o; o += NK;
   L.off_misc = o; o += 8;
   L.stride = (o + 7) & ~7;
@@ -65,9 +70,6 @@ inline TabLayout make_layout(int NM, int NK) {
   L.h_seq = 0u;
   return L;
 }
-
-// Families: index into off_knot / off_kpp.
-enum { F_HM = 0, F_PPMM = 1, F_HG = 2, F_PPGM = 3, F_PPGG = 4 };
 
 // Node tables of the halo integrals: every knot k of an epoch integrates over the
 // SAME ln(nu) nodes, so everything that does not depend on k (nu f(nu), b(nu), M(nu),
@@ -117,7 +119,7 @@ constexpr unsigned kStSearchExhausted = CHOMP_ST_MASS_SEARCH_EXHAUSTED;
 constexpr unsigned kStSigmaDivmax = CHOMP_ST_SIGMA_DIVMAX;
 constexpr unsigned kStHaloDivmax0 = CHOMP_ST_HALO_DIVMAX_H_M;       // << family index
 constexpr unsigned kStNonfinite = CHOMP_ST_NONFINITE;
-constexpr unsigned kStHaloBits = (31u * CHOMP_ST_HALO_DIVMAX_H_M) | CHOMP_ST_NONFINITE;
+constexpr unsigned kStHaloBits = (63u * CHOMP_ST_HALO_DIVMAX_H_M) | CHOMP_ST_NONFINITE;
 
 // Cooperative copy of POD blocks as doubles.
 __device__ __forceinline__ void copy_doubles(double* dst, const double* src, int n) {

@@ -19,10 +19,29 @@ namespace chomp {
 // needs in LDS, then streams k -> P with coalesced 8-byte accesses.
 // ---------------------------------------------------------------------------
 struct PowerFam { int fa, fb, fp; };
+__device__ __forceinline__ bool is_ssc(int w) {
+  return w == CHOMP_P_SSC_RESPONSE || w == CHOMP_P_MM_SSC;
+}
+// (the super-sample codes read h_m, I_1^2 and pp_mm: I_1^2 rides in the second 2-halo slot)
 __device__ __forceinline__ PowerFam power_families(int w) {
   if (w == CHOMP_P_GM) return PowerFam{F_HG, F_HM, F_PPGM};
   if (w == CHOMP_P_GG) return PowerFam{F_HG, F_HG, F_PPGG};
+  if (is_ssc(w)) return PowerFam{F_HM, F_I12, F_PPMM};
   return PowerFam{F_HM, F_HM, F_PPMM};
+}
+
+// HaloSuperSampleCovariance inside [k_min, k_max] (halo.py:1136-1169), from the linear spectrum
+// As = P_lin(k), h = h_m(k), i12 = I_1^2(k), pp = pp_mm(k) and the epoch's delta_b:
+//   P_mm = P_lin h^2 + pp (the very operations of P_mm's streaming shapes: the same bits),
+//   dlnP/ddelta_b = (68/21 P_lin h^2 + I_1^2) / P_mm,  P_mm_ssc = P_mm (1 + delta_b dlnP/ddelta_b).
+// Every launch shape evaluates this one function, so the shapes agree bit for bit.
+constexpr double kSscBeat = 68.0 / 21.0;
+__device__ __forceinline__ double ssc_in_range(int w, double As, double h, double i12, double pp,
+                                               double delta_b) {
+  const double h2 = h * h;
+  const double pmm = fma(As, h2, pp);
+  const double resp = fma(kSscBeat * As, h2, i12) / pmm;
+  return w == CHOMP_P_SSC_RESPONSE ? resp : pmm * fma(resp, delta_b, 1.0);
 }
 
 // Above k_max with Halo(extrapolate=True) (halo.py:300-312, 341-367, 405-431); x[] are
@@ -80,6 +99,7 @@ struct PowerEval {
   bool halofit, extrap;
   const double* tail;             // misc[3..7] of the epoch (k_power_extrap)
   double x0, dx, inv_dx, amp2, k_min, k_max, c_lo;
+  double delta_b = 0.0;           // the epoch's delta_b (CHOMP_P_MM_SSC; set by the caller)
 
   // Stage the coefficient sets of spectrum `which` of epoch table `t` into `sm`
   // (needs 12 (NK-1) doubles) and set the evaluator up.  All threads call it;
@@ -96,6 +116,7 @@ struct PowerEval {
     int fa = F_HM, fb = F_HM, fp = F_PPMM;
     if (w == CHOMP_P_GM) { fa = F_HG; fb = F_HM; fp = F_PPGM; }
     else if (w == CHOMP_P_GG) { fa = F_HG; fb = F_HG; fp = F_PPGG; }
+    else if (is_ssc(w)) { fb = F_I12; }
     double* a = sm;
     double* b = a + 4 * (NK - 1);
     double* p = b + 4 * (NK - 1);
@@ -121,7 +142,8 @@ struct PowerEval {
   __device__ __forceinline__ void finish_t() {
     amp2 = E->amp * E->sigma_norm * E->sigma_norm;
     if (w != CHOMP_P_LIN && !halofit) {
-      const double ha = pp_poly(ca, 0, 0.0), hb = pp_poly(cb, 0, 0.0), p0 = pp_poly(cp, 0, 0.0);
+      const double ha = pp_poly(ca, 0, 0.0), p0 = pp_poly(cp, 0, 0.0);
+      const double hb = is_ssc(w) ? ha : pp_poly(cb, 0, 0.0);   // (P_mm's constant)
       c_lo = ha * hb + p0 / linear_power_t<BAO>(*E, k_min);
     }
   }
@@ -142,6 +164,15 @@ struct PowerEval {
         pp = spline_eval_uniform(x0, dx, cp, NK, lk);
       }
       return pmm * ha * hb + pp;
+    }
+    if (is_ssc(w)) {                                      // halo.py:1136-1169
+      if (kv < k_min) return w == CHOMP_P_SSC_RESPONSE ? 0.0 : linear_power_t<BAO>(*E, kv) * c_lo;
+      if (!(kv <= k_max)) return 0.0;
+      const double lk = log(kv);
+      const double h = spline_eval_uniform(x0, dx, ca, NK, lk);
+      const double i12 = spline_eval_uniform(x0, dx, cb, NK, lk);
+      const double pp = spline_eval_uniform(x0, dx, cp, NK, lk);
+      return ssc_in_range(w, amp2 * power_shape_t<BAO>(*E, lk, kv), h, i12, pp, delta_b);
     }
     if (kv < k_min) return linear_power_t<BAO>(*E, kv) * c_lo;
     if (extrap ? kv < k_max : kv <= k_max) {
@@ -231,7 +262,8 @@ __global__ __launch_bounds__(256) void k_power(chomp_config cfg, TabLayout L,
                                                const Epoch* __restrict__ epochs,
                                                const double* __restrict__ tab, int which,
                                                int epoch0, const double* __restrict__ k,
-                                               size_t nk, double* __restrict__ out) {
+                                               size_t nk, double* __restrict__ out,
+                                               const double* __restrict__ delta_b) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   const int e = epoch0 + blockIdx.y;
@@ -239,6 +271,7 @@ __global__ __launch_bounds__(256) void k_power(chomp_config cfg, TabLayout L,
                kEpochDoubles);
   PowerEval P;
   P.stage(cfg, L, &E, tab + (size_t)e * L.stride, which, sm);
+  if (is_ssc(which & 15)) P.delta_b = delta_b[e];
   __syncthreads();
   P.template finish_t<BAO>();
   double* o = out + (size_t)blockIdx.y * nk;
@@ -264,10 +297,25 @@ __global__ __launch_bounds__(256) void k_power(chomp_config cfg, TabLayout L,
 template <bool BAO>
 __device__ __forceinline__ double power_lane(const chomp_config& cfg, const TabLayout& L,
                                              const Epoch& E, const double* t, int fa, int fb,
-                                             int fp, int w, bool extrap, double kv) {
+                                             int fp, int w, bool extrap, double kv,
+                                             double delta_b = 0.0) {
   if (w == CHOMP_P_LIN) return linear_power_t<BAO>(E, kv);
   const double x0 = log(cfg.k_min);
   const double dx = (log(cfg.k_max) - x0) / (double)(L.NK - 1);
+  if (is_ssc(w)) {                                        // halo.py:1136-1169 (fb: I_1^2)
+    if (kv < cfg.k_min) {                                 // P_mm's branch below, fb -> fa
+      if (w == CHOMP_P_SSC_RESPONSE) return 0.0;
+      const double c_lo = t[L.off_kpp[fa]] * t[L.off_kpp[fa]] +
+                          t[L.off_kpp[fp]] / linear_power_t<BAO>(E, cfg.k_min);
+      return linear_power_t<BAO>(E, kv) * c_lo;
+    }
+    if (!(kv <= cfg.k_max)) return 0.0;
+    const double lk = log(kv);
+    const double h = spline_eval_uniform(x0, dx, t + L.off_kpp[fa], L.NK, lk);
+    const double i12 = spline_eval_uniform(x0, dx, t + L.off_kpp[fb], L.NK, lk);
+    const double pp = spline_eval_uniform(x0, dx, t + L.off_kpp[fp], L.NK, lk);
+    return ssc_in_range(w, t[L.off_misc + 1] * power_shape_t<BAO>(E, lk, kv), h, i12, pp, delta_b);
+  }
   if (kv < cfg.k_min) {
     const double c_lo = t[L.off_kpp[fa]] * t[L.off_kpp[fb]] +
                         t[L.off_kpp[fp]] / linear_power_t<BAO>(E, cfg.k_min);
@@ -352,13 +400,15 @@ __device__ __forceinline__ void slow_list_append(int* slow, int parity, int k_gr
 // One wavefront's 128 k (two per lane) for the epochs [q_lo, q_hi) on the per-lane path: any
 // k, any knot interval, any order.  In-range k still re-use the Eisenstein-Hu shape across
 // epochs of one cosmology; k outside [k_min, k_max] take the full formula (halo.py:314-320).
-template <bool BAO>
+// SSC: w is one of the super-sample codes (a compile-time copy: P_mm's instances carry none of it).
+template <bool BAO, bool SSC = false>
 __device__ __forceinline__ void power_lanes_range(const chomp_config& cfg, const TabLayout& L,
                                                   const Epoch* __restrict__ epochs,
                                                   const double* __restrict__ tab, int w,
                                                   bool extrap, int epoch0, int q_lo, int q_hi,
                                                   const KLanes& s, size_t nk,
-                                                  double* __restrict__ out) {
+                                                  double* __restrict__ out,
+                                                  const double* __restrict__ delta_b = nullptr) {
   const PowerFam F = power_families(w);
   const int NK = L.NK;
   const double x0 = log(cfg.k_min);
@@ -372,6 +422,7 @@ __device__ __forceinline__ void power_lanes_range(const chomp_config& cfg, const
     double* o = out + (size_t)q * nk + s.i0;
     const bool same = q > q_lo && t[L.off_misc + 2] != 0.0;
     const double A = t[L.off_misc + 1];
+    const double db = SSC ? delta_b[e] : 0.0;
     if (!same && w != CHOMP_P_LIN) {
       sh0 = power_shape_t<BAO>(E, s.lk0, s.k0);
       sh1 = power_shape_t<BAO>(E, s.lk1, s.k1);
@@ -382,9 +433,9 @@ __device__ __forceinline__ void power_lanes_range(const chomp_config& cfg, const
         const double ha = pp_poly(t + L.off_kpp[F.fa], s.idx0, e0);
         const double hb = pp_poly(t + L.off_kpp[F.fb], s.idx0, e0);
         const double pp = pp_poly(t + L.off_kpp[F.fp], s.idx0, e0);
-        r = fma(A * sh0, ha * hb, pp);
+        r = SSC ? ssc_in_range(w, A * sh0, ha, hb, pp, db) : fma(A * sh0, ha * hb, pp);
       } else {
-        r = power_lane<BAO>(cfg, L, E, t, F.fa, F.fb, F.fp, w, extrap, s.k0);
+        r = power_lane<BAO>(cfg, L, E, t, F.fa, F.fb, F.fp, w, extrap, s.k0, db);
       }
       o[0] = r;
     }
@@ -394,9 +445,9 @@ __device__ __forceinline__ void power_lanes_range(const chomp_config& cfg, const
         const double ha = pp_poly(t + L.off_kpp[F.fa], s.idx1, e1);
         const double hb = pp_poly(t + L.off_kpp[F.fb], s.idx1, e1);
         const double pp = pp_poly(t + L.off_kpp[F.fp], s.idx1, e1);
-        r = fma(A * sh1, ha * hb, pp);
+        r = SSC ? ssc_in_range(w, A * sh1, ha, hb, pp, db) : fma(A * sh1, ha * hb, pp);
       } else {
-        r = power_lane<BAO>(cfg, L, E, t, F.fa, F.fb, F.fp, w, extrap, s.k1);
+        r = power_lane<BAO>(cfg, L, E, t, F.fa, F.fb, F.fp, w, extrap, s.k1, db);
       }
       o[1] = r;
     }
@@ -406,7 +457,7 @@ __device__ __forceinline__ void power_lanes_range(const chomp_config& cfg, const
 // The row-walking streaming pass (epochs of different cosmologies, or small grids).
 // grid (ceil(nk / 512), ceil(n_epoch / epochs_per_y)), block 256.  A wavefront whose k
 // do not qualify for the fast path only enters itself in the slow list.
-template <bool BAO>
+template <bool BAO, bool SSC = false>
 __global__ __launch_bounds__(256) void k_power_grid(chomp_config cfg, TabLayout L,
                                                     const Epoch* __restrict__ epochs,
                                                     const double* __restrict__ tab, int w,
@@ -415,7 +466,8 @@ __global__ __launch_bounds__(256) void k_power_grid(chomp_config cfg, TabLayout 
                                                     const double* __restrict__ k, size_t nk,
                                                     double* __restrict__ out,
                                                     int* __restrict__ slow, int parity,
-                                                    int inline_lanes, bool extrap) {
+                                                    int inline_lanes, bool extrap,
+                                                    const double* __restrict__ delta_b) {
   if (!inline_lanes) slow_list_begin(slow, parity);
   const int k_group = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
   const PowerFam F = power_families(w);
@@ -436,7 +488,8 @@ __global__ __launch_bounds__(256) void k_power_grid(chomp_config cfg, TabLayout 
   if (!fast) {
     if (inline_lanes) {            // small grids: this block's epochs on the per-lane path, here
       if ((size_t)k_group * 128 < nk)
-        power_lanes_range<BAO>(cfg, L, epochs, tab, w, extrap, epoch0, q_lo, q_hi, s, nk, out);
+        power_lanes_range<BAO, SSC>(cfg, L, epochs, tab, w, extrap, epoch0, q_lo, q_hi, s, nk, out,
+                                    delta_b);
     } else if ((threadIdx.x & 63) == 0 && blockIdx.y == 0 && (size_t)k_group * 128 < nk) {
       slow_list_append(slow, parity, k_group);
     }
@@ -504,8 +557,15 @@ __global__ __launch_bounds__(256) void k_power_grid(chomp_config cfg, TabLayout 
         pp1 = fma(fma(fma(P3, d1, P2), d1, P1), d1, P0);
       }
     }
-    const double r0 = fma(c.A * shape0, ha0 * hb0, pp0);
-    const double r1 = fma(c.A * shape1, ha1 * hb1, pp1);
+    double r0, r1;
+    if constexpr (SSC) {
+      const double db = delta_b[epoch0 + qc];
+      r0 = ssc_in_range(w, c.A * shape0, ha0, hb0, pp0, db);
+      r1 = ssc_in_range(w, c.A * shape1, ha1, hb1, pp1, db);
+    } else {
+      r0 = fma(c.A * shape0, ha0 * hb0, pp0);
+      r1 = fma(c.A * shape1, ha1 * hb1, pp1);
+    }
     double* o = out + (size_t)qc * nk + s.i0;
     // Streamed once, never re-read by this launch: 16-byte write-through (sc1) stores
     // (plain stores leave ~0.5 GB of dirty lines for the end-of-kernel release to
@@ -573,12 +633,13 @@ __global__ __launch_bounds__(256) void k_power_prep(chomp_config cfg, TabLayout 
 // row-major over the output.  nk even, out 16-byte aligned; winfo covers every k group
 // of the (padded) grid, groups past nk are marked slow.  n_epoch is a multiple of PER
 // (the host picks PER accordingly).
-template <int PER>
+template <int PER, bool SSC = false>
 __global__ __launch_bounds__(256) void k_power_stream(TabLayout L, const double* __restrict__ tab,
                                                       int w, int epoch0,
                                                       const double* __restrict__ ktab,
                                                       const int* __restrict__ winfo, size_t nk,
-                                                      double* __restrict__ out) {
+                                                      double* __restrict__ out,
+                                                      const double* __restrict__ delta_b) {
   const int k_group = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
   const int info = winfo[k_group];
   const size_t ti = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -595,11 +656,13 @@ __global__ __launch_bounds__(256) void k_power_stream(TabLayout L, const double*
   // the first use
   struct Row { double A, a0, a1, a2, a3, b0, b1, b2, b3, p0, p1, p2, p3; };
   Row r[PER];
+  double db[PER];
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const double* t = tab + (size_t)(epoch0 + q_lo + j) * L.stride;
     r[j] = Row{t[L.off_misc + 1], t[oa], t[oa + 1], t[oa + 2], t[oa + 3],
                t[ob], t[ob + 1], t[ob + 2], t[ob + 3], t[op], t[op + 1], t[op + 2], t[op + 3]};
+    db[j] = SSC ? delta_b[epoch0 + q_lo + j] : 0.0;
   }
   const double d0 = v.x, d1 = v.z;
   const bool s0 = v.y < 0.0, s1 = v.w < 0.0;
@@ -633,8 +696,14 @@ __global__ __launch_bounds__(256) void k_power_stream(TabLayout L, const double*
         pp1 = fma(fma(fma(P3, d1, P2), d1, P1), d1, P0);
       }
     }
-    const double r0 = fma(c.A * shape0, ha0 * hb0, pp0);
-    const double r1 = fma(c.A * shape1, ha1 * hb1, pp1);
+    double r0, r1;
+    if constexpr (SSC) {
+      r0 = ssc_in_range(w, c.A * shape0, ha0, hb0, pp0, db[j]);
+      r1 = ssc_in_range(w, c.A * shape1, ha1, hb1, pp1, db[j]);
+    } else {
+      r0 = fma(c.A * shape0, ha0 * hb0, pp0);
+      r1 = fma(c.A * shape1, ha1 * hb1, pp1);
+    }
     // write-through: the output is never re-read by this launch, and the k table must
     // stay in L2 next to it
     store_wt16(o, r0, r1);
@@ -652,12 +721,12 @@ __global__ __launch_bounds__(256) void k_power_stream(TabLayout L, const double*
 // (listed k group, chunk of epochs).  The chunk length adapts to the length of the list: few
 // listed groups -> short chunks over many wavefronts (the per-epoch coefficient loads of this
 // path are a dependent chain), a fully listed grid -> one item per group.
-template <bool BAO>
+template <bool BAO, bool SSC = false>
 __global__ __launch_bounds__(256) void k_power_grid_lanes(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs,
     const double* __restrict__ tab, int w, bool extrap, int epoch0, int n_epoch,
     const double* __restrict__ k, size_t nk, double* __restrict__ out,
-    const int* __restrict__ slow, int parity) {
+    const int* __restrict__ slow, int parity, const double* __restrict__ delta_b) {
   const int count = slow[parity];
   if (count == 0) return;
   const int NK = L.NK;
@@ -674,7 +743,8 @@ __global__ __launch_bounds__(256) void k_power_grid_lanes(
     int q_hi = q_lo + epochs_per_item;
     if (q_hi > n_epoch) q_hi = n_epoch;
     const KLanes s = load_k_lanes(cfg, NK, k, nk, (size_t)k_group * 64 + lane);
-    power_lanes_range<BAO>(cfg, L, epochs, tab, w, extrap, epoch0, q_lo, q_hi, s, nk, out);
+    power_lanes_range<BAO, SSC>(cfg, L, epochs, tab, w, extrap, epoch0, q_lo, q_hi, s, nk, out,
+                                delta_b);
   }
 }
 

@@ -20,7 +20,10 @@ from . import hod as hod_mod
 
 _WHICH = {"linear_power": (_lib.P_LIN, 0), "power_mm": (_lib.P_MM, _lib.FAM_MM),
           "power_gm": (_lib.P_GM, _lib.FAM_GM), "power_mg": (_lib.P_GM, _lib.FAM_GM),
-          "power_gg": (_lib.P_GG, _lib.FAM_GG)}
+          "power_gg": (_lib.P_GG, _lib.FAM_GG),
+          # HaloSuperSampleCovariance (halo.py:1136-1169): h_m, pp_mm and I_1^2 in one set-up
+          "dln_power_ddelta_b": (_lib.P_SSC_RESPONSE, _lib.FAM_SSC),
+          "power_mm_ssc": (_lib.P_MM_SSC, _lib.FAM_SSC)}
 
 
 def shard_indices(n, rank, world):
@@ -76,16 +79,27 @@ class HaloGrid(object):
         self._c_halo = self.ctx.pack_halo(self.halo, n) if n else None
         self._c_hod = self.ctx.pack_hod(self.hod, n) if n else None
         self._z = numpy.ascontiguousarray(self.z, dtype=numpy.float64)
+        self._delta_b = None          # per local epoch (power_mm_ssc); None: 0 everywhere
 
-    def set_parameters(self, cosmo=None, halo=None, hod=None):
+    def set_parameters(self, cosmo=None, halo=None, hod=None, delta_b=None):
         """New parameters for this rank's epochs, taking effect at the next setup(): the step of
         an MCMC / design loop.  Each argument: None (keep), one dict, a list with one dict per
         local epoch, or the packed ctypes array (Context.pack_*; cosmo also as a float64 array
-        [n_local, 10]) -- packing once outside the loop keeps the host out of the step."""
+        [n_local, 10]) -- packing once outside the loop keeps the host out of the step.
+        delta_b: HaloSuperSampleCovariance's delta_b (power_mm_ssc), a scalar or one value per
+        local epoch; it alone needs no new set-up."""
         import ctypes
         n = len(self.idx)
         if n == 0:
             return
+        if delta_b is not None:
+            db = numpy.ascontiguousarray(
+                numpy.broadcast_to(numpy.asarray(delta_b, dtype=numpy.float64), (n,)))
+            self._delta_b = db.copy()
+            if self._tables:             # (the set-up stands: install it now)
+                self.ctx.set_delta_b(self._delta_b, 0)
+            if cosmo is None and halo is None and hod is None:
+                return
         if cosmo is not None:
             self._c_cosmo = cosmo if isinstance(cosmo, ctypes.Array) else self.ctx.pack_cosmo(cosmo, n)
         if halo is not None:
@@ -105,6 +119,8 @@ class HaloGrid(object):
             return
         self.ctx.epochs_set(self._c_cosmo, self._z)
         self.ctx.stage_k(self._c_halo, self.kind, self._c_halo, self._c_hod, need)
+        if self._delta_b is not None:    # (chomp_epochs_set has reset every epoch's to 0)
+            self.ctx.set_delta_b(self._delta_b, 0)
         self._tables = need
 
     def status(self, warn=False):

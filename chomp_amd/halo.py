@@ -10,7 +10,10 @@ because they change the numbers a drop-in user gets:
   h_m / pp_mm flags are NOT reset (halo.py:220-235);
 * HaloFit fixes f_1..f_3 at construction and builds its sigma-spline once, at the
   first power_mm call; set_redshift()/set_cosmology() never refresh either
-  (halo.py:1254-1266, 1337-1338).
+  (halo.py:1254-1266, 1337-1338);
+* HaloSuperSampleCovariance builds its I_1^2 spline once: no setter resets
+  _initialized_i_1_2 (halo.py:135-235), and the class never extrapolates
+  (halo.py:1102-1108).
 """
 import numpy
 
@@ -133,7 +136,7 @@ class Halo(object):
         if new_mass:
             self._nbar_valid = False
         build = 0
-        for flag, bit in _FLAG_BITS:
+        for flag, bit in self._flag_bits:
             if (need_tables & bit) and not getattr(self, flag):
                 build |= bit
         if build or not self._nbar_valid:
@@ -148,7 +151,7 @@ class Halo(object):
                 self._mass_sig = msig
             else:
                 ctx.halo_setup(self._profile(), self.local_hod, tables)
-            for flag, bit in _FLAG_BITS:
+            for flag, bit in self._flag_bits:
                 if build & bit:
                     setattr(self, flag, True)
             self._nbar_valid = True
@@ -181,6 +184,7 @@ class Halo(object):
         return float(self._scalars()["delta_v"]) if dv == -1 else dv
 
     _exclusion = False          # HaloExclusion sets it: CHOMP_T_EXCLUSION on every build
+    _flag_bits = _FLAG_BITS     # (lazily built table, CHOMP_T_* bit) pairs of the class
 
     def _power_code(self, which):
         """CHOMP_P_* code of a spectrum of this object (extrapolation flag included)."""
@@ -408,6 +412,79 @@ class HaloExclusion(Halo):
                  mass_func=None, halo_dict=None, **kws):
         Halo.__init__(self, redshift, input_hod, cosmo_single_epoch,
                       mass_func, halo_dict, **kws)
+
+
+class HaloSuperSampleCovariance(Halo):
+    """The response of the halo-model matter spectrum to a long-wavelength background mode
+    delta_b, Takada & Hu 2013 (halo.py:1089-1199).  I_1^2 is the fourth knot table, built on the
+    device with h_m and pp_mm (CHOMP_FAM_SSC).  As in the reference, `extrapolate` is accepted
+    and dropped (halo.py:1102-1108), and no setter resets _initialized_i_1_2: after one, the
+    response combines fresh h_m, pp_mm and P_lin with the I_1^2 knots of the first build."""
+
+    _flag_bits = _FLAG_BITS + (("_initialized_i_1_2", _lib.T_I_1_2),)
+
+    def __init__(self, redshift=0.0, input_hod=None, cosmo_single_epoch=None,
+                 mass_func=None, halo_dict=None, extrapolate=False,
+                 delta_b=0.0, **kws):
+        Halo.__init__(self, redshift, input_hod, cosmo_single_epoch,
+                      mass_func, halo_dict, **kws)
+        self._delta_b = delta_b
+        self._initialized_i_1_2 = False
+        # knot tables (name -> knots) the device epoch must hold but does not: the I_1^2 knots
+        # across a rebuilt epoch, the tables init_from_halo copied; installed behind the next
+        # set-up (chomp_put_table needs the epoch's mass function)
+        self._knots_to_put = {}
+
+    @staticmethod
+    def init_from_halo(input_halo, delta_b=0.0):
+        """halo.py:1110-1134: a new object on the input's redshift, HOD, cosmology, mass
+        function and halo dictionary, with copies of the knot tables the input has built (as
+        they are, stale ones included)."""
+        halo_ssc = HaloSuperSampleCovariance(
+            input_halo.get_redshift(), input_halo.get_hod_object(),
+            input_halo.get_cosmology_object(), input_halo.get_mass(),
+            input_halo.get_halo(), input_halo.get_extrapolation(), delta_b)
+        for flag, bit in _FLAG_BITS:
+            if getattr(input_halo, flag) is True:
+                name = flag[len("_initialized_"):]
+                halo_ssc._knots_to_put[name] = input_halo._knots(name, bit)
+                setattr(halo_ssc, flag, True)
+        return halo_ssc
+
+    def _before_epochs_set(self):
+        # (the epoch about to be rebuilt holds the I_1^2 knots of the first build)
+        if (self._initialized_i_1_2 and "i_1_2" not in self._knots_to_put and
+                self._ctx is not None and self._epoch_sig is not None):
+            self._knots_to_put["i_1_2"] = self._ctx.table("i_1_2", 0)
+
+    def _sync(self, need_tables, defer_status=False):
+        ctx = Halo._sync(self, need_tables, defer_status)
+        if self._knots_to_put:           # (the epoch's mass function is set up by now)
+            for name, knots in self._knots_to_put.items():
+                ctx.put_table(name, knots, 0)
+            self._knots_to_put = {}
+        return ctx
+
+    def _power_code(self, which):
+        if which in (_lib.P_SSC_RESPONSE, _lib.P_MM_SSC):
+            return which
+        return Halo._power_code(self, which)
+
+    def dln_power_ddelta_b(self, k):
+        """halo.py:1136-1156: (68/21 h_m^2 P_lin + I_1^2) / P_mm inside [k_min, k_max],
+        exactly 0 outside."""
+        return self._power(_lib.P_SSC_RESPONSE, _lib.FAM_SSC, k)
+
+    def power_mm_ssc(self, k):
+        """halo.py:1158-1169: P_mm (1 + delta_b dlnP/ddelta_b)."""
+        # delta_b goes into the epoch as it stands after the set-up: chomp_epochs_set (a first
+        # call, a call after set_redshift / set_cosmology) resets every epoch's to 0
+        ctx = self._sync(_lib.FAM_SSC, defer_status=True)
+        ctx.set_delta_b([float(self._delta_b)], 0)
+        return self._power(_lib.P_MM_SSC, _lib.FAM_SSC, k)
+
+    def _i_1_2(self, k):
+        return self._ranged("i_1_2", _lib.T_I_1_2, k)
 
 
 class HaloFit(Halo):

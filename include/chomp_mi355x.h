@@ -77,18 +77,29 @@ typedef struct chomp_config {
 #define CHOMP_T_H_G 4u    /* Halo._initialize_h_g    halo.py:929-969   */
 #define CHOMP_T_PP_GM 8u  /* Halo._initialize_pp_gm  halo.py:1043-1086 */
 #define CHOMP_T_PP_GG 16u /* Halo._initialize_pp_gg  halo.py:996-1041  */
+/* HaloSuperSampleCovariance._initialize_i_1_2 (halo.py:1176-1199): I_1^2 = int dln nu
+ * nu f(nu) b(nu) y(k, M)^2 M / rho_bar over [nu_min, nu_max], the range of h_m / pp_mm. */
+#define CHOMP_T_I_1_2 32u
 /* OR-ed in: the object is a HaloExclusion (halo.py:1201-1233): h_m and h_g are built
  * with the halo-exclusion mass window in their integrands. */
 #define CHOMP_T_EXCLUSION 64u
 #define CHOMP_FAM_MM (CHOMP_T_H_M | CHOMP_T_PP_MM)               /* power_mm */
 #define CHOMP_FAM_GM (CHOMP_T_H_M | CHOMP_T_H_G | CHOMP_T_PP_GM) /* power_gm */
 #define CHOMP_FAM_GG (CHOMP_T_H_G | CHOMP_T_PP_GG)               /* power_gg */
+#define CHOMP_FAM_SSC (CHOMP_FAM_MM | CHOMP_T_I_1_2)               /* dln_power_ddelta_b */
 
 /* Power spectra served by chomp_power. */
 #define CHOMP_P_LIN 0 /* Halo.linear_power  halo.py:266-275 */
 #define CHOMP_P_MM 1  /* Halo.power_mm      halo.py:277-320 */
 #define CHOMP_P_GM 2  /* Halo.power_gm/mg   halo.py:322-389 */
 #define CHOMP_P_GG 3  /* Halo.power_gg      halo.py:391-439 */
+/* HaloSuperSampleCovariance (halo.py:1089-1199); need CHOMP_FAM_SSC, refuse HALOFIT and
+ * EXTRAPOLATE (the class never extrapolates, halo.py:1102-1108).  Inside [k_min, k_max]
+ * (inclusive) dlnP/ddelta_b = (68/21 h_m^2 P_lin + I_1^2) / P_mm, outside exactly 0
+ * (halo.py:1136-1156); P_mm_ssc = P_mm (1 + delta_b dlnP/ddelta_b) with the epoch's delta_b
+ * (chomp_set_delta_b): P_mm itself below k_min, 0 above k_max (halo.py:1158-1169). */
+#define CHOMP_P_SSC_RESPONSE 4 /* dln_power_ddelta_b halo.py:1136-1156 */
+#define CHOMP_P_MM_SSC 5       /* power_mm_ssc       halo.py:1158-1169 */
 #define CHOMP_P_HALOFIT 16 /* OR-ed in: HaloFit.power_* halo.py:1325-1413 */
 /* OR-ed in: Halo(extrapolate=True) -- above k_max P_mm continues as a rescaled linear
  * spectrum, P_gm / P_gg as power laws (halo.py:300-312, 341-367, 405-431); HaloFit
@@ -179,6 +190,10 @@ int chomp_power(chomp_ctx* ctx, int which, const double* k, size_t nk,
 /* Same for the epoch range [epoch0, epoch0 + n). */
 int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n,
                       const double* k, size_t nk, double* out, int mem);
+
+/* HaloSuperSampleCovariance._delta_b (halo.py:1104-1107) of epochs [epoch0, epoch0 + n): one
+ * value per epoch, read by CHOMP_P_MM_SSC.  chomp_epochs_set resets every epoch's to 0. */
+int chomp_set_delta_b(chomp_ctx* ctx, size_t epoch0, size_t n, const double* delta_b, int mem);
 
 /* Register a k grid (device memory, 16-byte aligned, even length) for repeated chomp_power /
  * chomp_power_range calls over the same cosmology: everything that depends on k alone -- ln k,
@@ -278,18 +293,19 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
  * MASS_SEARCH_EXHAUSTED: the walk did not end within 2047 steps (the reference loops on).
  * SIGMA_DIVMAX: a sigma(R) Romberg of the nu table exhausted divmax (scipy: AccuracyWarning).
  * HALO_DIVMAX_*: some knot of that table exhausted divmax (halo.py:909-915, 951-957, 976-982,
- *   1018-1024, 1065-1071; scipy returns the last row with an AccuracyWarning -- with the
+ *   1018-1024, 1065-1071, 1182-1189; scipy returns the last row with an AccuracyWarning -- with the
  *   default precision the discontinuous HOD integrands of pp_gm / pp_gg do this routinely).
  * NONFINITE: a knot table holds a NaN or an infinity. */
 #define CHOMP_ST_MASS_MIN_SATURATED 1u
 #define CHOMP_ST_MASS_MAX_SATURATED 2u
 #define CHOMP_ST_MASS_SEARCH_EXHAUSTED 4u
 #define CHOMP_ST_SIGMA_DIVMAX 8u
-#define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..4: H_M, PP_MM, H_G, PP_GM, PP_GG */
+#define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..5: H_M, PP_MM, H_G, PP_GM, PP_GG, I_1_2 */
 #define CHOMP_ST_HALO_DIVMAX_PP_MM 0x200u
 #define CHOMP_ST_HALO_DIVMAX_H_G 0x400u
 #define CHOMP_ST_HALO_DIVMAX_PP_GM 0x800u
 #define CHOMP_ST_HALO_DIVMAX_PP_GG 0x1000u
+#define CHOMP_ST_HALO_DIVMAX_I_1_2 0x2000u  /* halo.py:1182-1189 */
 #define CHOMP_ST_NONFINITE 0x10000u
 int chomp_get_status(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
 /* The same words without draining the stream.  chomp_status_post makes every epoch's word, as
@@ -366,8 +382,20 @@ int chomp_get_deep_stats(chomp_ctx* ctx, long long* out);
 #define CHOMP_TAB_PP_GG 6
 #define CHOMP_TAB_LEVELS 7  /* Romberg levels reached, 5 x halo_npoints, as doubles */
 #define CHOMP_TAB_HF_LN_SIGMA2 8 /* HaloFit._ln_sigma2_array [halo_npoints] */
+#define CHOMP_TAB_I_1_2 9   /* knots of HaloSuperSampleCovariance._i_1_2_spline [halo_npoints] */
+#define CHOMP_TAB_LEVELS_I_1_2 10 /* Romberg levels of the I_1^2 knots [halo_npoints], as doubles */
 int chomp_get_table(chomp_ctx* ctx, size_t epoch, int table, double* out,
                     size_t n);
+/* Install the knot values of one knot table (CHOMP_TAB_H_M .. CHOMP_TAB_PP_GG, CHOMP_TAB_I_1_2;
+ * n = halo_npoints, host buffer) for one epoch, rebuild its not-a-knot spline over ln k with the
+ * routine of the set-up and mark the table built: a get -> put round trip leaves every spectrum
+ * bit for bit as it was.  What a mirror of the reference's copied or stale splines needs once
+ * another object has set the epoch up again (halo.py:1116-1132: init_from_halo copies the
+ * input's splines; :135-235: no setter resets _initialized_i_1_2).  The table counts as built for
+ * THAT epoch only (until the next chomp_epochs_set): chomp_power refuses (CHOMP_ERR_STATE) a
+ * range with an epoch that neither a set-up nor a put has given the table.  Synchronises the
+ * host with the context's stream, so it is refused while the stream is being captured. */
+int chomp_put_table(chomp_ctx* ctx, size_t epoch, int table, const double* in, size_t n);
 
 /* ---- Projection: MultiEpoch, windows, kernel, correlation --------------------
  * One projection set-up per context. */
