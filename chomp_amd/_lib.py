@@ -109,6 +109,8 @@ EXPORTS = [
     "chomp_status_wait", "chomp_set_tuning",
     "chomp_get_deep_stats", "chomp_stage_k", "chomp_power_plan", "chomp_get_stream",
     "chomp_wtheta_cell", "chomp_stage_k_halofit", "chomp_set_delta_b", "chomp_put_table",
+    "chomp_kernel_ssc_setup", "chomp_kernel_ssc_raw", "chomp_kernel_ssc_eval",
+    "chomp_covariance_ssc",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
@@ -357,6 +359,12 @@ def lib():
         L.chomp_covariance_table.argtypes = [vp, i, sz, d, c_double_p, c_double_p,
                                              c_double_p, sz]
         L.chomp_covariance_gaussian.argtypes = [vp, d, d, d, d, vp, sz, vp, i]
+        L.chomp_kernel_ssc_setup.argtypes = [vp, d, d, d, c_double_p, c_double_p, sz, i,
+                                             c_double_p, c_double_p, c_double_p]
+        L.chomp_kernel_ssc_raw.argtypes = [vp, c_double_p, sz, c_double_p]
+        L.chomp_kernel_ssc_eval.argtypes = [vp, c_double_p, sz, c_double_p]
+        L.chomp_covariance_ssc.argtypes = [vp, sz, d, c_double_p, sz, c_double_p, c_double_p,
+                                           c_double_p]
         L.chomp_xi3d.argtypes = [vp, i, sz, d, d, vp, sz, vp, i]
         L.chomp_spline_eval.argtypes = [vp, c_double_p, c_double_p, sz, c_double_p, sz, i,
                                         c_double_p]
@@ -459,6 +467,7 @@ class Context(object):
         self._L.chomp_get_stream(self._h, ctypes.byref(sp))
         self.stream_ptr = sp.value or 0
         self.n_epoch = 0
+        self._proj_ssc = None            # the KernelCovariance whose kernel_ssc table is here
         self._plan_k = None
 
     # -- ordering against the caller's torch stream ------------------------------------
@@ -752,12 +761,14 @@ class Context(object):
     def kernel_setup(self, cosmo_dict, me_z_min, me_z_max, ktheta_min, ktheta_max,
                      wa, wb, bessel_order):
         c = cosmo_struct(cosmo_dict)
+        self._proj_ssc = None            # (a projection set-up drops the kernel_ssc table)
         self._check(self._L.chomp_kernel_setup(
             self._h, ctypes.byref(c), me_z_min, me_z_max, ktheta_min, ktheta_max,
             ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)))
 
     def multi_epoch_setup(self, cosmo_dict, z_min, z_max):
         c = cosmo_struct(cosmo_dict)
+        self._proj_ssc = None
         self._check(self._L.chomp_multi_epoch_setup(self._h, ctypes.byref(c),
                                                     float(z_min), float(z_max)))
 
@@ -873,6 +884,60 @@ class Context(object):
                 self._h, float(j0_limit), float(area), float(poisson_a), float(poisson_b),
                 ctypes.c_void_p(th.ctypes.data), ta.size, ctypes.c_void_p(out.ctypes.data),
                 HOST))
+        return out
+
+    def kernel_ssc_setup(self, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi, sigma2,
+                         with_table=True):
+        """Super-sample kernel of the context's windows.  Returns (info[3] = z_bar_NG,
+        chi(z_bar_NG), growth_factor(z_bar_NG); table and Romberg levels, each
+        [kernel_npoints, kernel_npoints], or None without the table)."""
+        n = self.config.kernel_npoints
+        x = numpy.ascontiguousarray(ln_chi, dtype=numpy.float64)
+        y = numpy.ascontiguousarray(sigma2, dtype=numpy.float64)
+        assert x.size == y.size
+        info = numpy.empty(3)
+        tab, lev = (numpy.empty((n, n)), numpy.empty((n, n))) if with_table else (None, None)
+        ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
+        self._check(self._L.chomp_kernel_ssc_setup(
+            self._h, float(ln_ktheta_min), float(ln_ktheta_max), float(j0_ssc_limit),
+            x.ctypes.data_as(c_double_p), y.ctypes.data_as(c_double_p), x.size,
+            int(bool(with_table)), ptr(info), ptr(tab), ptr(lev)))
+        return info, tab, (lev.astype(int) if with_table else None)
+
+    def _ssc_points(self, fn, a, b):
+        a = numpy.ascontiguousarray(a, dtype=numpy.float64).ravel()
+        b = numpy.ascontiguousarray(b, dtype=numpy.float64).ravel()
+        assert a.size == b.size
+        out = numpy.empty(a.size)
+        if a.size:
+            x = numpy.concatenate([a, b])
+            self._check(fn(self._h, x.ctypes.data_as(c_double_p), a.size,
+                           out.ctypes.data_as(c_double_p)))
+        return out
+
+    def kernel_ssc_raw(self, ln_ktheta_a, ln_ktheta_b):
+        return self._ssc_points(self._L.chomp_kernel_ssc_raw, ln_ktheta_a, ln_ktheta_b)
+
+    def kernel_ssc_eval(self, ln_ktheta_a, ln_ktheta_b):
+        return self._ssc_points(self._L.chomp_kernel_ssc_eval, ln_ktheta_a, ln_ktheta_b)
+
+    def covariance_ssc(self, epoch, area, theta_a, theta_b, knots=False):
+        """covariance_ssc for each pair; with knots=True also (k_b knots, Romberg levels),
+        each [n, kernel_npoints]."""
+        ta = numpy.ascontiguousarray(theta_a, dtype=numpy.float64).ravel()
+        tb = numpy.ascontiguousarray(theta_b, dtype=numpy.float64).ravel()
+        assert ta.size == tb.size
+        n, nk = ta.size, self.config.kernel_npoints
+        out = numpy.empty(n)
+        kn, lev = (numpy.empty((n, nk)), numpy.empty((n, nk))) if knots else (None, None)
+        if n:
+            th = numpy.concatenate([ta, tb])
+            ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
+            self._check(self._L.chomp_covariance_ssc(
+                self._h, epoch, float(area), th.ctypes.data_as(c_double_p), n,
+                out.ctypes.data_as(c_double_p), ptr(kn), ptr(lev)))
+        if knots:
+            return out, kn, lev.astype(int)
         return out
 
     def hod_stats(self, epoch0=0, n=None):

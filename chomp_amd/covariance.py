@@ -1,21 +1,25 @@
-"""covariance.Covariance for the Gaussian part of the w(theta) covariance
-(covariance.py:23-543, 778-793, 1085-1103), the consumer of P(k) and the windows that
+"""covariance.Covariance for the Gaussian and super-sample parts of the w(theta) covariance
+(covariance.py:23-543, 685-793, 1085-1103), the consumer of P(k) and the windows that
 SURVEY.md 8(f) ranks fourth.
 
 Accelerated: ``Covariance(corr, corr, nongaussian_cov=False)`` -- the use of
 examples/example_covariance_script.py: the projected spectrum over ln K
 (``_initialize_halo_splines``), ``covariance_G`` for every pair of bins in one launch,
-the Poisson term, ``get_covariance`` and ``write``.  Outside the scope (ChompScopeError):
-the trispectrum terms (``nongaussian_cov=True``, ``ssc_cov=True``: halo_trispectrum.py,
-perturbation_spectra.py), ``CovarianceMulti`` and ``CovarianceFourier``.  Two different
-correlation objects cannot be given to the reference's Covariance either (its constructor
-raises ValueError comparing them), so that branch is not built.
+the Poisson term, ``get_covariance`` and ``write`` -- and with ``ssc_cov=True`` the
+super-sample term on HaloSuperSampleCovariance copies of the halo:
+``KernelCovariance.kernel_ssc`` (kernel.py:961-972, 1113-1231) and ``covariance_ssc`` for every
+pair of bins in one call.  Outside the scope (ChompScopeError): the trispectrum term
+(``nongaussian_cov=True``: halo_trispectrum.py, perturbation_spectra.py), ``CovarianceMulti``
+and ``CovarianceFourier``.  Two different correlation objects cannot be given to the
+reference's Covariance either (its constructor raises ValueError comparing them), so that
+branch is not built.
 """
 import numpy
 from scipy import special
 
 from . import _lib
 from . import defaults
+from . import halo as halo_mod
 from . import kernel as kernel_mod
 from .correlation import _POWER
 
@@ -36,9 +40,13 @@ class AnnulusBin(object):
 
 
 class KernelCovariance(object):
-    """The part of kernel.KernelCovariance (kernel.py:864-960) the Gaussian term uses:
-    the four windows, the MultiEpoch and the common redshift / distance range.  Its own
-    kernels (kernel_NG, kernel_ssc) belong to the trispectrum terms."""
+    """kernel.KernelCovariance (kernel.py:864-1231): the four windows, the MultiEpoch, the
+    common redshift / distance range and the super-sample kernel ``kernel_ssc``.  The
+    trispectrum kernel (kernel / kernel_NG / raw_kernel / raw_kernel_NG) is outside the scope.
+
+    kernel_ssc is built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over --
+    on the device context of ``_ssc_context`` (Covariance points it at its halo copy's, so
+    the response and the table meet there) or else on a context of its own."""
 
     def __init__(self, ktheta_min, ktheta_max, window_function_a1, window_function_a2,
                  window_function_b1, window_function_b2, cosmo_multi_epoch,
@@ -55,16 +63,115 @@ class KernelCovariance(object):
         self.z_min = numpy.max([w.z_min for w in ws])
         self.z_max = numpy.min([w.z_max for w in ws])
         self.cosmo = cosmo_multi_epoch
+        npts = defaults.default_precision["kernel_npoints"]
+        self._ln_ktheta_array = numpy.linspace(self.ln_ktheta_min, self.ln_ktheta_max, npts)
+        bessel = defaults.default_precision["kernel_bessel_limit"]
+        self._j0_limit = special.jn_zeros(0, bessel)[-1]
+        self._j0_ssc_limit = special.jn_zeros(0, int(bessel * 8))[-1]        # kernel.py:949-952
+        self._j1_limit = special.jn_zeros(1, bessel)[-1]
+        self._proj_kernel = None     # the Kernel whose projection tables carry the windows
+        self._ssc_context = None     # callable -> device context of the table
+        self._ssc_key = None
+        self._ssc_table = False
 
     def get_cosmology(self):
         return self.cosmo.get_cosmology()
 
     def kernel(self, ln_ktheta_a, ln_ktheta_b):
         raise _lib.ChompScopeError(
-            "KernelCovariance.kernel_NG / kernel_ssc (kernel.py:987-1111) serve the "
-            "trispectrum terms: outside the accelerated scope")
+            "KernelCovariance.kernel / kernel_NG (kernel.py:978-1056) serve the trispectrum "
+            "term: outside the accelerated scope")
 
-    kernel_NG = raw_kernel = raw_kernel_NG = kernel_ssc = kernel
+    kernel_NG = raw_kernel = raw_kernel_NG = kernel
+
+    # -- the super-sample kernel ------------------------------------------------------
+    def _ssc(self, table=True):
+        """The device state of kernel_ssc, (re)built when the windows, the cosmology or the
+        context changed: z_bar_NG and the sigma^2 knots, and with `table` the 1275 integrals
+        and the bicubic (built only once something asks for them)."""
+        if not (self.window_function_a1 is self.window_function_b1 and
+                self.window_function_a2 is self.window_function_b2):
+            raise _lib.ChompScopeError(
+                "kernel_ssc is accelerated for a1 = b1 and a2 = b2 (Covariance(corr, corr))")
+        kern = self._proj_kernel
+        if kern is None:
+            kern = self._proj_kernel = kernel_mod.Kernel(
+                numpy.exp(self.ln_ktheta_min), numpy.exp(self.ln_ktheta_max),
+                self.window_function_a1, self.window_function_a2, self.cosmo)
+        ctx = self._ssc_context() if self._ssc_context is not None else kern._dev()
+        kern._setup_on(ctx)
+        key = (id(ctx), kern._signature(), self.ln_ktheta_min, self.ln_ktheta_max,
+               ctx.config.kernel_npoints)
+        fresh = key == self._ssc_key and ctx._proj_ssc is self
+        if not fresh or (table and not self._ssc_table):
+            info = ctx.kernel_info()
+            d = self.__dict__
+            d["_ssc_chi_min"], d["_ssc_chi_max"] = float(info["chi_min"]), float(info["chi_max"])
+            # kernel.py:1208-1222: sigma_r(chi, 0.0)^2 on logspace(chi_min, chi_max)
+            chi = numpy.logspace(numpy.log10(d["_ssc_chi_min"]), numpy.log10(d["_ssc_chi_max"]),
+                                 defaults.default_precision["corr_npoints"])
+            sigma = self.cosmo.sigma_r(chi, 0.0)
+            d["_ssc_ln_chi"] = numpy.log(chi)
+            d["_ssc_sigma2"] = sigma * sigma
+            out, d["_ssc_array"], d["_ssc_levels"] = ctx.kernel_ssc_setup(
+                self.ln_ktheta_min, self.ln_ktheta_max, self._j0_ssc_limit,
+                d["_ssc_ln_chi"], d["_ssc_sigma2"], with_table=table)
+            d["_ssc_z_bar_NG"], _, d["_ssc_D_z_NG"] = (float(v) for v in out)
+            self._ssc_key = key
+            self._ssc_table = table
+            ctx._proj_ssc = self
+        return ctx
+
+    def _ssc_value(name, table=False):
+        def get(self):
+            self._ssc(table)
+            return self.__dict__["_ssc_" + name]
+        return property(get)
+
+    # (the reference sets these at construction, kernel.py:918-932, 961-972; here they come
+    #  with the first that is asked for -- the scalars without the table, kernel.py:1132-1153)
+    z_bar_NG = _ssc_value("z_bar_NG")
+    chi_min = _ssc_value("chi_min")
+    chi_max = _ssc_value("chi_max")
+    _sigma2_ln_chi = _ssc_value("ln_chi")
+    _sigma2_knots = _ssc_value("sigma2")
+    _D_z_NG = _ssc_value("D_z_NG")
+    _kernel_ssc_array = _ssc_value("array", True)
+    _kernel_ssc_levels = _ssc_value("levels", True)
+    del _ssc_value
+
+    def _sigma2(self, chi):
+        """kernel.py:1224-1231."""
+        ctx = self._ssc(table=False)
+        c = numpy.asarray(chi, dtype=numpy.float64)
+        with numpy.errstate(invalid="ignore", divide="ignore"):
+            s = ctx.spline_eval(self._sigma2_ln_chi, self._sigma2_knots,
+                                numpy.log(numpy.atleast_1d(c)).ravel())
+        out = numpy.where((c.ravel() >= self.chi_min) & (c.ravel() <= self.chi_max), s, 0.0)
+        return out.reshape(c.shape)
+
+    def raw_kernel_ssc(self, ln_ktheta_a, ln_ktheta_b):
+        """kernel.py:1155-1206, quirks included: the Romberg over [ln chi_min, ln chi_max']
+        hands ln chi to the integrand as chi, and the norm takes ln(k theta_a) for k theta_a."""
+        ctx = self._ssc(table=False)
+        a, b = numpy.broadcast_arrays(numpy.asarray(ln_ktheta_a, dtype=numpy.float64),
+                                      numpy.asarray(ln_ktheta_b, dtype=numpy.float64))
+        out = ctx.kernel_ssc_raw(a.ravel(), b.ravel())
+        return float(out[0]) if a.ndim == 0 else out.reshape(a.shape)
+
+    def kernel_ssc(self, ln_ktheta_a, ln_ktheta_b):
+        """kernel.py:1113-1130: RectBivariateSpline's grid-shaped result, [len a, len b]
+        (callers index [0]); ln(k theta) <= min is clamped to min, above max gives 0."""
+        ctx = self._ssc()
+        a = numpy.asarray(ln_ktheta_a, dtype=numpy.float64)
+        b = numpy.asarray(ln_ktheta_b, dtype=numpy.float64)
+        a = numpy.where(a <= self.ln_ktheta_min, self.ln_ktheta_min, a)
+        b = numpy.where(b <= self.ln_ktheta_min, self.ln_ktheta_min, b)
+        inside = numpy.logical_and(a <= self.ln_ktheta_max, b <= self.ln_ktheta_max)
+        ga, gb = numpy.meshgrid(numpy.atleast_1d(a).ravel(), numpy.atleast_1d(b).ravel(),
+                                indexing="ij")
+        grid = ctx.kernel_ssc_eval(ga.ravel(), gb.ravel()).reshape(ga.shape)
+        return numpy.where(inside, grid, 0.0)
 
 
 class Covariance(object):
@@ -75,11 +182,10 @@ class Covariance(object):
                  n_a=1.0e4, n_b=1.0e4, variance=1.0, nongaussian_cov=True,
                  input_halo_trispectrum=None, power_spec='power_mm',
                  poisson_noise_only=False, ssc_cov=False, **kws):
-        if nongaussian_cov or ssc_cov or input_halo_trispectrum is not None:
+        if nongaussian_cov or input_halo_trispectrum is not None:
             raise _lib.ChompScopeError(
-                "the trispectrum terms of the covariance (covariance_NG, covariance_ssc; "
-                "halo_trispectrum.py) are outside the accelerated scope: pass "
-                "nongaussian_cov=False, ssc_cov=False")
+                "the trispectrum term of the covariance (covariance_NG; halo_trispectrum.py) "
+                "is outside the accelerated scope: pass nongaussian_cov=False")
         if input_correlation_a is not input_correlation_b:
             # The reference cannot get here either: covariance.py:60 compares the two
             # correlations with Correlation.__eq__ (correlation.py:119-131), which compares
@@ -118,7 +224,7 @@ class Covariance(object):
         except (TypeError, IndexError):
             self.n_b1 = self.n_b2 = n_b
         self.nongaussian_cov = False
-        self.ssc_cov = False
+        self.ssc_cov = bool(ssc_cov)
         self.poisson_noise_only = poisson_noise_only
 
         kern = input_correlation_a.kernel
@@ -139,8 +245,20 @@ class Covariance(object):
         self.variance = variance
         self.cosmic_shear = self._identify_cosmic_shear()
 
-        self.halo_a = input_correlation_a.halo
-        self.halo_b = input_correlation_b.halo
+        # covariance.py:144-151: with ssc_cov the halo objects are HaloSuperSampleCovariance
+        # copies made now, with whatever tables the correlation's halo has built by now; the
+        # Gaussian term is then projected from halo_a, not from the correlation's halo
+        if self.ssc_cov:
+            self.halo_a = halo_mod.HaloSuperSampleCovariance.init_from_halo(
+                input_correlation_a.halo)
+            self.halo_b = halo_mod.HaloSuperSampleCovariance.init_from_halo(
+                input_correlation_b.halo)
+        else:
+            self.halo_a = input_correlation_a.halo
+            self.halo_b = input_correlation_b.halo
+        # kernel_ssc lives in halo_a's context, beside the response it is integrated with
+        self.kernel._proj_kernel = kern
+        self.kernel._ssc_context = lambda: self.halo_a._context()
         self._initialized_halo_splines = False
         self._table_key = None
         self._ln_k_min = numpy.log(defaults.default_limits['k_min'])
@@ -163,10 +281,24 @@ class Covariance(object):
                 shear[0] * shear[3] or shear[1] * shear[2]]
 
     # -- device tables -----------------------------------------------------------
+    def _prepare_copy(self):
+        """Correlation._prepare on halo_a (ssc_cov): the windows' tables go into the copy's
+        context, and the copy is moved to z_bar as _initialize_halo_splines does (:460-461)."""
+        z_bar = self.corr_a.kernel.z_bar
+        self.halo_a.set_redshift(z_bar)
+        self.halo_b.set_redshift(z_bar)
+        code, need = _POWER[self.power_spec]
+        self.corr_a.kernel._setup_on(self.halo_a._context())
+        return self.halo_a._sync(need), self.halo_a._power_code(code)
+
     def _table(self):
-        """Projected spectrum over ln K in the correlation's device context
-        (covariance.py:455-543); rebuilt when anything it was built from has changed."""
-        ctx, code = self.corr_a._prepare(self.power_spec)
+        """Projected spectrum over ln K in the device context of the correlation, or of
+        halo_a with ssc_cov (covariance.py:455-543); rebuilt when anything it was built from
+        has changed."""
+        if self.ssc_cov:
+            ctx, code = self._prepare_copy()
+        else:
+            ctx, code = self.corr_a._prepare(self.power_spec)
         h = self.halo_a
         hod = h.get_hod_object()
         key = (id(ctx), self.corr_a.kernel._signature(), code, h._epoch_sig, h._mass_sig,
@@ -195,6 +327,15 @@ class Covariance(object):
     _projected_halo_b = _projected_halo_a
 
     def set_cosmology(self, cosmo_dict):
+        if self.ssc_cov:
+            # The reference ends in AttributeError here whatever ssc_cov is
+            # (HaloTrispectrumOneHalo.set_cosmology dereferences pert=None); with ssc_cov it
+            # would also have left halo_a the plain halo and kept the old kernel_ssc spline.
+            raise _lib.ChompScopeError(
+                "Covariance.set_cosmology with ssc_cov=True: the reference raises "
+                "AttributeError (covariance.py:262-270, halo_trispectrum.py) and would keep the "
+                "HaloSuperSampleCovariance copies and the kernel_ssc spline of the old cosmology; "
+                "build a new Covariance instead")
         self.corr_a.set_cosmology(cosmo_dict)
         self.halo_a = self.halo_b = self.corr_a.halo
         self._initialized_halo_splines = False
@@ -203,14 +344,23 @@ class Covariance(object):
         return self.kernel.get_cosmology()
 
     # -- covariance --------------------------------------------------------------
+    @property
+    def D_z_NG(self):
+        """covariance.py:143: MultiEpoch.growth_factor(z_bar_NG)."""
+        self.kernel._ssc(table=False)
+        return self.kernel._D_z_NG
+
     def get_covariance(self):
-        """covariance.py:297-317; the Gaussian term of all bin pairs is one launch."""
+        """covariance.py:297-317; the Gaussian term of all bin pairs is one launch, the
+        super-sample term one call."""
         nb = len(self.annular_bins)
         self.covar = numpy.zeros((nb, nb))
         iu = numpy.triu_indices(nb)
         centers = numpy.array([b.center for b in self.annular_bins])
         if not self.poisson_noise_only and nb:
             vals = self._covariance_G_pairs(centers[iu[0]], centers[iu[1]])
+            if self.ssc_cov:
+                vals = vals + self._covariance_ssc_pairs(centers[iu[0]], centers[iu[1]])
             self.covar[iu] = vals
             self.covar[(iu[1], iu[0])] = vals
         for i, b in enumerate(self.annular_bins):
@@ -224,8 +374,11 @@ class Covariance(object):
             cov_P = self.covariance_P(annular_bin_a.delta, annular_bin_a.center)
         if self.poisson_noise_only:
             return cov_P
-        return self.covariance_G(annular_bin_a.center, annular_bin_b.center,
-                                 annular_bin_a.delta, annular_bin_b.delta) + cov_P
+        res = self.covariance_G(annular_bin_a.center, annular_bin_b.center,
+                                annular_bin_a.delta, annular_bin_b.delta)
+        if self.ssc_cov:
+            res += self.covariance_ssc(annular_bin_a.center, annular_bin_b.center)
+        return res + cov_P
 
     def covariance_P(self, delta, theta, window_1=0, window_2=1):
         """covariance.py:338-359."""
@@ -259,7 +412,23 @@ class Covariance(object):
         raise _lib.ChompScopeError("covariance_NG (halo trispectrum) is outside the "
                                    "accelerated scope")
 
-    covariance_ssc = covariance_NG
+    def _covariance_ssc_pairs(self, theta_a, theta_b, knots=False):
+        if not hasattr(self.halo_a, "dln_power_ddelta_b"):
+            # covariance.py:772: the reference's integrand asks halo_a for it
+            raise AttributeError("'%s' object has no attribute 'dln_power_ddelta_b'"
+                                 % type(self.halo_a).__name__)
+        ctx = self.kernel._ssc()
+        self.halo_a._sync(_lib.FAM_SSC)
+        return ctx.covariance_ssc(0, self.area, theta_a, theta_b, knots)
+
+    def covariance_ssc(self, theta_a_rad, theta_b_rad):
+        """covariance.py:685-776: for each k_a knot a Romberg over ln k_b of
+        k_b^2 R(k_a) R(k_b) kernel_ssc(ln k_a theta_a, ln k_b theta_b), R = halo_a's
+        dln_power_ddelta_b; their spline, and the Romberg over ln k_a / (4 pi^2 area)."""
+        ta, tb = numpy.broadcast_arrays(numpy.asarray(theta_a_rad, dtype=numpy.float64),
+                                        numpy.asarray(theta_b_rad, dtype=numpy.float64))
+        out = self._covariance_ssc_pairs(ta.ravel(), tb.ravel())
+        return float(out[0]) if ta.ndim == 0 else out.reshape(ta.shape)
 
     def write(self, file_name):
         """covariance.py:778-793."""

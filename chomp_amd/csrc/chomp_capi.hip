@@ -21,6 +21,7 @@
 #include "../../include/chomp_mi355x.h"
 #include "chomp_power_kernels.h"
 #include "chomp_proj_kernels.h"
+#include "chomp_cov_kernels.h"
 #include "chomp_probe_kernel.h"
 
 using namespace chomp;

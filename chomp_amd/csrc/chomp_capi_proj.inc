@@ -149,6 +149,8 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
   P.ready = false;
   P.me_ready = false;
   P.cov_ready = false;
+  P.ssc_ready = false;
+  P.ssc_prep = false;
   P.L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
   // tabulated redshift distributions ride behind the projection tables
   size_t pp_doubles[2] = {0, 0};
@@ -252,6 +254,8 @@ int chomp_multi_epoch_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double z_m
   P.ready = false;
   P.me_ready = false;
   P.cov_ready = false;
+  P.ssc_ready = false;
+  P.ssc_prep = false;
   P.L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
   if (!P.d_pd) HIPCHK(hipMalloc(&P.d_pd, sizeof(ProjDev)));
   if (!P.d_pd_init) HIPCHK(hipMalloc(&P.d_pd_init, sizeof(ProjDev)));
@@ -698,5 +702,162 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area, doub
     HIPCHK(hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
+  return CHOMP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Super-sample covariance of w(theta) (chomp_cov_kernels.h)
+// ---------------------------------------------------------------------------
+static int ssc_stage_pairs(chomp_ctx* ctx, const double* theta, size_t n, const char* who) {
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!(theta[i] > 0.0))
+      return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": arguments must be positive");
+  const int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, theta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  return CHOMP_OK;
+}
+
+int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
+                           double j0_ssc_limit, const double* ln_chi, const double* sigma2,
+                           size_t n_sigma, int with_table, double* info, double* table,
+                           double* levels) {
+  if (!ctx || !ln_chi || !sigma2) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: bad args");
+  if (!with_table && (table || levels))
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: table / levels need with_table");
+  if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "kernel_ssc_setup before kernel_setup");
+  if (!(ln_ktheta_max > ln_ktheta_min) || !(j0_ssc_limit > 0.0))
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: ln(k theta) range / J0 limit");
+  const int N = ctx->proj.L.NKT;
+  if (n_sigma < 4 || n_sigma > 256 || N < 4 || N > 256)
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: corr_npoints and kernel_npoints must be "
+                                    "4..256");
+  for (size_t i = 1; i < n_sigma; ++i)
+    if (!(ln_chi[i] > ln_chi[i - 1]))
+      return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: ln chi knots must increase");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const ProjLayout& L = P.L;
+  const SscLayout S = make_ssc_layout(N, (int)n_sigma);
+  P.ssc_ready = false;
+  P.ssc_prep = false;
+  { const int rce = ensure(ctx, &P.d_ssc, &P.cap_ssc, (size_t)S.total); if (rce) return rce; }
+  HIPCHK(hipMemcpyAsync(P.d_ssc + S.sx, ln_chi, n_sigma * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  HIPCHK(hipMemcpyAsync(P.d_ssc + S.sy, sigma2, n_sigma * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  hipLaunchKernelGGL(k_ssc_prep, dim3(1), dim3(256), 0, ctx->stream, ctx->cfg, L, S, P.d_pd,
+                     P.d_tab, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, P.d_ssc);
+  if (with_table) {
+    const size_t sh = (size_t)(ProjLds::doubles(L) + 5 * S.NS - 4) * sizeof(double);
+    hipLaunchKernelGGL(k_ssc_table, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh, ctx->stream,
+                       ctx->cfg, L, S, P.d_pd, P.d_tab, ctx->d_j0, P.d_ssc, (const double*)nullptr,
+                       (const double*)nullptr, (double*)nullptr);
+    hipLaunchKernelGGL(k_ssc_bicubic, dim3(1), dim3(256), 0, ctx->stream, S, P.d_ssc);
+  }
+  HIPCHK(hipGetLastError());
+  P.ssc_ns = (int)n_sigma;
+  P.ssc_prep = true;
+  P.ssc_ready = with_table != 0;
+  if (info || table || levels) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (info) HIPCHK(hipMemcpy(info, P.d_ssc + S.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t b = (size_t)N * N * sizeof(double);
+    if (table) HIPCHK(hipMemcpy(table, P.d_ssc + S.tab, b, hipMemcpyDeviceToHost));
+    if (levels) HIPCHK(hipMemcpy(levels, P.d_ssc + S.lev, b, hipMemcpyDeviceToHost));
+  }
+  return CHOMP_OK;
+}
+
+int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
+  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_raw: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ssc_prep)
+    return fail(ctx, CHOMP_ERR_STATE, "kernel_ssc_raw before kernel_ssc_setup");
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!std::isfinite(ln_ktheta[i])) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_raw: ln(k theta) must be finite");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
+  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
+  if (rc) return rc;
+  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, ln_ktheta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  const size_t sh = (size_t)(ProjLds::doubles(P.L) + 5 * S.NS - 4) * sizeof(double);
+  hipLaunchKernelGGL(k_ssc_table, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, P.L, S,
+                     P.d_pd, P.d_tab, ctx->d_j0, P.d_ssc, ctx->d_stage_in, ctx->d_stage_in + n,
+                     ctx->d_stage_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return CHOMP_OK;
+}
+
+int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
+  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_eval: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ssc_ready)
+    return fail(ctx, CHOMP_ERR_STATE, "kernel_ssc_eval before kernel_ssc_setup");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
+  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
+  if (rc) return rc;
+  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, ln_ktheta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  unsigned gx = (unsigned)((n + 255) / 256);
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(k_ssc_eval, dim3(gx), dim3(256), 0, ctx->stream, S, P.d_ssc, ctx->d_stage_in,
+                     ctx->d_stage_in + n, (int)n, ctx->d_stage_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return CHOMP_OK;
+}
+
+int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double* theta,
+                         size_t n, double* out, double* kb_knots, double* kb_levels) {
+  if (!ctx || !theta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ssc_ready)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc before kernel_ssc_setup");
+  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: area must be positive");
+  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: at most 65535 pairs a call");
+  int rc = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch, 1, true);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
+  const int NK = ctx->cfg.kernel_npoints;
+  rc = ssc_stage_pairs(ctx, theta, n, "covariance_ssc");
+  if (rc) return rc;
+  // out | knots | levels
+  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n * (1 + 2 * (size_t)NK));
+  if (rc) return rc;
+  double* d_out = ctx->d_stage_out;
+  double* d_knots = d_out + n;
+  double* d_lev = d_knots + n * (size_t)NK;
+  const size_t sh = (size_t)ssc_kb_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_ssc_kb<BAO>, dim3((unsigned)NK, (unsigned)n), dim3(256), sh, ctx->stream,
+                       ctx->cfg, ctx->L, S, ctx->d_epochs, (int)epoch, ctx->d_tab, P.d_ssc,
+                       ctx->d_stage_in, ctx->d_stage_in + n, d_knots, d_lev);
+  });
+  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
+                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
+                     ctx->stream, ctx->cfg, area, d_knots, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (kb_knots)
+    HIPCHK(hipMemcpyAsync(kb_knots, d_knots, n * NK * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (kb_levels)
+    HIPCHK(hipMemcpyAsync(kb_levels, d_lev, n * NK * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return CHOMP_OK;
 }

@@ -92,12 +92,22 @@ struct ProjState {
   size_t pp_total = 0;     // doubles of tabulated redshift distributions behind the tables
   bool cov_ready = false;  // covariance table (chomp_covariance_table) valid
   double* d_cov = nullptr;
+  bool ssc_prep = false;   // sigma^2 spline and z_bar_NG (chomp_kernel_ssc_setup) valid
+  bool ssc_ready = false;  // ... and the kernel_ssc table with its bicubic
+  int ssc_ns = 0;          // sigma^2 knots of that set-up
+  double* d_ssc = nullptr;
+  size_t cap_ssc = 0;      // doubles allocated at d_ssc
 };
 inline void proj_free(ProjState& p) {
   if (p.d_pd) (void)hipFree(p.d_pd);
   if (p.d_pd_init) (void)hipFree(p.d_pd_init);
   if (p.d_tab) (void)hipFree(p.d_tab);
   if (p.d_cov) (void)hipFree(p.d_cov);
+  if (p.d_ssc) (void)hipFree(p.d_ssc);
+  p.d_ssc = nullptr;
+  p.cap_ssc = 0;
+  p.ssc_ready = false;
+  p.ssc_prep = false;
   p.d_pd = nullptr;
   p.d_pd_init = nullptr;
   p.d_tab = nullptr;

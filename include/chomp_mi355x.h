@@ -527,6 +527,40 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area,
                               double poisson_a, double poisson_b,
                               const double* theta, size_t n, double* out, int mem);
 
+/* Super-sample covariance of w(theta), Covariance(corr, corr, nongaussian_cov=False,
+ * ssc_cov=True), with a1 = b1 = window a and a2 = b2 = window b of the context's
+ * kernel_setup.  Host memory throughout.
+ *
+ * chomp_kernel_ssc_setup replaces KernelCovariance._find_z_bar (kernel.py:961-972),
+ * _initialize_sigma2_spline (:1208-1222) and _initialize_ssc_spline (:1132-1153).  The
+ * sigma^2 knots (ln chi[n_sigma], sigma2[n_sigma]: MultiEpoch.sigma_r(chi, 0)^2 on
+ * logspace(log10 chi_min, log10 chi_max, corr_npoints)) get their not-a-knot spline; the
+ * kernel_npoints x kernel_npoints table of raw_kernel_ssc over linspace(ln_ktheta_min,
+ * ln_ktheta_max, kernel_npoints) is integrated (upper triangle, mirrored) with the J0 limit
+ * j0_ssc_limit (kernel.py:951-952) and fitted with the tensor-product bicubic of
+ * RectBivariateSpline(s=0).  with_table = 0 stops after the sigma^2 spline and z_bar_NG (what
+ * chomp_kernel_ssc_raw needs); the table, its bicubic and the other two calls need 1.
+ * info[3] (z_bar_NG, chi(z_bar_NG), growth_factor(z_bar_NG)), table and levels (each
+ * [kernel_npoints^2], row-major in ln(k theta_a); with_table only) may be NULL.
+ *
+ * chomp_kernel_ssc_raw replaces raw_kernel_ssc (kernel.py:1155-1206) and
+ * chomp_kernel_ssc_eval kernel_ssc (:1113-1130) at n points: ln_ktheta holds ln(k theta_a)[n]
+ * then ln(k theta_b)[n].
+ *
+ * chomp_covariance_ssc replaces Covariance.covariance_ssc (covariance.py:685-776) for n pairs
+ * of bin centres: theta holds theta_a[n] then theta_b[n] (radians); the response
+ * dlnP_mm/ddelta_b is that of halo epoch `epoch` (HaloSuperSampleCovariance's tables).  area
+ * is in steradians.  kb_knots / kb_levels ([n * kernel_npoints], may be NULL) receive each
+ * pair's k_b integrals at the k_a knots and their Romberg levels. */
+int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
+                           double j0_ssc_limit, const double* ln_chi, const double* sigma2,
+                           size_t n_sigma, int with_table, double* info, double* table,
+                           double* levels);
+int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out);
+int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out);
+int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double* theta,
+                         size_t n, double* out, double* kb_knots, double* kb_levels);
+
 /* CorrelationFourier.correlation(l) (correlation.py:360-392): Limber C_l. */
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z,
                const double* ell, size_t n, double* out, int mem);
