@@ -1477,14 +1477,15 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
   if ((which & CHOMP_P_HALOFIT) == 0 &&
       (reinterpret_cast<uintptr_t>(dk) % 16 == 0) && (reinterpret_cast<uintptr_t>(dout) % 16 == 0)) {
     const unsigned gx = (unsigned)((nk + 511) / 512);
-    bool one_cosmology = true, streaming = true, lanes_needed = true;
+    bool one_cosmology = true;
     for (size_t i = 1; i < n; ++i) one_cosmology &= ctx->slot[epoch0 + i] == ctx->slot[epoch0];
     const int w = which & 15;
     size_t stream_min = (size_t)1 << 22;           // samples; below this the launches dominate
     // (chomp_set_tuning: the tests force either launch shape on small grids)
     if (ctx->tune[CHOMP_TUNE_E_STREAM_MIN] >= 0) stream_min = (size_t)ctx->tune[CHOMP_TUNE_E_STREAM_MIN];
-    int parity = 0;
     if (one_cosmology && w != CHOMP_P_LIN && nk % 2 == 0 && nk * n >= stream_min) {
+      int parity = 0;
+      bool lanes_needed = true;
       // (a k grid registered with chomp_power_plan keeps its k-only table: no prep launch)
       const bool planned = mem == CHOMP_DEVICE && plan_matches(ctx, epoch0, dk, nk);
       const bool timed = ctx->timing != 0;
@@ -1511,6 +1512,13 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
         HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
         ctx->timing_valid = true;
       }
+      // per-lane pass over the listed k groups (a planned grid knows whether it has any)
+      if (lanes_needed)
+        with_flag(ctx->with_bao, ssc, [&](auto BAO, auto SSC) {
+          hipLaunchKernelGGL((k_power_grid_lanes<BAO, SSC>), dim3(1024), dim3(256), 0, ctx->stream,
+                             ctx->cfg, L, ctx->d_epochs, ctx->d_tab, w, extrap, (int)epoch0, (int)n,
+                             dk, nk, dout, ctx->d_slow, parity, ctx->d_delta_b);
+        });
     } else {
       // enough blocks to fill 256 CUs: split the epochs over blockIdx.y when nk is small
       unsigned gy = (2048 + gx - 1) / gx;
@@ -1519,19 +1527,10 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
       gy = (unsigned)((n + epy - 1) / epy);
       with_flag(ctx->with_bao, ssc, [&](auto BAO, auto SSC) {
         hipLaunchKernelGGL((k_power_grid<BAO, SSC>), dim3(gx, gy), dim3(256), 0, ctx->stream, ctx->cfg,
-                           L, ctx->d_epochs, ctx->d_tab, w, (int)epoch0, (int)n, epy, 1, dk, nk,
-                           dout, ctx->d_slow, parity, 1, extrap, ctx->d_delta_b);
+                           L, ctx->d_epochs, ctx->d_tab, w, (int)epoch0, (int)n, epy, dk, nk, dout,
+                           extrap, ctx->d_delta_b);
       });
-      streaming = false;
     }
-    // per-lane pass over the listed k groups (streaming shape only; a planned grid knows
-    // whether it has any)
-    if (streaming && lanes_needed)
-      with_flag(ctx->with_bao, ssc, [&](auto BAO, auto SSC) {
-        hipLaunchKernelGGL((k_power_grid_lanes<BAO, SSC>), dim3(1024), dim3(256), 0, ctx->stream,
-                           ctx->cfg, L, ctx->d_epochs, ctx->d_tab, w, extrap, (int)epoch0, (int)n, dk,
-                           nk, dout, ctx->d_slow, parity, ctx->d_delta_b);
-      });
     if (ctx->timing_valid) HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   } else {
     unsigned gx = (unsigned)((nk + 255) / 256);

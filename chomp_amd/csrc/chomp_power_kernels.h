@@ -3,8 +3,9 @@
 //   k_power         generic per-sample kernel: Halo.linear_power/power_mm/power_gm/power_gg
 //                   (halo.py:266-439), HaloFit.power_* (halo.py:1325-1413)
 //   k_power_prep + k_power_stream   row-major streaming of a large (k, z) grid
-//   k_power_grid    row-walking streaming kernel (epochs of different cosmologies, small grids)
-//   k_power_grid_lanes  per-lane pass for unsorted / ragged / out-of-range k groups
+//   k_power_grid_lanes  per-lane pass of that shape for unsorted / ragged / out-of-range k groups
+//   k_power_grid    row-walking streaming kernel (epochs of different cosmologies, small grids);
+//                   it takes such k groups on the per-lane path itself
 //   k_power_extrap  constants of Halo(extrapolate=True) above k_max
 //   k_sigma_r, k_y_nfw, k_eval   point lookups of the mirror classes
 #pragma once
@@ -113,17 +114,14 @@ struct PowerEval {
     extrap = (which & CHOMP_P_EXTRAPOLATE) != 0 && !halofit;   // HaloFit ignores it
     tail = t + L.off_misc + 3;
     w = which & 15;
-    int fa = F_HM, fb = F_HM, fp = F_PPMM;
-    if (w == CHOMP_P_GM) { fa = F_HG; fb = F_HM; fp = F_PPGM; }
-    else if (w == CHOMP_P_GG) { fa = F_HG; fb = F_HG; fp = F_PPGG; }
-    else if (is_ssc(w)) { fb = F_I12; }
+    const PowerFam F = power_families(w);
     double* a = sm;
     double* b = a + 4 * (NK - 1);
     double* p = b + 4 * (NK - 1);
     if (needs_tables()) {
-      copy_doubles(a, t + L.off_kpp[fa], 4 * (NK - 1));
-      copy_doubles(b, t + L.off_kpp[fb], 4 * (NK - 1));
-      copy_doubles(p, t + L.off_kpp[fp], 4 * (NK - 1));
+      copy_doubles(a, t + L.off_kpp[F.fa], 4 * (NK - 1));
+      copy_doubles(b, t + L.off_kpp[F.fb], 4 * (NK - 1));
+      copy_doubles(p, t + L.off_kpp[F.fp], 4 * (NK - 1));
     }
     ca = a; cb = b; cp = p;
     k_min = cfg.k_min;
@@ -293,42 +291,23 @@ __global__ __launch_bounds__(256) void k_power(chomp_config cfg, TabLayout L,
 //     come through the scalar cache; any other wavefront takes the per-lane path.
 // Algorithmic traffic: 8 B read per k + 8 B written per (k, epoch) sample.
 // ---------------------------------------------------------------------------
-// P(k) of epoch table t for one k on the per-lane path (any k, any interval).
+// P(k) of epoch table t where the knot tables do not reach: k < k_min, k > k_max or NaN
+// (halo.py:314-320, the tail of Halo(extrapolate=True); 0 for the super-sample codes above
+// k_max and for the response below k_min), and every k of the linear spectrum.
 template <bool BAO>
-__device__ __forceinline__ double power_lane(const chomp_config& cfg, const TabLayout& L,
-                                             const Epoch& E, const double* t, int fa, int fb,
-                                             int fp, int w, bool extrap, double kv,
-                                             double delta_b = 0.0) {
+__device__ __forceinline__ double power_outside_knots(const chomp_config& cfg, const TabLayout& L,
+                                                      const Epoch& E, const double* t,
+                                                      const PowerFam& F, int w, bool extrap,
+                                                      double kv) {
   if (w == CHOMP_P_LIN) return linear_power_t<BAO>(E, kv);
-  const double x0 = log(cfg.k_min);
-  const double dx = (log(cfg.k_max) - x0) / (double)(L.NK - 1);
-  if (is_ssc(w)) {                                        // halo.py:1136-1169 (fb: I_1^2)
-    if (kv < cfg.k_min) {                                 // P_mm's branch below, fb -> fa
-      if (w == CHOMP_P_SSC_RESPONSE) return 0.0;
-      const double c_lo = t[L.off_kpp[fa]] * t[L.off_kpp[fa]] +
-                          t[L.off_kpp[fp]] / linear_power_t<BAO>(E, cfg.k_min);
-      return linear_power_t<BAO>(E, kv) * c_lo;
-    }
-    if (!(kv <= cfg.k_max)) return 0.0;
-    const double lk = log(kv);
-    const double h = spline_eval_uniform(x0, dx, t + L.off_kpp[fa], L.NK, lk);
-    const double i12 = spline_eval_uniform(x0, dx, t + L.off_kpp[fb], L.NK, lk);
-    const double pp = spline_eval_uniform(x0, dx, t + L.off_kpp[fp], L.NK, lk);
-    return ssc_in_range(w, t[L.off_misc + 1] * power_shape_t<BAO>(E, lk, kv), h, i12, pp, delta_b);
-  }
   if (kv < cfg.k_min) {
-    const double c_lo = t[L.off_kpp[fa]] * t[L.off_kpp[fb]] +
-                        t[L.off_kpp[fp]] / linear_power_t<BAO>(E, cfg.k_min);
+    if (w == CHOMP_P_SSC_RESPONSE) return 0.0;
+    const int fb = is_ssc(w) ? F.fa : F.fb;               // (fb holds I_1^2: P_mm's constant)
+    const double c_lo = t[L.off_kpp[F.fa]] * t[L.off_kpp[fb]] +
+                        t[L.off_kpp[F.fp]] / linear_power_t<BAO>(E, cfg.k_min);
     return linear_power_t<BAO>(E, kv) * c_lo;
   }
-  if (extrap ? kv < cfg.k_max : kv <= cfg.k_max) {
-    const double lk = log(kv);
-    const double ha = spline_eval_uniform(x0, dx, t + L.off_kpp[fa], L.NK, lk);
-    const double hb = spline_eval_uniform(x0, dx, t + L.off_kpp[fb], L.NK, lk);
-    const double pp = spline_eval_uniform(x0, dx, t + L.off_kpp[fp], L.NK, lk);
-    return 2.0 * kPi * kPi * delta_k_ln_t<BAO>(E, lk, kv) / (kv * kv * kv) * ha * hb + pp;
-  }
-  if (extrap) return power_tail<BAO>(E, t + L.off_misc + 3, w, kv, cfg.k_max);
+  if (extrap && !is_ssc(w)) return power_tail<BAO>(E, t + L.off_misc + 3, w, kv, cfg.k_max);
   return 0.0;
 }
 
@@ -371,6 +350,105 @@ __device__ __forceinline__ KLanes load_k_lanes(const chomp_config& cfg, int NK,
   return s;
 }
 
+// How a wavefront's k sit on the knots: worked out by k_power_prep and k_power_grid with
+// classify_wave, read back by k_power_stream from winfo / ktab.
+struct WaveKnots {
+  int idxu;           // the wavefront's lower knot interval (wave-uniform)
+  bool fast, two;     // takes the fast path; straddles the knot idxu + 1 (both wave-uniform)
+  bool s0, s1;        // this lane's k lies in the upper interval idxu + 1
+  double d0, d1;      // ln k - the lower knot of its interval
+};
+
+__device__ __forceinline__ WaveKnots classify_wave(const chomp_config& cfg, int NK, const KLanes& s,
+                                                   int w) {
+  WaveKnots v;
+  v.idxu = __builtin_amdgcn_readfirstlane(s.idx0);
+  // Fast path: every k of the wavefront present, in range and in knot interval idxu or
+  // idxu + 1 (a sorted grid straddles at most one knot per wavefront once nk >~ 6500;
+  // indices are clamped to NK - 2, so idxu + 1 never runs past the last piece).
+  v.fast = __all(s.have0 && s.have1 && s.in0 && s.in1 &&
+                 (s.idx0 == v.idxu || s.idx0 == v.idxu + 1) &&
+                 (s.idx1 == v.idxu || s.idx1 == v.idxu + 1)) &&
+           w != CHOMP_P_LIN;
+  v.two = !__all(s.idx0 == v.idxu && s.idx1 == v.idxu);
+  v.s0 = s.idx0 != v.idxu;
+  v.s1 = s.idx1 != v.idxu;
+  v.d0 = v.d1 = 0.0;
+  return v;
+}
+// ... and, for a wavefront on the fast path, the lanes' offsets d0 / d1 (k_power_prep takes them
+// after the shapes: held across power_shape they cost k_power_prep<true> two VGPRs).
+__device__ __forceinline__ void knot_offsets(const chomp_config& cfg, int NK, const KLanes& s,
+                                             WaveKnots& v) {
+  const double x0 = log(cfg.k_min);
+  const double dx = (log(cfg.k_max) - x0) / (double)(NK - 1);
+  const double xa = x0 + dx * (double)v.idxu, xb = x0 + dx * (double)(v.idxu + 1);
+  v.d0 = s.lk0 - (v.s0 ? xb : xa);
+  v.d1 = s.lk1 - (v.s1 ? xb : xa);
+}
+
+// The fast path's wave-uniform operands of one epoch (through the scalar cache): the
+// amplitude and the pp coefficients of h_a, h_b and the 1-halo term on knot interval idxu.
+struct Cubic {
+  double c0, c1, c2, c3;
+  __device__ __forceinline__ double at(double d) const { return fma(fma(fma(c3, d, c2), d, c1), d, c0); }
+};
+__device__ __forceinline__ Cubic cubic_at(const double* c) { return Cubic{c[0], c[1], c[2], c[3]}; }
+
+struct PowerRow { double A; Cubic a, b, p; };
+
+// Where those operands sit in an epoch table (the next interval's coefficients follow at +4).
+struct RowCols {
+  bool same_ab;       // P_mm and P_gg multiply a 2-halo factor by itself
+  int oa, ob, op;
+};
+__device__ __forceinline__ RowCols row_cols(const TabLayout& L, int w, int idxu) {
+  const PowerFam F = power_families(w);
+  return RowCols{F.fa == F.fb, L.off_kpp[F.fa] + 4 * idxu, L.off_kpp[F.fb] + 4 * idxu,
+                 L.off_kpp[F.fp] + 4 * idxu};
+}
+__device__ __forceinline__ PowerRow fetch_row(const TabLayout& L, const RowCols& o, const double* t) {
+  return PowerRow{t[L.off_misc + 1], cubic_at(t + o.oa), cubic_at(t + o.ob), cubic_at(t + o.op)};
+}
+
+// The fast path's two samples of one epoch (row c of epoch table t), sh0 / sh1 the lanes'
+// shapes.  k_power_grid and k_power_stream both evaluate this one function, so the launch
+// shapes agree bit for bit.
+template <bool SSC>
+__device__ __forceinline__ void power_fast_pair(const PowerRow& c, const double* t, const RowCols& o,
+                                                const WaveKnots& v, double sh0, double sh1, int w,
+                                                double db, double& r0, double& r1) {
+  const double d0 = v.d0, d1 = v.d1;
+  double ha0 = c.a.at(d0), pp0 = c.p.at(d0);
+  double ha1 = c.a.at(d1), pp1 = c.p.at(d1);
+  // (hb1 declared first: in the other order k_power_stream<1, false> takes 24 VGPRs, not 22)
+  double hb1 = ha1, hb0 = ha0;
+  if (!o.same_ab) {                // wave-uniform
+    hb0 = c.b.at(d0);
+    hb1 = c.b.at(d1);
+  }
+  if (v.two) {     // the wavefront straddles a knot: lanes above it use the next piece
+    const Cubic a = cubic_at(t + o.oa + 4), b = cubic_at(t + o.ob + 4), p = cubic_at(t + o.op + 4);
+    if (v.s0) {
+      ha0 = a.at(d0);
+      hb0 = b.at(d0);
+      pp0 = p.at(d0);
+    }
+    if (v.s1) {
+      ha1 = a.at(d1);
+      hb1 = b.at(d1);
+      pp1 = p.at(d1);
+    }
+  }
+  if constexpr (SSC) {
+    r0 = ssc_in_range(w, c.A * sh0, ha0, hb0, pp0, db);
+    r1 = ssc_in_range(w, c.A * sh1, ha1, hb1, pp1, db);
+  } else {
+    r0 = fma(c.A * sh0, ha0 * hb0, pp0);
+    r1 = fma(c.A * sh1, ha1 * hb1, pp1);
+  }
+}
+
 // 16-byte write-through store (sc1).  Issued from inline asm, so the compiler's hazard
 // recogniser does not see a VMEM store: a store of more than 64 bits must not be
 // followed directly by a VALU write of its data registers, hence the trailing s_nop.
@@ -382,12 +460,10 @@ __device__ __forceinline__ void store_wt16(double* p, double r0, double r1) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" : : "v"(p), "v"(bits) : "memory");
 }
 
-
-
-// Wavefronts (groups of 128 consecutive k) that cannot take a streaming path are
-// collected in a compact list for k_power_grid_lanes.  slow[0..1] are two counters used
-// by alternate launches (`parity`): a launch appends through slow[parity] and clears
-// slow[parity ^ 1] for the next one, so no separate memset is needed (launches of one
+// Wavefronts (groups of 128 consecutive k) that cannot take the streaming kernel are
+// collected by k_power_prep in a compact list for k_power_grid_lanes.  slow[0..1] are two
+// counters used by alternate launches (`parity`): a launch appends through slow[parity] and
+// clears slow[parity ^ 1] for the next one, so no separate memset is needed (launches of one
 // context are stream-ordered).  slow[2...] is the list.
 __device__ __forceinline__ void slow_list_begin(int* slow, int parity) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) slow[parity ^ 1] = 0;
@@ -427,154 +503,84 @@ __device__ __forceinline__ void power_lanes_range(const chomp_config& cfg, const
       sh0 = power_shape_t<BAO>(E, s.lk0, s.k0);
       sh1 = power_shape_t<BAO>(E, s.lk1, s.k1);
     }
-    if (s.have0) {
-      double r;
-      if (s.in0 && w != CHOMP_P_LIN) {
-        const double ha = pp_poly(t + L.off_kpp[F.fa], s.idx0, e0);
-        const double hb = pp_poly(t + L.off_kpp[F.fb], s.idx0, e0);
-        const double pp = pp_poly(t + L.off_kpp[F.fp], s.idx0, e0);
-        r = SSC ? ssc_in_range(w, A * sh0, ha, hb, pp, db) : fma(A * sh0, ha * hb, pp);
+    auto lane = [&](bool have, bool in, int idx, double d, double sh, double kv, double* ol) {
+      if (!have) return;
+      if (in && w != CHOMP_P_LIN) {
+        const double ha = pp_poly(t + L.off_kpp[F.fa], idx, d);
+        const double hb = pp_poly(t + L.off_kpp[F.fb], idx, d);
+        const double pp = pp_poly(t + L.off_kpp[F.fp], idx, d);
+        *ol = SSC ? ssc_in_range(w, A * sh, ha, hb, pp, db) : fma(A * sh, ha * hb, pp);
       } else {
-        r = power_lane<BAO>(cfg, L, E, t, F.fa, F.fb, F.fp, w, extrap, s.k0, db);
+        *ol = power_outside_knots<BAO>(cfg, L, E, t, F, w, extrap, kv);
       }
-      o[0] = r;
-    }
-    if (s.have1) {
-      double r;
-      if (s.in1 && w != CHOMP_P_LIN) {
-        const double ha = pp_poly(t + L.off_kpp[F.fa], s.idx1, e1);
-        const double hb = pp_poly(t + L.off_kpp[F.fb], s.idx1, e1);
-        const double pp = pp_poly(t + L.off_kpp[F.fp], s.idx1, e1);
-        r = SSC ? ssc_in_range(w, A * sh1, ha, hb, pp, db) : fma(A * sh1, ha * hb, pp);
-      } else {
-        r = power_lane<BAO>(cfg, L, E, t, F.fa, F.fb, F.fp, w, extrap, s.k1, db);
-      }
-      o[1] = r;
-    }
+    };
+    lane(s.have0, s.in0, s.idx0, e0, sh0, s.k0, o);
+    lane(s.have1, s.in1, s.idx1, e1, sh1, s.k1, o + 1);
   }
 }
 
 // The row-walking streaming pass (epochs of different cosmologies, or small grids).
 // grid (ceil(nk / 512), ceil(n_epoch / epochs_per_y)), block 256.  A wavefront whose k
-// do not qualify for the fast path only enters itself in the slow list.
+// do not qualify for the fast path evaluates its epochs on the per-lane path itself.
 template <bool BAO, bool SSC = false>
 __global__ __launch_bounds__(256) void k_power_grid(chomp_config cfg, TabLayout L,
                                                     const Epoch* __restrict__ epochs,
                                                     const double* __restrict__ tab, int w,
                                                     int epoch0, int n_epoch, int epochs_per_y,
-                                                    int rot,
                                                     const double* __restrict__ k, size_t nk,
-                                                    double* __restrict__ out,
-                                                    int* __restrict__ slow, int parity,
-                                                    int inline_lanes, bool extrap,
+                                                    double* __restrict__ out, bool extrap,
                                                     const double* __restrict__ delta_b) {
-  if (!inline_lanes) slow_list_begin(slow, parity);
   const int k_group = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
-  const PowerFam F = power_families(w);
-  const bool same_ab = F.fa == F.fb;
-  const int NK = L.NK;
-  const KLanes s = load_k_lanes(cfg, NK, k, nk, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
-  const int idxu = __builtin_amdgcn_readfirstlane(s.idx0);
-  // Fast path: every k of the wavefront present, in range and in knot interval idxu or
-  // idxu + 1 (a sorted grid straddles at most one knot per wavefront once nk >~ 6500;
-  // indices are clamped to NK - 2, so idxu + 1 never runs past the last piece).
-  const bool fast = __all(s.have0 && s.have1 && s.in0 && s.in1 &&
-                          (s.idx0 == idxu || s.idx0 == idxu + 1) &&
-                          (s.idx1 == idxu || s.idx1 == idxu + 1)) &&
-                    w != CHOMP_P_LIN;
+  const KLanes s = load_k_lanes(cfg, L.NK, k, nk, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+  WaveKnots v = classify_wave(cfg, L.NK, s, w);
   const int q_lo = blockIdx.y * epochs_per_y;
   int q_hi = q_lo + epochs_per_y;
   if (q_hi > n_epoch) q_hi = n_epoch;
-  if (!fast) {
-    if (inline_lanes) {            // small grids: this block's epochs on the per-lane path, here
-      if ((size_t)k_group * 128 < nk)
-        power_lanes_range<BAO, SSC>(cfg, L, epochs, tab, w, extrap, epoch0, q_lo, q_hi, s, nk, out,
-                                    delta_b);
-    } else if ((threadIdx.x & 63) == 0 && blockIdx.y == 0 && (size_t)k_group * 128 < nk) {
-      slow_list_append(slow, parity, k_group);
-    }
+  if (!v.fast) {
+    if ((size_t)k_group * 128 < nk)
+      power_lanes_range<BAO, SSC>(cfg, L, epochs, tab, w, extrap, epoch0, q_lo, q_hi, s, nk, out,
+                                  delta_b);
     return;
   }
-  const double x0 = log(cfg.k_min);
-  const double dx = (log(cfg.k_max) - x0) / (double)(NK - 1);
-  const bool two = !__all(s.idx0 == idxu && s.idx1 == idxu);  // wave-uniform
-  const bool s0 = s.idx0 != idxu, s1 = s.idx1 != idxu;         // lane uses the upper interval
-  const double xa = x0 + dx * (double)idxu, xb = x0 + dx * (double)(idxu + 1);
-  const double d0 = s.lk0 - (s0 ? xb : xa), d1 = s.lk1 - (s1 ? xb : xa);
-  const double k0 = s.k0, k1 = s.k1;
-  const int oa = L.off_kpp[F.fa] + 4 * idxu, ob = L.off_kpp[F.fb] + 4 * idxu,
-            op = L.off_kpp[F.fp] + 4 * idxu;
+  knot_offsets(cfg, L.NK, s, v);
+  const RowCols o = row_cols(L, w, v.idxu);
   double shape0 = 0.0, shape1 = 0.0;             // 2 pi^2 (k/H0)^(3+n) T^2 / k^3
   // Blocks start their walk at different rows (rows of a large grid are a power-of-two
   // stride apart: in lockstep every wavefront would hit the same HBM channels).
   const int cnt = q_hi - q_lo;
-  int q = q_lo + (int)((blockIdx.x * (unsigned)rot) % (unsigned)cnt);
+  int q = q_lo + (int)(blockIdx.x % (unsigned)cnt);
   // wave-uniform operands of one epoch: through the scalar cache, fetched one epoch
   // ahead of their use so that the loop never waits on a scalar load
-  struct Row { double A, flag, a0, a1, a2, a3, b0, b1, b2, b3, p0, p1, p2, p3; };
-  auto fetch = [&](int qq) {
-    const double* t = tab + (size_t)(epoch0 + qq) * L.stride;
-    return Row{t[L.off_misc + 1], t[L.off_misc + 2],
-               t[oa], t[oa + 1], t[oa + 2], t[oa + 3],
-               t[ob], t[ob + 1], t[ob + 2], t[ob + 3],
-               t[op], t[op + 1], t[op + 2], t[op + 3]};
-  };
-  Row nxt = fetch(q);
+  const double* tn = tab + (size_t)(epoch0 + q) * L.stride;
+  PowerRow nxt = fetch_row(L, o, tn);
+  double nxt_flag = tn[L.off_misc + 2];
   for (int j = 0; j < cnt; ++j) {
-    const Row c = nxt;
+    const PowerRow c = nxt;
+    const double flag = nxt_flag;
     const int qc = q;
     ++q;
     if (q == q_hi) q = q_lo;
-    nxt = fetch(q);                              // (one harmless re-fetch on the last trip)
-    const bool same = j > 0 && qc > q_lo && c.flag != 0.0;
+    tn = tab + (size_t)(epoch0 + q) * L.stride;   // (one harmless re-fetch on the last trip)
+    nxt = fetch_row(L, o, tn);
+    nxt_flag = tn[L.off_misc + 2];
+    const bool same = j > 0 && qc > q_lo && flag != 0.0;
     if (!same) {
       const Epoch& E = epochs[epoch0 + qc];
-      shape0 = power_shape_t<BAO>(E, s.lk0, k0);
-      shape1 = power_shape_t<BAO>(E, s.lk1, k1);
-    }
-    double ha0 = fma(fma(fma(c.a3, d0, c.a2), d0, c.a1), d0, c.a0);
-    double pp0 = fma(fma(fma(c.p3, d0, c.p2), d0, c.p1), d0, c.p0);
-    double ha1 = fma(fma(fma(c.a3, d1, c.a2), d1, c.a1), d1, c.a0);
-    double pp1 = fma(fma(fma(c.p3, d1, c.p2), d1, c.p1), d1, c.p0);
-    double hb0 = ha0, hb1 = ha1;   // P_mm and P_gg multiply a 2-halo factor by itself
-    if (!same_ab) {                // wave-uniform
-      hb0 = fma(fma(fma(c.b3, d0, c.b2), d0, c.b1), d0, c.b0);
-      hb1 = fma(fma(fma(c.b3, d1, c.b2), d1, c.b1), d1, c.b0);
-    }
-    if (two) {       // the wavefront straddles a knot: lanes above it use the next piece
-      const double* t = tab + (size_t)(epoch0 + qc) * L.stride;
-      const double A0 = t[oa + 4], A1 = t[oa + 5], A2 = t[oa + 6], A3 = t[oa + 7];
-      const double B0 = t[ob + 4], B1 = t[ob + 5], B2 = t[ob + 6], B3 = t[ob + 7];
-      const double P0 = t[op + 4], P1 = t[op + 5], P2 = t[op + 6], P3 = t[op + 7];
-      if (s0) {
-        ha0 = fma(fma(fma(A3, d0, A2), d0, A1), d0, A0);
-        hb0 = fma(fma(fma(B3, d0, B2), d0, B1), d0, B0);
-        pp0 = fma(fma(fma(P3, d0, P2), d0, P1), d0, P0);
-      }
-      if (s1) {
-        ha1 = fma(fma(fma(A3, d1, A2), d1, A1), d1, A0);
-        hb1 = fma(fma(fma(B3, d1, B2), d1, B1), d1, B0);
-        pp1 = fma(fma(fma(P3, d1, P2), d1, P1), d1, P0);
-      }
+      shape0 = power_shape_t<BAO>(E, s.lk0, s.k0);
+      shape1 = power_shape_t<BAO>(E, s.lk1, s.k1);
     }
     double r0, r1;
-    if constexpr (SSC) {
-      const double db = delta_b[epoch0 + qc];
-      r0 = ssc_in_range(w, c.A * shape0, ha0, hb0, pp0, db);
-      r1 = ssc_in_range(w, c.A * shape1, ha1, hb1, pp1, db);
-    } else {
-      r0 = fma(c.A * shape0, ha0 * hb0, pp0);
-      r1 = fma(c.A * shape1, ha1 * hb1, pp1);
-    }
-    double* o = out + (size_t)qc * nk + s.i0;
+    power_fast_pair<SSC>(c, tab + (size_t)(epoch0 + qc) * L.stride, o, v, shape0, shape1, w,
+                         SSC ? delta_b[epoch0 + qc] : 0.0, r0, r1);
+    double* ot = out + (size_t)qc * nk + s.i0;
     // Streamed once, never re-read by this launch: 16-byte write-through (sc1) stores
     // (plain stores leave ~0.5 GB of dirty lines for the end-of-kernel release to
     // write back; MI355X_MICROARCH.md rows "boundary" / "publish-large").
     if (s.vec) {
-      store_wt16(o, r0, r1);
+      store_wt16(ot, r0, r1);
     } else {
-      __builtin_nontemporal_store(r0, o);
-      __builtin_nontemporal_store(r1, o + 1);
+      __builtin_nontemporal_store(r0, ot);
+      __builtin_nontemporal_store(r1, ot + 1);
     }
   }
 }
@@ -603,30 +609,21 @@ __global__ __launch_bounds__(256) void k_power_prep(chomp_config cfg, TabLayout 
                                                     int* __restrict__ slow, int parity) {
   slow_list_begin(slow, parity);
   const int k_group = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
-  const int NK = L.NK;
   const size_t ti = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const KLanes s = load_k_lanes(cfg, NK, k, nk, ti);
-  const int idxu = __builtin_amdgcn_readfirstlane(s.idx0);
-  const bool fast = __all(s.have0 && s.have1 && s.in0 && s.in1 &&
-                          (s.idx0 == idxu || s.idx0 == idxu + 1) &&
-                          (s.idx1 == idxu || s.idx1 == idxu + 1)) &&
-                    w != CHOMP_P_LIN;
-  const bool two = !__all(s.idx0 == idxu && s.idx1 == idxu);
+  const KLanes s = load_k_lanes(cfg, L.NK, k, nk, ti);
+  WaveKnots v = classify_wave(cfg, L.NK, s, w);
   if ((threadIdx.x & 63) == 0) {
-    winfo[k_group] = idxu | (two ? kWaveTwo : 0) | (fast ? 0 : kWaveSlow);
-    if (!fast && (size_t)k_group * 128 < nk) slow_list_append(slow, parity, k_group);
+    winfo[k_group] = v.idxu | (v.two ? kWaveTwo : 0) | (v.fast ? 0 : kWaveSlow);
+    if (!v.fast && (size_t)k_group * 128 < nk) slow_list_append(slow, parity, k_group);
   }
-  if (!fast) return;
+  if (!v.fast) return;
   const Epoch& E = epochs[e_shape];
-  const double x0 = log(cfg.k_min);
-  const double dx = (log(cfg.k_max) - x0) / (double)(NK - 1);
-  const bool s0 = s.idx0 != idxu, s1 = s.idx1 != idxu;
-  const double xa = x0 + dx * (double)idxu, xb = x0 + dx * (double)(idxu + 1);
   const double sh0 = power_shape_t<BAO>(E, s.lk0, s.k0), sh1 = power_shape_t<BAO>(E, s.lk1, s.k1);
-  double4 v;
-  v.x = s.lk0 - (s0 ? xb : xa); v.y = s0 ? -sh0 : sh0;
-  v.z = s.lk1 - (s1 ? xb : xa); v.w = s1 ? -sh1 : sh1;
-  *reinterpret_cast<double4*>(ktab + 4 * ti) = v;
+  knot_offsets(cfg, L.NK, s, v);
+  double4 kt;
+  kt.x = v.d0; kt.y = v.s0 ? -sh0 : sh0;
+  kt.z = v.d1; kt.w = v.s1 ? -sh1 : sh1;
+  *reinterpret_cast<double4*>(ktab + 4 * ti) = kt;
 }
 
 // grid (roundup8(ceil(nk / 512)), ceil(n_epoch / PER)), block 256; blockIdx.x fastest =
@@ -643,84 +640,41 @@ __global__ __launch_bounds__(256) void k_power_stream(TabLayout L, const double*
   const int k_group = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
   const int info = winfo[k_group];
   const size_t ti = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const double4 v = *reinterpret_cast<const double4*>(ktab + 4 * ti);   // (padded: in bounds)
+  const double4 kt = *reinterpret_cast<const double4*>(ktab + 4 * ti);  // (padded: in bounds)
   if (info & kWaveSlow) return;
   const int idxu = info & kWaveIdxMask;
   const bool two = (info & kWaveTwo) != 0;
-  const PowerFam F = power_families(w);
-  const bool same_ab = F.fa == F.fb;
-  const int oa = L.off_kpp[F.fa] + 4 * idxu, ob = L.off_kpp[F.fb] + 4 * idxu,
-            op = L.off_kpp[F.fp] + 4 * idxu;
+  const RowCols o = row_cols(L, w, idxu);
   const int q_lo = blockIdx.y * PER;
   // wave-uniform operands of the PER rows: all fetched through the scalar cache before
   // the first use
-  struct Row { double A, a0, a1, a2, a3, b0, b1, b2, b3, p0, p1, p2, p3; };
-  Row r[PER];
+  PowerRow r[PER];
   double db[PER];
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
-    const double* t = tab + (size_t)(epoch0 + q_lo + j) * L.stride;
-    r[j] = Row{t[L.off_misc + 1], t[oa], t[oa + 1], t[oa + 2], t[oa + 3],
-               t[ob], t[ob + 1], t[ob + 2], t[ob + 3], t[op], t[op + 1], t[op + 2], t[op + 3]};
+    r[j] = fetch_row(L, o, tab + (size_t)(epoch0 + q_lo + j) * L.stride);
     db[j] = SSC ? delta_b[epoch0 + q_lo + j] : 0.0;
   }
-  const double d0 = v.x, d1 = v.z;
-  const bool s0 = v.y < 0.0, s1 = v.w < 0.0;
-  const double shape0 = fabs(v.y), shape1 = fabs(v.w);
-  double* o = out + (size_t)q_lo * nk + 2 * ti;
+  const WaveKnots v{idxu, true, two, kt.y < 0.0, kt.w < 0.0, kt.x, kt.z};
+  const double shape0 = fabs(kt.y), shape1 = fabs(kt.w);
+  double* ot = out + (size_t)q_lo * nk + 2 * ti;
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
-    const Row& c = r[j];
-    double ha0 = fma(fma(fma(c.a3, d0, c.a2), d0, c.a1), d0, c.a0);
-    double pp0 = fma(fma(fma(c.p3, d0, c.p2), d0, c.p1), d0, c.p0);
-    double ha1 = fma(fma(fma(c.a3, d1, c.a2), d1, c.a1), d1, c.a0);
-    double pp1 = fma(fma(fma(c.p3, d1, c.p2), d1, c.p1), d1, c.p0);
-    double hb0 = ha0, hb1 = ha1;   // P_mm and P_gg multiply a 2-halo factor by itself
-    if (!same_ab) {                // wave-uniform
-      hb0 = fma(fma(fma(c.b3, d0, c.b2), d0, c.b1), d0, c.b0);
-      hb1 = fma(fma(fma(c.b3, d1, c.b2), d1, c.b1), d1, c.b0);
-    }
-    if (two) {       // the wavefront straddles a knot: lanes above it use the next piece
-      const double* t = tab + (size_t)(epoch0 + q_lo + j) * L.stride;
-      const double A0 = t[oa + 4], A1 = t[oa + 5], A2 = t[oa + 6], A3 = t[oa + 7];
-      const double B0 = t[ob + 4], B1 = t[ob + 5], B2 = t[ob + 6], B3 = t[ob + 7];
-      const double P0 = t[op + 4], P1 = t[op + 5], P2 = t[op + 6], P3 = t[op + 7];
-      if (s0) {
-        ha0 = fma(fma(fma(A3, d0, A2), d0, A1), d0, A0);
-        hb0 = fma(fma(fma(B3, d0, B2), d0, B1), d0, B0);
-        pp0 = fma(fma(fma(P3, d0, P2), d0, P1), d0, P0);
-      }
-      if (s1) {
-        ha1 = fma(fma(fma(A3, d1, A2), d1, A1), d1, A0);
-        hb1 = fma(fma(fma(B3, d1, B2), d1, B1), d1, B0);
-        pp1 = fma(fma(fma(P3, d1, P2), d1, P1), d1, P0);
-      }
-    }
     double r0, r1;
-    if constexpr (SSC) {
-      r0 = ssc_in_range(w, c.A * shape0, ha0, hb0, pp0, db[j]);
-      r1 = ssc_in_range(w, c.A * shape1, ha1, hb1, pp1, db[j]);
-    } else {
-      r0 = fma(c.A * shape0, ha0 * hb0, pp0);
-      r1 = fma(c.A * shape1, ha1 * hb1, pp1);
-    }
+    power_fast_pair<SSC>(r[j], tab + (size_t)(epoch0 + q_lo + j) * L.stride, o, v, shape0, shape1,
+                         w, db[j], r0, r1);
     // write-through: the output is never re-read by this launch, and the k table must
     // stay in L2 next to it
-    store_wt16(o, r0, r1);
-    o += nk;
+    store_wt16(ot, r0, r1);
+    ot += nk;
   }
 }
 
-// The per-lane pass: any k, any knot interval, any order.  1-D grid; every wavefront
-// walks work items (listed k group, chunk of epochs).  The chunk length adapts to the
-// length of the list: few listed groups -> short chunks over many wavefronts (the
-// per-epoch coefficient loads of this path are a dependent chain), a fully listed grid
-// -> one item per group.  In-range k still re-use the Eisenstein-Hu shape across epochs
-// of one cosmology; k outside [k_min, k_max] take the full formula (halo.py:314-320).
-// The per-lane pass of the streaming shape: 1-D grid; every wavefront walks work items
-// (listed k group, chunk of epochs).  The chunk length adapts to the length of the list: few
-// listed groups -> short chunks over many wavefronts (the per-epoch coefficient loads of this
-// path are a dependent chain), a fully listed grid -> one item per group.
+// The per-lane pass of the streaming shape, over the k groups k_power_prep listed: 1-D grid;
+// every wavefront walks work items (listed k group, chunk of epochs).  The chunk length adapts
+// to the length of the list: few listed groups -> short chunks over many wavefronts (the
+// per-epoch coefficient loads of this path are a dependent chain), a fully listed grid -> one
+// item per group.
 template <bool BAO, bool SSC = false>
 __global__ __launch_bounds__(256) void k_power_grid_lanes(
     chomp_config cfg, TabLayout L, const Epoch* __restrict__ epochs,
