@@ -69,6 +69,15 @@ class HodPar(ctypes.Structure):
         "log_M_min", "sigma", "log_M_0", "log_M_1p", "alpha")]
 
 
+HOD_ZHENG, HOD_MANDELBAUM = 0, 1
+
+
+class HodModel(ctypes.Structure):
+    """chomp_hod_model: one epoch's HOD, tagged by its model (CHOMP_HOD_*)."""
+    _fields_ = [("kind", ctypes.c_int), ("reserved", ctypes.c_int), ("zheng", HodPar),
+                ("log_M_0", ctypes.c_double), ("w", ctypes.c_double)]
+
+
 class Config(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_double) for n in (
         "k_min", "k_max", "mass_min", "mass_max", "corr_precision",
@@ -111,6 +120,7 @@ EXPORTS = [
     "chomp_wtheta_cell", "chomp_stage_k_halofit", "chomp_set_delta_b", "chomp_put_table",
     "chomp_kernel_ssc_setup", "chomp_kernel_ssc_raw", "chomp_kernel_ssc_eval",
     "chomp_covariance_ssc",
+    "chomp_halo_setup_hod", "chomp_stage_k_hod", "chomp_stage_k_halofit_hod",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
@@ -318,6 +328,13 @@ def lib():
                                        ctypes.POINTER(HodPar), ctypes.c_uint]
         L.chomp_stage_k.argtypes = [vp, ctypes.POINTER(HaloPar), i, ctypes.POINTER(HaloPar),
                                     ctypes.POINTER(HodPar), ctypes.c_uint]
+        L.chomp_halo_setup_hod.argtypes = [vp, ctypes.POINTER(HaloPar),
+                                           ctypes.POINTER(HodModel), ctypes.c_uint]
+        L.chomp_stage_k_hod.argtypes = [vp, ctypes.POINTER(HaloPar), i, ctypes.POINTER(HaloPar),
+                                        ctypes.POINTER(HodModel), ctypes.c_uint]
+        L.chomp_stage_k_halofit_hod.argtypes = [vp, ctypes.POINTER(HaloPar), i,
+                                                ctypes.POINTER(HaloPar), ctypes.POINTER(HodModel),
+                                                ctypes.c_uint, sz, d, d, d, d, d]
         L.chomp_halofit_setup.argtypes = [vp, sz, sz, d, d, d, d, d]
         L.chomp_stage_k_halofit.argtypes = [vp, ctypes.POINTER(HaloPar), i, ctypes.POINTER(HaloPar),
                                             ctypes.POINTER(HodPar), ctypes.c_uint, sz, d, d, d, d, d]
@@ -423,6 +440,16 @@ def halo_struct(halo_dict):
 def hod_struct(hod):
     return HodPar(float(hod.log_M_min), float(hod.sigma), float(hod.log_M_0),
                   float(hod.log_M_1p), float(hod.alpha))
+
+
+def hod_model(hod):
+    """The chomp_hod_model of an HOD object: hod.HODMandelbaum by its class (log_M_0, w; the
+    library derives the rest); every other object is read as HODZheng's five numbers, so an
+    object without them fails here with AttributeError, as before."""
+    from . import hod as hod_mod
+    if isinstance(hod, hod_mod.HODMandelbaum):
+        return HodModel(HOD_MANDELBAUM, 0, HodPar(), float(hod.log_M_0), float(hod.w))
+    return HodModel(HOD_ZHENG, 0, hod_struct(hod), 0.0, 0.0)
 
 
 def _is_torch(x):
@@ -538,9 +565,11 @@ class Context(object):
 
     @staticmethod
     def pack_hod(hods, n):
+        """One HOD object (for all n epochs) or a list of n, of either model: the tagged
+        chomp_hod_model array the *_hod entry points take."""
         if not isinstance(hods, (list, tuple)):
             hods = [hods] * n
-        return (HodPar * n)(*[hod_struct(h) for h in hods])
+        return (HodModel * n)(*[hod_model(h) for h in hods])
 
     def epochs_set(self, cosmo, z, with_bao=False):
         """with_bao: SingleEpoch(with_bao=True), the E&H transfer function with wiggles."""
@@ -563,7 +592,7 @@ class Context(object):
         pa = profile if isinstance(profile, ctypes.Array) else self.pack_halo(profile, n)
         ha = hods if isinstance(hods, ctypes.Array) else self.pack_hod(hods, n)
         assert len(pa) == n and len(ha) == n
-        self._check(self._L.chomp_halo_setup(self._h, pa, ha, int(tables)))
+        self._check(self._L.chomp_halo_setup_hod(self._h, pa, ha, int(tables)))
 
     def stage_k(self, mass_halo, mf_kind, profile, hods, tables):
         """mass_setup + halo_setup in one call (chomp_stage_k)."""
@@ -572,7 +601,7 @@ class Context(object):
         pa = profile if isinstance(profile, ctypes.Array) else self.pack_halo(profile, n)
         ha = hods if isinstance(hods, ctypes.Array) else self.pack_hod(hods, n)
         assert len(ma) == n and len(pa) == n and len(ha) == n
-        self._check(self._L.chomp_stage_k(self._h, ma, int(mf_kind), pa, ha, int(tables)))
+        self._check(self._L.chomp_stage_k_hod(self._h, ma, int(mf_kind), pa, ha, int(tables)))
 
     def stage_k_halofit(self, mass_halo, mf_kind, profile, hods, tables, epoch, f1, f2, f3,
                         omega_l, w):
@@ -582,8 +611,8 @@ class Context(object):
         pa = profile if isinstance(profile, ctypes.Array) else self.pack_halo(profile, n)
         ha = hods if isinstance(hods, ctypes.Array) else self.pack_hod(hods, n)
         assert len(ma) == n and len(pa) == n and len(ha) == n
-        self._check(self._L.chomp_stage_k_halofit(self._h, ma, int(mf_kind), pa, ha, int(tables),
-                                                  epoch, f1, f2, f3, omega_l, w))
+        self._check(self._L.chomp_stage_k_halofit_hod(self._h, ma, int(mf_kind), pa, ha,
+                                                      int(tables), epoch, f1, f2, f3, omega_l, w))
 
     def halofit_setup(self, dst, src, f1, f2, f3, omega_l, w):
         self._check(self._L.chomp_halofit_setup(self._h, dst, src, f1, f2, f3,

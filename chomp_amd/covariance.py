@@ -302,8 +302,8 @@ class Covariance(object):
         h = self.halo_a
         hod = h.get_hod_object()
         key = (id(ctx), self.corr_a.kernel._signature(), code, h._epoch_sig, h._mass_sig,
-               tuple(getattr(hod, a, None) for a in ("log_M_min", "sigma", "log_M_0",
-                                                     "log_M_1p", "alpha")),
+               type(hod), tuple(getattr(hod, a, None) for a in ("log_M_min", "sigma", "log_M_0",
+                                                                "log_M_1p", "alpha", "w")),
                repr(sorted(h._profile_dict.items())), h.get_extrapolation(),
                self.corr_a.kernel.z_bar)
         if key != self._table_key or not self._initialized_halo_splines:

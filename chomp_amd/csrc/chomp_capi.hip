@@ -948,7 +948,19 @@ struct HaloPlan {
            group_hod(groups[3]);
   }
 };
-static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const chomp_hod_par* hod,
+// The tagged models of n Zheng parameter sets (the entry points that predate chomp_hod_model).
+static std::vector<chomp_hod_model> zheng_models(const chomp_hod_par* hod, size_t n) {
+  std::vector<chomp_hod_model> m(n);
+  for (size_t i = 0; i < n; ++i) {
+    m[i] = chomp_hod_model{};
+    m[i].kind = CHOMP_HOD_ZHENG;
+    m[i].zheng = hod[i];
+  }
+  return m;
+}
+static_assert(kHodZheng == CHOMP_HOD_ZHENG && kHodMandelbaum == CHOMP_HOD_MANDELBAUM,
+              "chomp_math.h's model numbers are the header's");
+static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const chomp_hod_model* hod,
                         unsigned tables, HaloPlan* P) {
   const size_t n = ctx->n_epoch;
   for (size_t i = 0; i < n; ++i)
@@ -956,10 +968,29 @@ static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const cho
       return fail(ctx, CHOMP_ERR_SCOPE,
                   "halo alpha != -1: the general-profile transform y_general "
                   "(halo.py:491-559) is outside the hot-path scope (NFW only)");
+  for (size_t i = 0; i < n; ++i)
+    if ((hod[i].kind != CHOMP_HOD_ZHENG && hod[i].kind != CHOMP_HOD_MANDELBAUM) ||
+        hod[i].reserved != 0)
+      return fail(ctx, CHOMP_ERR_ARG, "halo_setup: unknown HOD model");
   std::vector<HodDev> hd(n);
   for (size_t i = 0; i < n; ++i) {
-    const chomp_hod_par& h = hod[i];
     HodDev& d = hd[i];
+    d.model = hod[i].kind;
+    d.pad_ = 0;
+    d.w = 0.0;
+    d.M_min = 0.0;
+    if (hod[i].kind == CHOMP_HOD_MANDELBAUM) {
+      // hod.py:248-259: no HOD.__init__ values of its own beyond -1 (no moment zeros, no safe
+      // norm: every integral over the whole nu range); sigma = 0 and alpha = 1 keep the Zheng
+      // fields out of the way (alpha = 1: no node evaluation, see HaloPlan::eval)
+      d.log_M_0 = hod[i].log_M_0;
+      mandelbaum_constants(hod[i].log_M_0, &d.log_M_min, &d.M_min);
+      d.w = hod[i].w;
+      d.sigma = 0.0; d.log_M_1p = 0.0; d.alpha = 1.0;
+      d.first_zero = d.second_zero = d.safe_norm = -1.0;
+      continue;
+    }
+    const chomp_hod_par& h = hod[i].zheng;
     d.log_M_min = h.log_M_min; d.sigma = h.sigma; d.log_M_0 = h.log_M_0;
     d.log_M_1p = h.log_M_1p; d.alpha = h.alpha;
     // hod.py:172-186; the `secon_moment_zero` typo there means second_moment_zero
@@ -1203,8 +1234,8 @@ int chomp_mass_setup(chomp_ctx* ctx, const chomp_halo_par* par, int mf_kind) {
   return CHOMP_OK;
 }
 
-int chomp_halo_setup(chomp_ctx* ctx, const chomp_halo_par* profile,
-                     const chomp_hod_par* hod, unsigned tables) {
+int chomp_halo_setup_hod(chomp_ctx* ctx, const chomp_halo_par* profile,
+                         const chomp_hod_model* hod, unsigned tables) {
   StageRange range_(ctx, "chomp:halo_setup (Stage K: node tables, knot integrals)");
   if (!ctx || !profile || !hod) return fail(ctx, CHOMP_ERR_ARG, "halo_setup: bad args");
   if (!ctx->have_mass) return fail(ctx, CHOMP_ERR_STATE, "halo_setup before mass_setup");
@@ -1226,8 +1257,8 @@ int chomp_halo_setup(chomp_ctx* ctx, const chomp_halo_par* profile,
   return launch_halo_knots(ctx, P);
 }
 
-int chomp_stage_k(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
-                  const chomp_halo_par* profile, const chomp_hod_par* hod, unsigned tables) {
+int chomp_stage_k_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
+                      const chomp_halo_par* profile, const chomp_hod_model* hod, unsigned tables) {
   StageRange range_(ctx, "chomp:stage_k (Stage K: mass function + halo model)");
   if (!ctx || !mass_par || !profile || !hod) return fail(ctx, CHOMP_ERR_ARG, "stage_k: bad args");
   if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "stage_k before epochs_set");
@@ -1243,6 +1274,20 @@ int chomp_stage_k(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
   if (rc) return rc;
   ctx->have_mass = true;
   return launch_halo_knots(ctx, P);
+}
+
+int chomp_halo_setup(chomp_ctx* ctx, const chomp_halo_par* profile,
+                     const chomp_hod_par* hod, unsigned tables) {
+  if (!ctx || !profile || !hod) return fail(ctx, CHOMP_ERR_ARG, "halo_setup: bad args");
+  const std::vector<chomp_hod_model> m = zheng_models(hod, ctx->n_epoch);
+  return chomp_halo_setup_hod(ctx, profile, m.data(), tables);
+}
+
+int chomp_stage_k(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
+                  const chomp_halo_par* profile, const chomp_hod_par* hod, unsigned tables) {
+  if (!ctx || !mass_par || !profile || !hod) return fail(ctx, CHOMP_ERR_ARG, "stage_k: bad args");
+  const std::vector<chomp_hod_model> m = zheng_models(hod, ctx->n_epoch);
+  return chomp_stage_k_hod(ctx, mass_par, mf_kind, profile, m.data(), tables);
 }
 
 int chomp_set_transfer(chomp_ctx* ctx, int kind) {

@@ -63,6 +63,16 @@ int chomp_stage_k_halofit(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf
                           const chomp_halo_par* profile, const chomp_hod_par* hod,
                           unsigned tables, size_t epoch, double f_1, double f_2, double f_3,
                           double omega_l, double w) {
+  if (!ctx || !mass_par || !profile || !hod) return fail(ctx, CHOMP_ERR_ARG, "stage_k_halofit: bad args");
+  const std::vector<chomp_hod_model> m = zheng_models(hod, ctx->n_epoch);
+  return chomp_stage_k_halofit_hod(ctx, mass_par, mf_kind, profile, m.data(), tables, epoch, f_1,
+                                   f_2, f_3, omega_l, w);
+}
+
+int chomp_stage_k_halofit_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
+                              const chomp_halo_par* profile, const chomp_hod_model* hod,
+                              unsigned tables, size_t epoch, double f_1, double f_2,
+                              double f_3, double omega_l, double w) {
   StageRange range_(ctx, "chomp:stage_k_halofit");
   if (!ctx || !mass_par || !profile || !hod) return fail(ctx, CHOMP_ERR_ARG, "stage_k_halofit: bad args");
   if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "stage_k_halofit before epochs_set");

@@ -119,7 +119,7 @@ struct IntegrandGM {       // out[0] = h_g, out[1] = pp_gm
     const double y = y_nfw(*c.e, *c.sici, c.ln_k, lnm);
     double nf, b = 0.0, n1, n2;
     mf_node(*c.e, nu, ln_nu, want_hg, &nf, &b);
-    zheng_node(*c.e, mass, lnm, &n1, &n2);
+    hod_node(*c.e, mass, lnm, &n1, &n2);
     out[0] = nf * b * y * n1 / mass * (want_hg ? c.window(lnm) : 1.0);
     out[1] = (n1 < 1.0) ? nf * n1 * y : nf * n1 * y * y;
   }
@@ -134,7 +134,7 @@ struct IntegrandGG {       // out[0] = pp_gg
     const double y = y_nfw(*c.e, *c.sici, c.ln_k, lnm);
     double nf, b, n1, n2;
     mf_node(*c.e, nu, ln_nu, false, &nf, &b);
-    zheng_node(*c.e, mass, lnm, &n1, &n2);
+    hod_node(*c.e, mass, lnm, &n1, &n2);
     out[0] = (n2 < 1.0) ? nf * n2 * y / mass : nf * n2 * y * y / mass;
   }
 };
@@ -147,7 +147,7 @@ struct IntegrandNbar {     // halo.py:702-707
     const double mass = exp(lnm);
     double nf, b, n1, n2;
     mf_node(*c.e, nu, ln_nu, false, &nf, &b);
-    zheng_node(*c.e, mass, lnm, &n1, &n2);
+    hod_node(*c.e, mass, lnm, &n1, &n2);
     return nf * n1 / mass;
   }
 };
@@ -161,18 +161,21 @@ struct IntegrandHodStat {  // halo.py:745-750 (bias), 786-790 (m_eff), 833-838 (
     const double mass = exp(lnm);
     double nf, b = 1.0, n1, n2;
     mf_node(*c.e, nu, ln_nu, kind == 0, &nf, &b);
-    if (kind == 2) return nf * zheng_satellite(*c.e, mass) / mass;
-    zheng_node(*c.e, mass, lnm, &n1, &n2);
+    if (kind == 2) return nf * hod_satellite(*c.e, mass) / mass;
+    hod_node(*c.e, mass, lnm, &n1, &n2);
     return kind == 0 ? nf * b * n1 / mass : nf * n1;
   }
 };
 
-// HOD-derived constants (hod.py:172-186) are computed on the host (erfinv) and
-// passed in; the lower limits of the HOD integrals follow halo.py:935-939,
-// 1002-1006.
+// HOD-derived constants (hod.py:172-186, 248-259) are computed on the host (erfinv,
+// log10(3), 10**log_M_min) and passed in; the lower limits of the HOD integrals follow
+// halo.py:935-939, 1002-1006.  model: CHOMP_HOD_*; a Mandelbaum HOD has log_M_min = log10(3) +
+// log_M_0, sigma = 0, alpha = 1, no moment zeros and w, M_min of its own.
 struct HodDev {
   double log_M_min, sigma, log_M_0, log_M_1p, alpha;
   double first_zero, second_zero, safe_norm;
+  int model, pad_;
+  double w, M_min;
 };
 
 // Halo-profile and HOD constants of one epoch (Halo.__init__, halo.py:71-88; the
@@ -186,6 +189,7 @@ __device__ __forceinline__ void apply_halo_hod(Epoch& E, const chomp_halo_par& h
   E.hod_log_M_1p = h.log_M_1p; E.hod_alpha = h.alpha;
   E.hod_first_zero = h.first_zero; E.hod_second_zero = h.second_zero;
   E.hod_safe_norm = h.safe_norm;
+  E.hod_model = h.model; E.hod_w = h.w; E.hod_M_min = h.M_min;
   E.hod_M0 = pow(10.0, h.log_M_0);
   E.hod_M1p = pow(10.0, h.log_M_1p);
   const double dlnm = (E.ln_mass_max - E.ln_mass_min) / (double)(NM - 1);
@@ -237,6 +241,7 @@ __device__ __forceinline__ void apply_halo_hod_wave(Epoch& E, const chomp_halo_p
     E.hod_log_M_1p = h.log_M_1p; E.hod_alpha = h.alpha;
     E.hod_first_zero = h.first_zero; E.hod_second_zero = h.second_zero;
     E.hod_safe_norm = h.safe_norm;
+    E.hod_model = h.model; E.hod_w = h.w; E.hod_M_min = h.M_min;
     E.hod_M0 = M0;
     E.hod_M1p = M1p;
     E.ln_nu_lo_first = ln_nu1;
@@ -292,8 +297,8 @@ __device__ __forceinline__ void halo_node_fields(const Epoch& E, const double* n
   const double cp = 1.0 + con;
   const double ln_cp = log(cp);
   // state: the discrete state of the integrand at the node (halo_eval_coded's code): bit 0 the
-  // occupation below one (which power of y, halo.py:1038-1041, 1084-1086), bit 1 satellites
-  // on, bit 2 a step-function central occupation above its threshold
+  // occupation below one (which power of y, halo.py:1038-1041, 1084-1086), bits 1 and 2 the
+  // occupation model's own (hod_node)
   double wA, wB;
   int state = 0;
   if (group == 0) {
@@ -304,9 +309,7 @@ __device__ __forceinline__ void halo_node_fields(const Epoch& E, const double* n
     wB = nf * bias * mass;
   } else {
     double n1, n2;
-    zheng_node(E, mass, lnm, &n1, &n2);
-    state = (mass - E.hod_M0 > 0.0) ? 2 : 0;
-    if (E.hod_sigma <= 0.0 && lnm * 0.43429448190325182765 > E.hod_log_M_min) state |= 4;
+    state = hod_node(E, mass, lnm, &n1, &n2);
     if (group == 1) {
       wA = nf * bias * n1 / mass;
       wB = nf * n1;
@@ -701,7 +704,7 @@ inline void deep_weights_host(int LC, int top, double* w) {
 }
 
 // One node of a knot's integrand pair together with the discrete state of the integrand
-// there (which branch of every `if` of halo.py:1038-1041, 1084-1086 and hod.py:189-230 is
+// there (which branch of every `if` of halo.py:1038-1041, 1084-1086 and hod.py:189-230, 281-299 is
 // taken): the integrand is smooth wherever the state does not change.  Same arithmetic as
 // IntegrandMM / GM / GG; group 2 has one integrand (out[0] = 0).
 __device__ __forceinline__ void halo_eval_coded(int group, const HaloCtx& c, double ln_nu,
@@ -726,9 +729,7 @@ __device__ __forceinline__ void halo_eval_coded(int group, const HaloCtx& c, dou
   }
   const double mass = exp(lnm);
   double n1, n2;
-  zheng_node(E, mass, lnm, &n1, &n2);
-  int st = (mass - E.hod_M0 > 0.0) ? 2 : 0;                    // satellites on
-  if (E.hod_sigma <= 0.0 && lnm * 0.43429448190325182765 > E.hod_log_M_min) st |= 4;
+  int st = hod_node(E, mass, lnm, &n1, &n2);
   if (group == 1) {
     out[0] = nf * b * y * n1 / mass * c.window(lnm);
     out[1] = (n1 < 1.0) ? nf * n1 * y : nf * n1 * y * y;
@@ -750,9 +751,7 @@ __device__ __forceinline__ int halo_state_at(int group, const HaloCtx& c, double
   const double lnm = spline_eval(c.nu_knots, c.lnm_pp, c.NM, nu);
   const double mass = exp(lnm);
   double n1, n2;
-  zheng_node(E, mass, lnm, &n1, &n2);
-  int st = (mass - E.hod_M0 > 0.0) ? 2 : 0;
-  if (E.hod_sigma <= 0.0 && lnm * 0.43429448190325182765 > E.hod_log_M_min) st |= 4;
+  int st = hod_node(E, mass, lnm, &n1, &n2);
   st |= ((group == 1 ? n1 : n2) < 1.0) ? 1 : 0;
   return st;
 }

@@ -561,6 +561,10 @@ struct Epoch {
   // HOD (hod.py:156-186)
   double hod_log_M_min, hod_sigma, hod_log_M_0, hod_log_M_1p, hod_alpha;
   double hod_first_zero, hod_second_zero, hod_safe_norm, hod_M0, hod_M1p;
+  // the occupation model (CHOMP_HOD_*) and Mandelbaum's w and M_min = 10**log_M_min (its
+  // log_M_0 / log_M_min are hod_log_M_0 / hod_log_M_min)
+  int hod_model, pad_hod;
+  double hod_w, hod_M_min, pad_hod_d;
   double ln_nu_lo_first, ln_nu_lo_second;
   double n_bar_over_rho_bar, n_bar;
   // HaloFit (halo.py:1261-1319)
@@ -989,6 +993,66 @@ CHOMP_HD double zheng_first(const Epoch& e, double mass) {
 }
 CHOMP_HD double zheng_second(const Epoch& e, double mass) {
   const double ns = zheng_satellite(e, mass);
+  return (2.0 + ns) * ns;
+}
+
+// ---------------------------------------------------------------------------
+// Mandelbaum et al. 2005 HOD moments (hod.py:232-299): one central galaxy from M_0 up, and
+// satellites w (M / M_min)^2 below M_min = 3 M_0, w M / M_min from there (not multiplied by
+// the central term).  Both thresholds are decided as the reference decides them: on log10 of
+// the mass (`>=` for the central step, `<` for the lower satellite branch).
+// ---------------------------------------------------------------------------
+constexpr int kHodZheng = 0, kHodMandelbaum = 1;      // (= CHOMP_HOD_*, include/chomp_mi355x.h)
+// HODMandelbaum.__init__ (hod.py:248-259): log_M_min = log10(3) + log_M_0, and the 10**log_M_min
+// the moments divide by (computed once on the host, as the reference computes them).
+CHOMP_HD void mandelbaum_constants(double log_M_0, double* log_M_min, double* M_min) {
+  *log_M_min = log10(3.0) + log_M_0;
+  *M_min = pow(10.0, *log_M_min);
+}
+CHOMP_HD double mandelbaum_central(const Epoch& e, double mass) {
+  return log10(mass) >= e.hod_log_M_0 ? 1.0 : 0.0;
+}
+CHOMP_HD double mandelbaum_satellite_lm(const Epoch& e, double mass, double lm) {
+  const double r = mass / e.hod_M_min;
+  return lm < e.hod_log_M_min ? r * r * e.hod_w : r * e.hod_w;
+}
+CHOMP_HD double mandelbaum_satellite(const Epoch& e, double mass) {
+  return mandelbaum_satellite_lm(e, mass, log10(mass));
+}
+
+// The HOD moments at an integrand node of the epoch's model (a branch uniform per epoch), and
+// the discrete state the occupation puts the integrand in: bit 1 Zheng's satellites on /
+// Mandelbaum's upper satellite branch, bit 2 a step central occupation at or above its
+// threshold.  (Bit 0, which power of y the integrand takes, is the caller's.)
+CHOMP_HD int hod_node(const Epoch& e, double mass, double ln_mass, double* n_first,
+                      double* n_second) {
+  if (e.hod_model == kHodMandelbaum) {
+    const double lm = log10(mass);
+    const double nc = lm >= e.hod_log_M_0 ? 1.0 : 0.0;
+    const double ns = mandelbaum_satellite_lm(e, mass, lm);
+    *n_first = nc + ns;
+    *n_second = (2.0 + ns) * ns;
+    return (lm < e.hod_log_M_min ? 0 : 2) | (nc > 0.0 ? 4 : 0);
+  }
+  zheng_node(e, mass, ln_mass, n_first, n_second);
+  int st = (mass - e.hod_M0 > 0.0) ? 2 : 0;
+  if (e.hod_sigma <= 0.0 && ln_mass * 0.43429448190325182765 > e.hod_log_M_min) st |= 4;
+  return st;
+}
+
+// The four moments of the CHOMP_EV_HOD_* evaluator (and f_sat's N_sat), for the epoch's model.
+CHOMP_HD double hod_central(const Epoch& e, double mass) {
+  return e.hod_model == kHodMandelbaum ? mandelbaum_central(e, mass) : zheng_central(e, mass);
+}
+CHOMP_HD double hod_satellite(const Epoch& e, double mass) {
+  return e.hod_model == kHodMandelbaum ? mandelbaum_satellite(e, mass)
+                                              : zheng_satellite(e, mass);
+}
+CHOMP_HD double hod_first(const Epoch& e, double mass) {
+  return hod_central(e, mass) + hod_satellite(e, mass);
+}
+CHOMP_HD double hod_second(const Epoch& e, double mass) {
+  const double ns = hod_satellite(e, mass);
   return (2.0 + ns) * ns;
 }
 

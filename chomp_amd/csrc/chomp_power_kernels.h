@@ -762,10 +762,10 @@ __global__ void k_eval(TabLayout L, const Epoch* __restrict__ epochs, int e,
       case CHOMP_EV_LN_MASS_OF_NU: r = spline_eval(nu_knots, lnm_pp, NM, v); break;
       case CHOMP_EV_F_NU: r = f_nu(E, v); break;
       case CHOMP_EV_BIAS_NU: r = bias_nu(E, v); break;
-      case CHOMP_EV_HOD_FIRST: r = zheng_first(E, v); break;
-      case CHOMP_EV_HOD_SECOND: r = zheng_second(E, v); break;
-      case CHOMP_EV_HOD_CENTRAL: r = zheng_central(E, v); break;
-      case CHOMP_EV_HOD_SATELLITE: r = zheng_satellite(E, v); break;
+      case CHOMP_EV_HOD_FIRST: r = hod_first(E, v); break;
+      case CHOMP_EV_HOD_SECOND: r = hod_second(E, v); break;
+      case CHOMP_EV_HOD_CENTRAL: r = hod_central(E, v); break;
+      case CHOMP_EV_HOD_SATELLITE: r = hod_satellite(E, v); break;
       case CHOMP_EV_VIRIAL_RADIUS: r = exp((E.ln_rv_const + log(v)) * (1.0 / 3.0)); break;
       case CHOMP_EV_CONCENTRATION: r = exp(E.ln_c_const + E.beta * log(v)); break;
       case CHOMP_EV_DELTA_K:

@@ -41,6 +41,11 @@ def unshard_order(n, world):
     return [(i % world) * rpr + i // world for i in range(n)]
 
 
+def _hod_object(h):
+    """An HOD object as it is; a dictionary as HODZheng(dict)."""
+    return h if isinstance(h, hod_mod.HOD) else hod_mod.HODZheng(h)
+
+
 class HaloGrid(object):
     """P(k, z) for a batch of epochs on one GPU (or this rank's shard of it).
 
@@ -48,6 +53,8 @@ class HaloGrid(object):
     dicts (one per epoch); mass_function: 'st' or 'tinker'; halo_dict, hod_dict:
     one dict (or list).  Every epoch follows the reference's construction order
     Halo(z, HODZheng(hod_dict), SingleEpoch(z, cosmo_dict), MassFunction(...)).
+    hod_dict may also hold HOD objects (hod.HODZheng / hod.HODMandelbaum, one or one per
+    epoch, the models mixed freely); a dictionary always means HODZheng(hod_dict).
     """
 
     def __init__(self, z, cosmo_dict=None, halo_dict=None, hod_dict=None,
@@ -66,8 +73,8 @@ class HaloGrid(object):
         self.halo = pick(halo_dict if halo_dict is not None
                          else defaults.default_halo_dict)
         hd = hod_dict if hod_dict is not None else defaults.default_hod_dict
-        self.hod = ([hod_mod.HODZheng(h) for h in pick(hd)]
-                    if isinstance(hd, (list, tuple)) else hod_mod.HODZheng(hd))
+        self.hod = ([_hod_object(h) for h in pick(hd)]
+                    if isinstance(hd, (list, tuple)) else _hod_object(hd))
         self.kind = {"st": _lib.MF_ST, "tinker": _lib.MF_TINKER}[mass_function]
         self.z = self.z_all[self.idx]
         self.ctx = cosmology._context(stream=stream, device=device)
@@ -84,7 +91,7 @@ class HaloGrid(object):
     def set_parameters(self, cosmo=None, halo=None, hod=None, delta_b=None):
         """New parameters for this rank's epochs, taking effect at the next setup(): the step of
         an MCMC / design loop.  Each argument: None (keep), one dict, a list with one dict per
-        local epoch, or the packed ctypes array (Context.pack_*; cosmo also as a float64 array
+        local epoch (hod: HOD objects as well, see the class), or the packed ctypes array (Context.pack_*; cosmo also as a float64 array
         [n_local, 10]) -- packing once outside the loop keeps the host out of the step.
         delta_b: HaloSuperSampleCovariance's delta_b (power_mm_ssc), a scalar or one value per
         local epoch; it alone needs no new set-up."""
@@ -106,8 +113,8 @@ class HaloGrid(object):
             self._c_halo = halo if isinstance(halo, ctypes.Array) else self.ctx.pack_halo(halo, n)
         if hod is not None:
             if not isinstance(hod, ctypes.Array):
-                hod = self.ctx.pack_hod([hod_mod.HODZheng(h) for h in hod]
-                                        if isinstance(hod, (list, tuple)) else hod_mod.HODZheng(hod), n)
+                hod = self.ctx.pack_hod([_hod_object(h) for h in hod]
+                                        if isinstance(hod, (list, tuple)) else _hod_object(hod), n)
             self._c_hod = hod
         assert len(self._c_cosmo) == n and len(self._c_halo) == n and len(self._c_hod) == n
         self._tables = 0

@@ -28,6 +28,15 @@ _FLAG_BITS = (("_initialized_h_m", _lib.T_H_M), ("_initialized_pp_mm", _lib.T_PP
               ("_initialized_pp_gg", _lib.T_PP_GG))
 
 
+def _check_hod(input_hod):
+    """What the reference's _calculate_n_bar (halo.py:91, 194-212) reads of an HOD first: an
+    HODMandelbaum built without a dictionary lacks first_moment_zero and _safe_norm
+    (hod.py:250-253) and fails there with AttributeError."""
+    if isinstance(input_hod, hod.HODMandelbaum):
+        input_hod.first_moment_zero       # noqa: B018 (the attribute access is the check)
+        input_hod._safe_norm              # noqa: B018
+
+
 class Halo(object):
     """Seljak (2000) halo model (halo.py:23-1086)."""
 
@@ -61,6 +70,7 @@ class Halo(object):
         self._h = self.cosmo._h
         if input_hod is None:
             input_hod = hod.HODZheng()
+        _check_hod(input_hod)
         self.local_hod = input_hod
         self._extrapolate = extrapolate
         # the dictionary the PROFILE sees: fixed here, untouched by set_halo
@@ -248,6 +258,7 @@ class Halo(object):
 
     def set_hod_object(self, input_hod):
         """halo.py:194-212."""
+        _check_hod(input_hod)
         self.local_hod = input_hod
         self._nbar_valid = False
         self._reset_flags(all_tables=False)

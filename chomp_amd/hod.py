@@ -1,7 +1,7 @@
-"""hod.HOD / hod.HODZheng (hod.py:17-230): parameter holders with the reference's
-attribute and method names.  Inside the halo-model integrals the moments are
-evaluated on the device (chomp_math.h zheng_*); the public first_moment() /
-second_moment() accessors below are the same one-line closed forms."""
+"""hod.HOD / hod.HODZheng / hod.HODMandelbaum (hod.py:17-299): parameter holders with the
+reference's attribute and method names.  Inside the halo-model integrals the moments are
+evaluated on the device (chomp_math.h zheng_* / mandelbaum_*, dispatched by hod_node); the
+public first_moment() / second_moment() accessors below are the same one-line closed forms."""
 import math
 
 import numpy
@@ -137,6 +137,41 @@ class HODZheng(HOD):
     def second_moment(self, mass, z=None):
         n_sat = self.satellite_first_moment(mass)
         return (2 + n_sat) * n_sat
+
+
+class HODMandelbaum(HOD):
+    """Mandelbaum et al. 2005 HOD (hod.py:232-299): one central galaxy from M_0 up; satellites
+    w (M / M_min)^2 below M_min = 3 M_0 and w M / M_min above, independent of the central term.
+
+    As in the reference, without a dictionary HOD.__init__ is never called (hod.py:250-253): the
+    object has no hod_dict, first_moment_zero or _safe_norm, and a Halo built on it fails with
+    AttributeError.  set_hod(dict) re-initialises it."""
+
+    def __init__(self, hod_dict=None):
+        if hod_dict is None:
+            self.log_M_0 = 12.14
+            self.log_M_min = numpy.log10(3.0) + 12.14
+            self.w = 1.0
+        else:
+            self.log_M_0 = hod_dict["log_M_0"]
+            self.log_M_min = numpy.log10(3.0) + hod_dict["log_M_0"]
+            self.w = hod_dict["w"]
+            HOD.__init__(self, hod_dict)
+
+    def first_moment(self, mass, z=None):
+        return self.central_first_moment(mass) + self.satellite_first_moment(mass)
+
+    def second_moment(self, mass, z=None):
+        n_sat = self.satellite_first_moment(mass)
+        return (2 + n_sat) * n_sat
+
+    def central_first_moment(self, mass, z=None):
+        return numpy.where(numpy.log10(mass) >= self.log_M_0, 1.0, 0.0)
+
+    def satellite_first_moment(self, mass, z=None):
+        return numpy.where(numpy.log10(mass) < self.log_M_min,
+                           (mass / 10 ** self.log_M_min) ** 2 * self.w,
+                           mass / 10 ** self.log_M_min * self.w)
 
 
 class HODPoisson(HOD):

@@ -19,6 +19,7 @@ from . import _lib
 from . import defaults
 from . import grid
 from . import halo as halo_mod
+from . import hod as hod_mod
 
 default_parameter_dict = {"cosmo_dict": defaults.default_cosmo_dict,
                           "halo_dict": defaults.default_halo_dict,
@@ -34,6 +35,15 @@ def _hod_dict_of(h):
     if d is None:
         d = {key: getattr(h, key) for key in ("log_M_min", "sigma", "log_M_0", "log_M_1p", "alpha")}
     return dict(d)
+
+
+def _point_hod(local_hod, hod_dict):
+    """The HOD of one design point for the batch, in the halo's own model: Halo.set_hod re-
+    initialises the halo's HOD object from the point's dictionary (halo.py:181-192).  A Zheng HOD
+    goes as its dictionary (HaloGrid reads that as HODZheng)."""
+    if isinstance(local_hod, hod_mod.HODMandelbaum):
+        return hod_mod.HODMandelbaum(hod_dict) if hod_dict is not None else local_hod
+    return hod_dict if hod_dict is not None else _hod_dict_of(local_hod)
 
 
 def random_lhs(n, k):
@@ -143,7 +153,7 @@ class SimulationDesign(object):
                 self._apply_point(point)
                 cosmos.append(rec.cosmo if rec.cosmo is not None else dict(obj.cosmo.cosmo_dict))
                 halos.append(dict(obj.mass.halo_dict))
-                hods.append(rec.hod if rec.hod is not None else _hod_dict_of(obj.local_hod))
+                hods.append(_point_hod(obj.local_hod, rec.hod))
         finally:
             self._input_object = real
         kind = "tinker" if getattr(obj.mass, "_kind", 0) else "st"

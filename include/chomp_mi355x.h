@@ -54,6 +54,21 @@ typedef struct chomp_hod_par {
   double log_M_min, sigma, log_M_0, log_M_1p, alpha;
 } chomp_hod_par;
 
+/* Occupation models (chomp_hod_model.kind). */
+#define CHOMP_HOD_ZHENG 0
+#define CHOMP_HOD_MANDELBAUM 1
+
+/* One epoch's HOD, tagged by its model: hod.HODZheng (CHOMP_HOD_ZHENG: `zheng`) or
+ * hod.HODMandelbaum (hod.py:232-299, CHOMP_HOD_MANDELBAUM: log_M_0 and w; the library derives
+ * log_M_min = log10(3) + log_M_0 and 10**log_M_min as the reference does, and -- the HOD has no
+ * moment zeros and no safe norm -- integrates every HOD integral over the whole nu range).
+ * `reserved` must be 0; the fields of the other model are ignored. */
+typedef struct chomp_hod_model {
+  int kind, reserved;
+  chomp_hod_par zheng;
+  double log_M_0, w;
+} chomp_hod_model;
+
 /* Snapshot of defaults.default_limits + defaults.default_precision
  * (defaults.py:42-51, 62-92), taken when the context is created. */
 typedef struct chomp_config {
@@ -155,6 +170,10 @@ int chomp_mass_setup(chomp_ctx* ctx, const chomp_halo_par* par, int mf_kind);
  * which does not rebuild the profile splines). */
 int chomp_halo_setup(chomp_ctx* ctx, const chomp_halo_par* profile,
                      const chomp_hod_par* hod, unsigned tables);
+/* The same with one tagged HOD model per epoch (the models may differ from epoch to epoch);
+ * chomp_halo_setup(hod) is chomp_halo_setup_hod with CHOMP_HOD_ZHENG models of hod. */
+int chomp_halo_setup_hod(chomp_ctx* ctx, const chomp_halo_par* profile,
+                         const chomp_hod_model* hod, unsigned tables);
 
 /* chomp_mass_setup followed by chomp_halo_setup in fewer launches (the mass function's tail
  * and the halo model's node tables share a kernel): what a batch that always builds both --
@@ -162,6 +181,10 @@ int chomp_halo_setup(chomp_ctx* ctx, const chomp_halo_par* profile,
 int chomp_stage_k(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
                   const chomp_halo_par* profile, const chomp_hod_par* hod,
                   unsigned tables);
+/* The same with one tagged HOD model per epoch (see chomp_halo_setup_hod). */
+int chomp_stage_k_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
+                      const chomp_halo_par* profile, const chomp_hod_model* hod,
+                      unsigned tables);
 
 /* chomp_stage_k followed by chomp_halofit_setup(epoch, epoch, ...) in one call -- a HaloFit
  * object's first set-up (halo.py:1236-1266 then 1268-1319).  Same results, bit for bit; the
@@ -171,6 +194,11 @@ int chomp_stage_k_halofit(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf
                           const chomp_halo_par* profile, const chomp_hod_par* hod,
                           unsigned tables, size_t epoch, double f_1, double f_2, double f_3,
                           double omega_l, double w);
+/* The same with one tagged HOD model per epoch (see chomp_halo_setup_hod). */
+int chomp_stage_k_halofit_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kind,
+                              const chomp_halo_par* profile, const chomp_hod_model* hod,
+                              unsigned tables, size_t epoch, double f_1, double f_2,
+                              double f_3, double omega_l, double w);
 
 /* HaloFit._initialize_sigma_spline (halo.py:1268-1319) for epoch `src_epoch`,
  * stored as the HaloFit coefficient set of epoch `dst_epoch`; f_1..f_3, omega_l
@@ -214,7 +242,8 @@ int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k,
 
 /* Element-wise lookups of one epoch (host or device buffers):
  * MassFunction.nu / ln_mass / f_nu / bias_nu (mass_function.py:243-346),
- * HODZheng moments (hod.py:189-230), Halo.virial_radius / concentration
+ * the moments of the epoch's HOD model (HODZheng hod.py:189-230, HODMandelbaum hod.py:261-299),
+ * Halo.virial_radius / concentration
  * (halo.py:441-463), SingleEpoch.delta_k (cosmology.py:574-587). */
 #define CHOMP_EV_NU_OF_MASS 0
 #define CHOMP_EV_LN_MASS_OF_NU 1
@@ -585,7 +614,8 @@ int chomp_set_transfer(chomp_ctx* ctx, int kind);
 
 /* Halo.calculate_bias / calculate_m_eff / calculate_f_sat (halo.py:709-838) of epochs
  * [epoch0, epoch0 + n): out[3 i + {0, 1, 2}] = effective bias, effective halo mass,
- * satellite fraction (host buffer).  Needs chomp_halo_setup (n_bar). */
+ * satellite fraction (host buffer), each with the epoch's HOD model.  Needs chomp_halo_setup
+ * (n_bar). */
 int chomp_hod_stats(chomp_ctx* ctx, size_t epoch0, size_t n, double* out);
 
 /* Correlation3d.raw_correlation(r) (correlation.py:470-499): xi(r) = int dlnk k^2/(2 pi)
