@@ -70,6 +70,7 @@ class HodPar(ctypes.Structure):
 
 
 HOD_ZHENG, HOD_MANDELBAUM = 0, 1
+DE_EPOCH, DE_PROJ = 0, 1       # chomp_get_de_table sources
 
 
 class HodModel(ctypes.Structure):
@@ -121,10 +122,12 @@ EXPORTS = [
     "chomp_kernel_ssc_setup", "chomp_kernel_ssc_raw", "chomp_kernel_ssc_eval",
     "chomp_covariance_ssc",
     "chomp_halo_setup_hod", "chomp_stage_k_hod", "chomp_stage_k_halofit_hod",
+    "chomp_set_dark_energy", "chomp_get_de_table",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
 ST_MASS_MIN_SATURATED, ST_MASS_MAX_SATURATED, ST_MASS_SEARCH_EXHAUSTED, ST_SIGMA_DIVMAX = 1, 2, 4, 8
+ST_DE_DIVMAX = 0x10
 ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000,
                   "i_1_2": 0x2000}
 ST_NONFINITE = 0x10000
@@ -158,6 +161,8 @@ def describe_status(word):
         out.append("mass-limit search did not end within 2047 steps of 5 %")
     if word & ST_SIGMA_DIVMAX:
         out.append("a sigma(R) Romberg of the nu table exhausted divmax")
+    if word & ST_DE_DIVMAX:
+        out.append("a Romberg of the dark-energy pressure table exhausted divmax")
     for name, bit in ST_HALO_DIVMAX.items():
         if word & bit:
             out.append("%s: Romberg exhausted divmax at some knots (last row kept)" % name)
@@ -366,6 +371,8 @@ def lib():
         L.chomp_set_precision.argtypes = [vp, i]
         L.chomp_hod_stats.argtypes = [vp, sz, sz, c_double_p]
         L.chomp_set_transfer.argtypes = [vp, i]
+        L.chomp_set_dark_energy.argtypes = [vp, i]
+        L.chomp_get_de_table.argtypes = [vp, i, sz, i, c_double_p, sz]
         L.chomp_set_timing.argtypes = [vp, i]
         L.chomp_get_timing.argtypes = [vp, c_double_p, sz]
         L.chomp_get_status.argtypes = [vp, sz, sz, ctypes.POINTER(ctypes.c_uint)]
@@ -571,9 +578,12 @@ class Context(object):
             hods = [hods] * n
         return (HodModel * n)(*[hod_model(h) for h in hods])
 
-    def epochs_set(self, cosmo, z, with_bao=False):
-        """with_bao: SingleEpoch(with_bao=True), the E&H transfer function with wiggles."""
+    def epochs_set(self, cosmo, z, with_bao=False, dark_energy=False):
+        """with_bao: SingleEpoch(with_bao=True), the E&H transfer function with wiggles.
+        dark_energy: accept w0-wa cosmologies (chomp_set_dark_energy); off, they raise
+        ChompScopeError."""
         self._check(self._L.chomp_set_transfer(self._h, 1 if with_bao else 0))
+        self._check(self._L.chomp_set_dark_energy(self._h, 1 if dark_energy else 0))
         z = numpy.ascontiguousarray(numpy.atleast_1d(z), dtype=numpy.float64)
         n = z.size
         arr = cosmo if isinstance(cosmo, ctypes.Array) else self.pack_cosmo(cosmo, n)
@@ -788,18 +798,38 @@ class Context(object):
 
     # -- projection ------------------------------------------------------------
     def kernel_setup(self, cosmo_dict, me_z_min, me_z_max, ktheta_min, ktheta_max,
-                     wa, wb, bessel_order):
+                     wa, wb, bessel_order, dark_energy=False):
         c = cosmo_struct(cosmo_dict)
+        self._check(self._L.chomp_set_dark_energy(self._h, 1 if dark_energy else 0))
         self._proj_ssc = None            # (a projection set-up drops the kernel_ssc table)
         self._check(self._L.chomp_kernel_setup(
             self._h, ctypes.byref(c), me_z_min, me_z_max, ktheta_min, ktheta_max,
             ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)))
 
-    def multi_epoch_setup(self, cosmo_dict, z_min, z_max):
+    def multi_epoch_setup(self, cosmo_dict, z_min, z_max, dark_energy=False):
         c = cosmo_struct(cosmo_dict)
+        self._check(self._L.chomp_set_dark_energy(self._h, 1 if dark_energy else 0))
         self._proj_ssc = None
         self._check(self._L.chomp_multi_epoch_setup(self._h, ctypes.byref(c),
                                                     float(z_min), float(z_max)))
+
+    def de_table(self, source="epoch", epoch=0):
+        """The dark-energy pressure table of epoch `epoch`'s cosmology (source "epoch") or of
+        the projection set-up's (source "proj"): dict of ln_a, pressure, levels (int),
+        converged (bool) [cosmo_npoints] and the spline's coefficients pp [cosmo_npoints - 1, 4]."""
+        n = self.config.cosmo_npoints
+        src = {"epoch": DE_EPOCH, "proj": DE_PROJ}[source]
+        out = {}
+        for name, what, size in (("ln_a", 0, n), ("pressure", 1, n), ("levels", 2, n),
+                                 ("converged", 3, n), ("pp", 4, 4 * (n - 1))):
+            v = numpy.empty(size)
+            self._check(self._L.chomp_get_de_table(self._h, src, epoch, what,
+                                                   v.ctypes.data_as(c_double_p), size))
+            out[name] = v
+        out["levels"] = out["levels"].astype(numpy.int64)
+        out["converged"] = out["converged"] != 0.0
+        out["pp"] = out["pp"].reshape(n - 1, 4)
+        return out
 
     def me_eval(self, what, x):
         if _is_torch(x):

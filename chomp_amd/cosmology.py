@@ -4,12 +4,46 @@ surface (cosmology.py:25-728, 731-1164), backed by the HIP library.
 Numbers with an integral behind them (chi, sigma_8 normalisation, sigma_r, the
 linear spectrum) come from the device; closed-form background functions of an
 arbitrary redshift argument (E, E0, w) are one-line formulas kept on the host, as
-they are in the reference.
+they are in the reference.  A w0-wa cosmology (w0 != -1 or wa != 0) multiplies Omega_L0 in
+E0 by exp(P(ln a)), the reference's dark-energy pressure spline (cosmology.py:96-104,
+165-213): its knots are tabulated on the device, and the host evaluates the same spline.
 """
 import numpy
 
 from . import _lib
 from . import defaults
+
+
+def has_dark_energy(cosmo_dict):
+    """cosmology.py:96: dark energy is active iff w0 != -1 or wa != 0."""
+    return cosmo_dict["w0"] != -1.0 or cosmo_dict["wa"] != 0.0
+
+
+def _de_kw(cosmos):
+    """The opt-in of the set-up calls (_lib.Context.epochs_set / multi_epoch_setup /
+    kernel_setup) for `cosmos`: a dictionary, a sequence of dictionaries, a ctypes array of
+    _lib.Cosmo or a float64 array [n, 10].  {"dark_energy": True} when some cosmology has w0-wa
+    dark energy; {} otherwise, so that a Lambda-CDM set-up is called as it always was."""
+    if isinstance(cosmos, dict):
+        return {"dark_energy": True} if has_dark_energy(cosmos) else {}
+    if isinstance(cosmos, numpy.ndarray):
+        a = numpy.asarray(cosmos, dtype=numpy.float64).reshape(-1, 10)
+        de = bool(numpy.any((a[:, 8] != -1.0) | (a[:, 9] != 0.0)))
+    else:
+        de = any((c.w0 != -1.0 or c.wa != 0.0) if isinstance(c, _lib.Cosmo)
+                 else has_dark_energy(c) for c in cosmos)
+    return {"dark_energy": True} if de else {}
+
+
+def _de_spline_eval(tab, ln_a):
+    """The pressure spline of a device table (_lib.Context.de_table) at ln a, evaluated as the
+    device evaluates it (piecewise cubic, end pieces extrapolated as FITPACK does)."""
+    x = numpy.asarray(ln_a, dtype=numpy.float64)
+    knots, pp = tab["ln_a"], tab["pp"]
+    i = numpy.clip(numpy.searchsorted(knots, x, side="right") - 1, 0, knots.size - 2)
+    d = x - knots[i]
+    c = pp[i]
+    return ((c[..., 3] * d + c[..., 2]) * d + c[..., 1]) * d + c[..., 0]
 
 
 def _context(stream=None, device=None):
@@ -21,8 +55,8 @@ def _context(stream=None, device=None):
 
 
 class SingleEpoch(object):
-    """cosmology.py:25-728.  w0/wa != -1/0 are outside the accelerated scope.  As in the
-    reference, set_cosmology() re-runs __init__ without with_bao, i.e. switches it off."""
+    """cosmology.py:25-728, w0-wa dark energy included.  As in the reference, set_cosmology()
+    re-runs __init__ without with_bao, i.e. switches it off."""
 
     def __init__(self, redshift, cosmo_dict=None, with_bao=False, **kws):
         if redshift < 0.0:
@@ -43,15 +77,37 @@ class SingleEpoch(object):
         self._k_max = defaults.default_limits['k_max']
         self._ctx = None
         self._sc = None
+        self._de = None           # the dark-energy table (_lib.Context.de_table), when fetched
 
     # -- device state ----------------------------------------------------------
     def _dev(self):
         if self._ctx is None:
             self._ctx = _context()
         if self._sc is None:
-            self._ctx.epochs_set(self.cosmo_dict, [self._redshift], self._with_bao)
+            self._ctx.epochs_set(self.cosmo_dict, [self._redshift], self._with_bao,
+                                 **_de_kw(self.cosmo_dict))
             self._sc = self._ctx.scalars(0)
         return self._ctx
+
+    def _de_table(self):
+        """The pressure table of this cosmology (it does not depend on the redshift)."""
+        if self._de is None:
+            self._de = self._dev().de_table("epoch", 0)
+        return self._de
+
+    @property
+    def _de_pressure_array(self):
+        """cosmology.py:102: P at the knots a = logspace(log10(cosmo_precision), 0,
+        cosmo_npoints) (AttributeError without dark energy, as in the reference)."""
+        if not has_dark_energy(self.cosmo_dict):
+            raise AttributeError("'SingleEpoch' object has no attribute '_de_pressure_array'")
+        return self._de_table()["pressure"].copy()
+
+    def _de_pressure_spline(self, ln_a):
+        """cosmology.py:103-104: the pressure spline at ln a."""
+        if not has_dark_energy(self.cosmo_dict):
+            raise AttributeError("'SingleEpoch' object has no attribute '_de_pressure_spline'")
+        return _de_spline_eval(self._de_table(), ln_a)
 
     def _scalar(self, name):
         self._dev()
@@ -81,8 +137,11 @@ class SingleEpoch(object):
 
     def E0(self, redshift):
         a = 1.0 / (1.0 + redshift)
-        return (self._omega_l0 + self._omega_m0 / (a * a * a) +
-                self._omega_r0 / (a * a * a * a))
+        if self._w0 == -1.0 and self._wa == 0.0:
+            return (self._omega_l0 + self._omega_m0 / (a * a * a) +
+                    self._omega_r0 / (a * a * a * a))
+        return (self._omega_l0 * numpy.exp(self._de_pressure_spline(numpy.log(a))) +
+                self._omega_m0 / (a * a * a) + self._omega_r0 / (a * a * a * a))
 
     def E(self, redshift):
         return 1.0 / (self.H0 * numpy.sqrt(self.E0(redshift)))
@@ -211,15 +270,25 @@ class MultiEpoch(object):
         self._k_min, self._k_max = e0._k_min, e0._k_max
         self._ctx = None
         self._sig = None
+        if self._w0 != -1:                         # (cosmology.py:773-774, never filled in)
+            self._de_pressure_array = numpy.zeros(defaults.default_precision["cosmo_npoints"])
 
     def _dev(self):
         if self._ctx is None:
             self._ctx = _context()
         sig = (tuple(sorted(self.cosmo_dict.items())), self.z_min, self.z_max)
         if sig != self._sig:
-            self._ctx.multi_epoch_setup(self.cosmo_dict, self.z_min, self.z_max)
+            de = _de_kw(self.cosmo_dict)
+            self._ctx.multi_epoch_setup(self.cosmo_dict, self.z_min, self.z_max, **de)
+            if de:       # (epoch0's E0 takes the same table: no SingleEpoch set-up behind it)
+                self.epoch0._de = self._ctx.de_table("proj")
             self._sig = sig
         return self._ctx
+
+    def _de_ready(self):
+        """E0 of a w0-wa cosmology needs the pressure table: this MultiEpoch's own."""
+        if has_dark_energy(self.cosmo_dict) and self.epoch0._de is None:
+            self.epoch0._de = self._dev().de_table("proj")
 
     _z_array = property(lambda self: self._dev().kernel_table("me_z"))
     _chi_array = property(lambda self: self._dev().kernel_table("me_chi"))
@@ -245,6 +314,7 @@ class MultiEpoch(object):
         self._ctx = ctx
 
     def E(self, redshift):
+        self._de_ready()
         return self.epoch0.E(redshift)
 
     def comoving_distance(self, redshift):
@@ -265,11 +335,13 @@ class MultiEpoch(object):
     def omega_m(self, redshift=None):
         if redshift is None:
             redshift = 0.0
+        self._de_ready()
         return self._omega_m0 * (1.0 + redshift) ** 3 / self.epoch0.E0(redshift)
 
     def omega_l(self, redshift=None):
         if redshift is None:
             redshift = 0.0
+        self._de_ready()
         return self._omega_l0 / self.epoch0.E0(redshift)
 
     def linear_power(self, k, redshift=None):
@@ -315,6 +387,7 @@ class MultiEpoch(object):
     def rho_crit(self, redshift=None):
         if redshift is None:
             redshift = 0.0
+        self._de_ready()
         return 1.879 / (1.989) * 3.086 ** 3 * 1e10 * self.epoch0.E0(redshift)
 
     def rho_bar(self, redshift=None):

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <map>
 #include <unordered_map>
 #include <vector>
 
@@ -23,6 +24,7 @@
 #include "chomp_proj_kernels.h"
 #include "chomp_cov_kernels.h"
 #include "chomp_probe_kernel.h"
+#include "chomp_de_kernels.h"
 
 using namespace chomp;
 
@@ -66,6 +68,17 @@ struct RoctxApi {
     }
     return false;
   }
+};
+
+// Dark-energy pressure tables of one kind of set-up (the epochs' or the projection's): one per
+// distinct (w0, wa), in the order `keys` lists them, valid while the keys stay the same.
+struct DeTables {
+  std::vector<DePar> keys;
+  double* d_tab = nullptr;
+  DePar* d_par = nullptr;
+  size_t cap_tab = 0, cap_par = 0;
+  bool valid = false;
+  StagedBlock sh_par;
 };
 
 struct chomp_ctx {
@@ -169,6 +182,17 @@ struct chomp_ctx {
   bool slow_by_memset = false;     // set once a Stage E call has been captured into a HIP graph
   int precision = CHOMP_PREC_F64;  // chomp_set_precision
   int with_bao = 0;                // chomp_set_transfer
+  // w0-wa dark energy (chomp_set_dark_energy): the switch, the knots (ln a_i, then z_i; host-made,
+  // sent once), the epochs' and the projection's tables, and per epoch its table (-1: none)
+  int dark_energy = 0;
+  double* d_de_knots = nullptr;
+  size_t cap_de_knots = 0;
+  StagedBlock sh_de_knots;
+  DeTables de_ep, de_proj;
+  std::vector<int> de_slot;
+  int* d_de_slot = nullptr;
+  size_t cap_de_slot = 0;
+  StagedBlock sh_de_slot;
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
   bool timing_valid = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -577,14 +601,17 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_cand, ctx->d_cosmo, ctx->d_z, ctx->d_epochs, ctx->d_search, ctx->d_probe, ctx->d_count, ctx->d_pending,
                   ctx->d_tab, ctx->d_mass_par, ctx->d_profile, ctx->d_hod, ctx->d_nodes, ctx->d_snodes, ctx->d_slot, ctx->d_first, ctx->d_status, ctx->d_endp, ctx->d_npend,
                   ctx->d_stage_in, ctx->d_stage_in2, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
-                  ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b};
+                  ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
+                  ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
+                  ctx->de_proj.d_par};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
   for (void* p : ctx->host_graveyard) (void)hipHostFree(p);
   for (StagedBlock* b : {&ctx->sh_cosmo, &ctx->sh_z, &ctx->sh_mass, &ctx->sh_profile, &ctx->sh_hod,
                          &ctx->sh_slot, &ctx->sh_first, &ctx->sh_delta_b, &ctx->sh_proj, &ctx->sh_pp[0],
-                         &ctx->sh_pp[1]})
+                         &ctx->sh_pp[1], &ctx->sh_de_knots, &ctx->sh_de_slot, &ctx->de_ep.sh_par,
+                         &ctx->de_proj.sh_par})
     b->release();
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);
@@ -834,15 +861,101 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out) {
   return CHOMP_OK;
 }
 
+// -- w0-wa dark energy ----------------------------------------------------------------
+// The knots of the pressure tables (cosmology.py:98-102) made as numpy makes them:
+// a_i = 10 ** linspace(log10(cosmo_precision), 0, n); the tables take ln a_i, the integrals z_i =
+// 1 / a_i - 1.  Sent once per context (the configuration is fixed at its creation).
+static int de_knots(chomp_ctx* ctx) {
+  const int n = ctx->cfg.cosmo_npoints;
+  std::vector<double> k(2 * (size_t)n);
+  for (int i = 0; i < n; ++i) de_knot(ctx->cfg.cosmo_precision, n, i, &k[i], &k[n + i]);
+  const double* before = ctx->d_de_knots;
+  const int rc = ensure(ctx, &ctx->d_de_knots, &ctx->cap_de_knots, k.size());
+  if (rc) return rc;
+  if (ctx->d_de_knots != before) ctx->sh_de_knots.reset();
+  return upload(ctx, ctx->d_de_knots, k.data(), k.size() * sizeof(double), ctx->sh_de_knots);
+}
+
+// The tables of the distinct (w0, wa) of `keys`, queued on the context's stream -- or nothing,
+// when T already holds exactly these (the reference-shaped loop sets one epoch per z up).
+static int de_build(chomp_ctx* ctx, DeTables& T, const std::vector<DePar>& keys) {
+  const int n = ctx->cfg.cosmo_npoints;
+  const size_t nk = keys.size();
+  if (T.valid && T.keys.size() == nk &&
+      std::memcmp(T.keys.data(), keys.data(), nk * sizeof(DePar)) == 0)
+    return CHOMP_OK;
+  if (n < 4 || n > 240) return fail(ctx, CHOMP_ERR_ARG, "dark energy: cosmo_npoints must be 4..240");
+  if (nk > 65535) return fail(ctx, CHOMP_ERR_ARG, "dark energy: more than 65535 distinct (w0, wa)");
+  T.valid = false;
+  int rc = de_knots(ctx);
+  if (rc) return rc;
+  const DePar* before = T.d_par;
+  rc = ensure(ctx, &T.d_par, &T.cap_par, nk);
+  if (rc) return rc;
+  if (T.d_par != before) T.sh_par.reset();
+  rc = ensure(ctx, &T.d_tab, &T.cap_tab, nk * (size_t)de_stride(n));
+  if (rc) return rc;
+  rc = upload(ctx, T.d_par, keys.data(), nk * sizeof(DePar), T.sh_par);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_de_table, dim3((unsigned)n, (unsigned)nk), dim3(64 * kDeNW), 0, ctx->stream,
+                     ctx->cfg, T.d_par, ctx->d_de_knots, T.d_tab);
+  hipLaunchKernelGGL(k_de_spline, dim3((unsigned)nk), dim3(64), (size_t)(11 * n) * sizeof(double),
+                     ctx->stream, ctx->cfg, T.d_tab);
+  HIPCHK(hipGetLastError());
+  T.keys = keys;
+  T.valid = true;
+  return CHOMP_OK;
+}
+
+int chomp_set_dark_energy(chomp_ctx* ctx, int on) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  ctx->dark_energy = on != 0;
+  return CHOMP_OK;
+}
+
+int chomp_get_de_table(chomp_ctx* ctx, int source, size_t index, int what, double* out, size_t n) {
+  if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "get_de_table: bad args");
+  const int np = ctx->cfg.cosmo_npoints;
+  int off;
+  size_t want = (size_t)np;
+  switch (what) {
+    case CHOMP_DE_LN_A: off = de_off_ln_a(np); break;
+    case CHOMP_DE_PRESSURE: off = de_off_p(np); break;
+    case CHOMP_DE_LEVELS: off = de_off_level(np); break;
+    case CHOMP_DE_CONVERGED: off = de_off_conv(np); break;
+    case CHOMP_DE_PP: off = de_off_pp(np); want = 4 * (size_t)(np - 1); break;
+    default: return fail(ctx, CHOMP_ERR_ARG, "get_de_table: unknown table part");
+  }
+  if (n != want) return fail(ctx, CHOMP_ERR_ARG, "get_de_table: n must be cosmo_npoints (4 (cosmo_npoints - 1) for the coefficients)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* src;
+  if (source == CHOMP_DE_EPOCH) {
+    if (!ctx->have_epochs || index >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "get_de_table: epoch");
+    if (index >= ctx->de_slot.size() || ctx->de_slot[index] < 0)
+      return fail(ctx, CHOMP_ERR_STATE, "get_de_table: the epoch's cosmology has no dark energy");
+    src = ctx->de_ep.d_tab + (size_t)ctx->de_slot[index] * de_stride(np);
+  } else if (source == CHOMP_DE_PROJ) {
+    if (!ctx->proj.me_ready || !ctx->proj.de)
+      return fail(ctx, CHOMP_ERR_STATE, "get_de_table: no projection set-up with dark energy");
+    { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+    src = ctx->de_proj.d_tab;
+  } else {
+    return fail(ctx, CHOMP_ERR_ARG, "get_de_table: unknown source");
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(out, src + off, n * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
 int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
                      const double* z) {
   StageRange range_(ctx, "chomp:epochs_set (Stage K: sigma tables, mass-limit search)");
   if (!ctx || !cosmo || !z || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "epochs_set: bad args");
   for (size_t i = 0; i < n_epoch; ++i) {
-    if (cosmo[i].w0 != -1.0 || cosmo[i].wa != 0.0)
+    if (!ctx->dark_energy && has_dark_energy(cosmo[i].w0, cosmo[i].wa))
       return fail(ctx, CHOMP_ERR_SCOPE,
-                  "w0 != -1 or wa != 0: dynamical dark energy (cosmology.py:96-104, "
-                  "odeint growth) is outside the hot-path scope");
+                  "w0 != -1 or wa != 0: dynamical dark energy (cosmology.py:96-104) needs "
+                  "chomp_set_dark_energy(ctx, 1)");
     if (!(cosmo[i].omega_m0 > 0.0) || !(cosmo[i].h > 0.0) || !(cosmo[i].sigma_8 > 0.0))
       return fail(ctx, CHOMP_ERR_ARG, "epochs_set: omega_m0, h, sigma_8 must be > 0");
   }
@@ -895,6 +1008,30 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   if (rc) return rc;
   rc = upload(ctx, ctx->d_first, first.data(), n_epoch * sizeof(int), ctx->sh_first);
   if (rc) return rc;
+  // w0-wa dark energy: one pressure table per distinct (w0, wa), epoch -> table (-1: none).  A
+  // batch without dark energy queues nothing here.
+  std::vector<DePar> de_keys;
+  ctx->de_slot.assign(n_epoch, -1);
+  if (ctx->dark_energy) {
+    std::map<std::pair<double, double>, int> seen;
+    for (size_t i = 0; i < n_epoch; ++i) {
+      if (!has_dark_energy(cosmo[i].w0, cosmo[i].wa)) continue;
+      auto it = seen.emplace(std::make_pair(cosmo[i].w0, cosmo[i].wa), (int)de_keys.size());
+      if (it.second) de_keys.push_back(DePar{cosmo[i].w0, cosmo[i].wa});
+      ctx->de_slot[i] = it.first->second;
+    }
+  }
+  const bool any_de = !de_keys.empty();
+  if (any_de) {
+    rc = de_build(ctx, ctx->de_ep, de_keys);
+    if (rc) return rc;
+    const int* before = ctx->d_de_slot;
+    rc = ensure(ctx, &ctx->d_de_slot, &ctx->cap_de_slot, n_epoch);
+    if (rc) return rc;
+    if (ctx->d_de_slot != before) ctx->sh_de_slot.reset();
+    rc = upload(ctx, ctx->d_de_slot, ctx->de_slot.data(), n_epoch * sizeof(int), ctx->sh_de_slot);
+    if (rc) return rc;
+  }
   // (one cosmology or a few: most blocks, shortest launch; a batch of many: four nodes per
   //  thread and the ln S integrals one per wavefront -- see k_sigma_nodes)
   const unsigned gy = (unsigned)(n_slots + (n_epoch + 255) / 256);
@@ -918,6 +1055,11 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
     return CHOMP_OK;
   });
   if (rc) return rc;
+  // (dark energy: E0(z) and its dependents -- delta_c steers the mass-limit search below)
+  if (any_de)
+    hipLaunchKernelGGL(k_de_epochs, dim3((unsigned)((n_epoch + 63) / 64)), dim3(64), 0, ctx->stream,
+                       ctx->cfg, ctx->d_de_slot, (int)n_epoch, ctx->de_ep.d_tab, ctx->d_epochs,
+                       ctx->d_status);
   // (k_epoch_probe lives in chomp_probe.hip: the one kernel that is faster WITH machine LICM --
   //  but for the probing phase of a large batch, one wavefront per probe, compiled here)
   if (n_epoch >= 128)
@@ -929,6 +1071,9 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   chomp::launch_epoch_probe(ctx->with_bao != 0, (unsigned)n_epoch, ctx->stream, ctx->cfg,
                             ctx->d_epochs, ctx->d_search, ctx->d_cand, ctx->d_snodes,
                             ctx->d_probe, ctx->d_count, ctx->d_status);
+  if (any_de)
+    hipLaunchKernelGGL(k_de_chi, dim3((unsigned)n_epoch), dim3(64), 0, ctx->stream, ctx->cfg,
+                       ctx->d_de_slot, ctx->de_ep.d_tab, ctx->d_epochs);
   HIPCHK(hipGetLastError());
   ctx->have_epochs = true;
   return CHOMP_OK;

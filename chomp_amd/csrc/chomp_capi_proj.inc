@@ -121,13 +121,27 @@ static double bessel_zero_host(int order, int n) {
   return 0.5 * (lo + hi);
 }
 
+// The projection set-up's pressure table, when its cosmology has w0-wa dark energy (queued
+// on the stream in effect: the side stream), and the view its kernels evaluate E0 with.
+static int proj_dark_energy(chomp_ctx* ctx, const chomp_cosmo* cosmo, DeSpline* view) {
+  ProjState& P = ctx->proj;
+  P.de = has_dark_energy(cosmo->w0, cosmo->wa);
+  *view = DeSpline{nullptr, nullptr, 0};
+  if (!P.de) return CHOMP_OK;
+  const int rc = de_build(ctx, ctx->de_proj, std::vector<DePar>{DePar{cosmo->w0, cosmo->wa}});
+  if (rc) { P.de = false; return rc; }
+  *view = de_spline(ctx->de_proj.d_tab, ctx->cfg.cosmo_npoints);
+  return CHOMP_OK;
+}
+
 int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min,
                        double me_z_max, double ktheta_min, double ktheta_max,
                        const chomp_window* a, const chomp_window* b, int bessel_order) {
   StageRange range_(ctx, "chomp:kernel_setup (projection: MultiEpoch, windows, kernel knots)");
   if (!ctx || !cosmo || !a || !b) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: bad args");
   if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: bessel order must be 0 or 2");
-  if (cosmo->w0 != -1.0 || cosmo->wa != 0.0) return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup: w0/wa != -1/0 outside scope");
+  if (!ctx->dark_energy && has_dark_energy(cosmo->w0, cosmo->wa))
+    return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup: w0/wa != -1/0 needs chomp_set_dark_energy(ctx, 1)");
   if (!(ktheta_min > 0.0) || !(ktheta_max > ktheta_min)) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: ktheta range");
   const chomp_window* ws[2] = {a, b};
   for (int w = 0; w < 2; ++w) {
@@ -230,12 +244,22 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
   const ProjLayout& L = P.L;
   if (L.NC > 240 || L.NWp > 360 || L.NKT > 720)          // (the spline builds are staged in 64 KB of LDS)
     return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: cosmo/window/kernel_npoints too large");
-  hipLaunchKernelGGL(k_proj_chi, dim3(L.NC, 4), dim3(64), 0, ctx->stream, c, L, P.d_pd, P.d_tab);
+  DeSpline de;
+  { const int rcd = proj_dark_energy(ctx, cosmo, &de); if (rcd) return rcd; }
+  if (P.de)
+    hipLaunchKernelGGL(k_proj_chi<true>, dim3(L.NC, 4), dim3(64), 0, ctx->stream, c, L, P.d_pd, P.d_tab, de);
+  else
+    hipLaunchKernelGGL(k_proj_chi<false>, dim3(L.NC, 4), dim3(64), 0, ctx->stream, c, L, P.d_pd, P.d_tab, de);
   hipLaunchKernelGGL(k_proj_me_splines, dim3(3), dim3(192), (size_t)(33 * L.NC) * sizeof(double),
                      ctx->stream, c, L, P.d_pd, P.d_tab);
-  hipLaunchKernelGGL(k_proj_window, dim3(L.NWp, 2), dim3(64),
-                     (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, P.d_pd,
-                     P.d_tab);
+  if (P.de)
+    hipLaunchKernelGGL(k_proj_window<true>, dim3(L.NWp, 2), dim3(64),
+                       (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, P.d_pd,
+                       P.d_tab, de);
+  else
+    hipLaunchKernelGGL(k_proj_window<false>, dim3(L.NWp, 2), dim3(64),
+                       (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, P.d_pd,
+                       P.d_tab, de);
   hipLaunchKernelGGL(k_proj_window_splines, dim3(1), dim3(128),
                      (size_t)(22 * L.NWp) * sizeof(double), ctx->stream, c, L, P.d_pd, P.d_tab);
   hipLaunchKernelGGL(k_proj_kernel_knots, dim3(L.NKT), dim3(256),
@@ -253,7 +277,8 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
 int chomp_multi_epoch_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double z_min,
                             double z_max) {
   if (!ctx || !cosmo) return fail(ctx, CHOMP_ERR_ARG, "multi_epoch_setup: bad args");
-  if (cosmo->w0 != -1.0 || cosmo->wa != 0.0) return fail(ctx, CHOMP_ERR_SCOPE, "multi_epoch_setup: w0/wa != -1/0 outside scope");
+  if (!ctx->dark_energy && has_dark_energy(cosmo->w0, cosmo->wa))
+    return fail(ctx, CHOMP_ERR_SCOPE, "multi_epoch_setup: w0/wa != -1/0 needs chomp_set_dark_energy(ctx, 1)");
   if (!(z_max > z_min)) return fail(ctx, CHOMP_ERR_ARG, "multi_epoch_setup: z range");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
@@ -280,7 +305,12 @@ int chomp_multi_epoch_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double z_m
   { const int rcp = upload(ctx, P.d_pd_init, &pd, sizeof(pd), ctx->sh_proj); if (rcp) return rcp; }
   HIPCHK(hipMemcpyAsync(P.d_pd, P.d_pd_init, sizeof(pd), hipMemcpyDeviceToDevice, ctx->stream));
   if (P.L.NC > 240) return fail(ctx, CHOMP_ERR_ARG, "multi_epoch_setup: cosmo_npoints too large");
-  hipLaunchKernelGGL(k_proj_chi, dim3(P.L.NC, 1), dim3(64), 0, ctx->stream, c, P.L, P.d_pd, P.d_tab);
+  DeSpline de;
+  { const int rcd = proj_dark_energy(ctx, cosmo, &de); if (rcd) return rcd; }
+  if (P.de)
+    hipLaunchKernelGGL(k_proj_chi<true>, dim3(P.L.NC, 1), dim3(64), 0, ctx->stream, c, P.L, P.d_pd, P.d_tab, de);
+  else
+    hipLaunchKernelGGL(k_proj_chi<false>, dim3(P.L.NC, 1), dim3(64), 0, ctx->stream, c, P.L, P.d_pd, P.d_tab, de);
   hipLaunchKernelGGL(k_proj_me_splines, dim3(1), dim3(192),
                      (size_t)(33 * P.L.NC) * sizeof(double), ctx->stream, c, P.L, P.d_pd, P.d_tab);
   HIPCHK(hipGetLastError());

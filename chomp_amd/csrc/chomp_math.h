@@ -585,6 +585,69 @@ CHOMP_HD double E0_of(double om0, double ol0, double or0, double z) {
   return ol0 + om0 / (a * a * a) + or0 / (a * a * a * a);
 }
 
+// ---------------------------------------------------------------------------
+// w0-wa dark energy (cosmology.py:96-104, 165-213).  Active iff w0 != -1 or wa != 0.  The
+// reference tabulates P(a) = 3 int_0^z (1 + w(z')) / (1 + z') dz' with scipy's Romberg at
+// cosmo_npoints knots a_i = logspace(log10(cosmo_precision), 0, n), z_i = 1 / a_i - 1, splines
+// it in ln a (not-a-knot) and multiplies Omega_L0 by exp(P(ln a)) in E0(z).
+// ---------------------------------------------------------------------------
+CHOMP_HD bool has_dark_energy(double w0, double wa) { return w0 != -1.0 || wa != 0.0; }
+
+// cosmology.py:184-197: dpressuredz = (1 + w(z)) / (1 + z), w = w0 + wa (1 - a), a = 1 / (1 + z),
+// rounded as numpy rounds it (no contraction: the stopping levels are the reference's).
+struct DePressureIntegrand {
+  double w0, wa;
+  CHOMP_HD double operator()(double z) const {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double a = 1.0 / (1.0 + z);
+#if defined(__clang__)
+    const double w = w0 + wa * (1.0 - a);
+#else
+    volatile double prod = wa * (1.0 - a);
+    const double w = w0 + prod;
+#endif
+    return (1.0 + w) / (1.0 + z);
+  }
+};
+
+// Knot i of n (cosmology.py:98-102) as numpy makes it: a = 10 ** linspace(log10(cosmo_precision),
+// 0, n)[i]; the table takes ln a, the integral runs to z = 1 / a - 1.  (Host code: the library
+// sends the knots, so that pow / log are the C library's, as numpy's are.)
+inline void de_knot(double cosmo_precision, int n, int i, double* ln_a, double* z) {
+  const double a = pow(10.0, linspace_at(log10(cosmo_precision), 0.0, n, i));
+  *ln_a = log(a);
+  *z = 1.0 / a - 1.0;
+}
+
+// One cosmology's pressure table (n = cosmo_npoints knots), doubles at these offsets: ln a_i,
+// P_i, the Romberg level of knot i, 1 where knot i converged (0: divmax exhausted, scipy's
+// AccuracyWarning), then the spline's 4 (n - 1) piecewise-polynomial coefficients.
+CHOMP_HD int de_off_ln_a(int) { return 0; }
+CHOMP_HD int de_off_p(int n) { return n; }
+CHOMP_HD int de_off_level(int n) { return 2 * n; }
+CHOMP_HD int de_off_conv(int n) { return 3 * n; }
+CHOMP_HD int de_off_pp(int n) { return 4 * n; }
+CHOMP_HD int de_stride(int n) { return 8 * n - 4; }
+
+// The spline of one table: exp(P(ln a)) with ln a = -ln(1 + z) (numpy.log(1 / (1 + z))).
+struct DeSpline {
+  const double* ln_a;   // knots
+  const double* pp;     // coefficients
+  int n;
+  CHOMP_HD double factor(double a) const { return exp(spline_eval(ln_a, pp, n, log(a))); }
+};
+CHOMP_HD DeSpline de_spline(const double* tab, int n) {
+  return DeSpline{tab + de_off_ln_a(n), tab + de_off_pp(n), n};
+}
+
+// cosmology.py:165-182 with the pressure spline.
+CHOMP_HD double E0_de(double om0, double ol0, double or0, const DeSpline& de, double z) {
+  const double a = 1.0 / (1.0 + z);
+  return ol0 * de.factor(a) + om0 / (a * a * a) + or0 / (a * a * a * a);
+}
+
 // cosmology.py:215-231 (always returned by growth_factor_eval, :326)
 CHOMP_HD double growth_approx(double om0, double ol0, double a) {
   const double om = om0 / (a * a * a);
@@ -598,6 +661,7 @@ CHOMP_HD double growth_approx(double om0, double ol0, double a) {
 }
 
 CHOMP_HD void bao_constants(Epoch& e);
+CHOMP_HD void epoch_e0_dependents(Epoch& e);
 constexpr int kGTabIntervals = 8192;      // (= kGTabN of chomp_mass_kernels.h)
 CHOMP_HD void epoch_k_range(Epoch& e) {
   e.ln_k_min = log(e.k_min);
@@ -626,6 +690,26 @@ CHOMP_HD void epoch_background(Epoch& e, double cosmo_precision, double k_min,
   e.growth_norm = growth_approx(e.om0, e.ol0, 1.0);
   e.growth = growth_approx(e.om0, e.ol0, 1.0 / (1.0 + e.z)) / e.growth_norm;
   e.E0z = E0_of(e.om0, e.ol0, e.or0, e.z);
+  epoch_e0_dependents(e);
+  // Eisenstein-Hu constants; (Omb2)**(3/4) is **0 under Python 2 -> sqrt(11).
+  const double Omh2 = e.om0 * e.h * e.h;
+  const double ratio = e.ob0 / e.om0;
+  e.eh_theta = e.tcmb / 2.7;
+  e.eh_s = 44.5 * log(9.83 / Omh2) / sqrt(1.0 + 10.0 * 1.0);
+  e.eh_alpha = 1.0 - 0.328 * log(431.0 * Omh2) * ratio +
+               0.38 * log(22.3 * Omh2) * ratio * ratio;
+  e.eh_omh = e.om0 * e.h;
+  e.sigma_norm = 1.0;
+  e.amp = e.delta_H * e.delta_H / e.h * (e.growth * e.growth);
+  e.with_bao = with_bao ? 1 : 0;
+  e.pad_bao = 0;
+  if (e.with_bao) bao_constants(e);
+}
+
+// What follows from E0(z) (the epoch's E0z, growth and flatness flags set):
+// omega_m(z), omega_l(z) = Omega_L0 / E0 (no pressure factor, as in cosmology.py:384-391 --
+// what HaloFit receives), delta_c, delta_v and rho_bar (cosmology.py:375-447).
+CHOMP_HD void epoch_e0_dependents(Epoch& e) {
   const double opz = 1.0 + e.z;
   e.omega_m_z = e.om0 * (opz * opz * opz) / e.E0z;
   e.omega_l_z = e.ol0 / e.E0z;
@@ -643,19 +727,6 @@ CHOMP_HD void epoch_background(Epoch& e, double cosmo_precision, double k_min,
   e.delta_v = dv / e.growth;
   e.rho_bar = (1.879 / (1.989) * (3.086 * 3.086 * 3.086) * 1e10 * e.E0z) *
               e.omega_m_z;                            // :437-447
-  // Eisenstein-Hu constants; (Omb2)**(3/4) is **0 under Python 2 -> sqrt(11).
-  const double Omh2 = e.om0 * e.h * e.h;
-  const double ratio = e.ob0 / e.om0;
-  e.eh_theta = e.tcmb / 2.7;
-  e.eh_s = 44.5 * log(9.83 / Omh2) / sqrt(1.0 + 10.0 * 1.0);
-  e.eh_alpha = 1.0 - 0.328 * log(431.0 * Omh2) * ratio +
-               0.38 * log(22.3 * Omh2) * ratio * ratio;
-  e.eh_omh = e.om0 * e.h;
-  e.sigma_norm = 1.0;
-  e.amp = e.delta_H * e.delta_H / e.h * (e.growth * e.growth);
-  e.with_bao = with_bao ? 1 : 0;
-  e.pad_bao = 0;
-  if (e.with_bao) bao_constants(e);
 }
 
 // What the cosmology-only integrals (sigma node table, sigma_8, ln S(R)) need of an epoch
@@ -888,6 +959,14 @@ struct EIntegrand {
   double om0, ol0, or0, H0;
   CHOMP_HD double operator()(double z) const {
     return 1.0 / (H0 * sqrt(E0_of(om0, ol0, or0, z)));
+  }
+};
+// ... of a w0-wa cosmology.
+struct EIntegrandDE {
+  double om0, ol0, or0, H0;
+  DeSpline de;
+  CHOMP_HD double operator()(double z) const {
+    return 1.0 / (H0 * sqrt(E0_de(om0, ol0, or0, de, z)));
   }
 };
 

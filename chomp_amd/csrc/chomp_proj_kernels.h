@@ -83,6 +83,7 @@ inline ProjLayout make_proj_layout(int NC, int NWp, int NKT) {
 struct ProjState {
   bool ready = false;      // full kernel set-up done
   bool me_ready = false;   // MultiEpoch 0 tables valid
+  bool de = false;         // the set-up's cosmology has w0-wa dark energy (its table: chomp_ctx::de_proj)
   ProjLayout L;
   ProjDev host;            // host copy of the scalars (refreshed by kernel_info)
   ProjDev* d_pd = nullptr;
@@ -386,10 +387,11 @@ struct DndzRaw {
 };
 
 // grid (NC, 4), block 64.  y < 3: chi and growth of MultiEpoch y at grid point x;
-// y == 3, x < 2: normalisation of distribution x.
+// y == 3, x < 2: normalisation of distribution x.  DE: E with the pressure spline `de`.
+template <bool DE>
 __global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
                                                  ProjDev* __restrict__ pd,
-                                                 double* __restrict__ tab) {
+                                                 double* __restrict__ tab, DeSpline de) {
   const int i = blockIdx.x, m = blockIdx.y;
   if (m == 3) {
     if (i >= 2) return;
@@ -403,9 +405,14 @@ __global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
     return;
   }
   const double z = linspace_at(pd->me_z_min[m], pd->me_z_max[m], L.NC, i);
-  EIntegrand f{pd->om0, pd->ol0, pd->or0, pd->H0};
-  const double chi = romberg1<1>(f, 0.0, z, cfg.global_precision, cfg.cosmo_precision,
-                                 cfg.divmax, nullptr);
+  double chi;
+  if constexpr (DE) {
+    EIntegrandDE f{pd->om0, pd->ol0, pd->or0, pd->H0, de};
+    chi = romberg1<1>(f, 0.0, z, cfg.global_precision, cfg.cosmo_precision, cfg.divmax, nullptr);
+  } else {
+    EIntegrand f{pd->om0, pd->ol0, pd->or0, pd->H0};
+    chi = romberg1<1>(f, 0.0, z, cfg.global_precision, cfg.cosmo_precision, cfg.divmax, nullptr);
+  }
   if (threadIdx.x == 0) {
     tab[L.me_z[m] + i] = z;
     tab[L.me_chi[m] + i] = chi;
@@ -487,23 +494,36 @@ __global__ __launch_bounds__(192) void k_proj_me_splines(chomp_config cfg, ProjL
     tab[L.w_chi[w] + i] = linspace_at(lim[0], lim[1], L.NWp, i);
 }
 
+// E0(z) of the projection's cosmology: Lambda-CDM, or (DE) with the pressure spline.
+template <bool DE>
+__device__ __forceinline__ double proj_E0(const ProjDev& pd, const DeSpline& de, double z) {
+  if constexpr (DE) return E0_de(pd.om0, pd.ol0, pd.or0, de, z);
+  else return E0_of(pd.om0, pd.ol0, pd.or0, z);
+}
+
 // Lensing-efficiency integrand, kernel.py:479-484.
+template <bool DE>
 struct LensIntegrand {
   const double *chi_knots, *pp_z;
   int NC;
   const DndzDev* d;
   double om0, ol0, or0, H0, chi0;
+  DeSpline de;
   __device__ __forceinline__ double operator()(double c) const {
     const double z = spline_eval(chi_knots, pp_z, NC, c);
-    const double dzdchi = H0 * sqrt(E0_of(om0, ol0, or0, z));
+    double E0;
+    if constexpr (DE) E0 = E0_de(om0, ol0, or0, de, z);
+    else E0 = E0_of(om0, ol0, or0, z);
+    const double dzdchi = H0 * sqrt(E0);
     return dzdchi * dndz_eval(*d, z) * (c - chi0) / c;
   }
 };
 
 // grid (NWp, 2), block 64: raw window function of window y at its x-th chi knot.
+template <bool DE>
 __global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout L,
                                                     const ProjDev* __restrict__ pd,
-                                                    double* __restrict__ tab) {
+                                                    double* __restrict__ tab, DeSpline de) {
   extern __shared__ __align__(16) double sm[];
   __shared__ DndzDev D;
   const int i = blockIdx.x, w = blockIdx.y, m = w + 1, NC = L.NC;
@@ -517,7 +537,7 @@ __global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout
   const double z = spline_eval(chi_knots, pp_z, NC, chi);
   double val;
   if (pd->wkind[w] == CHOMP_WINDOW_GALAXY) {                       // kernel.py:382-387
-    val = pd->H0 * sqrt(E0_of(pd->om0, pd->ol0, pd->or0, z)) * dndz_eval(D, z);
+    val = pd->H0 * sqrt(proj_E0<DE>(*pd, de, z)) * dndz_eval(D, z);
   } else if (pd->wkind[w] == CHOMP_WINDOW_FLAT_CONVERGENCE) {      // kernel.py:507-513
     val = 3.0 / 2.0 * pd->om0 * (pd->H0 * pd->H0 * 1907.71);
   } else if (pd->wkind[w] == CHOMP_WINDOW_CONVERGENCE_DELTA) {     // kernel.py:541-556
@@ -532,7 +552,7 @@ __global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout
     if (bound < pd->w_g_chi_min[w]) bound = pd->w_g_chi_min[w];
     double g = 0.0;
     if (!(bound <= cfg.window_precision)) {
-      LensIntegrand f{chi_knots, pp_z, NC, &D, pd->om0, pd->ol0, pd->or0, pd->H0, chi};
+      LensIntegrand<DE> f{chi_knots, pp_z, NC, &D, pd->om0, pd->ol0, pd->or0, pd->H0, chi, de};
       g = romberg1<1>(f, bound, pd->w_chi_max[w], cfg.global_precision,
                       cfg.window_precision, cfg.divmax, nullptr);
     }

@@ -124,7 +124,7 @@ class HaloGrid(object):
         _, need = _WHICH[which]
         if len(self.idx) == 0:
             return
-        self.ctx.epochs_set(self._c_cosmo, self._z)
+        self.ctx.epochs_set(self._c_cosmo, self._z, **cosmology._de_kw(self._c_cosmo))
         self.ctx.stage_k(self._c_halo, self.kind, self._c_halo, self._c_hod, need)
         if self._delta_b is not None:    # (chomp_epochs_set has reset every epoch's to 0)
             self.ctx.set_delta_b(self._delta_b, 0)

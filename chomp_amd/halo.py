@@ -136,7 +136,8 @@ class Halo(object):
         if esig != self._epoch_sig:
             self._resolve_status(stacklevel=6)     # (the set-up below clears the device's words)
             self._before_epochs_set()
-            ctx.epochs_set(self.cosmo.cosmo_dict, [self.cosmo._redshift], bao)
+            ctx.epochs_set(self.cosmo.cosmo_dict, [self.cosmo._redshift], bao,
+                           **cosmology._de_kw(self.cosmo.cosmo_dict))
             self._epoch_sig = esig
             self._mass_sig = None
             self._nbar_valid = False

@@ -228,7 +228,7 @@ class WindowFunction(object):
         if sig != self._sig:
             s = self._struct()
             self._ctx.kernel_setup(self.cosmo.cosmo_dict, self.z_min, self.z_max,
-                                   1e-6, 1.0, s, s, 0)
+                                   1e-6, 1.0, s, s, 0, **cosmology._de_kw(self.cosmo.cosmo_dict))
             self._sig = sig
         return self._ctx
 
@@ -338,7 +338,8 @@ class Kernel(object):
             ctx.kernel_setup(self.cosmo.cosmo_dict, self.cosmo.z_min, self.cosmo.z_max,
                              self._ktheta[0], self._ktheta[1],
                              self.window_function_a._struct(),
-                             self.window_function_b._struct(), self._order)
+                             self.window_function_b._struct(), self._order,
+                             **cosmology._de_kw(self.cosmo.cosmo_dict))
             self._done[id(ctx)] = sig
             ctx._proj_owner = mine
             self._info = None            # (read back -- a synchronisation -- when first asked for)

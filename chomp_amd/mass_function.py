@@ -39,7 +39,8 @@ class MassFunction(object):
             self._ctx = cosmology._context()
         if sig != self._sig:
             self._ctx.epochs_set(self.cosmo.cosmo_dict, [self.cosmo._redshift],
-                                 getattr(self.cosmo, "_with_bao", False))
+                                 getattr(self.cosmo, "_with_bao", False),
+                                 **cosmology._de_kw(self.cosmo.cosmo_dict))
             self._ctx.mass_setup(self.halo_dict, self._kind)
             self._sc = self._ctx.scalars(0)
             self._sig = sig

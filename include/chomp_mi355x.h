@@ -38,7 +38,8 @@ extern "C" {
 
 typedef struct chomp_ctx chomp_ctx;
 
-/* defaults.default_cosmo_dict (defaults.py:6-18); w0/wa must be -1/0. */
+/* defaults.default_cosmo_dict (defaults.py:6-18).  w0/wa other than -1/0 (w0-wa dark energy)
+ * need chomp_set_dark_energy(ctx, 1); without it the set-ups refuse them (CHOMP_ERR_SCOPE). */
 typedef struct chomp_cosmo {
   double omega_m0, omega_b0, omega_l0, omega_r0, cmb_temp, h, sigma_8, n_scalar,
       w0, wa;
@@ -321,6 +322,8 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
  *   (cosmology.py:617-622, behind the reference's commented-out extrapolation warning).
  * MASS_SEARCH_EXHAUSTED: the walk did not end within 2047 steps (the reference loops on).
  * SIGMA_DIVMAX: a sigma(R) Romberg of the nu table exhausted divmax (scipy: AccuracyWarning).
+ * DE_DIVMAX: a knot of the epoch's dark-energy pressure table exhausted divmax
+ *   (cosmology.py:196-213; with the default precision the deepest 22 of the 50 knots do).
  * HALO_DIVMAX_*: some knot of that table exhausted divmax (halo.py:909-915, 951-957, 976-982,
  *   1018-1024, 1065-1071, 1182-1189; scipy returns the last row with an AccuracyWarning -- with the
  *   default precision the discontinuous HOD integrands of pp_gm / pp_gg do this routinely).
@@ -329,6 +332,7 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
 #define CHOMP_ST_MASS_MAX_SATURATED 2u
 #define CHOMP_ST_MASS_SEARCH_EXHAUSTED 4u
 #define CHOMP_ST_SIGMA_DIVMAX 8u
+#define CHOMP_ST_DE_DIVMAX 0x10u
 #define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..5: H_M, PP_MM, H_G, PP_GM, PP_GG, I_1_2 */
 #define CHOMP_ST_HALO_DIVMAX_PP_MM 0x200u
 #define CHOMP_ST_HALO_DIVMAX_H_G 0x400u
@@ -611,6 +615,32 @@ int chomp_wtheta_cell(chomp_ctx* ctx, int which, size_t epoch, double k_min, dou
 #define CHOMP_TRANSFER_EH 0
 #define CHOMP_TRANSFER_EH_BAO 1
 int chomp_set_transfer(chomp_ctx* ctx, int kind);
+
+/* w0-wa dark energy (cosmology.py:96-104, 165-213), opt-in: with `on` set, chomp_epochs_set,
+ * chomp_multi_epoch_setup and chomp_kernel_setup accept w0 != -1 or wa != 0 (off, the default:
+ * they refuse them with CHOMP_ERR_SCOPE).  For each distinct (w0, wa) the library tabulates
+ * P(a) = 3 int_0^z (1 + w(z')) / (1 + z') dz', w = w0 + wa (1 - a), with scipy's Romberg rule at
+ * the cosmo_npoints knots a_i = logspace(log10(cosmo_precision), 0, cosmo_npoints), splines it
+ * in ln a and evaluates E0(z) = Omega_L0 exp(P(ln a)) + Omega_m0 / a^3 + Omega_r0 / a^4 wherever
+ * E enters: chi, omega_m(z), delta_c, delta_v, rho_bar, the windows' dz/dchi and the lensing
+ * efficiency.  omega_l(z) stays Omega_L0 / E0 and the growth factor stays the Carroll et al.
+ * approximation, as in the reference.  A Lambda-CDM cosmology takes exactly the path (and gives
+ * the bits) it takes with the switch off.  A table is kept while its (w0, wa) recur. */
+int chomp_set_dark_energy(chomp_ctx* ctx, int on);
+/* One dark-energy table: source CHOMP_DE_EPOCH (the cosmology of epoch `index` of the last
+ * chomp_epochs_set) or CHOMP_DE_PROJ (the projection set-up's; index ignored).  what: the knots
+ * ln a_i, the pressures P_i, the Romberg levels, 1/0 for converged / divmax exhausted (n =
+ * cosmo_npoints each), or the spline's coefficients (n = 4 (cosmo_npoints - 1): piece i on
+ * [ln a_i, ln a_{i+1}] is sum_m pp[4 i + m] (ln a - ln a_i)^m).  Host buffer; synchronises.
+ * CHOMP_ERR_STATE when that cosmology has no dark energy. */
+#define CHOMP_DE_EPOCH 0
+#define CHOMP_DE_PROJ 1
+#define CHOMP_DE_LN_A 0
+#define CHOMP_DE_PRESSURE 1
+#define CHOMP_DE_LEVELS 2
+#define CHOMP_DE_CONVERGED 3
+#define CHOMP_DE_PP 4
+int chomp_get_de_table(chomp_ctx* ctx, int source, size_t index, int what, double* out, size_t n);
 
 /* Halo.calculate_bias / calculate_m_eff / calculate_f_sat (halo.py:709-838) of epochs
  * [epoch0, epoch0 + n): out[3 i + {0, 1, 2}] = effective bias, effective halo mass,
