@@ -40,7 +40,15 @@ TAB = {"ln_mass": 0, "nu": 1, "h_m": 2, "pp_mm": 3, "h_g": 4, "pp_gm": 5,
        "pp_gg": 6, "levels": 7, "hf_ln_sigma2": 8, "i_1_2": 9, "levels_i_1_2": 10}
 EV = {"nu_of_mass": 0, "ln_mass_of_nu": 1, "f_nu": 2, "bias_nu": 3,
       "hod_first": 4, "hod_second": 5, "hod_central": 6, "hod_satellite": 7,
-      "virial_radius": 8, "concentration": 9, "delta_k": 10}
+      "virial_radius": 8, "concentration": 9, "delta_k": 10, "bias_2_nu": 11,
+      "sigma_of_nu": 12}
+# chomp_pt_eval forms (CHOMP_PT_*) and the doubles of one configuration
+PT = {"Fs2": 0, "Fs2_len": 1, "Fs2_kdiff": 2, "Fs3": 3, "Fs3_parallelogram": 4, "F3": 5,
+      "Fs3_BCGS": 6, "bispectrum": 7, "bispectrum_len": 8, "trispectrum": 9,
+      "trispectrum_parallelogram": 10}
+PT_ARITY = {"Fs2": 6, "Fs2_len": 3, "Fs2_kdiff": 3, "Fs3": 9, "Fs3_parallelogram": 3, "F3": 9,
+            "Fs3_BCGS": 9, "bispectrum": 9, "bispectrum_len": 6, "trispectrum": 12,
+            "trispectrum_parallelogram": 3}
 HF_COUNT = 14
 KI = {name: i for i, name in enumerate([
     "z_bar", "chi_min", "chi_max", "z_min", "z_max", "D_zbar", "norm_a", "norm_b",
@@ -123,11 +131,13 @@ EXPORTS = [
     "chomp_covariance_ssc",
     "chomp_halo_setup_hod", "chomp_stage_k_hod", "chomp_stage_k_halofit_hod",
     "chomp_set_dark_energy", "chomp_get_de_table",
+    "chomp_set_second_order", "chomp_get_second_order", "chomp_pt_eval",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
 ST_MASS_MIN_SATURATED, ST_MASS_MAX_SATURATED, ST_MASS_SEARCH_EXHAUSTED, ST_SIGMA_DIVMAX = 1, 2, 4, 8
 ST_DE_DIVMAX = 0x10
+ST_B2_DIVMAX = 0x20
 ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000,
                   "i_1_2": 0x2000}
 ST_NONFINITE = 0x10000
@@ -163,6 +173,8 @@ def describe_status(word):
         out.append("a sigma(R) Romberg of the nu table exhausted divmax")
     if word & ST_DE_DIVMAX:
         out.append("a Romberg of the dark-energy pressure table exhausted divmax")
+    if word & ST_B2_DIVMAX:
+        out.append("the bias_2_norm Romberg exhausted divmax (mass_function.py:408-414)")
     for name, bit in ST_HALO_DIVMAX.items():
         if word & bit:
             out.append("%s: Romberg exhausted divmax at some knots (last row kept)" % name)
@@ -373,6 +385,9 @@ def lib():
         L.chomp_set_transfer.argtypes = [vp, i]
         L.chomp_set_dark_energy.argtypes = [vp, i]
         L.chomp_get_de_table.argtypes = [vp, i, sz, i, c_double_p, sz]
+        L.chomp_set_second_order.argtypes = [vp, i]
+        L.chomp_get_second_order.argtypes = [vp, sz, c_double_p, sz]
+        L.chomp_pt_eval.argtypes = [vp, i, sz, sz, vp, sz, vp, i]
         L.chomp_set_timing.argtypes = [vp, i]
         L.chomp_get_timing.argtypes = [vp, c_double_p, sz]
         L.chomp_get_status.argtypes = [vp, sz, sz, ctypes.POINTER(ctypes.c_uint)]
@@ -623,6 +638,47 @@ class Context(object):
         assert len(ma) == n and len(pa) == n and len(ha) == n
         self._check(self._L.chomp_stage_k_halofit_hod(self._h, ma, int(mf_kind), pa, ha,
                                                       int(tables), epoch, f1, f2, f3, omega_l, w))
+
+    def set_second_order(self, on=True):
+        """MassFunctionSecondOrder set-ups from now on (chomp_set_second_order)."""
+        self._check(self._L.chomp_set_second_order(self._h, 1 if on else 0))
+
+    def second_order(self, epoch=0):
+        """{"sigma": sigma(M) at the mass knots, "bias_2_norm", "level", "converged"} of the last
+        (second-order) mass set-up (chomp_get_second_order)."""
+        nm = self.config.mass_npoints
+        out = numpy.empty(nm + 3)
+        self._check(self._L.chomp_get_second_order(self._h, epoch,
+                                                    out.ctypes.data_as(c_double_p), out.size))
+        return {"sigma": out[:nm], "bias_2_norm": float(out[nm]), "level": int(out[nm + 1]),
+                "converged": bool(out[nm + 2])}
+
+    def pt_eval(self, form, args, epoch0=0, n=None):
+        """PerturbationTheory form `form` (a PT key) of configurations args [N, arity] over the
+        epochs [epoch0, epoch0 + n): [n, N].  args numpy (host path) or a contiguous float64 torch
+        cuda tensor (device path, asynchronous on the context's stream; returns a tensor)."""
+        n = self.n_epoch - epoch0 if n is None else n
+        na = PT_ARITY[form]
+        if _is_torch(args):
+            import torch
+            assert args.is_cuda and args.dtype == torch.float64 and args.is_contiguous()
+            m = args.numel() // na
+            assert m * na == args.numel()
+            out = torch.empty((n, m), dtype=torch.float64, device=args.device)
+            if m:
+                pair = self._torch_enter()
+                self._check(self._L.chomp_pt_eval(self._h, PT[form], epoch0, n,
+                                                  ctypes.c_void_p(args.data_ptr()), m,
+                                                  ctypes.c_void_p(out.data_ptr()), DEVICE))
+                self._torch_leave(pair)
+            return out
+        a = numpy.ascontiguousarray(args, dtype=numpy.float64).reshape(-1, na)
+        out = numpy.empty((n, a.shape[0]), dtype=numpy.float64)
+        if a.shape[0]:
+            self._check(self._L.chomp_pt_eval(self._h, PT[form], epoch0, n,
+                                              ctypes.c_void_p(a.ctypes.data), a.shape[0],
+                                              ctypes.c_void_p(out.ctypes.data), HOST))
+        return out
 
     def halofit_setup(self, dst, src, f1, f2, f3, omega_l, w):
         self._check(self._L.chomp_halofit_setup(self._h, dst, src, f1, f2, f3,

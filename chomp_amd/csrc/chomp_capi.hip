@@ -25,6 +25,7 @@
 #include "chomp_cov_kernels.h"
 #include "chomp_probe_kernel.h"
 #include "chomp_de_kernels.h"
+#include "chomp_pt_kernels.h"
 
 using namespace chomp;
 
@@ -193,6 +194,13 @@ struct chomp_ctx {
   int* d_de_slot = nullptr;
   size_t cap_de_slot = 0;
   StagedBlock sh_de_slot;
+  // MassFunctionSecondOrder (chomp_set_second_order): the switch, and per epoch the sigma knots,
+  // the sigma(nu) spline and bias_2_norm (B2Layout); have_b2: the last mass set-up made them
+  int second_order = 0;
+  bool have_b2 = false;
+  B2Layout B2;
+  double* d_b2 = nullptr;
+  size_t cap_b2 = 0;
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
   bool timing_valid = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -603,7 +611,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_stage_in, ctx->d_stage_in2, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par};
+                  ctx->de_proj.d_par, ctx->d_b2};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -1105,6 +1113,15 @@ static std::vector<chomp_hod_model> zheng_models(const chomp_hod_par* hod, size_
 }
 static_assert(kHodZheng == CHOMP_HOD_ZHENG && kHodMandelbaum == CHOMP_HOD_MANDELBAUM,
               "chomp_math.h's model numbers are the header's");
+static_assert(PT_FS2 == CHOMP_PT_FS2 && PT_FS2_LEN == CHOMP_PT_FS2_LEN &&
+                  PT_FS2_KDIFF == CHOMP_PT_FS2_KDIFF && PT_FS3 == CHOMP_PT_FS3 &&
+                  PT_FS3_PARALLELOGRAM == CHOMP_PT_FS3_PARALLELOGRAM && PT_F3 == CHOMP_PT_F3 &&
+                  PT_FS3_BCGS == CHOMP_PT_FS3_BCGS && PT_BISPECTRUM == CHOMP_PT_BISPECTRUM &&
+                  PT_BISPECTRUM_LEN == CHOMP_PT_BISPECTRUM_LEN &&
+                  PT_TRISPECTRUM == CHOMP_PT_TRISPECTRUM &&
+                  PT_TRISPECTRUM_PARALLELOGRAM == CHOMP_PT_TRISPECTRUM_PARALLELOGRAM &&
+                  kPtForms == CHOMP_PT_TRISPECTRUM_PARALLELOGRAM + 1,
+              "chomp_pt_kernels.h's form numbers are the header's");
 static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const chomp_hod_model* hod,
                         unsigned tables, HaloPlan* P) {
   const size_t n = ctx->n_epoch;
@@ -1174,11 +1191,23 @@ static int launch_nu_mass(chomp_ctx* ctx, int mf_kind, const HaloPlan* plan) {
   //  (the epochs as the grid's y axis: at most 65535 of them)
   const int ef = (ctx->n_slots < 16 || n > 65535) ? 1 : 0;
   // (fewer integrals than SIMDs to put them on: four wavefronts to an integral)
+  ctx->have_b2 = false;
+  if (ctx->second_order) {
+    ctx->B2 = make_b2_layout(L.NM);
+    const int rcb = ensure(ctx, &ctx->d_b2, &ctx->cap_b2, n * (size_t)ctx->B2.stride);
+    if (rcb) return rcb;
+  }
   with_flag(ctx->with_bao, (size_t)L.NM * n <= 512, [&](auto BAO, auto FEW) {
     constexpr int NW = FEW ? 4 : 1;
-    hipLaunchKernelGGL((k_nu_table<BAO, NW>), ef ? dim3((unsigned)n, L.NM) : dim3(L.NM, (unsigned)n),
-                       dim3(64 * NW), 0, ctx->stream, ctx->cfg, L, ctx->d_epochs, ctx->d_search,
-                       ctx->d_snodes, ctx->d_tab, ctx->d_status, ef);
+    const dim3 grid = ef ? dim3((unsigned)n, L.NM) : dim3(L.NM, (unsigned)n);
+    if (ctx->second_order)      // (the sigma knots of MassFunctionSecondOrder as well)
+      hipLaunchKernelGGL((k_nu_table<BAO, NW, true>), grid, dim3(64 * NW), 0, ctx->stream, ctx->cfg,
+                         L, ctx->d_epochs, ctx->d_search, ctx->d_snodes, ctx->d_tab, ctx->d_status,
+                         ef, ctx->d_b2, ctx->B2.stride);
+    else
+      hipLaunchKernelGGL((k_nu_table<BAO, NW>), grid, dim3(64 * NW), 0, ctx->stream, ctx->cfg, L,
+                         ctx->d_epochs, ctx->d_search, ctx->d_snodes, ctx->d_tab, ctx->d_status, ef,
+                         nullptr, 0);
   });
   const size_t sh = (size_t)mass_lds_doubles(L.NM) * sizeof(double);
   const int ng = plan && plan->ng > 0 ? plan->ng : 1;
@@ -1194,6 +1223,14 @@ static int launch_nu_mass(chomp_ctx* ctx, int mf_kind, const HaloPlan* plan) {
                      ctx->d_sici, ctx->d_nodes, ctx->d_endp, plan ? plan->groups[0] : -1,
                      plan ? plan->groups[1] : -1, plan ? plan->groups[2] : -1,
                      plan ? plan->groups[3] : -1, plan ? plan->kmask : 0u, ctx->d_status, ctx->d_npend, ctx->d_pending);
+  if (ctx->second_order) {
+    // MassFunctionSecondOrder._normalize's third integral (mass_function.py:408-414), behind the
+    // epochs' f_norm and bias_norm
+    hipLaunchKernelGGL(k_mass_b2, dim3((unsigned)n), dim3(64 * kB2NW),
+                       (size_t)b2_lds_doubles(L.NM) * sizeof(double), ctx->stream, ctx->cfg, L,
+                       ctx->B2, ctx->d_epochs, ctx->d_tab, ctx->d_b2, ctx->d_status);
+    ctx->have_b2 = true;
+  }
   HIPCHK(hipGetLastError());
   return CHOMP_OK;
 }
@@ -1793,12 +1830,16 @@ int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k, const double* 
 int chomp_eval(chomp_ctx* ctx, size_t epoch, int what, const double* x, size_t n, double* out,
                int mem) {
   if (!ctx || !x || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "eval: bad args");
-  if (what < 0 || what > CHOMP_EV_DELTA_K) return fail(ctx, CHOMP_ERR_ARG, "eval: unknown function");
+  if (what < 0 || what > CHOMP_EV_SIGMA_OF_NU) return fail(ctx, CHOMP_ERR_ARG, "eval: unknown function");
   if (!ctx->have_epochs || epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "eval: epoch");
-  const bool needs_mass = what <= CHOMP_EV_BIAS_NU;
+  const bool second = what == CHOMP_EV_BIAS_2_NU || what == CHOMP_EV_SIGMA_OF_NU;
+  const bool needs_mass = what <= CHOMP_EV_BIAS_NU || second;
   const bool needs_halo = what >= CHOMP_EV_HOD_FIRST && what <= CHOMP_EV_CONCENTRATION;
   if (needs_mass && !ctx->have_mass) return fail(ctx, CHOMP_ERR_STATE, "eval before mass_setup");
   if (needs_halo && !ctx->have_halo) return fail(ctx, CHOMP_ERR_STATE, "eval before halo_setup");
+  if (second && !ctx->have_b2)
+    return fail(ctx, CHOMP_ERR_STATE, "eval: the last mass set-up was not second-order "
+                                      "(chomp_set_second_order)");
   HIPCHK(hipSetDevice(ctx->device));
   const double* dx = x;
   double* dout = out;
@@ -1815,11 +1856,93 @@ int chomp_eval(chomp_ctx* ctx, size_t epoch, int what, const double* x, size_t n
   unsigned gx = (unsigned)((n + 255) / 256);
   if (gx > 1024) gx = 1024;
   const size_t sh = (size_t)(L.NM + 8 * (L.NM - 1)) * sizeof(double);
-  hipLaunchKernelGGL(k_eval, dim3(gx), dim3(256), sh, ctx->stream, L, ctx->d_epochs, (int)epoch,
-                     ctx->d_tab, what, dx, (int)n, dout);
+  if (second)
+    hipLaunchKernelGGL(k_eval_b2, dim3(gx), dim3(256), (size_t)(L.NM + 4 * (L.NM - 1)) * sizeof(double),
+                       ctx->stream, L, ctx->B2, ctx->d_epochs, (int)epoch, ctx->d_tab, ctx->d_b2,
+                       what, dx, (int)n, dout);
+  else
+    hipLaunchKernelGGL(k_eval, dim3(gx), dim3(256), sh, ctx->stream, L, ctx->d_epochs, (int)epoch,
+                       ctx->d_tab, what, dx, (int)n, dout);
   HIPCHK(hipGetLastError());
   if (mem == CHOMP_HOST) {
     HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return CHOMP_OK;
+}
+
+int chomp_set_second_order(chomp_ctx* ctx, int on) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  ctx->second_order = on != 0;
+  return CHOMP_OK;
+}
+
+int chomp_get_second_order(chomp_ctx* ctx, size_t epoch, double* out, size_t n) {
+  if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "get_second_order: bad args");
+  if (!ctx->have_mass || !ctx->have_b2 || epoch >= ctx->n_epoch)
+    return fail(ctx, CHOMP_ERR_STATE, "get_second_order: no second-order mass set-up of this epoch");
+  const int NM = ctx->L.NM;
+  if (n != (size_t)NM + 3) return fail(ctx, CHOMP_ERR_ARG, "get_second_order: length mismatch");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const double* b = ctx->d_b2 + epoch * (size_t)ctx->B2.stride;
+  HIPCHK(hipMemcpy(out, b + ctx->B2.off_sigma, NM * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out + NM, b + ctx->B2.off_sc, 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
+int chomp_pt_eval(chomp_ctx* ctx, int form, size_t epoch0, size_t n_epoch, const double* args,
+                  size_t n, double* out, int mem) {
+  StageRange range_(ctx, "chomp:pt_eval");
+  if (!ctx || !args || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "pt_eval: bad args");
+  if (form < 0 || form >= kPtForms) return fail(ctx, CHOMP_ERR_ARG, "pt_eval: unknown form");
+  if (mem != CHOMP_HOST && mem != CHOMP_DEVICE) return fail(ctx, CHOMP_ERR_ARG, "pt_eval: mem");
+  if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "pt_eval before epochs_set");
+  if (epoch0 + n_epoch > ctx->n_epoch || n_epoch > 65535)
+    return fail(ctx, CHOMP_ERR_ARG, "pt_eval: epoch range");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t na = (size_t)pt_arity(form);
+  const double* dargs = args;
+  double* dout = out;
+  if (mem == CHOMP_HOST) {
+    int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n * na);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n * n_epoch);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_stage_in, args, n * na * sizeof(double), hipMemcpyHostToDevice,
+                          ctx->stream));
+    dargs = ctx->d_stage_in;
+    dout = ctx->d_stage_out;
+  }
+  // (a grid-stride loop: about 4096 blocks over the whole launch -- 16 per CU -- with the epochs
+  //  as the y axis, so that a block stages its epoch once and then streams configurations)
+  size_t gx = (n + kPtThreads - 1) / kPtThreads;
+  size_t cap = 4096 / n_epoch;
+  if (cap < 1) cap = 1;
+  if (gx > cap) gx = cap;
+  const dim3 grid((unsigned)gx, (unsigned)n_epoch);
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    auto go = [&](auto F) {
+      hipLaunchKernelGGL((k_pt<BAO, decltype(F)::value>), grid, dim3(kPtThreads), 0, ctx->stream,
+                         ctx->d_epochs, (int)epoch0, dargs, n, dout);
+    };
+    switch (form) {
+      case PT_FS2: go(int_c<PT_FS2>{}); break;
+      case PT_FS2_LEN: go(int_c<PT_FS2_LEN>{}); break;
+      case PT_FS2_KDIFF: go(int_c<PT_FS2_KDIFF>{}); break;
+      case PT_FS3: go(int_c<PT_FS3>{}); break;
+      case PT_FS3_PARALLELOGRAM: go(int_c<PT_FS3_PARALLELOGRAM>{}); break;
+      case PT_F3: go(int_c<PT_F3>{}); break;
+      case PT_FS3_BCGS: go(int_c<PT_FS3_BCGS>{}); break;
+      case PT_BISPECTRUM: go(int_c<PT_BISPECTRUM>{}); break;
+      case PT_BISPECTRUM_LEN: go(int_c<PT_BISPECTRUM_LEN>{}); break;
+      case PT_TRISPECTRUM: go(int_c<PT_TRISPECTRUM>{}); break;
+      default: go(int_c<PT_TRISPECTRUM_PARALLELOGRAM>{}); break;
+    }
+  });
+  HIPCHK(hipGetLastError());
+  if (mem == CHOMP_HOST) {
+    HIPCHK(hipMemcpyAsync(out, dout, n * n_epoch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   return CHOMP_OK;

@@ -1005,15 +1005,19 @@ constexpr int kProbeStride = 24;   // doubles per epoch: nu[2][kProbes], chi, pa
 // node table for everybody).  epochs_fastest == 0: grid (NM, n_epoch), an epoch's fifty masses
 // side by side -- a batch of many cosmologies, where the blocks in flight should share as few of
 // the 131 KB node tables as possible (1024 cosmologies, epochs fastest: 600 us against 420).
+// SIG (a MassFunctionSecondOrder set-up, mass_function.py:383-386): sigma(M_i), the root of the
+// same integral, goes to sig[e sig_stride + i] as well.
 // ---------------------------------------------------------------------------
-template <bool BAO, int NW>
+template <bool BAO, int NW, bool SIG = false>
 __global__ __launch_bounds__(64 * NW) void k_nu_table(chomp_config cfg, TabLayout L,
                                                       const Epoch* __restrict__ epochs,
                                                       const double* __restrict__ search,
                                                       const double* __restrict__ snodes,
                                                       double* __restrict__ tab,
                                                       unsigned* __restrict__ status,
-                                                      int epochs_fastest) {
+                                                      int epochs_fastest,
+                                                      double* __restrict__ sig = nullptr,
+                                                      int sig_stride = 0) {
   __shared__ Epoch E;
   __shared__ double red[romberg_scratch<NW, 1>()];
   int e = epochs_fastest ? (int)blockIdx.x : (int)blockIdx.y;
@@ -1053,8 +1057,16 @@ __global__ __launch_bounds__(64 * NW) void k_nu_table(chomp_config cfg, TabLayou
   const double ln_lo = search[(e * 2 + 0) * 2], ln_hi = search[(e * 2 + 1) * 2];
   const double lnm = linspace_at(ln_lo, ln_hi, L.NM, i);
   bool conv = true;
-  const double nu = nu_of_mass_block<NW, 1, BAO>(E, snode, exp(lnm), cfg, cfg.cosmo_precision,
-                                                 red, &conv);
+  double nu;
+  if constexpr (SIG) {      // (nu_of_mass_block's operations, the root kept)
+    const double s2 = sigma2_block<NW, 1, BAO>(E, snode, scale_of_mass(E, exp(lnm)), cfg,
+                                               cfg.cosmo_precision, red, &conv);
+    const double sq = E.delta_c / sqrt(s2);
+    nu = sq * sq;
+    if (threadIdx.x == 0) sig[(size_t)e * sig_stride + i] = sqrt(s2);
+  } else {
+    nu = nu_of_mass_block<NW, 1, BAO>(E, snode, exp(lnm), cfg, cfg.cosmo_precision, red, &conv);
+  }
   if (threadIdx.x == 0) {
     double* t = tab + (size_t)e * L.stride;
     t[L.off_ln_mass + i] = lnm;

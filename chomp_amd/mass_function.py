@@ -1,5 +1,5 @@
-"""mass_function.MassFunction / TinkerMassFunction (mass_function.py:25-362,
-436-564) over the HIP library: the mass-limit search, the 50 sigma(M) integrals,
+"""mass_function.MassFunction / MassFunctionSecondOrder / TinkerMassFunction
+(mass_function.py:25-564) over the HIP library: the mass-limit search, the 50 sigma(M) integrals,
 the nu <-> ln M splines and the normalisations all run on the device."""
 import numpy
 
@@ -136,6 +136,41 @@ class MassFunction(object):
                     "#ttype3 = f(nu)\n#ttype4 = bias(nu)\n")
             for row in zip(*cols):
                 f.write("%1.10f %1.10f %1.10f %1.10f\n" % row)
+
+
+class MassFunctionSecondOrder(MassFunction):
+    """Sheth-Tormen with the second-order bias b2(nu) (mass_function.py:365-434).  The device
+    path is the Sheth-Tormen one (_kind MF_ST, so a Halo on it sets up exactly as on a
+    MassFunction); this object's own context also keeps sigma(M) at the mass knots, builds the
+    sigma(nu) spline and integrates bias_2_norm (chomp_set_second_order).  A setter that changes
+    the cosmology or the halo dictionary re-normalises b2 with the rest, as the overridden
+    _normalize does.  The nu table is the Sheth-Tormen (delta_c / sigma)^2; the reference's
+    subclass writes delta_c / sigma * delta_c / sigma (:386), equal to rounding."""
+
+    def _dev(self):
+        if self._ctx is None:
+            self._ctx = cosmology._context()
+            self._ctx.set_second_order(True)
+        return MassFunction._dev(self)
+
+    def _second(self):
+        return self._dev().second_order(0)
+
+    bias_2_norm = property(lambda self: self._second()["bias_2_norm"])
+    _bias_2_level = property(lambda self: self._second()["level"])
+    _sigma_array = property(lambda self: self._second()["sigma"].copy())
+
+    def _sigma_spline(self, nu):
+        """InterpolatedUnivariateSpline(_nu_array, _sigma_array) (:391-392)."""
+        return self._dev().eval("sigma_of_nu", nu)
+
+    def bias_2_nu(self, nu):
+        """:423-429."""
+        return self._dev().eval("bias_2_nu", nu)
+
+    def bias_2_mass(self, mass):
+        """:431-432."""
+        return self.bias_2_nu(self.nu(mass))
 
 
 class TinkerMassFunction(MassFunction):

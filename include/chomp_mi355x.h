@@ -257,6 +257,11 @@ int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k,
 #define CHOMP_EV_VIRIAL_RADIUS 8
 #define CHOMP_EV_CONCENTRATION 9
 #define CHOMP_EV_DELTA_K 10
+/* MassFunctionSecondOrder (mass_function.py:365-434; needs a mass set-up with
+ * chomp_set_second_order on): bias_2_nu (:423-429) and _sigma_spline, the not-a-knot sigma(nu)
+ * spline over the nu knots (:391-392), extrapolated by its end pieces as FITPACK does. */
+#define CHOMP_EV_BIAS_2_NU 11
+#define CHOMP_EV_SIGMA_OF_NU 12
 int chomp_eval(chomp_ctx* ctx, size_t epoch, int what, const double* x, size_t n,
                double* out, int mem);
 
@@ -333,6 +338,9 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
 #define CHOMP_ST_MASS_SEARCH_EXHAUSTED 4u
 #define CHOMP_ST_SIGMA_DIVMAX 8u
 #define CHOMP_ST_DE_DIVMAX 0x10u
+/* B2_DIVMAX: the bias_2_norm Romberg of a second-order set-up exhausted divmax
+ * (mass_function.py:408-414). */
+#define CHOMP_ST_B2_DIVMAX 0x20u
 #define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..5: H_M, PP_MM, H_G, PP_GM, PP_GG, I_1_2 */
 #define CHOMP_ST_HALO_DIVMAX_PP_MM 0x200u
 #define CHOMP_ST_HALO_DIVMAX_H_G 0x400u
@@ -429,6 +437,54 @@ int chomp_get_table(chomp_ctx* ctx, size_t epoch, int table, double* out,
  * range with an epoch that neither a set-up nor a put has given the table.  Synchronises the
  * host with the context's stream, so it is refused while the stream is being captured. */
 int chomp_put_table(chomp_ctx* ctx, size_t epoch, int table, const double* in, size_t n);
+
+/* ---- Second-order bias and perturbation theory ------------------------------ */
+
+/* mass_function.MassFunctionSecondOrder (mass_function.py:365-434), an opt-in of the context
+ * (off at creation).  With it on, every mass set-up (chomp_mass_setup, chomp_stage_k*) also keeps
+ * sigma(M) at the mass_npoints knots -- the integrals that give nu (:383-386) -- builds the
+ * not-a-knot sigma(nu) spline (:391-392) and integrates bias_2_norm = -int f(nu) b2(nu) dnu over
+ * [nu_min, nu_max] with bias_2_norm = 0 inside (:408-414; mass_precision, global_precision and
+ * divmax, the Romberg of the other normalisations; CHOMP_ST_B2_DIVMAX when divmax runs out).
+ * The nu table itself stays the Sheth-Tormen one, (delta_c / sigma)^2; the subclass writes
+ * delta_c / sigma * delta_c / sigma (:386), which differs from it by rounding.  Off, a set-up
+ * launches what it launched before. */
+int chomp_set_second_order(chomp_ctx* ctx, int on);
+/* out[n] of one epoch after a second-order set-up, n = mass_npoints + 3:
+ * _sigma_array [mass_npoints], bias_2_norm, its Romberg level, 1 if that Romberg converged. */
+int chomp_get_second_order(chomp_ctx* ctx, size_t epoch, double* out, size_t n);
+
+/* perturbation_spectra.PerturbationTheory (perturbation_spectra.py:59-345): the tree-level forms
+ * for n configurations over the epochs [epoch0, epoch0 + n_epoch) of the batch,
+ * out[(e - epoch0) n + i] (fp64).  args[i] holds the doubles of configuration i, row-major:
+ *   FS2                  (:89-105)   k1[3], k2[3]                        6
+ *   FS2_LEN              (:107-123)  k1, k2, z                           3
+ *   FS2_KDIFF            (:125-132)  k1, k2, mu                          3
+ *   FS3                  (:147-180)  k1[3], k2[3], k3[3]                 9
+ *   FS3_PARALLELOGRAM    (:182-199)  k1, k2, mu                          3
+ *   F3                   (:201-223)  k1[3], k2[3], k3[3]                 9
+ *   FS3_BCGS             (:225-229)  k1[3], k2[3], k3[3] (default F3)    9
+ *   BISPECTRUM           (:231-249)  k1[3], k2[3], k3[3]                 9
+ *   BISPECTRUM_LEN       (:251-259)  k1, k2, k3, z12, z13, z23           6
+ *   TRISPECTRUM          (:261-310)  k1[3], k2[3], k3[3], k4[3]         12
+ *   TRISPECTRUM_PARALLELOGRAM (:312-345) k1, k2, mu                      3
+ * The reference's operation order, thresholds and branches are kept (Fs3 and Fs3_BCGS disagree
+ * as shipped); every P_lin is the epoch's linear spectrum as CHOMP_P_LIN computes it.  Needs
+ * chomp_epochs_set only.  mem: CHOMP_HOST (staged, synchronous) or CHOMP_DEVICE (args and out in
+ * HBM, asynchronous on the context's stream). */
+#define CHOMP_PT_FS2 0
+#define CHOMP_PT_FS2_LEN 1
+#define CHOMP_PT_FS2_KDIFF 2
+#define CHOMP_PT_FS3 3
+#define CHOMP_PT_FS3_PARALLELOGRAM 4
+#define CHOMP_PT_F3 5
+#define CHOMP_PT_FS3_BCGS 6
+#define CHOMP_PT_BISPECTRUM 7
+#define CHOMP_PT_BISPECTRUM_LEN 8
+#define CHOMP_PT_TRISPECTRUM 9
+#define CHOMP_PT_TRISPECTRUM_PARALLELOGRAM 10
+int chomp_pt_eval(chomp_ctx* ctx, int form, size_t epoch0, size_t n_epoch, const double* args,
+                  size_t n, double* out, int mem);
 
 /* ---- Projection: MultiEpoch, windows, kernel, correlation --------------------
  * One projection set-up per context. */
