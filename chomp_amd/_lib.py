@@ -78,6 +78,9 @@ class HodPar(ctypes.Structure):
 
 
 HOD_ZHENG, HOD_MANDELBAUM = 0, 1
+# CHOMP_TRI_*: the n(M) of the one-halo trispectrum for each power_spec (halo_trispectrum.py:142-151);
+# any other string integrates with n = 1
+TRI_MOMENT = {"power_mmmm": 0, "power_gmmm": 1, "power_ggmm": 2, "power_gggm": 3, "power_gggg": 4}
 DE_EPOCH, DE_PROJ = 0, 1       # chomp_get_de_table sources
 
 
@@ -132,12 +135,14 @@ EXPORTS = [
     "chomp_halo_setup_hod", "chomp_stage_k_hod", "chomp_stage_k_halofit_hod",
     "chomp_set_dark_energy", "chomp_get_de_table",
     "chomp_set_second_order", "chomp_get_second_order", "chomp_pt_eval",
+    "chomp_tri1h_setup", "chomp_tri1h_eval", "chomp_tri1h_quad",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
 ST_MASS_MIN_SATURATED, ST_MASS_MAX_SATURATED, ST_MASS_SEARCH_EXHAUSTED, ST_SIGMA_DIVMAX = 1, 2, 4, 8
 ST_DE_DIVMAX = 0x10
 ST_B2_DIVMAX = 0x20
+ST_TRI1H_DIVMAX = 0x40
 ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000,
                   "i_1_2": 0x2000}
 ST_NONFINITE = 0x10000
@@ -175,6 +180,9 @@ def describe_status(word):
         out.append("a Romberg of the dark-energy pressure table exhausted divmax")
     if word & ST_B2_DIVMAX:
         out.append("the bias_2_norm Romberg exhausted divmax (mass_function.py:408-414)")
+    if word & ST_TRI1H_DIVMAX:
+        out.append("an I_0^4 Romberg of the one-halo trispectrum exhausted divmax "
+                   "(halo_trispectrum.py:89-95)")
     for name, bit in ST_HALO_DIVMAX.items():
         if word & bit:
             out.append("%s: Romberg exhausted divmax at some knots (last row kept)" % name)
@@ -388,6 +396,9 @@ def lib():
         L.chomp_set_second_order.argtypes = [vp, i]
         L.chomp_get_second_order.argtypes = [vp, sz, c_double_p, sz]
         L.chomp_pt_eval.argtypes = [vp, i, sz, sz, vp, sz, vp, i]
+        L.chomp_tri1h_setup.argtypes = [vp, sz, sz, i, vp, vp]
+        L.chomp_tri1h_eval.argtypes = [vp, sz, vp, vp, sz, vp, i]
+        L.chomp_tri1h_quad.argtypes = [vp, sz, i, vp, sz, vp, vp, i]
         L.chomp_set_timing.argtypes = [vp, i]
         L.chomp_get_timing.argtypes = [vp, c_double_p, sz]
         L.chomp_get_status.argtypes = [vp, sz, sz, ctypes.POINTER(ctypes.c_uint)]
@@ -679,6 +690,65 @@ class Context(object):
                                               ctypes.c_void_p(a.ctypes.data), a.shape[0],
                                               ctypes.c_void_p(out.ctypes.data), HOST))
         return out
+
+    # -- one-halo trispectrum -------------------------------------------------------
+    def tri1h_setup(self, moment, epoch0=0, n=None, copy_out=False):
+        """The I_0^4 table, its levels and its bicubic of the epochs [epoch0, epoch0 + n)
+        (chomp_tri1h_setup; moment: a CHOMP_TRI_* code).  copy_out: return (table, levels), each
+        [n, N, N] (synchronises); else None, asynchronous."""
+        n = self.n_epoch - epoch0 if n is None else n
+        if not copy_out:
+            self._check(self._L.chomp_tri1h_setup(self._h, epoch0, n, int(moment), None, None))
+            return None
+        nk = self.config.halo_npoints
+        tab = numpy.empty((n, nk, nk))
+        lev = numpy.empty((n, nk, nk))
+        self._check(self._L.chomp_tri1h_setup(self._h, epoch0, n, int(moment),
+                                              ctypes.c_void_p(tab.ctypes.data),
+                                              ctypes.c_void_p(lev.ctypes.data)))
+        return tab, lev
+
+    def tri1h_eval(self, ln_k1, ln_k2, epoch=0):
+        """The table's bicubic at the points (ln_k1[i], ln_k2[i]) (chomp_tri1h_eval), each
+        argument clamped into the knot range."""
+        a = numpy.ascontiguousarray(ln_k1, dtype=numpy.float64).ravel()
+        b = numpy.ascontiguousarray(ln_k2, dtype=numpy.float64).ravel()
+        assert a.size == b.size
+        out = numpy.empty(a.size)
+        if a.size:
+            self._check(self._L.chomp_tri1h_eval(self._h, epoch, ctypes.c_void_p(a.ctypes.data),
+                                                 ctypes.c_void_p(b.ctypes.data), a.size,
+                                                 ctypes.c_void_p(out.ctypes.data), HOST))
+        return out
+
+    def tri1h_quad(self, moment, k, epoch=0, levels=False):
+        """i_0_4 at the quadruples k [N, 4] (chomp_tri1h_quad): numpy (host path) or a contiguous
+        float64 torch cuda tensor (device path, asynchronous; returns tensors).  levels: also
+        return the Romberg levels."""
+        if _is_torch(k):
+            import torch
+            assert k.is_cuda and k.dtype == torch.float64 and k.is_contiguous()
+            m = k.numel() // 4
+            assert m * 4 == k.numel()
+            out = torch.empty(m, dtype=torch.float64, device=k.device)
+            lev = torch.empty(m, dtype=torch.float64, device=k.device) if levels else None
+            if m:
+                pair = self._torch_enter()
+                self._check(self._L.chomp_tri1h_quad(
+                    self._h, epoch, int(moment), ctypes.c_void_p(k.data_ptr()), m,
+                    ctypes.c_void_p(out.data_ptr()),
+                    ctypes.c_void_p(lev.data_ptr()) if levels else None, DEVICE))
+                self._torch_leave(pair)
+            return (out, lev) if levels else out
+        a = numpy.ascontiguousarray(k, dtype=numpy.float64).reshape(-1, 4)
+        out = numpy.empty(a.shape[0])
+        lev = numpy.empty(a.shape[0]) if levels else None
+        if a.shape[0]:
+            self._check(self._L.chomp_tri1h_quad(
+                self._h, epoch, int(moment), ctypes.c_void_p(a.ctypes.data), a.shape[0],
+                ctypes.c_void_p(out.ctypes.data),
+                ctypes.c_void_p(lev.ctypes.data) if levels else None, HOST))
+        return (out, lev) if levels else out
 
     def halofit_setup(self, dst, src, f1, f2, f3, omega_l, w):
         self._check(self._L.chomp_halofit_setup(self._h, dst, src, f1, f2, f3,

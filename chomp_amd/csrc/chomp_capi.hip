@@ -26,6 +26,7 @@
 #include "chomp_probe_kernel.h"
 #include "chomp_de_kernels.h"
 #include "chomp_pt_kernels.h"
+#include "chomp_tri_kernels.h"
 
 using namespace chomp;
 
@@ -201,6 +202,15 @@ struct chomp_ctx {
   B2Layout B2;
   double* d_b2 = nullptr;
   size_t cap_b2 = 0;
+  // HaloTrispectrumOneHalo (chomp_tri1h_setup): per epoch the I_0^4 table, its levels and its
+  // bicubic (TriLayout); tri_built: the epoch has one since chomp_epochs_set
+  TriLayout T3;
+  double* d_tri = nullptr;
+  size_t cap_tri = 0;
+  std::vector<char> tri_built;
+  double* d_tri_in = nullptr;      // staging of the host-pointer trispectrum calls
+  double* d_tri_out = nullptr;
+  size_t cap_tri_in = 0, cap_tri_out = 0;
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
   bool timing_valid = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -611,7 +621,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_stage_in, ctx->d_stage_in2, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par, ctx->d_b2};
+                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri_in, ctx->d_tri_out};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -978,6 +988,7 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   ctx->put_mask.assign(n_epoch, 0u);
   ctx->delta_b_zero = true;
   ctx->have_halofit.assign(n_epoch, 0);
+  ctx->tri_built.assign(n_epoch, 0);
   rc = upload(ctx, ctx->d_cosmo, cosmo, n_epoch * sizeof(chomp_cosmo), ctx->sh_cosmo);
   if (rc) return rc;
   rc = upload(ctx, ctx->d_z, z, n_epoch * sizeof(double), ctx->sh_z);
@@ -1481,6 +1492,7 @@ int chomp_set_transfer(chomp_ctx* ctx, int kind) {
     ctx->have_epochs = ctx->have_mass = ctx->have_halo = false;   // every table depends on T(k)
     ctx->fam_mask = 0;
     ctx->put_mask.assign(ctx->put_mask.size(), 0u);
+    ctx->tri_built.assign(ctx->tri_built.size(), 0);
   }
   return CHOMP_OK;
 }
@@ -1943,6 +1955,132 @@ int chomp_pt_eval(chomp_ctx* ctx, int form, size_t epoch0, size_t n_epoch, const
   HIPCHK(hipGetLastError());
   if (mem == CHOMP_HOST) {
     HIPCHK(hipMemcpyAsync(out, dout, n * n_epoch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return CHOMP_OK;
+}
+
+// -- HaloTrispectrumOneHalo (halo_trispectrum.py:13-151) ------------------------------------------
+static bool tri_moment_ok(int moment) { return moment >= CHOMP_TRI_MMMM && moment <= CHOMP_TRI_GGGG; }
+
+// Replaces _initialize_i_0_4 (halo_trispectrum.py:104-129): the 1275 i_0_4 calls of its loop
+// (:60-95, one scipy Romberg each) and the RectBivariateSpline fit, for a range of epochs.
+int chomp_tri1h_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, int moment,
+                      double* table_out, double* levels_out) {
+  StageRange range_(ctx, "chomp:tri1h_setup");
+  if (!ctx || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: bad args");
+  if (!tri_moment_ok(moment)) return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: unknown moment");
+  if (!ctx->have_halo) return fail(ctx, CHOMP_ERR_STATE, "tri1h_setup before a halo set-up");
+  if (epoch0 + n_epoch > ctx->n_epoch || n_epoch > 65535)
+    return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: epoch range");
+  const int N = ctx->L.NK;
+  if (N < 4 || N > 64)
+    return fail(ctx, CHOMP_ERR_SCOPE, "tri1h_setup: halo_npoints must lie in [4, 64]");
+  if (ctx->cfg.divmax > kMaxDivmax) return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: divmax");
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->T3 = make_tri_layout(N);
+  const TriLayout& T = ctx->T3;
+  const size_t need = ctx->n_epoch * (size_t)T.total;
+  if (need > ctx->cap_tri) {          // (a grown buffer holds no epoch's table)
+    const int rc = ensure(ctx, &ctx->d_tri, &ctx->cap_tri, need);
+    if (rc) return rc;
+    ctx->tri_built.assign(ctx->n_epoch, 0);
+  }
+  const int lds = tri_table_lds_doubles(ctx->L.NM, N) * (int)sizeof(double);
+  { const int rc = lds_opt_in(ctx, &k_tri1h_table, lds); if (rc) return rc; }
+  hipLaunchKernelGGL(k_tri1h_table, dim3((unsigned)T.nchunk, (unsigned)n_epoch), dim3(kTriThreads),
+                     (size_t)lds, ctx->stream, ctx->cfg, ctx->L, T, ctx->d_epochs, (int)epoch0,
+                     ctx->d_tab, ctx->d_sici, moment, ctx->d_tri);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_tri1h_bicubic, dim3((unsigned)n_epoch), dim3(256), 0, ctx->stream, T,
+                     (int)epoch0, ctx->d_tri, ctx->d_status);
+  HIPCHK(hipGetLastError());
+  for (size_t e = epoch0; e < epoch0 + n_epoch; ++e) ctx->tri_built[e] = 1;
+  if (table_out || levels_out) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t nn = (size_t)N * N;
+    for (size_t e = 0; e < n_epoch; ++e) {
+      const double* b = ctx->d_tri + (epoch0 + e) * (size_t)T.total;
+      if (table_out)
+        HIPCHK(hipMemcpy(table_out + e * nn, b + T.tab, nn * sizeof(double), hipMemcpyDeviceToHost));
+      if (levels_out)
+        HIPCHK(hipMemcpy(levels_out + e * nn, b + T.lev, nn * sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  return CHOMP_OK;
+}
+
+// Replaces the _i_0_4_spline(ln k1, ln k2) look-ups of i_0_4_parallelogram
+// (halo_trispectrum.py:97-102).
+int chomp_tri1h_eval(chomp_ctx* ctx, size_t epoch, const double* ln_k1, const double* ln_k2,
+                     size_t n, double* out, int mem) {
+  StageRange range_(ctx, "chomp:tri1h_eval");
+  if (!ctx || !ln_k1 || !ln_k2 || !out || n == 0 || n > (size_t)INT32_MAX)
+    return fail(ctx, CHOMP_ERR_ARG, "tri1h_eval: bad args");
+  if (mem != CHOMP_HOST && mem != CHOMP_DEVICE) return fail(ctx, CHOMP_ERR_ARG, "tri1h_eval: mem");
+  if (epoch >= ctx->n_epoch || epoch >= ctx->tri_built.size() || !ctx->tri_built[epoch])
+    return fail(ctx, CHOMP_ERR_STATE, "tri1h_eval: no trispectrum table of this epoch (chomp_tri1h_setup)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double *da = ln_k1, *db = ln_k2;
+  double* dout = out;
+  if (mem == CHOMP_HOST) {
+    int rc = ensure(ctx, &ctx->d_tri_in, &ctx->cap_tri_in, 2 * n);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->d_tri_out, &ctx->cap_tri_out, n);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_tri_in, ln_k1, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_tri_in + n, ln_k2, n * sizeof(double), hipMemcpyHostToDevice,
+                          ctx->stream));
+    da = ctx->d_tri_in;
+    db = ctx->d_tri_in + n;
+    dout = ctx->d_tri_out;
+  }
+  size_t gx = (n + 255) / 256;
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(k_tri1h_eval, dim3((unsigned)gx), dim3(256), 0, ctx->stream, ctx->T3,
+                     ctx->d_tri, (int)epoch, da, db, (int)n, dout);
+  HIPCHK(hipGetLastError());
+  if (mem == CHOMP_HOST) {
+    HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return CHOMP_OK;
+}
+
+// Replaces i_0_4 / trispectrum (halo_trispectrum.py:57-95): one scipy Romberg per call.
+int chomp_tri1h_quad(chomp_ctx* ctx, size_t epoch, int moment, const double* k, size_t n,
+                     double* out, double* levels, int mem) {
+  StageRange range_(ctx, "chomp:tri1h_quad");
+  if (!ctx || !k || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: bad args");
+  if (!tri_moment_ok(moment)) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: unknown moment");
+  if (mem != CHOMP_HOST && mem != CHOMP_DEVICE) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: mem");
+  if (!ctx->have_halo || epoch >= ctx->n_epoch)
+    return fail(ctx, CHOMP_ERR_STATE, "tri1h_quad before a halo set-up of this epoch");
+  const size_t nb = (n + kTriQuadWaves - 1) / kTriQuadWaves;
+  if (nb > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: too many quadruples");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* dk = k;
+  double* dout = out;
+  double* dlev = levels;
+  if (mem == CHOMP_HOST) {
+    int rc = ensure(ctx, &ctx->d_tri_in, &ctx->cap_tri_in, 4 * n);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->d_tri_out, &ctx->cap_tri_out, 2 * n);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_tri_in, k, 4 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    dk = ctx->d_tri_in;
+    dout = ctx->d_tri_out;
+    dlev = levels ? ctx->d_tri_out + n : nullptr;
+  }
+  const int lds = tri_quad_lds_doubles(ctx->L.NM) * (int)sizeof(double);
+  hipLaunchKernelGGL(k_tri1h_quad, dim3((unsigned)nb), dim3(64 * kTriQuadWaves), (size_t)lds,
+                     ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab,
+                     ctx->d_sici, moment, dk, (long)n, dout, dlev, ctx->d_status);
+  HIPCHK(hipGetLastError());
+  if (mem == CHOMP_HOST) {
+    HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (levels)
+      HIPCHK(hipMemcpyAsync(levels, dlev, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   return CHOMP_OK;

@@ -203,37 +203,45 @@ __global__ __launch_bounds__(256) void k_ssc_table(chomp_config cfg, ProjLayout 
   }
 }
 
-// grid 1, block 256: the tensor-product not-a-knot bicubic of the table -- what FITPACK's
-// regrid with s = 0 and kx = ky = 3 interpolates with (knots at x_0 x4, x_2 .. x_{N-3},
-// x_{N-1} x4 in both directions).  The 1D solver of chomp_math.h runs along b for every row,
-// then along a for every (interval, power) of the row pieces:
+// The tensor-product not-a-knot bicubic of an N x N table over the knots x in both directions
+// -- what FITPACK's regrid with s = 0 and kx = ky = 3 interpolates with (knots at x_0 x4, x_2 ..
+// x_{N-3}, x_{N-1} x4 in both directions).  The 1D solver of chomp_math.h runs along b for every
+// row, then along a for every (interval, power) of the row pieces:
 //   S(a, b) = sum_{p,q} bic[((ia (N-1) + jb) 4 + p) 4 + q] (a - x_ia)^p (b - x_jb)^q.
-__global__ __launch_bounds__(256) void k_ssc_bicubic(SscLayout S, double* __restrict__ st) {
-  const int N = S.N, M = N - 1;
-  const double* x = st + S.kx;
-  double* wk = st + S.work + (size_t)threadIdx.x * 6 * N;   // (4 M + 2 N doubles per thread)
+// One block (blockDim.x >= N; all threads call).  rowt: 4 (N-1) N doubles, work: 4 (N-1) 6 N
+// doubles (6 N per thread), bic: 16 (N-1)^2 doubles, all in global memory.  Shared by
+// KernelCovariance.kernel_ssc (k_ssc_bicubic) and HaloTrispectrumOneHalo (k_tri1h_bicubic).
+__device__ __forceinline__ void bicubic_build(int N, const double* x, const double* tab,
+                                              double* rowt, double* work, double* bic) {
+  const int M = N - 1;
+  double* wk = work + (size_t)threadIdx.x * 6 * N;   // (4 M + 2 N doubles per thread)
   if ((int)threadIdx.x < N) {
     const int i = threadIdx.x;
     double* c = wk;
-    spline_build(x, st + S.tab + (size_t)i * N, N, c, c + 4 * M);
-    for (int q = 0; q < 4 * M; ++q) st[S.rowt + (size_t)q * N + i] = c[q];
+    spline_build(x, tab + (size_t)i * N, N, c, c + 4 * M);
+    for (int q = 0; q < 4 * M; ++q) rowt[(size_t)q * N + i] = c[q];
   }
   __threadfence_block();
   __syncthreads();
   for (int q = threadIdx.x; q < 4 * M; q += blockDim.x) {
-    double* wq = st + S.work + (size_t)q * 6 * N;
+    double* wq = work + (size_t)q * 6 * N;
     double* c = wq;
-    spline_build(x, st + S.rowt + (size_t)q * N, N, c, c + 4 * M);
+    spline_build(x, rowt + (size_t)q * N, N, c, c + 4 * M);
     const int jb = q >> 2, mb = q & 3;
     for (int ia = 0; ia < M; ++ia)
       for (int ma = 0; ma < 4; ++ma)
-        st[S.bic + (((size_t)ia * M + jb) * 4 + ma) * 4 + mb] = c[4 * ia + ma];
+        bic[(((size_t)ia * M + jb) * 4 + ma) * 4 + mb] = c[4 * ia + ma];
   }
 }
 
-// KernelCovariance.kernel_ssc at one point (kernel.py:1113-1130): ln k theta <= min is clamped
-// to min; either above max gives 0.
-struct SscSpline {
+// grid 1, block 256: the bicubic of the kernel_ssc table.
+__global__ __launch_bounds__(256) void k_ssc_bicubic(SscLayout S, double* __restrict__ st) {
+  bicubic_build(S.N, st + S.kx, st + S.tab, st + S.rowt, st + S.work, st + S.bic);
+}
+
+// A bicubic of bicubic_build: knots x[0..N-1] (uniform in intent, lo = x_0, hi = x_{N-1}), the
+// interval search and the tensor-product polynomial, with no range rule of its own.
+struct Bicubic {
   const double *x, *bic;
   int N;
   double lo, hi;
@@ -245,10 +253,7 @@ struct SscSpline {
     if (i < N - 2 && v >= x[i + 1]) ++i;
     return i;
   }
-  __device__ __forceinline__ double operator()(double a, double b) const {
-    if (a <= lo) a = lo;
-    if (b <= lo) b = lo;
-    if (!(a <= hi && b <= hi)) return 0.0;
+  __device__ __forceinline__ double poly(double a, double b) const {
     const int ia = interval(a), jb = interval(b);
     const double da = a - x[ia], db = b - x[jb];
     const double* c = bic + ((size_t)ia * (N - 1) + jb) * 16;
@@ -259,8 +264,25 @@ struct SscSpline {
     return fma(fma(fma(r[3], da, r[2]), da, r[1]), da, r[0]);
   }
 };
+
+// KernelCovariance.kernel_ssc at one point (kernel.py:1113-1130): ln k theta <= min is clamped
+// to min; either above max gives 0.
+struct SscSpline : Bicubic {
+  __device__ __forceinline__ double operator()(double a, double b) const {
+    if (a <= lo) a = lo;
+    if (b <= lo) b = lo;
+    if (!(a <= hi && b <= hi)) return 0.0;
+    return poly(a, b);
+  }
+};
 __device__ __forceinline__ SscSpline ssc_spline(const SscLayout& S, const double* st) {
-  return SscSpline{st + S.kx, st + S.bic, S.N, st[S.scal + kSscLnMin], st[S.scal + kSscLnMax]};
+  SscSpline K;
+  K.x = st + S.kx;
+  K.bic = st + S.bic;
+  K.N = S.N;
+  K.lo = st[S.scal + kSscLnMin];
+  K.hi = st[S.scal + kSscLnMax];
+  return K;
 }
 
 __global__ void k_ssc_eval(SscLayout S, const double* __restrict__ st,

@@ -341,6 +341,10 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
 /* B2_DIVMAX: the bias_2_norm Romberg of a second-order set-up exhausted divmax
  * (mass_function.py:408-414). */
 #define CHOMP_ST_B2_DIVMAX 0x20u
+/* TRI1H_DIVMAX: an I_0^4 Romberg of the last one-halo trispectrum table of the epoch
+ * (chomp_tri1h_setup; halo_trispectrum.py:89-95), or of a chomp_tri1h_quad call since, exhausted
+ * divmax.  Each table set-up sets or clears it for its epochs. */
+#define CHOMP_ST_TRI1H_DIVMAX 0x40u
 #define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..5: H_M, PP_MM, H_G, PP_GM, PP_GG, I_1_2 */
 #define CHOMP_ST_HALO_DIVMAX_PP_MM 0x200u
 #define CHOMP_ST_HALO_DIVMAX_H_G 0x400u
@@ -485,6 +489,42 @@ int chomp_get_second_order(chomp_ctx* ctx, size_t epoch, double* out, size_t n);
 #define CHOMP_PT_TRISPECTRUM_PARALLELOGRAM 10
 int chomp_pt_eval(chomp_ctx* ctx, int form, size_t epoch0, size_t n_epoch, const double* args,
                   size_t n, double* out, int mem);
+
+/* ---- One-halo trispectrum ---------------------------------------------------- */
+
+/* halo_trispectrum.HaloTrispectrumOneHalo (halo_trispectrum.py:13-151).  moment: the n(M) of the
+ * integrand, the HOD moment its power_spec selects (:142-151) of the epoch's HOD model (the one
+ * the last halo set-up installed):
+ *   MMMM 1 ('power_mmmm' and any other string), GMMM <N>, GGMM <N(N-1)>, GGGM and GGGG
+ *   nth_moment(n = 3, 4) by the product formula of hod.py:68-92. */
+#define CHOMP_TRI_MMMM 0
+#define CHOMP_TRI_GMMM 1
+#define CHOMP_TRI_GGMM 2
+#define CHOMP_TRI_GGGM 3
+#define CHOMP_TRI_GGGG 4
+/* _initialize_i_0_4 (halo_trispectrum.py:104-129) for the epochs [epoch0, epoch0 + n_epoch):
+ * the N x N table (N = halo_npoints <= 64) of I_0^4(k_i, k_i, k_j, k_j) over the knots
+ * ln k_i = linspace(ln k_min, ln k_max, N) -- i_0_4 (:60-95): the Romberg over
+ * [ln nu_min, ln nu_max] of nu f(nu) y^2(k_i, M) y^2(k_j, M) M^3 n(M) with halo_precision,
+ * global_precision and divmax, / rho_bar^3 -- the upper triangle integrated and mirrored, each
+ * entry's Romberg level, and the bicubic RectBivariateSpline(kx = ky = 3, s = 0) of the table.
+ * Needs a halo set-up of those epochs (chomp_halo_setup*, chomp_stage_k*; no knot table has to
+ * be built).  table_out, levels_out (optional, host): n_epoch N N doubles, epoch-major,
+ * row-major (synchronises).  CHOMP_ST_TRI1H_DIVMAX reports an exhausted divmax. */
+int chomp_tri1h_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, int moment,
+                      double* table_out, double* levels_out);
+/* i_0_4_parallelogram's spline (halo_trispectrum.py:97-102) of one epoch's table at n points
+ * (ln_k1[i], ln_k2[i]): each argument is clamped into [ln k_min, ln k_max] as FITPACK's bispev
+ * does; the reference's k_min clamp and k_max mask (which shape the result) are the caller's.
+ * mem: CHOMP_HOST (staged, synchronous) or CHOMP_DEVICE. */
+int chomp_tri1h_eval(chomp_ctx* ctx, size_t epoch, const double* ln_k1, const double* ln_k2,
+                     size_t n, double* out, int mem);
+/* i_0_4 / trispectrum (halo_trispectrum.py:57-95) at n quadruples k[i][0..3] of one epoch, one
+ * Romberg each (the reference's rule); out[n], levels[n] (optional) the Romberg levels.  Needs a
+ * halo set-up of the epoch.  mem: CHOMP_HOST (staged, synchronous) or CHOMP_DEVICE (k, out and
+ * levels in HBM, asynchronous on the context's stream). */
+int chomp_tri1h_quad(chomp_ctx* ctx, size_t epoch, int moment, const double* k, size_t n,
+                     double* out, double* levels, int mem);
 
 /* ---- Projection: MultiEpoch, windows, kernel, correlation --------------------
  * One projection set-up per context. */
