@@ -5,6 +5,7 @@ The HIP library is the only compute path of this package: if it cannot be loaded
 fallback.
 """
 import ctypes
+import operator
 import os
 import subprocess
 import threading
@@ -366,8 +367,8 @@ def lib():
         L.chomp_power.argtypes = [vp, i, vp, sz, vp, i]
         L.chomp_power_range.argtypes = [vp, i, sz, sz, vp, sz, vp, i]
         L.chomp_power_plan.argtypes = [vp, sz, vp, sz]
-        L.chomp_sigma_r.argtypes = [vp, sz, c_double_p, sz, c_double_p]
-        L.chomp_y_nfw.argtypes = [vp, sz, c_double_p, c_double_p, sz, c_double_p]
+        L.chomp_sigma_r.argtypes = [vp, sz, vp, sz, vp]
+        L.chomp_y_nfw.argtypes = [vp, sz, vp, vp, sz, vp]
         L.chomp_get_scalars.argtypes = [vp, sz, c_double_p]
         L.chomp_get_table.argtypes = [vp, sz, i, c_double_p, sz]
         L.chomp_put_table.argtypes = [vp, sz, i, c_double_p, sz]
@@ -411,13 +412,11 @@ def lib():
         L.chomp_covariance_gaussian.argtypes = [vp, d, d, d, d, vp, sz, vp, i]
         L.chomp_kernel_ssc_setup.argtypes = [vp, d, d, d, c_double_p, c_double_p, sz, i,
                                              c_double_p, c_double_p, c_double_p]
-        L.chomp_kernel_ssc_raw.argtypes = [vp, c_double_p, sz, c_double_p]
-        L.chomp_kernel_ssc_eval.argtypes = [vp, c_double_p, sz, c_double_p]
-        L.chomp_covariance_ssc.argtypes = [vp, sz, d, c_double_p, sz, c_double_p, c_double_p,
-                                           c_double_p]
+        L.chomp_kernel_ssc_raw.argtypes = [vp, vp, sz, vp]
+        L.chomp_kernel_ssc_eval.argtypes = [vp, vp, sz, vp]
+        L.chomp_covariance_ssc.argtypes = [vp, sz, d, vp, sz, vp, vp, vp]
         L.chomp_xi3d.argtypes = [vp, i, sz, d, d, vp, sz, vp, i]
-        L.chomp_spline_eval.argtypes = [vp, c_double_p, c_double_p, sz, c_double_p, sz, i,
-                                        c_double_p]
+        L.chomp_spline_eval.argtypes = [vp, vp, vp, sz, vp, sz, i, vp]
         for name in EXPORTS:
             if name not in ("chomp_default_config", "chomp_ctx_destroy",
                             "chomp_last_error"):
@@ -487,6 +486,28 @@ def hod_model(hod):
 
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
+
+
+def _numel(x):
+    """Elements of a numpy array or a torch tensor."""
+    return x.size if isinstance(x, numpy.ndarray) else x.numel()
+
+
+_host_address = operator.attrgetter("ctypes.data")
+
+
+def _elementwise(*pre, shape=None):
+    """Context._run's body of an element-wise entry point fn(handle, *pre, x, n, out, mem): out
+    shaped like x (or `shape`)."""
+    return lambda mem, new, x: pre + (x, _numel(x), new(x.shape if shape is None else shape), mem)
+
+
+def _pairs(a, b):
+    """The pairs of the covariance calls: two host arrays of one length, one after the other."""
+    a = numpy.ascontiguousarray(a, dtype=numpy.float64).ravel()
+    b = numpy.ascontiguousarray(b, dtype=numpy.float64).ravel()
+    assert a.size == b.size
+    return numpy.concatenate([a, b])
 
 
 def _torch_current_stream(device):
@@ -670,26 +691,13 @@ class Context(object):
         cuda tensor (device path, asynchronous on the context's stream; returns a tensor)."""
         n = self.n_epoch - epoch0 if n is None else n
         na = PT_ARITY[form]
-        if _is_torch(args):
-            import torch
-            assert args.is_cuda and args.dtype == torch.float64 and args.is_contiguous()
-            m = args.numel() // na
-            assert m * na == args.numel()
-            out = torch.empty((n, m), dtype=torch.float64, device=args.device)
-            if m:
-                pair = self._torch_enter()
-                self._check(self._L.chomp_pt_eval(self._h, PT[form], epoch0, n,
-                                                  ctypes.c_void_p(args.data_ptr()), m,
-                                                  ctypes.c_void_p(out.data_ptr()), DEVICE))
-                self._torch_leave(pair)
-            return out
-        a = numpy.ascontiguousarray(args, dtype=numpy.float64).reshape(-1, na)
-        out = numpy.empty((n, a.shape[0]), dtype=numpy.float64)
-        if a.shape[0]:
-            self._check(self._L.chomp_pt_eval(self._h, PT[form], epoch0, n,
-                                              ctypes.c_void_p(a.ctypes.data), a.shape[0],
-                                              ctypes.c_void_p(out.ctypes.data), HOST))
-        return out
+
+        def body(mem, new, a):
+            m, rest = divmod(_numel(a), na)
+            if rest:
+                raise ValueError("pt_eval: %s takes %d numbers a configuration" % (form, na))
+            return PT[form], epoch0, n, a, m, new((n, m)), mem
+        return self._run(self._L.chomp_pt_eval, [args], body)[0]
 
     # -- one-halo trispectrum -------------------------------------------------------
     def tri1h_setup(self, moment, epoch0=0, n=None, copy_out=False):
@@ -710,45 +718,24 @@ class Context(object):
 
     def tri1h_eval(self, ln_k1, ln_k2, epoch=0):
         """The table's bicubic at the points (ln_k1[i], ln_k2[i]) (chomp_tri1h_eval), each
-        argument clamped into the knot range."""
-        a = numpy.ascontiguousarray(ln_k1, dtype=numpy.float64).ravel()
-        b = numpy.ascontiguousarray(ln_k2, dtype=numpy.float64).ravel()
-        assert a.size == b.size
-        out = numpy.empty(a.size)
-        if a.size:
-            self._check(self._L.chomp_tri1h_eval(self._h, epoch, ctypes.c_void_p(a.ctypes.data),
-                                                 ctypes.c_void_p(b.ctypes.data), a.size,
-                                                 ctypes.c_void_p(out.ctypes.data), HOST))
-        return out
+        argument clamped into the knot range: numpy (host path) or contiguous float64 torch cuda
+        tensors (device path, asynchronous; returns a tensor)."""
+        def body(mem, new, a, b):
+            assert _numel(a) == _numel(b)
+            return epoch, a, b, _numel(a), new(_numel(a)), mem
+        return self._run(self._L.chomp_tri1h_eval, [ln_k1, ln_k2], body)[0]
 
     def tri1h_quad(self, moment, k, epoch=0, levels=False):
         """i_0_4 at the quadruples k [N, 4] (chomp_tri1h_quad): numpy (host path) or a contiguous
         float64 torch cuda tensor (device path, asynchronous; returns tensors).  levels: also
         return the Romberg levels."""
-        if _is_torch(k):
-            import torch
-            assert k.is_cuda and k.dtype == torch.float64 and k.is_contiguous()
-            m = k.numel() // 4
-            assert m * 4 == k.numel()
-            out = torch.empty(m, dtype=torch.float64, device=k.device)
-            lev = torch.empty(m, dtype=torch.float64, device=k.device) if levels else None
-            if m:
-                pair = self._torch_enter()
-                self._check(self._L.chomp_tri1h_quad(
-                    self._h, epoch, int(moment), ctypes.c_void_p(k.data_ptr()), m,
-                    ctypes.c_void_p(out.data_ptr()),
-                    ctypes.c_void_p(lev.data_ptr()) if levels else None, DEVICE))
-                self._torch_leave(pair)
-            return (out, lev) if levels else out
-        a = numpy.ascontiguousarray(k, dtype=numpy.float64).reshape(-1, 4)
-        out = numpy.empty(a.shape[0])
-        lev = numpy.empty(a.shape[0]) if levels else None
-        if a.shape[0]:
-            self._check(self._L.chomp_tri1h_quad(
-                self._h, epoch, int(moment), ctypes.c_void_p(a.ctypes.data), a.shape[0],
-                ctypes.c_void_p(out.ctypes.data),
-                ctypes.c_void_p(lev.ctypes.data) if levels else None, HOST))
-        return (out, lev) if levels else out
+        def body(mem, new, a):
+            m, rest = divmod(_numel(a), 4)
+            if rest:
+                raise ValueError("tri1h_quad: k must be [N, 4]")
+            return epoch, int(moment), a, m, new(m), new(m) if levels else None, mem
+        outs = self._run(self._L.chomp_tri1h_quad, [k], body)
+        return tuple(outs) if levels else outs[0]
 
     def halofit_setup(self, dst, src, f1, f2, f3, omega_l, w):
         self._check(self._L.chomp_halofit_setup(self._h, dst, src, f1, f2, f3,
@@ -759,25 +746,8 @@ class Context(object):
         """k: numpy array (host path) or torch cuda tensor (device path, async on
         the context's stream).  Returns [n, nk] in the same kind of container."""
         n = self.n_epoch - epoch0 if n is None else n
-        if _is_torch(k):
-            import torch
-            assert k.is_cuda and k.dtype == torch.float64 and k.is_contiguous()
-            if out is None:
-                out = torch.empty((n, k.numel()), dtype=torch.float64, device=k.device)
-            pair = self._torch_enter()
-            self._check(self._L.chomp_power_range(
-                self._h, which, epoch0, n, ctypes.c_void_p(k.data_ptr()), k.numel(),
-                ctypes.c_void_p(out.data_ptr()), DEVICE))
-            self._torch_leave(pair)
-            return out
-        k = numpy.ascontiguousarray(k, dtype=numpy.float64).ravel()
-        if out is None:
-            out = numpy.empty((n, k.size), dtype=numpy.float64)
-        if k.size:
-            self._check(self._L.chomp_power_range(
-                self._h, which, epoch0, n, ctypes.c_void_p(k.ctypes.data), k.size,
-                ctypes.c_void_p(out.ctypes.data), HOST))
-        return out
+        return self._run(self._L.chomp_power_range, [k], lambda mem, new, k: (
+            which, epoch0, n, k, _numel(k), new((n, _numel(k)), out), mem))[0]
 
     def power_plan(self, k, epoch0=0):
         """Register a torch cuda k grid for repeated power() calls (chomp_power_plan): the
@@ -791,22 +761,14 @@ class Context(object):
         self._plan_k = k
 
     def sigma_r(self, epoch, scale):
-        s = numpy.ascontiguousarray(numpy.atleast_1d(scale), dtype=numpy.float64)
-        out = numpy.empty_like(s)
-        self._check(self._L.chomp_sigma_r(self._h, epoch, s.ctypes.data_as(c_double_p),
-                                          s.size, out.ctypes.data_as(c_double_p)))
-        return out
+        return self._run(self._L.chomp_sigma_r, [numpy.atleast_1d(scale)],
+                         lambda mem, new, s: (epoch, s, s.size, new(s.shape)))[0]
 
     def y_nfw(self, epoch, ln_k, mass):
         a, b = numpy.broadcast_arrays(numpy.asarray(ln_k, dtype=numpy.float64),
                                       numpy.asarray(mass, dtype=numpy.float64))
-        a = numpy.ascontiguousarray(a).ravel()
-        b = numpy.ascontiguousarray(b).ravel()
-        out = numpy.empty_like(a)
-        self._check(self._L.chomp_y_nfw(self._h, epoch, a.ctypes.data_as(c_double_p),
-                                        b.ctypes.data_as(c_double_p), a.size,
-                                        out.ctypes.data_as(c_double_p)))
-        return out
+        return self._run(self._L.chomp_y_nfw, [a, b],
+                         lambda mem, new, a, b: (epoch, a, b, a.size, new(a.size)))[0]
 
     def scalars(self, epoch=0):
         out = numpy.empty(SC_COUNT)
@@ -833,26 +795,13 @@ class Context(object):
     def set_delta_b(self, delta_b, epoch0=0):
         """HaloSuperSampleCovariance._delta_b of epochs [epoch0, epoch0 + len) (chomp_set_delta_b);
         numpy array / sequence (host) or torch cuda tensor (device, async on the stream)."""
-        if _is_torch(delta_b):
-            import torch
-            assert delta_b.is_cuda and delta_b.dtype == torch.float64 and delta_b.is_contiguous()
-            pair = self._torch_enter()
-            self._check(self._L.chomp_set_delta_b(self._h, epoch0, delta_b.numel(),
-                                                  ctypes.c_void_p(delta_b.data_ptr()), DEVICE))
-            self._torch_leave(pair)
-            return
-        v = numpy.ascontiguousarray(numpy.atleast_1d(delta_b), dtype=numpy.float64).ravel()
-        self._check(self._L.chomp_set_delta_b(self._h, epoch0, v.size,
-                                              ctypes.c_void_p(v.ctypes.data), HOST))
+        self._run(self._L.chomp_set_delta_b, [delta_b],
+                  lambda mem, new, v: (epoch0, _numel(v), v, mem))
 
     def eval(self, what, x, epoch=0):
         """Element-wise lookup; x numpy (any shape) or torch cuda tensor."""
-        if _is_torch(x):
-            return self._map1(self._L.chomp_eval, x, epoch, EV[what])
-        xa = numpy.asarray(x, dtype=numpy.float64)
-        out = self._map1(self._L.chomp_eval, numpy.ascontiguousarray(xa).ravel(),
-                         epoch, EV[what])
-        return out.reshape(xa.shape)
+        return self._run(self._L.chomp_eval, [x],
+                         _elementwise(epoch, EV[what], shape=numpy.shape(x)))[0]
 
     def halofit_get(self, epoch=0):
         out = numpy.empty(HF_COUNT)
@@ -958,12 +907,7 @@ class Context(object):
         return out
 
     def me_eval(self, what, x):
-        if _is_torch(x):
-            return self._map1(self._L.chomp_me_eval, x, ME[what])
-        xa = numpy.asarray(x, dtype=numpy.float64)
-        out = self._map1(self._L.chomp_me_eval, numpy.ascontiguousarray(xa).ravel(),
-                         ME[what])
-        return out.reshape(xa.shape)
+        return self._run(self._L.chomp_me_eval, [x], _elementwise(ME[what], shape=numpy.shape(x)))[0]
 
     def kernel_info(self):
         out = numpy.empty(KI_COUNT)
@@ -981,62 +925,59 @@ class Context(object):
                                                out.ctypes.data_as(c_double_p), n))
         return out
 
-    def _map1(self, fn, x, *pre):
-        """Apply an (in, n, out, mem) entry point to numpy or torch input."""
-        if _is_torch(x):
+    def _run(self, fn, xs, body):
+        """Call the array entry point fn on host or device arrays; returns the list of outputs.
+
+        The first of the inputs xs decides.  A torch tensor (every input then a contiguous float64
+        cuda tensor) is used in place: DEVICE, asynchronous on the context's stream and ordered
+        against the caller's.  Anything else goes through numpy.ascontiguousarray(float64): HOST.
+        body(mem, new, *xs) returns fn's arguments after the context handle, its arrays as they
+        are (they are passed as pointers); new(shape) allocates an output of the same kind
+        (new(shape, given): the caller's own array instead), and the outputs are returned in the
+        order of those calls.  The library is not called when an input is empty."""
+        outs = []
+        if _is_torch(xs[0]):
             import torch
-            assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()
-            out = torch.empty_like(x)
-            pair = self._torch_enter()
-            self._check(fn(self._h, *pre, ctypes.c_void_p(x.data_ptr()), x.numel(),
-                           ctypes.c_void_p(out.data_ptr()), DEVICE))
+            for x in xs:
+                assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()
+            mem, empty, array, address = DEVICE, xs[0].new_empty, torch.Tensor, torch.Tensor.data_ptr
+            called = all(x.numel() for x in xs)
+        else:
+            xs = [numpy.ascontiguousarray(x, dtype=numpy.float64) for x in xs]
+            mem, empty, array, address = HOST, numpy.empty, numpy.ndarray, _host_address
+            called = all(x.size for x in xs)
+
+        def new(shape, given=None):
+            outs.append(empty(shape) if given is None else given)
+            return outs[-1]
+        args = body(mem, new, *xs)
+        if called:
+            pair = self._torch_enter() if mem == DEVICE else None
+            self._check(fn(self._h, *[address(a) if isinstance(a, array) else a for a in args]))
             self._torch_leave(pair)
-            return out
-        x = numpy.ascontiguousarray(x, dtype=numpy.float64)
-        out = numpy.empty_like(x)
-        if x.size:
-            self._check(fn(self._h, *pre, ctypes.c_void_p(x.ctypes.data), x.size,
-                           ctypes.c_void_p(out.ctypes.data), HOST))
-        return out
+        return outs
 
     def kernel_eval(self, ln_ktheta):
-        return self._map1(self._L.chomp_kernel_eval, ln_ktheta)
+        return self._run(self._L.chomp_kernel_eval, [ln_ktheta], _elementwise())[0]
 
     def kernel_raw(self, ln_ktheta):
-        return self._map1(self._L.chomp_kernel_raw, ln_ktheta)
+        return self._run(self._L.chomp_kernel_raw, [ln_ktheta], _elementwise())[0]
 
     def window_eval(self, which, chi):
-        return self._map1(self._L.chomp_window_eval, chi, int(which))
+        return self._run(self._L.chomp_window_eval, [chi], _elementwise(int(which)))[0]
 
     def wtheta(self, which, epoch, k_min, k_max, D_z, theta):
-        return self._map1(self._L.chomp_wtheta, theta, int(which), epoch,
-                          float(k_min), float(k_max), float(D_z))
+        return self._run(self._L.chomp_wtheta, [theta], _elementwise(
+            int(which), epoch, float(k_min), float(k_max), float(D_z)))[0]
 
     def wtheta_cell(self, which, epoch, k_min, k_max, D_z, theta, ell):
         """(w(theta), C_l) of one set-up in one call (chomp_wtheta_cell): with torch cuda
         tensors C_l is computed beside w(theta) on the context's side stream; same numbers as
-        wtheta() and cell()."""
-        if _is_torch(theta):
-            import torch
-            assert _is_torch(ell)
-            for x in (theta, ell):
-                assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()
-            w, c = torch.empty_like(theta), torch.empty_like(ell)
-            pair = self._torch_enter()
-            self._check(self._L.chomp_wtheta_cell(
-                self._h, int(which), epoch, float(k_min), float(k_max), float(D_z),
-                ctypes.c_void_p(theta.data_ptr()), theta.numel(), ctypes.c_void_p(w.data_ptr()),
-                ctypes.c_void_p(ell.data_ptr()), ell.numel(), ctypes.c_void_p(c.data_ptr()), DEVICE))
-            self._torch_leave(pair)
-            return w, c
-        th = numpy.ascontiguousarray(theta, dtype=numpy.float64).ravel()
-        el = numpy.ascontiguousarray(ell, dtype=numpy.float64).ravel()
-        w, c = numpy.empty_like(th), numpy.empty_like(el)
-        if th.size and el.size:
-            self._check(self._L.chomp_wtheta_cell(
-                self._h, int(which), epoch, float(k_min), float(k_max), float(D_z),
-                ctypes.c_void_p(th.ctypes.data), th.size, ctypes.c_void_p(w.ctypes.data),
-                ctypes.c_void_p(el.ctypes.data), el.size, ctypes.c_void_p(c.ctypes.data), HOST))
+        wtheta() and cell().  Torch outputs keep the inputs' shapes, numpy outputs are flat."""
+        w, c = self._run(self._L.chomp_wtheta_cell, [theta, ell], lambda mem, new, th, el: (
+            int(which), epoch, float(k_min), float(k_max), float(D_z), th, _numel(th),
+            new(th.shape if mem == DEVICE else _numel(th)), el, _numel(el),
+            new(el.shape if mem == DEVICE else _numel(el)), mem))
         return w, c
 
     def set_timing(self, on=True):
@@ -1059,17 +1000,10 @@ class Context(object):
         return ln_K, proj, lev.astype(int)
 
     def covariance_gaussian(self, j0_limit, area, poisson_a, poisson_b, theta_a, theta_b):
-        ta = numpy.ascontiguousarray(theta_a, dtype=numpy.float64).ravel()
-        tb = numpy.ascontiguousarray(theta_b, dtype=numpy.float64).ravel()
-        assert ta.size == tb.size
-        th = numpy.concatenate([ta, tb])
-        out = numpy.empty(ta.size)
-        if ta.size:
-            self._check(self._L.chomp_covariance_gaussian(
-                self._h, float(j0_limit), float(area), float(poisson_a), float(poisson_b),
-                ctypes.c_void_p(th.ctypes.data), ta.size, ctypes.c_void_p(out.ctypes.data),
-                HOST))
-        return out
+        return self._run(self._L.chomp_covariance_gaussian, [_pairs(theta_a, theta_b)],
+                         lambda mem, new, th: (float(j0_limit), float(area), float(poisson_a),
+                                               float(poisson_b), th, th.size // 2,
+                                               new(th.size // 2), mem))[0]
 
     def kernel_ssc_setup(self, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi, sigma2,
                          with_table=True):
@@ -1089,41 +1023,27 @@ class Context(object):
             int(bool(with_table)), ptr(info), ptr(tab), ptr(lev)))
         return info, tab, (lev.astype(int) if with_table else None)
 
-    def _ssc_points(self, fn, a, b):
-        a = numpy.ascontiguousarray(a, dtype=numpy.float64).ravel()
-        b = numpy.ascontiguousarray(b, dtype=numpy.float64).ravel()
-        assert a.size == b.size
-        out = numpy.empty(a.size)
-        if a.size:
-            x = numpy.concatenate([a, b])
-            self._check(fn(self._h, x.ctypes.data_as(c_double_p), a.size,
-                           out.ctypes.data_as(c_double_p)))
-        return out
-
     def kernel_ssc_raw(self, ln_ktheta_a, ln_ktheta_b):
-        return self._ssc_points(self._L.chomp_kernel_ssc_raw, ln_ktheta_a, ln_ktheta_b)
+        return self._run(self._L.chomp_kernel_ssc_raw, [_pairs(ln_ktheta_a, ln_ktheta_b)],
+                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
 
     def kernel_ssc_eval(self, ln_ktheta_a, ln_ktheta_b):
-        return self._ssc_points(self._L.chomp_kernel_ssc_eval, ln_ktheta_a, ln_ktheta_b)
+        return self._run(self._L.chomp_kernel_ssc_eval, [_pairs(ln_ktheta_a, ln_ktheta_b)],
+                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
 
     def covariance_ssc(self, epoch, area, theta_a, theta_b, knots=False):
         """covariance_ssc for each pair; with knots=True also (k_b knots, Romberg levels),
         each [n, kernel_npoints]."""
-        ta = numpy.ascontiguousarray(theta_a, dtype=numpy.float64).ravel()
-        tb = numpy.ascontiguousarray(theta_b, dtype=numpy.float64).ravel()
-        assert ta.size == tb.size
-        n, nk = ta.size, self.config.kernel_npoints
-        out = numpy.empty(n)
-        kn, lev = (numpy.empty((n, nk)), numpy.empty((n, nk))) if knots else (None, None)
-        if n:
-            th = numpy.concatenate([ta, tb])
-            ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
-            self._check(self._L.chomp_covariance_ssc(
-                self._h, epoch, float(area), th.ctypes.data_as(c_double_p), n,
-                out.ctypes.data_as(c_double_p), ptr(kn), ptr(lev)))
+        nk = self.config.kernel_npoints
+
+        def body(mem, new, th):
+            n = th.size // 2
+            return (epoch, float(area), th, n, new(n), new((n, nk)) if knots else None,
+                    new((n, nk)) if knots else None)
+        outs = self._run(self._L.chomp_covariance_ssc, [_pairs(theta_a, theta_b)], body)
         if knots:
-            return out, kn, lev.astype(int)
-        return out
+            return outs[0], outs[1], outs[2].astype(int)
+        return outs[0]
 
     def hod_stats(self, epoch0=0, n=None):
         """[n, 3]: effective bias, effective halo mass, satellite fraction."""
@@ -1133,21 +1053,16 @@ class Context(object):
         return out
 
     def xi3d(self, which, epoch, k_min, k_max, r):
-        return self._map1(self._L.chomp_xi3d, r, int(which), epoch, float(k_min), float(k_max))
+        return self._run(self._L.chomp_xi3d, [r], _elementwise(
+            int(which), epoch, float(k_min), float(k_max)))[0]
 
     def spline_eval(self, xk, yk, x, deriv=0):
         """Not-a-knot cubic spline through (xk, yk) at x (FITPACK k=3, s=0); deriv=1: its
         first derivative."""
         xk = numpy.ascontiguousarray(xk, dtype=numpy.float64)
         yk = numpy.ascontiguousarray(yk, dtype=numpy.float64)
-        xa = numpy.ascontiguousarray(numpy.atleast_1d(x), dtype=numpy.float64).ravel()
-        out = numpy.empty_like(xa)
-        if xa.size:
-            self._check(self._L.chomp_spline_eval(
-                self._h, xk.ctypes.data_as(c_double_p), yk.ctypes.data_as(c_double_p), xk.size,
-                xa.ctypes.data_as(c_double_p), xa.size, int(deriv),
-                out.ctypes.data_as(c_double_p)))
-        return out
+        return self._run(self._L.chomp_spline_eval, [numpy.atleast_1d(x)], lambda mem, new, x: (
+            xk, yk, xk.size, x, x.size, int(deriv), new(x.size)))[0]
 
     def set_precision(self, mode):
         """Arithmetic of the w(theta) integral: PREC_F64 (default, the only mode held to
@@ -1155,4 +1070,4 @@ class Context(object):
         self._check(self._L.chomp_set_precision(self._h, int(mode)))
 
     def cell(self, which, epoch, D_z, ell):
-        return self._map1(self._L.chomp_cell, ell, int(which), epoch, float(D_z))
+        return self._run(self._L.chomp_cell, [ell], _elementwise(int(which), epoch, float(D_z)))[0]

@@ -8,6 +8,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstddef>
@@ -149,7 +150,6 @@ struct chomp_ctx {
 
   // staging for host-pointer calls
   double* d_stage_in = nullptr;
-  double* d_stage_in2 = nullptr;
   double* d_kcache = nullptr;      // device copy of the last host k grid of chomp_power
   const double* kcache_ptr = nullptr;   // (== d_kcache while kcache_shadow describes its contents)
   size_t cap_kcache = 0;
@@ -208,15 +208,12 @@ struct chomp_ctx {
   double* d_tri = nullptr;
   size_t cap_tri = 0;
   std::vector<char> tri_built;
-  double* d_tri_in = nullptr;      // staging of the host-pointer trispectrum calls
-  double* d_tri_out = nullptr;
-  size_t cap_tri_in = 0, cap_tri_out = 0;
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
   bool timing_valid = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<int> slot;           // host copy: epoch -> cosmology slot
   size_t n_slots = 1;              // distinct cosmologies of the batch
-  size_t cap_in = 0, cap_in2 = 0, cap_out = 0;
+  size_t cap_in = 0, cap_out = 0;
 
   // projection
   ProjState proj;
@@ -420,6 +417,76 @@ int ensure_host(chomp_ctx* ctx, double** p, size_t* cap, size_t n) {
   return CHOMP_OK;
 }
 
+// The memory space of a call's arrays: CHOMP_HOST or CHOMP_DEVICE, nothing else
+// (include/chomp_mi355x.h, "Memory-space convention").
+int check_mem(chomp_ctx* ctx, int mem, const char* who) {
+  if (mem == CHOMP_HOST || mem == CHOMP_DEVICE) return CHOMP_OK;
+  return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": mem");
+}
+
+// The array arguments of one call.  Device arrays are used in place.  Host arrays get a segment
+// each, one after another on 16-byte boundaries: inputs in d_stage_in, sent by place(); outputs in
+// d_stage_out, copied back by finish(), which then waits for the stream once.  A host output
+// without an array (nullptr) keeps its segment but is not copied back.  place(n) also sets aside
+// a scratch segment of n doubles of d_stage_in, neither sent nor copied back.
+// rc: CHOMP_ERR_ARG when `mem` is neither CHOMP_HOST nor CHOMP_DEVICE; callers return it before any
+// other work, and place() refuses to stage anything with it set.
+struct Staging {
+  template <class T>
+  struct Seg { T* host; T** dev; size_t off, n; };
+  chomp_ctx* ctx;
+  bool host;
+  int rc;
+  double* scratch = nullptr;
+  std::vector<Seg<const double>> ins;
+  std::vector<Seg<double>> outs;
+  size_t n_in = 0, n_out = 0;
+
+  Staging(chomp_ctx* c, int mem, const char* who)
+      : ctx(c), host(mem == CHOMP_HOST), rc(check_mem(c, mem, who)) {}
+  static size_t take(size_t* used, size_t n) {
+    const size_t off = *used;
+    *used += (n + 1) & ~(size_t)1;
+    return off;
+  }
+  // *d: the array the kernels use (for a host array: set by place())
+  void in(const double* x, size_t n, const double** d) {
+    *d = x;
+    if (host) ins.push_back({x, d, take(&n_in, n), n});
+  }
+  void out(double* y, size_t n, double** d) {
+    *d = y;
+    if (host) outs.push_back({y, d, take(&n_out, n), n});
+  }
+  int place(size_t n_scratch = 0) {
+    if (rc) return rc;             // (an unknown mem never takes either path)
+    const size_t off_scratch = take(&n_in, n_scratch);
+    if (n_in) { const int e = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n_in); if (e) return e; }
+    if (n_out) { const int e = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n_out); if (e) return e; }
+    for (const Seg<const double>& s : ins) {
+      *s.dev = ctx->d_stage_in + s.off;
+      HIPCHK(hipMemcpyAsync(ctx->d_stage_in + s.off, s.host, s.n * sizeof(double),
+                            hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (const Seg<double>& s : outs) *s.dev = ctx->d_stage_out + s.off;
+    if (n_scratch) scratch = ctx->d_stage_in + off_scratch;
+    return CHOMP_OK;
+  }
+  int finish() {
+    HIPCHK(hipGetLastError());
+    if (!host) return CHOMP_OK;
+    for (const Seg<double>& s : outs)
+      if (s.host)
+        HIPCHK(hipMemcpyAsync(s.host, ctx->d_stage_out + s.off, s.n * sizeof(double),
+                              hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CHOMP_OK;
+  }
+};
+
+// The 1-D grid of the element-wise kernels: a block per 256 elements, at most 1024 blocks.
+dim3 grid_1d(size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)); }
+
 // erfinv(y) for y in (-1, 1): Newton on erf/erfc (used once per HOD, hod.py:172-175).
 double erfinv_host(double y) {
   if (y <= -1.0) return -INFINITY;
@@ -618,10 +685,10 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
   void* ptrs[] = {ctx->d_sici, ctx->d_j0, ctx->d_j2, ctx->d_tinker, ctx->d_gl16,
                   ctx->d_cand, ctx->d_cosmo, ctx->d_z, ctx->d_epochs, ctx->d_search, ctx->d_probe, ctx->d_count, ctx->d_pending,
                   ctx->d_tab, ctx->d_mass_par, ctx->d_profile, ctx->d_hod, ctx->d_nodes, ctx->d_snodes, ctx->d_slot, ctx->d_first, ctx->d_status, ctx->d_endp, ctx->d_npend,
-                  ctx->d_stage_in, ctx->d_stage_in2, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
+                  ctx->d_stage_in, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri_in, ctx->d_tri_out};
+                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -1616,12 +1683,13 @@ static int ensure_delta_b(chomp_ctx* ctx) {
 }
 
 int chomp_set_delta_b(chomp_ctx* ctx, size_t epoch0, size_t n, const double* delta_b, int mem) {
-  if (!ctx || !delta_b || n == 0 || (mem != CHOMP_HOST && mem != CHOMP_DEVICE))
-    return fail(ctx, CHOMP_ERR_ARG, "set_delta_b: bad args");
+  if (!ctx || !delta_b || n == 0) return fail(ctx, CHOMP_ERR_ARG, "set_delta_b: bad args");
+  int rc = check_mem(ctx, mem, "set_delta_b");
+  if (rc) return rc;
   if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "set_delta_b before epochs_set");
   if (epoch0 + n > ctx->n_epoch) return fail(ctx, CHOMP_ERR_ARG, "set_delta_b: epoch range");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = ensure_delta_b(ctx);
+  rc = ensure_delta_b(ctx);
   if (rc) return rc;
   if (mem == CHOMP_DEVICE) {
     HIPCHK(hipMemcpyAsync(ctx->d_delta_b + epoch0, delta_b, n * sizeof(double),
@@ -1674,6 +1742,8 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
   int rc = check_power(ctx, which, epoch0, n, true);
   if (rc) return rc;
   if (!k || !out || nk == 0) return fail(ctx, CHOMP_ERR_ARG, "power: null buffer");
+  rc = check_mem(ctx, mem, "power");
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   const bool ssc = (which & 15) == CHOMP_P_SSC_RESPONSE || (which & 15) == CHOMP_P_MM_SSC;
   if (ssc) {
@@ -1800,21 +1870,18 @@ int chomp_sigma_r(chomp_ctx* ctx, size_t epoch, const double* scale, size_t n, d
   if (!ctx || !scale || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "sigma_r: bad args");
   if (!ctx->have_epochs || epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "sigma_r: epoch");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n);
+  Staging st(ctx, CHOMP_HOST, "sigma_r");
+  const double* d_scale;
+  double* d_out;
+  st.in(scale, n, &d_scale);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
   if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, scale, n * sizeof(double), hipMemcpyHostToDevice,
-                        ctx->stream));
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_sigma_r<BAO>, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg,
-                       ctx->d_epochs, (int)epoch, ctx->d_stage_in, ctx->d_snodes, ctx->d_stage_out);
+                       ctx->d_epochs, (int)epoch, d_scale, ctx->d_snodes, d_out);
   });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost,
-                        ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return CHOMP_OK;
+  return st.finish();
 }
 
 int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k, const double* mass, size_t n,
@@ -1822,26 +1889,24 @@ int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k, const double* 
   if (!ctx || !ln_k || !mass || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "y_nfw: bad args");
   if (!ctx->have_halo || epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "y_nfw before halo_setup");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n);
+  Staging st(ctx, CHOMP_HOST, "y_nfw");
+  const double *d_ln_k, *d_mass;
+  double* d_out;
+  st.in(ln_k, n, &d_ln_k);
+  st.in(mass, n, &d_mass);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
   if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_stage_in2, &ctx->cap_in2, n);
-  if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, ln_k, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->d_stage_in2, mass, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_y_nfw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                     ctx->d_epochs, (int)epoch, ctx->d_sici, ctx->d_stage_in, ctx->d_stage_in2,
-                     (int)n, ctx->d_stage_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return CHOMP_OK;
+                     ctx->d_epochs, (int)epoch, ctx->d_sici, d_ln_k, d_mass, (int)n, d_out);
+  return st.finish();
 }
 
 int chomp_eval(chomp_ctx* ctx, size_t epoch, int what, const double* x, size_t n, double* out,
                int mem) {
   if (!ctx || !x || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "eval: bad args");
+  Staging st(ctx, mem, "eval");
+  if (st.rc) return st.rc;
   if (what < 0 || what > CHOMP_EV_SIGMA_OF_NU) return fail(ctx, CHOMP_ERR_ARG, "eval: unknown function");
   if (!ctx->have_epochs || epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "eval: epoch");
   const bool second = what == CHOMP_EV_BIAS_2_NU || what == CHOMP_EV_SIGMA_OF_NU;
@@ -1853,34 +1918,22 @@ int chomp_eval(chomp_ctx* ctx, size_t epoch, int what, const double* x, size_t n
     return fail(ctx, CHOMP_ERR_STATE, "eval: the last mass set-up was not second-order "
                                       "(chomp_set_second_order)");
   HIPCHK(hipSetDevice(ctx->device));
-  const double* dx = x;
-  double* dout = out;
-  if (mem == CHOMP_HOST) {
-    int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_stage_in, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    dx = ctx->d_stage_in;
-    dout = ctx->d_stage_out;
-  }
+  const double* dx;
+  double* dout;
+  st.in(x, n, &dx);
+  st.out(out, n, &dout);
+  const int rc = st.place();
+  if (rc) return rc;
   const TabLayout& L = ctx->L;
-  unsigned gx = (unsigned)((n + 255) / 256);
-  if (gx > 1024) gx = 1024;
   const size_t sh = (size_t)(L.NM + 8 * (L.NM - 1)) * sizeof(double);
   if (second)
-    hipLaunchKernelGGL(k_eval_b2, dim3(gx), dim3(256), (size_t)(L.NM + 4 * (L.NM - 1)) * sizeof(double),
+    hipLaunchKernelGGL(k_eval_b2, grid_1d(n), dim3(256), (size_t)(L.NM + 4 * (L.NM - 1)) * sizeof(double),
                        ctx->stream, L, ctx->B2, ctx->d_epochs, (int)epoch, ctx->d_tab, ctx->d_b2,
                        what, dx, (int)n, dout);
   else
-    hipLaunchKernelGGL(k_eval, dim3(gx), dim3(256), sh, ctx->stream, L, ctx->d_epochs, (int)epoch,
+    hipLaunchKernelGGL(k_eval, grid_1d(n), dim3(256), sh, ctx->stream, L, ctx->d_epochs, (int)epoch,
                        ctx->d_tab, what, dx, (int)n, dout);
-  HIPCHK(hipGetLastError());
-  if (mem == CHOMP_HOST) {
-    HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return CHOMP_OK;
+  return st.finish();
 }
 
 int chomp_set_second_order(chomp_ctx* ctx, int on) {
@@ -1908,24 +1961,19 @@ int chomp_pt_eval(chomp_ctx* ctx, int form, size_t epoch0, size_t n_epoch, const
   StageRange range_(ctx, "chomp:pt_eval");
   if (!ctx || !args || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "pt_eval: bad args");
   if (form < 0 || form >= kPtForms) return fail(ctx, CHOMP_ERR_ARG, "pt_eval: unknown form");
-  if (mem != CHOMP_HOST && mem != CHOMP_DEVICE) return fail(ctx, CHOMP_ERR_ARG, "pt_eval: mem");
+  Staging st(ctx, mem, "pt_eval");
+  if (st.rc) return st.rc;
   if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "pt_eval before epochs_set");
   if (epoch0 + n_epoch > ctx->n_epoch || n_epoch > 65535)
     return fail(ctx, CHOMP_ERR_ARG, "pt_eval: epoch range");
   HIPCHK(hipSetDevice(ctx->device));
   const size_t na = (size_t)pt_arity(form);
-  const double* dargs = args;
-  double* dout = out;
-  if (mem == CHOMP_HOST) {
-    int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n * na);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n * n_epoch);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_stage_in, args, n * na * sizeof(double), hipMemcpyHostToDevice,
-                          ctx->stream));
-    dargs = ctx->d_stage_in;
-    dout = ctx->d_stage_out;
-  }
+  const double* dargs;
+  double* dout;
+  st.in(args, n * na, &dargs);
+  st.out(out, n * n_epoch, &dout);
+  const int rc = st.place();
+  if (rc) return rc;
   // (a grid-stride loop: about 4096 blocks over the whole launch -- 16 per CU -- with the epochs
   //  as the y axis, so that a block stages its epoch once and then streams configurations)
   size_t gx = (n + kPtThreads - 1) / kPtThreads;
@@ -1952,12 +2000,7 @@ int chomp_pt_eval(chomp_ctx* ctx, int form, size_t epoch0, size_t n_epoch, const
       default: go(int_c<PT_TRISPECTRUM_PARALLELOGRAM>{}); break;
     }
   });
-  HIPCHK(hipGetLastError());
-  if (mem == CHOMP_HOST) {
-    HIPCHK(hipMemcpyAsync(out, dout, n * n_epoch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return CHOMP_OK;
+  return st.finish();
 }
 
 // -- HaloTrispectrumOneHalo (halo_trispectrum.py:13-151) ------------------------------------------
@@ -2017,34 +2060,21 @@ int chomp_tri1h_eval(chomp_ctx* ctx, size_t epoch, const double* ln_k1, const do
   StageRange range_(ctx, "chomp:tri1h_eval");
   if (!ctx || !ln_k1 || !ln_k2 || !out || n == 0 || n > (size_t)INT32_MAX)
     return fail(ctx, CHOMP_ERR_ARG, "tri1h_eval: bad args");
-  if (mem != CHOMP_HOST && mem != CHOMP_DEVICE) return fail(ctx, CHOMP_ERR_ARG, "tri1h_eval: mem");
+  Staging st(ctx, mem, "tri1h_eval");
+  if (st.rc) return st.rc;
   if (epoch >= ctx->n_epoch || epoch >= ctx->tri_built.size() || !ctx->tri_built[epoch])
     return fail(ctx, CHOMP_ERR_STATE, "tri1h_eval: no trispectrum table of this epoch (chomp_tri1h_setup)");
   HIPCHK(hipSetDevice(ctx->device));
-  const double *da = ln_k1, *db = ln_k2;
-  double* dout = out;
-  if (mem == CHOMP_HOST) {
-    int rc = ensure(ctx, &ctx->d_tri_in, &ctx->cap_tri_in, 2 * n);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_tri_out, &ctx->cap_tri_out, n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_tri_in, ln_k1, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_tri_in + n, ln_k2, n * sizeof(double), hipMemcpyHostToDevice,
-                          ctx->stream));
-    da = ctx->d_tri_in;
-    db = ctx->d_tri_in + n;
-    dout = ctx->d_tri_out;
-  }
-  size_t gx = (n + 255) / 256;
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_tri1h_eval, dim3((unsigned)gx), dim3(256), 0, ctx->stream, ctx->T3,
-                     ctx->d_tri, (int)epoch, da, db, (int)n, dout);
-  HIPCHK(hipGetLastError());
-  if (mem == CHOMP_HOST) {
-    HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return CHOMP_OK;
+  const double *da, *db;
+  double* dout;
+  st.in(ln_k1, n, &da);
+  st.in(ln_k2, n, &db);
+  st.out(out, n, &dout);
+  const int rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tri1h_eval, grid_1d(n), dim3(256), 0, ctx->stream, ctx->T3, ctx->d_tri,
+                     (int)epoch, da, db, (int)n, dout);
+  return st.finish();
 }
 
 // Replaces i_0_4 / trispectrum (halo_trispectrum.py:57-95): one scipy Romberg per call.
@@ -2053,37 +2083,26 @@ int chomp_tri1h_quad(chomp_ctx* ctx, size_t epoch, int moment, const double* k, 
   StageRange range_(ctx, "chomp:tri1h_quad");
   if (!ctx || !k || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: bad args");
   if (!tri_moment_ok(moment)) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: unknown moment");
-  if (mem != CHOMP_HOST && mem != CHOMP_DEVICE) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: mem");
+  Staging st(ctx, mem, "tri1h_quad");
+  if (st.rc) return st.rc;
   if (!ctx->have_halo || epoch >= ctx->n_epoch)
     return fail(ctx, CHOMP_ERR_STATE, "tri1h_quad before a halo set-up of this epoch");
   const size_t nb = (n + kTriQuadWaves - 1) / kTriQuadWaves;
   if (nb > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: too many quadruples");
   HIPCHK(hipSetDevice(ctx->device));
-  const double* dk = k;
-  double* dout = out;
-  double* dlev = levels;
-  if (mem == CHOMP_HOST) {
-    int rc = ensure(ctx, &ctx->d_tri_in, &ctx->cap_tri_in, 4 * n);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_tri_out, &ctx->cap_tri_out, 2 * n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_tri_in, k, 4 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    dk = ctx->d_tri_in;
-    dout = ctx->d_tri_out;
-    dlev = levels ? ctx->d_tri_out + n : nullptr;
-  }
+  const double* dk;
+  double* dout;
+  double* dlev = nullptr;
+  st.in(k, 4 * n, &dk);
+  st.out(out, n, &dout);
+  if (levels) st.out(levels, n, &dlev);
+  const int rc = st.place();
+  if (rc) return rc;
   const int lds = tri_quad_lds_doubles(ctx->L.NM) * (int)sizeof(double);
   hipLaunchKernelGGL(k_tri1h_quad, dim3((unsigned)nb), dim3(64 * kTriQuadWaves), (size_t)lds,
                      ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab,
                      ctx->d_sici, moment, dk, (long)n, dout, dlev, ctx->d_status);
-  HIPCHK(hipGetLastError());
-  if (mem == CHOMP_HOST) {
-    HIPCHK(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (levels)
-      HIPCHK(hipMemcpyAsync(levels, dlev, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return CHOMP_OK;
+  return st.finish();
 }
 
 int chomp_halofit_get(chomp_ctx* ctx, size_t epoch, double* out) {

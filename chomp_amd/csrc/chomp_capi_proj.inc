@@ -1,33 +1,5 @@
 // HaloFit + projection entry points (included inside extern "C" of chomp_capi.hip).
 
-// Shared host/device-buffer plumbing of the element-wise and per-sample integrals.
-struct Staged {
-  const double* in;
-  double* out;
-};
-static int stage_in(chomp_ctx* ctx, const double* x, size_t n, double* out, int mem, Staged* s) {
-  s->in = x;
-  s->out = out;
-  if (mem == CHOMP_HOST) {
-    int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_stage_in, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    s->in = ctx->d_stage_in;
-    s->out = ctx->d_stage_out;
-  }
-  return CHOMP_OK;
-}
-static int stage_out(chomp_ctx* ctx, double* out, size_t n, int mem, const Staged& s) {
-  HIPCHK(hipGetLastError());
-  if (mem == CHOMP_HOST) {
-    HIPCHK(hipMemcpyAsync(out, s.out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return CHOMP_OK;
-}
-
 // The two launches of a HaloFit set-up (halo.py:1261-1317) on the context's current stream.
 static int halofit_launch(chomp_ctx* ctx, size_t dst, size_t src, double f_1, double f_2,
                           double f_3, double omega_l, double w) {
@@ -321,17 +293,20 @@ int chomp_multi_epoch_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double z_m
 
 int chomp_me_eval(chomp_ctx* ctx, int what, const double* x, size_t n, double* out, int mem) {
   if (!ctx || !x || !out || n == 0 || what < 0 || what > 2) return fail(ctx, CHOMP_ERR_ARG, "me_eval: bad args");
+  Staging st(ctx, mem, "me_eval");
+  if (st.rc) return st.rc;
   if (!ctx->proj.me_ready) return fail(ctx, CHOMP_ERR_STATE, "me_eval before multi_epoch_setup / kernel_setup");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  Staged s;
-  int rc = stage_in(ctx, x, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(x, n, &din);
+  st.out(out, n, &dout);
+  const int rc = st.place();
   if (rc) return rc;
-  unsigned gx = (unsigned)((n + 255) / 256);
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_me_eval, dim3(gx), dim3(256), 0, ctx->stream, ctx->proj.L,
-                     ctx->proj.d_pd, ctx->proj.d_tab, what, s.in, (int)n, s.out);
-  return stage_out(ctx, out, n, mem, s);
+  hipLaunchKernelGGL(k_me_eval, grid_1d(n), dim3(256), 0, ctx->stream, ctx->proj.L,
+                     ctx->proj.d_pd, ctx->proj.d_tab, what, din, (int)n, dout);
+  return st.finish();
 }
 
 int chomp_kernel_info(chomp_ctx* ctx, double* out) {
@@ -384,53 +359,66 @@ int chomp_kernel_table(chomp_ctx* ctx, int table, double* out, size_t n) {
 
 int chomp_kernel_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out, int mem) {
   if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_raw: bad args");
+  Staging st(ctx, mem, "kernel_raw");
+  if (st.rc) return st.rc;
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "kernel_raw before kernel_setup");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  Staged s;
-  int rc = stage_in(ctx, ln_ktheta, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(ln_ktheta, n, &din);
+  st.out(out, n, &dout);
+  const int rc = st.place();
   if (rc) return rc;
   const ProjLayout& L = ctx->proj.L;
   hipLaunchKernelGGL(k_proj_kernel_knots, dim3((unsigned)n), dim3(256),
                      (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, ctx->cfg, L,
                      ctx->proj.d_pd, ctx->proj.d_tab,
-                     ctx->proj.host.order == 0 ? ctx->d_j0 : ctx->d_j2, s.in, s.out);
-  return stage_out(ctx, out, n, mem, s);
+                     ctx->proj.host.order == 0 ? ctx->d_j0 : ctx->d_j2, din, dout);
+  return st.finish();
 }
 
 int chomp_kernel_eval(chomp_ctx* ctx, const double* x, size_t n, double* out, int mem) {
   if (!ctx || !x || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_eval: bad args");
+  Staging st(ctx, mem, "kernel_eval");
+  if (st.rc) return st.rc;
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "kernel_eval before kernel_setup");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  Staged s;
-  int rc = stage_in(ctx, x, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(x, n, &din);
+  st.out(out, n, &dout);
+  const int rc = st.place();
   if (rc) return rc;
-  unsigned gx = (unsigned)((n + 255) / 256);
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_kernel_eval, dim3(gx), dim3(256), 0, ctx->stream, ctx->proj.L,
-                     ctx->proj.d_pd, ctx->proj.d_tab, s.in, (int)n, s.out);
-  return stage_out(ctx, out, n, mem, s);
+  hipLaunchKernelGGL(k_kernel_eval, grid_1d(n), dim3(256), 0, ctx->stream, ctx->proj.L,
+                     ctx->proj.d_pd, ctx->proj.d_tab, din, (int)n, dout);
+  return st.finish();
 }
 
 int chomp_window_eval(chomp_ctx* ctx, int which, const double* x, size_t n, double* out, int mem) {
   if (!ctx || !x || !out || n == 0 || which < 0 || which > 1) return fail(ctx, CHOMP_ERR_ARG, "window_eval: bad args");
+  Staging st(ctx, mem, "window_eval");
+  if (st.rc) return st.rc;
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "window_eval before kernel_setup");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  Staged s;
-  int rc = stage_in(ctx, x, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(x, n, &din);
+  st.out(out, n, &dout);
+  const int rc = st.place();
   if (rc) return rc;
-  unsigned gx = (unsigned)((n + 255) / 256);
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_window_eval, dim3(gx), dim3(256), 0, ctx->stream, ctx->proj.L,
-                     ctx->proj.d_pd, ctx->proj.d_tab, which, s.in, (int)n, s.out);
-  return stage_out(ctx, out, n, mem, s);
+  hipLaunchKernelGGL(k_window_eval, grid_1d(n), dim3(256), 0, ctx->stream, ctx->proj.L,
+                     ctx->proj.d_pd, ctx->proj.d_tab, which, din, (int)n, dout);
+  return st.finish();
 }
 
 static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_max, double D_z,
                        const double* theta, size_t n, double* out, int mem) {
   if (!ctx || !theta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "wtheta: bad args");
+  Staging st(ctx, mem, "wtheta");
+  if (st.rc) return st.rc;
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "wtheta before kernel_setup");
   int rc = check_power(ctx, which, epoch, 1);
   if (rc) return rc;
@@ -440,8 +428,11 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
   HIPCHK(hipSetDevice(ctx->device));
   rc = prepare_extrapolation(ctx, which, epoch, 1);
   if (rc) return rc;
-  Staged s;
-  rc = stage_in(ctx, theta, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(theta, n, &din);
+  st.out(out, n, &dout);
+  rc = st.place();
   if (rc) return rc;
   const ProjLayout& L = ctx->proj.L;
   const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
@@ -451,14 +442,14 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
     auto mixed = [&](auto PREC) {
       hipLaunchKernelGGL(k_wtheta_mixed<PREC>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
                          ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd,
-                         ctx->proj.d_tab, k_min, k_max, D_z, s.in, s.out);
+                         ctx->proj.d_tab, k_min, k_max, D_z, din, dout);
     };
     switch (ctx->precision) {
       case CHOMP_PREC_F32_EVAL: mixed(int_c<CHOMP_PREC_F32_EVAL>{}); break;
       case CHOMP_PREC_F32_TABLES: mixed(int_c<CHOMP_PREC_F32_TABLES>{}); break;
       default: mixed(int_c<CHOMP_PREC_F32_ALL>{}); break;
     }
-    return stage_out(ctx, out, n, mem, s);
+    return st.finish();
   }
   // fp64: the theta-independent factor of the integrand on the Romberg nodes first, then the
   // moment route (k_wtheta_moments + k_wtheta_fast: every level within the node table, segments
@@ -485,36 +476,41 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
                          ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min), std::log(k_max), rec,
                          segtot);
       hipLaunchKernelGGL(k_wtheta_fast, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->cfg, L,
-                         ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, s.in, s.out, ctx->d_wnodes, rec,
+                         ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, din, dout, ctx->d_wnodes, rec,
                          segtot, LT, nseg);
     } else {
       hipLaunchKernelGGL((k_wtheta<HF, BAO>), dim3((unsigned)n), dim3(64 * kWthetaNW), sh, ctx->stream,
                          ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd,
-                         ctx->proj.d_tab, k_min, k_max, D_z, s.in, s.out, ctx->d_wnodes, LT);
+                         ctx->proj.d_tab, k_min, k_max, D_z, din, dout, ctx->d_wnodes, LT);
     }
   });
-  return stage_out(ctx, out, n, mem, s);
+  return st.finish();
 }
 
 int chomp_xi3d(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_max,
                const double* r, size_t n, double* out, int mem) {
   if (!ctx || !r || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "xi3d: bad args");
+  Staging st(ctx, mem, "xi3d");
+  if (st.rc) return st.rc;
   int rc = check_power(ctx, which, epoch, 1);
   if (rc) return rc;
   if (!(k_min > 0.0) || !(k_max > k_min)) return fail(ctx, CHOMP_ERR_ARG, "xi3d: k range");
   HIPCHK(hipSetDevice(ctx->device));
   rc = prepare_extrapolation(ctx, which, epoch, 1);
   if (rc) return rc;
-  Staged s;
-  rc = stage_in(ctx, r, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(r, n, &din);
+  st.out(out, n, &dout);
+  rc = st.place();
   if (rc) return rc;
   const size_t sh = (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double);
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_xi3d<BAO>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
                        ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->d_j0, k_min,
-                       k_max, s.in, s.out);
+                       k_max, din, dout);
   });
-  return stage_out(ctx, out, n, mem, s);
+  return st.finish();
 }
 
 int chomp_spline_eval(chomp_ctx* ctx, const double* xk, const double* yk, size_t nk,
@@ -525,24 +521,18 @@ int chomp_spline_eval(chomp_ctx* ctx, const double* xk, const double* yk, size_t
   for (size_t i = 1; i < nk; ++i)
     if (!(xk[i] > xk[i - 1])) return fail(ctx, CHOMP_ERR_ARG, "spline_eval: knots must increase");
   HIPCHK(hipSetDevice(ctx->device));
-  // staging layout: xk | yk | coefficients | work | x   -> out
-  const size_t n_in = 2 * nk + 4 * (nk - 1) + 2 * nk + n;
-  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n_in);
+  Staging st(ctx, CHOMP_HOST, "spline_eval");
+  const double *d_xk, *d_yk, *dx;
+  double* dout;
+  st.in(xk, nk, &d_xk);
+  st.in(yk, nk, &d_yk);
+  st.in(x, n, &dx);
+  st.out(out, n, &dout);
+  const int rc = st.place(4 * (nk - 1) + 2 * nk);   // scratch: the coefficients, then work
   if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-  if (rc) return rc;
-  double* d = ctx->d_stage_in;
-  double* dx = d + 2 * nk + 4 * (nk - 1) + 2 * nk;
-  HIPCHK(hipMemcpyAsync(d, xk, nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(d + nk, yk, nk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_spline_eval, dim3(1), dim3(256), 0, ctx->stream, d, d + nk, (int)nk,
-                     d + 2 * nk, d + 2 * nk + 4 * (nk - 1), dx, (int)n, deriv, ctx->d_stage_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost,
-                        ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return CHOMP_OK;
+  hipLaunchKernelGGL(k_spline_eval, dim3(1), dim3(256), 0, ctx->stream, d_xk, d_yk, (int)nk,
+                     st.scratch, st.scratch + 4 * (nk - 1), dx, (int)n, deriv, dout);
+  return st.finish();
 }
 
 int chomp_set_precision(chomp_ctx* ctx, int mode) {
@@ -556,6 +546,8 @@ int chomp_set_precision(chomp_ctx* ctx, int mode) {
 static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const double* ell, size_t n,
                      double* out, int mem) {
   if (!ctx || !ell || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "cell: bad args");
+  Staging st(ctx, mem, "cell");
+  if (st.rc) return st.rc;
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "cell before kernel_setup");
   int rc = check_power(ctx, which, epoch, 1);
   if (rc) return rc;
@@ -568,8 +560,11 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   HIPCHK(hipSetDevice(ctx->device));
   rc = prepare_extrapolation(ctx, which, epoch, 1);
   if (rc) return rc;
-  Staged s;
-  rc = stage_in(ctx, ell, n, out, mem, &s);
+  const double* din;
+  double* dout;
+  st.in(ell, n, &din);
+  st.out(out, n, &dout);
+  rc = st.place();
   if (rc) return rc;
   // the chi-only factors of the integrand on the Romberg nodes first
   const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
@@ -598,13 +593,13 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
     if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
       hipLaunchKernelGGL((k_cell4<HF, BAO>), dim3((unsigned)((n + 3) / 4)), dim3(256), sh,
                          ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,
-                         ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, (int)n,
-                         s.out, ctx->d_cnodes, LT, pk_tab, split, deep, state);
+                         ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n,
+                         dout, ctx->d_cnodes, LT, pk_tab, split, deep, state);
     } else {   // (no level beyond the node table in k_cell: the lean instance)
       with_flag(split > LT, [&](auto BEYOND) {
         hipLaunchKernelGGL((k_cell<HF, BAO, BEYOND>), dim3((unsigned)n), dim3(256), sh, ctx->stream,
                            ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which,
-                           ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out, ctx->d_cnodes, LT,
+                           ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, dout, ctx->d_cnodes, LT,
                            pk_tab, split, deep, state);
       });
     }
@@ -613,12 +608,12 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
     if (rcl) return rcl;
     hipLaunchKernelGGL((k_cell_deep<HF, BAO>), dim3(gdeep), dim3(kCellDeepThreads), shd,
                        ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,
-                       ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, s.in, s.out,
+                       ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, dout,
                        ctx->d_cnodes, LT, pk_tab, split, deep, state);
     return CHOMP_OK;
   });
   if (rc) return rc;
-  return stage_out(ctx, out, n, mem, s);
+  return st.finish();
 }
 
 int chomp_wtheta(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_max, double D_z,
@@ -650,6 +645,7 @@ int chomp_wtheta_cell(chomp_ctx* ctx, int which, size_t epoch, double k_min, dou
                       const double* ell, size_t n_ell, double* c_out, int mem) {
   StageRange range_(ctx, "chomp:wtheta_cell");
   if (!ctx) return CHOMP_ERR_ARG;
+  { const int rcm = check_mem(ctx, mem, "wtheta_cell"); if (rcm) return rcm; }
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   int rc = CHOMP_OK;
@@ -712,53 +708,34 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area, doub
                               int mem) {
   if (!ctx || !theta || !out || n == 0)
     return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian: bad args");
+  Staging st(ctx, mem, "covariance_gaussian");
+  if (st.rc) return st.rc;
   if (!ctx->proj.cov_ready)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_gaussian before covariance_table");
   if (!(j0_limit > 0.0) || !(area > 0.0))
     return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian: j0_limit and area must be positive");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  const double* d_theta = theta;
-  double* d_out = out;
-  if (mem == CHOMP_HOST) {
+  if (st.host)
     for (size_t i = 0; i < 2 * n; ++i)
       if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian: theta must be positive");
-    int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_stage_in, theta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
-                          ctx->stream));
-    d_theta = ctx->d_stage_in;
-    d_out = ctx->d_stage_out;
-  }
+  const double* d_theta;
+  double* d_out;
+  st.in(theta, 2 * n, &d_theta);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
   const CovLayout C = make_cov_layout(ctx->proj.L.NKT);
   const size_t sh = (size_t)(C.N + 4 * (C.N - 1)) * sizeof(double);
   hipLaunchKernelGGL(k_cov_gaussian, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, C,
                      ctx->proj.d_cov, ctx->d_j0, j0_limit, area, poisson_a, poisson_b, d_theta,
                      d_theta + n, d_out, (double*)nullptr);
-  HIPCHK(hipGetLastError());
-  if (mem == CHOMP_HOST) {
-    HIPCHK(hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return CHOMP_OK;
+  return st.finish();
 }
 
 // ---------------------------------------------------------------------------
 // Super-sample covariance of w(theta) (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
-static int ssc_stage_pairs(chomp_ctx* ctx, const double* theta, size_t n, const char* who) {
-  for (size_t i = 0; i < 2 * n; ++i)
-    if (!(theta[i] > 0.0))
-      return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": arguments must be positive");
-  const int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, theta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
-                        ctx->stream));
-  return CHOMP_OK;
-}
-
 int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
                            double j0_ssc_limit, const double* ln_chi, const double* sigma2,
                            size_t n_sigma, int with_table, double* info, double* table,
@@ -821,20 +798,17 @@ int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, doub
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   ProjState& P = ctx->proj;
   const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
-  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
+  Staging st(ctx, CHOMP_HOST, "kernel_ssc_raw");
+  const double* d_in;
+  double* d_out;
+  st.in(ln_ktheta, 2 * n, &d_in);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
   if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, ln_ktheta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
-                        ctx->stream));
   const size_t sh = (size_t)(ProjLds::doubles(P.L) + 5 * S.NS - 4) * sizeof(double);
   hipLaunchKernelGGL(k_ssc_table, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, P.L, S,
-                     P.d_pd, P.d_tab, ctx->d_j0, P.d_ssc, ctx->d_stage_in, ctx->d_stage_in + n,
-                     ctx->d_stage_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return CHOMP_OK;
+                     P.d_pd, P.d_tab, ctx->d_j0, P.d_ssc, d_in, d_in + n, d_out);
+  return st.finish();
 }
 
 int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
@@ -845,20 +819,16 @@ int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, dou
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   ProjState& P = ctx->proj;
   const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
-  int rc = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, 2 * n);
+  Staging st(ctx, CHOMP_HOST, "kernel_ssc_eval");
+  const double* d_in;
+  double* d_out;
+  st.in(ln_ktheta, 2 * n, &d_in);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
   if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->d_stage_in, ln_ktheta, 2 * n * sizeof(double), hipMemcpyHostToDevice,
-                        ctx->stream));
-  unsigned gx = (unsigned)((n + 255) / 256);
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_ssc_eval, dim3(gx), dim3(256), 0, ctx->stream, S, P.d_ssc, ctx->d_stage_in,
-                     ctx->d_stage_in + n, (int)n, ctx->d_stage_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, ctx->d_stage_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return CHOMP_OK;
+  hipLaunchKernelGGL(k_ssc_eval, grid_1d(n), dim3(256), 0, ctx->stream, S, P.d_ssc, d_in, d_in + n,
+                     (int)n, d_out);
+  return st.finish();
 }
 
 int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double* theta,
@@ -875,29 +845,25 @@ int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double
   ProjState& P = ctx->proj;
   const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
   const int NK = ctx->cfg.kernel_npoints;
-  rc = ssc_stage_pairs(ctx, theta, n, "covariance_ssc");
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: arguments must be positive");
+  Staging st(ctx, CHOMP_HOST, "covariance_ssc");
+  const double* d_theta;
+  double *d_out, *d_knots, *d_lev;   // (k_ssc_outer reads the knots: staged even when not copied back)
+  st.in(theta, 2 * n, &d_theta);
+  st.out(out, n, &d_out);
+  st.out(kb_knots, n * NK, &d_knots);
+  st.out(kb_levels, n * NK, &d_lev);
+  rc = st.place();
   if (rc) return rc;
-  // out | knots | levels
-  rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n * (1 + 2 * (size_t)NK));
-  if (rc) return rc;
-  double* d_out = ctx->d_stage_out;
-  double* d_knots = d_out + n;
-  double* d_lev = d_knots + n * (size_t)NK;
   const size_t sh = (size_t)ssc_kb_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_ssc_kb<BAO>, dim3((unsigned)NK, (unsigned)n), dim3(256), sh, ctx->stream,
                        ctx->cfg, ctx->L, S, ctx->d_epochs, (int)epoch, ctx->d_tab, P.d_ssc,
-                       ctx->d_stage_in, ctx->d_stage_in + n, d_knots, d_lev);
+                       d_theta, d_theta + n, d_knots, d_lev);
   });
   hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
                      (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
                      ctx->stream, ctx->cfg, area, d_knots, d_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (kb_knots)
-    HIPCHK(hipMemcpyAsync(kb_knots, d_knots, n * NK * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (kb_levels)
-    HIPCHK(hipMemcpyAsync(kb_levels, d_lev, n * NK * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return CHOMP_OK;
+  return st.finish();
 }

@@ -14,6 +14,7 @@
  * `mem` argument: CHOMP_HOST (pointer is host memory; the library stages it) or
  * CHOMP_DEVICE (pointer is HBM on the context's device, e.g. torch
  * tensor.data_ptr(); no copy, the call is asynchronous on the context's stream).
+ * Any other `mem` is refused with CHOMP_ERR_ARG before anything is copied or launched.
  *
  * Threading: one HIP stream per context; calls on one context must be serialised
  * by the caller; distinct contexts are independent.

@@ -1072,3 +1072,124 @@ def test_deep_knots_with_other_point_counts():
     finally:
         defaults.default_precision.clear()
         defaults.default_precision.update(saved)
+
+
+def _staging_ctx():
+    """A small context with every set-up the array entry points read: two epochs with the
+    second-order mass function, the halo model's and I_1^2's knot tables and the one-halo
+    trispectrum table, and a projection with its covariance table."""
+    from chomp_amd import _lib, cosmology, defaults, hod, kernel
+    c, hd = defaults.default_cosmo_dict, defaults.default_halo_dict
+    ctx = cosmology._context()
+    ctx.epochs_set(c, [0.0, 0.5])
+    ctx.set_second_order(True)
+    ctx.stage_k(hd, _lib.MF_ST, hd, hod.HODZheng(), _lib.FAM_SSC)
+    ctx.tri1h_setup(_lib.TRI_MOMENT["power_mmmm"])
+    w = kernel.WindowFunctionGalaxy(kernel.dNdzMagLim(0.0, 2.0, 2.0, 0.3, 2.0),
+                                    cosmology.MultiEpoch(0.0, 2.0, c))
+    ctx.kernel_setup(c, 0.0, 2.0, 1e-6, 1.0, w._struct(), w._struct(), 0)
+    ctx.covariance_table(_lib.P_MM, 0, 1.0)
+    return ctx
+
+
+def test_host_and_device_arrays_give_the_same_bits(torch_mod):
+    """Every array entry point with both paths returns the same bits for numpy arrays (staged by
+    the library) as for torch cuda tensors (used in place), and empty input of either kind comes
+    back empty."""
+    torch = torch_mod
+    from chomp_amd import _lib
+    ctx = _staging_ctx()
+
+    def dev(a):
+        return torch.from_numpy(numpy.ascontiguousarray(a, dtype=numpy.float64)).cuda()
+
+    def same(fn, *arrays):
+        host, device = fn(*arrays), fn(*[dev(a) for a in arrays])
+        host = host if isinstance(host, tuple) else (host,)
+        device = device if isinstance(device, tuple) else (device,)
+        assert len(host) == len(device)
+        for h, d in zip(host, device):
+            assert isinstance(h, numpy.ndarray) and torch.is_tensor(d) and d.is_cuda
+            d = d.cpu().numpy()
+            assert h.shape == d.shape and numpy.array_equal(h.view(numpy.int64), d.view(numpy.int64))
+
+    mass, nu = numpy.array([1e11, 3e12, 1e14, 1e15]), numpy.array([0.3, 1.0, 2.0, 4.0])
+    k = numpy.logspace(-3, 1.5, 37)
+    for what in _lib.EV:
+        x = k if what == "delta_k" else (nu if what.endswith("_nu") else mass)
+        same(lambda x: ctx.eval(what, x, 1), x)
+    for what in _lib.ME:
+        same(lambda x: ctx.me_eval(what, x), [100.0, 1000.0, 3000.0] if what == "z_of_chi" else [0.1, 0.7, 1.5])
+    ln_kt = numpy.linspace(numpy.log(1e-5), numpy.log(0.5), 9)
+    same(ctx.kernel_eval, ln_kt)
+    same(ctx.kernel_raw, ln_kt[:3])
+    for which in (0, 1):
+        same(lambda x: ctx.window_eval(which, x), [200.0, 900.0, 2000.0])
+    theta, ell = numpy.logspace(-5, -2, 5), numpy.logspace(1, 4, 6)
+    same(lambda t: ctx.wtheta(_lib.P_MM, 0, 1e-3, 1e2, 1.0, t), theta)
+    same(lambda l: ctx.cell(_lib.P_MM, 0, 1.0, l), ell)
+    same(lambda t, l: ctx.wtheta_cell(_lib.P_MM, 0, 1e-3, 1e2, 1.0, t, l), theta, ell)
+    same(lambda r: ctx.xi3d(_lib.P_MM, 0, 1e-3, 1e2, r), [1.0, 10.0, 50.0])
+    same(lambda a: ctx.pt_eval("bispectrum", a), numpy.random.default_rng(7).uniform(-0.3, 0.3, (16, 9)))
+    quads = numpy.array([[0.1, 0.1, 0.2, 0.2], [0.01, 0.5, 1.0, 0.3], [2.0, 2.0, 2.0, 2.0]])
+    same(lambda q: ctx.tri1h_quad(_lib.TRI_MOMENT["power_mmmm"], q, 1, levels=True), quads)
+    same(lambda a, b: ctx.tri1h_eval(a, b, 1), numpy.log([2e-3, 0.3, 7.0]), numpy.log([0.05, 1.0, 40.0]))
+    for which in (_lib.P_LIN, _lib.P_MM):
+        same(lambda k: ctx.power(which, k), k)
+    # delta_b from either side: the same P_mm_ssc
+    db = numpy.array([0.02, -0.01])
+    ctx.set_delta_b(db)
+    ssc = ctx.power(_lib.P_MM_SSC, k)
+    assert not numpy.array_equal(ssc, ctx.power(_lib.P_MM, k))
+    ctx.set_delta_b(numpy.zeros(2))
+    ctx.set_delta_b(dev(db))
+    assert numpy.array_equal(ctx.power(_lib.P_MM_SSC, k).view(numpy.int64), ssc.view(numpy.int64))
+    # empty input: empty outputs of the same kind, no library call
+    for x in (numpy.empty(0), dev(numpy.empty(0))):
+        for fn in (ctx.kernel_eval, lambda x: ctx.eval("f_nu", x, 0), lambda x: ctx.power(_lib.P_MM, x),
+                   lambda x: ctx.pt_eval("Fs2", x), lambda x: ctx.tri1h_quad(0, x, 0, levels=True),
+                   lambda x: ctx.tri1h_eval(x, x, 0),
+                   lambda x: ctx.wtheta_cell(_lib.P_MM, 0, 1e-3, 1e2, 1.0, x, x)):
+            outs = fn(x)
+            for o in outs if isinstance(outs, tuple) else (outs,):
+                assert type(o) is type(x) and 0 in tuple(o.shape)
+        ctx.set_delta_b(x)
+    torch.cuda.synchronize()
+
+
+def test_unknown_mem_is_refused(torch_mod):
+    """A `mem` other than CHOMP_HOST / CHOMP_DEVICE is refused with CHOMP_ERR_ARG before anything
+    runs, and the context stays usable.  (Device arrays only: a build without the check would
+    hand host addresses to a kernel.)"""
+    import ctypes
+    torch = torch_mod
+    from chomp_amd import _lib
+    ctx = _staging_ctx()
+    L, h = ctx._L, ctx._h
+    x = torch.tensor([0.5, 1.0, 2.0], dtype=torch.float64, device="cuda")
+    pairs = torch.tensor([1e-3, 2e-3, 1e-3, 3e-3], dtype=torch.float64, device="cuda")
+    out = torch.zeros(16, dtype=torch.float64, device="cuda")
+    p, o2, bad = (lambda t: ctypes.c_void_p(t.data_ptr())), out[8:], 2
+    calls = {
+        "eval": lambda: L.chomp_eval(h, 0, _lib.EV["f_nu"], p(x), 3, p(out), bad),
+        "me_eval": lambda: L.chomp_me_eval(h, 0, p(x), 3, p(out), bad),
+        "kernel_raw": lambda: L.chomp_kernel_raw(h, p(x), 3, p(out), bad),
+        "kernel_eval": lambda: L.chomp_kernel_eval(h, p(x), 3, p(out), bad),
+        "window_eval": lambda: L.chomp_window_eval(h, 0, p(x), 3, p(out), bad),
+        "wtheta": lambda: L.chomp_wtheta(h, _lib.P_MM, 0, 1e-3, 1e2, 1.0, p(x), 3, p(out), bad),
+        "cell": lambda: L.chomp_cell(h, _lib.P_MM, 0, 1.0, p(x), 3, p(out), bad),
+        "wtheta_cell": lambda: L.chomp_wtheta_cell(h, _lib.P_MM, 0, 1e-3, 1e2, 1.0, p(x), 3, p(out),
+                                                   p(x), 3, p(o2), bad),
+        "xi3d": lambda: L.chomp_xi3d(h, _lib.P_MM, 0, 1e-3, 1e2, p(x), 3, p(out), bad),
+        "covariance_gaussian": lambda: L.chomp_covariance_gaussian(h, 10.0, 1.0, 0.0, 0.0, p(pairs), 2,
+                                                                   p(out), bad),
+        "power_range": lambda: L.chomp_power_range(h, _lib.P_MM, 0, 2, p(x), 3, p(out), bad),
+        "power": lambda: L.chomp_power(h, _lib.P_MM, p(x), 3, p(out), bad),
+    }
+    for name, call in calls.items():
+        assert call() == _lib.ERR_ARG, name
+        assert "mem" in L.chomp_last_error(h).decode(), name
+    torch.cuda.synchronize()
+    assert torch.count_nonzero(out).item() == 0            # nothing ran
+    k = numpy.logspace(-2, 0, 5)
+    assert numpy.all(ctx.power(_lib.P_MM, k) > 0) and numpy.all(numpy.isfinite(ctx.kernel_eval(k)))
