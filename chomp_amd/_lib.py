@@ -137,6 +137,8 @@ EXPORTS = [
     "chomp_set_dark_energy", "chomp_get_de_table",
     "chomp_set_second_order", "chomp_get_second_order", "chomp_pt_eval",
     "chomp_tri1h_setup", "chomp_tri1h_eval", "chomp_tri1h_quad",
+    "chomp_kernel_ng_setup", "chomp_kernel_ng_raw", "chomp_kernel_ng_eval",
+    "chomp_covariance_ng",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
@@ -144,6 +146,7 @@ ST_MASS_MIN_SATURATED, ST_MASS_MAX_SATURATED, ST_MASS_SEARCH_EXHAUSTED, ST_SIGMA
 ST_DE_DIVMAX = 0x10
 ST_B2_DIVMAX = 0x20
 ST_TRI1H_DIVMAX = 0x40
+ST_COV_NG_DIVMAX = 0x80
 ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000,
                   "i_1_2": 0x2000}
 ST_NONFINITE = 0x10000
@@ -184,6 +187,10 @@ def describe_status(word):
     if word & ST_TRI1H_DIVMAX:
         out.append("an I_0^4 Romberg of the one-halo trispectrum exhausted divmax "
                    "(halo_trispectrum.py:89-95)")
+    if word & ST_COV_NG_DIVMAX:
+        out.append("a Romberg of the trispectrum term of the covariance (raw_kernel_NG, "
+                   "kernel.py:1067-1072, or a k_b integral, covariance.py:665-671) exhausted "
+                   "divmax")
     for name, bit in ST_HALO_DIVMAX.items():
         if word & bit:
             out.append("%s: Romberg exhausted divmax at some knots (last row kept)" % name)
@@ -415,6 +422,10 @@ def lib():
         L.chomp_kernel_ssc_raw.argtypes = [vp, vp, sz, vp]
         L.chomp_kernel_ssc_eval.argtypes = [vp, vp, sz, vp]
         L.chomp_covariance_ssc.argtypes = [vp, sz, d, vp, sz, vp, vp, vp]
+        L.chomp_kernel_ng_setup.argtypes = [vp, d, i, c_double_p, c_double_p, c_double_p]
+        L.chomp_kernel_ng_raw.argtypes = [vp, vp, sz, vp]
+        L.chomp_kernel_ng_eval.argtypes = [vp, vp, sz, vp]
+        L.chomp_covariance_ng.argtypes = [vp, d, vp, sz, d, d, vp, sz, vp, vp, vp]
         L.chomp_xi3d.argtypes = [vp, i, sz, d, d, vp, sz, vp, i]
         L.chomp_spline_eval.argtypes = [vp, vp, vp, sz, vp, sz, i, vp]
         for name in EXPORTS:
@@ -549,6 +560,7 @@ class Context(object):
         self.stream_ptr = sp.value or 0
         self.n_epoch = 0
         self._proj_ssc = None            # the KernelCovariance whose kernel_ssc table is here
+        self._proj_ng = None             # ... and whose kernel_NG table is
         self._plan_k = None
 
     # -- ordering against the caller's torch stream ------------------------------------
@@ -876,7 +888,8 @@ class Context(object):
                      wa, wb, bessel_order, dark_energy=False):
         c = cosmo_struct(cosmo_dict)
         self._check(self._L.chomp_set_dark_energy(self._h, 1 if dark_energy else 0))
-        self._proj_ssc = None            # (a projection set-up drops the kernel_ssc table)
+        # (a projection set-up drops the kernel_ssc and kernel_NG tables)
+        self._proj_ssc = self._proj_ng = None
         self._check(self._L.chomp_kernel_setup(
             self._h, ctypes.byref(c), me_z_min, me_z_max, ktheta_min, ktheta_max,
             ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)))
@@ -884,7 +897,7 @@ class Context(object):
     def multi_epoch_setup(self, cosmo_dict, z_min, z_max, dark_energy=False):
         c = cosmo_struct(cosmo_dict)
         self._check(self._L.chomp_set_dark_energy(self._h, 1 if dark_energy else 0))
-        self._proj_ssc = None
+        self._proj_ssc = self._proj_ng = None
         self._check(self._L.chomp_multi_epoch_setup(self._h, ctypes.byref(c),
                                                     float(z_min), float(z_max)))
 
@@ -1041,6 +1054,55 @@ class Context(object):
             return (epoch, float(area), th, n, new(n), new((n, nk)) if knots else None,
                     new((n, nk)) if knots else None)
         outs = self._run(self._L.chomp_covariance_ssc, [_pairs(theta_a, theta_b)], body)
+        if knots:
+            return outs[0], outs[1], outs[2].astype(int)
+        return outs[0]
+
+    def kernel_ng_setup(self, j0_limit, with_table=True):
+        """Trispectrum kernel of the context's windows, after kernel_ssc_setup.  Returns (table,
+        Romberg levels, min(table)), the first two [kernel_npoints, kernel_npoints]; (None, None,
+        None) without the table."""
+        if not with_table:
+            self._check(self._L.chomp_kernel_ng_setup(self._h, float(j0_limit), 0, None, None,
+                                                      None))
+            return None, None, None
+        n = self.config.kernel_npoints
+        tab, lev, mn = numpy.empty((n, n)), numpy.empty((n, n)), numpy.empty(1)
+        self._check(self._L.chomp_kernel_ng_setup(
+            self._h, float(j0_limit), 1, tab.ctypes.data_as(c_double_p),
+            lev.ctypes.data_as(c_double_p), mn.ctypes.data_as(c_double_p)))
+        return tab, lev.astype(int), numpy.float64(mn[0])
+
+    def warn_cov_ng_divmax(self, what, stacklevel=4):
+        """ChompAccuracyWarning if ST_COV_NG_DIVMAX is set (on the context's first epoch)."""
+        if self.n_epoch and self.status(0, 1)[0] & ST_COV_NG_DIVMAX:
+            import warnings
+            warnings.warn("%s: %s" % (what, "; ".join(describe_status(ST_COV_NG_DIVMAX))),
+                          ChompAccuracyWarning, stacklevel=stacklevel)
+
+    def kernel_ng_raw(self, ln_ktheta_a, ln_ktheta_b):
+        return self._run(self._L.chomp_kernel_ng_raw, [_pairs(ln_ktheta_a, ln_ktheta_b)],
+                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+
+    def kernel_ng_eval(self, ln_ktheta_a, ln_ktheta_b):
+        return self._run(self._L.chomp_kernel_ng_eval, [_pairs(ln_ktheta_a, ln_ktheta_b)],
+                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+
+    def covariance_ng(self, area, tri_table, tri_k_min, tri_k_max, theta_a, theta_b,
+                      knots=False):
+        """covariance_NG for each pair with the I_0^4 table tri_table [N, N] over
+        linspace(ln tri_k_min, ln tri_k_max, N); with knots=True also (k_b knots, Romberg
+        levels), each [n, kernel_npoints]."""
+        nk = self.config.kernel_npoints
+        tri = numpy.ascontiguousarray(tri_table, dtype=numpy.float64)
+        if tri.ndim != 2 or tri.shape[0] != tri.shape[1]:
+            raise ValueError("covariance_ng: the I_0^4 table must be square")
+
+        def body(mem, new, th):
+            n = th.size // 2
+            return (float(area), tri, tri.shape[0], float(tri_k_min), float(tri_k_max), th, n,
+                    new(n), new((n, nk)) if knots else None, new((n, nk)) if knots else None)
+        outs = self._run(self._L.chomp_covariance_ng, [_pairs(theta_a, theta_b)], body)
         if knots:
             return outs[0], outs[1], outs[2].astype(int)
         return outs[0]

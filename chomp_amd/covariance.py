@@ -1,6 +1,6 @@
-"""covariance.Covariance for the Gaussian and super-sample parts of the w(theta) covariance
-(covariance.py:23-543, 685-793, 1085-1103), the consumer of P(k) and the windows that
-SURVEY.md 8(f) ranks fourth.
+"""covariance.Covariance for the Gaussian, super-sample and one-halo trispectrum parts of the
+w(theta) covariance (covariance.py:23-793, 1085-1103), the consumer of P(k) and the windows
+that SURVEY.md 8(f) ranks fourth.
 
 Accelerated: ``Covariance(corr, corr, nongaussian_cov=False)`` -- the use of
 examples/example_covariance_script.py: the projected spectrum over ln K
@@ -8,9 +8,15 @@ examples/example_covariance_script.py: the projected spectrum over ln K
 the Poisson term, ``get_covariance`` and ``write`` -- and with ``ssc_cov=True`` the
 super-sample term on HaloSuperSampleCovariance copies of the halo:
 ``KernelCovariance.kernel_ssc`` (kernel.py:961-972, 1113-1231) and ``covariance_ssc`` for every
-pair of bins in one call.  Outside the scope (ChompScopeError): the trispectrum term
-(``nongaussian_cov=True``: halo_trispectrum.py, perturbation_spectra.py), ``CovarianceMulti``
-and ``CovarianceFourier``.  Two different correlation objects cannot be given to the
+pair of bins in one call.  With ``nongaussian_cov=True`` and a
+``halo_trispectrum.HaloTrispectrumOneHalo`` handed in as ``input_halo_trispectrum`` the
+one-halo trispectrum term: ``KernelCovariance.kernel_NG`` (kernel.py:996-1073, 1103-1111) and
+``covariance_NG`` (covariance.py:593-683) for every pair of bins in one call.  The object has
+to be given: the reference never moves its default HaloTrispectrumOneHalo() off z = 0 (the
+set_redshift(z_bar_NG) lines are commented out), so the redshift, the HOD and power_spec of the
+trispectrum are the caller's choice.  Outside the scope (ChompScopeError): ``nongaussian_cov=True``
+without such an object, the full ``HaloTrispectrum``, ``CovarianceMulti`` and
+``CovarianceFourier``.  Two different correlation objects cannot be given to the
 reference's Covariance either (its constructor raises ValueError comparing them), so that
 branch is not built.
 """
@@ -20,6 +26,7 @@ from scipy import special
 from . import _lib
 from . import defaults
 from . import halo as halo_mod
+from . import halo_trispectrum
 from . import kernel as kernel_mod
 from .correlation import _POWER
 
@@ -41,16 +48,17 @@ class AnnulusBin(object):
 
 class KernelCovariance(object):
     """kernel.KernelCovariance (kernel.py:864-1231): the four windows, the MultiEpoch, the
-    common redshift / distance range and the super-sample kernel ``kernel_ssc``.  The
-    trispectrum kernel (kernel / kernel_NG / raw_kernel / raw_kernel_NG) is outside the scope.
+    common redshift / distance range, the super-sample kernel ``kernel_ssc`` and, with
+    ``trispectrum_kernel=True``, the trispectrum kernel (kernel / kernel_NG / raw_kernel /
+    raw_kernel_NG); without it those four raise ChompScopeError.
 
-    kernel_ssc is built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over --
+    Both kernels are built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over --
     on the device context of ``_ssc_context`` (Covariance points it at its halo copy's, so
     the response and the table meet there) or else on a context of its own."""
 
     def __init__(self, ktheta_min, ktheta_max, window_function_a1, window_function_a2,
                  window_function_b1, window_function_b2, cosmo_multi_epoch,
-                 force_quad=False):
+                 force_quad=False, trispectrum_kernel=False):
         if force_quad:
             raise _lib.ChompScopeError("force_quad=True is outside the accelerated scope")
         self.ln_ktheta_min = numpy.log(ktheta_min)
@@ -73,16 +81,75 @@ class KernelCovariance(object):
         self._ssc_context = None     # callable -> device context of the table
         self._ssc_key = None
         self._ssc_table = False
+        self._trispectrum_kernel = bool(trispectrum_kernel)
+        self._ng_key = None
+        self._ng_table = False
 
     def get_cosmology(self):
         return self.cosmo.get_cosmology()
 
-    def kernel(self, ln_ktheta_a, ln_ktheta_b):
-        raise _lib.ChompScopeError(
-            "KernelCovariance.kernel / kernel_NG (kernel.py:978-1056) serve the trispectrum "
-            "term: outside the accelerated scope")
+    # -- the trispectrum kernel -------------------------------------------------------
+    def _ng(self, table=True):
+        """The device state of kernel_NG, on top of kernel_ssc's scalars (z_bar_NG is found
+        once, there): (re)built when those were, and with `table` the 1275 integrals, their
+        minimum and the bicubic of log(table - 10 min) (built only once something asks)."""
+        if not self._trispectrum_kernel:
+            raise _lib.ChompScopeError(
+                "KernelCovariance.kernel / kernel_NG / raw_kernel / raw_kernel_NG "
+                "(kernel.py:996-1073) serve the trispectrum term: pass trispectrum_kernel=True "
+                "(Covariance does, given nongaussian_cov=True and a HaloTrispectrumOneHalo)")
+        ctx = self._ssc(table=False)
+        fresh = self._ssc_key == self._ng_key and ctx._proj_ng is self
+        if not fresh or (table and not self._ng_table):
+            d = self.__dict__
+            d["_ng_array"], d["_ng_levels"], d["_ng_min"] = ctx.kernel_ng_setup(
+                self._j0_limit, with_table=table)
+            self._ng_key = self._ssc_key
+            self._ng_table = table
+            ctx._proj_ng = self
+            if table:
+                ctx.warn_cov_ng_divmax("raw_kernel_NG")
+        return ctx
 
-    kernel_NG = raw_kernel = raw_kernel_NG = kernel
+    def _ng_value(name):
+        def get(self):
+            self._ng()
+            return self.__dict__["_ng_" + name]
+        return property(get)
+
+    _kernel_array = _ng_value("array")
+    _kernel_levels = _ng_value("levels")
+    _kernel_NG_min = _ng_value("min")
+    del _ng_value
+
+    def raw_kernel_NG(self, ln_ktheta_a, ln_ktheta_b):
+        """kernel.py:1035-1073, quirk included: the norm takes ln(k theta_a) for k theta_a."""
+        ctx = self._ng(table=False)
+        a, b = numpy.broadcast_arrays(numpy.asarray(ln_ktheta_a, dtype=numpy.float64),
+                                      numpy.asarray(ln_ktheta_b, dtype=numpy.float64))
+        out = ctx.kernel_ng_raw(a.ravel(), b.ravel())
+        return float(out[0]) if a.ndim == 0 else out.reshape(a.shape)
+
+    def raw_kernel(self, ln_ktheta_a, ln_ktheta_b):
+        return self.raw_kernel_NG(ln_ktheta_a, ln_ktheta_b)
+
+    def kernel_NG(self, ln_ktheta_a, ln_ktheta_b):
+        """kernel.py:999-1014: exp(spline) + 10 min on RectBivariateSpline's grid,
+        [len a, len b] (callers index [0]); ln(k theta) < min is clamped to min, above max
+        gives 0."""
+        ctx = self._ng()
+        a = numpy.asarray(ln_ktheta_a, dtype=numpy.float64)
+        b = numpy.asarray(ln_ktheta_b, dtype=numpy.float64)
+        a = numpy.where(a < self.ln_ktheta_min, self.ln_ktheta_min, a)
+        b = numpy.where(b < self.ln_ktheta_min, self.ln_ktheta_min, b)
+        inside = numpy.logical_and(a <= self.ln_ktheta_max, b <= self.ln_ktheta_max)
+        ga, gb = numpy.meshgrid(numpy.atleast_1d(a).ravel(), numpy.atleast_1d(b).ravel(),
+                                indexing="ij")
+        grid = ctx.kernel_ng_eval(ga.ravel(), gb.ravel()).reshape(ga.shape)
+        return numpy.where(inside, grid, 0.0)
+
+    def kernel(self, ln_ktheta_a, ln_ktheta_b):
+        return self.kernel_NG(ln_ktheta_a, ln_ktheta_b)
 
     # -- the super-sample kernel ------------------------------------------------------
     def _ssc(self, table=True):
@@ -182,10 +249,22 @@ class Covariance(object):
                  n_a=1.0e4, n_b=1.0e4, variance=1.0, nongaussian_cov=True,
                  input_halo_trispectrum=None, power_spec='power_mm',
                  poisson_noise_only=False, ssc_cov=False, **kws):
-        if nongaussian_cov or input_halo_trispectrum is not None:
+        if nongaussian_cov and input_halo_trispectrum is None:
             raise _lib.ChompScopeError(
-                "the trispectrum term of the covariance (covariance_NG; halo_trispectrum.py) "
-                "is outside the accelerated scope: pass nongaussian_cov=False")
+                "the trispectrum term of the covariance (covariance_NG) is built for an explicit "
+                "one-halo trispectrum: pass input_halo_trispectrum=halo_trispectrum."
+                "HaloTrispectrumOneHalo(redshift, ...) -- the reference's default object stays "
+                "at z = 0 whatever z_bar_NG is -- or nongaussian_cov=False")
+        if not nongaussian_cov and input_halo_trispectrum is not None:
+            raise _lib.ChompScopeError(
+                "input_halo_trispectrum with nongaussian_cov=False: the trispectrum term "
+                "(covariance_NG) would not be used; pass nongaussian_cov=True to build it")
+        if nongaussian_cov and not isinstance(input_halo_trispectrum,
+                                              halo_trispectrum.HaloTrispectrumOneHalo):
+            raise _lib.ChompScopeError(
+                "the trispectrum term of the covariance is accelerated for a halo_trispectrum."
+                "HaloTrispectrumOneHalo, not %s (HaloTrispectrum, the two- to four-halo terms, "
+                "is outside the scope)" % type(input_halo_trispectrum).__name__)
         if input_correlation_a is not input_correlation_b:
             # The reference cannot get here either: covariance.py:60 compares the two
             # correlations with Correlation.__eq__ (correlation.py:119-131), which compares
@@ -223,7 +302,8 @@ class Covariance(object):
             self.n_b1, self.n_b2 = n_b[0], n_b[1]
         except (TypeError, IndexError):
             self.n_b1 = self.n_b2 = n_b
-        self.nongaussian_cov = False
+        self.nongaussian_cov = bool(nongaussian_cov)
+        self.halo_tri = input_halo_trispectrum
         self.ssc_cov = bool(ssc_cov)
         self.poisson_noise_only = poisson_noise_only
 
@@ -232,7 +312,8 @@ class Covariance(object):
             numpy.power(10.0, self.log_theta_min) * defaults.default_limits["k_min"],
             numpy.power(10.0, self.log_theta_max) * defaults.default_limits["k_max"],
             kern.window_function_a, kern.window_function_b,
-            kern.window_function_a, kern.window_function_b, kern.cosmo)
+            kern.window_function_a, kern.window_function_b, kern.cosmo,
+            trispectrum_kernel=self.nongaussian_cov)
         # covariance.py:108-115.  The reference's Kernel holds *copies* of its two
         # windows, each with a private copy of the MultiEpoch, and WindowFunction.__eq__
         # (kernel.py:248-259) compares those by identity: two windows are "equal" only
@@ -256,7 +337,8 @@ class Covariance(object):
         else:
             self.halo_a = input_correlation_a.halo
             self.halo_b = input_correlation_b.halo
-        # kernel_ssc lives in halo_a's context, beside the response it is integrated with
+        # kernel_ssc and kernel_NG live in halo_a's context (the first beside the response it is
+        # integrated with)
         self.kernel._proj_kernel = kern
         self.kernel._ssc_context = lambda: self.halo_a._context()
         self._initialized_halo_splines = False
@@ -339,6 +421,12 @@ class Covariance(object):
         self.corr_a.set_cosmology(cosmo_dict)
         self.halo_a = self.halo_b = self.corr_a.halo
         self._initialized_halo_splines = False
+        if self.nongaussian_cov:
+            # covariance.py:268: the trispectrum moves to z_bar_NG of the new cosmology -- the
+            # kernel state is rebuilt for it first (its key holds the cosmology).  With
+            # pert=None this raises AttributeError after the halo model has moved, as the
+            # reference does; covariance_NG reads the object's table anew at every call.
+            self.halo_tri.set_cosmology(cosmo_dict, self.kernel.z_bar_NG)
 
     def get_cosmology(self):
         return self.kernel.get_cosmology()
@@ -352,13 +440,15 @@ class Covariance(object):
 
     def get_covariance(self):
         """covariance.py:297-317; the Gaussian term of all bin pairs is one launch, the
-        super-sample term one call."""
+        trispectrum and super-sample terms one call each."""
         nb = len(self.annular_bins)
         self.covar = numpy.zeros((nb, nb))
         iu = numpy.triu_indices(nb)
         centers = numpy.array([b.center for b in self.annular_bins])
         if not self.poisson_noise_only and nb:
             vals = self._covariance_G_pairs(centers[iu[0]], centers[iu[1]])
+            if self.nongaussian_cov:
+                vals = vals + self._covariance_NG_pairs(centers[iu[0]], centers[iu[1]])
             if self.ssc_cov:
                 vals = vals + self._covariance_ssc_pairs(centers[iu[0]], centers[iu[1]])
             self.covar[iu] = vals
@@ -376,6 +466,8 @@ class Covariance(object):
             return cov_P
         res = self.covariance_G(annular_bin_a.center, annular_bin_b.center,
                                 annular_bin_a.delta, annular_bin_b.delta)
+        if self.nongaussian_cov:
+            res += self.covariance_NG(annular_bin_a.center, annular_bin_b.center)
         if self.ssc_cov:
             res += self.covariance_ssc(annular_bin_a.center, annular_bin_b.center)
         return res + cov_P
@@ -408,9 +500,29 @@ class Covariance(object):
                                                                  dtype=numpy.float64).ravel())
         return float(out[0]) if ta.ndim == 0 else out.reshape(ta.shape)
 
+    def _covariance_NG_pairs(self, theta_a, theta_b, knots=False):
+        if not self.nongaussian_cov:
+            raise _lib.ChompScopeError(
+                "covariance_NG needs the trispectrum term: Covariance(..., nongaussian_cov=True, "
+                "input_halo_trispectrum=HaloTrispectrumOneHalo(...))")
+        tri = self.halo_tri
+        if not tri._initialized_i_0_4:
+            tri._initialize_i_0_4()
+        ctx = self.kernel._ng()
+        out = ctx.covariance_ng(self.area, tri._i_0_4_array, tri._k_min, tri._k_max,
+                                theta_a, theta_b, knots)
+        ctx.warn_cov_ng_divmax("covariance_NG")
+        return out
+
     def covariance_NG(self, theta_a_rad, theta_b_rad):
-        raise _lib.ChompScopeError("covariance_NG (halo trispectrum) is outside the "
-                                   "accelerated scope")
+        """covariance.py:593-683: for each k_a knot a Romberg over ln k_b of
+        k_b^2 T(k_a, k_b) kernel_NG(ln k_a theta_a, ln k_b theta_b) / D(z_bar_NG)^4, T =
+        halo_tri's trispectrum_parallelogram at that object's own redshift; their spline, and
+        the Romberg over ln k_a / (4 pi^2 area)."""
+        ta, tb = numpy.broadcast_arrays(numpy.asarray(theta_a_rad, dtype=numpy.float64),
+                                        numpy.asarray(theta_b_rad, dtype=numpy.float64))
+        out = self._covariance_NG_pairs(ta.ravel(), tb.ravel())
+        return float(out[0]) if ta.ndim == 0 else out.reshape(ta.shape)
 
     def _covariance_ssc_pairs(self, theta_a, theta_b, knots=False):
         if not hasattr(self.halo_a, "dln_power_ddelta_b"):

@@ -147,6 +147,8 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
   P.cov_ready = false;
   P.ssc_ready = false;
   P.ssc_prep = false;
+  P.ng_ready = false;
+  P.ng_prep = false;
   P.L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
   // tabulated redshift distributions ride behind the projection tables
   size_t pp_doubles[2] = {0, 0};
@@ -263,6 +265,8 @@ int chomp_multi_epoch_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double z_m
   P.cov_ready = false;
   P.ssc_ready = false;
   P.ssc_prep = false;
+  P.ng_ready = false;
+  P.ng_prep = false;
   P.L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
   if (!P.d_pd) HIPCHK(hipMalloc(&P.d_pd, sizeof(ProjDev)));
   if (!P.d_pd_init) HIPCHK(hipMalloc(&P.d_pd_init, sizeof(ProjDev)));
@@ -862,6 +866,146 @@ int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double
                        ctx->cfg, ctx->L, S, ctx->d_epochs, (int)epoch, ctx->d_tab, P.d_ssc,
                        d_theta, d_theta + n, d_knots, d_lev);
   });
+  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
+                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
+                     ctx->stream, ctx->cfg, area, d_knots, d_out);
+  return st.finish();
+}
+
+// ---------------------------------------------------------------------------
+// One-halo trispectrum term of the covariance of w(theta) (chomp_cov_kernels.h)
+// ---------------------------------------------------------------------------
+// The status word CHOMP_ST_COV_NG_DIVMAX goes to: the context's first epoch, if it has one.
+static unsigned* ng_status(chomp_ctx* ctx) {
+  return ctx->n_epoch > 0 ? ctx->d_status : nullptr;
+}
+
+int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, double* table,
+                          double* levels, double* table_min) {
+  if (!ctx) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_setup: bad args");
+  if (!with_table && (table || levels || table_min))
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_setup: table / levels / min need with_table");
+  if (!ctx->proj.ready || !ctx->proj.ssc_prep)
+    return fail(ctx, CHOMP_ERR_STATE, "kernel_ng_setup before kernel_ssc_setup");
+  if (!(j0_limit > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_setup: J0 limit");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const ProjLayout& L = P.L;
+  const int N = L.NKT;
+  const SscLayout S = make_ssc_layout(N, P.ssc_ns);
+  const NgLayout G = make_ng_layout(N);
+  P.ng_ready = false;
+  P.ng_prep = false;
+  { const int rce = ensure(ctx, &P.d_ng, &P.cap_ng, (size_t)G.total); if (rce) return rce; }
+  hipLaunchKernelGGL(k_ng_prep, dim3(1), dim3(256), 0, ctx->stream, S, G, P.d_ssc, j0_limit,
+                     P.d_ng, ng_status(ctx));
+  if (with_table) {
+    const size_t sh = (size_t)ProjLds::doubles(L) * sizeof(double);
+    hipLaunchKernelGGL(k_ng_table, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh, ctx->stream,
+                       ctx->cfg, L, G, P.d_pd, P.d_tab, ctx->d_j0, P.d_ng, (const double*)nullptr,
+                       (const double*)nullptr, (double*)nullptr, ng_status(ctx));
+    hipLaunchKernelGGL(k_ng_bicubic, dim3(1), dim3(256), 0, ctx->stream, G, P.d_ng);
+  }
+  HIPCHK(hipGetLastError());
+  P.ng_prep = true;
+  P.ng_ready = with_table != 0;
+  if (table || levels || table_min) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t b = (size_t)N * N * sizeof(double);
+    if (table) HIPCHK(hipMemcpy(table, P.d_ng + G.tab, b, hipMemcpyDeviceToHost));
+    if (levels) HIPCHK(hipMemcpy(levels, P.d_ng + G.lev, b, hipMemcpyDeviceToHost));
+    if (table_min)
+      HIPCHK(hipMemcpy(table_min, P.d_ng + G.scal + kNgMin, sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return CHOMP_OK;
+}
+
+int chomp_kernel_ng_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
+  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_raw: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ng_prep)
+    return fail(ctx, CHOMP_ERR_STATE, "kernel_ng_raw before kernel_ng_setup");
+  if (n > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_raw: too many points");
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!std::isfinite(ln_ktheta[i])) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_raw: ln(k theta) must be finite");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const NgLayout G = make_ng_layout(P.L.NKT);
+  Staging st(ctx, CHOMP_HOST, "kernel_ng_raw");
+  const double* d_in;
+  double* d_out;
+  st.in(ln_ktheta, 2 * n, &d_in);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
+  const size_t sh = (size_t)ProjLds::doubles(P.L) * sizeof(double);
+  hipLaunchKernelGGL(k_ng_table, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, P.L, G,
+                     P.d_pd, P.d_tab, ctx->d_j0, P.d_ng, d_in, d_in + n, d_out, ng_status(ctx));
+  return st.finish();
+}
+
+int chomp_kernel_ng_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
+  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_eval: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ng_ready)
+    return fail(ctx, CHOMP_ERR_STATE, "kernel_ng_eval before kernel_ng_setup");
+  if (n > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_eval: too many points");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const NgLayout G = make_ng_layout(P.L.NKT);
+  Staging st(ctx, CHOMP_HOST, "kernel_ng_eval");
+  const double* d_in;
+  double* d_out;
+  st.in(ln_ktheta, 2 * n, &d_in);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ng_eval, grid_1d(n), dim3(256), 0, ctx->stream, G, P.d_ng, d_in, d_in + n,
+                     (int)n, d_out);
+  return st.finish();
+}
+
+int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, size_t n_tri,
+                        double tri_k_min, double tri_k_max, const double* theta, size_t n,
+                        double* out, double* kb_knots, double* kb_levels) {
+  if (!ctx || !tri_table || !theta || !out || n == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ng_ready)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ng before kernel_ng_setup");
+  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: area must be positive");
+  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: at most 65535 pairs a call");
+  if (n_tri < 4 || n_tri > 64)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: the I_0^4 table must be 4..64 knots a side");
+  if (!(tri_k_min > 0.0) || !(tri_k_max > tri_k_min))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: the I_0^4 table's k range");
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: arguments must be positive");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const NgLayout G = make_ng_layout(P.L.NKT);
+  const NgTriLayout T = make_ng_tri_layout((int)n_tri);
+  const int NK = ctx->cfg.kernel_npoints;
+  { const int rce = ensure(ctx, &P.d_ng_tri, &P.cap_ng_tri, (size_t)T.total); if (rce) return rce; }
+  Staging st(ctx, CHOMP_HOST, "covariance_ng");
+  const double *d_theta, *d_tri_in;
+  double *d_out, *d_knots, *d_lev;   // (k_ssc_outer reads the knots: staged even when not copied back)
+  st.in(theta, 2 * n, &d_theta);
+  st.in(tri_table, n_tri * n_tri, &d_tri_in);
+  st.out(out, n, &d_out);
+  st.out(kb_knots, n * NK, &d_knots);
+  st.out(kb_levels, n * NK, &d_lev);
+  const int rc = st.place();
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(P.d_ng_tri + T.tab, d_tri_in, n_tri * n_tri * sizeof(double),
+                        hipMemcpyDeviceToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_ng_tri, dim3(1), dim3(256), 0, ctx->stream, T, tri_k_min, tri_k_max,
+                     P.d_ng_tri);
+  const size_t sh = (size_t)ng_kb_lds_doubles(G.N, T.N) * sizeof(double);
+  hipLaunchKernelGGL(k_ng_kb, dim3((unsigned)NK, (unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+                     G, T, P.d_ng, P.d_ng_tri, tri_k_min, tri_k_max, d_theta, d_theta + n, d_knots,
+                     d_lev, ng_status(ctx));
   hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
                      (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
                      ctx->stream, ctx->cfg, area, d_knots, d_out);

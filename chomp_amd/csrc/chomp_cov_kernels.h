@@ -1,6 +1,8 @@
-// chomp_cov_kernels.h -- the super-sample covariance of w(theta) (gfx950):
-// Covariance(corr, corr, nongaussian_cov=False, ssc_cov=True), covariance.py:144-151, 685-776,
-// on KernelCovariance.kernel_ssc, kernel.py:961-972, 1113-1231.
+// chomp_cov_kernels.h -- the super-sample and one-halo trispectrum terms of the covariance of
+// w(theta) (gfx950): Covariance(corr, corr, ssc_cov=True), covariance.py:144-151, 685-776, on
+// KernelCovariance.kernel_ssc, kernel.py:961-972, 1113-1231; and Covariance(corr, corr,
+// nongaussian_cov=True, input_halo_trispectrum=HaloTrispectrumOneHalo), covariance.py:593-683, on
+// KernelCovariance.kernel_NG, kernel.py:996-1073, 1103-1111.
 //
 //   k_ssc_prep      sigma^2 spline over ln chi, z_bar_NG and its chi / growth
 //   k_ssc_table     raw_kernel_ssc: the 50 x 50 knot table (upper triangle, mirrored, levels)
@@ -8,7 +10,16 @@
 //   k_ssc_bicubic   RectBivariateSpline(s=0) of the table as a piecewise bicubic
 //   k_ssc_eval      kernel_ssc with the reference's clamp and zero rules
 //   k_ssc_kb        covariance_ssc, inner integrals: one k_b Romberg per (pair, k_a knot)
-//   k_ssc_outer     covariance_ssc, the k_a spline and the outer Romberg per pair
+//   k_ssc_outer     covariance_ssc / covariance_NG, the k_a spline and the outer Romberg per pair
+//
+//   k_ng_prep       the kernel_NG state from the kernel_ssc one (z_bar_NG, its chi and growth, the
+//                   ln k theta knots)
+//   k_ng_table      raw_kernel_NG: the knot table (upper triangle, mirrored, levels) or the
+//                   caller's points
+//   k_ng_bicubic    min(table) and the bicubic of log(table - 10 min)
+//   k_ng_eval       kernel_NG with the reference's clamp and zero rules
+//   k_ng_tri        the bicubic of an uploaded I_0^4 table (HaloTrispectrumOneHalo's)
+//   k_ng_kb         covariance_NG, inner integrals: one k_b Romberg per (pair, k_a knot)
 //
 // Everything runs in one context: the halo copy's.  The windows and the MultiEpoch are set up
 // there (Kernel._setup_on, as Correlation._prepare does for its own halo), so the table, its
@@ -64,12 +75,13 @@ struct Sigma2View {
 };
 
 // kernel.py:1048-1056 (_kernel_NG_integrand) with a1 = b1 = window a, a2 = b2 = window b, in
-// the reference's order of operations.
+// the reference's order of operations (norm = 1 multiplies exactly).
 __device__ __forceinline__ double ssc_ng_integrand(const ProjLds& P, const BesselTab* B,
-                                                   double chi, double kta, double ktb) {
+                                                   double chi, double kta, double ktb,
+                                                   double norm = 1.0) {
   const double D = P.me.growth_factor(P.me.redshift(chi));
   const double wa = P.wa(chi), wb = P.wb(chi);
-  return wa * wb * wa * wb * D * D * D * D / (chi * chi) * bessel_j<0>(kta * chi, *B) *
+  return norm * wa * wb * wa * wb * D * D * D * D / (chi * chi) * bessel_j<0>(kta * chi, *B) *
          bessel_j<0>(ktb * chi, *B);
 }
 
@@ -239,6 +251,15 @@ __global__ __launch_bounds__(256) void k_ssc_bicubic(SscLayout S, double* __rest
   bicubic_build(S.N, st + S.kx, st + S.tab, st + S.rowt, st + S.work, st + S.bic);
 }
 
+// One cell of a bicubic of bicubic_build: sum_{p,q} c[4 p + q] da^p db^q, db innermost.
+__device__ __forceinline__ double bicubic_cell(const double* c, double da, double db) {
+  double r[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    r[p] = fma(fma(fma(c[4 * p + 3], db, c[4 * p + 2]), db, c[4 * p + 1]), db, c[4 * p]);
+  return fma(fma(fma(r[3], da, r[2]), da, r[1]), da, r[0]);
+}
+
 // A bicubic of bicubic_build: knots x[0..N-1] (uniform in intent, lo = x_0, hi = x_{N-1}), the
 // interval search and the tensor-product polynomial, with no range rule of its own.
 struct Bicubic {
@@ -256,12 +277,7 @@ struct Bicubic {
   __device__ __forceinline__ double poly(double a, double b) const {
     const int ia = interval(a), jb = interval(b);
     const double da = a - x[ia], db = b - x[jb];
-    const double* c = bic + ((size_t)ia * (N - 1) + jb) * 16;
-    double r[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-      r[p] = fma(fma(fma(c[4 * p + 3], db, c[4 * p + 2]), db, c[4 * p + 1]), db, c[4 * p]);
-    return fma(fma(fma(r[3], da, r[2]), da, r[1]), da, r[0]);
+    return bicubic_cell(bic + ((size_t)ia * (N - 1) + jb) * 16, da, db);
   }
 };
 
@@ -319,16 +335,23 @@ struct SscRow {
       lc[q] = fma(fma(fma(cc[12], da, cc[8]), da, cc[4]), da, cc[0]);
     }
   }
-  __device__ __forceinline__ double operator()(double b) const {
-    if (zero) return 0.0;
+  // the clamp and zero rules on b: false where the value is 0
+  __device__ __forceinline__ bool inside(double& b) const {
+    if (zero) return false;
     if (b <= lo) b = lo;
-    if (!(b <= hi)) return 0.0;
+    return b <= hi;
+  }
+  // the row's cubic at b in [lo, hi]
+  __device__ __forceinline__ double at(double b) const {
     const double inv_dx = (double)(N - 1) / (hi - lo);
     int j = (int)floor((b - lo) * inv_dx);
     j = j < 0 ? 0 : (j > N - 2 ? N - 2 : j);
     if (j > 0 && b < x[j]) --j;
     if (j < N - 2 && b >= x[j + 1]) ++j;
     return pp_poly(c, j, b - x[j]);
+  }
+  __device__ __forceinline__ double operator()(double b) const {
+    return inside(b) ? at(b) : 0.0;
   }
 };
 
@@ -383,7 +406,8 @@ __global__ __launch_bounds__(256) void k_ssc_kb(chomp_config cfg, TabLayout HL, 
   }
 }
 
-// covariance.py:694-721: the not-a-knot spline of the k_a knots, norm = 1 / spline(0), the
+// covariance.py:605-622, 694-721 (covariance_NG and covariance_ssc alike): the not-a-knot spline
+// of the k_a knots, norm = 1 / spline(0), the
 // Romberg over ln k_a of k_a^2 spline norm, / (4 pi^2 norm area).
 struct SscKaIntegrand {
   const double *x, *pp;
@@ -428,6 +452,314 @@ __global__ __launch_bounds__(256) void k_ssc_outer(chomp_config cfg, double area
                     cfg.divmax, red) / (4.0 * kPi * kPi * norm * area);
   }
   if (threadIdx.x == 0) out[pair] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The one-halo trispectrum term: KernelCovariance.kernel_NG and Covariance.covariance_NG
+// ---------------------------------------------------------------------------------------------
+constexpr unsigned kStCovNgDivmax = CHOMP_ST_COV_NG_DIVMAX;
+
+// Device block of the kernel_NG state: scalars | ln k theta knots | table | levels |
+// log(table - 10 min) | its bicubic | scratch of the bicubic build.  It holds its own copy of
+// what it takes from the kernel_ssc block, so a later kernel_ssc set-up leaves it valid.
+struct NgLayout {
+  int N, scal, kx, tab, lev, ltab, bic, rowt, work, total;
+};
+inline NgLayout make_ng_layout(int N) {
+  NgLayout G;
+  G.N = N;
+  int o = 0;
+  G.scal = o; o += 8;
+  G.kx = o; o += N;
+  G.tab = o; o += N * N;
+  G.lev = o; o += N * N;
+  G.ltab = o; o += N * N;
+  G.bic = o; o += 16 * (N - 1) * (N - 1);
+  G.rowt = o; o += 4 * (N - 1) * N;
+  G.work = o; o += 4 * (N - 1) * (6 * N);
+  G.total = (o + 7) & ~7;
+  return G;
+}
+// scalars 0..5 as kSsc* (kSscLimit holds _j0_limit here), then min(table)
+constexpr int kNgMin = 6;
+
+// Device block of an uploaded I_0^4 table: ln k knots | table | bicubic | scratch.
+struct NgTriLayout {
+  int N, kx, tab, bic, rowt, work, total;
+};
+inline NgTriLayout make_ng_tri_layout(int N) {
+  NgTriLayout T;
+  T.N = N;
+  int o = 0;
+  T.kx = o; o += N;
+  T.tab = o; o += N * N;
+  T.bic = o; o += 16 * (N - 1) * (N - 1);
+  T.rowt = o; o += 4 * (N - 1) * N;
+  T.work = o; o += 4 * (N - 1) * (6 * N);
+  T.total = (o + 7) & ~7;
+  return T;
+}
+// Dynamic LDS of k_ng_kb, in doubles: the kernel_NG row (SscRow) and the trispectrum row.
+inline int ng_kb_lds_doubles(int N, int NT) { return 5 * N - 4 + NT + 16 * (NT - 1); }
+
+// grid 1, block 256: z_bar_NG, chi(z_bar_NG), D(z_bar_NG) and the ln k theta knots from the
+// kernel_ssc block (k_ssc_prep has run), _j0_limit, and the status bit cleared.
+__global__ __launch_bounds__(256) void k_ng_prep(SscLayout S, NgLayout G,
+                                                 const double* __restrict__ st, double j0_limit,
+                                                 double* __restrict__ ng,
+                                                 unsigned* __restrict__ status) {
+  const int t = threadIdx.x;
+  for (int i = t; i < G.N; i += blockDim.x) ng[G.kx + i] = st[S.kx + i];
+  if (t < 8) ng[G.scal + t] = t == kSscLimit ? j0_limit : (t < kSscLimit ? st[S.scal + t] : 0.0);
+  if (t == 0 && status) atomicAnd(status, ~kStCovNgDivmax);
+}
+
+// kernel.py:1103-1111 (_kernel_NG_integrand) with the norm of raw_kernel_NG; the Romberg
+// variable is chi itself.
+struct NgKernelIntegrand {
+  const ProjLds* P;
+  const BesselTab* B;
+  double kta, ktb, norm;
+  __device__ __forceinline__ double operator()(double chi) const {
+    return ssc_ng_integrand(*P, B, chi, kta, ktb, norm);
+  }
+};
+
+// grid n integrals, block 256, LDS ProjLds::doubles.  ln_a == nullptr: the knot table of
+// _initialize_NG_spline (kernel.py:1016-1030), block b -> the b-th (i, j), i <= j, of the upper
+// triangle, written to [i][j] and [j][i] with its Romberg level; otherwise
+// raw_kernel_NG(ln_a[b], ln_b[b]) into out.
+__global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L, NgLayout G,
+                                                  const ProjDev* __restrict__ pdg,
+                                                  const double* __restrict__ ptab,
+                                                  const BesselTab* __restrict__ bess_g,
+                                                  double* __restrict__ ng,
+                                                  const double* __restrict__ ln_a,
+                                                  const double* __restrict__ ln_b,
+                                                  double* __restrict__ out,
+                                                  unsigned* __restrict__ status) {
+  extern __shared__ __align__(16) double sm[];
+  __shared__ ProjDev pd;
+  __shared__ BesselTab B;
+  __shared__ double red[romberg_scratch<4, 2>()];
+  copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
+  copy_doubles(reinterpret_cast<double*>(&B), reinterpret_cast<const double*>(bess_g),
+               (int)(sizeof(BesselTab) / sizeof(double)));
+  __syncthreads();
+  ProjLds P;
+  P.stage(L, pd, ptab, sm);
+  P.bess = &B;
+  __syncthreads();
+  int i = 0, j = 0;
+  double la, lb;
+  if (ln_a) {
+    la = ln_a[blockIdx.x];
+    lb = ln_b[blockIdx.x];
+  } else {
+    int b = (int)blockIdx.x;                       // row i holds N - i entries
+    while (b >= G.N - i) { b -= G.N - i; ++i; }
+    j = i + b;
+    la = ng[G.kx + i];
+    lb = ng[G.kx + j];
+  }
+  // kernel.py:1044-1073
+  const double kta = exp(la), ktb = exp(lb);
+  const double lim = ng[G.scal + kSscLimit];
+  double chi_max = fmax(lim / kta, lim / ktb);
+  double v = 0.0;
+  int level = 0;
+  bool zero = false, converged = true;
+  if (chi_max >= pd.chi_max) chi_max = pd.chi_max;
+  else if (chi_max <= pd.chi_min) zero = true;
+  if (!zero) {
+    // the norm passes ln(k theta_a) where k theta_a belongs (kernel.py:1055-1056)
+    const double inv = ssc_ng_integrand(P, &B, ng[G.scal + kSscChiPeak], la, la, 1.0);
+    const double norm = (inv > 1e-16 || inv < -1e-16) ? 1.0 / inv : 1.0;
+    const NgKernelIntegrand f{&P, &B, kta, ktb, norm};
+    Scalar1<NgKernelIntegrand> w{f};
+    const RombergOut<1> r = romberg_group<4, 1>(w, pd.chi_min, chi_max, cfg.global_precision,
+                                                cfg.kernel_precision, cfg.divmax, red);
+    v = r.value[0] / norm;
+    level = r.level[0];
+    converged = r.converged[0];
+  }
+  if (threadIdx.x == 0) {
+    if (ln_a) {
+      out[blockIdx.x] = v;
+    } else {
+      ng[G.tab + i * G.N + j] = v;
+      ng[G.tab + j * G.N + i] = v;
+      ng[G.lev + i * G.N + j] = (double)level;
+      ng[G.lev + j * G.N + i] = (double)level;
+    }
+    if (!converged && status) atomicOr(status, kStCovNgDivmax);
+  }
+}
+
+// grid 1, block 256: kernel.py:1026-1029 -- min(table) (numpy.min: a NaN entry gives NaN), then
+// the bicubic of log(table - 10 min).  Nothing is guarded: with min >= 0 an entry equal to
+// 10 min gives log(0) and the reference's spline is not finite either.
+__global__ __launch_bounds__(256) void k_ng_bicubic(NgLayout G, double* __restrict__ ng) {
+  __shared__ double part[256];
+  const int t = threadIdx.x, NN = G.N * G.N;
+  double m = INFINITY;
+  bool nan = false;
+  for (int q = t; q < NN; q += blockDim.x) {
+    const double v = ng[G.tab + q];
+    nan = nan || isnan(v);
+    m = v < m ? v : m;
+  }
+  part[t] = nan ? NAN : m;
+  __syncthreads();
+  if (t == 0) {
+    for (int q = 0; q < (int)blockDim.x; ++q) {
+      const double v = part[q];
+      nan = nan || isnan(v);
+      m = v < m ? v : m;
+    }
+    part[0] = nan ? NAN : m;
+    ng[G.scal + kNgMin] = part[0];
+  }
+  __syncthreads();
+  const double off = part[0] * 10.0;
+  for (int q = t; q < NN; q += blockDim.x) ng[G.ltab + q] = log(ng[G.tab + q] - off);
+  __threadfence_block();
+  __syncthreads();
+  bicubic_build(G.N, ng + G.kx, ng + G.ltab, ng + G.rowt, ng + G.work, ng + G.bic);
+}
+
+// The bicubic of log(table - 10 min) with kernel_ssc's range rules (kernel.py:1003-1014 clamps
+// with < where kernel_ssc has <=: the clamped value is the same), and 10 min.
+struct NgSpline {
+  SscSpline K;
+  double off;
+  // kernel_NG at one point
+  __device__ __forceinline__ double operator()(double a, double b) const {
+    if (a <= K.lo) a = K.lo;
+    if (b <= K.lo) b = K.lo;
+    if (!(a <= K.hi && b <= K.hi)) return 0.0;
+    return exp(K.poly(a, b)) + off;
+  }
+};
+__device__ __forceinline__ NgSpline ng_spline(const NgLayout& G, const double* ng) {
+  NgSpline K;
+  K.K.x = ng + G.kx;
+  K.K.bic = ng + G.bic;
+  K.K.N = G.N;
+  K.K.lo = ng[G.scal + kSscLnMin];
+  K.K.hi = ng[G.scal + kSscLnMax];
+  K.off = ng[G.scal + kNgMin] * 10.0;
+  return K;
+}
+
+__global__ void k_ng_eval(NgLayout G, const double* __restrict__ ng,
+                          const double* __restrict__ a, const double* __restrict__ b, int n,
+                          double* __restrict__ out) {
+  const NgSpline K = ng_spline(G, ng);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = K(a[i], b[i]);
+}
+
+// grid 1, block 256: the ln k knots linspace(ln k_min, ln k_max, N) and the bicubic of the
+// uploaded I_0^4 table -- the knots and the routine of k_tri1h_table / k_tri1h_bicubic, so the
+// coefficients are those of the trispectrum object's own context.
+__global__ __launch_bounds__(256) void k_ng_tri(NgTriLayout T, double k_min, double k_max,
+                                                double* __restrict__ tri) {
+  const double ln_k_min = log(k_min), ln_k_max = log(k_max);
+  for (int i = threadIdx.x; i < T.N; i += blockDim.x)
+    tri[T.kx + i] = linspace_at(ln_k_min, ln_k_max, T.N, i);
+  __threadfence_block();
+  __syncthreads();
+  bicubic_build(T.N, tri + T.kx, tri + T.tab, tri + T.rowt, tri + T.work, tri + T.bic);
+}
+
+// trispectrum_parallelogram(k_a, .) of HaloTrispectrumOneHalo at one fixed k_a
+// (halo_trispectrum.py:100-106): k < k_min is clamped to k_min, either k > k_max gives 0, and
+// the spline clamps ln k into its knot range (k_tri1h_eval).  The 16 (N - 1) coefficients of
+// k_a's row of cells are staged in LDS and the cell polynomial is Bicubic::poly's, so the value
+// is k_tri1h_eval's at the same (ln k_a, ln k_b).  lds: N + 16 (N - 1) doubles.  All threads
+// call build(); a barrier must follow before use.
+struct TriRow {
+  Bicubic B;                       // (x: the knots in LDS; bic: the row's cells in LDS)
+  double k_min, k_max, da;
+  bool zero;                       // k_a above k_max (or NaN): every value is 0
+  __device__ __forceinline__ void build(const NgTriLayout& T, const double* tri, double k_min_,
+                                        double k_max_, double ka, double* lds) {
+    double* lx = lds;
+    double* lc = lds + T.N;
+    Bicubic K;
+    K.x = tri + T.kx; K.bic = tri + T.bic; K.N = T.N;
+    K.lo = K.x[0]; K.hi = K.x[T.N - 1];
+    B = K; B.x = lx; B.bic = lc;
+    k_min = k_min_; k_max = k_max_;
+    if (ka < k_min) ka = k_min;
+    zero = !(ka <= k_max);
+    for (int i = threadIdx.x; i < T.N; i += blockDim.x) lx[i] = K.x[i];
+    da = 0.0;
+    if (zero) return;
+    double u = log(ka);
+    u = u < K.lo ? K.lo : (u > K.hi ? K.hi : u);
+    const int ia = K.interval(u);
+    da = u - K.x[ia];
+    const double* src = K.bic + (size_t)ia * (T.N - 1) * 16;
+    for (int q = threadIdx.x; q < 16 * (T.N - 1); q += blockDim.x) lc[q] = src[q];
+  }
+  __device__ __forceinline__ double operator()(double kb) const {
+    if (kb < k_min) kb = k_min;
+    if (zero || !(kb <= k_max)) return 0.0;
+    double v = log(kb);
+    v = v < B.lo ? B.lo : (v > B.hi ? B.hi : v);
+    const int jb = B.interval(v);
+    return bicubic_cell(B.bic + (size_t)jb * 16, da, v - B.x[jb]);
+  }
+};
+
+// covariance.py:673-683 (_kb_integrand): k_b^2 T(k_a, k_b) kernel_NG(ln k_a theta_a,
+// ln k_b theta_b), norm = 1.
+struct NgKbIntegrand {
+  const TriRow* T;
+  const SscRow* K;
+  double off, theta_b;
+  __device__ __forceinline__ double operator()(double ln_kb) const {
+    const double kb = exp(ln_kb);
+    double b = log(kb * theta_b);
+    const double kern = K->inside(b) ? exp(K->at(b)) + off : 0.0;
+    return kb * kb * 1.0 * (*T)(kb) * kern;
+  }
+};
+
+// grid (kernel_npoints, n pairs), block 256: the k_b integral at k_a knot x of pair y
+// (covariance.py:624-671), / D(z_bar_NG)^4.  LDS: ng_kb_lds_doubles.
+__global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgTriLayout T,
+                                               const double* __restrict__ ng,
+                                               const double* __restrict__ tri, double tri_k_min,
+                                               double tri_k_max,
+                                               const double* __restrict__ theta_a,
+                                               const double* __restrict__ theta_b,
+                                               double* __restrict__ knots,
+                                               double* __restrict__ levels,
+                                               unsigned* __restrict__ status) {
+  extern __shared__ __align__(16) double sm[];
+  __shared__ double red[romberg_scratch<4, 2>()];
+  const int i = blockIdx.x, pair = blockIdx.y, NK = cfg.kernel_npoints;
+  const double ln_k_min = log(cfg.k_min), ln_k_max = log(cfg.k_max);
+  const double ka = exp(linspace_at(ln_k_min, ln_k_max, NK, i));
+  const NgSpline S = ng_spline(G, ng);
+  SscRow K;
+  K.build(S.K, log(ka * theta_a[pair]), sm);
+  TriRow R;
+  R.build(T, tri, tri_k_min, tri_k_max, ka, sm + 5 * G.N - 4);
+  __syncthreads();
+  const NgKbIntegrand f{&R, &K, S.off, theta_b[pair]};
+  Scalar1<NgKbIntegrand> w{f};
+  const RombergOut<1> r = romberg_group<4, 1>(w, ln_k_min, ln_k_max, cfg.global_precision,
+                                              cfg.corr_precision, cfg.divmax, red);
+  if (threadIdx.x == 0) {
+    const double D = ng[G.scal + kSscDz];
+    knots[(size_t)pair * NK + i] = r.value[0] / (1.0 * D * D * D * D);
+    if (levels) levels[(size_t)pair * NK + i] = (double)r.level[0];
+    if (!r.converged[0] && status) atomicOr(status, kStCovNgDivmax);
+  }
 }
 
 }  // namespace chomp

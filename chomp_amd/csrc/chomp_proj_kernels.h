@@ -98,6 +98,12 @@ struct ProjState {
   int ssc_ns = 0;          // sigma^2 knots of that set-up
   double* d_ssc = nullptr;
   size_t cap_ssc = 0;      // doubles allocated at d_ssc
+  bool ng_prep = false;    // kernel_NG scalars and knots (chomp_kernel_ng_setup) valid
+  bool ng_ready = false;   // ... and the kernel_NG table with its log-offset bicubic
+  double* d_ng = nullptr;
+  size_t cap_ng = 0;       // doubles allocated at d_ng
+  double* d_ng_tri = nullptr;   // the I_0^4 table of the last chomp_covariance_ng and its bicubic
+  size_t cap_ng_tri = 0;
 };
 inline void proj_free(ProjState& p) {
   if (p.d_pd) (void)hipFree(p.d_pd);
@@ -109,6 +115,12 @@ inline void proj_free(ProjState& p) {
   p.cap_ssc = 0;
   p.ssc_ready = false;
   p.ssc_prep = false;
+  if (p.d_ng) (void)hipFree(p.d_ng);
+  if (p.d_ng_tri) (void)hipFree(p.d_ng_tri);
+  p.d_ng = p.d_ng_tri = nullptr;
+  p.cap_ng = p.cap_ng_tri = 0;
+  p.ng_ready = false;
+  p.ng_prep = false;
   p.d_pd = nullptr;
   p.d_pd_init = nullptr;
   p.d_tab = nullptr;

@@ -346,6 +346,11 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
  * (chomp_tri1h_setup; halo_trispectrum.py:89-95), or of a chomp_tri1h_quad call since, exhausted
  * divmax.  Each table set-up sets or clears it for its epochs. */
 #define CHOMP_ST_TRI1H_DIVMAX 0x40u
+/* COV_NG_DIVMAX: on the context's first epoch -- a raw_kernel_NG Romberg of the last
+ * chomp_kernel_ng_setup (kernel.py:1067-1072), of a chomp_kernel_ng_raw call or a k_b Romberg of
+ * a chomp_covariance_ng call (covariance.py:665-671) since, exhausted divmax.  The set-up
+ * clears it first. */
+#define CHOMP_ST_COV_NG_DIVMAX 0x80u
 #define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..5: H_M, PP_MM, H_G, PP_GM, PP_GG, I_1_2 */
 #define CHOMP_ST_HALO_DIVMAX_PP_MM 0x200u
 #define CHOMP_ST_HALO_DIVMAX_H_G 0x400u
@@ -690,6 +695,42 @@ int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, doub
 int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out);
 int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double* theta,
                          size_t n, double* out, double* kb_knots, double* kb_levels);
+
+/* One-halo trispectrum term of the covariance of w(theta), Covariance(corr, corr,
+ * nongaussian_cov=True, input_halo_trispectrum=HaloTrispectrumOneHalo), with a1 = b1 = window a
+ * and a2 = b2 = window b of the context's kernel_setup.  Host memory throughout.
+ *
+ * chomp_kernel_ng_setup replaces KernelCovariance._initialize_NG_spline (kernel.py:1016-1030).
+ * It needs chomp_kernel_ssc_setup (with_table 0 is enough) for z_bar_NG, chi(z_bar_NG),
+ * growth_factor(z_bar_NG) and the ln(k theta) knots, and keeps its own copy of them.  The
+ * kernel_npoints x kernel_npoints table of raw_kernel_NG (:1035-1073: the Romberg over chi up
+ * to max(j0_limit / k theta_a, j0_limit / k theta_b), j0_limit being _j0_limit, :944-945) is
+ * integrated (upper triangle, mirrored); min = min(table), and log(table - 10 min) gets the
+ * tensor-product bicubic of RectBivariateSpline(s=0).  with_table = 0 stops before the table
+ * (what chomp_kernel_ng_raw needs); the other two calls need 1.  table and levels (each
+ * [kernel_npoints^2], row-major in ln(k theta_a)) and table_min[1] may be NULL (with_table
+ * only).
+ *
+ * chomp_kernel_ng_raw replaces raw_kernel / raw_kernel_NG and chomp_kernel_ng_eval kernel /
+ * kernel_NG (:996-1014: exp(spline) + 10 min; ln(k theta) below the range is clamped, above it
+ * the value is 0) at n points: ln_ktheta holds ln(k theta_a)[n] then ln(k theta_b)[n].
+ *
+ * chomp_covariance_ng replaces Covariance.covariance_NG (covariance.py:593-683) for n pairs of
+ * bin centres: theta holds theta_a[n] then theta_b[n] (radians), area is in steradians.  The
+ * trispectrum is trispectrum_parallelogram of a HaloTrispectrumOneHalo (halo_trispectrum.py:
+ * 100-106): tri_table[n_tri^2] is its I_0^4 table (chomp_tri1h_setup's, row-major) over
+ * linspace(ln tri_k_min, ln tri_k_max, n_tri); the call rebuilds that table's bicubic with the
+ * routine of chomp_tri1h_setup and applies the k_min clamp and the k_max mask.  kb_knots /
+ * kb_levels ([n * kernel_npoints], may be NULL) receive each pair's k_b integrals at the k_a
+ * knots (divided by growth_factor(z_bar_NG)^4) and their Romberg levels.
+ * CHOMP_ST_COV_NG_DIVMAX reports an exhausted divmax. */
+int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, double* table,
+                          double* levels, double* table_min);
+int chomp_kernel_ng_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out);
+int chomp_kernel_ng_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out);
+int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, size_t n_tri,
+                        double tri_k_min, double tri_k_max, const double* theta, size_t n,
+                        double* out, double* kb_knots, double* kb_levels);
 
 /* CorrelationFourier.correlation(l) (correlation.py:360-392): Limber C_l. */
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z,
