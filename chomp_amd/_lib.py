@@ -137,6 +137,8 @@ EXPORTS = [
     "chomp_set_dark_energy", "chomp_get_de_table",
     "chomp_set_second_order", "chomp_get_second_order", "chomp_pt_eval",
     "chomp_tri1h_setup", "chomp_tri1h_eval", "chomp_tri1h_quad",
+    "chomp_tri_setup", "chomp_tri_table_eval", "chomp_tri_terms", "chomp_tri_proj",
+    "chomp_tri_triple",
     "chomp_kernel_ng_setup", "chomp_kernel_ng_raw", "chomp_kernel_ng_eval",
     "chomp_covariance_ng",
 ]
@@ -149,7 +151,9 @@ ST_TRI1H_DIVMAX = 0x40
 ST_COV_NG_DIVMAX = 0x80
 ST_HALO_DIVMAX = {"h_m": 0x100, "pp_mm": 0x200, "h_g": 0x400, "pp_gm": 0x800, "pp_gg": 0x1000,
                   "i_1_2": 0x2000}
+ST_TRI_DIVMAX = 0x4000
 ST_NONFINITE = 0x10000
+TRI_TAB = {"i_1_2": 0, "i_1_3": 1, "i_2_2": 2, "i_2_1": 3, "i_0_4": 4, "i_1_1": 5}
 ST_SATURATED = ST_MASS_MIN_SATURATED | ST_MASS_MAX_SATURATED
 TUNE_E_STREAM_MIN, TUNE_DEEP_LITERAL, TUNE_ROCTX, TUNE_WTHETA_DIRECT = 0, 2, 3, 4
 TUNE_CELL_ONE_KERNEL = 5
@@ -187,6 +191,10 @@ def describe_status(word):
     if word & ST_TRI1H_DIVMAX:
         out.append("an I_0^4 Romberg of the one-halo trispectrum exhausted divmax "
                    "(halo_trispectrum.py:89-95)")
+    if word & ST_TRI_DIVMAX:
+        out.append("a Romberg of the HaloTrispectrum tables or of tri_spec_proj_integral exhausted "
+                   "divmax, or an end point of the latter was not finite (k1 = k2: the result is "
+                   "NaN, halo_trispectrum.py:267-278, 655-836)")
     if word & ST_COV_NG_DIVMAX:
         out.append("a Romberg of the trispectrum term of the covariance (raw_kernel_NG, "
                    "kernel.py:1067-1072, or a k_b integral, covariance.py:665-671) exhausted "
@@ -407,6 +415,11 @@ def lib():
         L.chomp_tri1h_setup.argtypes = [vp, sz, sz, i, vp, vp]
         L.chomp_tri1h_eval.argtypes = [vp, sz, vp, vp, sz, vp, i]
         L.chomp_tri1h_quad.argtypes = [vp, sz, i, vp, sz, vp, vp, i]
+        L.chomp_tri_setup.argtypes = [vp, sz, sz, vp, vp]
+        L.chomp_tri_table_eval.argtypes = [vp, sz, i, vp, vp, sz, vp, i]
+        L.chomp_tri_terms.argtypes = [vp, sz, sz, vp, sz, vp, i]
+        L.chomp_tri_proj.argtypes = [vp, sz, sz, vp, sz, vp, vp, vp, i]
+        L.chomp_tri_triple.argtypes = [vp, sz, vp, sz, vp, vp, i]
         L.chomp_set_timing.argtypes = [vp, i]
         L.chomp_get_timing.argtypes = [vp, c_double_p, sz]
         L.chomp_get_status.argtypes = [vp, sz, sz, ctypes.POINTER(ctypes.c_uint)]
@@ -747,6 +760,71 @@ class Context(object):
                 raise ValueError("tri1h_quad: k must be [N, 4]")
             return epoch, int(moment), a, m, new(m), new(m) if levels else None, mem
         outs = self._run(self._L.chomp_tri1h_quad, [k], body)
+        return tuple(outs) if levels else outs[0]
+
+    # -- two- to four-halo trispectrum ------------------------------------------------
+    def tri_setup(self, epoch0=0, n=None, copy_out=False):
+        """The five mass-integral tables of HaloTrispectrum, their levels and splines of the
+        epochs [epoch0, epoch0 + n) (chomp_tri_setup).  copy_out: return (tables, levels), each a
+        dictionary name -> [n, N, N] ([n, N] for "i_2_1") (synchronises); else None."""
+        n = self.n_epoch - epoch0 if n is None else n
+        if not copy_out:
+            self._check(self._L.chomp_tri_setup(self._h, epoch0, n, None, None))
+            return None
+        nk = self.config.halo_npoints
+        per = 4 * nk * nk + nk
+        raw = [numpy.empty((n, per)), numpy.empty((n, per))]
+        self._check(self._L.chomp_tri_setup(self._h, epoch0, n,
+                                            ctypes.c_void_p(raw[0].ctypes.data),
+                                            ctypes.c_void_p(raw[1].ctypes.data)))
+        outs = []
+        for r in raw:
+            d = {}
+            for j, name in enumerate(("i_0_4", "i_1_2", "i_1_3", "i_2_2")):
+                d[name] = r[:, j * nk * nk:(j + 1) * nk * nk].reshape(n, nk, nk).copy()
+            d["i_2_1"] = r[:, 4 * nk * nk:].copy()
+            outs.append(d)
+        return tuple(outs)
+
+    def tri_table_eval(self, table, k1, k2, epoch=0):
+        """Table `table` (a TRI_TAB key) at the points (k1[i], k2[i]) with the reference's clamp
+        and zero rules (chomp_tri_table_eval); numpy or contiguous float64 torch cuda tensors."""
+        def body(mem, new, a, b):
+            if _numel(a) != _numel(b):
+                raise ValueError("tri_table_eval: k1 and k2 differ in length")
+            return epoch, TRI_TAB[table], a, b, _numel(a), new(_numel(a)), mem
+        return self._run(self._L.chomp_tri_table_eval, [k1, k2], body)[0]
+
+    def tri_terms(self, kkz, epoch=0, pt_epoch=0):
+        """t_1_h .. t_4_h [N, 4] at the configurations kkz [N, 3] = (k1, k2, z)
+        (chomp_tri_terms); numpy or a contiguous float64 torch cuda tensor."""
+        def body(mem, new, a):
+            m, rest = divmod(_numel(a), 3)
+            if rest:
+                raise ValueError("tri_terms: kkz must be [N, 3]")
+            return epoch, pt_epoch, a, m, new((m, 4)), mem
+        return self._run(self._L.chomp_tri_terms, [kkz], body)[0]
+
+    def tri_proj(self, kk, epoch=0, pt_epoch=0, levels=False):
+        """tri_spec_proj_integral at the pairs kk [N, 2] (chomp_tri_proj).  levels: also return
+        the Romberg levels and the per-pair flags (1: NaN end point or divmax)."""
+        def body(mem, new, a):
+            m, rest = divmod(_numel(a), 2)
+            if rest:
+                raise ValueError("tri_proj: kk must be [N, 2]")
+            return (epoch, pt_epoch, a, m, new(m), new(m) if levels else None,
+                    new(m) if levels else None, mem)
+        outs = self._run(self._L.chomp_tri_proj, [kk], body)
+        return tuple(outs) if levels else outs[0]
+
+    def tri_triple(self, k, epoch=0, levels=False):
+        """i_1_3 at the triples k [N, 3] (chomp_tri_triple)."""
+        def body(mem, new, a):
+            m, rest = divmod(_numel(a), 3)
+            if rest:
+                raise ValueError("tri_triple: k must be [N, 3]")
+            return epoch, a, m, new(m), new(m) if levels else None, mem
+        outs = self._run(self._L.chomp_tri_triple, [k], body)
         return tuple(outs) if levels else outs[0]
 
     def halofit_setup(self, dst, src, f1, f2, f3, omega_l, w):

@@ -208,6 +208,13 @@ struct chomp_ctx {
   double* d_tri = nullptr;
   size_t cap_tri = 0;
   std::vector<char> tri_built;
+  int tri_moment = -1;             // the moment of the I_0^4 tables in d_tri (the last chomp_tri1h_setup)
+  // HaloTrispectrum (chomp_tri_setup): per epoch the I_1^2, I_1^3, I_2^2 and I_2^1 tables with
+  // their levels and splines (TriTabLayout); tri4_built as tri_built
+  TriTabLayout Q4;
+  double* d_tri4 = nullptr;
+  size_t cap_tri4 = 0;
+  std::vector<char> tri4_built;
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
   bool timing_valid = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -688,7 +695,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_stage_in, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri};
+                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -1056,6 +1063,7 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   ctx->delta_b_zero = true;
   ctx->have_halofit.assign(n_epoch, 0);
   ctx->tri_built.assign(n_epoch, 0);
+  ctx->tri4_built.assign(n_epoch, 0);
   rc = upload(ctx, ctx->d_cosmo, cosmo, n_epoch * sizeof(chomp_cosmo), ctx->sh_cosmo);
   if (rc) return rc;
   rc = upload(ctx, ctx->d_z, z, n_epoch * sizeof(double), ctx->sh_z);
@@ -1560,6 +1568,7 @@ int chomp_set_transfer(chomp_ctx* ctx, int kind) {
     ctx->fam_mask = 0;
     ctx->put_mask.assign(ctx->put_mask.size(), 0u);
     ctx->tri_built.assign(ctx->tri_built.size(), 0);
+    ctx->tri4_built.assign(ctx->tri4_built.size(), 0);
   }
   return CHOMP_OK;
 }
@@ -2038,6 +2047,11 @@ int chomp_tri1h_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, int moment,
   hipLaunchKernelGGL(k_tri1h_bicubic, dim3((unsigned)n_epoch), dim3(256), 0, ctx->stream, T,
                      (int)epoch0, ctx->d_tri, ctx->d_status);
   HIPCHK(hipGetLastError());
+  if (ctx->tri_moment != moment) {     // (tables of another moment are not this call's)
+    for (size_t e = 0; e < ctx->tri_built.size(); ++e)
+      if (e < epoch0 || e >= epoch0 + n_epoch) ctx->tri_built[e] = 0;
+    ctx->tri_moment = moment;
+  }
   for (size_t e = epoch0; e < epoch0 + n_epoch; ++e) ctx->tri_built[e] = 1;
   if (table_out || levels_out) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2099,9 +2113,194 @@ int chomp_tri1h_quad(chomp_ctx* ctx, size_t epoch, int moment, const double* k, 
   const int rc = st.place();
   if (rc) return rc;
   const int lds = tri_quad_lds_doubles(ctx->L.NM) * (int)sizeof(double);
-  hipLaunchKernelGGL(k_tri1h_quad, dim3((unsigned)nb), dim3(64 * kTriQuadWaves), (size_t)lds,
+  hipLaunchKernelGGL(k_tri1h_quad<4>, dim3((unsigned)nb), dim3(64 * kTriQuadWaves), (size_t)lds,
                      ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab,
-                     ctx->d_sici, moment, dk, (long)n, dout, dlev, ctx->d_status);
+                     ctx->d_sici, moment, dk, (long)n, dout, dlev, ctx->d_status,
+                     kStTri1hDivmax);
+  return st.finish();
+}
+
+// -- HaloTrispectrum (halo_trispectrum.py:153-837) -------------------------------------------------
+// Replaces the five _initialize_i_* loops (:592-836): 4 x 1275 + 50 scipy Rombergs and the spline
+// fits, for a range of epochs.
+int chomp_tri_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, double* tables_out,
+                    double* levels_out) {
+  StageRange range_(ctx, "chomp:tri_setup");
+  if (!ctx || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "tri_setup: bad args");
+  if (!ctx->have_halo) return fail(ctx, CHOMP_ERR_STATE, "tri_setup before a halo set-up");
+  if (!ctx->have_b2)
+    return fail(ctx, CHOMP_ERR_STATE, "tri_setup: the last mass set-up was not second-order "
+                                      "(chomp_set_second_order)");
+  {
+    const int rc = chomp_tri1h_setup(ctx, epoch0, n_epoch, CHOMP_TRI_MMMM, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  const int N = ctx->L.NK;
+  ctx->Q4 = make_tri_tab_layout(N);
+  const TriTabLayout& Q = ctx->Q4;
+  const size_t need = ctx->n_epoch * (size_t)Q.total;
+  if (need > ctx->cap_tri4 || ctx->tri4_built.size() != ctx->n_epoch) {
+    const int rc = ensure(ctx, &ctx->d_tri4, &ctx->cap_tri4, need);
+    if (rc) return rc;
+    ctx->tri4_built.assign(ctx->n_epoch, 0);
+  }
+  const int lds = tri_tab_lds_doubles(ctx->L.NM, N) * (int)sizeof(double);
+  { const int rc = lds_opt_in(ctx, &k_tri_table, lds); if (rc) return rc; }
+  hipLaunchKernelGGL(k_tri_table, dim3((unsigned)Q.T.nchunk, (unsigned)n_epoch, 4u),
+                     dim3(kTriThreads), (size_t)lds, ctx->stream, ctx->cfg, ctx->L, ctx->B2, Q,
+                     ctx->d_epochs, (int)epoch0, ctx->d_tab, ctx->d_b2, ctx->d_sici, ctx->d_tri4);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_tri_finish, dim3((unsigned)n_epoch, 4u), dim3(256), 0, ctx->stream, Q,
+                     (int)epoch0, ctx->d_tri4, ctx->d_status);
+  HIPCHK(hipGetLastError());
+  for (size_t e = epoch0; e < epoch0 + n_epoch; ++e) ctx->tri4_built[e] = 1;
+  if (tables_out || levels_out) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t nn = (size_t)N * N, per = 4 * nn + (size_t)N;
+    for (size_t e = 0; e < n_epoch; ++e) {
+      const double* b1 = ctx->d_tri + (epoch0 + e) * (size_t)ctx->T3.total;
+      const double* b4 = ctx->d_tri4 + (epoch0 + e) * (size_t)Q.total;
+      for (int w = 0; w < 2; ++w) {
+        double* o = w == 0 ? tables_out : levels_out;
+        if (!o) continue;
+        o += e * per;
+        const int o2 = w == 0 ? Q.T.tab : Q.T.lev;
+        HIPCHK(hipMemcpy(o, b1 + o2, nn * sizeof(double), hipMemcpyDeviceToHost));
+        for (int k = 0; k < kTriKinds2d; ++k)
+          HIPCHK(hipMemcpy(o + (k + 1) * nn, b4 + (size_t)k * Q.T.total + o2, nn * sizeof(double),
+                           hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o + 4 * nn, b4 + (w == 0 ? Q.tab : Q.lev), N * sizeof(double),
+                         hipMemcpyDeviceToHost));
+      }
+    }
+  }
+  return CHOMP_OK;
+}
+
+static int tri_ready(chomp_ctx* ctx, size_t epoch, const char* who) {
+  if (epoch >= ctx->n_epoch || epoch >= ctx->tri4_built.size() || !ctx->tri4_built[epoch] ||
+      epoch >= ctx->tri_built.size() || !ctx->tri_built[epoch] ||
+      ctx->tri_moment != CHOMP_TRI_MMMM)
+    return fail(ctx, CHOMP_ERR_STATE, std::string(who) + ": no HaloTrispectrum tables of this epoch (chomp_tri_setup)");
+  return CHOMP_OK;
+}
+
+// Replaces the spline look-ups of i_0_4_parallelogram, i_1_2, i_1_3_parallelogram, i_2_1, i_2_2.
+int chomp_tri_table_eval(chomp_ctx* ctx, size_t epoch, int table, const double* k1,
+                         const double* k2, size_t n, double* out, int mem) {
+  StageRange range_(ctx, "chomp:tri_table_eval");
+  if (!ctx || !k1 || !k2 || !out || n == 0 || n > (size_t)INT32_MAX)
+    return fail(ctx, CHOMP_ERR_ARG, "tri_table_eval: bad args");
+  if (table < CHOMP_TRI_TAB_I_1_2 || table > CHOMP_TRI_TAB_I_1_1)
+    return fail(ctx, CHOMP_ERR_ARG, "tri_table_eval: unknown table");
+  Staging st(ctx, mem, "tri_table_eval");
+  if (st.rc) return st.rc;
+  { const int rc = tri_ready(ctx, epoch, "tri_table_eval"); if (rc) return rc; }
+  if (table == CHOMP_TRI_TAB_I_1_1 && !((ctx->fam_mask | ctx->put_mask[epoch]) & (1u << F_HM)))
+    return fail(ctx, CHOMP_ERR_STATE, "tri_table_eval: the h_m knot table was not built (chomp_halo_setup)");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double *da, *db;
+  double* dout;
+  st.in(k1, n, &da);
+  st.in(k2, n, &db);
+  st.out(out, n, &dout);
+  const int rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tri_lookup, grid_1d(n), dim3(256), 0, ctx->stream, ctx->cfg, ctx->L, ctx->T3,
+                     ctx->Q4, ctx->d_tab, ctx->d_tri, ctx->d_tri4, (int)epoch, table, da, db,
+                     (int)n, dout);
+  return st.finish();
+}
+
+static int tri_terms_ready(chomp_ctx* ctx, size_t epoch, size_t pt_epoch, const char* who) {
+  const int rc = tri_ready(ctx, epoch, who);
+  if (rc) return rc;
+  if (pt_epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": pt_epoch");
+  if (!((ctx->fam_mask | ctx->put_mask[epoch]) & (1u << F_HM)))
+    return fail(ctx, CHOMP_ERR_STATE, std::string(who) + ": the h_m knot table was not built (chomp_halo_setup)");
+  return CHOMP_OK;
+}
+
+// Replaces t_1_h .. t_4_h (:320-512), one Python call chain per configuration.
+int chomp_tri_terms(chomp_ctx* ctx, size_t epoch, size_t pt_epoch, const double* kkz, size_t n,
+                    double* out, int mem) {
+  StageRange range_(ctx, "chomp:tri_terms");
+  if (!ctx || !kkz || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "tri_terms: bad args");
+  Staging st(ctx, mem, "tri_terms");
+  if (st.rc) return st.rc;
+  { const int rc = tri_terms_ready(ctx, epoch, pt_epoch, "tri_terms"); if (rc) return rc; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* dk;
+  double* dout;
+  st.in(kkz, 3 * n, &dk);
+  st.out(out, 4 * n, &dout);
+  const int rc = st.place();
+  if (rc) return rc;
+  size_t gx = (n + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_tri_terms<BAO>, dim3((unsigned)gx), dim3(256), 0, ctx->stream, ctx->cfg,
+                       ctx->L, ctx->T3, ctx->Q4, ctx->d_epochs, (int)epoch, (int)pt_epoch,
+                       ctx->d_tab, ctx->d_tri, ctx->d_tri4, dk, n, dout);
+  });
+  return st.finish();
+}
+
+// Replaces tri_spec_proj_integral (:267-278): one scipy Romberg over theta per pair.
+int chomp_tri_proj(chomp_ctx* ctx, size_t epoch, size_t pt_epoch, const double* kk, size_t n,
+                   double* out, double* levels, double* flags, int mem) {
+  StageRange range_(ctx, "chomp:tri_proj");
+  if (!ctx || !kk || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "tri_proj: bad args");
+  Staging st(ctx, mem, "tri_proj");
+  if (st.rc) return st.rc;
+  { const int rc = tri_terms_ready(ctx, epoch, pt_epoch, "tri_proj"); if (rc) return rc; }
+  const size_t nb = (n + kTriProjWaves - 1) / kTriProjWaves;
+  if (nb > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "tri_proj: too many pairs");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* dk;
+  double* dout;
+  double* dlev = nullptr;
+  double* dflag = nullptr;
+  st.in(kk, 2 * n, &dk);
+  st.out(out, n, &dout);
+  if (levels) st.out(levels, n, &dlev);
+  if (flags) st.out(flags, n, &dflag);
+  const int rc = st.place();
+  if (rc) return rc;
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_tri_proj<BAO>, dim3((unsigned)nb), dim3(64 * kTriProjWaves), 0,
+                       ctx->stream, ctx->cfg, ctx->L, ctx->T3, ctx->Q4, ctx->d_epochs, (int)epoch,
+                       (int)pt_epoch, ctx->d_tab, ctx->d_tri, ctx->d_tri4, dk, (long)n, dout, dlev,
+                       dflag, ctx->d_status);
+  });
+  return st.finish();
+}
+
+// Replaces i_1_3 (:690-705): one scipy Romberg per call.
+int chomp_tri_triple(chomp_ctx* ctx, size_t epoch, const double* k, size_t n, double* out,
+                     double* levels, int mem) {
+  StageRange range_(ctx, "chomp:tri_triple");
+  if (!ctx || !k || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "tri_triple: bad args");
+  Staging st(ctx, mem, "tri_triple");
+  if (st.rc) return st.rc;
+  if (!ctx->have_halo || epoch >= ctx->n_epoch)
+    return fail(ctx, CHOMP_ERR_STATE, "tri_triple before a halo set-up of this epoch");
+  const size_t nb = (n + kTriQuadWaves - 1) / kTriQuadWaves;
+  if (nb > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "tri_triple: too many triples");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* dk;
+  double* dout;
+  double* dlev = nullptr;
+  st.in(k, 3 * n, &dk);
+  st.out(out, n, &dout);
+  if (levels) st.out(levels, n, &dlev);
+  const int rc = st.place();
+  if (rc) return rc;
+  const int lds = tri_quad_lds_doubles(ctx->L.NM) * (int)sizeof(double);
+  hipLaunchKernelGGL(k_tri1h_quad<3>, dim3((unsigned)nb), dim3(64 * kTriQuadWaves), (size_t)lds,
+                     ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab,
+                     ctx->d_sici, CHOMP_TRI_MMMM, dk, (long)n, dout, dlev, ctx->d_status,
+                     kStTriDivmax);
   return st.finish();
 }
 

@@ -351,6 +351,10 @@ int chomp_get_scalars(chomp_ctx* ctx, size_t epoch, double* out);
  * a chomp_covariance_ng call (covariance.py:665-671) since, exhausted divmax.  The set-up
  * clears it first. */
 #define CHOMP_ST_COV_NG_DIVMAX 0x80u
+/* TRI_DIVMAX: a Romberg of the last HaloTrispectrum tables of the epoch (chomp_tri_setup;
+ * halo_trispectrum.py:655-836), or of a chomp_tri_proj / chomp_tri_triple call since, exhausted
+ * divmax; for chomp_tri_proj also a non-finite end point (k1 = k2), where the result is NaN. */
+#define CHOMP_ST_TRI_DIVMAX 0x4000u
 #define CHOMP_ST_HALO_DIVMAX_H_M 0x100u   /* << 0..5: H_M, PP_MM, H_G, PP_GM, PP_GG, I_1_2 */
 #define CHOMP_ST_HALO_DIVMAX_PP_MM 0x200u
 #define CHOMP_ST_HALO_DIVMAX_H_G 0x400u
@@ -531,6 +535,50 @@ int chomp_tri1h_eval(chomp_ctx* ctx, size_t epoch, const double* ln_k1, const do
  * levels in HBM, asynchronous on the context's stream). */
 int chomp_tri1h_quad(chomp_ctx* ctx, size_t epoch, int moment, const double* k, size_t n,
                      double* out, double* levels, int mem);
+
+/* ---- HaloTrispectrum (halo_trispectrum.py:153-837): the two- to four-halo terms ----
+ * Tables of chomp_tri_setup / chomp_tri_table_eval. */
+#define CHOMP_TRI_TAB_I_1_2 0
+#define CHOMP_TRI_TAB_I_1_3 1
+#define CHOMP_TRI_TAB_I_2_2 2
+#define CHOMP_TRI_TAB_I_2_1 3
+#define CHOMP_TRI_TAB_I_0_4 4
+#define CHOMP_TRI_TAB_I_1_1 5   /* _h_m(k1): 0 outside [k_min, k_max], no clamp (halo.py:649-652) */
+/* _initialize_i_0_4 / _i_1_2 / _i_1_3 / _i_2_1 / _i_2_2 (halo_trispectrum.py:592-836) for the
+ * epochs [epoch0, epoch0 + n_epoch): the four N x N tables (upper triangle integrated and
+ * mirrored) and the N-knot table of I_2^1, every integral's Romberg level, the bicubics and the
+ * not-a-knot spline.  I_0^4 is chomp_tri1h_setup's with CHOMP_TRI_MMMM (called from here).
+ * Needs a second-order mass set-up (chomp_set_second_order) and a halo set-up of those epochs.
+ * tables_out, levels_out (optional, host): per epoch 4 N N + N doubles in the order I_0^4,
+ * I_1^2, I_1^3, I_2^2 (row-major) and I_2^1 (synchronises).  CHOMP_ST_TRI_DIVMAX (and, for
+ * I_0^4, CHOMP_ST_TRI1H_DIVMAX) reports an exhausted divmax.
+ * The I_0^4 table is the context's one-halo table: a later chomp_tri1h_setup with another moment
+ * replaces it, and the calls below then return CHOMP_ERR_STATE until chomp_tri_setup is called
+ * again.  As for chomp_tri1h_setup, the tables belong to the mass and halo set-up they were built
+ * from: after a new chomp_mass_setup / chomp_halo_setup* on the same context call this again
+ * (chomp_epochs_set forgets the tables by itself). */
+int chomp_tri_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, double* tables_out,
+                    double* levels_out);
+/* One table's spline (table: CHOMP_TRI_TAB_*) of one epoch at n points (k1[i], k2[i]) with the
+ * reference's rules: k < k_min is clamped to k_min, k > k_max gives 0 (I_2^1 reads k1 only).
+ * mem: CHOMP_HOST (staged, synchronous) or CHOMP_DEVICE. */
+int chomp_tri_table_eval(chomp_ctx* ctx, size_t epoch, int table, const double* k1,
+                         const double* k2, size_t n, double* out, int mem);
+/* t_1_h, t_2_h, t_3_h, t_4_h (halo_trispectrum.py:320-512) at n configurations kkz[i][0..2] =
+ * (k1, k2, cos theta): out[i][0..3].  epoch: the halo model's (tables of chomp_tri_setup and the
+ * h_m knot table); pt_epoch: the PerturbationTheory object's, whose linear spectrum the
+ * bispectrum and trispectrum forms use.  mem as above. */
+int chomp_tri_terms(chomp_ctx* ctx, size_t epoch, size_t pt_epoch, const double* kkz, size_t n,
+                    double* out, int mem);
+/* tri_spec_proj_integral (halo_trispectrum.py:267-278) at n pairs kk[i][0..1]: out[n], and
+ * (optional) levels[n], the Romberg levels, and flags[n], 1 where the result is NaN from a
+ * non-finite end point or divmax ran out (CHOMP_ST_TRI_DIVMAX is raised then).  mem as above. */
+int chomp_tri_proj(chomp_ctx* ctx, size_t epoch, size_t pt_epoch, const double* kk, size_t n,
+                   double* out, double* levels, double* flags, int mem);
+/* i_1_3(k1, k2, k3) (halo_trispectrum.py:690-705) at n triples k[i][0..2] of one epoch, one
+ * Romberg each: out[n], levels[n] (optional).  Needs a halo set-up of the epoch.  mem as above. */
+int chomp_tri_triple(chomp_ctx* ctx, size_t epoch, const double* k, size_t n, double* out,
+                     double* levels, int mem);
 
 /* ---- Projection: MultiEpoch, windows, kernel, correlation --------------------
  * One projection set-up per context. */
