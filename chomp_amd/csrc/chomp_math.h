@@ -51,8 +51,11 @@ CHOMP_HD double fma_k(double a, double b, double c) { return fma(a, b, c); }
 // algorithm and coefficients (n = rint(x log2 e), Cody-Waite reduction by ln 2 in two FMAs, the
 // degree-11 polynomial, ldexp), operation for operation -- the same bits -- with the polynomial's
 // addends read from scalar registers (fma_k): 9 of its 11 steps cost the library's inlined code
-// three vector instructions each.  The library's two range clamps are left out: v_ldexp_f64
-// overflows to inf and underflows to 0 by itself.
+// three vector instructions each.  The library's two range clamps are kept, as selects on x (no
+// branch): v_ldexp_f64 overflows to inf and underflows to 0 by itself for a finite polynomial
+// value, but at x = +-inf the reduction is inf - inf (NaN instead of inf / 0), and for |x| beyond
+// ~1e16 it leaves a huge r, the polynomial overflows and ldexp hands its +-inf through with
+// either sign.  The clamps are the library's thresholds, ln(DBL_MAX) and ln(2^-1075).
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ double exp(double x) {
   const double n = rint(x * 1.4426950408889634);                       // 0x3ff71547652b82fe
@@ -69,7 +72,10 @@ __device__ __forceinline__ double exp(double x) {
   p = fma_k(r, p, __longlong_as_double(0x3fe000000000000bLL));
   p = fma(r, p, 1.0);
   p = fma(r, p, 1.0);
-  return ldexp(p, (int)n);
+  double z = ldexp(p, (int)n);
+  z = x > __longlong_as_double(0x40862e42fefa39efLL) ? __longlong_as_double(0x7ff0000000000000LL) : z;
+  z = x < __longlong_as_double(0xc0874910d52d3051LL) ? 0.0 : z;
+  return z;
 }
 #else
 CHOMP_HD double exp(double x) { return ::exp(x); }
