@@ -1,22 +1,59 @@
-"""Builds and loads tests/devcheck/libdevcheck.so, the TEST-ONLY device harness of the fp64
-primitives (chomp_math.h) and the wavefront Romberg (chomp_romberg.h): the device counterpart of
-tests/hostcheck.  Compiled with the product's own compiler flags (imported from chomp_amd._lib,
-never copied) and rebuilt only when the content of what it is compiled from changes, as _lib.py
-does for the product library.  hipcc cross-compiles for gfx950 without a GPU."""
+"""Builds and loads the TEST-ONLY device harnesses under tests/devcheck, the device counterparts
+of tests/hostcheck: libdevcheck.so (devcheck.hip: the fp64 primitives of chomp_math.h and the
+wavefront Romberg of chomp_romberg.h) and libdevphys.so (devphys.hip: the halo-model physics of
+chomp_math.h, through the product's whole header chain from chomp_cov_kernels.h down).  Each harness is
+compiled with the product's compiler flags (imported from chomp_amd._lib, never copied) and
+rebuilt only when the content of what IT is compiled from changes, as _lib.py does for the
+product library: its own source, .so and content hash, the hash over every product header it
+includes.  hipcc cross-compiles for gfx950 without a GPU."""
 import ctypes
 import hashlib
 import os
+import re
 import subprocess
 
 from chomp_amd import _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DIR = os.path.join(HERE, "devcheck")
-SRC = os.path.join(DIR, "devcheck.hip")
-SO = os.path.join(DIR, "libdevcheck.so")
-HASH = SO + ".srchash"
-HEADERS = [os.path.join(_lib.CSRC, name)
-           for name in ("chomp_math.h", "chomp_romberg.h", "special_tables.h")]
+
+
+def included_headers(src):
+    """Every file that `src` includes with quotes, transitively (the product headers and the C
+    header: whatever a change of can change the harness), in a fixed order."""
+    seen, todo = [], [src]
+    while todo:
+        path = todo.pop()
+        with open(path) as f:
+            text = f.read()
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
+            inc = os.path.normpath(os.path.join(os.path.dirname(path), name))
+            if inc not in seen and os.path.exists(inc):     # (not one found through -I)
+                seen.append(inc)
+                todo.append(inc)
+    return sorted(seen)
+
+
+class Harness:
+    """One translation unit tests/devcheck/<name>.hip -> lib<name>.so (+ .srchash)."""
+
+    def __init__(self, name):
+        self.name = name
+        self.src = os.path.join(DIR, name + ".hip")
+        self.so = os.path.join(DIR, "lib" + name + ".so")
+        self.hash = self.so + ".srchash"
+
+    @property
+    def headers(self):
+        return included_headers(self.src)
+
+
+HARNESSES = {"devcheck": Harness("devcheck"), "devphys": Harness("devphys")}
+# the first harness under its earlier names
+SRC = HARNESSES["devcheck"].src
+SO = HARNESSES["devcheck"].so
+HASH = HARNESSES["devcheck"].hash
+HEADERS = HARNESSES["devcheck"].headers
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 _i, _p = ctypes.c_int, c_double_p
@@ -39,6 +76,25 @@ ENTRY_POINTS = {
     "dc_index": [_i, _p, _i, _p],
     "dc_gauss": [_i, _p, _i, _p],
 }
+_v, _ip = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)
+_d = ctypes.c_double
+# the same for the second harness (devphys.hip)
+PHYS_ENTRY_POINTS = {
+    "dp_sizeof_epoch": [], "dp_epoch_inputs": [], "dp_power_fields": [], "dp_mf_fields": [],
+    "dp_hod_fields": [], "dp_nfw_fields": [],
+    "dp_epoch_field_names": [], "dp_epoch_offsets": [_ip],
+    "dp_epoch": [_p, _v],
+    "dp_scalars": [_v, _p, _p, _i, _p],
+    "dp_power": [_v, _p, _i, _p],
+    "dp_sigma": [_v, _d, _p, _i, _p, _p],
+    "dp_mf": [_v, _p, _p, _i, _p],
+    "dp_hod": [_v, _p, _i, _p],
+    "dp_nfw": [_v, _p, _p, _i, _p],
+    "dp_exclusion": [_p, _i, _p],
+    "dp_e0_de": [_v, _p, _p, _i, _p, _i, _p, _p],
+    "dp_linspace": [_p, _p, _p, _p, _i, _d, _d, _p],
+}
+ALL_ENTRY_POINTS = {"devcheck": ENTRY_POINTS, "devphys": PHYS_ENTRY_POINTS}
 # dc_quad shapes
 SHAPE = {"group1": 0, "group2": 1, "group4": 2, "group8": 3, "group16": 4,
          "group1_nf2": 5, "group4_nf2": 6, "group4_unroll4": 7, "group4_fast4": 8,
@@ -57,44 +113,59 @@ def have_hipcc():
     return os.path.exists(hipcc())
 
 
-def source_hash():
+def source_hash(harness="devcheck"):
+    H = HARNESSES[harness]
     h = hashlib.sha256()
     h.update(repr(flags()).encode())
-    for path in [SRC] + HEADERS:
+    for path in [H.src] + H.headers:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()
 
 
-def build(force=False):
-    """Compile the harness (no-op when it was built from exactly these sources and flags)."""
-    want = source_hash()
-    if not force and os.path.exists(SO):
+def build(force=False, harness="devcheck"):
+    """Compile one harness (no-op when it was built from exactly these sources and flags)."""
+    H = HARNESSES[harness]
+    want = source_hash(harness)
+    if not force and os.path.exists(H.so):
         try:
-            with open(HASH) as f:
+            with open(H.hash) as f:
                 if f.read().strip() == want:
-                    return SO
+                    return H.so
         except OSError:
             pass
-    tmp = SO + ".tmp%d" % os.getpid()
-    subprocess.check_call([hipcc()] + flags() + ["-shared", "-o", tmp, SRC], cwd=DIR)
-    os.replace(tmp, SO)
-    with open(HASH, "w") as f:
+    tmp = H.so + ".tmp%d" % os.getpid()
+    subprocess.check_call([hipcc()] + flags() + ["-shared", "-o", tmp, H.src], cwd=DIR)
+    os.replace(tmp, H.so)
+    with open(H.hash, "w") as f:
         f.write(want + "\n")
-    return SO
+    return H.so
 
 
-def load():
-    """Build if necessary and load the harness, on the process's one HIP runtime."""
-    path = build()
+VOID = {"devcheck": ("dc_fma_k_constants", "dc_gl16"), "devphys": ("dp_epoch_offsets",)}
+
+
+def load(harness="devcheck"):
+    """Build if necessary and load one harness, on the process's one HIP runtime."""
+    path = build(harness=harness)
     _lib._preload_hip_runtime()
     L = ctypes.CDLL(path)
-    for name, argtypes in ENTRY_POINTS.items():
+    for name, argtypes in ALL_ENTRY_POINTS[harness].items():
         fn = getattr(L, name)           # AttributeError: the harness lacks an entry point
         fn.argtypes = argtypes
-        fn.restype = None if name in ("dc_fma_k_constants", "dc_gl16") else ctypes.c_int
+        fn.restype = None if name in VOID[harness] else ctypes.c_int
+    if harness == "devphys":
+        L.dp_epoch_field_names.restype = ctypes.c_char_p
     return L
+
+
+def epoch_fields(L):
+    """{field name: (byte offset, is_int)} of the Epoch fields the devphys harness lists."""
+    names = L.dp_epoch_field_names().decode().strip(",").split(",")
+    raw = (ctypes.c_int * (2 * len(names)))()
+    L.dp_epoch_offsets(raw)
+    return {nm: (raw[2 * j], bool(raw[2 * j + 1])) for j, nm in enumerate(names)}
 
 
 def ptr(a):

@@ -122,4 +122,23 @@ void hc_zheng(Epoch* e, const double* hod, const double* mass, int n, double* n1
   e->hod_M0 = pow(10.0, hod[2]); e->hod_M1p = pow(10.0, hod[3]);
   for (int i = 0; i < n; ++i) { n1[i] = zheng_first(*e, mass[i]); n2[i] = zheng_second(*e, mass[i]); }
 }
+// the three forms of the NFW transform on node fields given by the caller (what the device
+// harness formed), and the exclusion window: the host side of tests/test_gpu_devphys.py's
+// cancellation bounds.  out: [3][n]
+void hc_nfw_forms(const Epoch* e, const double* lnk, const double* lnm, int n, const double* ln_rs,
+                  const double* con, const double* ln_cp, const double* inv_mass_k,
+                  const double* rs, const double* inv_cprs, const double* k, const double* inv_k,
+                  double* out) {
+  init();
+  for (int i = 0; i < n; ++i) {
+    out[i] = y_nfw(*e, g_sici, lnk[i], lnm[i]);
+    out[n + i] = y_nfw_core(g_sici, lnk[i], ln_rs[i], con[i], ln_cp[i], inv_mass_k[i]);
+    out[2 * n + i] = y_nfw_core_tab(g_sici, lnk[i], k[i], inv_k[i], ln_rs[i], con[i], ln_cp[i],
+                                    inv_mass_k[i], rs[i], inv_cprs[i]);
+  }
+}
+void hc_exclusion(const double* kR, int n, double* out) {
+  init();
+  for (int i = 0; i < n; ++i) out[i] = exclusion_window(g_sici, kR[i]);
+}
 }

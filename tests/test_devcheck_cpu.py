@@ -1,9 +1,12 @@
-"""The device harness of the fp64 primitives and the wavefront Romberg (tests/devcheck) compiles
-for gfx950 against the current headers and exports every entry point the GPU tests
-(test_gpu_devmath.py, test_gpu_romberg.py) use.  No GPU is needed: hipcc cross-compiles.  This
+"""The device harnesses (tests/devcheck: devcheck.hip, the fp64 primitives and the wavefront
+Romberg; devphys.hip, the halo-model physics) compile for
+gfx950 against the current headers and export every entry point the GPU tests
+(test_gpu_devmath.py, test_gpu_romberg.py; test_gpu_devphys.py) use.  No GPU is needed: hipcc cross-compiles.  This
 keeps the harness from rotting when a header's signature changes in a change developed without
 a GPU."""
 import ctypes
+import os
+import re
 
 import pytest
 
@@ -27,3 +30,74 @@ def test_devcheck_compiles_and_exports():
     # the flags are the product's, not a copy
     from chomp_amd import _lib
     assert devcheck_build.flags() == _lib.HIPCC_FLAGS + _lib.NO_LICM
+
+
+@pytest.mark.skipif(not devcheck_build.have_hipcc(), reason="hipcc is not installed")
+def test_devphys_compiles_and_exports():
+    H = devcheck_build.HARNESSES["devphys"]
+    other = devcheck_build.HARNESSES["devcheck"]
+    devcheck_build.build()
+    stamp = os.stat(other.so).st_mtime_ns
+    path = devcheck_build.build(harness="devphys")
+    assert path == H.so != other.so
+    assert devcheck_build.build(harness="devphys") == path
+    assert os.stat(other.so).st_mtime_ns == stamp             # (the other harness: left alone)
+    with open(H.hash) as f:
+        assert f.read().strip() == devcheck_build.source_hash("devphys")
+    L = ctypes.CDLL(path)
+    for name in devcheck_build.PHYS_ENTRY_POINTS:
+        assert hasattr(L, name), name
+    # every entry point the GPU tests name is declared (and so exported, above)
+    here = os.path.dirname(os.path.abspath(__file__))
+    for test in ("test_gpu_devphys.py",):
+        with open(os.path.join(here, test)) as f:
+            named = set(re.findall(r"\b(dp_[a-z0-9_]+)\b", f.read()))
+        assert named, test
+        assert named <= set(devcheck_build.PHYS_ENTRY_POINTS), named
+    # the getters run on the host
+    L.dp_sizeof_epoch.restype = ctypes.c_int
+    L.dp_epoch_field_names.restype = ctypes.c_char_p
+    names = L.dp_epoch_field_names().decode().strip(",").split(",")
+    raw = (ctypes.c_int * (2 * len(names)))()
+    L.dp_epoch_offsets(raw)
+    size = L.dp_sizeof_epoch()
+    assert size % 16 == 0 and names[0] == "om0" and raw[0] == 0
+    assert all(0 <= raw[2 * j] <= size - (4 if raw[2 * j + 1] else 8) for j in range(len(names)))
+    assert len(set(raw[0::2])) == len(names)
+    assert raw[2 * names.index("mf_kind") + 1] == 1 and raw[2 * names.index("delta_c") + 1] == 0
+
+
+def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
+    """Each harness's hash covers the product headers it includes, transitively: devphys.hip
+    reaches chomp_math.h through chomp_cov_kernels.h, and a change in any header of that chain
+    changes its hash; a header only the second harness includes leaves the first one's alone."""
+    from chomp_amd import _lib
+    phys = devcheck_build.HARNESSES["devphys"].headers
+    base = [os.path.basename(p) for p in phys]
+    for need in ("chomp_cov_kernels.h", "chomp_proj_kernels.h", "chomp_power_kernels.h",
+                 "chomp_halo_kernels.h", "chomp_mass_kernels.h", "chomp_romberg.h",
+                 "chomp_math.h", "special_tables.h", "chomp_mi355x.h"):
+        assert need in base, need
+    first = [os.path.basename(p) for p in devcheck_build.HARNESSES["devcheck"].headers]
+    assert sorted(first) == ["chomp_math.h", "chomp_romberg.h", "special_tables.h"]
+    # a changed header (a scratch copy of the tree's csrc: no committed file is touched)
+    import shutil
+    root = tmp_path / "tree"
+    shutil.copytree(os.path.join(_lib.CSRC), root / "chomp_amd" / "csrc")
+    shutil.copytree(os.path.join(os.path.dirname(_lib.CSRC), "..", "include"), root / "include")
+    os.makedirs(root / "tests" / "devcheck")
+    for H in devcheck_build.HARNESSES.values():
+        shutil.copy(H.src, root / "tests" / "devcheck")
+    copies = {n: devcheck_build.Harness(n) for n in devcheck_build.HARNESSES}
+    for H in copies.values():
+        H.src = str(root / "tests" / "devcheck" / (H.name + ".hip"))
+    monkeypatch.setattr(devcheck_build, "HARNESSES", copies)
+    before = {n: devcheck_build.source_hash(n) for n in copies}
+    with open(root / "chomp_amd" / "csrc" / "chomp_cov_kernels.h", "a") as f:
+        f.write("// changed\n")
+    after = {n: devcheck_build.source_hash(n) for n in copies}
+    assert after["devphys"] != before["devphys"] and after["devcheck"] == before["devcheck"]
+    with open(root / "chomp_amd" / "csrc" / "chomp_math.h", "a") as f:
+        f.write("// changed\n")
+    last = {n: devcheck_build.source_hash(n) for n in copies}
+    assert last["devphys"] != after["devphys"] and last["devcheck"] != after["devcheck"]
