@@ -141,6 +141,8 @@ EXPORTS = [
     "chomp_tri_triple",
     "chomp_kernel_ng_setup", "chomp_kernel_ng_raw", "chomp_kernel_ng_eval",
     "chomp_covariance_ng",
+    "chomp_set_general_profile", "chomp_y_general", "chomp_y_general_table",
+    "chomp_halo_normalization",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
@@ -408,6 +410,10 @@ def lib():
         L.chomp_hod_stats.argtypes = [vp, sz, sz, c_double_p]
         L.chomp_set_transfer.argtypes = [vp, i]
         L.chomp_set_dark_energy.argtypes = [vp, i]
+        L.chomp_set_general_profile.argtypes = [vp, i]
+        L.chomp_y_general.argtypes = [vp, sz, d, vp, sz, vp]
+        L.chomp_y_general_table.argtypes = [vp, sz, vp, vp]
+        L.chomp_halo_normalization.argtypes = [vp, sz, vp, sz, vp]
         L.chomp_get_de_table.argtypes = [vp, i, sz, i, c_double_p, sz]
         L.chomp_set_second_order.argtypes = [vp, i]
         L.chomp_get_second_order.argtypes = [vp, sz, c_double_p, sz]
@@ -669,15 +675,19 @@ class Context(object):
         assert len(arr) == self.n_epoch
         self._check(self._L.chomp_mass_setup(self._h, arr, int(mf_kind)))
 
-    def halo_setup(self, profile, hods, tables):
+    def halo_setup(self, profile, hods, tables, general_profile=False):
+        """general_profile: accept halo dictionaries with alpha != -1 (chomp_set_general_profile);
+        off, they raise ChompScopeError."""
+        self._check(self._L.chomp_set_general_profile(self._h, 1 if general_profile else 0))
         n = self.n_epoch
         pa = profile if isinstance(profile, ctypes.Array) else self.pack_halo(profile, n)
         ha = hods if isinstance(hods, ctypes.Array) else self.pack_hod(hods, n)
         assert len(pa) == n and len(ha) == n
         self._check(self._L.chomp_halo_setup_hod(self._h, pa, ha, int(tables)))
 
-    def stage_k(self, mass_halo, mf_kind, profile, hods, tables):
+    def stage_k(self, mass_halo, mf_kind, profile, hods, tables, general_profile=False):
         """mass_setup + halo_setup in one call (chomp_stage_k)."""
+        self._check(self._L.chomp_set_general_profile(self._h, 1 if general_profile else 0))
         n = self.n_epoch
         ma = mass_halo if isinstance(mass_halo, ctypes.Array) else self.pack_halo(mass_halo, n)
         pa = profile if isinstance(profile, ctypes.Array) else self.pack_halo(profile, n)
@@ -686,8 +696,9 @@ class Context(object):
         self._check(self._L.chomp_stage_k_hod(self._h, ma, int(mf_kind), pa, ha, int(tables)))
 
     def stage_k_halofit(self, mass_halo, mf_kind, profile, hods, tables, epoch, f1, f2, f3,
-                        omega_l, w):
+                        omega_l, w, general_profile=False):
         """stage_k + halofit_setup(epoch, epoch, ...) in one call (chomp_stage_k_halofit)."""
+        self._check(self._L.chomp_set_general_profile(self._h, 1 if general_profile else 0))
         n = self.n_epoch
         ma = mass_halo if isinstance(mass_halo, ctypes.Array) else self.pack_halo(mass_halo, n)
         pa = profile if isinstance(profile, ctypes.Array) else self.pack_halo(profile, n)
@@ -859,6 +870,29 @@ class Context(object):
                                       numpy.asarray(mass, dtype=numpy.float64))
         return self._run(self._L.chomp_y_nfw, [a, b],
                          lambda mem, new, a, b: (epoch, a, b, a.size, new(a.size)))[0]
+
+    def y_general(self, epoch, ln_k, mass):
+        """Halo.y_general at one scalar ln k (chomp_y_general): the table of y over the mass knots
+        is integrated at that ln k, splined in ln M and evaluated at `mass` (0 outside the mass
+        table)."""
+        m = numpy.atleast_1d(numpy.asarray(mass, dtype=numpy.float64))
+        return self._run(self._L.chomp_y_general, [m],
+                         lambda mem, new, m: (epoch, float(ln_k), m, m.size, new(m.shape)))[0]
+
+    def y_general_table(self, epoch=0):
+        """(y[k][M], Romberg levels) of the epoch's general-profile table (chomp_y_general_table),
+        each [halo_npoints, mass_npoints].  Synchronises."""
+        shape = (self.config.halo_npoints, self.config.mass_npoints)
+        y, lev = numpy.empty(shape), numpy.empty(shape)
+        self._check(self._L.chomp_y_general_table(self._h, epoch, ctypes.c_void_p(y.ctypes.data),
+                                                  ctypes.c_void_p(lev.ctypes.data)))
+        return y, lev
+
+    def halo_normalization(self, mass, epoch=0):
+        """Halo.halo_normalization (chomp_halo_normalization) at `mass`."""
+        m = numpy.atleast_1d(numpy.asarray(mass, dtype=numpy.float64))
+        return self._run(self._L.chomp_halo_normalization, [m],
+                         lambda mem, new, m: (epoch, m, m.size, new(m.shape)))[0]
 
     def scalars(self, epoch=0):
         out = numpy.empty(SC_COUNT)

@@ -28,6 +28,7 @@
 #include "chomp_de_kernels.h"
 #include "chomp_pt_kernels.h"
 #include "chomp_tri_kernels.h"
+#include "chomp_profile_kernels.h"
 
 using namespace chomp;
 
@@ -215,6 +216,15 @@ struct chomp_ctx {
   double* d_tri4 = nullptr;
   size_t cap_tri4 = 0;
   std::vector<char> tri4_built;
+  // General-slope halo profiles (chomp_set_general_profile): the switch, per epoch the y(k, M)
+  // table with its levels and splines (ProfLayout), and which epochs of the last halo set-up have
+  // one (prof_general: alpha != -1 in a set-up that took the general path)
+  int general_profile = 0;
+  ProfLayout PL;
+  double* d_prof = nullptr;
+  size_t cap_prof = 0;
+  std::vector<char> prof_general;
+  bool prof_built = false;         // ... and that set-up built knot tables (some family asked for)
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
   bool timing_valid = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -695,7 +705,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_stage_in, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4};
+                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4, ctx->d_prof};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -1005,6 +1015,12 @@ int chomp_set_dark_energy(chomp_ctx* ctx, int on) {
   return CHOMP_OK;
 }
 
+int chomp_set_general_profile(chomp_ctx* ctx, int on) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  ctx->general_profile = on != 0;
+  return CHOMP_OK;
+}
+
 int chomp_get_de_table(chomp_ctx* ctx, int source, size_t index, int what, double* out, size_t n) {
   if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "get_de_table: bad args");
   const int np = ctx->cfg.cosmo_npoints;
@@ -1064,6 +1080,7 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   ctx->have_halofit.assign(n_epoch, 0);
   ctx->tri_built.assign(n_epoch, 0);
   ctx->tri4_built.assign(n_epoch, 0);
+  ctx->prof_general.assign(n_epoch, 0);
   rc = upload(ctx, ctx->d_cosmo, cosmo, n_epoch * sizeof(chomp_cosmo), ctx->sh_cosmo);
   if (rc) return rc;
   rc = upload(ctx, ctx->d_z, z, n_epoch * sizeof(double), ctx->sh_z);
@@ -1182,6 +1199,7 @@ struct HaloPlan {
   int ng = 0;
   int want_nbar = 1;
   bool eval = false;     // some epoch's HOD has alpha != 1: the deep-level sums evaluate nodes
+  bool general = false;  // some epoch's profile has alpha != -1 (chomp_set_general_profile)
   bool has_hod() const {
     return group_hod(groups[0]) || group_hod(groups[1]) || group_hod(groups[2]) ||
            group_hod(groups[3]);
@@ -1211,11 +1229,20 @@ static_assert(PT_FS2 == CHOMP_PT_FS2 && PT_FS2_LEN == CHOMP_PT_FS2_LEN &&
 static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const chomp_hod_model* hod,
                         unsigned tables, HaloPlan* P) {
   const size_t n = ctx->n_epoch;
-  for (size_t i = 0; i < n; ++i)
-    if (profile[i].alpha != -1.0)
+  for (size_t i = 0; i < n; ++i) {
+    if (profile[i].alpha == -1.0) continue;
+    if (!ctx->general_profile)
       return fail(ctx, CHOMP_ERR_SCOPE,
                   "halo alpha != -1: the general-profile transform y_general "
-                  "(halo.py:491-559) is outside the hot-path scope (NFW only)");
+                  "(halo.py:491-559) is outside the hot-path scope (NFW only) unless "
+                  "chomp_set_general_profile(ctx, 1)");
+    // (the profile's mass integral, halo.py:887, diverges at the centre for alpha <= -3)
+    // (... and profile_mass_integral is validated to 1e-13 up to alpha = 3.5: the cancellation in
+    //  its second series grows with alpha, 7e-10 at alpha = 15.5)
+    if (!(profile[i].alpha > -3.0) || !(profile[i].alpha <= kProfileAlphaMax))
+      return fail(ctx, CHOMP_ERR_ARG, "halo_setup: alpha must lie in (-3, 3.5]");
+    P->general = true;
+  }
   for (size_t i = 0; i < n; ++i)
     if ((hod[i].kind != CHOMP_HOD_ZHENG && hod[i].kind != CHOMP_HOD_MANDELBAUM) ||
         hod[i].reserved != 0)
@@ -1485,6 +1512,53 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
   return CHOMP_OK;
 }
 
+// The halo set-up of a batch with some alpha != -1 (chomp_set_general_profile), behind the stage
+// that put the epochs' halo / HOD constants into their records: the y(k, M) tables and their
+// splines, the knot integrals with the literal integrands, the epochs' finalisation.  Every
+// epoch of the batch goes this way, those with alpha = -1 with y_nfw inline.
+static int launch_halo_general(chomp_ctx* ctx, const HaloPlan& P, const chomp_halo_par* profile) {
+  { const int rcm = mirror_next(ctx); if (rcm) return rcm; }
+  const size_t n = ctx->n_epoch;
+  const TabLayout& L = ctx->L;
+  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "halo_setup: at most 65535 epochs with a general profile");
+  ctx->PL = make_prof_layout(L.NM, L.NK);
+  const ProfLayout& PL = ctx->PL;
+  int rc = ensure(ctx, &ctx->d_prof, &ctx->cap_prof, n * (size_t)PL.stride);
+  if (rc) return rc;
+  if (P.fam) {                      // (a set-up for n_bar alone integrates no y)
+    hipLaunchKernelGGL(k_y_general_table, dim3((unsigned)L.NM, (unsigned)L.NK, (unsigned)n), dim3(64), 0,
+                       ctx->stream, ctx->cfg, L, PL, ctx->d_epochs, 0, ctx->d_tab, ctx->d_profile, 0, 0.0,
+                       1, ctx->d_prof, ctx->d_status);
+    hipLaunchKernelGGL(k_y_general_splines, dim3((unsigned)L.NK, (unsigned)n), dim3(64),
+                       (size_t)(11 * L.NM) * sizeof(double), ctx->stream, L, PL, 0, ctx->d_tab,
+                       ctx->d_profile, 0, 1, 0, ctx->d_prof);
+  }
+  const unsigned ng = (unsigned)(P.ng > 0 ? P.ng : 1);
+  hipLaunchKernelGGL(k_halo_knots_general, dim3((unsigned)n, (unsigned)L.NK + 1u, ng), dim3(256),
+                     (size_t)knots_general_lds_doubles(L.NM) * sizeof(double), ctx->stream, ctx->cfg, L,
+                     PL, ctx->d_epochs, ctx->d_tab, ctx->d_profile, ctx->d_hod, ctx->d_sici, ctx->d_prof,
+                     P.groups[0], P.groups[1], P.groups[2], P.groups[3], P.kmask, ctx->d_status);
+  hipLaunchKernelGGL(k_halo_finalize_general, dim3((unsigned)n), dim3(256),
+                     (size_t)finalize_lds_doubles(L.NK) * sizeof(double), ctx->stream, ctx->cfg, L,
+                     ctx->d_epochs, ctx->d_tab, P.fam, ctx->d_status);
+  HIPCHK(hipGetLastError());
+  for (size_t i = 0; i < n; ++i) ctx->prof_general[i] = profile[i].alpha != -1.0;
+  ctx->prof_built = P.fam != 0;
+  ctx->have_halo = true;
+  ctx->fam_mask |= P.fam;
+  ctx->status_mirrored = ctx->L.h_status != nullptr;
+  return CHOMP_OK;
+}
+
+// The plan of the stage in front of launch_halo_general: the epochs' constants and nothing else
+// (no integration group: no node tables).
+static HaloPlan constants_only(const HaloPlan& P) {
+  HaloPlan Q = P;
+  Q.ng = 0;
+  Q.groups[0] = Q.groups[1] = Q.groups[2] = Q.groups[3] = -1;
+  return Q;
+}
+
 int chomp_mass_setup(chomp_ctx* ctx, const chomp_halo_par* par, int mf_kind) {
   StageRange range_(ctx, "chomp:mass_setup (Stage K: nu table, mass function)");
   if (!ctx || !par) return fail(ctx, CHOMP_ERR_ARG, "mass_setup: bad args");
@@ -1514,6 +1588,14 @@ int chomp_halo_setup_hod(chomp_ctx* ctx, const chomp_halo_par* profile,
   const size_t n = ctx->n_epoch;
   const TabLayout& L = ctx->L;
   const size_t sh = (size_t)(L.NM + 8 * (L.NM - 1) + kKnotScratch) * sizeof(double);
+  if (P.general) {
+    hipLaunchKernelGGL(k_halo_nodes, dim3((unsigned)n, 1, 1), dim3(256), sh, ctx->stream, ctx->cfg, L,
+                       ctx->d_epochs, ctx->d_tab, ctx->d_profile, ctx->d_hod, ctx->d_sici,
+                       ctx->d_nodes, ctx->d_endp, -1, -1, -1, -1, 0u, ctx->d_status, ctx->d_npend,
+                       ctx->d_pending);
+    return launch_halo_general(ctx, P, profile);
+  }
+  std::fill(ctx->prof_general.begin(), ctx->prof_general.end(), 0);
   // (few epochs: the table's nodes over several blocks each)
   const unsigned ngy = (unsigned)(P.ng > 0 ? P.ng : 1);
   unsigned nchunks = (unsigned)(512 / (n * ngy));
@@ -1538,6 +1620,14 @@ int chomp_stage_k_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kin
   HaloPlan P;
   rc = halo_prepare(ctx, profile, hod, tables, &P);
   if (rc) return rc;
+  if (P.general) {
+    const HaloPlan Q = constants_only(P);
+    rc = launch_nu_mass(ctx, mf_kind, &Q);
+    if (rc) return rc;
+    ctx->have_mass = true;
+    return launch_halo_general(ctx, P, profile);
+  }
+  std::fill(ctx->prof_general.begin(), ctx->prof_general.end(), 0);
   rc = launch_nu_mass(ctx, mf_kind, &P);
   if (rc) return rc;
   ctx->have_mass = true;
@@ -1911,6 +2001,84 @@ int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k, const double* 
   return st.finish();
 }
 
+// The context's general-profile buffer for the current batch (a set-up with alpha != -1 has made
+// it; an NFW-only one has not).
+static int ensure_prof(chomp_ctx* ctx) {
+  ctx->PL = make_prof_layout(ctx->L.NM, ctx->L.NK);
+  return ensure(ctx, &ctx->d_prof, &ctx->cap_prof, ctx->n_epoch * (size_t)ctx->PL.stride);
+}
+
+int chomp_y_general(chomp_ctx* ctx, size_t epoch, double ln_k, const double* mass, size_t n,
+                    double* out) {
+  if (!ctx || !mass || !out || n == 0 || n > (size_t)INT32_MAX)
+    return fail(ctx, CHOMP_ERR_ARG, "y_general: bad args");
+  if (!ctx->have_halo || epoch >= ctx->n_epoch) return fail(ctx, CHOMP_ERR_STATE, "y_general before halo_setup");
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = ensure_prof(ctx);
+  if (rc) return rc;
+  Staging st(ctx, CHOMP_HOST, "y_general");
+  const double* d_mass;
+  double* d_out;
+  st.in(mass, n, &d_mass);
+  st.out(out, n, &d_out);
+  rc = st.place();
+  if (rc) return rc;
+  const TabLayout& L = ctx->L;
+  const ProfLayout& PL = ctx->PL;
+  // (the table of _initialize_y_spline at this ln k -- the epoch's scratch row -- and its spline)
+  hipLaunchKernelGGL(k_y_general_table, dim3((unsigned)L.NM, 1, 1), dim3(64), 0, ctx->stream, ctx->cfg,
+                     L, PL, ctx->d_epochs, (int)epoch, ctx->d_tab, ctx->d_profile, L.NK, ln_k, 0,
+                     ctx->d_prof, ctx->d_status);
+  hipLaunchKernelGGL(k_y_general_splines, dim3(1, 1), dim3(64), (size_t)(11 * L.NM) * sizeof(double),
+                     ctx->stream, L, PL, (int)epoch, ctx->d_tab, ctx->d_profile, L.NK, 0, 0, ctx->d_prof);
+  hipLaunchKernelGGL(k_y_general_eval, grid_1d(n), dim3(256), (size_t)(5 * L.NM - 4) * sizeof(double),
+                     ctx->stream, L, PL, ctx->d_epochs, (int)epoch, ctx->d_tab, ctx->d_prof, L.NK,
+                     d_mass, (int)n, d_out);
+  return st.finish();
+}
+
+int chomp_y_general_table(chomp_ctx* ctx, size_t epoch, double* out_y, double* out_level) {
+  if (!ctx || (!out_y && !out_level)) return fail(ctx, CHOMP_ERR_ARG, "y_general_table: bad args");
+  if (!ctx->have_halo || epoch >= ctx->n_epoch || !ctx->prof_general[epoch] || !ctx->prof_built)
+    return fail(ctx, CHOMP_ERR_STATE, "y_general_table: the last halo set-up built no general-profile "
+                                      "table for this epoch (alpha = -1, or no chomp_set_general_profile)");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const ProfLayout& PL = ctx->PL;
+  const size_t nn = (size_t)PL.NK * PL.NM;
+  const double* b = ctx->d_prof + epoch * (size_t)PL.stride;
+  if (out_y) HIPCHK(hipMemcpy(out_y, b + PL.off_y, nn * sizeof(double), hipMemcpyDeviceToHost));
+  if (out_level) HIPCHK(hipMemcpy(out_level, b + PL.off_level, nn * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
+int chomp_halo_normalization(chomp_ctx* ctx, size_t epoch, const double* mass, size_t n, double* out) {
+  if (!ctx || !mass || !out || n == 0 || n > (size_t)INT32_MAX)
+    return fail(ctx, CHOMP_ERR_ARG, "halo_normalization: bad args");
+  if (!ctx->have_halo || epoch >= ctx->n_epoch)
+    return fail(ctx, CHOMP_ERR_STATE, "halo_normalization before halo_setup");
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = ensure_prof(ctx);
+  if (rc) return rc;
+  Staging st(ctx, CHOMP_HOST, "halo_normalization");
+  const double* d_mass;
+  double* d_out;
+  st.in(mass, n, &d_mass);
+  st.out(out, n, &d_out);
+  rc = st.place();
+  if (rc) return rc;
+  const TabLayout& L = ctx->L;
+  const ProfLayout& PL = ctx->PL;
+  hipLaunchKernelGGL(k_halo_normalization_knots, dim3(1), dim3(64), 0, ctx->stream, L, PL, ctx->d_epochs,
+                     (int)epoch, ctx->d_tab, ctx->d_profile, ctx->d_prof);
+  hipLaunchKernelGGL(k_y_general_splines, dim3(1, 1), dim3(64), (size_t)(11 * L.NM) * sizeof(double),
+                     ctx->stream, L, PL, (int)epoch, ctx->d_tab, ctx->d_profile, 0, 0, 1, ctx->d_prof);
+  hipLaunchKernelGGL(k_halo_normalization_eval, grid_1d(n), dim3(256),
+                     (size_t)(5 * L.NM - 4) * sizeof(double), ctx->stream, L, PL, (int)epoch, ctx->d_tab,
+                     ctx->d_prof, d_mass, (int)n, d_out);
+  return st.finish();
+}
+
 int chomp_eval(chomp_ctx* ctx, size_t epoch, int what, const double* x, size_t n, double* out,
                int mem) {
   if (!ctx || !x || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "eval: bad args");
@@ -2017,12 +2185,22 @@ static bool tri_moment_ok(int moment) { return moment >= CHOMP_TRI_MMMM && momen
 
 // Replaces _initialize_i_0_4 (halo_trispectrum.py:104-129): the 1275 i_0_4 calls of its loop
 // (:60-95, one scipy Romberg each) and the RectBivariateSpline fit, for a range of epochs.
+// The trispectrum tables integrate y_nfw at k that are no knots of the halo tables: an epoch whose
+// last halo set-up had alpha != -1 is outside their scope.
+static int nfw_only(chomp_ctx* ctx, size_t epoch0, size_t n, const char* who) {
+  for (size_t e = epoch0; e < epoch0 + n && e < ctx->prof_general.size(); ++e)
+    if (ctx->prof_general[e])
+      return fail(ctx, CHOMP_ERR_SCOPE, std::string(who) + ": halo alpha != -1 (NFW only)");
+  return CHOMP_OK;
+}
+
 int chomp_tri1h_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, int moment,
                       double* table_out, double* levels_out) {
   StageRange range_(ctx, "chomp:tri1h_setup");
   if (!ctx || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: bad args");
   if (!tri_moment_ok(moment)) return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: unknown moment");
   if (!ctx->have_halo) return fail(ctx, CHOMP_ERR_STATE, "tri1h_setup before a halo set-up");
+  { const int rcs = nfw_only(ctx, epoch0, n_epoch, "tri1h_setup"); if (rcs) return rcs; }
   if (epoch0 + n_epoch > ctx->n_epoch || n_epoch > 65535)
     return fail(ctx, CHOMP_ERR_ARG, "tri1h_setup: epoch range");
   const int N = ctx->L.NK;
@@ -2101,6 +2279,7 @@ int chomp_tri1h_quad(chomp_ctx* ctx, size_t epoch, int moment, const double* k, 
   if (st.rc) return st.rc;
   if (!ctx->have_halo || epoch >= ctx->n_epoch)
     return fail(ctx, CHOMP_ERR_STATE, "tri1h_quad before a halo set-up of this epoch");
+  { const int rcs = nfw_only(ctx, epoch, 1, "tri1h_quad"); if (rcs) return rcs; }
   const size_t nb = (n + kTriQuadWaves - 1) / kTriQuadWaves;
   if (nb > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "tri1h_quad: too many quadruples");
   HIPCHK(hipSetDevice(ctx->device));
@@ -2128,6 +2307,7 @@ int chomp_tri_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, double* table
   StageRange range_(ctx, "chomp:tri_setup");
   if (!ctx || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "tri_setup: bad args");
   if (!ctx->have_halo) return fail(ctx, CHOMP_ERR_STATE, "tri_setup before a halo set-up");
+  { const int rcs = nfw_only(ctx, epoch0, n_epoch, "tri_setup"); if (rcs) return rcs; }
   if (!ctx->have_b2)
     return fail(ctx, CHOMP_ERR_STATE, "tri_setup: the last mass set-up was not second-order "
                                       "(chomp_set_second_order)");

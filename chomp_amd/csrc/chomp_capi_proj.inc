@@ -57,7 +57,9 @@ int chomp_stage_k_halofit_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, in
   HaloPlan P;
   rc = halo_prepare(ctx, profile, hod, tables, &P);
   if (rc) return rc;
-  rc = launch_nu_mass(ctx, mf_kind, &P);
+  const HaloPlan Q = P.general ? constants_only(P) : P;
+  if (!P.general) std::fill(ctx->prof_general.begin(), ctx->prof_general.end(), 0);
+  rc = launch_nu_mass(ctx, mf_kind, &Q);
   if (rc) return rc;
   ctx->have_mass = true;
   bool forked = false;
@@ -68,7 +70,7 @@ int chomp_stage_k_halofit_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, in
     forked = side.on();
     rc = halofit_launch(ctx, epoch, epoch, f_1, f_2, f_3, omega_l, w);
   }
-  const int rck = rc ? rc : launch_halo_knots(ctx, P);
+  const int rck = rc ? rc : (P.general ? launch_halo_general(ctx, P, profile) : launch_halo_knots(ctx, P));
   if (forked) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_side_done, 0));
   return rck;
 }

@@ -1230,4 +1230,84 @@ CHOMP_HD void halo_constants(Epoch& e, double c0_in, double beta, double delta_v
   e.ln_c_const = log(e.c0) - e.beta * log(e.m_star);
 }
 
+// ---------------------------------------------------------------------------
+// General inner slope, halo_dict["alpha"] != -1: rho(x) ~ x^alpha (1 + x)^-(3 + alpha), x = r / r_s
+// (halo.py:491-559, 880-897).
+// ---------------------------------------------------------------------------
+// sum_{n >= 0} v^(a + n) / (a + n) = int_0^v t^(a - 1) / (1 - t) dt for 0 <= v <= 1/2, a > 0.
+CHOMP_HD double profile_mass_head(double a, double v) {
+  double sum = 0.0, p = 1.0;
+  for (int n = 0; n < 400; ++n) {
+    const double t = p / (a + (double)n);
+    sum += t;
+    if (t < 1e-17 * sum) break;
+    p *= v;
+  }
+  return pow(v, a) * sum;
+}
+
+// int_0^c x^(2 + alpha) (1 + x)^-(3 + alpha) dx = c^a / a 2F1(a, a; a + 1; -c), a = 3 + alpha > 0
+// (the reference's rho_norm, halo.py:893-895).  With u = x / (1 + x) (Pfaff's transformation) it is
+// int_0^(c / (1 + c)) u^(a - 1) / (1 - u) du: the series above up to u = 1/2 and, beyond, with
+// s = 1 - u and (1 - s)^(a - 1) expanded about s = 0,
+//   ln((1 + c) / 2) + sum_{n >= 1} B_n (2^-n - s_c^n) / n,  B_n = prod_{j <= n} (j - a) / j,
+// s_c = 1 / (1 + c).  Both series gain a binary digit per term whatever c is (about 55 terms each;
+// B_n ends by itself for integer a: alpha = -1 gives ln(1 + c) - c / (1 + c)).
+// Validated against the 2F1 form to 1e-13 relative for -3 < alpha <= kProfileAlphaMax and
+// 0.5 <= c <= 1e4 (worst 1.1e-14, at alpha = 3.5); the second series alternates for a > 1 and its
+// cancellation grows with a (9e-14 at alpha = 5.5, 7e-10 at 15.5), so the set-ups refuse more.
+constexpr double kProfileAlphaMax = 3.5;
+CHOMP_HD double profile_mass_integral(double alpha, double c) {
+  const double a = 3.0 + alpha;
+  const double u = c / (1.0 + c);
+  if (u <= 0.5) return profile_mass_head(a, u);
+  const double sc = 1.0 / (1.0 + c);
+  double sum = 0.0, B = 1.0, ph = 1.0, ps = 1.0;
+  for (int n = 1; n < 400; ++n) {
+    B *= ((double)n - a) / (double)n;
+    ph *= 0.5;
+    ps *= sc;
+    sum += B * (ph - ps) / (double)n;
+    if (B == 0.0 || (n > 4 && fabs(B) * ph / (double)n < 1e-17 * fabs(sum))) break;
+  }
+  return profile_mass_head(a, 0.5) + log(0.5 * (1.0 + c)) + sum;
+}
+
+// Halo._halo_normalization (halo.py:880-897): rho_s / rho_norm for concentration con.
+CHOMP_HD double halo_normalization(double rho_bar, double delta_v, double alpha, double con) {
+  const double rho_s = (rho_bar * delta_v * con * con * con) / 3.0;
+  return rho_s / profile_mass_integral(alpha, con);
+}
+
+// numpy.sinc(t) = sin(pi t) / (pi t), the argument multiplied as numpy does.
+CHOMP_HD double sinc_numpy(double t) {
+  const double y = kPi * (t == 0.0 ? 1.0e-20 : t);
+  return sin(y) / y;
+}
+
+// Halo._y_integrand (halo.py:531-541) at x = r / r_s with the reference's operation order:
+// norm x^2 [x^alpha / (1 + x)^(3 + alpha)] sinc(k r / pi), r = x r_vir / c.
+struct YGeneralIntegrand {
+  double alpha, k, r_vir, con, norm;
+  CHOMP_HD double operator()(double x) const {
+    const double r = x * r_vir / con;
+    const double prof = pow(x, alpha) / pow(1.0 + x, 3.0 + alpha);
+    return norm * (x * x) * prof * sinc_numpy(k * r / kPi);
+  }
+};
+
+// The normalisation of _initialize_y_spline (halo.py:512-517): one over the integrand at x = 1,
+// or at x = 1 + pi / 4 where the sinc at x = 1 vanishes.
+CHOMP_HD double y_general_norm(double alpha, double k, double r_vir, double con) {
+  const YGeneralIntegrand f{alpha, k, r_vir, con, 1.0};
+  if (fabs(sinc_numpy(k * r_vir / (con * kPi))) <= 1e-16) return 1.0 / f(1.0 + kPi / 4.0);
+  return 1.0 / f(1.0);
+}
+
+// The factor that turns the Romberg value into the table entry (halo.py:524-525).
+CHOMP_HD double y_general_scale(double r_vir, double con, double halo_norm, double mass) {
+  const double rs = r_vir / con;
+  return 4.0 * kPi * (rs * rs * rs) * halo_norm / mass;
+}
+
 }  // namespace chomp

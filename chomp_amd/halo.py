@@ -41,7 +41,8 @@ class Halo(object):
     """Seljak (2000) halo model (halo.py:23-1086)."""
 
     def __init__(self, redshift=0.0, input_hod=None, cosmo_single_epoch=None,
-                 mass_func=None, halo_dict=None, extrapolate=False, **kws):
+                 mass_func=None, halo_dict=None, extrapolate=False, general_profile=False,
+                 **kws):
         self._k_min = defaults.default_limits['k_min']
         self._k_max = defaults.default_limits['k_max']
         self._ln_k_max = numpy.log(self._k_max)
@@ -63,10 +64,18 @@ class Halo(object):
         self.c0 = halo_dict["c0"] / (1.0 + self._redshift)
         self.beta = halo_dict["beta"]
         self.alpha = halo_dict["alpha"]
+        # general_profile: the opt-in for alpha != -1 (y_general, halo.py:491-559): the table of
+        # y over the mass knots integrated on the device for every ln k knot
+        # (chomp_set_general_profile); without it such a dictionary stays a scope error
+        self._general_profile = bool(general_profile)
         if self.alpha != -1.0:
-            raise _lib.ChompScopeError(
-                "halo alpha != -1 (y_general, halo.py:491-559) is outside the "
-                "hot-path scope: NFW only")
+            if not self._general_profile:
+                raise _lib.ChompScopeError(
+                    "halo alpha != -1 (y_general, halo.py:491-559) is outside the "
+                    "hot-path scope: NFW only (pass general_profile=True)")
+            if not -3.0 < self.alpha <= 3.5:
+                raise ValueError("halo alpha must lie in (-3, 3.5]: the profile's mass diverges "
+                                 "at -3, and its integral is validated up to 3.5")
         self._h = self.cosmo._h
         if input_hod is None:
             input_hod = hod.HODZheng()
@@ -95,6 +104,11 @@ class Halo(object):
         # (halo.py:151-153) but c0/beta stay with the splines built at __init__ /
         # set_cosmology from self.halo_dict as well; set_halo changes neither.
         return self._profile_dict
+
+    def _profile_kw(self):
+        """The set-ups' keyword of an object that opted in to alpha != -1 (none otherwise: the
+        call is the one an NFW object has always made)."""
+        return {"general_profile": True} if self._general_profile else {}
 
     _status_pending = False
     _status_word = 0
@@ -161,7 +175,7 @@ class Halo(object):
                 self._stage_k(ctx, tables)
                 self._mass_sig = msig
             else:
-                ctx.halo_setup(self._profile(), self.local_hod, tables)
+                ctx.halo_setup(self._profile(), self.local_hod, tables, **self._profile_kw())
             for flag, bit in self._flag_bits:
                 if build & bit:
                     setattr(self, flag, True)
@@ -173,7 +187,8 @@ class Halo(object):
         return ctx
 
     def _stage_k(self, ctx, tables):
-        ctx.stage_k(self.mass.halo_dict, self.mass._kind, self._profile(), self.local_hod, tables)
+        ctx.stage_k(self.mass.halo_dict, self.mass._kind, self._profile(), self.local_hod, tables,
+                    **self._profile_kw())
 
     def _before_epochs_set(self):
         pass
@@ -268,10 +283,12 @@ class Halo(object):
         return self.halo_dict
 
     def set_halo(self, halo_dict=None):
-        """halo.py:220-235: only the mass function sees the new dictionary."""
+        """halo.py:220-235: only the mass function sees the new dictionary -- and the profile is
+        NFW from here on, whatever the dictionary's alpha (:231)."""
         self.c0 = halo_dict["c0"] / (1.0 + self._redshift)
         self.beta = halo_dict["beta"]
         self.alpha = -1.0
+        self._profile_dict = dict(self._profile_dict, alpha=-1.0)
         self.mass.set_halo(halo_dict)
         self.set_hod_object(self.local_hod)
 
@@ -306,12 +323,27 @@ class Halo(object):
     def concentration(self, mass):
         return self._sync(0).eval("concentration", mass)
 
+    def halo_normalization(self, mass):
+        """halo.py:465-474, for the profile of the last set-up (after set_halo: NFW's)."""
+        m = numpy.asarray(mass, dtype=numpy.float64)
+        return self._sync(0).halo_normalization(m.ravel()).reshape(m.shape)
+
     def y(self, ln_k, mass):
+        """halo.py:476-489."""
+        if self.alpha == -1.0:
+            return self.y_nfw(ln_k, mass)
+        return self.y_general(ln_k, mass)
+
+    def y_general(self, ln_k, mass):
+        """halo.py:491-498: one scalar ln k (the reference compares it with the ln k of its last
+        table), any masses; 0 outside the mass table."""
+        m = numpy.asarray(mass, dtype=numpy.float64)
+        return self._sync(0).y_general(0, float(ln_k), m.ravel()).reshape(m.shape)
+
+    def y_nfw(self, ln_k, mass):
         m = numpy.asarray(mass, dtype=numpy.float64)
         out = self._sync(0).y_nfw(0, ln_k, m)
         return out.reshape(numpy.broadcast(numpy.asarray(ln_k), m).shape)
-
-    y_nfw = y
 
     # knot accessors (the reference's *_spline evaluated inside [k_min, k_max])
     def _knots(self, name, need):
@@ -455,7 +487,8 @@ class HaloSuperSampleCovariance(Halo):
         halo_ssc = HaloSuperSampleCovariance(
             input_halo.get_redshift(), input_halo.get_hod_object(),
             input_halo.get_cosmology_object(), input_halo.get_mass(),
-            input_halo.get_halo(), input_halo.get_extrapolation(), delta_b)
+            input_halo.get_halo(), input_halo.get_extrapolation(), delta_b,
+            general_profile=getattr(input_halo, "_general_profile", False))
         for flag, bit in _FLAG_BITS:
             if getattr(input_halo, flag) is True:
                 name = flag[len("_initialized_"):]
@@ -503,9 +536,9 @@ class HaloFit(Halo):
     """HALOFIT with the Takahashi et al. 2012 coefficients (halo.py:1236-1412)."""
 
     def __init__(self, redshift=0.0, input_hod=None, cosmo_single_epoch=None,
-                 mass_func=None, halo_dict=None, **kws):
+                 mass_func=None, halo_dict=None, general_profile=False, **kws):
         Halo.__init__(self, redshift, input_hod, cosmo_single_epoch, mass_func,
-                      halo_dict)
+                      halo_dict, general_profile=general_profile)
         self._initialize_halo_fit()
         self._initialized_sigma_spline = False
         self._hf_coef = None
@@ -547,7 +580,7 @@ class HaloFit(Halo):
             return Halo._stage_k(self, ctx, tables)
         ctx.stage_k_halofit(self.mass.halo_dict, self.mass._kind, self._profile(), self.local_hod,
                             tables, 0, float(self._f_1), float(self._f_2), float(self._f_3),
-                            float(self._omega_l), float(self._w))
+                            float(self._omega_l), float(self._w), **self._profile_kw())
         self._hf_coef = None
         self._initialized_sigma_spline = True
 

@@ -139,7 +139,9 @@ class SimulationDesign(object):
         # point-by-point loop, which reproduces that.
         return (type(obj) is halo_mod.Halo and self._method in _BATCHED_METHODS and
                 self._ind_var is not None and not self._vary_halo and
-                not obj.get_extrapolation())
+                not obj.get_extrapolation() and
+                # (HaloGrid batches NFW epochs: a general-profile object keeps the loop)
+                not getattr(obj, "_general_profile", False))
 
     def _run_batched(self):
         """Every design point = one epoch of one HaloGrid."""

@@ -828,6 +828,40 @@ int chomp_set_dark_energy(chomp_ctx* ctx, int on);
 #define CHOMP_DE_PP 4
 int chomp_get_de_table(chomp_ctx* ctx, int source, size_t index, int what, double* out, size_t n);
 
+/* Halo profiles with a general inner slope, halo_dict["alpha"] != -1 (y_general,
+ * halo.py:491-559), opt-in: with `on` set the halo set-ups (chomp_halo_setup*, chomp_stage_k*)
+ * accept alpha != -1 (off, the default: they refuse it with CHOMP_ERR_SCOPE) in (-3, 3.5]: alpha <= -3,
+ * where the profile's mass diverges, and alpha > 3.5, beyond which the profile's mass integral is
+ * not validated to 1e-13, are CHOMP_ERR_ARG.  For every ln k knot of the halo tables the
+ * library then tabulates y(k, M) at the mass_npoints mass knots -- one integral of
+ * x^(2 + alpha) (1 + x)^-(3 + alpha) sinc(k r_s x / pi) over [1e-8, c] each, scipy's Romberg rule
+ * with rtol = halo_precision, normalised as the reference normalises it -- splines it in ln M and
+ * integrates h_m .. pp_gg, I_1^2 and n_bar with that spline (zero outside the mass table) in
+ * place of the NFW transform.  The knot tables land where the NFW ones do: chomp_power, the
+ * projections and everything else that reads P(k) run unchanged.
+ * A set-up whose epochs all have alpha = -1 takes exactly the launches (and gives the bits) it
+ * takes with the switch off.  A set-up with ANY alpha != -1 takes the general path for all its
+ * epochs, those with alpha = -1 with the NFW transform inline: their tables agree with the NFW
+ * path's to the last digits, not bit for bit.  A y(k, M) integral that exhausts divmax raises
+ * CHOMP_ST_HALO_DIVMAX_H_M.  The trispectrum set-ups (chomp_tri1h_setup, chomp_tri1h_quad,
+ * chomp_tri_setup) keep refusing an epoch with alpha != -1 (CHOMP_ERR_SCOPE). */
+int chomp_set_general_profile(chomp_ctx* ctx, int on);
+/* Halo.y_general(ln_k, mass) of one epoch at ONE ln k (any value) and n masses (host): the
+ * table of y over the mass knots is integrated at that ln k with the alpha of the epoch's last
+ * halo set-up (alpha = -1 included: the Romberg value, not the closed form), splined in ln M and
+ * evaluated; 0 outside [mass_min, mass_max] of the mass table (halo.py:496-498). */
+int chomp_y_general(chomp_ctx* ctx, size_t epoch, double ln_k, const double* mass, size_t n,
+                    double* out);
+/* The y(k, M) table of one epoch as the last general-profile set-up built it, and the Romberg
+ * level of each of its integrals: halo_npoints x mass_npoints doubles each, ln k slowest (either
+ * pointer may be NULL).  Host buffers; synchronises.  CHOMP_ERR_STATE for an epoch without one. */
+int chomp_y_general_table(chomp_ctx* ctx, size_t epoch, double* out_y, double* out_level);
+/* Halo.halo_normalization(mass) (halo.py:465-474, 880-897) of one epoch at n masses (host): exp
+ * of the not-a-knot spline over ln M of ln(rho_s / rho_norm) at the mass knots, for the alpha of
+ * the epoch's last halo set-up (any alpha > -3, -1 included). */
+int chomp_halo_normalization(chomp_ctx* ctx, size_t epoch, const double* mass, size_t n,
+                             double* out);
+
 /* Halo.calculate_bias / calculate_m_eff / calculate_f_sat (halo.py:709-838) of epochs
  * [epoch0, epoch0 + n): out[3 i + {0, 1, 2}] = effective bias, effective halo mass,
  * satellite fraction (host buffer), each with the epoch's HOD model.  Needs chomp_halo_setup
