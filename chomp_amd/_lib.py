@@ -127,6 +127,8 @@ EXPORTS = [
     "chomp_set_precision", "chomp_xi3d", "chomp_spline_eval", "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
     "chomp_covariance_table", "chomp_covariance_gaussian",
+    "chomp_covariance_cross_stage", "chomp_covariance_table_cross",
+    "chomp_covariance_gaussian_cross",
     "chomp_set_timing", "chomp_get_timing", "chomp_get_status", "chomp_status_post",
     "chomp_status_wait", "chomp_set_tuning",
     "chomp_get_deep_stats", "chomp_stage_k", "chomp_power_plan", "chomp_get_stream",
@@ -436,6 +438,10 @@ def lib():
         L.chomp_covariance_table.argtypes = [vp, i, sz, d, c_double_p, c_double_p,
                                              c_double_p, sz]
         L.chomp_covariance_gaussian.argtypes = [vp, d, d, d, d, vp, sz, vp, i]
+        L.chomp_covariance_cross_stage.argtypes = [vp, i, vp, i, sz]
+        L.chomp_covariance_table_cross.argtypes = [vp, d, d, c_double_p, c_double_p,
+                                                   c_double_p, sz]
+        L.chomp_covariance_gaussian_cross.argtypes = [vp, d, d, d, d, d, d, vp, sz, vp, i]
         L.chomp_kernel_ssc_setup.argtypes = [vp, d, d, d, c_double_p, c_double_p, sz, i,
                                              c_double_p, c_double_p, c_double_p]
         L.chomp_kernel_ssc_raw.argtypes = [vp, vp, sz, vp]
@@ -1129,6 +1135,35 @@ class Context(object):
                          lambda mem, new, th: (float(j0_limit), float(area), float(poisson_a),
                                                float(poisson_b), th, th.size // 2,
                                                new(th.size // 2), mem))[0]
+
+    def covariance_cross_stage(self, slot, src, which, epoch=0):
+        """Snapshot of one side of a cross block into this context (slot 0: correlation a, 1: b):
+        the projection set-up and spectrum `which` of halo epoch `epoch` of context `src`."""
+        self._check(self._L.chomp_covariance_cross_stage(self._h, int(slot), src._h, int(which),
+                                                         epoch))
+
+    def covariance_table_cross(self, D_a, D_b):
+        """(ln_K [kernel_npoints], the projected spectra a, b, ab, ba [4, kernel_npoints], their
+        Romberg levels [4, kernel_npoints]) of the two staged sides."""
+        n = self.config.kernel_npoints
+        ln_K, tab, lev = numpy.empty(n), numpy.empty((4, n)), numpy.empty((4, n))
+        self._check(self._L.chomp_covariance_table_cross(
+            self._h, float(D_a), float(D_b), ln_K.ctypes.data_as(c_double_p),
+            tab.ctypes.data_as(c_double_p), lev.ctypes.data_as(c_double_p), n))
+        return ln_K, tab, lev.astype(int)
+
+    def covariance_gaussian_cross(self, j0_limit, area, poisson, theta_a, theta_b=None):
+        """covariance_G of a cross block for pairs of bin centres.  poisson: the four
+        proj_power_poisson(window_pair = 0..3).  (theta_a, theta_b): host arrays of one length;
+        or theta_a alone, a contiguous float64 torch cuda tensor holding theta_a[n] then
+        theta_b[n], which stays on the device (so does the result)."""
+        pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
+        p = [float(v) for v in poisson]
+        assert len(p) == 4
+        return self._run(self._L.chomp_covariance_gaussian_cross, [pairs],
+                         lambda mem, new, th: (float(j0_limit), float(area), p[0], p[1], p[2],
+                                               p[3], th, _numel(th) // 2,
+                                               new(_numel(th) // 2), mem))[0]
 
     def kernel_ssc_setup(self, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi, sigma2,
                          with_table=True):

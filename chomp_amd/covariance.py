@@ -1,6 +1,6 @@
-"""covariance.Covariance for the Gaussian, super-sample and one-halo trispectrum parts of the
-w(theta) covariance (covariance.py:23-793, 1085-1103), the consumer of P(k) and the windows
-that SURVEY.md 8(f) ranks fourth.
+"""covariance.Covariance and CovarianceMulti for the Gaussian, super-sample and one-halo
+trispectrum parts of the w(theta) covariance (covariance.py:23-871, 1085-1103), the consumer of
+P(k) and the windows that SURVEY.md 8(f) ranks fourth.
 
 Accelerated: ``Covariance(corr, corr, nongaussian_cov=False)`` -- the use of
 examples/example_covariance_script.py: the projected spectrum over ln K
@@ -14,11 +14,21 @@ one-halo trispectrum term: ``KernelCovariance.kernel_NG`` (kernel.py:996-1073, 1
 ``covariance_NG`` (covariance.py:593-683) for every pair of bins in one call.  The object has
 to be given: the reference never moves its default HaloTrispectrumOneHalo() off z = 0 (the
 set_redshift(z_bar_NG) lines are commented out), so the redshift, the HOD and power_spec of the
-trispectrum are the caller's choice.  Outside the scope (ChompScopeError): ``nongaussian_cov=True``
-without such an object, the full ``HaloTrispectrum``, ``CovarianceMulti`` and
-``CovarianceFourier``.  Two different correlation objects cannot be given to the
-reference's Covariance either (its constructor raises ValueError comparing them), so that
-branch is not built.
+trispectrum are the caller's choice.
+
+``Covariance(corr_a, corr_b, nongaussian_cov=False)`` with two different correlations is the
+Gaussian cross-covariance of two measurements (the matching_corrs == False branch,
+covariance.py:422-453, 495-541): four projected spectra a, b, ab, ba on one ln K grid and
+``covariance_G`` with two two-point terms, all pairs of bins in one launch; no Poisson term on the
+diagonal (:312).  The reference's constructor cannot get there as shipped -- it compares the two
+correlations with Correlation.__eq__ (correlation.py:119-131), which raises ValueError on the
+numpy arrays in their dictionaries -- but with that one comparison answered (two objects: not
+equal) the branch runs, and that is what is reproduced.  ``CovarianceMulti`` (covariance.py:796-871)
+assembles the joint matrix of several correlations from such blocks.
+
+Outside the scope (ChompScopeError): ``nongaussian_cov=True`` without a HaloTrispectrumOneHalo,
+the full ``HaloTrispectrum``, the trispectrum and super-sample terms of a cross block, and
+``CovarianceFourier``.
 """
 import numpy
 from scipy import special
@@ -52,7 +62,8 @@ class KernelCovariance(object):
     ``trispectrum_kernel=True``, the trispectrum kernel (kernel / kernel_NG / raw_kernel /
     raw_kernel_NG); without it those four raise ChompScopeError.
 
-    Both kernels are built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over --
+    Both kernels are built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over; a
+    cross block, Covariance(corr_a, corr_b), holds four windows and uses neither --
     on the device context of ``_ssc_context`` (Covariance points it at its halo copy's, so
     the response and the table meet there) or else on a context of its own."""
 
@@ -249,6 +260,9 @@ class Covariance(object):
                  n_a=1.0e4, n_b=1.0e4, variance=1.0, nongaussian_cov=True,
                  input_halo_trispectrum=None, power_spec='power_mm',
                  poisson_noise_only=False, ssc_cov=False, **kws):
+        cross = input_correlation_a is not input_correlation_b
+        if cross:
+            self._check_cross(input_correlation_a, input_correlation_b, nongaussian_cov, ssc_cov)
         if nongaussian_cov and input_halo_trispectrum is None:
             raise _lib.ChompScopeError(
                 "the trispectrum term of the covariance (covariance_NG) is built for an explicit "
@@ -265,17 +279,6 @@ class Covariance(object):
                 "the trispectrum term of the covariance is accelerated for a halo_trispectrum."
                 "HaloTrispectrumOneHalo, not %s (HaloTrispectrum, the two- to four-halo terms, "
                 "is outside the scope)" % type(input_halo_trispectrum).__name__)
-        if input_correlation_a is not input_correlation_b:
-            # The reference cannot get here either: covariance.py:60 compares the two
-            # correlations with Correlation.__eq__ (correlation.py:119-131), which compares
-            # their attribute dictionaries -- numpy arrays included -- and raises
-            # "ValueError: The truth value of an array ... is ambiguous" for two different
-            # objects.  The four-spectra branch (covariance.py:497-532) is dead code as shipped.
-            raise _lib.ChompScopeError(
-                "Covariance of two different correlation objects: the reference raises "
-                "ValueError at covariance.py:60 for them (Correlation.__eq__ compares numpy "
-                "arrays); only Covariance(corr, corr) can run there, and that is what is "
-                "accelerated")
         self.annular_bins = []
         self.log_theta_min = input_correlation_a.log_theta_min
         self.log_theta_max = input_correlation_a.log_theta_max
@@ -284,7 +287,11 @@ class Covariance(object):
         self.bins_per_decade = bins_per_decade
         self.corr_a = input_correlation_a
         self.corr_b = input_correlation_b
-        self.matching_corrs = True
+        # covariance.py:61-64.  Correlation.__eq__ (correlation.py:119-131) compares attribute
+        # dictionaries -- numpy arrays included -- and raises "ValueError: The truth value of an
+        # array ... is ambiguous" for two different objects; it can return True only for one
+        # object given twice.  For two objects the answer it could not give is False.
+        self.matching_corrs = not cross
         while theta < numpy.power(10.0, self.log_theta_max):
             if (theta >= numpy.power(10.0, self.log_theta_min) and
                     theta < numpy.power(10.0, self.log_theta_max)):
@@ -308,18 +315,22 @@ class Covariance(object):
         self.poisson_noise_only = poisson_noise_only
 
         kern = input_correlation_a.kernel
+        kern_b = input_correlation_b.kernel
         self.kernel = KernelCovariance(
             numpy.power(10.0, self.log_theta_min) * defaults.default_limits["k_min"],
             numpy.power(10.0, self.log_theta_max) * defaults.default_limits["k_max"],
             kern.window_function_a, kern.window_function_b,
-            kern.window_function_a, kern.window_function_b, kern.cosmo,
+            kern_b.window_function_a, kern_b.window_function_b, kern.cosmo,
             trispectrum_kernel=self.nongaussian_cov)
         # covariance.py:108-115.  The reference's Kernel holds *copies* of its two
         # windows, each with a private copy of the MultiEpoch, and WindowFunction.__eq__
         # (kernel.py:248-259) compares those by identity: two windows are "equal" only
         # when they are the same object.  With one correlation given twice that is the
         # case for the pairs (a1, b1) and (a2, b2) and for no other, whatever the windows.
-        self.equal_windows = [False, False, False, False, True, True]
+        # Two correlations hold those same objects only when they share their Kernel: the
+        # windows of two Kernels are different copies even when made from one window.
+        same = kern is kern_b
+        self.equal_windows = [False, False, False, False, same, same]
         self.density = [self.n_a1 / self.area, self.n_a2 / self.area,
                         self.n_b1 / self.area, self.n_b2 / self.area,
                         self.n_a1 / self.area, self.n_a2 / self.area]
@@ -349,11 +360,38 @@ class Covariance(object):
             0, defaults.default_precision["kernel_bessel_limit"])[-1]
         if power_spec is None:
             power_spec = 'linear_power'
-        if power_spec not in _POWER or not hasattr(self.halo_a, power_spec):
+        if (power_spec not in _POWER or not hasattr(self.halo_a, power_spec) or
+                not hasattr(self.halo_b, power_spec)):
             print("WARNING: Invalid input for power spectra variable,")
             print("\t setting to linear_power")
             power_spec = 'linear_power'
         self.power_spec = power_spec
+
+    @staticmethod
+    def _check_cross(corr_a, corr_b, nongaussian_cov, ssc_cov):
+        """The limits of a cross block, Covariance(corr_a, corr_b) of two different objects."""
+        if nongaussian_cov or ssc_cov:
+            raise _lib.ChompScopeError(
+                "Covariance of two different correlation objects is accelerated for its Gaussian "
+                "term only: the trispectrum and super-sample terms of a cross block are outside "
+                "the scope -- pass nongaussian_cov=False (and leave ssc_cov=False)")
+        for corr in (corr_a, corr_b):
+            if not isinstance(corr.halo, halo_mod.Halo):
+                # (the two sides are staged from their halos' device contexts)
+                raise _lib.ChompScopeError(
+                    "Covariance of two different correlation objects needs a chomp_amd halo.Halo "
+                    "(or a subclass) behind each of them, not %s" % type(corr.halo).__name__)
+        cos_a, cos_b = corr_a.kernel.cosmo, corr_b.kernel.cosmo
+        if sorted(cos_a.cosmo_dict.items()) != sorted(cos_b.cosmo_dict.items()):
+            raise _lib.ChompScopeError(
+                "Covariance of two correlations whose MultiEpoch cosmologies differ: distances "
+                "and growth are taken from correlation a's alone (covariance.py:93-102), which "
+                "has no meaning for b's windows; give both one cosmology")
+        names = [getattr(c, "_power_name", None) for c in (corr_a, corr_b)]
+        if None not in names and names[0] != names[1]:
+            raise _lib.ChompScopeError(
+                "Covariance of two correlations with different power_spec (%s, %s): one "
+                "spectrum name serves both halos (covariance.py:551-586)" % tuple(names))
 
     def _identify_cosmic_shear(self):
         shear = [isinstance(w, kernel_mod.WindowFunctionConvergence) for w in (
@@ -398,17 +436,90 @@ class Covariance(object):
             self._initialized_halo_splines = True
         return ctx
 
+    @staticmethod
+    def _halo_signature(h):
+        """Everything a halo's spectrum is built from, readable without the device."""
+        hod = h.get_hod_object()
+        return (id(h), type(h).__name__, tuple(sorted(h.cosmo.cosmo_dict.items())),
+                h.cosmo._redshift, bool(getattr(h.cosmo, "_with_bao", False)),
+                tuple(sorted(h.mass.halo_dict.items())), h.mass._kind, type(hod),
+                tuple(getattr(hod, a, None) for a in ("log_M_min", "sigma", "log_M_0",
+                                                      "log_M_1p", "alpha", "w")),
+                repr(sorted(h._profile_dict.items())), h.get_extrapolation())
+
+    def _table_cross(self):
+        """The four projected spectra a, b, ab, ba of a cross block over one ln K grid
+        (covariance.py:455-543, matching_corrs == False), in the device context of correlation
+        a's halo; rebuilt when anything they were built from has changed.
+
+        Each side is set up where it lives -- its Kernel and its halo at its own z_bar, in its
+        halo's context -- and a snapshot of it is staged into a's context, so neither two
+        Halo objects nor one shared by both correlations have to hold two set-ups at once.  When
+        ``corr_a.halo is corr_b.halo`` the reference's two set_redshift calls (:465-466) leave
+        that one object at z_bar_b: both spectra are then P at z_bar_b, here as there."""
+        ca, cb = self.corr_a, self.corr_b
+        ha, hb = self.halo_a, self.halo_b
+        z_a, z_b = ca.kernel.z_bar, cb.kernel.z_bar
+        if ha is not hb:
+            ha.set_redshift(z_a)
+        hb.set_redshift(z_b)
+        ctx = ha._context()
+        key = (id(ctx), self.power_spec, ca.kernel._signature(), cb.kernel._signature(),
+               z_a, z_b, self._halo_signature(ha), self._halo_signature(hb))
+        if (key != self._table_key or not self._initialized_halo_splines or
+                getattr(ctx, "_cov_cross_owner", None) is not self):
+            self._z_bar_G_a, self._z_bar_G_b = z_a, z_b
+            # covariance.py:468-469: both from correlation a's MultiEpoch
+            self._D_z_a = ca._growth_at_z_bar()
+            self._D_z_b = float(ca.kernel.cosmo.growth_factor(z_b))
+            ctx_a, code_a = ca._prepare(self.power_spec)
+            ctx.covariance_cross_stage(0, ctx_a, code_a)
+            ctx_b, code_b = cb._prepare(self.power_spec)
+            ctx.covariance_cross_stage(1, ctx_b, code_b)
+            self._ln_K_array, tab, lev = ctx.covariance_table_cross(self._D_z_a, self._D_z_b)
+            (self._halo_a_array, self._halo_b_array, self._halo_ab_array,
+             self._halo_ba_array) = tab
+            (self._halo_a_levels, self._halo_b_levels, self._halo_ab_levels,
+             self._halo_ba_levels) = lev
+            self._ln_K_min, self._ln_K_max = self._ln_K_array[0], self._ln_K_array[-1]
+            self._table_key = key
+            self._initialized_halo_splines = True
+            ctx._cov_cross_owner = self
+        return ctx
+
+    def _tables(self):
+        return self._table() if self.matching_corrs else self._table_cross()
+
     def _initialize_halo_splines(self):
         self._initialized_halo_splines = False
-        self._table()
+        self._tables()
+
+    def _projected(self, name, K):
+        ctx = self._tables()
+        return ctx.spline_eval(self._ln_K_array, getattr(self, "_halo_%s_array" % name),
+                               numpy.log(K))
 
     def _projected_halo_a(self, K):
-        ctx = self._table()
-        return ctx.spline_eval(self._ln_K_array, self._halo_a_array, numpy.log(K))
+        return self._projected("a", K)
 
-    _projected_halo_b = _projected_halo_a
+    def _projected_halo_b(self, K):
+        """covariance.py:215-224: a's spline for one correlation given twice."""
+        return self._projected("a" if self.matching_corrs else "b", K)
+
+    def _projected_halo_ab(self, K):
+        return self._projected("ab", K)
+
+    def _projected_halo_ba(self, K):
+        return self._projected("ba", K)
 
     def set_cosmology(self, cosmo_dict):
+        if not self.matching_corrs:
+            # (the reference would go on with the KernelCovariance, its chi limits and the
+            #  halo objects of the old cosmology in part: covariance.py:252-270)
+            raise _lib.ChompScopeError(
+                "Covariance.set_cosmology on a cross covariance (two different correlation "
+                "objects) is outside the scope: set the cosmology of both correlations and "
+                "build a new Covariance")
         if self.ssc_cov:
             # The reference ends in AttributeError here whatever ssc_cov is
             # (HaloTrispectrumOneHalo.set_cosmology dereferences pert=None); with ssc_cov it
@@ -453,8 +564,9 @@ class Covariance(object):
                 vals = vals + self._covariance_ssc_pairs(centers[iu[0]], centers[iu[1]])
             self.covar[iu] = vals
             self.covar[(iu[1], iu[0])] = vals
-        for i, b in enumerate(self.annular_bins):
-            self.covar[i, i] += self.covariance_P(b.delta, b.center)
+        if self.matching_corrs:                              # covariance.py:312
+            for i, b in enumerate(self.annular_bins):
+                self.covar[i, i] += self.covariance_P(b.delta, b.center)
         return self.covar
 
     def covariance(self, annular_bin_a, annular_bin_b):
@@ -488,6 +600,11 @@ class Covariance(object):
         return 0.0
 
     def _covariance_G_pairs(self, theta_a, theta_b):
+        if not self.matching_corrs:
+            ctx = self._table_cross()
+            return ctx.covariance_gaussian_cross(
+                self._j0_limit, self.area, [self.proj_power_poisson(p) for p in range(4)],
+                theta_a, theta_b)
         ctx = self._table()
         return ctx.covariance_gaussian(self._j0_limit, self.area,
                                        self.proj_power_poisson(0),
@@ -552,6 +669,48 @@ class Covariance(object):
                     f.writelines('%1.16f %1.16f %1.16f\n' % (
                         bin_a.center * rad_to_deg, bin_b.center * rad_to_deg,
                         self.covar[idx_a, idx_b]))
+
+
+class CovarianceMulti(Covariance):
+    """covariance.py:796-871: the joint covariance of several correlations, one Covariance per
+    pair (i <= j) in ``covariance_list[i][j - i]``, assembled into ``wcovar`` by
+    ``get_covariance``.  Every block owns its tables.  With more than one correlation the
+    off-diagonal blocks are cross-covariances, Gaussian term only: pass nongaussian_cov=False
+    (the default, True, is the reference's, and raises ChompScopeError for them)."""
+
+    def __init__(self, correlation_object_list, bins_per_decade=5,
+                 survey_area_deg2=4 * numpy.pi * strad_to_deg2,
+                 n_a=1e6, n_b=1e6, variance=1.0, nongaussian_cov=True,
+                 input_halo_trispectrum=None, poisson_noise_only=False, **kws):
+        self.covariance_list = []
+        n = len(correlation_object_list)
+        for idx1 in range(n):
+            row = []
+            for idx2 in range(idx1, n):
+                row.append(Covariance(
+                    input_correlation_a=correlation_object_list[idx1],
+                    input_correlation_b=correlation_object_list[idx2],
+                    bins_per_decade=bins_per_decade, survey_area_deg2=survey_area_deg2,
+                    n_a=n_a, n_b=n_b, variance=variance, nongaussian_cov=nongaussian_cov,
+                    input_halo_trispectrum=input_halo_trispectrum,
+                    poisson_noise_only=poisson_noise_only))
+            self.covariance_list.append(row)
+        self.annular_bins = self.covariance_list[0][0].annular_bins
+        self.theta_bins = len(self.annular_bins)
+        self.wcovar = numpy.empty((self.theta_bins * n, self.theta_bins * n))
+
+    def get_covariance(self):
+        """covariance.py:854-871: block (i, j) and its mirror both receive the block's covar."""
+        for idx1, row in enumerate(self.covariance_list):
+            for idx2, cov in enumerate(row):
+                cov.get_covariance()
+                row_ndx1 = idx1 * self.theta_bins
+                row_ndx2 = row_ndx1 + self.theta_bins
+                col_ndx1 = (idx1 + idx2) * self.theta_bins
+                col_ndx2 = col_ndx1 + self.theta_bins
+                self.wcovar[row_ndx1:row_ndx2, col_ndx1:col_ndx2] = cov.covar
+                self.wcovar[col_ndx1:col_ndx2, row_ndx1:row_ndx2] = cov.covar
+        return self.wcovar
 
 
 class FiniteAreaEffect(object):

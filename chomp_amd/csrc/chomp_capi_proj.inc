@@ -740,6 +740,120 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area, doub
 }
 
 // ---------------------------------------------------------------------------
+// Gaussian cross-covariance of two w(theta): Covariance(corr_a, corr_b)
+// ---------------------------------------------------------------------------
+int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int which,
+                                 size_t epoch) {
+  if (!ctx || !src) return fail(ctx, CHOMP_ERR_ARG, "covariance_cross_stage: bad args");
+  if (slot < 0 || slot > 1) return fail(ctx, CHOMP_ERR_ARG, "covariance_cross_stage: slot must be 0 or 1");
+  if (!src->proj.ready)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_cross_stage: the source context has no kernel_setup");
+  { const int rcp = check_power(src, which, epoch, 1); if (rcp) return fail(ctx, rcp, "covariance_cross_stage: source: " + src->err); }
+  if (src->device != ctx->device)
+    return fail(ctx, CHOMP_ERR_SCOPE, "covariance_cross_stage: both contexts must be on one device");
+  if (std::memcmp(&src->cfg, &ctx->cfg, sizeof(chomp_config)) != 0 || src->with_bao != ctx->with_bao)
+    return fail(ctx, CHOMP_ERR_SCOPE, "covariance_cross_stage: both contexts must share one "
+                                      "configuration and transfer function");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(src); if (rcj) return fail(ctx, rcj, "covariance_cross_stage: source: " + src->err); }
+  { const int rce = prepare_extrapolation(src, which, epoch, 1); if (rce) return fail(ctx, rce, "covariance_cross_stage: source: " + src->err); }
+  // (another context's stream is not ordered against this one: wait for what it holds before
+  //  the copies, and for the copies before it may rewrite what they read)
+  if (src != ctx) HIPCHK(hipStreamSynchronize(src->stream));
+  CrossState& X = ctx->cross;
+  const ProjLayout& L = src->proj.L;
+  const CrossLayout C = make_cross_layout(L.NKT, src->L.stride, L.total);
+  if (!X.d || X.C.total != C.total || X.C.htab[1] != C.htab[1] || X.C.ln_K != C.ln_K)
+    X.staged[0] = X.staged[1] = false;                   // (another layout: both sides again)
+  { const double* before = X.d;
+    const int rce = ensure(ctx, &X.d, &X.cap, (size_t)C.total); if (rce) return rce;
+    if (X.d != before) X.staged[0] = X.staged[1] = false; }
+  X.C = C;
+  X.ready = false;
+  X.staged[slot] = false;
+  const auto copy = [&](int off, const void* from, size_t doubles) {
+    return hipMemcpyAsync(X.d + off, from, doubles * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+  };
+  HIPCHK(copy(C.ep[slot], src->d_epochs + epoch, kEpochDoubles));
+  HIPCHK(copy(C.htab[slot], src->d_tab + epoch * (size_t)src->L.stride, (size_t)src->L.stride));
+  HIPCHK(copy(C.pd[slot], src->proj.d_pd, kProjDoubles));
+  HIPCHK(copy(C.ptab[slot], src->proj.d_tab, (size_t)L.total));
+  if (src != ctx) HIPCHK(hipStreamSynchronize(ctx->stream));
+  X.staged[slot] = true;
+  X.which[slot] = which;
+  return CHOMP_OK;
+}
+
+int chomp_covariance_table_cross(chomp_ctx* ctx, double D_a, double D_b, double* ln_K,
+                                 double* tables, double* levels, size_t n) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  CrossState& X = ctx->cross;
+  if (!X.staged[0] || !X.staged[1])
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_table_cross before covariance_cross_stage of both slots");
+  if (!(D_a > 0.0) || !(D_b > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_table_cross: D_a, D_b");
+  const chomp_config& c = ctx->cfg;
+  const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
+  const CrossLayout& C = X.C;
+  if (C.pd[0] - C.htab[0] != ctx->L.stride || C.N != L.NKT)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_table_cross: the snapshots are of another configuration");
+  if ((ln_K || tables || levels) && n != (size_t)C.N)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_table_cross: length must be kernel_npoints");
+  HIPCHK(hipSetDevice(ctx->device));
+  X.ready = false;
+  const size_t sh = (size_t)cov_cross_lds_doubles(ctx->L.NK, L) * sizeof(double);
+  if (sh > 64 * 1024)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_table_cross: halo/cosmo/window_npoints too large for "
+                                    "the two spectra and four windows of a cross block");
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_cov_cross_knots<BAO>, dim3((unsigned)C.N, 4), dim3(256), sh, ctx->stream,
+                       c, ctx->L, L, C, X.which[0], X.which[1], D_a, D_b, X.d);
+  });
+  hipLaunchKernelGGL(k_cov_cross_spline, dim3(4), dim3(64), 0, ctx->stream, C, X.d);
+  HIPCHK(hipGetLastError());
+  X.ready = true;
+  if (ln_K || tables || levels) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t b = (size_t)C.N * sizeof(double);
+    if (ln_K) HIPCHK(hipMemcpy(ln_K, X.d + C.ln_K, b, hipMemcpyDeviceToHost));
+    for (int t = 0; t < 4; ++t) {
+      if (tables) HIPCHK(hipMemcpy(tables + (size_t)t * C.N, X.d + C.proj[t], b, hipMemcpyDeviceToHost));
+      if (levels) HIPCHK(hipMemcpy(levels + (size_t)t * C.N, X.d + C.lev[t], b, hipMemcpyDeviceToHost));
+    }
+  }
+  return CHOMP_OK;
+}
+
+int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area,
+                                    double poisson_0, double poisson_1, double poisson_2,
+                                    double poisson_3, const double* theta, size_t n, double* out,
+                                    int mem) {
+  if (!ctx || !theta || !out || n == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian_cross: bad args");
+  Staging st(ctx, mem, "covariance_gaussian_cross");
+  if (st.rc) return st.rc;
+  if (!ctx->cross.ready)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_gaussian_cross before covariance_table_cross");
+  if (!(j0_limit > 0.0) || !(area > 0.0))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian_cross: j0_limit and area must be positive");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (st.host)
+    for (size_t i = 0; i < 2 * n; ++i)
+      if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian_cross: theta must be positive");
+  const double* d_theta;
+  double* d_out;
+  st.in(theta, 2 * n, &d_theta);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
+  const CrossLayout& C = ctx->cross.C;
+  const size_t sh = (size_t)(C.N + 16 * (C.N - 1)) * sizeof(double);
+  hipLaunchKernelGGL(k_cov_cross_gaussian, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+                     C, ctx->cross.d, ctx->d_j0, j0_limit, area, poisson_0, poisson_1, poisson_2,
+                     poisson_3, d_theta, d_theta + n, d_out, (double*)nullptr);
+  return st.finish();
+}
+
+// ---------------------------------------------------------------------------
 // Super-sample covariance of w(theta) (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
 int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,

@@ -2025,4 +2025,251 @@ __global__ __launch_bounds__(256) void k_cov_gaussian(chomp_config cfg, CovLayou
   }
 }
 
+// ---------------------------------------------------------------------------
+// Gaussian cross-covariance of two w(theta): Covariance(corr_a, corr_b), the matching_corrs ==
+// False branch (covariance.py:422-453, 495-541)
+// ---------------------------------------------------------------------------
+// A cross block needs two projection set-ups (four windows) and two P(k) epochs at once, and a
+// context holds one of each: the block's context keeps a snapshot ("slot") of each side --
+// slot 0 correlation a, slot 1 correlation b -- taken from whichever context holds that side
+// (chomp_covariance_cross_stage): the epoch record, the epoch's knot tables, the projection
+// scalars and the projection tables.  Behind the slots: ln K knots | the four projected spectra
+// a, b, ab, ba | their splines | their Romberg levels | scalars {ln_K_min, ln_K_max, D_a, D_b,
+// chi_peak_a, chi_peak_b} | spline_build's work, per table.
+constexpr int kCrossA = 0, kCrossB = 1, kCrossAB = 2, kCrossBA = 3;
+struct CrossLayout {
+  int N, ep[2], htab[2], pd[2], ptab[2];
+  int ln_K, proj[4], pp[4], lev[4], scal, work[4], total;
+};
+inline CrossLayout make_cross_layout(int N, int h_stride, int p_total) {
+  CrossLayout C;
+  C.N = N;
+  int o = 0;
+  for (int s = 0; s < 2; ++s) {
+    C.ep[s] = o; o += kEpochDoubles;
+    C.htab[s] = o; o += h_stride;
+    C.pd[s] = o; o += kProjDoubles;
+    C.ptab[s] = o; o += p_total;
+    o = (o + 1) & ~1;
+  }
+  C.ln_K = o; o += N;
+  for (int t = 0; t < 4; ++t) {
+    C.proj[t] = o; o += N;
+    C.pp[t] = o; o += 4 * (N - 1);
+    C.lev[t] = o; o += N;
+    C.work[t] = o; o += 2 * N;
+  }
+  C.scal = o; o += 8;
+  C.total = (o + 7) & ~7;
+  return C;
+}
+struct CrossState {
+  double* d = nullptr;     // the block of CrossLayout
+  size_t cap = 0;          // doubles allocated at d
+  CrossLayout C;
+  bool staged[2] = {false, false};   // slot holds a snapshot (chomp_covariance_cross_stage)
+  int which[2] = {0, 0};   // ... of this spectrum
+  bool ready = false;      // the four tables and their splines (chomp_covariance_table_cross) valid
+};
+// Dynamic LDS of k_cov_cross_knots, in doubles: two PowerEval stagings, the MultiEpoch of
+// ProjLds and four window splines.
+inline int cov_cross_lds_doubles(int NK_halo, const ProjLayout& L) {
+  return 24 * (NK_halo - 1) + L.NC + 8 * (L.NC - 1) + 16 * (L.NWp - 1);
+}
+
+// covariance.py:545-591 with kernel.py:1075-1101: the integrand of table T.  a and b take their
+// own spectrum, ab and ba the geometric mean of the two; the windows are (a1, a2), (b1, b2),
+// (a1, b2), (a2, b1); the growth factor and z(chi) are those of correlation a's MultiEpoch
+// (Covariance.kernel.cosmo) throughout.  The end-point guard is CovProjIntegrand's.
+template <bool BAO>
+struct CovCrossIntegrand {
+  const PowerEval *Pa, *Pb;
+  const MEView* me;
+  const WindowView* w;             // a1, a2, b1, b2
+  int T;
+  double K, norm;
+  __device__ __forceinline__ double operator()(double chi) const {
+    const double D = me->growth_factor(me->redshift(chi));
+    double k = K / chi;
+    if (k > Pa->k_max && k <= Pa->k_max * (1.0 + 8.9e-16)) k = Pa->k_max;
+    double power, ww;
+    if (T == kCrossA) {
+      power = Pa->template eval_t<BAO>(k);
+      ww = w[0](chi) * w[1](chi);
+    } else if (T == kCrossB) {
+      power = Pb->template eval_t<BAO>(k);
+      ww = w[2](chi) * w[3](chi);
+    } else {
+      power = sqrt(Pa->template eval_t<BAO>(k) * Pb->template eval_t<BAO>(k));
+      ww = T == kCrossAB ? w[0](chi) * w[3](chi) : w[1](chi) * w[2](chi);
+    }
+    return norm * power * (ww * D * D / (chi * chi));
+  }
+};
+
+// grid (N = kernel_npoints, 4 tables), block 256: knot x of table y of
+// Covariance._initialize_halo_splines (covariance.py:455-531).  LDS: cov_cross_lds_doubles.
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_cov_cross_knots(chomp_config cfg, TabLayout HL,
+                                                         ProjLayout L, CrossLayout C, int which_a,
+                                                         int which_b, double D_a, double D_b,
+                                                         double* __restrict__ ct) {
+  extern __shared__ __align__(16) double sm[];
+  __shared__ Epoch Ea, Eb;
+  __shared__ ProjDev pda, pdb;
+  __shared__ double red[romberg_scratch<4, 2>()];
+  __shared__ double sc[4];         // chi_peak_a, chi_peak_b, chi_min_b, chi_max_b
+  copy_doubles(reinterpret_cast<double*>(&Ea), ct + C.ep[0], kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&Eb), ct + C.ep[1], kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pda), ct + C.pd[0], kProjDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pdb), ct + C.pd[1], kProjDoubles);
+  __syncthreads();
+  PowerEval Pa, Pb;
+  Pa.stage(cfg, HL, &Ea, ct + C.htab[0], which_a, sm);
+  Pb.stage(cfg, HL, &Eb, ct + C.htab[1], which_b, sm + 12 * (HL.NK - 1));
+  const int NC = L.NC, NW = L.NWp;
+  double* chi_t = sm + 24 * (HL.NK - 1);                // [NC]
+  double* pp_z = chi_t + NC;                            // [4 (NC - 1)]
+  double* pp_g = pp_z + 4 * (NC - 1);
+  double* wpp = pp_g + 4 * (NC - 1);                    // 4 x [4 (NW - 1)]
+  const double* pta = ct + C.ptab[0];
+  const double* ptb = ct + C.ptab[1];
+  copy_doubles(chi_t, pta + L.me_chi[0], NC);
+  copy_doubles(pp_z, pta + L.me_pp_z[0], 4 * (NC - 1));
+  copy_doubles(pp_g, pta + L.me_pp_g[0], 4 * (NC - 1));
+  for (int q = 0; q < 4; ++q)
+    copy_doubles(wpp + q * 4 * (NW - 1), (q < 2 ? pta : ptb) + L.w_pp[q & 1], 4 * (NW - 1));
+  const MEView me{nullptr, chi_t, nullptr, pp_z, pp_g, NC, pda.me_z_min[0], pda.me_z_max[0]};
+  WindowView w[4];
+  for (int q = 0; q < 4; ++q) {
+    const ProjDev& pd = q < 2 ? pda : pdb;
+    w[q] = WindowView{wpp + q * 4 * (NW - 1), NW, pd.w_chi_min[q & 1], pd.w_chi_max[q & 1]};
+  }
+  if (threadIdx.x == 0) {
+    const MEView g = me_view(L, pda, pta, 0);
+    sc[0] = g.comoving_distance(D_a);                    // :470-471: growth factors used as z
+    sc[1] = g.comoving_distance(D_b);
+    // :129-140: b's redshift range on a's MultiEpoch
+    const double c0 = g.comoving_distance(pdb.z_min);
+    sc[2] = cfg.window_precision > c0 ? cfg.window_precision : c0;
+    sc[3] = g.comoving_distance(pdb.z_max);
+  }
+  __syncthreads();
+  Pa.template finish_t<BAO>();
+  Pb.template finish_t<BAO>();
+  const int i = blockIdx.x, T = blockIdx.y;
+  const double chi_min_a = pda.chi_min, chi_max_a = pda.chi_max;
+  const double chi_min_b = sc[2], chi_max_b = sc[3];
+  const double ln_K_min = log(fmin(cfg.k_min * chi_min_a, cfg.k_min * chi_min_b));   // :162-167
+  const double ln_K_max = log(fmax(cfg.k_max * chi_max_a, cfg.k_max * chi_max_b));
+  const double ln_K = linspace_at(ln_K_min, ln_K_max, C.N, i);
+  const double K = exp(ln_K);
+  double chi_min = K / cfg.k_max, chi_max = K / cfg.k_min;
+  if (T != kCrossA) {
+    if (chi_min < chi_min_b) chi_min = chi_min_b;
+    if (chi_max > chi_max_b) chi_max = chi_max_b;
+  }
+  if (T != kCrossB) {                                    // (ab, ba: b's limits, then a's, :512-515)
+    if (chi_min < chi_min_a) chi_min = chi_min_a;
+    if (chi_max > chi_max_a) chi_max = chi_max_a;
+  }
+  CovCrossIntegrand<BAO> f{&Pa, &Pb, &me, w, kCrossA, K, 1.0};
+  const double peak_a = f(sc[0]);
+  f.T = kCrossB;
+  const double peak_b = f(sc[1]);
+  const double norm_int = T == kCrossA ? peak_a : (T == kCrossB ? peak_b : sqrt(peak_a * peak_b));
+  f.T = T;
+  f.norm = norm_int > 0.0 ? 1.0 / norm_int : 1.0;
+  int level = 0;
+  const double v = romberg1<4>(f, chi_min, chi_max, cfg.global_precision, cfg.corr_precision,
+                               cfg.divmax, red, &level);
+  if (threadIdx.x == 0) {
+    if (T == 0) ct[C.ln_K + i] = ln_K;
+    ct[C.proj[T] + i] = v / f.norm;
+    ct[C.lev[T] + i] = (double)level;
+    if (i == 0 && T == 0) {
+      ct[C.scal + 0] = ln_K_min;
+      ct[C.scal + 1] = ln_K_max;
+      ct[C.scal + 2] = D_a;
+      ct[C.scal + 3] = D_b;
+      ct[C.scal + 4] = sc[0];
+      ct[C.scal + 5] = sc[1];
+    }
+  }
+}
+
+// grid 4, block 64: the not-a-knot spline of table blockIdx.x (covariance.py:533-541).
+__global__ void k_cov_cross_spline(CrossLayout C, double* __restrict__ ct) {
+  const int T = blockIdx.x;
+  if (threadIdx.x == 0 && T < 4)
+    spline_build(ct + C.ln_K, ct + C.proj[T], C.N, ct + C.pp[T], ct + C.work[T]);
+}
+
+// covariance.py:422-453 (_covariance_G_integrand, matching_corrs == False): two two-point terms
+// from the four projected spectra; poiss[p] = proj_power_poisson(window_pair = p).
+struct CovCrossGIntegrand {
+  const double *xk, *pp;           // pp: the four splines, 4 (N - 1) doubles each
+  int N;
+  const BesselTab* B;
+  double theta_a, theta_b, inv_Da, inv_Db, poiss[4], norm;
+  __device__ __forceinline__ double operator()(double ln_K) const {
+    const double K = exp(ln_K);
+    const double x = log(K);
+    const int M = 4 * (N - 1);
+    const double Pa = spline_eval(xk, pp, N, x) * (inv_Da * inv_Da);
+    const double Pb = spline_eval(xk, pp + M, N, x) * (inv_Db * inv_Db);
+    const double Pab = spline_eval(xk, pp + 2 * M, N, x) * (inv_Da * inv_Db);
+    const double Pba = spline_eval(xk, pp + 3 * M, N, x) * (inv_Da * inv_Db);
+    const double t1 = Pa * Pb + Pa * poiss[2] + Pb * poiss[0];
+    const double t2 = Pab * Pba + Pab * poiss[1] + Pba * poiss[3];
+    return K * K * norm * (t1 + t2) * bessel_j<0>(K * theta_a, *B) * bessel_j<0>(K * theta_b, *B);
+  }
+};
+
+// grid n pairs, block 256: Covariance.covariance_G(theta_a, theta_b) of a cross block
+// (covariance.py:361-390).  LDS: N + 16 (N - 1) doubles.
+__global__ __launch_bounds__(256) void k_cov_cross_gaussian(chomp_config cfg, CrossLayout C,
+                                                            const double* __restrict__ ct,
+                                                            const BesselTab* __restrict__ bess_g,
+                                                            double j0_limit, double area,
+                                                            double poiss0, double poiss1,
+                                                            double poiss2, double poiss3,
+                                                            const double* __restrict__ theta_a,
+                                                            const double* __restrict__ theta_b,
+                                                            double* __restrict__ out,
+                                                            double* __restrict__ levels) {
+  extern __shared__ __align__(16) double sm[];
+  __shared__ BesselTab B;
+  __shared__ double red[romberg_scratch<4, 2>()];
+  const int M = 4 * (C.N - 1);
+  double* xk = sm;
+  double* pp = sm + C.N;
+  copy_doubles(xk, ct + C.ln_K, C.N);
+  for (int t = 0; t < 4; ++t) copy_doubles(pp + t * M, ct + C.pp[t], M);
+  copy_doubles(reinterpret_cast<double*>(&B), reinterpret_cast<const double*>(bess_g),
+               (int)(sizeof(BesselTab) / sizeof(double)));
+  __syncthreads();
+  const double ln_K_min = ct[C.scal + 0], ln_K_hi = ct[C.scal + 1];
+  const double D_a = ct[C.scal + 2], D_b = ct[C.scal + 3];
+  const double ta = theta_a[blockIdx.x], tb = theta_b[blockIdx.x];
+  double ln_K_max = log(fmax(j0_limit / ta, j0_limit / tb));
+  double v = 0.0;
+  int level = 0;
+  if (ln_K_max > ln_K_hi) ln_K_max = ln_K_hi;
+  if (ln_K_max > ln_K_min) {
+    CovCrossGIntegrand f{xk, pp, C.N, &B, 0.0, 0.0, 1.0 / D_a, 1.0 / D_b,
+                         {poiss0, poiss1, poiss2, poiss3}, 1.0};
+    const double norm = 1.0 / f(0.0);                    // :383
+    f.theta_a = ta;
+    f.theta_b = tb;
+    f.norm = norm;
+    v = romberg1<4>(f, ln_K_min, ln_K_max, cfg.global_precision, cfg.corr_precision,
+                    cfg.divmax, red, &level) / (norm * 2.0 * kPi * area);
+  }
+  if (threadIdx.x == 0) {
+    out[blockIdx.x] = v;
+    if (levels) levels[blockIdx.x] = (double)level;
+  }
+}
+
 }  // namespace chomp

@@ -710,6 +710,43 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area,
                               double poisson_a, double poisson_b,
                               const double* theta, size_t n, double* out, int mem);
 
+/* Gaussian cross-covariance of two w(theta), Covariance(corr_a, corr_b) with two different
+ * correlations and nongaussian_cov=False: the matching_corrs == False branch
+ * (covariance.py:422-453, 495-541).
+ *
+ * A cross block reads four windows and two P(k) epochs, and a context holds one projection
+ * set-up and -- for one Halo object -- one epoch.  chomp_covariance_cross_stage therefore takes
+ * a snapshot of one side into `ctx`: slot 0 is correlation a, slot 1 correlation b.  `src` (which
+ * may be `ctx` itself) is the context that holds that side now: its kernel_setup (windows,
+ * MultiEpoch, z range) and spectrum `which` of its halo epoch `epoch`, moved to that
+ * correlation's z_bar by the caller (:465-466).  Later changes of `src` do not reach the
+ * snapshot.  Both contexts must be on one device and share configuration and transfer function
+ * (CHOMP_ERR_SCOPE otherwise).  When src is another context the call waits for both streams.
+ *
+ * chomp_covariance_table_cross replaces Covariance._initialize_halo_splines for the block: on
+ * kernel_npoints knots in ln K from ln(k_min min(chi_min_a, chi_min_b)) to
+ * ln(k_max max(chi_max_a, chi_max_b)) (:162-167) the four projected spectra
+ *   a:  P_a W_a1 W_a2,  b:  P_b W_b1 W_b2,  ab: sqrt(P_a P_b) W_a1 W_b2,  ba: sqrt(P_a P_b) W_a2 W_b1
+ * (each times D^2 / chi^2, over chi) with the reference's limits -- a's range, b's range, and for
+ * ab / ba b's clamped again to a's -- normalisations and Romberg tolerances, and their splines.
+ * Growth factor, z(chi) and the chi limits of both sides are those of slot 0's MultiEpoch
+ * (Covariance.kernel.cosmo is correlation a's).  D_a / D_b are its growth_factor(z_bar_a / b)
+ * (:468-469).  ln_K [n], tables [4][n] and levels [4][n] (n = kernel_npoints, host, may be
+ * NULL; rows in the order a, b, ab, ba) receive the knots, the tables and the Romberg levels.
+ *
+ * chomp_covariance_gaussian_cross replaces Covariance.covariance_G for n pairs of bin centres
+ * of the block: theta holds theta_a[n] then theta_b[n] (radians); poisson_p is
+ * proj_power_poisson(window_pair = p) (:427-428, 443-444); j0_limit and area as in
+ * chomp_covariance_gaussian. */
+int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int which,
+                                 size_t epoch);
+int chomp_covariance_table_cross(chomp_ctx* ctx, double D_a, double D_b, double* ln_K,
+                                 double* tables, double* levels, size_t n);
+int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area,
+                                    double poisson_0, double poisson_1, double poisson_2,
+                                    double poisson_3, const double* theta, size_t n,
+                                    double* out, int mem);
+
 /* Super-sample covariance of w(theta), Covariance(corr, corr, nongaussian_cov=False,
  * ssc_cov=True), with a1 = b1 = window a and a2 = b2 = window b of the context's
  * kernel_setup.  Host memory throughout.
