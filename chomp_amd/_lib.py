@@ -26,6 +26,7 @@ FAM_MM, FAM_GM, FAM_GG = T_H_M | T_PP_MM, T_H_M | T_H_G | T_PP_GM, T_H_G | T_PP_
 FAM_SSC = FAM_MM | T_I_1_2
 P_LIN, P_MM, P_GM, P_GG, P_HALOFIT, P_EXTRAPOLATE = 0, 1, 2, 3, 16, 32
 P_SSC_RESPONSE, P_MM_SSC = 4, 5
+CROSS_WINDOWS = -1   # chomp_covariance_cross_stage: the projection set-up alone
 PREC_F64, PREC_F32_EVAL, PREC_F32_TABLES, PREC_F32_ALL = 0, 1, 2, 3
 DNDZ_MAGLIM, DNDZ_GAUSSIAN, DNDZ_BOXCAR, DNDZ_PPOLY = 0, 1, 2, 3
 WINDOW_GALAXY, WINDOW_CONVERGENCE, WINDOW_FLAT_CONVERGENCE, WINDOW_CONVERGENCE_DELTA = 0, 1, 2, 3
@@ -143,6 +144,7 @@ EXPORTS = [
     "chomp_tri_triple",
     "chomp_kernel_ng_setup", "chomp_kernel_ng_raw", "chomp_kernel_ng_eval",
     "chomp_covariance_ng",
+    "chomp_covariance_cross_range", "chomp_kernel_ssc_setup_cross", "chomp_covariance_ssc_cross",
     "chomp_set_general_profile", "chomp_y_general", "chomp_y_general_table",
     "chomp_halo_normalization",
 ]
@@ -447,6 +449,9 @@ def lib():
         L.chomp_kernel_ssc_raw.argtypes = [vp, vp, sz, vp]
         L.chomp_kernel_ssc_eval.argtypes = [vp, vp, sz, vp]
         L.chomp_covariance_ssc.argtypes = [vp, sz, d, vp, sz, vp, vp, vp]
+        L.chomp_covariance_cross_range.argtypes = [vp, c_double_p]
+        L.chomp_kernel_ssc_setup_cross.argtypes = L.chomp_kernel_ssc_setup.argtypes
+        L.chomp_covariance_ssc_cross.argtypes = [vp, d, vp, sz, vp, vp, vp]
         L.chomp_kernel_ng_setup.argtypes = [vp, d, i, c_double_p, c_double_p, c_double_p]
         L.chomp_kernel_ng_raw.argtypes = [vp, vp, sz, vp]
         L.chomp_kernel_ng_eval.argtypes = [vp, vp, sz, vp]
@@ -1165,9 +1170,16 @@ class Context(object):
                                                p[3], th, _numel(th) // 2,
                                                new(_numel(th) // 2), mem))[0]
 
+    def covariance_cross_range(self):
+        """(z_min, z_max, chi_min, chi_max) of the four windows in the two staged slots."""
+        out = numpy.empty(4)
+        self._check(self._L.chomp_covariance_cross_range(self._h, out.ctypes.data_as(c_double_p)))
+        return tuple(float(v) for v in out)
+
     def kernel_ssc_setup(self, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi, sigma2,
-                         with_table=True):
-        """Super-sample kernel of the context's windows.  Returns (info[3] = z_bar_NG,
+                         with_table=True, cross=False):
+        """Super-sample kernel of the context's windows, or with `cross` of the four windows in
+        the two staged slots of a cross block.  Returns (info[3] = z_bar_NG,
         chi(z_bar_NG), growth_factor(z_bar_NG); table and Romberg levels, each
         [kernel_npoints, kernel_npoints], or None without the table)."""
         n = self.config.kernel_npoints
@@ -1177,7 +1189,8 @@ class Context(object):
         info = numpy.empty(3)
         tab, lev = (numpy.empty((n, n)), numpy.empty((n, n))) if with_table else (None, None)
         ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
-        self._check(self._L.chomp_kernel_ssc_setup(
+        fn = self._L.chomp_kernel_ssc_setup_cross if cross else self._L.chomp_kernel_ssc_setup
+        self._check(fn(
             self._h, float(ln_ktheta_min), float(ln_ktheta_max), float(j0_ssc_limit),
             x.ctypes.data_as(c_double_p), y.ctypes.data_as(c_double_p), x.size,
             int(bool(with_table)), ptr(info), ptr(tab), ptr(lev)))
@@ -1201,6 +1214,20 @@ class Context(object):
             return (epoch, float(area), th, n, new(n), new((n, nk)) if knots else None,
                     new((n, nk)) if knots else None)
         outs = self._run(self._L.chomp_covariance_ssc, [_pairs(theta_a, theta_b)], body)
+        if knots:
+            return outs[0], outs[1], outs[2].astype(int)
+        return outs[0]
+
+    def covariance_ssc_cross(self, area, theta_a, theta_b, knots=False):
+        """covariance_ssc of a cross block for each pair (halo_a's response at k_a, halo_b's at
+        k_b, from the staged slots); with knots=True also (k_b knots, Romberg levels)."""
+        nk = self.config.kernel_npoints
+
+        def body(mem, new, th):
+            n = th.size // 2
+            return (float(area), th, n, new(n), new((n, nk)) if knots else None,
+                    new((n, nk)) if knots else None)
+        outs = self._run(self._L.chomp_covariance_ssc_cross, [_pairs(theta_a, theta_b)], body)
         if knots:
             return outs[0], outs[1], outs[2].astype(int)
         return outs[0]

@@ -26,9 +26,19 @@ numpy arrays in their dictionaries -- but with that one comparison answered (two
 equal) the branch runs, and that is what is reproduced.  ``CovarianceMulti`` (covariance.py:796-871)
 assembles the joint matrix of several correlations from such blocks.
 
+``Covariance(corr_a, corr_b, cross_terms=True)`` adds the trispectrum and super-sample terms of
+such a cross block (``nongaussian_cov=True`` with a HaloTrispectrumOneHalo, ``ssc_cov=True``):
+``KernelCovariance(..., four_windows=True)`` is the reference's kernel with a1 != b1 or a2 != b2
+(kernel.py:893-972, 1035-1111, 1155-1206) -- the common range of the four windows, z_bar_NG of
+a1 a2 b1 b2 D^4 / chi^2, kernel_ssc and kernel_NG -- and ``covariance_ssc`` takes halo_a's response
+at k_a and halo_b's at k_b (covariance.py:763-776), each halo a HaloSuperSampleCovariance copy
+at its own correlation's z_bar.  The order of the two angles matters there.  Both are opt-in:
+without the keyword a cross block refuses the two terms as before.  ``CovarianceMulti`` forwards
+``cross_terms`` and ``ssc_cov`` to every block.
+
 Outside the scope (ChompScopeError): ``nongaussian_cov=True`` without a HaloTrispectrumOneHalo,
-the full ``HaloTrispectrum``, the trispectrum and super-sample terms of a cross block, and
-``CovarianceFourier``.
+the full ``HaloTrispectrum``, the trispectrum and super-sample terms of a cross block without
+``cross_terms=True``, four windows with no redshift in common, and ``CovarianceFourier``.
 """
 import numpy
 from scipy import special
@@ -62,14 +72,20 @@ class KernelCovariance(object):
     ``trispectrum_kernel=True``, the trispectrum kernel (kernel / kernel_NG / raw_kernel /
     raw_kernel_NG); without it those four raise ChompScopeError.
 
-    Both kernels are built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over; a
-    cross block, Covariance(corr_a, corr_b), holds four windows and uses neither --
+    Both kernels are built for a1 = b1 and a2 = b2 -- what Covariance(corr, corr) hands over --
     on the device context of ``_ssc_context`` (Covariance points it at its halo copy's, so
-    the response and the table meet there) or else on a context of its own."""
+    the response and the table meet there) or else on a context of its own.
+
+    With ``four_windows=True`` (a1, a2) and (b1, b2) may be different window objects
+    (kernel.py:910-972): the two pairs are staged as the two slots of a cross block -- by the
+    Covariance that owns this object (``_stage``), or else from two Kernels of its own -- and the
+    same tables are built from the product a1 a2 b1 b2 over the range the four windows share.
+    Windows with no redshift in common raise ChompScopeError.  Without the keyword four different
+    windows are refused as before."""
 
     def __init__(self, ktheta_min, ktheta_max, window_function_a1, window_function_a2,
                  window_function_b1, window_function_b2, cosmo_multi_epoch,
-                 force_quad=False, trispectrum_kernel=False):
+                 force_quad=False, trispectrum_kernel=False, four_windows=False):
         if force_quad:
             raise _lib.ChompScopeError("force_quad=True is outside the accelerated scope")
         self.ln_ktheta_min = numpy.log(ktheta_min)
@@ -95,6 +111,34 @@ class KernelCovariance(object):
         self._trispectrum_kernel = bool(trispectrum_kernel)
         self._ng_key = None
         self._ng_table = False
+        self._four_windows = bool(four_windows)
+        self._stage = None           # callable -> (context holding the two slots, their stamp)
+        self._side_kernels = None    # without one: two Kernels of this object's own (_stage_own)
+        self._own_stamp = None
+
+    def _matching(self):
+        return (self.window_function_a1 is self.window_function_b1 and
+                self.window_function_a2 is self.window_function_b2)
+
+    def _stage_own(self):
+        """The two slots from two Kernels of this object's own, (a1, a2) and (b1, b2), windows
+        only; in (a1, a2)'s context."""
+        if self._side_kernels is None:
+            kt = (numpy.exp(self.ln_ktheta_min), numpy.exp(self.ln_ktheta_max))
+            self._side_kernels = (
+                kernel_mod.Kernel(kt[0], kt[1], self.window_function_a1, self.window_function_a2,
+                                  self.cosmo),
+                kernel_mod.Kernel(kt[0], kt[1], self.window_function_b1, self.window_function_b2,
+                                  self.cosmo))
+        ka, kb = self._side_kernels
+        ctx = ka._dev()
+        stamp = (ka._signature(), kb._signature())
+        if getattr(ctx, "_cov_cross_owner", None) is not self or self._own_stamp != stamp:
+            ctx.covariance_cross_stage(0, ctx, _lib.CROSS_WINDOWS)
+            ctx.covariance_cross_stage(1, kb._dev(), _lib.CROSS_WINDOWS)
+            ctx._cov_cross_owner = self
+            self._own_stamp = stamp
+        return ctx, stamp
 
     def get_cosmology(self):
         return self.cosmo.get_cosmology()
@@ -167,10 +211,13 @@ class KernelCovariance(object):
         """The device state of kernel_ssc, (re)built when the windows, the cosmology or the
         context changed: z_bar_NG and the sigma^2 knots, and with `table` the 1275 integrals
         and the bicubic (built only once something asks for them)."""
-        if not (self.window_function_a1 is self.window_function_b1 and
-                self.window_function_a2 is self.window_function_b2):
+        if self._four_windows:
+            return self._ssc_four(table)
+        if not self._matching():
             raise _lib.ChompScopeError(
-                "kernel_ssc is accelerated for a1 = b1 and a2 = b2 (Covariance(corr, corr))")
+                "kernel_ssc is accelerated for a1 = b1 and a2 = b2 (Covariance(corr, corr)); "
+                "four different windows need four_windows=True (Covariance(corr_a, corr_b, "
+                "cross_terms=True) passes it)")
         kern = self._proj_kernel
         if kern is None:
             kern = self._proj_kernel = kernel_mod.Kernel(
@@ -194,6 +241,32 @@ class KernelCovariance(object):
             out, d["_ssc_array"], d["_ssc_levels"] = ctx.kernel_ssc_setup(
                 self.ln_ktheta_min, self.ln_ktheta_max, self._j0_ssc_limit,
                 d["_ssc_ln_chi"], d["_ssc_sigma2"], with_table=table)
+            d["_ssc_z_bar_NG"], _, d["_ssc_D_z_NG"] = (float(v) for v in out)
+            self._ssc_key = key
+            self._ssc_table = table
+            ctx._proj_ssc = self
+        return ctx
+
+    def _ssc_four(self, table):
+        """_ssc for four different windows: the same state, from the two staged slots."""
+        if not self.z_min < self.z_max:
+            raise _lib.ChompScopeError(
+                "KernelCovariance: the four windows have no redshift in common (z_min = %g >= "
+                "z_max = %g, kernel.py:910-916)" % (self.z_min, self.z_max))
+        ctx, stamp = self._stage() if self._stage is not None else self._stage_own()
+        key = (id(ctx), stamp, self.ln_ktheta_min, self.ln_ktheta_max, ctx.config.kernel_npoints)
+        fresh = key == self._ssc_key and ctx._proj_ssc is self
+        if not fresh or (table and not self._ssc_table):
+            d = self.__dict__
+            _, _, d["_ssc_chi_min"], d["_ssc_chi_max"] = ctx.covariance_cross_range()
+            chi = numpy.logspace(numpy.log10(d["_ssc_chi_min"]), numpy.log10(d["_ssc_chi_max"]),
+                                 defaults.default_precision["corr_npoints"])
+            sigma = self.cosmo.sigma_r(chi, 0.0)
+            d["_ssc_ln_chi"] = numpy.log(chi)
+            d["_ssc_sigma2"] = sigma * sigma
+            out, d["_ssc_array"], d["_ssc_levels"] = ctx.kernel_ssc_setup(
+                self.ln_ktheta_min, self.ln_ktheta_max, self._j0_ssc_limit,
+                d["_ssc_ln_chi"], d["_ssc_sigma2"], with_table=table, cross=True)
             d["_ssc_z_bar_NG"], _, d["_ssc_D_z_NG"] = (float(v) for v in out)
             self._ssc_key = key
             self._ssc_table = table
@@ -259,10 +332,11 @@ class Covariance(object):
                  bins_per_decade=5.0, survey_area_deg2=20,
                  n_a=1.0e4, n_b=1.0e4, variance=1.0, nongaussian_cov=True,
                  input_halo_trispectrum=None, power_spec='power_mm',
-                 poisson_noise_only=False, ssc_cov=False, **kws):
+                 poisson_noise_only=False, ssc_cov=False, cross_terms=False, **kws):
         cross = input_correlation_a is not input_correlation_b
         if cross:
-            self._check_cross(input_correlation_a, input_correlation_b, nongaussian_cov, ssc_cov)
+            self._check_cross(input_correlation_a, input_correlation_b, nongaussian_cov, ssc_cov,
+                              cross_terms)
         if nongaussian_cov and input_halo_trispectrum is None:
             raise _lib.ChompScopeError(
                 "the trispectrum term of the covariance (covariance_NG) is built for an explicit "
@@ -321,7 +395,7 @@ class Covariance(object):
             numpy.power(10.0, self.log_theta_max) * defaults.default_limits["k_max"],
             kern.window_function_a, kern.window_function_b,
             kern_b.window_function_a, kern_b.window_function_b, kern.cosmo,
-            trispectrum_kernel=self.nongaussian_cov)
+            trispectrum_kernel=self.nongaussian_cov, four_windows=cross and bool(cross_terms))
         # covariance.py:108-115.  The reference's Kernel holds *copies* of its two
         # windows, each with a private copy of the MultiEpoch, and WindowFunction.__eq__
         # (kernel.py:248-259) compares those by identity: two windows are "equal" only
@@ -352,6 +426,10 @@ class Covariance(object):
         # integrated with)
         self.kernel._proj_kernel = kern
         self.kernel._ssc_context = lambda: self.halo_a._context()
+        # ... and of a cross block from the two slots its Gaussian tables are built from
+        self.kernel._stage = lambda: (self._table_cross(), self._cross_stamp)
+        self._cross_stamp = 0
+        self._copy_keys = None
         self._initialized_halo_splines = False
         self._table_key = None
         self._ln_k_min = numpy.log(defaults.default_limits['k_min'])
@@ -368,13 +446,14 @@ class Covariance(object):
         self.power_spec = power_spec
 
     @staticmethod
-    def _check_cross(corr_a, corr_b, nongaussian_cov, ssc_cov):
+    def _check_cross(corr_a, corr_b, nongaussian_cov, ssc_cov, cross_terms=False):
         """The limits of a cross block, Covariance(corr_a, corr_b) of two different objects."""
-        if nongaussian_cov or ssc_cov:
+        if (nongaussian_cov or ssc_cov) and not cross_terms:
             raise _lib.ChompScopeError(
                 "Covariance of two different correlation objects is accelerated for its Gaussian "
                 "term only: the trispectrum and super-sample terms of a cross block are outside "
-                "the scope -- pass nongaussian_cov=False (and leave ssc_cov=False)")
+                "the scope -- pass nongaussian_cov=False (and leave ssc_cov=False), or opt in to "
+                "both terms with cross_terms=True")
         for corr in (corr_a, corr_b):
             if not isinstance(corr.halo, halo_mod.Halo):
                 # (the two sides are staged from their halos' device contexts)
@@ -458,8 +537,10 @@ class Covariance(object):
         ``corr_a.halo is corr_b.halo`` the reference's two set_redshift calls (:465-466) leave
         that one object at z_bar_b: both spectra are then P at z_bar_b, here as there."""
         ca, cb = self.corr_a, self.corr_b
-        ha, hb = self.halo_a, self.halo_b
         z_a, z_b = ca.kernel.z_bar, cb.kernel.z_bar
+        if self.ssc_cov:
+            self._renew_copies(z_a, z_b)
+        ha, hb = self.halo_a, self.halo_b
         if ha is not hb:
             ha.set_redshift(z_a)
         hb.set_redshift(z_b)
@@ -472,10 +553,11 @@ class Covariance(object):
             # covariance.py:468-469: both from correlation a's MultiEpoch
             self._D_z_a = ca._growth_at_z_bar()
             self._D_z_b = float(ca.kernel.cosmo.growth_factor(z_b))
-            ctx_a, code_a = ca._prepare(self.power_spec)
+            ctx_a, code_a = self._prepare_side(ca, ha)
             ctx.covariance_cross_stage(0, ctx_a, code_a)
-            ctx_b, code_b = cb._prepare(self.power_spec)
+            ctx_b, code_b = self._prepare_side(cb, hb)
             ctx.covariance_cross_stage(1, ctx_b, code_b)
+            self._cross_stamp += 1     # (what was built from the slots -- kernel_ssc, kernel_NG -- is void)
             self._ln_K_array, tab, lev = ctx.covariance_table_cross(self._D_z_a, self._D_z_b)
             (self._halo_a_array, self._halo_b_array, self._halo_ab_array,
              self._halo_ba_array) = tab
@@ -486,6 +568,33 @@ class Covariance(object):
             self._initialized_halo_splines = True
             ctx._cov_cross_owner = self
         return ctx
+
+    def _prepare_side(self, corr, h):
+        """One side of a cross block set up where it lives: Correlation._prepare; with ssc_cov on
+        the halo copy instead (as _prepare_copy), whose epoch then also holds the tables of the
+        response; so does that of a HaloSuperSampleCovariance handed in by the caller."""
+        if hasattr(h, "dln_power_ddelta_b"):
+            h._sync(_lib.FAM_SSC)
+        if not self.ssc_cov:
+            return corr._prepare(self.power_spec)
+        code, need = _POWER[self.power_spec]
+        corr.kernel._setup_on(h._context())
+        return h._sync(need | _lib.FAM_SSC), h._power_code(code)
+
+    def _renew_copies(self, z_a, z_b):
+        """The HaloSuperSampleCovariance copies of a cross block follow their correlations: the
+        reference makes them once, at construction (covariance.py:144-149), and a copy keeps the
+        I_1^2 knots of its first build whatever is set on it later; after a change of a
+        correlation's windows, z_bar, HOD or halo the side's copy is made again, so the block
+        holds what one built from the changed correlations would."""
+        keys = [(c.kernel._signature(), z, self._halo_signature(c.halo))
+                for c, z in ((self.corr_a, z_a), (self.corr_b, z_b))]
+        if self._copy_keys is not None:
+            if keys[0] != self._copy_keys[0]:
+                self.halo_a = halo_mod.HaloSuperSampleCovariance.init_from_halo(self.corr_a.halo)
+            if keys[1] != self._copy_keys[1]:
+                self.halo_b = halo_mod.HaloSuperSampleCovariance.init_from_halo(self.corr_b.halo)
+        self._copy_keys = keys
 
     def _tables(self):
         return self._table() if self.matching_corrs else self._table_cross()
@@ -646,6 +755,12 @@ class Covariance(object):
             # covariance.py:772: the reference's integrand asks halo_a for it
             raise AttributeError("'%s' object has no attribute 'dln_power_ddelta_b'"
                                  % type(self.halo_a).__name__)
+        if not self.matching_corrs:
+            if not hasattr(self.halo_b, "dln_power_ddelta_b"):
+                raise AttributeError("'%s' object has no attribute 'dln_power_ddelta_b'"
+                                     % type(self.halo_b).__name__)
+            # (the slots hold both responses: _prepare_side)
+            return self.kernel._ssc().covariance_ssc_cross(self.area, theta_a, theta_b, knots)
         ctx = self.kernel._ssc()
         self.halo_a._sync(_lib.FAM_SSC)
         return ctx.covariance_ssc(0, self.area, theta_a, theta_b, knots)
@@ -653,7 +768,8 @@ class Covariance(object):
     def covariance_ssc(self, theta_a_rad, theta_b_rad):
         """covariance.py:685-776: for each k_a knot a Romberg over ln k_b of
         k_b^2 R(k_a) R(k_b) kernel_ssc(ln k_a theta_a, ln k_b theta_b), R = halo_a's
-        dln_power_ddelta_b; their spline, and the Romberg over ln k_a / (4 pi^2 area)."""
+        dln_power_ddelta_b (in a cross block halo_a's at k_a and halo_b's at k_b, so the order of
+        the two angles matters); their spline, and the Romberg over ln k_a / (4 pi^2 area)."""
         ta, tb = numpy.broadcast_arrays(numpy.asarray(theta_a_rad, dtype=numpy.float64),
                                         numpy.asarray(theta_b_rad, dtype=numpy.float64))
         out = self._covariance_ssc_pairs(ta.ravel(), tb.ravel())
@@ -676,12 +792,16 @@ class CovarianceMulti(Covariance):
     pair (i <= j) in ``covariance_list[i][j - i]``, assembled into ``wcovar`` by
     ``get_covariance``.  Every block owns its tables.  With more than one correlation the
     off-diagonal blocks are cross-covariances, Gaussian term only: pass nongaussian_cov=False
-    (the default, True, is the reference's, and raises ChompScopeError for them)."""
+    (the default, True, is the reference's, and raises ChompScopeError for them) -- or
+    cross_terms=True, which every block receives and which opens the trispectrum and super-sample
+    terms of the cross blocks (Covariance).  ssc_cov is forwarded too; the reference forwards
+    neither, and the defaults leave its behaviour."""
 
     def __init__(self, correlation_object_list, bins_per_decade=5,
                  survey_area_deg2=4 * numpy.pi * strad_to_deg2,
                  n_a=1e6, n_b=1e6, variance=1.0, nongaussian_cov=True,
-                 input_halo_trispectrum=None, poisson_noise_only=False, **kws):
+                 input_halo_trispectrum=None, poisson_noise_only=False, cross_terms=False,
+                 ssc_cov=False, **kws):
         self.covariance_list = []
         n = len(correlation_object_list)
         for idx1 in range(n):
@@ -693,7 +813,8 @@ class CovarianceMulti(Covariance):
                     bins_per_decade=bins_per_decade, survey_area_deg2=survey_area_deg2,
                     n_a=n_a, n_b=n_b, variance=variance, nongaussian_cov=nongaussian_cov,
                     input_halo_trispectrum=input_halo_trispectrum,
-                    poisson_noise_only=poisson_noise_only))
+                    poisson_noise_only=poisson_noise_only, ssc_cov=ssc_cov,
+                    cross_terms=cross_terms))
             self.covariance_list.append(row)
         self.annular_bins = self.covariance_list[0][0].annular_bins
         self.theta_bins = len(self.annular_bins)

@@ -748,7 +748,8 @@ int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int w
   if (slot < 0 || slot > 1) return fail(ctx, CHOMP_ERR_ARG, "covariance_cross_stage: slot must be 0 or 1");
   if (!src->proj.ready)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_cross_stage: the source context has no kernel_setup");
-  { const int rcp = check_power(src, which, epoch, 1); if (rcp) return fail(ctx, rcp, "covariance_cross_stage: source: " + src->err); }
+  const bool windows_only = which == CHOMP_CROSS_WINDOWS;
+  if (!windows_only) { const int rcp = check_power(src, which, epoch, 1); if (rcp) return fail(ctx, rcp, "covariance_cross_stage: source: " + src->err); }
   if (src->device != ctx->device)
     return fail(ctx, CHOMP_ERR_SCOPE, "covariance_cross_stage: both contexts must be on one device");
   if (std::memcmp(&src->cfg, &ctx->cfg, sizeof(chomp_config)) != 0 || src->with_bao != ctx->with_bao)
@@ -756,7 +757,7 @@ int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int w
                                       "configuration and transfer function");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(src); if (rcj) return fail(ctx, rcj, "covariance_cross_stage: source: " + src->err); }
-  { const int rce = prepare_extrapolation(src, which, epoch, 1); if (rce) return fail(ctx, rce, "covariance_cross_stage: source: " + src->err); }
+  if (!windows_only) { const int rce = prepare_extrapolation(src, which, epoch, 1); if (rce) return fail(ctx, rce, "covariance_cross_stage: source: " + src->err); }
   // (another context's stream is not ordered against this one: wait for what it holds before
   //  the copies, and for the copies before it may rewrite what they read)
   if (src != ctx) HIPCHK(hipStreamSynchronize(src->stream));
@@ -771,16 +772,28 @@ int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int w
   X.C = C;
   X.ready = false;
   X.staged[slot] = false;
+  // (the kernel_ssc / kernel_NG states of the block's four windows were built from the slots)
+  if (ctx->proj.ssc_four) ctx->proj.ssc_prep = ctx->proj.ssc_ready = false;
+  if (ctx->proj.ng_four) ctx->proj.ng_prep = ctx->proj.ng_ready = false;
   const auto copy = [&](int off, const void* from, size_t doubles) {
     return hipMemcpyAsync(X.d + off, from, doubles * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
   };
-  HIPCHK(copy(C.ep[slot], src->d_epochs + epoch, kEpochDoubles));
-  HIPCHK(copy(C.htab[slot], src->d_tab + epoch * (size_t)src->L.stride, (size_t)src->L.stride));
+  if (!windows_only) {
+    HIPCHK(copy(C.ep[slot], src->d_epochs + epoch, kEpochDoubles));
+    HIPCHK(copy(C.htab[slot], src->d_tab + epoch * (size_t)src->L.stride, (size_t)src->L.stride));
+  }
   HIPCHK(copy(C.pd[slot], src->proj.d_pd, kProjDoubles));
   HIPCHK(copy(C.ptab[slot], src->proj.d_tab, (size_t)L.total));
   if (src != ctx) HIPCHK(hipStreamSynchronize(ctx->stream));
   X.staged[slot] = true;
   X.which[slot] = which;
+  {   // what chomp_covariance_ssc_cross asks of the snapshot: the families of the response
+    const unsigned need = (1u << F_HM) | (1u << F_PPMM) | (1u << F_I12);
+    X.response[slot] = !windows_only && ((src->fam_mask | src->put_mask[epoch]) & need) == need;
+  }
+  const ProjDev& hp = src->proj.host;                    // kernel.py:910-916, this side's share
+  X.z_min[slot] = std::max(hp.w_z_min[0], hp.w_z_min[1]);
+  X.z_max[slot] = std::min(hp.w_z_max[0], hp.w_z_max[1]);
   return CHOMP_OK;
 }
 
@@ -790,6 +803,8 @@ int chomp_covariance_table_cross(chomp_ctx* ctx, double D_a, double D_b, double*
   CrossState& X = ctx->cross;
   if (!X.staged[0] || !X.staged[1])
     return fail(ctx, CHOMP_ERR_STATE, "covariance_table_cross before covariance_cross_stage of both slots");
+  if (X.which[0] == CHOMP_CROSS_WINDOWS || X.which[1] == CHOMP_CROSS_WINDOWS)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_table_cross: a slot holds windows only (CHOMP_CROSS_WINDOWS)");
   if (!(D_a > 0.0) || !(D_b > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_table_cross: D_a, D_b");
   const chomp_config& c = ctx->cfg;
   const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
@@ -856,10 +871,42 @@ int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area
 // ---------------------------------------------------------------------------
 // Super-sample covariance of w(theta) (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
-int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
-                           double j0_ssc_limit, const double* ln_chi, const double* sigma2,
-                           size_t n_sigma, int with_table, double* info, double* table,
-                           double* levels) {
+// The windows behind the context's kernel_ssc / kernel_NG state: its own kernel_setup, or the two
+// slots of its cross block.
+static CovSrc cov_src(chomp_ctx* ctx, bool four) {
+  ProjState& P = ctx->proj;
+  if (!four) return CovSrc{P.d_pd, P.d_tab, nullptr, nullptr};
+  const CrossState& X = ctx->cross;
+  return CovSrc{reinterpret_cast<const ProjDev*>(X.d + X.C.pd[0]), X.d + X.C.ptab[0],
+                reinterpret_cast<const ProjDev*>(X.d + X.C.pd[1]), X.d + X.C.ptab[1]};
+}
+
+// The dynamic LDS of a launch beside the kernel's static LDS fits the 64 kB a workgroup may use.
+static bool fits_lds(const void* kernel, size_t dynamic_bytes) {
+  hipFuncAttributes attr;
+  if (hipFuncGetAttributes(&attr, kernel) != hipSuccess) return false;
+  return dynamic_bytes + attr.sharedSizeBytes <= 64 * 1024;
+}
+
+// A cross block's slots are staged, of this configuration, and their windows overlap.
+static int check_cross_windows(chomp_ctx* ctx, const char* what) {
+  const CrossState& X = ctx->cross;
+  const std::string w(what);
+  if (!X.staged[0] || !X.staged[1])
+    return fail(ctx, CHOMP_ERR_STATE, w + " before covariance_cross_stage of both slots");
+  if (X.C.pd[0] - X.C.htab[0] != ctx->L.stride || X.C.N != ctx->proj.L.NKT ||
+      X.C.ptab[1] - X.C.ptab[0] < ctx->proj.L.total)
+    return fail(ctx, CHOMP_ERR_STATE, w + ": the snapshots are of another configuration");
+  if (!(std::max(X.z_min[0], X.z_min[1]) < std::min(X.z_max[0], X.z_max[1])))
+    return fail(ctx, CHOMP_ERR_SCOPE, w + ": the four windows have no redshift in common "
+                                          "(kernel.py:910-916 would give z_min >= z_max)");
+  return CHOMP_OK;
+}
+
+static int kernel_ssc_setup(chomp_ctx* ctx, bool four, double ln_ktheta_min, double ln_ktheta_max,
+                            double j0_ssc_limit, const double* ln_chi, const double* sigma2,
+                            size_t n_sigma, int with_table, double* info, double* table,
+                            double* levels) {
   if (!ctx || !ln_chi || !sigma2) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: bad args");
   if (!with_table && (table || levels))
     return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: table / levels need with_table");
@@ -873,11 +920,16 @@ int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_kthet
   for (size_t i = 1; i < n_sigma; ++i)
     if (!(ln_chi[i] > ln_chi[i - 1]))
       return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: ln chi knots must increase");
+  if (four) { const int rcx = check_cross_windows(ctx, "kernel_ssc_setup_cross"); if (rcx) return rcx; }
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   ProjState& P = ctx->proj;
   const ProjLayout& L = P.L;
   const SscLayout S = make_ssc_layout(N, (int)n_sigma);
+  const size_t sh = (size_t)ssc_table_lds_doubles(L, S.NS, four) * sizeof(double);
+  if (four && !fits_lds(reinterpret_cast<const void*>(&k_ssc_table<true>), sh))
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup_cross: cosmo/window/corr_npoints too large "
+                                    "for the four windows of a cross block");
   P.ssc_ready = false;
   P.ssc_prep = false;
   { const int rce = ensure(ctx, &P.d_ssc, &P.cap_ssc, (size_t)S.total); if (rce) return rce; }
@@ -885,17 +937,20 @@ int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_kthet
                         ctx->stream));
   HIPCHK(hipMemcpyAsync(P.d_ssc + S.sy, sigma2, n_sigma * sizeof(double), hipMemcpyHostToDevice,
                         ctx->stream));
-  hipLaunchKernelGGL(k_ssc_prep, dim3(1), dim3(256), 0, ctx->stream, ctx->cfg, L, S, P.d_pd,
-                     P.d_tab, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, P.d_ssc);
-  if (with_table) {
-    const size_t sh = (size_t)(ProjLds::doubles(L) + 5 * S.NS - 4) * sizeof(double);
-    hipLaunchKernelGGL(k_ssc_table, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh, ctx->stream,
-                       ctx->cfg, L, S, P.d_pd, P.d_tab, ctx->d_j0, P.d_ssc, (const double*)nullptr,
-                       (const double*)nullptr, (double*)nullptr);
+  const CovSrc src = cov_src(ctx, four);
+  with_flag(four, [&](auto FOUR) {
+    hipLaunchKernelGGL(k_ssc_prep<FOUR>, dim3(1), dim3(256), 0, ctx->stream, ctx->cfg, L, S, src,
+                       ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, P.d_ssc);
+    if (with_table)
+      hipLaunchKernelGGL(k_ssc_table<FOUR>, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh,
+                         ctx->stream, ctx->cfg, L, S, src, ctx->d_j0, P.d_ssc,
+                         (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
+  });
+  if (with_table)
     hipLaunchKernelGGL(k_ssc_bicubic, dim3(1), dim3(256), 0, ctx->stream, S, P.d_ssc);
-  }
   HIPCHK(hipGetLastError());
   P.ssc_ns = (int)n_sigma;
+  P.ssc_four = four;
   P.ssc_prep = true;
   P.ssc_ready = with_table != 0;
   if (info || table || levels) {
@@ -906,6 +961,38 @@ int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_kthet
     if (levels) HIPCHK(hipMemcpy(levels, P.d_ssc + S.lev, b, hipMemcpyDeviceToHost));
   }
   return CHOMP_OK;
+}
+
+int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
+                           double j0_ssc_limit, const double* ln_chi, const double* sigma2,
+                           size_t n_sigma, int with_table, double* info, double* table,
+                           double* levels) {
+  return kernel_ssc_setup(ctx, false, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi, sigma2,
+                          n_sigma, with_table, info, table, levels);
+}
+
+int chomp_kernel_ssc_setup_cross(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
+                                 double j0_ssc_limit, const double* ln_chi, const double* sigma2,
+                                 size_t n_sigma, int with_table, double* info, double* table,
+                                 double* levels) {
+  return kernel_ssc_setup(ctx, true, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi, sigma2,
+                          n_sigma, with_table, info, table, levels);
+}
+
+int chomp_covariance_cross_range(chomp_ctx* ctx, double* info) {
+  if (!ctx || !info) return fail(ctx, CHOMP_ERR_ARG, "covariance_cross_range: bad args");
+  if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "covariance_cross_range before kernel_setup");
+  { const int rcx = check_cross_windows(ctx, "covariance_cross_range"); if (rcx) return rcx; }
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  Staging st(ctx, CHOMP_HOST, "covariance_cross_range");
+  double* d_out;
+  st.out(info, 4, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_cov_cross_range, dim3(1), dim3(64), 0, ctx->stream, ctx->cfg, ctx->proj.L,
+                     cov_src(ctx, true), d_out);
+  return st.finish();
 }
 
 int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
@@ -925,9 +1012,12 @@ int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, doub
   st.out(out, n, &d_out);
   const int rc = st.place();
   if (rc) return rc;
-  const size_t sh = (size_t)(ProjLds::doubles(P.L) + 5 * S.NS - 4) * sizeof(double);
-  hipLaunchKernelGGL(k_ssc_table, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, P.L, S,
-                     P.d_pd, P.d_tab, ctx->d_j0, P.d_ssc, d_in, d_in + n, d_out);
+  const size_t sh = (size_t)ssc_table_lds_doubles(P.L, S.NS, P.ssc_four) * sizeof(double);
+  const CovSrc src = cov_src(ctx, P.ssc_four);
+  with_flag(P.ssc_four, [&](auto FOUR) {
+    hipLaunchKernelGGL(k_ssc_table<FOUR>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+                       P.L, S, src, ctx->d_j0, P.d_ssc, d_in, d_in + n, d_out);
+  });
   return st.finish();
 }
 
@@ -956,6 +1046,9 @@ int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double
   if (!ctx || !theta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: bad args");
   if (!ctx->proj.ready || !ctx->proj.ssc_ready)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc before kernel_ssc_setup");
+  if (ctx->proj.ssc_four)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc: the kernel_ssc table is a cross block's "
+                                      "(chomp_covariance_ssc_cross serves it)");
   if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: area must be positive");
   if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: at most 65535 pairs a call");
   int rc = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch, 1, true);
@@ -988,6 +1081,49 @@ int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double
   return st.finish();
 }
 
+int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta, size_t n,
+                               double* out, double* kb_knots, double* kb_levels) {
+  if (!ctx || !theta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: bad args");
+  if (!ctx->proj.ready || !ctx->proj.ssc_ready || !ctx->proj.ssc_four)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc_cross before kernel_ssc_setup_cross");
+  { const int rcx = check_cross_windows(ctx, "covariance_ssc_cross"); if (rcx) return rcx; }
+  const CrossState& X = ctx->cross;
+  if (!X.response[0] || !X.response[1])
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc_cross: the staged epochs do not hold the "
+                                      "knot tables of the super-sample response (h_m, pp_mm, i_1_2)");
+  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: area must be positive");
+  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: at most 65535 pairs a call");
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: arguments must be positive");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  ProjState& P = ctx->proj;
+  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
+  const int NK = ctx->cfg.kernel_npoints;
+  const size_t sh = (size_t)ssc_kb_cross_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
+  if (!(ctx->with_bao ? fits_lds(reinterpret_cast<const void*>(&k_ssc_kb_cross<true>), sh) : fits_lds(reinterpret_cast<const void*>(&k_ssc_kb_cross<false>), sh)))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: halo/kernel_npoints too large for the "
+                                    "two responses of a cross block");
+  Staging st(ctx, CHOMP_HOST, "covariance_ssc_cross");
+  const double* d_theta;
+  double *d_out, *d_knots, *d_lev;   // (k_ssc_outer reads the knots: staged even when not copied back)
+  st.in(theta, 2 * n, &d_theta);
+  st.out(out, n, &d_out);
+  st.out(kb_knots, n * NK, &d_knots);
+  st.out(kb_levels, n * NK, &d_lev);
+  const int rc = st.place();
+  if (rc) return rc;
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_ssc_kb_cross<BAO>, dim3((unsigned)NK, (unsigned)n), dim3(256), sh,
+                       ctx->stream, ctx->cfg, ctx->L, S, X.C, X.d, P.d_ssc, d_theta, d_theta + n,
+                       d_knots, d_lev);
+  });
+  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
+                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
+                     ctx->stream, ctx->cfg, area, d_knots, d_out);
+  return st.finish();
+}
+
 // ---------------------------------------------------------------------------
 // One-halo trispectrum term of the covariance of w(theta) (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
@@ -1011,19 +1147,30 @@ int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, doubl
   const int N = L.NKT;
   const SscLayout S = make_ssc_layout(N, P.ssc_ns);
   const NgLayout G = make_ng_layout(N);
+  // (the windows are those of the kernel_ssc state: a cross block's four, or the context's two)
+  const bool four = P.ssc_four;
+  if (four) { const int rcx = check_cross_windows(ctx, "kernel_ng_setup"); if (rcx) return rcx; }
+  const size_t sh = (size_t)ng_table_lds_doubles(L, four) * sizeof(double);
+  if (four && !fits_lds(reinterpret_cast<const void*>(&k_ng_table<true>), sh))
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_setup: cosmo/window_npoints too large for the four "
+                                    "windows of a cross block");
   P.ng_ready = false;
   P.ng_prep = false;
   { const int rce = ensure(ctx, &P.d_ng, &P.cap_ng, (size_t)G.total); if (rce) return rce; }
   hipLaunchKernelGGL(k_ng_prep, dim3(1), dim3(256), 0, ctx->stream, S, G, P.d_ssc, j0_limit,
                      P.d_ng, ng_status(ctx));
   if (with_table) {
-    const size_t sh = (size_t)ProjLds::doubles(L) * sizeof(double);
-    hipLaunchKernelGGL(k_ng_table, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh, ctx->stream,
-                       ctx->cfg, L, G, P.d_pd, P.d_tab, ctx->d_j0, P.d_ng, (const double*)nullptr,
-                       (const double*)nullptr, (double*)nullptr, ng_status(ctx));
+    const CovSrc src = cov_src(ctx, four);
+    with_flag(four, [&](auto FOUR) {
+      hipLaunchKernelGGL(k_ng_table<FOUR>, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh,
+                         ctx->stream, ctx->cfg, L, G, src, ctx->d_j0, P.d_ng,
+                         (const double*)nullptr, (const double*)nullptr, (double*)nullptr,
+                         ng_status(ctx));
+    });
     hipLaunchKernelGGL(k_ng_bicubic, dim3(1), dim3(256), 0, ctx->stream, G, P.d_ng);
   }
   HIPCHK(hipGetLastError());
+  P.ng_four = four;
   P.ng_prep = true;
   P.ng_ready = with_table != 0;
   if (table || levels || table_min) {
@@ -1055,9 +1202,12 @@ int chomp_kernel_ng_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, doubl
   st.out(out, n, &d_out);
   const int rc = st.place();
   if (rc) return rc;
-  const size_t sh = (size_t)ProjLds::doubles(P.L) * sizeof(double);
-  hipLaunchKernelGGL(k_ng_table, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, P.L, G,
-                     P.d_pd, P.d_tab, ctx->d_j0, P.d_ng, d_in, d_in + n, d_out, ng_status(ctx));
+  const size_t sh = (size_t)ng_table_lds_doubles(P.L, P.ng_four) * sizeof(double);
+  const CovSrc src = cov_src(ctx, P.ng_four);
+  with_flag(P.ng_four, [&](auto FOUR) {
+    hipLaunchKernelGGL(k_ng_table<FOUR>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+                       P.L, G, src, ctx->d_j0, P.d_ng, d_in, d_in + n, d_out, ng_status(ctx));
+  });
   return st.finish();
 }
 

@@ -10,6 +10,7 @@
 //   k_ssc_bicubic   RectBivariateSpline(s=0) of the table as a piecewise bicubic
 //   k_ssc_eval      kernel_ssc with the reference's clamp and zero rules
 //   k_ssc_kb        covariance_ssc, inner integrals: one k_b Romberg per (pair, k_a knot)
+//   k_ssc_kb_cross  ... of a cross block: halo_a's response at k_a, halo_b's at k_b
 //   k_ssc_outer     covariance_ssc / covariance_NG, the k_a spline and the outer Romberg per pair
 //
 //   k_ng_prep       the kernel_NG state from the kernel_ssc one (z_bar_NG, its chi and growth, the
@@ -20,6 +21,12 @@
 //   k_ng_eval       kernel_NG with the reference's clamp and zero rules
 //   k_ng_tri        the bicubic of an uploaded I_0^4 table (HaloTrispectrumOneHalo's)
 //   k_ng_kb         covariance_NG, inner integrals: one k_b Romberg per (pair, k_a knot)
+//
+// k_ssc_prep, k_ssc_table and k_ng_table are templates over where the four windows come from
+// (CovSrc / CovWindows): a matching block's two windows, each used twice, or the four windows in
+// the two slots of a cross block (Covariance(corr_a, corr_b, cross_terms=True), kernel.py:893-972
+// with a1 != b1 or a2 != b2; k_cov_cross_range gives that block's common range).  Everything
+// behind the tables is shared.
 //
 // Everything runs in one context: the halo copy's.  The windows and the MultiEpoch are set up
 // there (Kernel._setup_on, as Correlation._prepare does for its own halo), so the table, its
@@ -42,7 +49,7 @@ inline SscLayout make_ssc_layout(int N, int NS) {
   S.N = N;
   S.NS = NS;
   int o = 0;
-  S.scal = o; o += 8;
+  S.scal = o; o += 16;
   S.kx = o; o += N;
   S.sx = o; o += NS;
   S.sy = o; o += NS;
@@ -58,9 +65,13 @@ inline SscLayout make_ssc_layout(int N, int NS) {
 // scalars
 constexpr int kSscZBar = 0, kSscChiPeak = 1, kSscDz = 2, kSscLnMin = 3, kSscLnMax = 4,
               kSscLimit = 5;
+// ... and the common range of the four windows (kernel.py:910-931), which the table kernels read
+constexpr int kSscZMin = 8, kSscZMax = 9, kSscChiMin = 10, kSscChiMax = 11;
 
 // Dynamic LDS of the covariance_ssc launches, in doubles.
 inline int ssc_kb_lds_doubles(int NK_halo, int N) { return 12 * (NK_halo - 1) + 5 * N - 4; }
+// ... with the two responses of a cross block
+inline int ssc_kb_cross_lds_doubles(int NK_halo, int N) { return 24 * (NK_halo - 1) + 5 * N - 4; }
 inline int ssc_outer_lds_doubles(int N) { return N + N + 4 * (N - 1) + 2 * N; }
 
 // kernel.py:1224-1231 (_sigma2): the spline of sigma^2 in ln chi inside [chi_min, chi_max], 0
@@ -74,33 +85,95 @@ struct Sigma2View {
   }
 };
 
-// kernel.py:1048-1056 (_kernel_NG_integrand) with a1 = b1 = window a, a2 = b2 = window b, in
-// the reference's order of operations (norm = 1 multiplies exactly).
-__device__ __forceinline__ double ssc_ng_integrand(const ProjLds& P, const BesselTab* B,
+// Where the four windows a1, a2, b1, b2 of a KernelCovariance come from.  A matching block
+// (Covariance(corr, corr)) has a1 = b1, a2 = b2: the two windows of one projection set-up (pd,
+// ptab), each used twice.  A cross block (FOUR) takes a1, a2 and the MultiEpoch from slot 0 of the
+// block's CrossLayout (pd, ptab) and b1, b2 from slot 1 (pd_b, ptab_b): kernel.py:918-931, the
+// MultiEpoch is correlation a's throughout.
+struct CovSrc {
+  const ProjDev* pd;
+  const double* ptab;
+  const ProjDev* pd_b;
+  const double* ptab_b;
+};
+template <bool FOUR>
+struct CovWindows {
+  ProjLds P;                       // MultiEpoch, a1, a2
+  WindowView b1, b2;               // (FOUR only)
+  // Carve `sm` and copy the tables in (all threads; barrier afterwards); pd, pd_b: copies of the
+  // sources' scalars the caller holds in LDS.
+  __device__ __forceinline__ double* stage(const ProjLayout& L, const CovSrc& src,
+                                           const ProjDev& pd, const ProjDev& pd_b, double* sm) {
+    double* end = P.stage(L, pd, src.ptab, sm);
+    if constexpr (FOUR) {
+      const int n = 4 * (L.NWp - 1);
+      copy_doubles(end, src.ptab_b + L.w_pp[0], n);
+      copy_doubles(end + n, src.ptab_b + L.w_pp[1], n);
+      b1 = WindowView{end, L.NWp, pd_b.w_chi_min[0], pd_b.w_chi_max[0]};
+      b2 = WindowView{end + n, L.NWp, pd_b.w_chi_min[1], pd_b.w_chi_max[1]};
+      end += 2 * n;
+    }
+    return end;
+  }
+  // the four window values at chi, in the reference's order a1, a2, b1, b2
+  __device__ __forceinline__ void at(double chi, double& a1, double& a2, double& b1v,
+                                     double& b2v) const {
+    a1 = P.wa(chi);
+    a2 = P.wb(chi);
+    if constexpr (FOUR) {
+      b1v = b1(chi);
+      b2v = b2(chi);
+    } else {
+      b1v = a1;
+      b2v = a2;
+    }
+  }
+  static __host__ __device__ int doubles(const ProjLayout& L) {
+    return ProjLds::doubles(L) + (FOUR ? 8 * (L.NWp - 1) : 0);
+  }
+};
+// Dynamic LDS of k_ssc_table / k_ng_table, in doubles.
+inline int ssc_table_lds_doubles(const ProjLayout& L, int NS, bool four) {
+  return (four ? CovWindows<true>::doubles(L) : CovWindows<false>::doubles(L)) + 5 * NS - 4;
+}
+inline int ng_table_lds_doubles(const ProjLayout& L, bool four) {
+  return four ? CovWindows<true>::doubles(L) : CovWindows<false>::doubles(L);
+}
+
+// kernel.py:1103-1111 (_kernel_NG_integrand): a1 a2 b1 b2 D^4 / chi^2 J0 J0 in the reference's
+// order of operations (norm = 1 multiplies exactly); with a1 = b1, a2 = b2 of a matching block
+// that is wa wb wa wb.
+template <bool FOUR>
+__device__ __forceinline__ double ssc_ng_integrand(const CovWindows<FOUR>& W, const BesselTab* B,
                                                    double chi, double kta, double ktb,
                                                    double norm = 1.0) {
-  const double D = P.me.growth_factor(P.me.redshift(chi));
-  const double wa = P.wa(chi), wb = P.wb(chi);
-  return norm * wa * wb * wa * wb * D * D * D * D / (chi * chi) * bessel_j<0>(kta * chi, *B) *
+  const double D = W.P.me.growth_factor(W.P.me.redshift(chi));
+  double a1, a2, b1, b2;
+  W.at(chi, a1, a2, b1, b2);
+  return norm * a1 * a2 * b1 * b2 * D * D * D * D / (chi * chi) * bessel_j<0>(kta * chi, *B) *
          bessel_j<0>(ktb * chi, *B);
 }
 
-// kernel.py:1208-1215 (_kernel_ssc_integrand) as raw_kernel_ssc calls it: the Romberg variable
+// kernel.py:1197-1206 (_kernel_ssc_integrand) as raw_kernel_ssc calls it: the Romberg variable
 // is x = ln chi, and it is what the integrand receives as chi -- every factor is evaluated at x.
 // Where sigma^2(x) or a window is 0 the value is 0 (numpy multiplies the zero into finite
 // numbers there; a J0 or growth of a negative x is never formed).
+template <bool FOUR>
 struct SscKernelIntegrand {
-  const ProjLds* P;
+  const CovWindows<FOUR>* W;
   const Sigma2View* S;
   const BesselTab* B;
   double kta, ktb, norm;
   __device__ __forceinline__ double operator()(double x) const {
     const double s2 = (*S)(x);
     if (s2 == 0.0) return 0.0;
-    const double wa = P->wa(x), wb = P->wb(x);
-    if (wa == 0.0 || wb == 0.0) return 0.0;
-    const double D = P->me.growth_factor(P->me.redshift(x));
-    return norm * wa * wb * wa * wb * D * D * D * D * D * D * s2 / x *
+    double a1, a2, b1, b2;
+    W->at(x, a1, a2, b1, b2);
+    if (a1 == 0.0 || a2 == 0.0) return 0.0;
+    if constexpr (FOUR)
+      if (b1 == 0.0 || b2 == 0.0) return 0.0;
+    const double D = W->P.me.growth_factor(W->P.me.redshift(x));
+    return norm * a1 * a2 * b1 * b2 * D * D * D * D * D * D * s2 / x *
            bessel_j<0>(kta * x, *B) * bessel_j<0>(ktb * x, *B);
   }
 };
@@ -109,26 +182,42 @@ struct SscKernelIntegrand {
 // MultiEpoch.sigma_r(chi, 0)^2 from the device's sigma(R)), the ln k theta knots and z_bar_NG
 // (kernel.py:961-972: the first argmax over linspace(z_min, z_max, N) of W^4 D^4 / chi^2, chi
 // floored at window_precision), its chi and MultiEpoch.growth_factor (covariance.py:143).
+// FOUR: the four windows of a cross block and their common range -- z_min = max, z_max = min of the
+// two sides', chi_min = max(window_precision, chi(z_min)), chi_max = chi(z_max) on slot 0's
+// MultiEpoch (kernel.py:910-931).  The range goes into the scalars in both cases.
+template <bool FOUR>
 __global__ __launch_bounds__(256) void k_ssc_prep(chomp_config cfg, ProjLayout L, SscLayout S,
-                                                  const ProjDev* __restrict__ pdg,
-                                                  const double* __restrict__ ptab,
-                                                  double ln_kt_min, double ln_kt_max,
+                                                  CovSrc src, double ln_kt_min, double ln_kt_max,
                                                   double j0_limit, double* __restrict__ st) {
   __shared__ double cand[256];
   __shared__ double work[2 * 256];
-  const ProjDev& pd = *pdg;
+  const ProjDev& pd = *src.pd;
+  const double* ptab = src.ptab;
   const MEView me = me_view(L, pd, ptab, 0);
   const WindowView wa{ptab + L.w_pp[0], L.NWp, pd.w_chi_min[0], pd.w_chi_max[0]};
   const WindowView wb{ptab + L.w_pp[1], L.NWp, pd.w_chi_min[1], pd.w_chi_max[1]};
+  WindowView wc = wa, wd = wb;
+  double z_min = pd.z_min, z_max = pd.z_max, chi_min = pd.chi_min, chi_max = pd.chi_max;
+  if constexpr (FOUR) {
+    const ProjDev& pb = *src.pd_b;
+    wc = WindowView{src.ptab_b + L.w_pp[0], L.NWp, pb.w_chi_min[0], pb.w_chi_max[0]};
+    wd = WindowView{src.ptab_b + L.w_pp[1], L.NWp, pb.w_chi_min[1], pb.w_chi_max[1]};
+    z_min = pb.z_min > z_min ? pb.z_min : z_min;
+    z_max = pb.z_max < z_max ? pb.z_max : z_max;
+    const double c0 = me.comoving_distance(z_min);
+    chi_min = cfg.window_precision > c0 ? cfg.window_precision : c0;
+    chi_max = me.comoving_distance(z_max);
+  }
   const int t = threadIdx.x;
   for (int i = t; i < S.N; i += blockDim.x) st[S.kx + i] = linspace_at(ln_kt_min, ln_kt_max, S.N, i);
   if (t < S.N) {
-    const double z = linspace_at(pd.z_min, pd.z_max, S.N, t);
+    const double z = linspace_at(z_min, z_max, S.N, t);
     double chi = me.comoving_distance(z);
     if (!(chi > cfg.window_precision)) chi = cfg.window_precision;
     const double D = me.growth_factor(me.redshift(chi));
     const double a = wa(chi), b = wb(chi);
-    cand[t] = a * b * a * b * D * D * D * D / (chi * chi);
+    const double c = FOUR ? wc(chi) : a, d = FOUR ? wd(chi) : b;
+    cand[t] = a * b * c * d * D * D * D * D / (chi * chi);
   }
   __syncthreads();
   if (t != 0) return;
@@ -137,42 +226,68 @@ __global__ __launch_bounds__(256) void k_ssc_prep(chomp_config cfg, ProjLayout L
   int best = 0;
   for (int i = 1; i < S.N && !isnan(cand[best]); ++i)
     if (isnan(cand[i]) || cand[i] > cand[best]) best = i;
-  const double zb = linspace_at(pd.z_min, pd.z_max, S.N, best);
+  const double zb = linspace_at(z_min, z_max, S.N, best);
   st[S.scal + kSscZBar] = zb;
   st[S.scal + kSscChiPeak] = me.comoving_distance(zb);
   st[S.scal + kSscDz] = me.growth_factor(zb);
   st[S.scal + kSscLnMin] = ln_kt_min;
   st[S.scal + kSscLnMax] = ln_kt_max;
   st[S.scal + kSscLimit] = j0_limit;
+  st[S.scal + kSscZMin] = z_min;
+  st[S.scal + kSscZMax] = z_max;
+  st[S.scal + kSscChiMin] = chi_min;
+  st[S.scal + kSscChiMax] = chi_max;
+}
+
+// grid 1, block 64: out[4] = z_min, z_max, chi_min, chi_max of a cross block's four windows, as
+// k_ssc_prep<true> finds them -- what the host lays the sigma^2 knots over before that launch.
+__global__ void k_cov_cross_range(chomp_config cfg, ProjLayout L, CovSrc src,
+                                  double* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  const ProjDev& pd = *src.pd;
+  const ProjDev& pb = *src.pd_b;
+  const MEView me = me_view(L, pd, src.ptab, 0);
+  const double z_min = pb.z_min > pd.z_min ? pb.z_min : pd.z_min;
+  const double z_max = pb.z_max < pd.z_max ? pb.z_max : pd.z_max;
+  const double c0 = me.comoving_distance(z_min);
+  out[0] = z_min;
+  out[1] = z_max;
+  out[2] = cfg.window_precision > c0 ? cfg.window_precision : c0;
+  out[3] = me.comoving_distance(z_max);
 }
 
 // grid n integrals, block 256.  ln_a == nullptr: the knot table of _initialize_ssc_spline
 // (kernel.py:1132-1153), block b -> the b-th (i, j), i <= j, of the upper triangle, written to
 // [i][j] and [j][i] with its Romberg level; otherwise raw_kernel_ssc(ln_a[b], ln_b[b]) into out.
+template <bool FOUR>
 __global__ __launch_bounds__(256) void k_ssc_table(chomp_config cfg, ProjLayout L, SscLayout S,
-                                                   const ProjDev* __restrict__ pdg,
-                                                   const double* __restrict__ ptab,
+                                                   CovSrc src,
                                                    const BesselTab* __restrict__ bess_g,
                                                    double* __restrict__ st,
                                                    const double* __restrict__ ln_a,
                                                    const double* __restrict__ ln_b,
                                                    double* __restrict__ out) {
   extern __shared__ __align__(16) double sm[];
-  __shared__ ProjDev pd;
+  __shared__ ProjDev pd, pd_b;      // (pd_b: FOUR only)
   __shared__ BesselTab B;
   __shared__ double red[romberg_scratch<4, 2>()];
-  copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(src.pd), kProjDoubles);
+  if constexpr (FOUR)
+    copy_doubles(reinterpret_cast<double*>(&pd_b), reinterpret_cast<const double*>(src.pd_b),
+                 kProjDoubles);
   copy_doubles(reinterpret_cast<double*>(&B), reinterpret_cast<const double*>(bess_g),
                (int)(sizeof(BesselTab) / sizeof(double)));
   __syncthreads();
-  ProjLds P;
-  double* sx = P.stage(L, pd, ptab, sm);
+  CovWindows<FOUR> P;
+  double* sx = P.stage(L, src, pd, pd_b, sm);
   double* spp = sx + S.NS;
   copy_doubles(sx, st + S.sx, S.NS);
   copy_doubles(spp, st + S.spp, 4 * (S.NS - 1));
-  P.bess = &B;
+  P.P.bess = &B;
   __syncthreads();
-  const Sigma2View sig{sx, spp, S.NS, pd.chi_min, pd.chi_max};
+  // the common range of the windows (k_ssc_prep; pd's own for a matching block)
+  const double chi_lo = st[S.scal + kSscChiMin], chi_hi = st[S.scal + kSscChiMax];
+  const Sigma2View sig{sx, spp, S.NS, chi_lo, chi_hi};
   int i = 0, j = 0;
   double la, lb;
   if (ln_a) {
@@ -192,14 +307,14 @@ __global__ __launch_bounds__(256) void k_ssc_table(chomp_config cfg, ProjLayout 
   double v = 0.0;
   int level = 0;
   bool zero = false;
-  if (chi_max >= pd.chi_max) chi_max = pd.chi_max;
-  else if (chi_max <= pd.chi_min) zero = true;
+  if (chi_max >= chi_hi) chi_max = chi_hi;
+  else if (chi_max <= chi_lo) zero = true;
   if (!zero) {
     // the norm passes ln(k theta_a) where k theta_a belongs (kernel.py:1178-1183)
     const double inv = ssc_ng_integrand(P, &B, st[S.scal + kSscChiPeak], la, la);
     const double norm = (inv > 1e-16 || inv < -1e-16) ? 1.0 / inv : 1.0;
-    SscKernelIntegrand f{&P, &sig, &B, kta, ktb, norm};
-    const double r = romberg1<4>(f, log(pd.chi_min), log(chi_max), cfg.global_precision,
+    SscKernelIntegrand<FOUR> f{&P, &sig, &B, kta, ktb, norm};
+    const double r = romberg1<4>(f, log(chi_lo), log(chi_max), cfg.global_precision,
                                  cfg.kernel_precision, cfg.divmax, red, &level);
     v = r * (16.0 * kPi * kPi / 9.0) / norm;
   }
@@ -358,6 +473,7 @@ struct SscRow {
 // covariance.py:765-776 (_kb_ssc_integrand): k_b^2 R(k_a) R(k_b) kernel_ssc(ln k_a theta_a,
 // ln k_b theta_b), norm = 1, with R = dln_power_ddelta_b of the context's epoch -- the Stage E
 // function itself (PowerEval, CHOMP_P_SSC_RESPONSE), exactly 0 outside [k_min, k_max].
+// In a cross block R(k_a) is halo_a's (in ra) and P is halo_b's response (:771-772).
 template <bool BAO>
 struct SscKbIntegrand {
   const PowerEval* P;
@@ -397,6 +513,45 @@ __global__ __launch_bounds__(256) void k_ssc_kb(chomp_config cfg, TabLayout HL, 
   __syncthreads();
   P.template finish_t<BAO>();
   SscKbIntegrand<BAO> f{&P, &K, P.template eval_t<BAO>(ka), theta_b[pair]};
+  int level = 0;
+  const double v = romberg1<4>(f, ln_k_min, ln_k_max, cfg.global_precision, cfg.corr_precision,
+                               cfg.divmax, red, &level);
+  if (threadIdx.x == 0) {
+    knots[(size_t)pair * NK + i] = v;
+    if (levels) levels[(size_t)pair * NK + i] = (double)level;
+  }
+}
+
+// k_ssc_kb of a cross block: R(k_a) from slot 0's epoch (halo_a at z_bar_a) and R(k_b) from
+// slot 1's (halo_b at z_bar_b), both CHOMP_P_SSC_RESPONSE, staged side by side in LDS as
+// k_cov_cross_knots stages its two spectra.  LDS: ssc_kb_cross_lds_doubles.
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_ssc_kb_cross(chomp_config cfg, TabLayout HL, SscLayout S,
+                                                      CrossLayout C,
+                                                      const double* __restrict__ ct,
+                                                      const double* __restrict__ st,
+                                                      const double* __restrict__ theta_a,
+                                                      const double* __restrict__ theta_b,
+                                                      double* __restrict__ knots,
+                                                      double* __restrict__ levels) {
+  extern __shared__ __align__(16) double sm[];
+  __shared__ Epoch Ea, Eb;
+  __shared__ double red[romberg_scratch<4, 2>()];
+  copy_doubles(reinterpret_cast<double*>(&Ea), ct + C.ep[0], kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&Eb), ct + C.ep[1], kEpochDoubles);
+  __syncthreads();
+  PowerEval Pa, Pb;
+  Pa.stage(cfg, HL, &Ea, ct + C.htab[0], CHOMP_P_SSC_RESPONSE, sm);
+  Pb.stage(cfg, HL, &Eb, ct + C.htab[1], CHOMP_P_SSC_RESPONSE, sm + 12 * (HL.NK - 1));
+  const int i = blockIdx.x, pair = blockIdx.y, NK = cfg.kernel_npoints;
+  const double ln_k_min = log(cfg.k_min), ln_k_max = log(cfg.k_max);
+  const double ka = exp(linspace_at(ln_k_min, ln_k_max, NK, i));
+  SscRow K;
+  K.build(ssc_spline(S, st), log(ka * theta_a[pair]), sm + 24 * (HL.NK - 1));
+  __syncthreads();
+  Pa.template finish_t<BAO>();
+  Pb.template finish_t<BAO>();
+  SscKbIntegrand<BAO> f{&Pb, &K, Pa.template eval_t<BAO>(ka), theta_b[pair]};
   int level = 0;
   const double v = romberg1<4>(f, ln_k_min, ln_k_max, cfg.global_precision, cfg.corr_precision,
                                cfg.divmax, red, &level);
@@ -469,7 +624,7 @@ inline NgLayout make_ng_layout(int N) {
   NgLayout G;
   G.N = N;
   int o = 0;
-  G.scal = o; o += 8;
+  G.scal = o; o += 16;
   G.kx = o; o += N;
   G.tab = o; o += N * N;
   G.lev = o; o += N * N;
@@ -480,7 +635,7 @@ inline NgLayout make_ng_layout(int N) {
   G.total = (o + 7) & ~7;
   return G;
 }
-// scalars 0..5 as kSsc* (kSscLimit holds _j0_limit here), then min(table)
+// scalars 0..5 and 8..11 as kSsc* (kSscLimit holds _j0_limit here), and min(table)
 constexpr int kNgMin = 6;
 
 // Device block of an uploaded I_0^4 table: ln k knots | table | bicubic | scratch.
@@ -510,14 +665,16 @@ __global__ __launch_bounds__(256) void k_ng_prep(SscLayout S, NgLayout G,
                                                  unsigned* __restrict__ status) {
   const int t = threadIdx.x;
   for (int i = t; i < G.N; i += blockDim.x) ng[G.kx + i] = st[S.kx + i];
-  if (t < 8) ng[G.scal + t] = t == kSscLimit ? j0_limit : (t < kSscLimit ? st[S.scal + t] : 0.0);
+  if (t < 16)
+    ng[G.scal + t] = t == kSscLimit ? j0_limit : (t < kSscLimit || t >= kSscZMin ? st[S.scal + t] : 0.0);
   if (t == 0 && status) atomicAnd(status, ~kStCovNgDivmax);
 }
 
 // kernel.py:1103-1111 (_kernel_NG_integrand) with the norm of raw_kernel_NG; the Romberg
 // variable is chi itself.
+template <bool FOUR>
 struct NgKernelIntegrand {
-  const ProjLds* P;
+  const CovWindows<FOUR>* P;
   const BesselTab* B;
   double kta, ktb, norm;
   __device__ __forceinline__ double operator()(double chi) const {
@@ -525,13 +682,13 @@ struct NgKernelIntegrand {
   }
 };
 
-// grid n integrals, block 256, LDS ProjLds::doubles.  ln_a == nullptr: the knot table of
+// grid n integrals, block 256, LDS ng_table_lds_doubles.  ln_a == nullptr: the knot table of
 // _initialize_NG_spline (kernel.py:1016-1030), block b -> the b-th (i, j), i <= j, of the upper
 // triangle, written to [i][j] and [j][i] with its Romberg level; otherwise
 // raw_kernel_NG(ln_a[b], ln_b[b]) into out.
+template <bool FOUR>
 __global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L, NgLayout G,
-                                                  const ProjDev* __restrict__ pdg,
-                                                  const double* __restrict__ ptab,
+                                                  CovSrc src,
                                                   const BesselTab* __restrict__ bess_g,
                                                   double* __restrict__ ng,
                                                   const double* __restrict__ ln_a,
@@ -539,17 +696,22 @@ __global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L
                                                   double* __restrict__ out,
                                                   unsigned* __restrict__ status) {
   extern __shared__ __align__(16) double sm[];
-  __shared__ ProjDev pd;
+  __shared__ ProjDev pd, pd_b;      // (pd_b: FOUR only)
   __shared__ BesselTab B;
   __shared__ double red[romberg_scratch<4, 2>()];
-  copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(src.pd), kProjDoubles);
+  if constexpr (FOUR)
+    copy_doubles(reinterpret_cast<double*>(&pd_b), reinterpret_cast<const double*>(src.pd_b),
+                 kProjDoubles);
   copy_doubles(reinterpret_cast<double*>(&B), reinterpret_cast<const double*>(bess_g),
                (int)(sizeof(BesselTab) / sizeof(double)));
   __syncthreads();
-  ProjLds P;
-  P.stage(L, pd, ptab, sm);
-  P.bess = &B;
+  CovWindows<FOUR> P;
+  P.stage(L, src, pd, pd_b, sm);
+  P.P.bess = &B;
   __syncthreads();
+  // the common range of the windows (k_ssc_prep, through k_ng_prep; pd's own for a matching block)
+  const double chi_lo = ng[G.scal + kSscChiMin], chi_hi = ng[G.scal + kSscChiMax];
   int i = 0, j = 0;
   double la, lb;
   if (ln_a) {
@@ -569,15 +731,15 @@ __global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L
   double v = 0.0;
   int level = 0;
   bool zero = false, converged = true;
-  if (chi_max >= pd.chi_max) chi_max = pd.chi_max;
-  else if (chi_max <= pd.chi_min) zero = true;
+  if (chi_max >= chi_hi) chi_max = chi_hi;
+  else if (chi_max <= chi_lo) zero = true;
   if (!zero) {
     // the norm passes ln(k theta_a) where k theta_a belongs (kernel.py:1055-1056)
     const double inv = ssc_ng_integrand(P, &B, ng[G.scal + kSscChiPeak], la, la, 1.0);
     const double norm = (inv > 1e-16 || inv < -1e-16) ? 1.0 / inv : 1.0;
-    const NgKernelIntegrand f{&P, &B, kta, ktb, norm};
-    Scalar1<NgKernelIntegrand> w{f};
-    const RombergOut<1> r = romberg_group<4, 1>(w, pd.chi_min, chi_max, cfg.global_precision,
+    const NgKernelIntegrand<FOUR> f{&P, &B, kta, ktb, norm};
+    Scalar1<NgKernelIntegrand<FOUR>> w{f};
+    const RombergOut<1> r = romberg_group<4, 1>(w, chi_lo, chi_max, cfg.global_precision,
                                                 cfg.kernel_precision, cfg.divmax, red);
     v = r.value[0] / norm;
     level = r.level[0];

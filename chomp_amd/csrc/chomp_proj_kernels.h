@@ -98,6 +98,8 @@ struct ProjState {
   int ssc_ns = 0;          // sigma^2 knots of that set-up
   double* d_ssc = nullptr;
   size_t cap_ssc = 0;      // doubles allocated at d_ssc
+  bool ssc_four = false;   // that state is of the four windows of a cross block (chomp_kernel_ssc_setup_cross)
+  bool ng_four = false;    // ... and so is the kernel_NG state built from it
   bool ng_prep = false;    // kernel_NG scalars and knots (chomp_kernel_ng_setup) valid
   bool ng_ready = false;   // ... and the kernel_NG table with its log-offset bicubic
   double* d_ng = nullptr;
@@ -2069,6 +2071,8 @@ struct CrossState {
   CrossLayout C;
   bool staged[2] = {false, false};   // slot holds a snapshot (chomp_covariance_cross_stage)
   int which[2] = {0, 0};   // ... of this spectrum
+  bool response[2] = {false, false};   // ... whose knot tables hold the super-sample response
+  double z_min[2] = {0, 0}, z_max[2] = {0, 0};   // ... and this redshift range of its two windows
   bool ready = false;      // the four tables and their splines (chomp_covariance_table_cross) valid
 };
 // Dynamic LDS of k_cov_cross_knots, in doubles: two PowerEval stagings, the MultiEpoch of

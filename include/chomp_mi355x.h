@@ -722,6 +722,8 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area,
  * correlation's z_bar by the caller (:465-466).  Later changes of `src` do not reach the
  * snapshot.  Both contexts must be on one device and share configuration and transfer function
  * (CHOMP_ERR_SCOPE otherwise).  When src is another context the call waits for both streams.
+ * which = CHOMP_CROSS_WINDOWS takes the projection set-up alone (src needs no halo epoch): enough
+ * for the kernels of the four windows, chomp_kernel_ssc_setup_cross and what follows it.
  *
  * chomp_covariance_table_cross replaces Covariance._initialize_halo_splines for the block: on
  * kernel_npoints knots in ln K from ln(k_min min(chi_min_a, chi_min_b)) to
@@ -738,6 +740,7 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area,
  * of the block: theta holds theta_a[n] then theta_b[n] (radians); poisson_p is
  * proj_power_poisson(window_pair = p) (:427-428, 443-444); j0_limit and area as in
  * chomp_covariance_gaussian. */
+#define CHOMP_CROSS_WINDOWS (-1)
 int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int which,
                                  size_t epoch);
 int chomp_covariance_table_cross(chomp_ctx* ctx, double D_a, double D_b, double* ln_K,
@@ -780,6 +783,37 @@ int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, doub
 int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out);
 int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double* theta,
                          size_t n, double* out, double* kb_knots, double* kb_levels);
+
+/* The super-sample and trispectrum terms of a cross block, Covariance(corr_a, corr_b,
+ * cross_terms=True): KernelCovariance with a1 != b1 or a2 != b2 (kernel.py:893-972, 1035-1111,
+ * 1155-1206) and _kb_ssc_integrand with halo_a at k_a and halo_b at k_b (covariance.py:763-776).
+ * Everything works from the two slots of chomp_covariance_cross_stage: slot 0 holds a1, a2 and
+ * the MultiEpoch (correlation a's throughout, kernel.py:918-931), slot 1 holds b1, b2.  The window
+ * product is a1 a2 b1 b2 in that order.  Host memory throughout.
+ *
+ * chomp_covariance_cross_range gives info[4] = z_min, z_max, chi_min, chi_max of the four windows:
+ * z_min the largest of their z_min, z_max the smallest of their z_max, chi_min =
+ * max(window_precision, chi(z_min)), chi_max = chi(z_max) (kernel.py:910-931) -- the range the
+ * caller lays the sigma^2 knots over.  Windows with no redshift in common (z_min >= z_max) are
+ * CHOMP_ERR_SCOPE, here and in the calls below, before anything is launched.
+ *
+ * chomp_kernel_ssc_setup_cross is chomp_kernel_ssc_setup for those four windows: same
+ * arguments, limits, norm, tolerances and outputs.  The kernel_ssc state of the context is
+ * then the block's: chomp_kernel_ssc_raw / _eval, chomp_kernel_ng_setup / _raw / _eval and
+ * chomp_covariance_ng serve it unchanged (chomp_kernel_ng_setup takes its windows from where the
+ * kernel_ssc state took them).  Staging a slot again drops it.
+ *
+ * chomp_covariance_ssc_cross is chomp_covariance_ssc with two responses: dlnP_mm/ddelta_b of
+ * slot 0's epoch at k_a and of slot 1's at k_b (both snapshots must have been taken with the
+ * families h_m, pp_mm and i_1_2 built: CHOMP_ERR_STATE otherwise).  The order of the arguments
+ * matters: (theta_a, theta_b) is not (theta_b, theta_a). */
+int chomp_covariance_cross_range(chomp_ctx* ctx, double* info);
+int chomp_kernel_ssc_setup_cross(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
+                                 double j0_ssc_limit, const double* ln_chi, const double* sigma2,
+                                 size_t n_sigma, int with_table, double* info, double* table,
+                                 double* levels);
+int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta, size_t n,
+                               double* out, double* kb_knots, double* kb_levels);
 
 /* One-halo trispectrum term of the covariance of w(theta), Covariance(corr, corr,
  * nongaussian_cov=True, input_halo_trispectrum=HaloTrispectrumOneHalo), with a1 = b1 = window a
