@@ -147,6 +147,8 @@ EXPORTS = [
     "chomp_covariance_cross_range", "chomp_kernel_ssc_setup_cross", "chomp_covariance_ssc_cross",
     "chomp_set_general_profile", "chomp_y_general", "chomp_y_general_table",
     "chomp_halo_normalization",
+    "chomp_covariance_fourier_zbar", "chomp_covariance_fourier_table",
+    "chomp_covariance_fourier_gaussian",
 ]
 
 # chomp_get_status bits (include/chomp_mi355x.h)
@@ -452,6 +454,10 @@ def lib():
         L.chomp_covariance_cross_range.argtypes = [vp, c_double_p]
         L.chomp_kernel_ssc_setup_cross.argtypes = L.chomp_kernel_ssc_setup.argtypes
         L.chomp_covariance_ssc_cross.argtypes = [vp, d, vp, sz, vp, vp, vp]
+        L.chomp_covariance_fourier_zbar.argtypes = [vp, c_double_p, sz, c_double_p]
+        L.chomp_covariance_fourier_table.argtypes = [vp, i, ctypes.POINTER(sz), c_double_p, sz,
+                                                     c_double_p, c_double_p, c_double_p]
+        L.chomp_covariance_fourier_gaussian.argtypes = [vp, vp, sz, vp, i]
         L.chomp_kernel_ng_setup.argtypes = [vp, d, i, c_double_p, c_double_p, c_double_p]
         L.chomp_kernel_ng_raw.argtypes = [vp, vp, sz, vp]
         L.chomp_kernel_ng_eval.argtypes = [vp, vp, sz, vp]
@@ -680,6 +686,11 @@ class Context(object):
         self._check(self._L.chomp_epochs_set(self._h, n, arr,
                                              z.ctypes.data_as(c_double_p)))
         self.n_epoch = n
+
+    def set_transfer(self, with_bao):
+        """The transfer function alone (epochs_set sets it as well): contexts that exchange
+        snapshots must agree on it."""
+        self._check(self._L.chomp_set_transfer(self._h, 1 if with_bao else 0))
 
     def mass_setup(self, halo, mf_kind):
         arr = halo if isinstance(halo, ctypes.Array) else self.pack_halo(halo, self.n_epoch)
@@ -1231,6 +1242,37 @@ class Context(object):
         if knots:
             return outs[0], outs[1], outs[2].astype(int)
         return outs[0]
+
+    def covariance_fourier_zbar(self, z):
+        """_calculate_zbar of the four window pairs a1a2, b1b2, a1b2, b1a2 in the two staged slots
+        on the grid z: [4, 7] = z_min, z_max, z_bar, chi(z_bar), chi(z_min), chi(z_max),
+        growth_factor(z_bar) per pair."""
+        z = numpy.ascontiguousarray(z, dtype=numpy.float64)
+        info = numpy.empty((4, 7))
+        self._check(self._L.chomp_covariance_fourier_zbar(
+            self._h, z.ctypes.data_as(c_double_p), z.size, info.ctypes.data_as(c_double_p)))
+        return info
+
+    def covariance_fourier_table(self, which, epochs, ln_l):
+        """The four Limber tables of CovarianceFourier over the knots ln_l, pair X from spectrum
+        `which` of halo epoch epochs[X]: (norms [4], tables [4, n] = integral / D(z_bar)^2, Romberg
+        levels [4, n])."""
+        x = numpy.ascontiguousarray(ln_l, dtype=numpy.float64)
+        n = x.size
+        ep = (ctypes.c_size_t * 4)(*[int(e) for e in epochs])
+        norms, tab, lev = numpy.empty(4), numpy.empty((4, n)), numpy.empty((4, n))
+        self._check(self._L.chomp_covariance_fourier_table(
+            self._h, int(which), ep, x.ctypes.data_as(c_double_p), n,
+            norms.ctypes.data_as(c_double_p), tab.ctypes.data_as(c_double_p),
+            lev.ctypes.data_as(c_double_p)))
+        return norms, tab, lev.astype(int)
+
+    def covariance_fourier_gaussian(self, ln_l_and_l):
+        """[5, n]: the four _pl_X and covariance_G at n multipoles; the argument holds ln l[n] then
+        l[n] (a host array, or a contiguous float64 torch cuda tensor: the result stays on the
+        device then)."""
+        return self._run(self._L.chomp_covariance_fourier_gaussian, [ln_l_and_l],
+                         lambda mem, new, x: (x, _numel(x) // 2, new((5, _numel(x) // 2)), mem))[0]
 
     def kernel_ng_setup(self, j0_limit, with_table=True):
         """Trispectrum kernel of the context's windows, after kernel_ssc_setup.  Returns (table,

@@ -1,6 +1,7 @@
 """covariance.Covariance and CovarianceMulti for the Gaussian, super-sample and one-halo
 trispectrum parts of the w(theta) covariance (covariance.py:23-871, 1085-1103), the consumer of
-P(k) and the windows that SURVEY.md 8(f) ranks fourth.
+P(k) and the windows that SURVEY.md 8(f) ranks fourth; and covariance.CovarianceFourier, the
+Gaussian covariance of C_l (covariance.py:874-1083).
 
 Accelerated: ``Covariance(corr, corr, nongaussian_cov=False)`` -- the use of
 examples/example_covariance_script.py: the projected spectrum over ln K
@@ -38,7 +39,12 @@ without the keyword a cross block refuses the two terms as before.  ``Covariance
 
 Outside the scope (ChompScopeError): ``nongaussian_cov=True`` without a HaloTrispectrumOneHalo,
 the full ``HaloTrispectrum``, the trispectrum and super-sample terms of a cross block without
-``cross_terms=True``, four windows with no redshift in common, and ``CovarianceFourier``.
+``cross_terms=True``, and four windows with no redshift in common.
+
+``CovarianceFourier(l_min, l_max, KernelCovariance(...), Halo(...))`` (covariance.py:874-1083) is the
+Gaussian covariance of C_l: z_bar of the four window pairs, four P_mm epochs in the halo's
+context, the four Limber tables over ln l (4 x corr_npoints Romberg integrals in one launch),
+their splines, and ``covariance_G(l)`` element-wise on the device.
 """
 import numpy
 from scipy import special
@@ -832,6 +838,220 @@ class CovarianceMulti(Covariance):
                 self.wcovar[row_ndx1:row_ndx2, col_ndx1:col_ndx2] = cov.covar
                 self.wcovar[col_ndx1:col_ndx2, row_ndx1:row_ndx2] = cov.covar
         return self.wcovar
+
+
+class CovarianceFourier(object):
+    """covariance.py:874-1083: the Gaussian covariance of C_l.  Four Limber spectra over ln l,
+    one per window pair X = a1a2, b1b2, a1b2, b1a2, each P_mm at that pair's z_bar:
+    ``covariance_G(l) = (pl_a1a2 pl_b1b2 + pl_a1b2 pl_b1a2) / (2 l + 1)``.
+
+    Reproduced as shipped, quirks included: z_bar is the first argmax of w1 w2 / chi^2 D^2 on
+    linspace(min z_min_X, max z_max_X, kernel_npoints) (:1067-1075; windows that reach down to
+    window_precision put it at the first grid point); the norms take the windows a1 and a2
+    whatever the pair, l = chi (k = 1) and halo_a1a2's spectrum for a1b2 (:987-1006); the tables
+    are integral / D(z_bar)^2 with the norm still in (:1048-1063), so _pl_X is C_l / D(z_bar)^2;
+    ``covariance(l_a, l_b)`` is empty and returns None; ``input_halo`` itself is halo_a1a2 and is
+    moved to z_bar_a1a2.  The two print statements are dropped.
+
+    One deviation: the reference's other three halos are ``copy(input_halo)``, shallow copies that
+    share one MassFunction which every set_redshift moves (halo.py:159), so with four different
+    z_bar each halo integrates its tables with the mass function of the last redshift set.  Here
+    the four are independent epochs (deep-copy semantics); where the z_bar coincide the two agree.
+
+    Only the four windows and the MultiEpoch of the KernelCovariance are read: neither kernel_ssc
+    nor kernel_NG is built, whatever its ``four_windows``.  Outside the scope (ChompScopeError,
+    before anything is launched): no KernelCovariance, an ``input_halo`` that is not exactly a
+    halo.Halo with an NFW profile, a pair of windows with no redshift in common."""
+
+    _PAIRS = ("a1a2", "b1b2", "a1b2", "b1a2")
+
+    def __init__(self, l_min, l_max, input_kernel_covariance=None, input_halo=None,
+                 input_halo_trispectrum=None, **kws):
+        if input_kernel_covariance is None:
+            raise _lib.ChompScopeError(
+                "CovarianceFourier needs a KernelCovariance (input_kernel_covariance): the "
+                "reference's default, None, fails at its first attribute (covariance.py:887)")
+        if type(input_halo) is not halo_mod.Halo or input_halo._general_profile:
+            raise _lib.ChompScopeError(
+                "CovarianceFourier is accelerated for an input_halo that is exactly a chomp_amd "
+                "halo.Halo with an NFW profile, not %s: its four spectra are four epochs of one "
+                "halo model" % ("a general_profile Halo" if type(input_halo) is halo_mod.Halo
+                                else type(input_halo).__name__))
+        self._ln_l_min = numpy.log(l_min)
+        self._ln_l_max = numpy.log(l_max)
+        self._ln_l_array = numpy.linspace(self._ln_l_min, self._ln_l_max,
+                                          defaults.default_precision["corr_npoints"])
+        self.kernel = input_kernel_covariance
+        self._refresh_ranges()
+        self.window_a1 = self.kernel.window_function_a1.window_function
+        self.window_a2 = self.kernel.window_function_a2.window_function
+        self.window_b1 = self.kernel.window_function_b1.window_function
+        self.window_b2 = self.kernel.window_function_b2.window_function
+        self.halo_a1a2 = input_halo
+        self.halo_tri = input_halo_trispectrum
+        self._initialized_pl = False
+        self._table_key = None
+        self._side_kernels = None
+
+    def _windows(self):
+        k = self.kernel
+        return (k.window_function_a1, k.window_function_a2, k.window_function_b1,
+                k.window_function_b2)
+
+    def _refresh_ranges(self):
+        """covariance.py:887-910 (the reference sets these once, at construction; here they follow
+        the windows, so that the tables after a change are those of a new object)."""
+        a1, a2, b1, b2 = self._windows()
+        for name, (w1, w2) in zip(self._PAIRS, ((a1, a2), (b1, b2), (a1, b2), (b1, a2))):
+            z_min, z_max = numpy.max([w1.z_min, w2.z_min]), numpy.min([w1.z_max, w2.z_max])
+            if not z_min < z_max:
+                raise _lib.ChompScopeError(
+                    "CovarianceFourier: the windows of pair %s have no redshift in common (z_min "
+                    "= %g >= z_max = %g)" % (name, z_min, z_max))
+            setattr(self, "_z_min_" + name, z_min)
+            setattr(self, "_z_max_" + name, z_max)
+        self._z_array = numpy.linspace(
+            numpy.min([getattr(self, "_z_min_" + p) for p in self._PAIRS]),
+            numpy.max([getattr(self, "_z_max_" + p) for p in self._PAIRS]),
+            defaults.default_precision["kernel_npoints"])
+
+    def _kernels(self):
+        """Two Kernels of this object's own whose set-ups the two cross slots are staged from,
+        windows only: (a1, a2) with the MultiEpoch, and (b1, b2)."""
+        k = self.kernel
+        if self._side_kernels is None or self._side_kernels[2] != self._windows() + (k.cosmo,):
+            kt = (numpy.exp(k.ln_ktheta_min), numpy.exp(k.ln_ktheta_max))
+            a1, a2, b1, b2 = self._windows()
+            self._side_kernels = (kernel_mod.Kernel(kt[0], kt[1], a1, a2, k.cosmo),
+                                  kernel_mod.Kernel(kt[0], kt[1], b1, b2, k.cosmo),
+                                  self._windows() + (k.cosmo,))
+        return self._side_kernels[:2]
+
+    @staticmethod
+    def _halo_key(h):
+        """What P_mm of a halo is built from apart from its redshift, readable without the
+        device (the HOD does not enter)."""
+        return (id(h), tuple(sorted(h.cosmo.cosmo_dict.items())),
+                bool(getattr(h.cosmo, "_with_bao", False)), tuple(sorted(h.mass.halo_dict.items())),
+                h.mass._kind, repr(sorted(h._profile_dict.items())), h.get_extrapolation())
+
+    def _tables(self):
+        """The device state in input_halo's context -- z_bar, the four epochs, the knot tables
+        and their splines -- rebuilt when anything it was built from has changed."""
+        h = self.halo_a1a2
+        if type(h) is not halo_mod.Halo or h._general_profile:
+            raise _lib.ChompScopeError("CovarianceFourier: halo_a1a2 must be a halo.Halo (NFW)")
+        ctx = h._context()
+        ka, kb = self._kernels()
+        cfg = ctx.config
+        key = (id(ctx), ka._signature(), kb._signature(), self._halo_key(h), self._ln_l_min,
+               self._ln_l_max, cfg.corr_npoints, cfg.kernel_npoints)
+        if (key == self._table_key and self._initialized_pl and
+                getattr(ctx, "_cov_fourier_owner", None) is self):
+            return ctx
+        self._initialized_pl = False
+        self._refresh_ranges()
+        bao = bool(getattr(h.cosmo, "_with_bao", False))
+        for c in (ctx, ka._dev(), kb._dev()):
+            c.set_transfer(bao)
+        # (whoever owned the slots stages again when it next needs them)
+        ctx._cov_cross_owner = self
+        ctx.covariance_cross_stage(0, ka._dev(), _lib.CROSS_WINDOWS)
+        ctx.covariance_cross_stage(1, kb._dev(), _lib.CROSS_WINDOWS)
+        info = ctx.covariance_fourier_zbar(self._z_array)
+        z_bar = [float(v) for v in info[:, 2]]
+        for p, z in zip(self._PAIRS, z_bar):
+            setattr(self, "_z_bar_G_" + p, z)
+        self._pl_scalars = info
+        # covariance.py:968-971, with four independent halos: one epoch per distinct z_bar,
+        # input_halo's own first
+        h.set_redshift(z_bar[0])
+        distinct = sorted(set(z_bar), key=z_bar.index)
+        if len(distinct) == 1:
+            h._sync(_lib.FAM_MM)
+        else:
+            h._sync_epochs(distinct, _lib.FAM_MM)
+        epochs = [distinct.index(z) for z in z_bar]
+        norms, tab, lev = ctx.covariance_fourier_table(h._power_code(_lib.P_MM), epochs,
+                                                       self._ln_l_array)
+        for i, p in enumerate(self._PAIRS):
+            if not (numpy.isfinite(norms[i]) and norms[i] > 0.0):
+                raise ValueError(
+                    "CovarianceFourier._initialize_pl: the norm integrand of pair %s -- a1 a2 "
+                    "D^2 / chi^2 P_mm(k = 1) at chi(z_bar = %g) (covariance.py:987-1006) -- is "
+                    "not positive and finite (norm = %r): the windows a1 and a2 do not both "
+                    "cover that redshift; the reference's table would be inf / NaN"
+                    % (p, z_bar[i], float(norms[i])))
+        for i, p in enumerate(self._PAIRS):
+            setattr(self, "_norm_G_" + p, float(norms[i]))
+            self.__dict__["_pl_%s_array" % p] = tab[i]
+            self.__dict__["_pl_%s_levels" % p] = lev[i]
+        self._table_key = key
+        self._initialized_pl = True
+        ctx._cov_fourier_owner = self
+        return ctx
+
+    def _initialize_pl(self):
+        self._initialized_pl = False
+        self._tables()
+
+    def _calculate_zbar(self, window1, window2):
+        """covariance.py:1067-1075 for two of this object's windows (the bound window_function
+        methods the reference passes, or the window objects)."""
+        ws = self._windows()
+        owners = [getattr(w, "__self__", w) for w in (window1, window2)]
+        for i, p in enumerate(((0, 1), (2, 3), (0, 3), (2, 1))):
+            if owners[0] is ws[p[0]] and owners[1] is ws[p[1]]:
+                self._tables()
+                return getattr(self, "_z_bar_G_" + self._PAIRS[i])
+        raise _lib.ChompScopeError(
+            "_calculate_zbar is served for the four pairs of this object's windows: (a1, a2), "
+            "(b1, b2), (a1, b2), (b1, a2)")
+
+    def _evaluate(self, l):
+        """[5, n] of a flat multipole array: the four _pl_X and covariance_G.  The logarithm and
+        so the range rule are numpy's, on the host (covariance.py:935-938)."""
+        ctx = self._tables()
+        if _lib._is_torch(l):
+            import torch
+            lh = l.detach().cpu().numpy().astype(numpy.float64).ravel()
+            with numpy.errstate(all="ignore"):
+                x = numpy.concatenate([numpy.log(lh), lh])
+            return ctx.covariance_fourier_gaussian(torch.as_tensor(x, device=l.device))
+        lh = numpy.ascontiguousarray(l, dtype=numpy.float64).ravel()
+        with numpy.errstate(all="ignore"):
+            x = numpy.concatenate([numpy.log(lh), lh])
+        if lh.size == 0:
+            return numpy.empty((5, 0))
+        return ctx.covariance_fourier_gaussian(x)
+
+    def _row(self, row, l):
+        if _lib._is_torch(l):
+            return self._evaluate(l)[row].reshape(l.shape)
+        la = numpy.asarray(l, dtype=numpy.float64)
+        out = self._evaluate(la)[row]
+        return float(out[0]) if la.ndim == 0 else out.reshape(la.shape)
+
+    def _pl_a1a2(self, l):
+        return self._row(0, l)
+
+    def _pl_b1b2(self, l):
+        return self._row(1, l)
+
+    def _pl_a1b2(self, l):
+        return self._row(2, l)
+
+    def _pl_b1a2(self, l):
+        return self._row(3, l)
+
+    def covariance_G(self, l):
+        """covariance.py:928-932.  A scalar gives a float, an array an array of its shape; a
+        float64 torch cuda tensor gives a tensor on its device."""
+        return self._row(4, l)
+
+    def covariance(self, l_a, l_b):
+        """covariance.py:925-926: empty in the reference."""
+        return None
 
 
 class FiniteAreaEffect(object):

@@ -235,6 +235,7 @@ struct chomp_ctx {
   // projection
   ProjState proj;
   CrossState cross;             // Covariance(corr_a, corr_b): the two sides' snapshots and the four tables
+  FourierState fourier;         // CovarianceFourier: the four pairs' scalars, Limber tables and splines
   // The side stream.  The projection set-up (chomp_kernel_setup / chomp_multi_epoch_setup:
   // a chain of six small launches) depends on nothing the halo set-up produces, and C_l on
   // nothing w(theta) produces: they run here, beside the context's stream, ordered against it
@@ -723,6 +724,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
   if (ctx->h_stage_out) (void)hipHostFree(ctx->h_stage_out);
   proj_free(ctx->proj);
   if (ctx->cross.d) (void)hipFree(ctx->cross.d);
+  if (ctx->fourier.d) (void)hipFree(ctx->fourier.d);
   for (hipEvent_t e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {ctx->ev_side_go, ctx->ev_proj_ready, ctx->ev_side_done})

@@ -869,6 +869,157 @@ int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area
 }
 
 // ---------------------------------------------------------------------------
+// Gaussian covariance of C_l: CovarianceFourier (chomp_cov_kernels.h)
+// ---------------------------------------------------------------------------
+static bool fits_lds(const void* kernel, size_t dynamic_bytes);
+
+// The two slots hold windows of this context's configuration.
+static int check_fourier_slots(chomp_ctx* ctx, const ProjLayout& L, const char* what) {
+  const CrossState& X = ctx->cross;
+  const std::string w(what);
+  if (!X.staged[0] || !X.staged[1])
+    return fail(ctx, CHOMP_ERR_STATE, w + " before covariance_cross_stage of both slots");
+  if (X.C.pd[0] - X.C.htab[0] != ctx->L.stride || X.C.N != L.NKT ||
+      X.C.ptab[1] - X.C.ptab[0] < L.total)
+    return fail(ctx, CHOMP_ERR_STATE, w + ": the snapshots are of another configuration");
+  return CHOMP_OK;
+}
+
+static CovSrc fourier_src(const chomp_ctx* ctx) {
+  const CrossState& X = ctx->cross;
+  return CovSrc{reinterpret_cast<const ProjDev*>(X.d + X.C.pd[0]), X.d + X.C.ptab[0],
+                reinterpret_cast<const ProjDev*>(X.d + X.C.pd[1]), X.d + X.C.ptab[1]};
+}
+
+int chomp_covariance_fourier_zbar(chomp_ctx* ctx, const double* z, size_t n_z, double* info) {
+  if (!ctx || !z) return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_zbar: bad args");
+  if (n_z < 1 || n_z > 256)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_zbar: the z grid must hold 1..256 points");
+  const chomp_config& c = ctx->cfg;
+  if (c.corr_npoints < 4)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_zbar: corr_npoints must be at least 4");
+  const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
+  { const int rcs = check_fourier_slots(ctx, L, "covariance_fourier_zbar"); if (rcs) return rcs; }
+  HIPCHK(hipSetDevice(ctx->device));
+  FourierState& S = ctx->fourier;
+  S.zbar = S.ready = false;
+  const CrossState& X = ctx->cross;
+  {   // covariance.py:887-903: every pair needs a redshift range, before anything is launched
+    ProjDev hp[2];
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < 2; ++s)
+      HIPCHK(hipMemcpy(&hp[s], X.d + X.C.pd[s], sizeof(ProjDev), hipMemcpyDeviceToHost));
+    static const char* const names[4] = {"a1a2", "b1b2", "a1b2", "b1a2"};
+    for (int p = 0; p < 4; ++p) {
+      const ProjDev& p1 = hp[(p == kCovfB1B2 || p == kCovfB1A2) ? 1 : 0];
+      const ProjDev& p2 = hp[(p == kCovfB1B2 || p == kCovfA1B2) ? 1 : 0];
+      if (!(std::max(p1.w_z_min[0], p2.w_z_min[1]) < std::min(p1.w_z_max[0], p2.w_z_max[1])))
+        return fail(ctx, CHOMP_ERR_SCOPE, std::string("covariance_fourier_zbar: the windows of "
+                    "pair ") + names[p] + " have no redshift in common");
+    }
+  }
+  const FourierLayout F = make_fourier_layout(c.corr_npoints);
+  { const int rce = ensure(ctx, &S.d, &S.cap, (size_t)F.total); if (rce) return rce; }
+  S.F = F;
+  Staging st(ctx, CHOMP_HOST, "covariance_fourier_zbar");
+  const double* d_z;
+  st.in(z, n_z, &d_z);
+  const int rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_covf_zbar, dim3(4), dim3(256), 0, ctx->stream, L, F, fourier_src(ctx), d_z,
+                     (int)n_z, S.d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  S.zbar = true;
+  if (info) {
+    double sc[32];
+    HIPCHK(hipMemcpy(sc, S.d + F.scal, sizeof(sc), hipMemcpyDeviceToHost));
+    for (int p = 0; p < 4; ++p)
+      for (int q = 0; q < 7; ++q) info[7 * p + q] = sc[8 * p + q];
+  }
+  return CHOMP_OK;
+}
+
+int chomp_covariance_fourier_table(chomp_ctx* ctx, int which, const size_t epoch[4],
+                                   const double* ln_l, size_t n, double* norms, double* tables,
+                                   double* levels) {
+  if (!ctx || !epoch || !ln_l) return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_table: bad args");
+  FourierState& S = ctx->fourier;
+  if (!S.zbar) return fail(ctx, CHOMP_ERR_STATE, "covariance_fourier_table before covariance_fourier_zbar");
+  if ((which & 15) != CHOMP_P_MM || (which & CHOMP_P_HALOFIT))
+    return fail(ctx, CHOMP_ERR_SCOPE, "covariance_fourier_table: the tables are built from Halo.power_mm "
+                                      "(CHOMP_P_MM, with or without CHOMP_P_EXTRAPOLATE)");
+  for (int p = 0; p < 4; ++p) {
+    const int rcp = check_power(ctx, which, epoch[p], 1);
+    if (rcp) return rcp;
+  }
+  const chomp_config& c = ctx->cfg;
+  const FourierLayout& F = S.F;
+  if (n != (size_t)F.N || F.N != c.corr_npoints)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_table: length must be corr_npoints");
+  for (size_t i = 1; i < n; ++i)
+    if (!(ln_l[i] > ln_l[i - 1]))
+      return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_table: ln l knots must increase");
+  const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
+  { const int rcs = check_fourier_slots(ctx, L, "covariance_fourier_table"); if (rcs) return rcs; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t sh = (size_t)covf_lds_doubles(ctx->L.NK, L) * sizeof(double);
+  if (!(ctx->with_bao ? fits_lds(reinterpret_cast<const void*>(&k_covf_knots<true>), sh)
+                      : fits_lds(reinterpret_cast<const void*>(&k_covf_knots<false>), sh)))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_table: halo/cosmo/window_npoints too large "
+                                    "for the spectrum and the windows of a pair");
+  S.ready = false;
+  for (int p = 0; p < 4; ++p) {
+    bool seen = false;
+    for (int q = 0; q < p; ++q) seen = seen || epoch[q] == epoch[p];
+    if (seen) continue;
+    const int rce = prepare_extrapolation(ctx, which, epoch[p], 1);
+    if (rce) return rce;
+  }
+  HIPCHK(hipMemcpyAsync(S.d + F.ln_l, ln_l, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_covf_knots<BAO>, dim3((unsigned)F.N, 4), dim3(256), sh, ctx->stream, c,
+                       ctx->L, L, F, fourier_src(ctx), ctx->d_epochs, ctx->d_tab, which,
+                       (int)epoch[0], (int)epoch[1], (int)epoch[2], (int)epoch[3], S.d);
+  });
+  hipLaunchKernelGGL(k_covf_spline, dim3(4), dim3(64), 0, ctx->stream, F, S.d);
+  HIPCHK(hipGetLastError());
+  // (the copy above reads the caller's array: done before the call returns)
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  S.ln_l_min = ln_l[0];
+  S.ln_l_max = ln_l[n - 1];
+  S.ready = true;
+  const size_t b = (size_t)F.N * sizeof(double);
+  for (int p = 0; p < 4; ++p) {
+    if (norms) HIPCHK(hipMemcpy(norms + p, S.d + F.scal + 8 * p + kCovfNorm, sizeof(double), hipMemcpyDeviceToHost));
+    if (tables) HIPCHK(hipMemcpy(tables + (size_t)p * F.N, S.d + F.tab[p], b, hipMemcpyDeviceToHost));
+    if (levels) HIPCHK(hipMemcpy(levels + (size_t)p * F.N, S.d + F.lev[p], b, hipMemcpyDeviceToHost));
+  }
+  return CHOMP_OK;
+}
+
+int chomp_covariance_fourier_gaussian(chomp_ctx* ctx, const double* l, size_t n, double* out,
+                                      int mem) {
+  if (!ctx || !l || !out || n == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_gaussian: bad args");
+  Staging st(ctx, mem, "covariance_fourier_gaussian");
+  if (st.rc) return st.rc;
+  const FourierState& S = ctx->fourier;
+  if (!S.ready)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_fourier_gaussian before covariance_fourier_table");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* d_l;
+  double* d_out;
+  st.in(l, 2 * n, &d_l);
+  st.out(out, 5 * n, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_covf_eval, grid_1d(n), dim3(256), 0, ctx->stream, S.F, S.d, S.ln_l_min,
+                     S.ln_l_max, d_l, n, d_out);
+  return st.finish();
+}
+
+// ---------------------------------------------------------------------------
 // Super-sample covariance of w(theta) (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
 // The windows behind the context's kernel_ssc / kernel_NG state: its own kernel_setup, or the two

@@ -22,6 +22,13 @@
 //   k_ng_tri        the bicubic of an uploaded I_0^4 table (HaloTrispectrumOneHalo's)
 //   k_ng_kb         covariance_NG, inner integrals: one k_b Romberg per (pair, k_a knot)
 //
+// ... and the Gaussian covariance of C_l, CovarianceFourier, covariance.py:874-1083 (at the end):
+//
+//   k_covf_zbar     z_bar and the range of the four window pairs a1a2, b1b2, a1b2, b1a2
+//   k_covf_knots    the four Limber tables over ln l: one Romberg over chi per (knot, pair)
+//   k_covf_spline   the not-a-knot splines of their logarithms
+//   k_covf_eval     _pl_X and covariance_G at the caller's multipoles
+//
 // k_ssc_prep, k_ssc_table and k_ng_table are templates over where the four windows come from
 // (CovSrc / CovWindows): a matching block's two windows, each used twice, or the four windows in
 // the two slots of a cross block (Covariance(corr_a, corr_b, cross_terms=True), kernel.py:893-972
@@ -921,6 +928,230 @@ __global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgT
     knots[(size_t)pair * NK + i] = r.value[0] / (1.0 * D * D * D * D);
     if (levels) levels[(size_t)pair * NK + i] = (double)r.level[0];
     if (!r.converged[0] && status) atomicOr(status, kStCovNgDivmax);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Gaussian covariance of C_l: CovarianceFourier (covariance.py:874-1083)
+// ---------------------------------------------------------------------------
+// Four Limber tables over ln l, one per window pair X = a1a2, b1b2, a1b2, b1a2, each from the
+// P_mm of its own halo epoch (at that pair's z_bar).  The windows and the MultiEpoch are the two
+// slots of a cross block staged with CHOMP_CROSS_WINDOWS (slot 0: a1, a2 and the MultiEpoch; slot
+// 1: b1, b2); the epochs are the context's own.  Device block: per pair 8 scalars | ln l knots |
+// per pair {table, its logarithm, the spline of that, Romberg levels, spline_build's work}.
+constexpr int kCovfA1A2 = 0, kCovfB1B2 = 1, kCovfA1B2 = 2, kCovfB1A2 = 3;
+// scalars of a pair
+constexpr int kCovfZMin = 0, kCovfZMax = 1, kCovfZBar = 2, kCovfChiBar = 3, kCovfChiMin = 4,
+              kCovfChiMax = 5, kCovfDBar = 6, kCovfNorm = 7;
+struct FourierLayout {
+  int N, scal, ln_l, tab[4], logt[4], pp[4], lev[4], work[4], total;
+};
+inline FourierLayout make_fourier_layout(int N) {
+  FourierLayout F;
+  F.N = N;
+  int o = 0;
+  F.scal = o; o += 4 * 8;
+  F.ln_l = o; o += N;
+  for (int t = 0; t < 4; ++t) {
+    F.tab[t] = o; o += N;
+    F.logt[t] = o; o += N;
+    F.pp[t] = o; o += 4 * (N - 1);
+    F.lev[t] = o; o += N;
+    F.work[t] = o; o += 2 * N;
+  }
+  F.total = (o + 7) & ~7;
+  return F;
+}
+struct FourierState {
+  double* d = nullptr;     // the block of FourierLayout
+  size_t cap = 0;          // doubles allocated at d
+  FourierLayout F;
+  bool zbar = false;       // the scalars of the four pairs (chomp_covariance_fourier_zbar) valid
+  bool ready = false;      // ... and the four tables with their splines (chomp_covariance_fourier_table)
+  double ln_l_min = 0.0, ln_l_max = 0.0;
+};
+// Dynamic LDS of k_covf_knots, in doubles: one PowerEval staging, the MultiEpoch and the pair's two
+// window splines.
+inline int covf_lds_doubles(int NK_halo, const ProjLayout& L) {
+  return 12 * (NK_halo - 1) + L.NC + 8 * (L.NC - 1) + 8 * (L.NWp - 1);
+}
+
+// The two windows of pair X in the two slots: (first of slot 0 or 1, second of slot 0 or 1).
+__device__ __forceinline__ void covf_pair_windows(const ProjLayout& L, const CovSrc& src, int X,
+                                                  const double** pp1, const double** pp2,
+                                                  const ProjDev** pd1, const ProjDev** pd2) {
+  const bool first_b = X == kCovfB1B2 || X == kCovfB1A2;
+  const bool second_b = X == kCovfB1B2 || X == kCovfA1B2;
+  *pd1 = first_b ? src.pd_b : src.pd;
+  *pd2 = second_b ? src.pd_b : src.pd;
+  *pp1 = (first_b ? src.ptab_b : src.ptab) + L.w_pp[0];
+  *pp2 = (second_b ? src.ptab_b : src.ptab) + L.w_pp[1];
+}
+
+// grid 4 (pairs), block 256: _calculate_zbar (covariance.py:1067-1075) on the caller's z grid
+// (CovarianceFourier._z_array, nz <= 256): the first argmax of w1 w2 / chi^2 D(z(chi))^2 at chi =
+// comoving_distance(z) -- numpy.argmax: the first of equal maxima, and the first NaN if there is
+// one -- and the pair's scalars: z_min = max, z_max = min of its two windows', z_bar, chi(z_bar),
+// chi(z_min), chi(z_max), MultiEpoch.growth_factor(z_bar).
+__global__ __launch_bounds__(256) void k_covf_zbar(ProjLayout L, FourierLayout F, CovSrc src,
+                                                   const double* __restrict__ z, int nz,
+                                                   double* __restrict__ ft) {
+  __shared__ double cand[256];
+  const int X = blockIdx.x, t = threadIdx.x;
+  const double *pp1, *pp2;
+  const ProjDev *pd1, *pd2;
+  covf_pair_windows(L, src, X, &pp1, &pp2, &pd1, &pd2);
+  const MEView me = me_view(L, *src.pd, src.ptab, 0);
+  const WindowView w1{pp1, L.NWp, pd1->w_chi_min[0], pd1->w_chi_max[0]};
+  const WindowView w2{pp2, L.NWp, pd2->w_chi_min[1], pd2->w_chi_max[1]};
+  if (t < nz) {
+    const double chi = me.comoving_distance(z[t]);
+    const double D = me.growth_factor(me.redshift(chi));
+    cand[t] = w1(chi) * w2(chi) / (chi * chi) * D * D;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  int best = 0;
+  for (int i = 1; i < nz && !isnan(cand[best]); ++i)
+    if (isnan(cand[i]) || cand[i] > cand[best]) best = i;
+  const double z_min = pd1->w_z_min[0] > pd2->w_z_min[1] ? pd1->w_z_min[0] : pd2->w_z_min[1];
+  const double z_max = pd1->w_z_max[0] < pd2->w_z_max[1] ? pd1->w_z_max[0] : pd2->w_z_max[1];
+  double* s = ft + F.scal + 8 * X;
+  s[kCovfZMin] = z_min;
+  s[kCovfZMax] = z_max;
+  s[kCovfZBar] = z[best];
+  s[kCovfChiBar] = me.comoving_distance(z[best]);
+  s[kCovfChiMin] = me.comoving_distance(z_min);
+  s[kCovfChiMax] = me.comoving_distance(z_max);
+  s[kCovfDBar] = me.growth_factor(z[best]);
+  s[kCovfNorm] = 0.0;
+}
+
+// covariance.py:1077-1083 (_pl_integrand) in the reference's order of operations.  The end-point
+// guard is CovProjIntegrand's.
+template <bool BAO>
+struct CovFourierIntegrand {
+  const PowerEval* P;
+  const MEView* me;
+  const WindowView *w1, *w2;
+  double l, norm;
+  __device__ __forceinline__ double operator()(double chi) const {
+    const double D = me->growth_factor(me->redshift(chi));
+    double k = l / chi;
+    if (k > P->k_max && k <= P->k_max * (1.0 + 8.9e-16)) k = P->k_max;
+    return norm * (*w1)(chi) * (*w2)(chi) * D * D / (chi * chi) * P->template eval_t<BAO>(k);
+  }
+};
+
+// grid (N = corr_npoints, 4 pairs), block 256: knot x of table y of _initialize_pl
+// (covariance.py:958-1044), the Romberg over [chi(z_min_X), chi(z_max_X)] of norm_X w1 w2 D^2 /
+// chi^2 P_mm,X(l / chi) with epoch[X]'s spectrum, divided by D(z_bar_X)^2.  norm_X is formed here
+// as the reference forms it (:987-1006): 1 / integrand at chi(z_bar_X) with l = chi (k = 1), the
+// windows a1 and a2 whatever the pair, and the spectrum of epoch[X] -- but halo_a1a2's, epoch[0],
+// for a1b2.  A norm integrand that is not positive and finite leaves the knot NaN (the host
+// reports it).  LDS: covf_lds_doubles.
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_covf_knots(chomp_config cfg, TabLayout HL, ProjLayout L,
+                                                    FourierLayout F, CovSrc src,
+                                                    const Epoch* __restrict__ epochs,
+                                                    const double* __restrict__ htab, int which,
+                                                    int e0, int e1, int e2, int e3,
+                                                    double* __restrict__ ft) {
+  extern __shared__ __align__(16) double sm[];
+  __shared__ Epoch E;
+  __shared__ ProjDev pda;
+  __shared__ double red[romberg_scratch<4, 2>()];
+  const int i = blockIdx.x, X = blockIdx.y;
+  const int e = X == 0 ? e0 : (X == 1 ? e1 : (X == 2 ? e2 : e3));
+  const int en = X == kCovfA1B2 ? e0 : e;                // (:997-1001: halo_a1a2)
+  copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[en]),
+               kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pda), reinterpret_cast<const double*>(src.pd),
+               kProjDoubles);
+  __syncthreads();
+  PowerEval P;
+  P.stage(cfg, HL, &E, htab + (size_t)en * HL.stride, which, sm);
+  const int NC = L.NC, NW = L.NWp;
+  double* chi_t = sm + 12 * (HL.NK - 1);                // [NC]
+  double* pp_z = chi_t + NC;                            // [4 (NC - 1)]
+  double* pp_g = pp_z + 4 * (NC - 1);
+  double* wpp = pp_g + 4 * (NC - 1);                    // 2 x [4 (NW - 1)]
+  const double *pp1, *pp2;
+  const ProjDev *pd1, *pd2;
+  covf_pair_windows(L, src, X, &pp1, &pp2, &pd1, &pd2);
+  copy_doubles(chi_t, src.ptab + L.me_chi[0], NC);
+  copy_doubles(pp_z, src.ptab + L.me_pp_z[0], 4 * (NC - 1));
+  copy_doubles(pp_g, src.ptab + L.me_pp_g[0], 4 * (NC - 1));
+  copy_doubles(wpp, pp1, 4 * (NW - 1));
+  copy_doubles(wpp + 4 * (NW - 1), pp2, 4 * (NW - 1));
+  const MEView me{nullptr, chi_t, nullptr, pp_z, pp_g, NC, pda.me_z_min[0], pda.me_z_max[0]};
+  const WindowView w1{wpp, NW, pd1->w_chi_min[0], pd1->w_chi_max[0]};
+  const WindowView w2{wpp + 4 * (NW - 1), NW, pd2->w_chi_min[1], pd2->w_chi_max[1]};
+  __syncthreads();
+  P.template finish_t<BAO>();
+  const double* s = ft + F.scal + 8 * X;
+  const double chi_bar = s[kCovfChiBar], D_bar = s[kCovfDBar];
+  // the norm: a1 and a2 (read where they lie: one evaluation), l = exp(ln chi)
+  const WindowView a1{src.ptab + L.w_pp[0], NW, pda.w_chi_min[0], pda.w_chi_max[0]};
+  const WindowView a2{src.ptab + L.w_pp[1], NW, pda.w_chi_min[1], pda.w_chi_max[1]};
+  CovFourierIntegrand<BAO> f{&P, &me, &a1, &a2, exp(log(chi_bar)), 1.0};
+  const double norm_int = f(chi_bar);
+  if (en != e) {                                         // (a1b2: now its own epoch's spectrum)
+    __syncthreads();
+    copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
+                 kEpochDoubles);
+    __syncthreads();
+    P.stage(cfg, HL, &E, htab + (size_t)e * HL.stride, which, sm);
+    __syncthreads();
+    P.template finish_t<BAO>();
+  }
+  const bool ok = norm_int > 0.0 && norm_int < INFINITY;
+  double v = NAN;
+  int level = 0;
+  if (ok) {
+    f.w1 = &w1;
+    f.w2 = &w2;
+    f.l = exp(ft[F.ln_l + i]);
+    f.norm = 1.0 / norm_int;
+    v = romberg1<4>(f, s[kCovfChiMin], s[kCovfChiMax], cfg.global_precision, cfg.corr_precision,
+                    cfg.divmax, red, &level) / (D_bar * D_bar);
+  }
+  if (threadIdx.x == 0) {
+    ft[F.tab[X] + i] = v;
+    ft[F.lev[X] + i] = (double)level;
+    if (i == 0) ft[F.scal + 8 * X + kCovfNorm] = 1.0 / norm_int;
+  }
+}
+
+// grid 4, block 64: the not-a-knot spline of ln(table blockIdx.x) over ln l (covariance.py:1048-1063).
+__global__ void k_covf_spline(FourierLayout F, double* __restrict__ ft) {
+  const int X = blockIdx.x;
+  if (threadIdx.x != 0 || X >= 4) return;
+  for (int i = 0; i < F.N; ++i) ft[F.logt[X] + i] = log(ft[F.tab[X] + i]);
+  spline_build(ft + F.ln_l, ft + F.logt[X], F.N, ft + F.pp[X], ft + F.work[X]);
+}
+
+// Element-wise over n multipoles, x = ln l[n] then l[n]: out[X n + j] = _pl_X(l_j) =
+// exp(spline_X(ln l)) / norm_X inside ln_l_min <= ln l <= ln_l_max and exactly 0 outside
+// (covariance.py:934-956), and out[4 n + j] = covariance_G(l_j) = (pl_a1a2 pl_b1b2 + pl_a1b2
+// pl_b1a2) / (2 l + 1) (:928-932).
+__global__ __launch_bounds__(256) void k_covf_eval(FourierLayout F, const double* __restrict__ ft,
+                                                   double ln_l_min, double ln_l_max,
+                                                   const double* __restrict__ x, size_t n,
+                                                   double* __restrict__ out) {
+  for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n;
+       j += (size_t)gridDim.x * blockDim.x) {
+    const double ln_l = x[j], l = x[n + j];
+    const bool inside = ln_l >= ln_l_min && ln_l <= ln_l_max;
+    double p[4];
+#pragma unroll
+    for (int X = 0; X < 4; ++X) {
+      p[X] = inside ? exp(spline_eval(ft + F.ln_l, ft + F.pp[X], F.N, ln_l)) /
+                          ft[F.scal + 8 * X + kCovfNorm]
+                    : 0.0;
+      out[(size_t)X * n + j] = p[X];
+    }
+    out[4 * n + j] = 1.0 / (2.0 * l + 1.0) * (p[0] * p[1] + p[2] * p[3]);
   }
 }
 

@@ -186,6 +186,38 @@ class Halo(object):
             self._resolve_status(stacklevel=5)
         return ctx
 
+    def _sync_epochs(self, redshifts, need_tables):
+        """A batch of epochs in this object's context: its cosmology, mass function, profile and
+        HOD at each of `redshifts`, the tables of `need_tables` built for all of them in one
+        set-up chain.  redshifts[0] must be the object's own redshift: that is epoch 0, which the
+        object goes on using as if _sync had built it.  (CovarianceFourier's four halos.)"""
+        assert redshifts[0] == self.cosmo._redshift == self._redshift
+        ctx = self._context()
+        bao = bool(getattr(self.cosmo, "_with_bao", False))
+        cd = self.cosmo.cosmo_dict
+        self._resolve_status(stacklevel=6)         # (the set-up below clears the device's words)
+        self._before_epochs_set()
+        self._epoch_sig = self._mass_sig = None     # (until the set-up has returned)
+        self._nbar_valid = False
+        ctx.epochs_set(cd, list(redshifts), bao, **cosmology._de_kw(cd))
+        self._after_epochs_set()
+        build = 0
+        for flag, bit in self._flag_bits:
+            if need_tables & bit:
+                build |= bit
+        self._stage_k(ctx, build | (_lib.T_EXCLUSION if self._exclusion else 0))
+        self._epoch_sig = (tuple(sorted(cd.items())), self.cosmo._redshift, bao)
+        self._mass_sig = (tuple(sorted(self.mass.halo_dict.items())), self.mass._kind)
+        self._reset_flags(all_tables=True)
+        for flag, bit in self._flag_bits:
+            if build & bit:
+                setattr(self, flag, True)
+        self._nbar_valid = True
+        ctx.status_post()
+        self._status_pending = True
+        self._resolve_status(stacklevel=5)
+        return ctx
+
     def _stage_k(self, ctx, tables):
         ctx.stage_k(self.mass.halo_dict, self.mass._kind, self._profile(), self.local_hod, tables,
                     **self._profile_kw())

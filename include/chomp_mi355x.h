@@ -815,6 +815,49 @@ int chomp_kernel_ssc_setup_cross(chomp_ctx* ctx, double ln_ktheta_min, double ln
 int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta, size_t n,
                                double* out, double* kb_knots, double* kb_levels);
 
+/* Gaussian covariance of C_l, covariance.CovarianceFourier (covariance.py:874-1083): four Limber
+ * tables over ln l, one per window pair X = a1a2, b1b2, a1b2, b1a2 (that order throughout), each
+ * from the P_mm of a halo epoch at that pair's z_bar.
+ *
+ * The four windows come from the two slots of chomp_covariance_cross_stage (CHOMP_CROSS_WINDOWS is
+ * enough): slot 0 holds a1, a2 and the MultiEpoch, slot 1 holds b1, b2.  The three calls below keep
+ * a state of their own in `ctx`; they read the slots and the context's epochs and change neither.
+ * Staging a slot again after chomp_covariance_fourier_zbar makes the scalars stale: call it again.
+ *
+ * chomp_covariance_fourier_zbar replaces _calculate_zbar (:1067-1075) for the four pairs: on the
+ * caller's grid z[n_z] (CovarianceFourier._z_array, n_z <= 256) the first maximum of
+ * w1 w2 / chi^2 D(z(chi))^2 at chi = comoving_distance(z), as numpy.argmax finds it.  A pair whose
+ * two windows have no redshift in common is CHOMP_ERR_SCOPE before anything is launched.  info[4][7]
+ * (host, may be NULL) receives per pair z_min (the larger of its windows' z_min), z_max (the
+ * smaller of their z_max), z_bar, comoving_distance(z_bar), comoving_distance(z_min),
+ * comoving_distance(z_max) and growth_factor(z_bar), all of slot 0's MultiEpoch.  Synchronises.
+ *
+ * chomp_covariance_fourier_table replaces _initialize_pl (:958-1065): for every knot ln_l[n]
+ * (host, increasing, n = corr_npoints) and pair the Romberg integral over [chi(z_min_X),
+ * chi(z_max_X)] of norm_X w1 w2 D^2 / chi^2 P(l / chi) at global_precision / corr_precision /
+ * divmax, divided by growth_factor(z_bar_X)^2, and the not-a-knot spline of its logarithm.  `which`
+ * is CHOMP_P_MM, with CHOMP_P_EXTRAPOLATE or without (anything else: CHOMP_ERR_SCOPE); epoch[X] is
+ * the context's halo epoch that carries pair X's spectrum -- the caller has moved it to z_bar_X;
+ * pairs may share an epoch.  norm_X is formed as the reference forms it, quirks included
+ * (:987-1006): the reciprocal of the integrand at chi(z_bar_X) with l = chi, the windows a1 and a2
+ * whatever the pair, and the spectrum of epoch[X] -- except for a1b2, which takes epoch[0]'s
+ * (halo_a1a2).  A norm integrand that is not positive and finite leaves that pair's table NaN and
+ * its norm as 1 / integrand; the caller decides.  norms[4], tables[4][n] and levels[4][n] (host,
+ * may be NULL) receive the norms, the tables (integral / D^2, before the logarithm) and the
+ * Romberg levels reached.  Synchronises.
+ *
+ * chomp_covariance_fourier_gaussian replaces _pl_a1a2 .. _pl_b1a2 (:934-956) and covariance_G
+ * (:928-932) at n multipoles: l holds ln l[n] then l[n] -- the logarithms are the caller's, so the
+ * range rule ln_l[0] <= ln l <= ln_l[n-1] is decided by the caller's arithmetic -- and out[5][n]
+ * receives the four _pl_X = exp(spline_X(ln l)) / norm_X (exactly 0 outside the range) and
+ * covariance_G = (pl_a1a2 pl_b1b2 + pl_a1b2 pl_b1a2) / (2 l + 1). */
+int chomp_covariance_fourier_zbar(chomp_ctx* ctx, const double* z, size_t n_z, double* info);
+int chomp_covariance_fourier_table(chomp_ctx* ctx, int which, const size_t epoch[4],
+                                   const double* ln_l, size_t n, double* norms, double* tables,
+                                   double* levels);
+int chomp_covariance_fourier_gaussian(chomp_ctx* ctx, const double* l, size_t n, double* out,
+                                      int mem);
+
 /* One-halo trispectrum term of the covariance of w(theta), Covariance(corr, corr,
  * nongaussian_cov=True, input_halo_trispectrum=HaloTrispectrumOneHalo), with a1 = b1 = window a
  * and a2 = b2 = window b of the context's kernel_setup.  Host memory throughout.
