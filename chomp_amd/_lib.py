@@ -124,7 +124,7 @@ EXPORTS = [
     "chomp_eval", "chomp_halofit_get", "chomp_halofit_put",
     "chomp_multi_epoch_setup", "chomp_me_eval",
     "chomp_kernel_setup", "chomp_kernel_info", "chomp_kernel_table",
-    "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_cell",
+    "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_wtheta_epochs", "chomp_cell",
     "chomp_set_precision", "chomp_xi3d", "chomp_spline_eval", "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
     "chomp_covariance_table", "chomp_covariance_gaussian",
@@ -166,7 +166,8 @@ ST_SATURATED = ST_MASS_MIN_SATURATED | ST_MASS_MAX_SATURATED
 TUNE_E_STREAM_MIN, TUNE_DEEP_LITERAL, TUNE_ROCTX, TUNE_WTHETA_DIRECT = 0, 2, 3, 4
 TUNE_CELL_ONE_KERNEL = 5
 TUNE_DEEP_TOL, TUNE_DEEP_MAX_BREAKS, TUNE_DEEP_MAX_FINE, TUNE_DEEP_SLOTS = 6, 7, 8, 10
-TUNE_COUNT = 11   # (1 and 9: retired knobs, refused like any unknown number)
+TUNE_WTHETA_EPOCH_CHUNK = 11
+TUNE_COUNT = 12   # (1 and 9: retired knobs, refused like any unknown number)
 
 
 class ChompAccuracyWarning(UserWarning):
@@ -410,6 +411,7 @@ def lib():
         L.chomp_kernel_raw.argtypes = [vp, vp, sz, vp, i]
         L.chomp_window_eval.argtypes = [vp, i, vp, sz, vp, i]
         L.chomp_wtheta.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, i]
+        L.chomp_wtheta_epochs.argtypes = [vp, i, sz, sz, d, d, d, vp, sz, vp, i]
         L.chomp_cell.argtypes = [vp, i, sz, d, vp, sz, vp, i]
         L.chomp_wtheta_cell.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, vp, sz, vp, i]
         L.chomp_set_precision.argtypes = [vp, i]
@@ -1116,6 +1118,13 @@ class Context(object):
     def wtheta(self, which, epoch, k_min, k_max, D_z, theta):
         return self._run(self._L.chomp_wtheta, [theta], _elementwise(
             int(which), epoch, float(k_min), float(k_max), float(D_z)))[0]
+
+    def wtheta_epochs(self, which, epoch0, n_epoch, k_min, k_max, D_z, theta):
+        """w(theta) of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (chomp_wtheta_epochs):
+        [n_epoch, theta.size], row e what wtheta(which, epoch0 + e, ...) returns, bit for bit."""
+        return self._run(self._L.chomp_wtheta_epochs, [theta], lambda mem, new, th: (
+            int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), float(D_z), th,
+            _numel(th), new((int(n_epoch), _numel(th))), mem))[0]
 
     def wtheta_cell(self, which, epoch, k_min, k_max, D_z, theta, ell):
         """(w(theta), C_l) of one set-up in one call (chomp_wtheta_cell): with torch cuda

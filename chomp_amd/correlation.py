@@ -134,6 +134,106 @@ class Correlation(object):
         self.halo._resolve_status()            # (the result is on the host: nothing to hide)
         return float(out[0]) if th.ndim == 0 else out.reshape(th.shape)
 
+    # -- the batch over HODs ---------------------------------------------------
+    def _hods_scope(self, hods=None):
+        """ChompScopeError unless correlation_hods serves this object (and `hods`); no device
+        work.  Returns the HODs as objects."""
+        from . import hod as hod_mod
+        h = self.halo
+
+        def refuse(why):
+            raise _lib.ChompScopeError("correlation_hods: %s; use the loop set_hod / "
+                                       "set_hod_object + correlation" % why)
+        if type(h) is not halo_mod.Halo:
+            refuse("the halo is a %s, the batch takes a plain halo.Halo" % type(h).__name__)
+        if getattr(h, "_general_profile", False):
+            refuse("a general_profile halo (HaloGrid batches NFW epochs)")
+        if h.get_extrapolation():
+            refuse("an extrapolated spectrum (chomp_wtheta_epochs takes none)")
+        if getattr(h.cosmo, "_with_bao", False):
+            refuse("a with_bao cosmology")
+        # HaloGrid's epochs take ONE halo dictionary for the mass function and the profile; after
+        # set_halo the two of a Halo differ (halo.py:220-235)
+        prof, mass = h._profile(), h.mass.halo_dict
+        if any(prof.get(key) != mass.get(key) for key in set(prof) | set(mass)):
+            refuse("the halo's profile and mass-function dictionaries differ (after set_halo)")
+        objs = []
+        for i, one in enumerate(hods if hods is not None else ()):
+            if isinstance(one, dict):
+                one = hod_mod.HODZheng(one)
+            if type(one) not in (hod_mod.HODZheng, hod_mod.HODMandelbaum):
+                refuse("hods[%d] is a %s, not a dictionary, HODZheng or HODMandelbaum"
+                       % (i, type(one).__name__))
+            objs.append(one)
+        return objs
+
+    def correlation_hods(self, theta_rad, hods, with_status=False):
+        """w(theta) for many HODs in one call: the array [len(hods), theta.size] whose row i is
+        what set_hod_object(<hods[i] as an object>) followed by correlation(theta_rad) returns on
+        a fresh Halo -- the loop of the reference's example script (example_script.py:141-143)
+        as one batch.  hods: HOD dictionaries (HODZheng's) or hod.HODZheng / hod.HODMandelbaum
+        objects, mixed freely.  This object's own halo and HOD are not touched.
+
+        Every HOD is one epoch of one grid.HaloGrid at the halo's redshift (the kernel's z_bar)
+        with the halo's cosmology, mass function and halo dictionary; the Kernel is staged on the
+        grid's context and Context.wtheta_epochs evaluates all rows.  The grid is kept, keyed by
+        what it was built from (the number of HODs, redshift, cosmology, halo dictionary, mass
+        function and the defaults.default_limits / default_precision its context snapshots): a
+        later call with the same key only replaces the HODs.  The grid's context stays on the
+        device and stream it was created on.  The Kernel is not left as it was: staging it on the
+        grid's context makes that context the one its later read-backs (z_bar, chi_min, ...) are
+        served from, and the kernel keeps the context alive; its numbers do not change.
+
+        The set-up's status word of every point is read with the result, raised as a
+        ChompAccuracyWarning / ChompParityWarning naming the point, kept in
+        `self.hods_status` (uint32 [len(hods)]) and returned as the second element with
+        with_status=True.  A torch cuda theta returns a tensor.
+
+        ChompScopeError (before any launch): a halo that is not exactly halo.Halo, a
+        general_profile halo, extrapolation, with_bao, a halo whose profile and mass-function
+        dictionaries differ (after set_halo), an HOD of another class."""
+        import warnings
+        from . import grid
+        objs = self._hods_scope(hods)
+        n_hod = len(objs)
+        th = theta_rad if _lib._is_torch(theta_rad) else numpy.asarray(theta_rad, dtype=numpy.float64)
+        flat = th.reshape(-1) if _lib._is_torch(th) else numpy.ascontiguousarray(th).ravel()
+        if n_hod == 0:
+            out = flat.new_empty((0, flat.numel())) if _lib._is_torch(flat) else numpy.empty((0, flat.size))
+            self.hods_status = numpy.zeros(0, dtype=numpy.uint32)
+            return (out, self.hods_status) if with_status else out
+        h = self.halo
+        code, _ = _POWER[self._power_name]
+        kind = "tinker" if getattr(h.mass, "_kind", 0) else "st"
+        from . import defaults
+        # (a context snapshots defaults.default_limits / default_precision when it is created)
+        key = (n_hod, float(h.get_redshift()), tuple(sorted(h.cosmo.cosmo_dict.items())),
+               tuple(sorted(h.mass.halo_dict.items())), kind,
+               tuple(sorted(defaults.default_limits.items())),
+               tuple(sorted(defaults.default_precision.items())))
+        hg = self._hods_grid[1] if getattr(self, "_hods_grid", (None,))[0] == key else None
+        if hg is None:
+            hg = grid.HaloGrid(numpy.full(n_hod, h.get_redshift()), cosmo_dict=dict(h.cosmo.cosmo_dict),
+                               halo_dict=dict(h.mass.halo_dict), hod_dict=objs, mass_function=kind)
+            self._hods_grid = (key, hg)
+        else:
+            hg.set_parameters(hod=objs)
+        self.kernel._setup_on(hg.ctx)
+        hg.setup(self._power_name)
+        out = hg.ctx.wtheta_epochs(h._power_code(code), 0, n_hod, self._k_lim[0], self._k_lim[1],
+                                   self.D_z, flat)
+        words = hg.status()                    # (synchronises: the words belong to this result)
+        self.hods_status = words
+        for i, w in enumerate(words):
+            w = int(w)
+            if w:
+                category = (_lib.ChompParityWarning
+                            if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
+                            else _lib.ChompAccuracyWarning)
+                warnings.warn("HOD %d: %s" % (i, "; ".join(_lib.describe_status(w))), category,
+                              stacklevel=2)
+        return (out, words) if with_status else out
+
     def write(self, output_file_name):
         with open(output_file_name, "w") as f:
             f.write("#ttype1 = theta [deg]\n#ttype2 = wtheta\n")

@@ -631,6 +631,87 @@ int chomp_wtheta(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k
   return wtheta_impl(ctx, which, epoch, k_min, k_max, D_z, theta, n, out, mem);
 }
 
+// w(theta) of n_epoch epochs that share the projection set-up, the k range and D_z (an HOD design
+// or chain at one cosmology): the three launches of wtheta_impl with an epoch axis, the epochs
+// worked off in chunks of kWthEpochChunk (layout: chomp_proj_kernels.h, "The epoch axis").
+int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
+                        double k_max, double D_z, const double* theta, size_t n, double* out,
+                        int mem) {
+  StageRange range_(ctx, "chomp:wtheta_epochs");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!theta || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "wtheta_epochs: bad args");
+  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "wtheta_epochs: n * n_epoch too large");
+  Staging st(ctx, mem, "wtheta_epochs");
+  if (st.rc) return st.rc;
+  if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "wtheta_epochs before kernel_setup");
+  // (what the call does not serve is said first: a HaloFit code on epochs without a HaloFit
+  //  set-up is out of scope here, not a state to repair)
+  if (ctx->precision != CHOMP_PREC_F64)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: fp64 only (the narrowed precision modes belong to chomp_wtheta)");
+  if (which & CHOMP_P_HALOFIT)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: HaloFit spectra are evaluated by chomp_wtheta");
+  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: extrapolated spectra are evaluated by chomp_wtheta");
+  if (ctx->with_bao)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: the wiggle transfer function is evaluated by chomp_wtheta");
+  int rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  if (!(k_min > 0.0) || !(k_max > k_min) || !(D_z > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_epochs: k range / D_z");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  const double* din;
+  double* dout;
+  st.in(theta, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = st.place();
+  if (rc) return rc;
+  // (the route and the sizes as in wtheta_impl)
+  const ProjLayout& L = ctx->proj.L;
+  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
+  const int LT = ctx->cfg.divmax < kWthetaTabLevel ? ctx->cfg.divmax : kWthetaTabLevel;
+  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const double dxK = (ctx->proj.host.ln_kt_max - ctx->proj.host.ln_kt_min) / (double)(L.NKT - 1);
+  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
+  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
+  const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
+                    ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
+  const size_t stride = wth_epoch_stride(LT, nseg, fast);
+  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
+                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
+  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
+  if (rc) return rc;
+  double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // (of the chunk's first epoch)
+  double* segtot = rec + 4 * wth_rec_count(LT);
+  const unsigned gnodes = (unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
+  {
+    constexpr bool HF = false, BAO = false;
+    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the scratch is reused in stream order)
+      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+      const int e0 = (int)(epoch0 + c0);
+      double* o = dout + c0 * n;
+      hipLaunchKernelGGL((k_wtheta_nodes_epochs<HF, BAO>), dim3(gnodes, E), dim3(256),
+                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, k_min, k_max, D_z, LT,
+                         ctx->d_wnodes, stride);
+      if (fast) {
+        hipLaunchKernelGGL(k_wtheta_moments_epochs, dim3((unsigned)nseg, (unsigned)LT, kWthParts * E),
+                           dim3(256), 0, ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min),
+                           std::log(k_max), rec, segtot, stride);
+        hipLaunchKernelGGL(k_wtheta_fast_epochs, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
+                           ctx->cfg, L, ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, din, o,
+                           ctx->d_wnodes, rec, segtot, LT, nseg, stride);
+      } else {
+        hipLaunchKernelGGL((k_wtheta_epochs<HF, BAO>), dim3((unsigned)n, E), dim3(64 * kWthetaNW), sh,
+                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                           ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, D_z, din, o, ctx->d_wnodes,
+                           LT, stride);
+      }
+    }
+  }
+  return st.finish();
+}
+
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z, const double* ell, size_t n,
                double* out, int mem) {
   StageRange range_(ctx, "chomp:cell");

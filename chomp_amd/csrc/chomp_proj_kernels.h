@@ -789,12 +789,13 @@ struct WthetaIntegrand {
 // grid ceil((2^LT + 1) / (256 kWthNodesPerThread)), block 256.
 constexpr int kWthetaTabLevel = 20;     // 2^20 + 1 doubles = 8 MiB: the default divmax
 constexpr int kWthNodesPerThread = 8;
+// (the body of k_wtheta_nodes and k_wtheta_nodes_epochs; bx: the block's index along the nodes)
 template <bool HF, bool BAO>
-__global__ __launch_bounds__(256) void k_wtheta_nodes(chomp_config cfg, TabLayout HL,
-                                                      const Epoch* __restrict__ epochs, int e,
-                                                      const double* __restrict__ htab, int which,
-                                                      double k_min, double k_max, double D_z,
-                                                      int LT, double* __restrict__ nodes) {
+__device__ __forceinline__ void wth_nodes_body(const chomp_config& cfg, const TabLayout& HL,
+                                               const Epoch* __restrict__ epochs, int e,
+                                               const double* __restrict__ htab, int which,
+                                               double k_min, double k_max, double D_z, int LT,
+                                               double* __restrict__ nodes, unsigned bx) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
@@ -808,7 +809,7 @@ __global__ __launch_bounds__(256) void k_wtheta_nodes(chomp_config cfg, TabLayou
   //  node -- at one node per thread, 4097 blocks of it, that staging was most of the 33 us)
 #pragma unroll 2
   for (int r = 0; r < kWthNodesPerThread; ++r) {
-    const long idx = ((long)blockIdx.x * kWthNodesPerThread + r) * blockDim.x + threadIdx.x;
+    const long idx = ((long)bx * kWthNodesPerThread + r) * blockDim.x + threadIdx.x;
     if (idx > (1L << LT)) return;
     double x;
     if (idx < 2) {
@@ -823,6 +824,27 @@ __global__ __launch_bounds__(256) void k_wtheta_nodes(chomp_config cfg, TabLayou
     const double k = exp(x);
     nodes[idx] = k * k / (2.0 * kPi) * P.template at_ln<HF, BAO>(x, k) * (1.0 / (D_z * D_z));
   }
+}
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256) void k_wtheta_nodes(chomp_config cfg, TabLayout HL,
+                                                      const Epoch* __restrict__ epochs, int e,
+                                                      const double* __restrict__ htab, int which,
+                                                      double k_min, double k_max, double D_z,
+                                                      int LT, double* __restrict__ nodes) {
+  wth_nodes_body<HF, BAO>(cfg, HL, epochs, e, htab, which, k_min, k_max, D_z, LT, nodes, blockIdx.x);
+}
+// ... with an epoch axis (chomp_wtheta_epochs): grid (as k_wtheta_nodes, E), block 256; row
+// blockIdx.y tabulates epoch e0 + blockIdx.y into its own table, `stride` doubles after the
+// previous one.  Every block stages its own epoch exactly as k_wtheta_nodes does.
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256) void k_wtheta_nodes_epochs(chomp_config cfg, TabLayout HL,
+                                                             const Epoch* __restrict__ epochs, int e0,
+                                                             const double* __restrict__ htab, int which,
+                                                             double k_min, double k_max, double D_z,
+                                                             int LT, double* __restrict__ nodes,
+                                                             size_t stride) {
+  wth_nodes_body<HF, BAO>(cfg, HL, epochs, e0 + (int)blockIdx.y, htab, which, k_min, k_max, D_z, LT,
+                          nodes + stride * blockIdx.y, blockIdx.x);
 }
 
 // correlation.py:270-275 from the node table (levels <= LT), directly beyond
@@ -846,10 +868,11 @@ struct WthetaTabIntegrand {
 // theta run to 2^18..2^20 nodes (the kernel oscillates in ln k theta) and set the launch's
 // duration, hence the wide group.
 constexpr int kWthetaNW = 16;
+// (the body of k_wtheta and k_wtheta_epochs: theta[0] into out[0])
 template <bool HF, bool BAO>
-__global__ __launch_bounds__(64 * kWthetaNW) void k_wtheta(chomp_config cfg, TabLayout HL, ProjLayout L,
-                                                const Epoch* __restrict__ epochs, int e,
-                                                const double* __restrict__ htab, int which,
+__device__ __forceinline__ void wth_direct_body(const chomp_config& cfg, const TabLayout& HL,
+                                                const ProjLayout& L, const Epoch* __restrict__ epochs,
+                                                int e, const double* __restrict__ htab, int which,
                                                 const ProjDev* __restrict__ pd,
                                                 const double* __restrict__ ptab, double k_min,
                                                 double k_max, double D_z,
@@ -868,12 +891,39 @@ __global__ __launch_bounds__(64 * kWthetaNW) void k_wtheta(chomp_config cfg, Tab
   __syncthreads();
   P.template finish_t<BAO>();
   const KernelView K{kpp, L.NKT, pd->ln_kt_min, pd->ln_kt_max};
-  const double th = theta[blockIdx.x];
+  const double th = theta[0];
   WthetaTabIntegrand<HF, BAO> f{nodes, LT, {&P, &K, th, 1.0 / (D_z * D_z), log(th)}};
   const RombergOut<1> r = romberg_group<kWthetaNW, 1>(f, log(k_min), log(k_max),
                                                       cfg.global_precision, cfg.corr_precision,
                                                       cfg.divmax, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = r.value[0];
+  if (threadIdx.x == 0) out[0] = r.value[0];
+}
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(64 * kWthetaNW) void k_wtheta(chomp_config cfg, TabLayout HL, ProjLayout L,
+                                                const Epoch* __restrict__ epochs, int e,
+                                                const double* __restrict__ htab, int which,
+                                                const ProjDev* __restrict__ pd,
+                                                const double* __restrict__ ptab, double k_min,
+                                                double k_max, double D_z,
+                                                const double* __restrict__ theta,
+                                                double* __restrict__ out,
+                                                const double* __restrict__ nodes, int LT) {
+  wth_direct_body<HF, BAO>(cfg, HL, L, epochs, e, htab, which, pd, ptab, k_min, k_max, D_z,
+                           theta + blockIdx.x, out + blockIdx.x, nodes, LT);
+}
+// ... with an epoch axis: grid (n_theta, E), block 64 * kWthetaNW; row blockIdx.y integrates
+// epoch e0 + blockIdx.y from its own node table into out[blockIdx.y * n_theta + blockIdx.x].
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(64 * kWthetaNW) void k_wtheta_epochs(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, double k_min, double k_max, double D_z,
+    const double* __restrict__ theta, double* __restrict__ out, const double* __restrict__ nodes,
+    int LT, size_t stride) {
+  wth_direct_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pd, ptab, k_min,
+                           k_max, D_z, theta + blockIdx.x,
+                           out + (size_t)blockIdx.y * gridDim.x + blockIdx.x,
+                           nodes + stride * blockIdx.y, LT);
 }
 
 // ---------------------------------------------------------------------------
@@ -933,10 +983,31 @@ struct WthSeg {
 // 256 * kWthItems nodes.  No block waits for another.
 constexpr int kWthParts = 8;
 __host__ __device__ inline size_t wth_rec_count(int LT) { return ((size_t)1 << LT) / kWthItems + 2; }
-__global__ __launch_bounds__(256) void k_wtheta_moments(const double* __restrict__ nodes, int LT,
-                                                        int nseg, double a, double b,
-                                                        double* __restrict__ rec,
-                                                        double* __restrict__ segtot) {
+
+// The epoch axis (chomp_wtheta_epochs: one w(theta) per HOD of a design or chain).  The epochs of
+// a call share everything but the node table g_j, so a chunk of E epochs keeps E copies of the
+// single-epoch scratch -- node table, moment records, segment totals, in that order -- one after
+// another in the context's w(theta) work buffer at a fixed stride (wth_epoch_stride: 12 MiB at
+// the default divmax = 20), and the *_epochs kernels address epoch i at i * stride.  A call
+// works its epochs off in chunks of kWthEpochChunk = 16, which bounds the buffer at 192 MiB
+// however many epochs are asked for, while a chunk still fills the device (16 x 513 node blocks,
+// 16 x n_theta Romberg blocks).  CHOMP_TUNE_WTHETA_EPOCH_CHUNK overrides the chunk (at most
+// kWthEpochChunkMax, the 3 GiB mark).  Per (theta, epoch) the arithmetic is the single-epoch
+// kernels': both sets of __global__s call the same bodies.
+constexpr int kWthEpochChunk = 16;
+constexpr int kWthEpochChunkMax = 256;
+// The doubles of one epoch's scratch (fast: with the records and totals of the moment route);
+// even, so that every epoch's records stay 16-byte aligned.
+inline size_t wth_epoch_stride(int LT, int nseg, bool fast) {
+  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const size_t n = n_nodes + 1 + (fast ? 4 * wth_rec_count(LT) + 4 * (size_t)(LT + 1) * (size_t)nseg + 2 : 0);
+  return (n + 1) & ~(size_t)1;
+}
+
+// (the body of k_wtheta_moments and k_wtheta_moments_epochs; part: the block's part of its segment)
+__device__ __forceinline__ void wth_moments_body(const double* __restrict__ nodes, int LT, int nseg,
+                                                 double a, double b, double* __restrict__ rec,
+                                                 double* __restrict__ segtot, unsigned part) {
   __shared__ double wtot[2][4][4];
   __shared__ double ctot[4][4];
   const int m = blockIdx.x, lev = blockIdx.y + 1, t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -947,9 +1018,9 @@ __global__ __launch_bounds__(256) void k_wtheta_moments(const double* __restrict
   const long len = j1 - j0;
   long parts = (len + kTile - 1) / kTile;
   parts = parts > kWthParts ? kWthParts : parts;
-  if ((long)blockIdx.z >= parts) return;                    // (block-uniform; also len == 0)
+  if ((long)part >= parts) return;                          // (block-uniform; also len == 0)
   const long plen = (len + parts - 1) / parts;
-  const long p0 = j0 + plen * blockIdx.z;
+  const long p0 = j0 + plen * part;
   const long p1 = p0 + plen < j1 ? p0 + plen : j1;
   const double h = (b - a) / (double)n, lox = a + 0.5 * h;
   const double O = G.origin(m);
@@ -1047,6 +1118,23 @@ __global__ __launch_bounds__(256) void k_wtheta_moments(const double* __restrict
     for (int q = 0; q < 4; ++q) carry[q] = next[q];
   }
 }
+__global__ __launch_bounds__(256) void k_wtheta_moments(const double* __restrict__ nodes, int LT,
+                                                        int nseg, double a, double b,
+                                                        double* __restrict__ rec,
+                                                        double* __restrict__ segtot) {
+  wth_moments_body(nodes, LT, nseg, a, b, rec, segtot, blockIdx.z);
+}
+// ... with an epoch axis: grid (nseg, LT, kWthParts * E), block 256; blockIdx.z = part +
+// kWthParts * epoch, every epoch's node table, records and segment totals `stride` doubles after
+// the previous epoch's.
+__global__ __launch_bounds__(256) void k_wtheta_moments_epochs(const double* __restrict__ nodes,
+                                                               int LT, int nseg, double a, double b,
+                                                               double* __restrict__ rec,
+                                                               double* __restrict__ segtot,
+                                                               size_t stride) {
+  const size_t off = stride * (blockIdx.z / kWthParts);
+  wth_moments_body(nodes + off, LT, nseg, a, b, rec + off, segtot + off, blockIdx.z % kWthParts);
+}
 
 // Moments of the whole of segment m (0 for an empty one).
 __device__ __forceinline__ void wth_seg_total(const double* __restrict__ segtot, int m,
@@ -1073,15 +1161,15 @@ __device__ __forceinline__ double wth_combine(const double (&D)[4], double dl, d
 // (four levels a round); lane i <= NP holds knot i of the kernel spline: the first node at or
 // beyond it and the prefix moments just below.  Levels <= LT only (the host keeps the
 // node-by-node kernel for a divmax beyond the table).  Needs NKT <= 63.
-__global__ __launch_bounds__(256) void k_wtheta_fast(chomp_config cfg, ProjLayout L,
-                                                     const ProjDev* __restrict__ pd,
-                                                     const double* __restrict__ ptab, double k_min,
-                                                     double k_max, const double* __restrict__ theta,
-                                                     double* __restrict__ out,
-                                                     const double* __restrict__ nodes,
-                                                     const double* __restrict__ rec,
-                                                     const double* __restrict__ segtot, int LT,
-                                                     int nseg) {
+// (the body of k_wtheta_fast and k_wtheta_fast_epochs: theta[0] into out[0])
+__device__ __forceinline__ void wth_fast_body(const chomp_config& cfg, const ProjLayout& L,
+                                              const ProjDev* __restrict__ pd,
+                                              const double* __restrict__ ptab, double k_min,
+                                              double k_max, const double* __restrict__ theta,
+                                              double* __restrict__ out,
+                                              const double* __restrict__ nodes,
+                                              const double* __restrict__ rec,
+                                              const double* __restrict__ segtot, int LT, int nseg) {
   __shared__ double level_sum[2][4];
   __shared__ double ctab[(kWthetaTabLevel + 1) * 32];   // the rows' weights (RombergRows2::ctab)
   romberg_weights_to_lds(ctab, LT);
@@ -1091,7 +1179,7 @@ __global__ __launch_bounds__(256) void k_wtheta_fast(chomp_config cfg, ProjLayou
   const double lo = pd->ln_kt_min, hi = pd->ln_kt_max;
   const int NP = L.NKT - 1;                              // spline pieces
   const double dxK = (hi - lo) / (double)NP;
-  const double s = log(theta[blockIdx.x]);
+  const double s = log(theta[0]);
   const double* pp = ptab + L.k_pp;
   const int piece = lane < NP ? lane : NP - 1;
   const double c0 = pp[4 * piece], c1 = pp[4 * piece + 1], c2 = pp[4 * piece + 2],
@@ -1196,7 +1284,33 @@ __global__ __launch_bounds__(256) void k_wtheta_fast(chomp_config cfg, ProjLayou
     for (int q = 0; q < 4 && 4 * g + 1 + q <= LT && !R.all_done(); ++q)
       R.advance(4 * g + 1 + q, level_sum[g & 1][q], 0.0);
   }
-  if (threadIdx.x == 0) out[blockIdx.x] = R.value[0];
+  if (threadIdx.x == 0) out[0] = R.value[0];
+}
+__global__ __launch_bounds__(256) void k_wtheta_fast(chomp_config cfg, ProjLayout L,
+                                                     const ProjDev* __restrict__ pd,
+                                                     const double* __restrict__ ptab, double k_min,
+                                                     double k_max, const double* __restrict__ theta,
+                                                     double* __restrict__ out,
+                                                     const double* __restrict__ nodes,
+                                                     const double* __restrict__ rec,
+                                                     const double* __restrict__ segtot, int LT,
+                                                     int nseg) {
+  wth_fast_body(cfg, L, pd, ptab, k_min, k_max, theta + blockIdx.x, out + blockIdx.x, nodes, rec,
+                segtot, LT, nseg);
+}
+// ... with an epoch axis: grid (n_theta, E), block 256: one Romberg per (theta, epoch), epoch
+// blockIdx.y from its own tables (`stride` doubles apart) into out[blockIdx.y * n_theta +
+// blockIdx.x]; epochs stop at their own levels.  theta is the fast grid axis, so the blocks that
+// are resident together mostly share an epoch and its records in L2.
+__global__ __launch_bounds__(256) void k_wtheta_fast_epochs(
+    chomp_config cfg, ProjLayout L, const ProjDev* __restrict__ pd, const double* __restrict__ ptab,
+    double k_min, double k_max, const double* __restrict__ theta, double* __restrict__ out,
+    const double* __restrict__ nodes, const double* __restrict__ rec,
+    const double* __restrict__ segtot, int LT, int nseg, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  wth_fast_body(cfg, L, pd, ptab, k_min, k_max, theta + blockIdx.x,
+                out + (size_t)blockIdx.y * gridDim.x + blockIdx.x, nodes + off, rec + off,
+                segtot + off, LT, nseg);
 }
 
 // ---------------------------------------------------------------------------

@@ -7,7 +7,8 @@ set_cosmology / set_halo / set_hod and the requested method.  That generic loop 
 (it works with every chomp_amd object).  When the object is a Halo and the method one of
 its spectra, the design is the native batch axis of the device library: every design
 point becomes one epoch of a HaloGrid and all of them are built and evaluated by the same
-kernel launches.
+kernel launches.  A design over HOD parameters of
+Correlation.correlation is batched the same way, through Correlation.correlation_hods.
 """
 import copy
 import warnings
@@ -16,6 +17,7 @@ import numpy
 import pandas
 
 from . import _lib
+from . import correlation as correlation_mod
 from . import defaults
 from . import grid
 from . import halo as halo_mod
@@ -132,7 +134,45 @@ class SimulationDesign(object):
             values = getattr(self._input_object, self._method)(self._ind_var)
         return pandas.Series(numpy.asarray(values).flatten())
 
+    def _hods_design_scope(self):
+        """ChompScopeError unless this design is one Correlation.correlation_hods serves: exactly a
+        Correlation, its `correlation` over an independent variable, only HOD parameters varying
+        (a cosmology point needs its own projection set-up, and a context holds one; halo
+        parameters keep the loop as in the Halo route), and the object within correlation_hods'
+        own scope.  No device work."""
+        obj = self._input_object
+        why = None
+        if type(obj) is not correlation_mod.Correlation:
+            why = "the object is a %s, not exactly a correlation.Correlation" % type(obj).__name__
+        elif self._method != "correlation":
+            why = "the method is %r, not 'correlation'" % (self._method,)
+        elif self._ind_var is None:
+            why = "no independent_var (theta) is given"
+        elif not self._vary_hod:
+            why = "no HOD parameter varies"
+        elif self._vary_cosmology:
+            why = "a cosmology parameter varies"
+        elif self._vary_halo:
+            why = "a halo parameter varies ('alpha' names the halo profile's slope first)"
+        if why is not None:
+            raise _lib.ChompScopeError("the batched design over Correlation.correlation_hods does "
+                                       "not serve this design: %s; use batched=False" % why)
+        obj._hods_scope()
+
+    def _batched_route(self):
+        """"halo" / "correlation": the batched route this design takes by itself; None: the loop."""
+        if isinstance(self._input_object, correlation_mod.Correlation):
+            try:
+                self._hods_design_scope()
+            except _lib.ChompScopeError:
+                return None
+            return "correlation"
+        return "halo" if self._batched_halo() else None
+
     def _batched(self):
+        return self._batched_route() is not None
+
+    def _batched_halo(self):
         obj = self._input_object
         # Halo.set_halo only reaches the mass function and leaks into later points through
         # set_cosmology (halo.py:151-162, 220-235): designs over halo parameters keep the
@@ -167,7 +207,10 @@ class SimulationDesign(object):
         # concern.  What the point-by-point loop reports through Halo._sync (an exhausted divmax =
         # scipy's AccuracyWarning; a saturated mass-limit search, where the reference's own answer
         # is decided by rounding noise and may differ by percents) must not get lost in a batch.
-        words = hg.status()
+        self._warn_design_status(hg.status(), stacklevel=4)
+        return pandas.DataFrame(numpy.asarray(out).T, columns=self.points.index)
+
+    def _warn_design_status(self, words, stacklevel):
         self.design_status = pandas.Series([int(w) for w in words], index=self.points.index,
                                            name="status", dtype="int64")
         for label, w in self.design_status.items():
@@ -176,13 +219,39 @@ class SimulationDesign(object):
                             if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
                             else _lib.ChompAccuracyWarning)
                 warnings.warn("design point %s: %s" % (label, "; ".join(_lib.describe_status(w))),
-                              category, stacklevel=3)
+                              category, stacklevel=stacklevel)
+
+    def _run_batched_hods(self):
+        """Every design point = one HOD of one Correlation.correlation_hods call."""
+        real, rec = self._input_object, _Recorder()
+        self._hods_design_scope()             # (ChompScopeError before anything is recorded)
+        hods = []
+        self._input_object = rec
+        try:
+            for _, point in self.points.iterrows():
+                rec.cosmo = rec.halo = rec.hod = None
+                self._apply_point(point)
+                hods.append(_point_hod(real.halo.local_hod, rec.hod))
+        finally:
+            self._input_object = real
+        theta = numpy.asarray(self._ind_var, dtype=numpy.float64)
+        with warnings.catch_warnings():       # (raised below, naming the design point)
+            warnings.simplefilter("ignore", _lib.ChompAccuracyWarning)
+            warnings.simplefilter("ignore", _lib.ChompParityWarning)
+            out, words = real.correlation_hods(theta.ravel(), hods, with_status=True)
+        self._warn_design_status(words, stacklevel=4)
         return pandas.DataFrame(numpy.asarray(out).T, columns=self.points.index)
 
     def run_design(self, batched=None, with_status=False):
         """simulation_design.py:140-155.  Returns a DataFrame with one column per design
         point holding the flattened output of the method.  batched=None picks the
-        one-launch path when the object / method allow it.
+        one-launch path when the object / method allow it: a Halo and one of its spectra
+        (cosmology and HOD may vary), or a Correlation, its `correlation` and a design over HOD
+        parameters only (Correlation.correlation_hods, with its scope).  A Correlation design
+        that varies cosmology or halo parameters keeps the point-by-point loop: a cosmology
+        point needs its own projection set-up, and a device context holds one.  batched=False
+        forces the loop; batched=True on a Correlation raises ChompScopeError when the object
+        or the design is outside that scope (nothing a point sets is ever dropped silently).
 
         The batched path keeps the status word of every design point (chomp_get_status bits) in
         `self.design_status` (an int64 Series indexed like the design points) and raises them as
@@ -194,7 +263,12 @@ class SimulationDesign(object):
             batched = self._batched()
         self.design_status = None
         if batched:
-            self.design_values = self._run_batched()
+            route = self._batched_route()
+            if route is None:                  # (forced)
+                route = ("correlation" if isinstance(self._input_object, correlation_mod.Correlation)
+                         else "halo")
+            self.design_values = (self._run_batched_hods() if route == "correlation"
+                                  else self._run_batched())
         else:
             self.design_values = self.points.transpose().apply(self._run_des_point)
         self.values_frame = self.design_values
@@ -273,3 +347,34 @@ class SimulationDesignHubbleNormalizedDensities(SimulationDesign):
         cosmo_dict['omega_b0'] = values['omega_bh2'] / cosmo_dict['h'] ** 2
         cosmo_dict['omega_l0'] = 1.0 - cosmo_dict['omega_m0'] - cosmo_dict['omega_r0']
         self._input_object.set_cosmology(cosmo_dict)
+
+
+class SimulationDesignHODWakeAssumptions(SimulationDesign):
+    """simulation_design.py:268-293: the HOD design with M_0 tied to M_min (log_M_0 = log_M_min at
+    every point) in a flat universe (omega_l0 = 1 - omega_m0 - omega_r0 whenever the cosmology is
+    set).  The reference's methods name variables that do not exist there (`params`,
+    `cosmo_dict` inside set_hod); this is what they spell out: the design's values by name into
+    the dictionary, the derived parameter, then the object's setter with that dictionary."""
+
+    def __init__(self, input_chomp_object, method_name, params, n_design=100,
+                 independent_var=None, default_param_dict=None):
+        SimulationDesign.__init__(self, input_chomp_object, method_name, params,
+                                  n_design, independent_var, default_param_dict)
+
+    def set_cosmology(self, cosmo_dict=None, values=None):
+        if cosmo_dict is None:
+            cosmo_dict = self._default_param_dict['cosmo_dict']
+        for key in self.params.keys():
+            if key in cosmo_dict and key in values:
+                cosmo_dict[key] = values[key]
+        cosmo_dict['omega_l0'] = 1.0 - cosmo_dict['omega_m0'] - cosmo_dict['omega_r0']
+        self._input_object.set_cosmology(cosmo_dict)
+
+    def set_hod(self, hod_dict=None, values=None):
+        if hod_dict is None:
+            hod_dict = self._default_param_dict['hod_dict']
+        for key in self.params.keys():
+            if key in hod_dict and key in values:
+                hod_dict[key] = values[key]
+        hod_dict['log_M_0'] = hod_dict['log_M_min']
+        self._input_object.set_hod(hod_dict)

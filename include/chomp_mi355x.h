@@ -402,6 +402,10 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
  *                            in rounds (the path of a batch of hundreds of epochs, for a test)
  *   CHOMP_TUNE_WTHETA_DIRECT 1: w(theta) by evaluating the kernel spline at every Romberg node
  *                            (the checker of the moment route of chomp_wtheta)
+ *   CHOMP_TUNE_WTHETA_EPOCH_CHUNK  epochs that chomp_wtheta_epochs evaluates per round of
+ *                            launches (default 16, at most 256; its work buffer holds one chunk,
+ *                            about 12 MiB per epoch at divmax = 20): a small value lets a test
+ *                            cross the seam between two chunks with a handful of epochs
  *   CHOMP_TUNE_CELL_ONE_KERNEL 1: C_l with every Romberg level in the per-multipole kernel (the
  *                            checker of the hand-over to k_cell_deep)
  *   CHOMP_TUNE_ROCTX         1: roctx ranges around the stages on the host timeline (one per
@@ -418,7 +422,8 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
 #define CHOMP_TUNE_DEEP_MAX_BREAKS 7
 #define CHOMP_TUNE_DEEP_MAX_FINE 8
 #define CHOMP_TUNE_DEEP_SLOTS 10
-#define CHOMP_TUNE_COUNT 11
+#define CHOMP_TUNE_WTHETA_EPOCH_CHUNK 11
+#define CHOMP_TUNE_COUNT 12
 int chomp_set_tuning(chomp_ctx* ctx, int what, long long value);
 /* Measurement aid: out[7] <- knots beyond the node tables done so far (since the context was
  * created) by [0] the fast deep-level sums, [1] literal evaluation of every node; why literal:
@@ -689,6 +694,20 @@ int chomp_window_eval(chomp_ctx* ctx, int which_window, const double* chi,
 int chomp_wtheta(chomp_ctx* ctx, int which, size_t epoch, double k_min,
                  double k_max, double D_z, const double* theta, size_t n,
                  double* out, int mem);
+/* Correlation.correlation(theta) for epochs epoch0 .. epoch0 + n_epoch - 1 of one context that
+ * share the projection set-up, k range and D_z: out[e * n + i] = what chomp_wtheta(ctx, which,
+ * epoch0 + e, ..., theta, n, ...) returns at i, bit for bit.  The batch axis of an HOD design or
+ * chain (the loop of set_hod + correlation in the reference's example script, and
+ * simulation_design.py:116-155 over HOD parameters): the epochs differ in their halo-model
+ * tables only, and the three launches of chomp_wtheta run once per chunk of 16 epochs
+ * (CHOMP_TUNE_WTHETA_EPOCH_CHUNK) instead of once per epoch.  fp64 only; CHOMP_ERR_SCOPE for the
+ * narrowed precision modes, for HaloFit spectra (CHOMP_P_HALOFIT), for spectra extrapolated
+ * beyond the halo's k range (CHOMP_P_EXTRAPOLATE on a halo-model spectrum) and for a context with
+ * the wiggle transfer function (chomp_set_transfer): chomp_wtheta serves those, one epoch at a
+ * time. */
+int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
+                        double k_max, double D_z, const double* theta, size_t n, double* out,
+                        int mem);
 /* Gaussian covariance of w(theta), Covariance(corr, corr) with nongaussian_cov=False.
  *
  * chomp_covariance_table replaces Covariance._initialize_halo_splines (covariance.py:455-543,
