@@ -416,7 +416,7 @@ __device__ __forceinline__ void halo_epoch_begin(Epoch& E, const chomp_halo_par&
                                                  const HodDev& h, const double* nu_pp,
                                                  double lnm0, int NM, unsigned* status_e,
                                                  int* npend_e, int* pending, bool first_epoch) {
-  // (called by the 64 lanes of one wavefront)
+  // (called by the 64 lanes of one wavefront, any of the block's)
   apply_halo_hod_wave(E, hp, h, nu_pp, lnm0, NM);
   if ((threadIdx.x & 63) != 0) return;
   atomicAnd(status_e, ~kStHaloBits);
@@ -500,17 +500,19 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
   MassLds M;
   M.carve(sm, L.NM);
   const int n_search = (int)(search[(e * 2 + 0) * 2 + 1] + search[(e * 2 + 1) * 2 + 1]);
+  // (halo_epoch_begin needs m_star and the nu spline, not the normalisations: on the block's last
+  //  wavefront beside the normalisation pass, which leaves it idle; the record that the first
+  //  block publishes at the end of mass_setup_block then carries the halo / HOD constants)
   mass_setup_block(cfg, L, E, epochs, e, first, search[(e * 2 + 0) * 2], search[(e * 2 + 1) * 2],
-                   n_search, tab + (size_t)e * L.stride, mass_par[e], mf_kind, tinker, gl16, M);
+                   n_search, tab + (size_t)e * L.stride, mass_par[e], mf_kind, tinker, gl16, M,
+                   [&] {
+                     if (do_nodes)
+                       halo_epoch_begin(E, profile[e], hod[e], M.c_nu, M.x_lnm[0], L.NM,
+                                        first ? &status[e] : &scratch_status,
+                                        first ? &npend[e] : &scratch_npend, pending,
+                                        first && e == 0);
+                   });
   if (!do_nodes) return;
-  if (threadIdx.x < 64)
-    halo_epoch_begin(E, profile[e], hod[e], M.c_nu, M.x_lnm[0], L.NM,
-                     first ? &status[e] : &scratch_status, first ? &npend[e] : &scratch_npend,
-                     pending, first && e == 0);
-  __syncthreads();
-  if (first)
-    copy_doubles(reinterpret_cast<double*>(&epochs[e]), reinterpret_cast<const double*>(&E),
-                 kEpochDoubles);
   const int group = pick_group((int)blockIdx.y, g0, g1, g2, g3);
   if (group < 0 || group > 3) return;            // n_bar only: the record is all it needs
   halo_nodes_block(cfg, L, E, S, M.y_nu, M.c_lnm, group, (mask & kMaskExclusion) != 0,

@@ -1132,11 +1132,16 @@ __host__ __device__ inline int mass_lds_doubles(int NM) {
   return 2 * NM + 8 * (NM - 1) + 18 * NM + 32 + romberg_scratch<4, 2>();
 }
 
+// beside: called by the 64 lanes of the block's last wavefront once m_star and the splines
+// stand and before the record is published -- work that needs neither normalisation and writes
+// fields of E that nothing here reads (a halo set-up's halo_epoch_begin).  The normalisation
+// pass keeps that wavefront idle (128 nodes on threads 0..127), so it runs beside the pass.
+template <class Beside>
 __device__ __forceinline__ void mass_setup_block(
     const chomp_config& cfg, const TabLayout& L, Epoch& E, Epoch* __restrict__ epochs, int e,
     bool publish, double ln_mass_min, double ln_mass_max, int n_search, double* __restrict__ t,
     const chomp_halo_par& hp, int mf_kind, const TinkerTab* __restrict__ tinker,
-    const double* __restrict__ gl16, const MassLds& M) {
+    const double* __restrict__ gl16, const MassLds& M, Beside&& beside) {
   const int NM = L.NM;
   copy_doubles(M.x_lnm, t + L.off_ln_mass, NM);
   copy_doubles(M.y_nu, t + L.off_nu, NM);
@@ -1217,6 +1222,7 @@ __device__ __forceinline__ void mass_setup_block(
                                     cfg.mass_precision, cfg.divmax, M.red);
     __syncthreads();
     if (threadIdx.x == 0) E.bias_norm = 1.0 / norm;
+    if (threadIdx.x >= blockDim.x - 64) beside();     // (every wavefront integrates here: behind it)
     __syncthreads();
   } else {
     // both integrals in one pass over the 128 nodes (f_norm = bias_norm = 1 in E meanwhile):
@@ -1225,6 +1231,7 @@ __device__ __forceinline__ void mass_setup_block(
     constexpr int NT = 256;
     const double wd = (b - a) / 8.0;
     double p1 = 0.0, p2 = 0.0;
+    if (threadIdx.x >= NT - 64) beside();             // (no node of the pass on these threads)
     for (int idx = threadIdx.x; idx < 16 * 8; idx += NT) {
       const int pn = idx >> 4, q = idx & 15;
       const double mid = a + wd * ((double)pn + 0.5);
