@@ -1149,14 +1149,18 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   }
   // (one cosmology or a few: most blocks, shortest launch; a batch of many: four nodes per
   //  thread and the ln S integrals one per wavefront -- see k_sigma_nodes)
-  const unsigned gy = (unsigned)(n_slots + (n_epoch + 255) / 256);
+  // (the probes as one launch -- n_epoch < 128, launch_epoch_probe -- take chi from this launch:
+  //  its chi rows, one block per epoch; a large batch integrates it in its probing phase)
+  const bool chi_here = n_epoch < (size_t)kProbeLargeBatch;
   rc = with_flag(ctx->with_bao, n_slots >= 16, [&](auto BAO, auto MANY) {
     constexpr int NPT = MANY ? 4 : 1;
-    hipLaunchKernelGGL((k_sigma_nodes<BAO, NPT>),
-                       dim3(sigma_node_blocks<NPT>() + sigma_lns_blocks<NPT>() + sigma_gtab_blocks<NPT>(), gy),
+    constexpr int gx = sigma_node_blocks<NPT>() + sigma_lns_blocks<NPT>() + sigma_gtab_blocks<NPT>();
+    const unsigned gy = (unsigned)(n_slots + sigma_epoch_rows((int)n_epoch) +
+                                   (chi_here ? sigma_chi_rows((int)n_epoch, gx) : 0));
+    hipLaunchKernelGGL((k_sigma_nodes<BAO, NPT>), dim3(gx, gy),
                        dim3(256), 0, ctx->stream, ctx->cfg, ctx->d_cosmo, ctx->d_z, ctx->d_first,
                        ctx->d_slot, (int)n_slots, (int)n_epoch, ctx->d_epochs, ctx->d_snodes,
-                       ctx->d_status);
+                       ctx->d_status, chi_here ? ctx->d_probe : nullptr);
     if (!MANY) return CHOMP_OK;
     // ... and the aiming tables behind them (the g table of a cosmology staged in LDS; the
     // instance with BAO stages none)
@@ -1177,7 +1181,7 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
                        ctx->d_status);
   // (k_epoch_probe lives in chomp_probe.hip: the one kernel that is faster WITH machine LICM --
   //  but for the probing phase of a large batch, one wavefront per probe, compiled here)
-  if (n_epoch >= 128)
+  if (n_epoch >= (size_t)kProbeLargeBatch)
     with_flag(ctx->with_bao, [&](auto BAO) {
       hipLaunchKernelGGL((k_epoch_probe<BAO, 1, 1>), dim3((unsigned)n_epoch, 2 * kProbes), dim3(64), 0,
                          ctx->stream, ctx->cfg, ctx->d_epochs, ctx->d_search, ctx->d_cand, ctx->d_snodes,

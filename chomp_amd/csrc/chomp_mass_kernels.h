@@ -338,6 +338,24 @@ __host__ __device__ constexpr int sigma_lns_blocks() { return NPT == 1 ? kSGrid 
 template <int NPT>
 __host__ __device__ constexpr int sigma_gtab_blocks() { return (kGTabCount + 256 * NPT - 1) / (256 * NPT); }
 
+// The probe record of an epoch (k_epoch_probe, chomp_probe_kernel.h).
+constexpr int kProbes = 4;
+constexpr int kProbeStride = 24;   // doubles per epoch: nu[2][kProbes], chi, pad[3], plan[2][4]
+// Epochs from which the probes are two launches (probing, certifying) and chi is the probing
+// phase's; below, one launch with chi from k_sigma_nodes.
+constexpr int kProbeLargeBatch = 128;
+
+// Rows of the grid behind the cosmologies' (blockIdx.y >= n_slots): the epoch rows, one thread
+// per epoch in their first block, and -- probe != nullptr, a (k, z) grid or a small batch, whose
+// mass-limit probes run as ONE launch behind this one -- the chi rows, one block per epoch: the
+// comoving distance, which depends on nothing this launch computes, into the epoch's probe
+// record.  It was the head of one of the long mass_max-side probes of k_epoch_probe, i.e. on
+// the critical path of that launch; here it ends well inside the ln S integrals.
+__host__ __device__ constexpr int sigma_epoch_rows(int n_epoch) { return (n_epoch + 255) / 256; }
+__host__ __device__ constexpr int sigma_chi_rows(int n_epoch, int blocks_x) {
+  return (n_epoch + blocks_x - 1) / blocks_x;
+}
+
 template <bool BAO, int NPT>
 __global__ __launch_bounds__(256) void k_sigma_nodes(chomp_config cfg,
                                                      const chomp_cosmo* __restrict__ cosmo,
@@ -346,11 +364,26 @@ __global__ __launch_bounds__(256) void k_sigma_nodes(chomp_config cfg,
                                                      const int* __restrict__ slots, int n_slots,
                                                      int n_epoch, Epoch* __restrict__ epochs,
                                                      double* __restrict__ snodes,
-                                                     unsigned* __restrict__ status) {
+                                                     unsigned* __restrict__ status,
+                                                     double* __restrict__ probe) {
   static_assert(NPT == 1 || NPT == 4, "nodes per thread");
   static_assert(kSGrid % 4 == 0, "four ln S points to a block");
   __shared__ Epoch E;
   __shared__ double red[romberg_scratch<4, 1>()];
+  if ((int)blockIdx.y >= n_slots + sigma_epoch_rows(n_epoch)) {
+    // ---- chi row (only launched with probe != nullptr): comoving distance of one epoch,
+    // cosmology.py:106-110, from the inputs as epoch_background reads them
+    const int e = ((int)blockIdx.y - n_slots - sigma_epoch_rows(n_epoch)) * (int)gridDim.x +
+                  (int)blockIdx.x;
+    if (e >= n_epoch) return;                       // (block-uniform)
+    const chomp_cosmo c = cosmo[e];
+    const double z = zin[e] < 0.0 ? 0.0 : zin[e];
+    EIntegrand f{c.omega_m0, c.omega_l0, c.omega_r0, 100.0 / (2.998 * 100000.0)};
+    const double chi = romberg1<4>(f, 0.0, z, cfg.global_precision, cfg.cosmo_precision,
+                                   cfg.divmax, red);
+    if (threadIdx.x == 0) probe[(size_t)e * kProbeStride + 2 * kProbes] = chi;
+    return;
+  }
   if ((int)blockIdx.y >= n_slots) {
     const int e = ((int)blockIdx.y - n_slots) * 256 + (int)threadIdx.x;
     if (blockIdx.x != 0 || e >= n_epoch) return;
@@ -991,8 +1024,6 @@ using int_c = std::integral_constant<int, N>;
 void launch_epoch_probe(bool bao, unsigned n_epoch, hipStream_t stream, const chomp_config& cfg,
                         Epoch* epochs, double* search, const double* cand, const double* snodes,
                         double* probe, int* count, unsigned* status);
-constexpr int kProbes = 4;
-constexpr int kProbeStride = 24;   // doubles per epoch: nu[2][kProbes], chi, pad[3], plan[2][4]
 
 // ---------------------------------------------------------------------------
 // k_nu_table: one sigma(R) Romberg of the nu table per block of 64 NW threads,

@@ -8,9 +8,11 @@
 namespace chomp {
 
 // grid (n_epoch, 2 * kProbes), block 64 * kInitNW.  blockIdx.y = kProbes * side + p
-// certifies candidate j - 2 + p of side 0 (mass_min) / 1 (mass_max); role kProbes also
-// does the comoving distance (or only that, with fixed mass limits; a ninth block per epoch
-// for it was measured: 576 blocks for 512 resident ones, 34.1 against 32.8 us).  The last block of
+// certifies candidate j - 2 + p of side 0 (mass_min) / 1 (mass_max).  The comoving distance is
+// in the epoch's probe record when PHASE 0 starts (k_sigma_nodes' chi rows: as the head of role
+// kProbes it made that block the last of its epoch in a third of the epochs, 1.9 us of the
+// launch); role kProbes of a large batch's probing phase integrates it, and with fixed mass
+// limits it is the one block of an epoch that works: chi and the limits' logarithms.  The last block of
 // an epoch to finish combines the results (count[e], reset by it): a side whose probes
 // show "fails at c - 1, passes at c" is settled; any other (the estimate off by more than
 // the probes cover, a walk that leaves the ln S table: rare) falls back to the bracketing
@@ -22,7 +24,10 @@ namespace chomp {
 // L2 write-back on this chip -- costs more than the probes: PHASE 1 (the same grid) only
 // probes, PHASE 2 (grid n_epoch) certifies behind the kernel boundary.  Same numbers.
 // NW: wavefronts per block.  kInitNW for a (k, z) grid (the launch lasts as long as one probe:
-// four wavefronts on each) and for the certifying phase; 1 for the probing phase of a large
+// four wavefronts on each; eight, with or without the 128-register cap that keeps all 512 blocks
+// of 64 epochs resident, lengthen the step by 6-11 us: a probe is a chain of Romberg levels of a
+// node or two per lane, and a wider block only adds to each level's hand-over) and
+// for the certifying phase; 1 for the probing phase of a large
 // batch -- its 8 n_epoch integrals fill the chip as single wavefronts, with no barrier or LDS
 // hand-over per Romberg level (1024 epochs: 241 -> 72 us; the four-wavefront kernel ran at 41 % of
 // its VALU issue rate).
@@ -55,14 +60,19 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 4 : 1) void k_epoch_probe(
   }
   __syncthreads();
   double* pr = probe + (size_t)e * kProbeStride;
-  if (chi_role) {                  // comoving distance, cosmology.py:106-110
-    EIntegrand f{E.om0, E.ol0, E.or0, E.H0};
-    const double chi = romberg1<NW>(f, 0.0, E.z, cfg.global_precision,
-                                         cfg.cosmo_precision, cfg.divmax, red);
-    __syncthreads();
+  if (chi_role && (PHASE != 0 || fixed)) {
+    double chi;
+    if constexpr (PHASE == 0) {    // (from k_sigma_nodes' chi rows, the launch before)
+      chi = pr[2 * kProbes];
+    } else {                       // comoving distance, cosmology.py:106-110
+      EIntegrand f{E.om0, E.ol0, E.or0, E.H0};
+      chi = romberg1<NW>(f, 0.0, E.z, cfg.global_precision, cfg.cosmo_precision, cfg.divmax, red);
+      __syncthreads();
+    }
     if (threadIdx.x == 0) {
       E.chi = chi;
-      __hip_atomic_store(pr + 2 * kProbes, chi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (PHASE != 0)
+        __hip_atomic_store(pr + 2 * kProbes, chi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     if (fixed) {
