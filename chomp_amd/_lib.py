@@ -124,7 +124,8 @@ EXPORTS = [
     "chomp_eval", "chomp_halofit_get", "chomp_halofit_put",
     "chomp_multi_epoch_setup", "chomp_me_eval",
     "chomp_kernel_setup", "chomp_kernel_info", "chomp_kernel_table",
-    "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_wtheta_epochs", "chomp_cell",
+    "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_wtheta_epochs",
+    "chomp_cell", "chomp_cell_epochs",
     "chomp_set_precision", "chomp_xi3d", "chomp_spline_eval", "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
     "chomp_covariance_table", "chomp_covariance_gaussian",
@@ -413,6 +414,7 @@ def lib():
         L.chomp_wtheta.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, i]
         L.chomp_wtheta_epochs.argtypes = [vp, i, sz, sz, d, d, d, vp, sz, vp, i]
         L.chomp_cell.argtypes = [vp, i, sz, d, vp, sz, vp, i]
+        L.chomp_cell_epochs.argtypes = [vp, i, sz, sz, d, vp, sz, vp, i]
         L.chomp_wtheta_cell.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, vp, sz, vp, i]
         L.chomp_set_precision.argtypes = [vp, i]
         L.chomp_hod_stats.argtypes = [vp, sz, sz, c_double_p]
@@ -1358,3 +1360,10 @@ class Context(object):
 
     def cell(self, which, epoch, D_z, ell):
         return self._run(self._L.chomp_cell, [ell], _elementwise(int(which), epoch, float(D_z)))[0]
+
+    def cell_epochs(self, which, epoch0, n_epoch, D_z, ell):
+        """C_l of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (chomp_cell_epochs):
+        [n_epoch, ell.size], row e what cell(which, epoch0 + e, D_z, ell) returns, bit for bit."""
+        return self._run(self._L.chomp_cell_epochs, [ell], lambda mem, new, el: (
+            int(which), int(epoch0), int(n_epoch), float(D_z), el, _numel(el),
+            new((int(n_epoch), _numel(el))), mem))[0]

@@ -135,6 +135,8 @@ class Correlation(object):
         return float(out[0]) if th.ndim == 0 else out.reshape(th.shape)
 
     # -- the batch over HODs ---------------------------------------------------
+    _hods_export = "chomp_wtheta_epochs"      # (the C entry point behind correlation_hods)
+
     def _hods_scope(self, hods=None):
         """ChompScopeError unless correlation_hods serves this object (and `hods`); no device
         work.  Returns the HODs as objects."""
@@ -149,7 +151,7 @@ class Correlation(object):
         if getattr(h, "_general_profile", False):
             refuse("a general_profile halo (HaloGrid batches NFW epochs)")
         if h.get_extrapolation():
-            refuse("an extrapolated spectrum (chomp_wtheta_epochs takes none)")
+            refuse("an extrapolated spectrum (%s takes none)" % self._hods_export)
         if getattr(h.cosmo, "_with_bao", False):
             refuse("a with_bao cosmology")
         # HaloGrid's epochs take ONE halo dictionary for the mass function and the profile; after
@@ -168,7 +170,8 @@ class Correlation(object):
         return objs
 
     def correlation_hods(self, theta_rad, hods, with_status=False):
-        """w(theta) for many HODs in one call: the array [len(hods), theta.size] whose row i is
+        """w(theta) for many HODs in one call (on a CorrelationFourier: C_l, theta_rad being l;
+        the two classes differ in _hods_evaluate alone): the array [len(hods), theta.size] whose row i is
         what set_hod_object(<hods[i] as an object>) followed by correlation(theta_rad) returns on
         a fresh Halo -- the loop of the reference's example script (example_script.py:141-143)
         as one batch.  hods: HOD dictionaries (HODZheng's) or hod.HODZheng / hod.HODMandelbaum
@@ -220,8 +223,7 @@ class Correlation(object):
             hg.set_parameters(hod=objs)
         self.kernel._setup_on(hg.ctx)
         hg.setup(self._power_name)
-        out = hg.ctx.wtheta_epochs(h._power_code(code), 0, n_hod, self._k_lim[0], self._k_lim[1],
-                                   self.D_z, flat)
+        out = self._hods_evaluate(hg.ctx, h._power_code(code), n_hod, flat)
         words = hg.status()                    # (synchronises: the words belong to this result)
         self.hods_status = words
         for i, w in enumerate(words):
@@ -233,6 +235,11 @@ class Correlation(object):
                 warnings.warn("HOD %d: %s" % (i, "; ".join(_lib.describe_status(w))), category,
                               stacklevel=2)
         return (out, words) if with_status else out
+
+    def _hods_evaluate(self, ctx, code, n_hod, flat):
+        """The one call of correlation_hods that knows the observable: [n_hod, flat.size] of the
+        grid's epochs 0 .. n_hod - 1 on its context."""
+        return ctx.wtheta_epochs(code, 0, n_hod, self._k_lim[0], self._k_lim[1], self.D_z, flat)
 
     def write(self, output_file_name):
         with open(output_file_name, "w") as f:
@@ -279,6 +286,20 @@ class CorrelationFourier(Correlation):
         out = ctx.cell(code, 0, self.D_z, numpy.ascontiguousarray(la).ravel())
         self.halo._resolve_status()
         return float(out[0]) if la.ndim == 0 else out.reshape(la.shape)
+
+    # -- the batch over HODs ---------------------------------------------------
+    _hods_export = "chomp_cell_epochs"
+
+    def _hods_evaluate(self, ctx, code, n_hod, flat):
+        """correlation_hods(l, hods, with_status=False) is Correlation's, inherited whole -- the
+        scope and its refusals, the kept HaloGrid and its key, the Kernel staged on the grid's
+        context, the status words and `hods_status`, a tensor for a torch cuda l -- with this as
+        its evaluating call: row i of the array [len(hods), l.size] is what
+        set_hod_object(<hods[i] as an object>) followed by correlation(l) returns on a fresh Halo.
+        Context.cell_epochs builds one chi-only node table per call and runs the epochs' spectrum
+        tables and Romberg integrals with an epoch axis, each row bit for bit what Context.cell
+        returns for that epoch."""
+        return ctx.cell_epochs(code, 0, n_hod, self.D_z, flat)
 
     def write(self, output_file_name):
         with open(output_file_name, "w") as f:

@@ -584,7 +584,7 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   int* deep = reinterpret_cast<int*>(ctx->d_cnodes + off_list);
   hipLaunchKernelGGL(k_cell_nodes, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256),
                      (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, L, ctx->proj.d_pd,
-                     ctx->proj.d_tab, D_z, LT, ctx->d_cnodes, deep);
+                     ctx->proj.d_tab, D_z, LT, ctx->d_cnodes, deep, 1, (size_t)0);
   // ... and the spectrum itself on a uniform ln k grid (no-wiggle spectra)
   double* pk_tab = ctx->with_bao ? nullptr : ctx->d_cnodes + 3 * n_nodes;
   // levels beyond kCellSplitLevel by k_cell_deep (CHOMP_TUNE_CELL_ONE_KERNEL: all in k_cell)
@@ -719,6 +719,98 @@ int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z, const double
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   return cell_impl(ctx, which, epoch, D_z, ell, n, out, mem);
+}
+
+// C_l of n_epoch epochs that share the projection set-up and D_z (an HOD design or chain at one
+// cosmology): the launches of cell_impl with an epoch axis behind ONE node table, the epochs worked
+// off in chunks of kWthEpochChunk (layout: chomp_proj_kernels.h, "The epoch axis" of C_l).
+int chomp_cell_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double D_z,
+                      const double* ell, size_t n, double* out, int mem) {
+  StageRange range_(ctx, "chomp:cell_epochs");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!ell || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: bad args");
+  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: n * n_epoch too large");
+  Staging st(ctx, mem, "cell_epochs");
+  if (st.rc) return st.rc;
+  if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "cell_epochs before kernel_setup");
+  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
+  if (ctx->precision != CHOMP_PREC_F64)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: fp64 only (no narrowed precision mode evaluates C_l)");
+  if (which & CHOMP_P_HALOFIT)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: HaloFit spectra are evaluated by chomp_cell");
+  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: extrapolated spectra are evaluated by chomp_cell");
+  if (ctx->with_bao)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: the wiggle transfer function is evaluated by chomp_cell");
+  int rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  if (!(D_z > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: D_z");
+  // (the sizes, the split and the route as in cell_impl)
+  const ProjLayout& L = ctx->proj.L;
+  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
+  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);   // (k_cell_deep_epochs)
+  constexpr int kDeepLds = 160 * 1024 - 4096;
+  if (shd > kDeepLds) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: halo_npoints too large for k_cell_deep");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  const double* din;
+  double* dout;
+  st.in(ell, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = st.place();
+  if (rc) return rc;
+  const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
+  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const size_t stride = cell_epoch_stride(n);
+  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
+                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
+  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
+  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, 3 * n_nodes + stride * chunk);
+  if (rc) return rc;
+  double* pk_tab = ctx->d_cnodes + 3 * n_nodes;            // (of the chunk's first epoch)
+  double* state = pk_tab + kPTabN + 1;
+  int* deep = reinterpret_cast<int*>(state + n * kRombergDump);
+  hipLaunchKernelGGL(k_cell_nodes, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256),
+                     (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, L, ctx->proj.d_pd,
+                     ctx->proj.d_tab, D_z, LT, ctx->d_cnodes, deep, (int)chunk, 2 * stride);
+  const int split = (ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL] > 0 || ctx->cfg.divmax <= kCellSplitLevel)
+                        ? ctx->cfg.divmax : kCellSplitLevel;
+  const unsigned gdeep = (unsigned)(n < 512 ? n : 512);
+  {
+    constexpr bool HF = false, BAO = false;
+    if (split < ctx->cfg.divmax) {
+      const int rcl = lds_opt_in(ctx, &k_cell_deep_epochs<HF, BAO>, kDeepLds);
+      if (rcl) return rcl;
+    }
+    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the slabs are reused in stream order)
+      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+      const int e0 = (int)(epoch0 + c0);
+      double* o = dout + c0 * n;
+      hipLaunchKernelGGL((k_cell_ptab_epochs<HF, BAO>), dim3((kPTabN + 256) / 256, E), dim3(256),
+                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, pk_tab,
+                         c0 ? deep : (int*)nullptr, stride);
+      if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
+        hipLaunchKernelGGL((k_cell4_epochs<HF, BAO>), dim3((unsigned)((n + 3) / 4), E), dim3(256), sh,
+                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                           ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n, o, ctx->d_cnodes, LT,
+                           pk_tab, split, deep, state, stride);
+      } else {
+        with_flag(split > LT, [&](auto BEYOND) {
+          hipLaunchKernelGGL((k_cell_epochs<HF, BAO, BEYOND>), dim3((unsigned)n, E), dim3(256), sh,
+                             ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                             ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, o, ctx->d_cnodes, LT, pk_tab,
+                             split, deep, state, stride);
+        });
+      }
+      if (split >= ctx->cfg.divmax) continue;
+      hipLaunchKernelGGL((k_cell_deep_epochs<HF, BAO>), dim3(gdeep, E), dim3(kCellDeepThreads), shd,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                         ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n, o, ctx->d_cnodes, LT,
+                         pk_tab, split, deep, state, stride);
+    }
+  }
+  return st.finish();
 }
 
 // w(theta) and C_l of one set-up in one call (configs[3], [4]: both observables of a survey).

@@ -1604,10 +1604,14 @@ constexpr int kCellTabLevel = 16;       // 3 x (2^16 + 1) doubles = 1.5 MiB (the
 __global__ __launch_bounds__(256) void k_cell_nodes(ProjLayout L, const ProjDev* __restrict__ pdg,
                                                     const double* __restrict__ ptab, double D_z,
                                                     int LT, double* __restrict__ nodes,
-                                                    int* __restrict__ deep) {
+                                                    int* __restrict__ deep, int n_lists,
+                                                    size_t list_stride) {
   extern __shared__ __align__(16) double sm[];
   __shared__ ProjDev pd;
-  if (blockIdx.x == 0 && threadIdx.x < 2) deep[threadIdx.x] = 0;   // k_cell's list: count, head
+  // k_cell's lists, one per epoch of the call (chomp_cell: one): count, head
+  if (blockIdx.x == 0)
+    for (int q = threadIdx.x; q < 2 * n_lists; q += blockDim.x)
+      deep[(q >> 1) * list_stride + (q & 1)] = 0;
   copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
   __syncthreads();
   ProjLds G;
@@ -1643,11 +1647,12 @@ __global__ __launch_bounds__(256) void k_cell_nodes(ProjLayout L, const ProjDev*
 // linear spectrum / the extrapolations, halo.py:300-320).  No-wiggle spectra only.
 // grid ceil((kPTabN + 1) / 256), block 256; dynamic LDS 12 (NK - 1) doubles.
 constexpr int kPTabN = 8192;
+// (the body of k_cell_ptab and k_cell_ptab_epochs; bx: the block's index along the table)
 template <bool HF, bool BAO>
-__global__ __launch_bounds__(256) void k_cell_ptab(chomp_config cfg, TabLayout HL,
-                                                   const Epoch* __restrict__ epochs, int e,
-                                                   const double* __restrict__ htab, int which,
-                                                   double* __restrict__ ptab_out) {
+__device__ __forceinline__ void cell_ptab_body(const chomp_config& cfg, const TabLayout& HL,
+                                               const Epoch* __restrict__ epochs, int e,
+                                               const double* __restrict__ htab, int which,
+                                               double* __restrict__ ptab_out, unsigned bx) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
@@ -1656,7 +1661,7 @@ __global__ __launch_bounds__(256) void k_cell_ptab(chomp_config cfg, TabLayout H
   P.stage(cfg, HL, &E, htab + (size_t)e * HL.stride, which, sm);
   __syncthreads();
   P.template finish_t<BAO>();
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = bx * blockDim.x + threadIdx.x;
   if (i > kPTabN) return;
   const double x0 = log(cfg.k_min), x1 = log(cfg.k_max);
   double x = x0 + (x1 - x0) * ((double)i / (double)kPTabN);
@@ -1665,6 +1670,48 @@ __global__ __launch_bounds__(256) void k_cell_ptab(chomp_config cfg, TabLayout H
   if (i == 0) { k = cfg.k_min; x = x0; }
   if (i == kPTabN) { k = cfg.k_max; x = x1; }
   ptab_out[i] = P.template at_ln<HF, BAO>(x, k);
+}
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256) void k_cell_ptab(chomp_config cfg, TabLayout HL,
+                                                   const Epoch* __restrict__ epochs, int e,
+                                                   const double* __restrict__ htab, int which,
+                                                   double* __restrict__ ptab_out) {
+  cell_ptab_body<HF, BAO>(cfg, HL, epochs, e, htab, which, ptab_out, blockIdx.x);
+}
+
+// The epoch axis (chomp_cell_epochs: one C_l per HOD of a design or chain).  The chi-only node
+// table of k_cell_nodes does not depend on the epoch and is built once per call; what an epoch
+// owns -- its spectrum table, the Romberg states of its multipoles and its deep list -- follows
+// the node table in the context's C_l work buffer, one slab per epoch of the chunk at a fixed
+// stride (cell_epoch_stride):
+//   3 (2^LT + 1) doubles   F_j, ln chi_j, chi_j                       (shared)
+//   then per epoch:  kPTabN + 1 doubles       P(k) of k_cell_ptab
+//                    n kRombergDump doubles   state[kRombergDump * multipole]
+//                    2 + n ints               deep list: count, head, multipoles
+// and the *_epochs kernels address the slab of epoch i at i * stride from the first one's table,
+// states and list.  A list holds multipoles of its own epoch only: a block of k_cell_deep_epochs
+// then stages one spectrum table for its lifetime, as k_cell_deep does.  A call works its epochs
+// off in chunks of kWthEpochChunk (CHOMP_TUNE_WTHETA_EPOCH_CHUNK: the knob of both batched
+// projections); a slab is 64 KiB + 276 n bytes, so the buffer stays small whatever the chunk.
+// k_cell_nodes empties the lists of the first chunk, k_cell_ptab_epochs those of a later one (the
+// slabs are reused in stream order).  Per (multipole, epoch) the arithmetic is the single-epoch
+// kernels': both sets of __global__s call the same bodies.
+inline size_t cell_epoch_stride(size_t n) {
+  return (size_t)kPTabN + 1 + n * kRombergDump + (n + 3) / 2 + 1;
+}
+// grid (as k_cell_ptab, E), block 256: row blockIdx.y stages epoch e0 + blockIdx.y and writes that
+// epoch's table.  deep (the first epoch's list; null: k_cell_nodes has emptied them): the row
+// empties its list.
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256) void k_cell_ptab_epochs(chomp_config cfg, TabLayout HL,
+                                                          const Epoch* __restrict__ epochs, int e0,
+                                                          const double* __restrict__ htab, int which,
+                                                          double* __restrict__ ptab_out,
+                                                          int* __restrict__ deep, size_t stride) {
+  if (deep != nullptr && blockIdx.x == 0 && threadIdx.x < 2)
+    deep[2 * stride * blockIdx.y + threadIdx.x] = 0;
+  cell_ptab_body<HF, BAO>(cfg, HL, epochs, e0 + (int)blockIdx.y, htab, which,
+                          ptab_out + stride * blockIdx.y, blockIdx.x);
 }
 
 // correlation.py:387-392 from the node table (levels <= LT), directly beyond
@@ -1739,18 +1786,18 @@ struct CellTabIntegrand {
 //  reads of tables another kernel wrote -- a microsecond a piece on a CU whose L2 has not seen
 //  them -- and set the launch's duration: 65 us measured against 9 us for a level-8 block.)
 constexpr int kCellSplitLevel = 11;
+// (the body of k_cell and k_cell_epochs: multipole il of ell into out[il])
 template <bool HF, bool BAO, bool DIRECT>
-// (three blocks per CU for the lean instance: 168 registers, one fewer than it would take)
-__global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell(chomp_config cfg, TabLayout HL, ProjLayout L,
-                                              const Epoch* __restrict__ epochs, int e,
-                                              const double* __restrict__ htab, int which,
-                                              const ProjDev* __restrict__ pdg,
-                                              const double* __restrict__ ptab, double D_z,
-                                              const double* __restrict__ ell,
-                                              double* __restrict__ out,
-                                              const double* __restrict__ nodes, int LT,
-                                              const double* __restrict__ pk_tab, int split,
-                                              int* __restrict__ deep, double* __restrict__ state) {
+__device__ __forceinline__ void cell_body(const chomp_config& cfg, const TabLayout& HL,
+                                          const ProjLayout& L, const Epoch* __restrict__ epochs, int e,
+                                          const double* __restrict__ htab, int which,
+                                          const ProjDev* __restrict__ pdg,
+                                          const double* __restrict__ ptab, double D_z,
+                                          const double* __restrict__ ell, double* __restrict__ out,
+                                          const double* __restrict__ nodes, int LT,
+                                          const double* __restrict__ pk_tab, int split,
+                                          int* __restrict__ deep, double* __restrict__ state,
+                                          unsigned il) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   __shared__ ProjDev pd;
@@ -1766,18 +1813,49 @@ __global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell(chomp_config cfg, 
   G.bess = nullptr;
   __syncthreads();
   P.template finish_t<BAO>();
-  const double l = ell[blockIdx.x];
+  const double l = ell[il];
   const double px0 = log(cfg.k_min), pdx = (log(cfg.k_max) - px0) / (double)kPTabN;
   CellTabIntegrand<HF, BAO, DIRECT> f{&P, nodes, (1L << LT) + 1, LT, l, log(l), pk_tab, px0, pdx,
                                       1.0 / pdx, {&P, &G, l, 1.0 / (D_z * D_z)}};
   const bool hand_over = split < cfg.divmax;
   const RombergOut<1> r = romberg_group<4, 1, CellTabIntegrand<HF, BAO, DIRECT>, 4>(
       f, pd.chi_min, pd.chi_max, cfg.global_precision, cfg.corr_precision, split, red,
-      hand_over ? state + (size_t)blockIdx.x * kRombergDump : nullptr);
+      hand_over ? state + (size_t)il * kRombergDump : nullptr);
   if (threadIdx.x == 0) {
-    out[blockIdx.x] = r.value[0];
-    if (hand_over && !r.converged[0]) deep[2 + atomicAdd(&deep[0], 1)] = (int)blockIdx.x;
+    out[il] = r.value[0];
+    if (hand_over && !r.converged[0]) deep[2 + atomicAdd(&deep[0], 1)] = (int)il;
   }
+}
+template <bool HF, bool BAO, bool DIRECT>
+// (three blocks per CU for the lean instance: 168 registers, one fewer than it would take)
+__global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell(chomp_config cfg, TabLayout HL, ProjLayout L,
+                                              const Epoch* __restrict__ epochs, int e,
+                                              const double* __restrict__ htab, int which,
+                                              const ProjDev* __restrict__ pdg,
+                                              const double* __restrict__ ptab, double D_z,
+                                              const double* __restrict__ ell,
+                                              double* __restrict__ out,
+                                              const double* __restrict__ nodes, int LT,
+                                              const double* __restrict__ pk_tab, int split,
+                                              int* __restrict__ deep, double* __restrict__ state) {
+  cell_body<HF, BAO, DIRECT>(cfg, HL, L, epochs, e, htab, which, pdg, ptab, D_z, ell, out, nodes, LT,
+                             pk_tab, split, deep, state, blockIdx.x);
+}
+// ... with an epoch axis (chomp_cell_epochs): grid (n_ell, E), block 256; row blockIdx.y integrates
+// epoch e0 + blockIdx.y from its own spectrum table into out[blockIdx.y * n_ell + blockIdx.x], with
+// its own states and list (pk_tab, deep, state: the first epoch's, `stride` doubles to the next).
+template <bool HF, bool BAO, bool DIRECT>
+__global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell_epochs(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pdg,
+    const double* __restrict__ ptab, double D_z, const double* __restrict__ ell,
+    double* __restrict__ out, const double* __restrict__ nodes, int LT,
+    const double* __restrict__ pk_tab, int split, int* __restrict__ deep,
+    double* __restrict__ state, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  cell_body<HF, BAO, DIRECT>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pdg, ptab, D_z, ell,
+                             out + (size_t)blockIdx.y * gridDim.x, nodes, LT, pk_tab + off, split,
+                             deep + 2 * off, state + off, blockIdx.x);
 }
 
 // k_cell4: the same integrals, FOUR multipoles to a block -- one per wavefront up to level
@@ -1791,17 +1869,19 @@ __global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell(chomp_config cfg, 
 // deep ones are the highest l: one to a block).  grid ceil(n_ell / 4), block 256; the lean
 // instance only (split <= LT, split >= 6).
 constexpr int kCell4Level = 8;     // (7: 27.6, 8: 24.3, 9: 25.2, 10: 28.7 us per configs[3] launch)
+// (the body of k_cell4 and k_cell4_epochs; bx: the block's index along the multipoles)
 template <bool HF, bool BAO>
-__global__ __launch_bounds__(256, 3) void k_cell4(chomp_config cfg, TabLayout HL, ProjLayout L,
-                                              const Epoch* __restrict__ epochs, int e,
-                                              const double* __restrict__ htab, int which,
-                                              const ProjDev* __restrict__ pdg,
-                                              const double* __restrict__ ptab, double D_z,
-                                              const double* __restrict__ ell, int n_ell,
-                                              double* __restrict__ out,
-                                              const double* __restrict__ nodes, int LT,
-                                              const double* __restrict__ pk_tab, int split,
-                                              int* __restrict__ deep, double* __restrict__ state) {
+__device__ __forceinline__ void cell4_body(const chomp_config& cfg, const TabLayout& HL,
+                                           const ProjLayout& L, const Epoch* __restrict__ epochs, int e,
+                                           const double* __restrict__ htab, int which,
+                                           const ProjDev* __restrict__ pdg,
+                                           const double* __restrict__ ptab, double D_z,
+                                           const double* __restrict__ ell, int n_ell,
+                                           double* __restrict__ out,
+                                           const double* __restrict__ nodes, int LT,
+                                           const double* __restrict__ pk_tab, int split,
+                                           int* __restrict__ deep, double* __restrict__ state,
+                                           unsigned bx) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   __shared__ ProjDev pd;
@@ -1821,7 +1901,7 @@ __global__ __launch_bounds__(256, 3) void k_cell4(chomp_config cfg, TabLayout HL
   __syncthreads();
   P.template finish_t<BAO>();
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-  const int il = (int)blockIdx.x + (int)gridDim.x * wave;
+  const int il = (int)bx + (int)gridDim.x * wave;
   const bool have = il < n_ell;
   const double px0 = log(cfg.k_min), pdx = (log(cfg.k_max) - px0) / (double)kPTabN;
   const double a = pd.chi_min, b = pd.chi_max;
@@ -1845,7 +1925,7 @@ __global__ __launch_bounds__(256, 3) void k_cell4(chomp_config cfg, TabLayout HL
   __syncthreads();
   for (int w = 0; w < 4; ++w) {
     if (!co_need[w]) continue;                   // (block-uniform)
-    const int ilw = (int)blockIdx.x + (int)gridDim.x * w;
+    const int ilw = (int)bx + (int)gridDim.x * w;
     const double l = ell[ilw];
     CellTabIntegrand<HF, BAO, false> f{&P, nodes, (1L << LT) + 1, LT, l, log(l), pk_tab, px0, pdx,
                                        1.0 / pdx, {&P, &G, l, 1.0 / (D_z * D_z)}};
@@ -1890,6 +1970,35 @@ __global__ __launch_bounds__(256, 3) void k_cell4(chomp_config cfg, TabLayout HL
     }
   }
 }
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256, 3) void k_cell4(chomp_config cfg, TabLayout HL, ProjLayout L,
+                                              const Epoch* __restrict__ epochs, int e,
+                                              const double* __restrict__ htab, int which,
+                                              const ProjDev* __restrict__ pdg,
+                                              const double* __restrict__ ptab, double D_z,
+                                              const double* __restrict__ ell, int n_ell,
+                                              double* __restrict__ out,
+                                              const double* __restrict__ nodes, int LT,
+                                              const double* __restrict__ pk_tab, int split,
+                                              int* __restrict__ deep, double* __restrict__ state) {
+  cell4_body<HF, BAO>(cfg, HL, L, epochs, e, htab, which, pdg, ptab, D_z, ell, n_ell, out, nodes, LT,
+                      pk_tab, split, deep, state, blockIdx.x);
+}
+// ... with an epoch axis: grid (ceil(n_ell / 4), E), block 256; row blockIdx.y as in k_cell_epochs
+// (wavefront w of block (b, y) keeps multipole b + gridDim.x w of epoch e0 + y).
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256, 3) void k_cell4_epochs(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pdg,
+    const double* __restrict__ ptab, double D_z, const double* __restrict__ ell, int n_ell,
+    double* __restrict__ out, const double* __restrict__ nodes, int LT,
+    const double* __restrict__ pk_tab, int split, int* __restrict__ deep,
+    double* __restrict__ state, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  cell4_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pdg, ptab, D_z, ell, n_ell,
+                      out + (size_t)blockIdx.y * n_ell, nodes, LT, pk_tab + off, split, deep + 2 * off,
+                      state + off, blockIdx.x);
+}
 
 // One node by the general route (inlined: a call would put a stack -- scratch memory -- behind
 // every launch of the kernel, used or not).
@@ -1907,14 +2016,15 @@ __device__ __forceinline__ double cell_node_general(const CellTabIntegrand<HF, B
 // nodes are spread over eight wavefronts, four to a thread in flight.
 // dynamic LDS: 12 (NK - 1) + ProjLds::doubles(L) + kPTabN + 1 doubles.
 constexpr int kCellDeepThreads = 512;
+// (the body of k_cell_deep and k_cell_deep_epochs; bx: the block's index among its list's blocks)
 template <bool HF, bool BAO>
-__global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep(
-    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e,
-    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pdg,
-    const double* __restrict__ ptab, double D_z, const double* __restrict__ ell,
-    double* __restrict__ out, const double* __restrict__ nodes, int LT,
+__device__ __forceinline__ void cell_deep_body(
+    const chomp_config& cfg, const TabLayout& HL, const ProjLayout& L,
+    const Epoch* __restrict__ epochs, int e, const double* __restrict__ htab, int which,
+    const ProjDev* __restrict__ pdg, const double* __restrict__ ptab, double D_z,
+    const double* __restrict__ ell, double* __restrict__ out, const double* __restrict__ nodes, int LT,
     const double* __restrict__ pk_tab, int split, int* __restrict__ deep,
-    const double* __restrict__ state) {
+    const double* __restrict__ state, unsigned bx) {
   constexpr int NW = kCellDeepThreads / 64, NT = kCellDeepThreads, U = 4;
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
@@ -1922,7 +2032,7 @@ __global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep(
   __shared__ double red[2 * NW];
   __shared__ int item_sh;
   const int count = deep[0];
-  if ((int)blockIdx.x >= count) return;                  // (block-uniform)
+  if ((int)bx >= count) return;                         // (block-uniform)
   copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
                kEpochDoubles);
   copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
@@ -1981,6 +2091,34 @@ __global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep(
     }
     if (threadIdx.x == 0) out[il] = R.value;
   }
+}
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pdg,
+    const double* __restrict__ ptab, double D_z, const double* __restrict__ ell,
+    double* __restrict__ out, const double* __restrict__ nodes, int LT,
+    const double* __restrict__ pk_tab, int split, int* __restrict__ deep,
+    const double* __restrict__ state) {
+  cell_deep_body<HF, BAO>(cfg, HL, L, epochs, e, htab, which, pdg, ptab, D_z, ell, out, nodes, LT,
+                          pk_tab, split, deep, state, blockIdx.x);
+}
+// ... with an epoch axis: grid (min(n_ell, 512), E), block 512; the blocks of row blockIdx.y draw
+// from the list of epoch e0 + blockIdx.y alone, so what a block stages -- the epoch's splines, the
+// projection tables, the epoch's spectrum table -- holds for every item it draws; a block beyond
+// its list's count leaves at once.
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep_epochs(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pdg,
+    const double* __restrict__ ptab, double D_z, const double* __restrict__ ell, int n_ell,
+    double* __restrict__ out, const double* __restrict__ nodes, int LT,
+    const double* __restrict__ pk_tab, int split, int* __restrict__ deep,
+    const double* __restrict__ state, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  cell_deep_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pdg, ptab, D_z, ell,
+                          out + (size_t)blockIdx.y * n_ell, nodes, LT, pk_tab + off, split,
+                          deep + 2 * off, state + off, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------

@@ -8,7 +8,8 @@ set_cosmology / set_halo / set_hod and the requested method.  That generic loop 
 its spectra, the design is the native batch axis of the device library: every design
 point becomes one epoch of a HaloGrid and all of them are built and evaluated by the same
 kernel launches.  A design over HOD parameters of
-Correlation.correlation is batched the same way, through Correlation.correlation_hods.
+Correlation.correlation or CorrelationFourier.correlation is batched the same way, through the
+object's correlation_hods.
 """
 import copy
 import warnings
@@ -136,18 +137,21 @@ class SimulationDesign(object):
 
     def _hods_design_scope(self):
         """ChompScopeError unless this design is one Correlation.correlation_hods serves: exactly a
-        Correlation, its `correlation` over an independent variable, only HOD parameters varying
+        Correlation or a CorrelationFourier (any other subclass may evaluate something else under
+        the same name), its `correlation` over an independent variable (theta; l of a
+        CorrelationFourier), only HOD parameters varying
         (a cosmology point needs its own projection set-up, and a context holds one; halo
         parameters keep the loop as in the Halo route), and the object within correlation_hods'
         own scope.  No device work."""
         obj = self._input_object
         why = None
-        if type(obj) is not correlation_mod.Correlation:
-            why = "the object is a %s, not exactly a correlation.Correlation" % type(obj).__name__
+        if type(obj) not in (correlation_mod.Correlation, correlation_mod.CorrelationFourier):
+            why = ("the object is a %s, not exactly a correlation.Correlation or "
+                   "correlation.CorrelationFourier" % type(obj).__name__)
         elif self._method != "correlation":
             why = "the method is %r, not 'correlation'" % (self._method,)
         elif self._ind_var is None:
-            why = "no independent_var (theta) is given"
+            why = "no independent_var (theta, or l of a CorrelationFourier) is given"
         elif not self._vary_hod:
             why = "no HOD parameter varies"
         elif self._vary_cosmology:
@@ -222,7 +226,8 @@ class SimulationDesign(object):
                               category, stacklevel=stacklevel)
 
     def _run_batched_hods(self):
-        """Every design point = one HOD of one Correlation.correlation_hods call."""
+        """Every design point = one HOD of one correlation_hods call (w(theta) of a Correlation,
+        C_l of a CorrelationFourier: the independent variable is theta or l)."""
         real, rec = self._input_object, _Recorder()
         self._hods_design_scope()             # (ChompScopeError before anything is recorded)
         hods = []
@@ -246,8 +251,8 @@ class SimulationDesign(object):
         """simulation_design.py:140-155.  Returns a DataFrame with one column per design
         point holding the flattened output of the method.  batched=None picks the
         one-launch path when the object / method allow it: a Halo and one of its spectra
-        (cosmology and HOD may vary), or a Correlation, its `correlation` and a design over HOD
-        parameters only (Correlation.correlation_hods, with its scope).  A Correlation design
+        (cosmology and HOD may vary), or a Correlation or CorrelationFourier, its `correlation` and
+        a design over HOD parameters only (the object's correlation_hods, with its scope).  A Correlation design
         that varies cosmology or halo parameters keeps the point-by-point loop: a cosmology
         point needs its own projection set-up, and a device context holds one.  batched=False
         forces the loop; batched=True on a Correlation raises ChompScopeError when the object

@@ -405,7 +405,9 @@ int chomp_status_wait(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out);
  *   CHOMP_TUNE_WTHETA_EPOCH_CHUNK  epochs that chomp_wtheta_epochs evaluates per round of
  *                            launches (default 16, at most 256; its work buffer holds one chunk,
  *                            about 12 MiB per epoch at divmax = 20): a small value lets a test
- *                            cross the seam between two chunks with a handful of epochs
+ *                            cross the seam between two chunks with a handful of epochs.  It serves
+ *                            both batched projections: chomp_cell_epochs takes its chunk from it
+ *                            too (64 KiB + 276 bytes per multipole for every epoch of a chunk)
  *   CHOMP_TUNE_CELL_ONE_KERNEL 1: C_l with every Romberg level in the per-multipole kernel (the
  *                            checker of the hand-over to k_cell_deep)
  *   CHOMP_TUNE_ROCTX         1: roctx ranges around the stages on the host timeline (one per
@@ -916,6 +918,19 @@ int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, si
 /* CorrelationFourier.correlation(l) (correlation.py:360-392): Limber C_l. */
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z,
                const double* ell, size_t n, double* out, int mem);
+/* CorrelationFourier.correlation(l) for epochs epoch0 .. epoch0 + n_epoch - 1 of one context that
+ * share the projection set-up and D_z: out[e * n + i] = what chomp_cell(ctx, which, epoch0 + e,
+ * D_z, ell, n, ...) returns at i, bit for bit.  The batch axis of an HOD design or chain over C_l
+ * (the loop of set_hod + correlation, as chomp_wtheta_epochs for w(theta)): the chi-only node
+ * table is built once per call, and the spectrum table, the per-multipole Romberg and the deep
+ * levels run once per chunk of 16 epochs (CHOMP_TUNE_WTHETA_EPOCH_CHUNK) instead of once per
+ * epoch, every epoch taking the route chomp_cell would take.  fp64 only; CHOMP_ERR_SCOPE for the
+ * narrowed precision modes, for HaloFit spectra (CHOMP_P_HALOFIT), for spectra extrapolated
+ * beyond the halo's k range (CHOMP_P_EXTRAPOLATE on a halo-model spectrum) and for a context with
+ * the wiggle transfer function (chomp_set_transfer): chomp_cell serves those, one epoch at a
+ * time. */
+int chomp_cell_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double D_z,
+                      const double* ell, size_t n, double* out, int mem);
 
 /* Both observables of one survey set-up -- Correlation.correlation(theta) (correlation.py:
  * 242-275) and CorrelationFourier.correlation(l) (correlation.py:360-392) on the same kernel,
