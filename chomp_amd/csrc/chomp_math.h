@@ -438,7 +438,7 @@ CHOMP_HD double spline_eval_uniform(double x0, double dx, const double* c, int n
 // first two derivatives at one point: what HaloFit needs for n_eff and C
 // (halo.py:1289-1294).  Knots as FITPACK's fpcurf chooses them for s = 0, odd k:
 // 6-fold end knots and the data sites x[3] .. x[n-4] inside.
-// work: (n + 6) + 11 n + n doubles.  n >= 7.
+// work: (n + 6) + 11 n + n doubles.  n >= 6 (at 6 there is no interior knot).
 // ---------------------------------------------------------------------------
 // B-spline basis of degree p (<= 5) at x in knot span m: N[r] = B_{m-p+r,p}(x).
 CHOMP_HD void bspline_basis(const double* t, int m, int p, double x, double* N) {

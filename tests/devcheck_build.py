@@ -1,7 +1,9 @@
 """Builds and loads the TEST-ONLY device harnesses under tests/devcheck, the device counterparts
 of tests/hostcheck: libdevcheck.so (devcheck.hip: the fp64 primitives of chomp_math.h and the
-wavefront Romberg of chomp_romberg.h) and libdevphys.so (devphys.hip: the halo-model physics of
-chomp_math.h, through the product's whole header chain from chomp_cov_kernels.h down).  Each harness is
+wavefront Romberg of chomp_romberg.h), libdevphys.so (devphys.hip: the halo-model physics of
+chomp_math.h, through the product's whole header chain from chomp_cov_kernels.h down) and
+libdevproj.so (devproj.hip: the moment route of w(theta), the bicubic tables and HaloFit's
+quintic derivatives of chomp_proj_kernels.h / chomp_cov_kernels.h).  Each harness is
 compiled with the product's compiler flags (imported from chomp_amd._lib, never copied) and
 rebuilt only when the content of what IT is compiled from changes, as _lib.py does for the
 product library: its own source, .so and content hash, the hash over every product header it
@@ -48,7 +50,8 @@ class Harness:
         return included_headers(self.src)
 
 
-HARNESSES = {"devcheck": Harness("devcheck"), "devphys": Harness("devphys")}
+HARNESSES = {"devcheck": Harness("devcheck"), "devphys": Harness("devphys"),
+             "devproj": Harness("devproj")}
 # the first harness under its earlier names
 SRC = HARNESSES["devcheck"].src
 SO = HARNESSES["devcheck"].so
@@ -94,7 +97,20 @@ PHYS_ENTRY_POINTS = {
     "dp_e0_de": [_v, _p, _p, _i, _p, _i, _p, _p],
     "dp_linspace": [_p, _p, _p, _p, _i, _d, _d, _p],
 }
-ALL_ENTRY_POINTS = {"devcheck": ENTRY_POINTS, "devphys": PHYS_ENTRY_POINTS}
+# ... and for the third (devproj.hip)
+PROJ_ENTRY_POINTS = {
+    "dj_wth_items": [], "dj_wth_parts": [],
+    "dj_wth_sizes": [_i, _i, _i, _p],
+    "dj_moments": [_p, _i, _i, _d, _d, _i, _p],
+    "dj_wtheta": [_p, _i, _i, _d, _d, _i, _i, _p, _d, _d, _p, _i, _ip, _i, _d, _d, _p, _p, _p],
+    "dj_kernel_eval": [_i, _p, _d, _d, _p, _i, _p],
+    "dj_ssc": [_i, _p, _p, _d, _d, _p, _p, _i, _p, _i, _p, _i, _p, _p, _p],
+    "dj_ng": [_i, _p, _p, _d, _d, _p, _p, _i, _p, _p, _p],
+    "dj_quintic_grid": [_i, _p],
+    "dj_quintic": [_p, _i, _p, _i, _p],
+}
+ALL_ENTRY_POINTS = {"devcheck": ENTRY_POINTS, "devphys": PHYS_ENTRY_POINTS,
+                    "devproj": PROJ_ENTRY_POINTS}
 # dc_quad shapes
 SHAPE = {"group1": 0, "group2": 1, "group4": 2, "group8": 3, "group16": 4,
          "group1_nf2": 5, "group4_nf2": 6, "group4_unroll4": 7, "group4_fast4": 8,
@@ -143,7 +159,8 @@ def build(force=False, harness="devcheck"):
     return H.so
 
 
-VOID = {"devcheck": ("dc_fma_k_constants", "dc_gl16"), "devphys": ("dp_epoch_offsets",)}
+VOID = {"devcheck": ("dc_fma_k_constants", "dc_gl16"), "devphys": ("dp_epoch_offsets",),
+        "devproj": ("dj_quintic_grid",)}
 
 
 def load(harness="devcheck"):

@@ -16,8 +16,6 @@ asserts for the host build; [derived] a first-order propagated bound times two; 
 twice the maximum measured against mpmath, rounded up to a power of two (the measured maxima
 are in DESIGN.md section 3).  Each test prints what it measured before it asserts."""
 import ctypes
-import os
-import subprocess
 
 import mpmath
 import numpy
@@ -25,7 +23,7 @@ import pytest
 
 import devcheck_build as dcb
 from devcheck_build import call, ptr
-from conftest import ROOT
+import hostcheck_build
 from params import c_dict
 from oracle import chomp_oracle as o
 
@@ -820,13 +818,7 @@ def mp_y_addends(z, con, mass_k_inv):
 
 
 def _hostcheck():
-    so = os.path.join(ROOT, "tests", "hostcheck", "libhostcheck.so")
-    src = os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cpp")
-    hdr = os.path.join(ROOT, "chomp_amd", "csrc", "chomp_math.h")
-    if (not os.path.exists(so) or
-            os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, src])
-    return ctypes.CDLL(so)
+    return hostcheck_build.load()
 
 
 def test_y_nfw(dp):

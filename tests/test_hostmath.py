@@ -3,18 +3,16 @@
 They check the device special functions / splines / integrand pieces against
 SciPy and the oracle; the kernels themselves are tested with -m gpu."""
 import ctypes
-import os
-import subprocess
 
 import numpy
 import pytest
 from scipy import special
 from scipy.interpolate import InterpolatedUnivariateSpline
 
-from conftest import ROOT, rel_err
+import hostcheck_build
+from conftest import rel_err
 from oracle import chomp_oracle as o
 
-HC = os.path.join(ROOT, "tests", "hostcheck")
 dp = ctypes.POINTER(ctypes.c_double)
 
 
@@ -24,14 +22,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def hc():
-    so = os.path.join(HC, "libhostcheck.so")
-    src = os.path.join(HC, "hostcheck.cpp")
-    hdr = os.path.join(ROOT, "chomp_amd", "csrc", "chomp_math.h")
-    if (not os.path.exists(so) or
-            os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared",
-                               "-o", so, src])
-    return ctypes.CDLL(so)
+    return hostcheck_build.load()
 
 
 def test_sici(hc):
