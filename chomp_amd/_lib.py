@@ -56,6 +56,7 @@ KI = {name: i for i, name in enumerate([
     "z_bar", "chi_min", "chi_max", "z_min", "z_max", "D_zbar", "norm_a", "norm_b",
     "wa_chi_min", "wa_chi_max", "wb_chi_min", "wb_chi_max", "j_limit"])}
 KI_COUNT = 13
+KERNEL_SETS_MAX = 1024      # CHOMP_KERNEL_SETS_MAX: the sets of one chomp_kernel_setup_sets
 ME = {"chi_of_z": 0, "z_of_chi": 1, "growth_of_z": 2}
 KTAB = {"ln_ktheta": 0, "kernel": 1, "wa_chi": 2, "wa": 3, "wb_chi": 4, "wb": 5,
         "me_z": 6, "me_chi": 7, "me_growth": 8, "levels": 9}
@@ -126,6 +127,8 @@ EXPORTS = [
     "chomp_kernel_setup", "chomp_kernel_info", "chomp_kernel_table",
     "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_wtheta_epochs",
     "chomp_cell", "chomp_cell_epochs",
+    "chomp_kernel_setup_sets", "chomp_kernel_info_sets", "chomp_kernel_table_set",
+    "chomp_wtheta_sets",
     "chomp_set_precision", "chomp_xi3d", "chomp_spline_eval", "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
     "chomp_covariance_table", "chomp_covariance_gaussian",
@@ -413,6 +416,11 @@ def lib():
         L.chomp_window_eval.argtypes = [vp, i, vp, sz, vp, i]
         L.chomp_wtheta.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, i]
         L.chomp_wtheta_epochs.argtypes = [vp, i, sz, sz, d, d, d, vp, sz, vp, i]
+        L.chomp_kernel_setup_sets.argtypes = [vp, sz, ctypes.POINTER(Cosmo), d, d, d, d,
+                                              ctypes.POINTER(Window), ctypes.POINTER(Window), i]
+        L.chomp_kernel_info_sets.argtypes = [vp, c_double_p]
+        L.chomp_kernel_table_set.argtypes = [vp, sz, i, c_double_p, sz]
+        L.chomp_wtheta_sets.argtypes = [vp, i, sz, sz, d, d, vp, vp, sz, vp, i]
         L.chomp_cell.argtypes = [vp, i, sz, d, vp, sz, vp, i]
         L.chomp_cell_epochs.argtypes = [vp, i, sz, sz, d, vp, sz, vp, i]
         L.chomp_wtheta_cell.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, vp, sz, vp, i]
@@ -1075,6 +1083,54 @@ class Context(object):
         self._check(self._L.chomp_kernel_table(self._h, KTAB[name],
                                                out.ctypes.data_as(c_double_p), n))
         return out
+
+    # -- the cosmology axis of the projection set-up --------------------------
+    def kernel_setup_sets(self, cosmo_dicts, me_z_min, me_z_max, ktheta_min, ktheta_max,
+                          wa, wb, bessel_order):
+        """One projection set-up per cosmology (chomp_kernel_setup_sets): cosmo_dicts a list of
+        dictionaries, a float64 array [n, 10] or the packed ctypes array (pack_cosmo).  The sets
+        live beside the single set-up of kernel_setup, which stays as it is.  At most
+        KERNEL_SETS_MAX sets per call (ValueError); ChompScopeError for a w0-wa cosmology or a
+        tabulated redshift distribution."""
+        arr = (cosmo_dicts if isinstance(cosmo_dicts, ctypes.Array)
+               else self.pack_cosmo(cosmo_dicts, len(cosmo_dicts)))
+        self._check(self._L.chomp_kernel_setup_sets(
+            self._h, len(arr), arr, me_z_min, me_z_max, ktheta_min, ktheta_max,
+            ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)))
+        self._n_sets = len(arr)
+
+    def kernel_info_sets(self):
+        """kernel_info() of every set, as a dictionary of arrays [n_set]; one synchronising
+        read-back."""
+        n = getattr(self, "_n_sets", 0)
+        out = numpy.empty((max(n, 1), KI_COUNT))
+        self._check(self._L.chomp_kernel_info_sets(self._h, out.ctypes.data_as(c_double_p)))
+        return {name: out[:n, i].copy() for name, i in KI.items()}
+
+    def kernel_table_set(self, set_index, name):
+        """kernel_table(name) of one set."""
+        cfg = self.config
+        n = {"ln_ktheta": cfg.kernel_npoints, "kernel": cfg.kernel_npoints,
+             "levels": cfg.kernel_npoints, "me_z": cfg.cosmo_npoints,
+             "me_chi": cfg.cosmo_npoints, "me_growth": cfg.cosmo_npoints}.get(
+                 name, cfg.window_npoints)
+        out = numpy.empty(n)
+        self._check(self._L.chomp_kernel_table_set(self._h, int(set_index), KTAB[name],
+                                                   out.ctypes.data_as(c_double_p), n))
+        return out
+
+    def wtheta_sets(self, which, epoch0, n_epoch, k_min, k_max, D_z, theta):
+        """w(theta) of the epochs epoch0 .. epoch0 + n_epoch - 1, epoch epoch0 + e against
+        projection set e with growth D_z[e] (chomp_wtheta_sets): [n_epoch, theta.size], row e what
+        kernel_setup(<cosmology e>) + wtheta(which, epoch0 + e, ..., D_z[e], theta) returns, bit
+        for bit.  D_z is a host array; theta a host array or a torch cuda tensor, as in
+        wtheta_epochs."""
+        D = numpy.ascontiguousarray(D_z, dtype=numpy.float64).ravel()
+        if D.size != int(n_epoch):
+            raise ValueError("wtheta_sets: D_z must hold one growth factor per epoch")
+        return self._run(self._L.chomp_wtheta_sets, [theta], lambda mem, new, th: (
+            int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), _host_address(D), th,
+            _numel(th), new((int(n_epoch), _numel(th))), mem))[0]
 
     def _run(self, fn, xs, body):
         """Call the array entry point fn on host or device arrays; returns the list of outputs.

@@ -137,15 +137,16 @@ class Correlation(object):
     # -- the batch over HODs ---------------------------------------------------
     _hods_export = "chomp_wtheta_epochs"      # (the C entry point behind correlation_hods)
 
-    def _hods_scope(self, hods=None):
+    def _hods_scope(self, hods=None, who="correlation_hods",
+                    loop="set_hod / set_hod_object + correlation"):
         """ChompScopeError unless correlation_hods serves this object (and `hods`); no device
-        work.  Returns the HODs as objects."""
+        work.  Returns the HODs as objects.  who / loop: the batch that asks and the loop it
+        names instead (correlation_cosmologies shares this scope)."""
         from . import hod as hod_mod
         h = self.halo
 
         def refuse(why):
-            raise _lib.ChompScopeError("correlation_hods: %s; use the loop set_hod / "
-                                       "set_hod_object + correlation" % why)
+            raise _lib.ChompScopeError("%s: %s; use the loop %s" % (who, why, loop))
         if type(h) is not halo_mod.Halo:
             refuse("the halo is a %s, the batch takes a plain halo.Halo" % type(h).__name__)
         if getattr(h, "_general_profile", False):
@@ -241,6 +242,121 @@ class Correlation(object):
         grid's epochs 0 .. n_hod - 1 on its context."""
         return ctx.wtheta_epochs(code, 0, n_hod, self._k_lim[0], self._k_lim[1], self.D_z, flat)
 
+    # -- the batch over cosmologies --------------------------------------------
+    def _cosmologies_scope(self, cosmo_dicts, hods=None):
+        """ChompScopeError unless correlation_cosmologies serves this object, these cosmologies
+        and `hods`; no device work.  Returns the HODs as objects (None without `hods`)."""
+        from . import cosmology
+        from . import kernel as kernel_mod
+        who, loop = "correlation_cosmologies", "set_cosmology (+ set_hod_object) + correlation"
+        objs = self._hods_scope(hods, who=who, loop=loop)
+
+        def refuse(why):
+            raise _lib.ChompScopeError("%s: %s; use the loop %s" % (who, why, loop))
+        if self.kernel._z_bar_override is not None:
+            refuse("the kernel has an assigned z_bar (Correlation.set_redshift); the batch finds "
+                   "z_bar per cosmology, as set_cosmology does")
+        for name in ("window_function_a", "window_function_b"):
+            dist = getattr(getattr(self.kernel, name, None), "_redshift_dist", None)
+            if isinstance(dist, kernel_mod.dNdzInterpolation):
+                refuse("%s has a tabulated redshift distribution (%s)" % (name, type(dist).__name__))
+        for i, c in enumerate(cosmo_dicts):
+            if cosmology.has_dark_energy(c):
+                refuse("cosmology %d has w0-wa dark energy" % i)
+        if hods is not None and len(objs) != len(cosmo_dicts):
+            raise ValueError("correlation_cosmologies: %d hods for %d cosmologies"
+                             % (len(objs), len(cosmo_dicts)))
+        return objs if hods is not None else None
+
+    def correlation_cosmologies(self, theta_rad, cosmo_dicts, hods=None, with_status=False):
+        """w(theta) for many cosmologies in one call: the array [len(cosmo_dicts), theta.size]
+        whose row i is what set_cosmology(cosmo_dicts[i]) followed by correlation(theta_rad)
+        returns on a fresh Correlation of the same kernel, halo parameters and HOD -- the loop
+        of a cosmology design (correlation.py:161-171 and kernel.py:657-676 per point of
+        simulation_design.py:116-155) as one batch.  With `hods` (one per point: dictionaries,
+        hod.HODZheng or hod.HODMandelbaum, as in correlation_hods) set_hod_object(hods[i]) is
+        applied as well.  This object's own kernel, halo, cosmology and HOD are not touched.
+
+        The work: one projection set-up per point on the kept grid's context
+        (Kernel._setup_sets_on), ONE read-back of every point's z_bar and D(z_bar) -- the only
+        synchronisation besides the result and the status words --, one grid.HaloGrid epoch per
+        point at z = z_bar[i] with cosmo_dicts[i], and Context.wtheta_sets.  As in the loop
+        (set_cosmology moves the halo to the new z_bar, whatever keep_halo_z_bar said at
+        construction) the batch ALWAYS evaluates the halo at z_bar[i].  The grid is kept, keyed by
+        the number of points, the halo dictionary, the mass function and the defaults a context
+        snapshots: a later call replaces cosmologies, redshifts and HODs only.  More points than
+        _lib.KERNEL_SETS_MAX are worked off in blocks of that size.
+
+        The status word of every point is read with the result, raised as a warning naming
+        "cosmology i", kept in `self.cosmologies_status` (uint32) beside
+        `self.cosmologies_z_bar` (the redshifts found) and returned as the second element with
+        with_status=True.  A torch cuda theta returns a tensor.
+
+        ChompScopeError (before any launch): everything correlation_hods refuses, a kernel with
+        an assigned z_bar (after set_redshift), a dNdzInterpolation / dNdChiGaussian window, a
+        w0-wa cosmology among the points.  C_l (CorrelationFourier) is not batched over
+        cosmologies yet."""
+        import warnings
+        from . import defaults
+        from . import grid
+        cosmo_dicts = [dict(c) for c in cosmo_dicts]
+        objs = self._cosmologies_scope(cosmo_dicts, hods)
+        n_pt = len(cosmo_dicts)
+        th = theta_rad if _lib._is_torch(theta_rad) else numpy.asarray(theta_rad, dtype=numpy.float64)
+        flat = th.reshape(-1) if _lib._is_torch(th) else numpy.ascontiguousarray(th).ravel()
+        n_th = flat.numel() if _lib._is_torch(flat) else flat.size
+        self.cosmologies_status = numpy.zeros(n_pt, dtype=numpy.uint32)
+        self.cosmologies_z_bar = numpy.zeros(n_pt)
+        if n_pt == 0 or n_th == 0:
+            out = flat.new_empty((n_pt, n_th)) if _lib._is_torch(flat) else numpy.empty((n_pt, n_th))
+            return (out, self.cosmologies_status) if with_status else out
+        h = self.halo
+        code, _ = _POWER[self._power_name]
+        kind = "tinker" if getattr(h.mass, "_kind", 0) else "st"
+        rows = []
+        for b0 in range(0, n_pt, _lib.KERNEL_SETS_MAX):
+            cosmos = cosmo_dicts[b0:b0 + _lib.KERNEL_SETS_MAX]
+            n = len(cosmos)
+            block_hods = objs[b0:b0 + n] if objs is not None else h.local_hod
+            # (a context snapshots defaults.default_limits / default_precision when it is created)
+            key = (n, tuple(sorted(h.mass.halo_dict.items())), kind,
+                   tuple(sorted(defaults.default_limits.items())),
+                   tuple(sorted(defaults.default_precision.items())))
+            kept = getattr(self, "_cosmologies_grid", (None, None))
+            hg = kept[1] if kept[0] == key else None
+            if hg is None:
+                hg = grid.HaloGrid(numpy.zeros(n), cosmo_dict=cosmos, halo_dict=dict(h.mass.halo_dict),
+                                   hod_dict=block_hods if objs is None else list(block_hods),
+                                   mass_function=kind)
+                self._cosmologies_grid = (key, hg)
+            self.kernel._setup_sets_on(hg.ctx, cosmos)
+            info = hg.ctx.kernel_info_sets()           # (synchronises: z_bar and D(z_bar) per point)
+            z_bar, D_z = info["z_bar"], info["D_zbar"]
+            hg.set_parameters(cosmo=cosmos, z=z_bar,
+                              hod=block_hods if objs is None else list(block_hods))
+            hg.setup(self._power_name)
+            rows.append(hg.ctx.wtheta_sets(h._power_code(code), 0, n, self._k_lim[0], self._k_lim[1],
+                                           D_z, flat))
+            self.cosmologies_status[b0:b0 + n] = hg.status()   # (synchronises: this block's words)
+            self.cosmologies_z_bar[b0:b0 + n] = z_bar
+        if len(rows) == 1:
+            out = rows[0]
+        elif _lib._is_torch(flat):
+            import torch
+            out = torch.cat(rows)
+        else:
+            out = numpy.concatenate(rows)
+        words = self.cosmologies_status
+        for i, w in enumerate(words):
+            w = int(w)
+            if w:
+                category = (_lib.ChompParityWarning
+                            if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
+                            else _lib.ChompAccuracyWarning)
+                warnings.warn("cosmology %d: %s" % (i, "; ".join(_lib.describe_status(w))), category,
+                              stacklevel=2)
+        return (out, words) if with_status else out
+
     def write(self, output_file_name):
         with open(output_file_name, "w") as f:
             f.write("#ttype1 = theta [deg]\n#ttype2 = wtheta\n")
@@ -300,6 +416,16 @@ class CorrelationFourier(Correlation):
         tables and Romberg integrals with an epoch axis, each row bit for bit what Context.cell
         returns for that epoch."""
         return ctx.cell_epochs(code, 0, n_hod, self.D_z, flat)
+
+    def correlation_cosmologies(self, l, cosmo_dicts, hods=None, with_status=False):
+        """C_l is not batched over cosmologies yet: the chi-only node table of
+        Context.cell_epochs belongs to one projection set-up, and a set axis on it is the
+        follow-up to Correlation.correlation_cosmologies.  Raises ChompScopeError (it must never
+        return w(theta))."""
+        raise _lib.ChompScopeError(
+            "CorrelationFourier.correlation_cosmologies: C_l over cosmologies is not batched yet "
+            "(the follow-up: a set axis on chomp_cell_epochs' chi-only node table); use the loop "
+            "set_cosmology + correlation")
 
     def write(self, output_file_name):
         with open(output_file_name, "w") as f:

@@ -136,6 +136,7 @@ struct chomp_ctx {
   std::vector<char> have_halofit;
   StagedBlock sh_cosmo, sh_z, sh_mass, sh_profile, sh_hod, sh_slot, sh_first;
   StagedBlock sh_proj, sh_pp[2];   // projection scalars, tabulated redshift distributions
+  StagedBlock sh_sets;             // the ProjDev blocks of chomp_kernel_setup_sets
   // pinned host mirrors of the staging buffers of host-pointer calls (chomp_power)
   unsigned* h_status = nullptr;    // chomp_status_post: pinned copy of d_status ...
   size_t cap_hstatus = 0, n_hstatus = 0;
@@ -234,6 +235,7 @@ struct chomp_ctx {
 
   // projection
   ProjState proj;
+  ProjSets sets;                // chomp_kernel_setup_sets: one projection set-up per cosmology
   CrossState cross;             // Covariance(corr_a, corr_b): the two sides' snapshots and the four tables
   FourierState fourier;         // CovarianceFourier: the four pairs' scalars, Limber tables and splines
   // The side stream.  The projection set-up (chomp_kernel_setup / chomp_multi_epoch_setup:
@@ -707,7 +709,8 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_stage_in, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4, ctx->d_prof};
+                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4, ctx->d_prof,
+                  ctx->sets.d_pd, ctx->sets.d_pd_init, ctx->sets.d_tab};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -715,7 +718,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
   for (StagedBlock* b : {&ctx->sh_cosmo, &ctx->sh_z, &ctx->sh_mass, &ctx->sh_profile, &ctx->sh_hod,
                          &ctx->sh_slot, &ctx->sh_first, &ctx->sh_delta_b, &ctx->sh_proj, &ctx->sh_pp[0],
                          &ctx->sh_pp[1], &ctx->sh_de_knots, &ctx->sh_de_slot, &ctx->de_ep.sh_par,
-                         &ctx->de_proj.sh_par})
+                         &ctx->de_proj.sh_par, &ctx->sh_sets})
     b->release();
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);

@@ -108,6 +108,67 @@ static int proj_dark_energy(chomp_ctx* ctx, const chomp_cosmo* cosmo, DeSpline* 
   return CHOMP_OK;
 }
 
+// What chomp_kernel_setup and chomp_kernel_setup_sets validate alike (who: the caller's name).
+static int proj_check_args(chomp_ctx* ctx, const char* who, double ktheta_min, double ktheta_max,
+                           const chomp_window* const ws[2]) {
+  const std::string w_ = std::string(who) + ": ";
+  if (!(ktheta_min > 0.0) || !(ktheta_max > ktheta_min)) return fail(ctx, CHOMP_ERR_ARG, w_ + "ktheta range");
+  for (int w = 0; w < 2; ++w) {
+    if (ws[w]->kind < CHOMP_WINDOW_GALAXY || ws[w]->kind > CHOMP_WINDOW_CONVERGENCE_DELTA)
+      return fail(ctx, CHOMP_ERR_SCOPE, w_ + "unknown window kind");
+    const chomp_dndz& dz = ws[w]->dist;
+    if (dz.kind != CHOMP_DNDZ_MAGLIM && dz.kind != CHOMP_DNDZ_GAUSSIAN &&
+        dz.kind != CHOMP_DNDZ_BOXCAR && dz.kind != CHOMP_DNDZ_PPOLY)
+      return fail(ctx, CHOMP_ERR_SCOPE, w_ + "only dNdz / dNdzMagLim / dNdzGaussian / "
+                                             "dNdzInterpolation are in scope");
+    if (dz.kind == CHOMP_DNDZ_PPOLY) {
+      if (!dz.pp_breaks || !dz.pp_coef || dz.pp_n < 1 || dz.pp_n > 65536 || dz.pp_order < 0 ||
+          dz.pp_order > 5)
+        return fail(ctx, CHOMP_ERR_ARG, w_ + "dNdzInterpolation spline (pieces / order)");
+      for (int i = 0; i < dz.pp_n; ++i)
+        if (!(dz.pp_breaks[i + 1] > dz.pp_breaks[i]))
+          return fail(ctx, CHOMP_ERR_ARG, w_ + "dNdzInterpolation breaks must increase");
+    }
+  }
+  return CHOMP_OK;
+}
+
+// The ProjDev block of one set-up as the host prepares it (the device fills in the rest: norms,
+// ranges, z_bar).  A tabulated distribution's table is the caller's to add (pp, pp_n, pp_order).
+static ProjDev proj_host_block(const chomp_config& c, const chomp_cosmo* cosmo, double me_z_min,
+                               double me_z_max, double ktheta_min, double ktheta_max,
+                               const chomp_window* const ws[2], int bessel_order, double j_limit) {
+  ProjDev pd;
+  std::memset(&pd, 0, sizeof(pd));
+  pd.om0 = cosmo->omega_m0; pd.ol0 = cosmo->omega_l0; pd.or0 = cosmo->omega_r0;
+  pd.H0 = 100.0 / (2.998 * 100000.0);
+  pd.growth_norm = growth_approx(pd.om0, pd.ol0, 1.0);
+  pd.me_z_min[0] = me_z_min < 0.0 ? 0.0 : me_z_min;          // cosmology.py:748-750
+  pd.me_z_max[0] = me_z_max;
+  for (int w = 0; w < 2; ++w) {
+    const chomp_window& W = *ws[w];
+    pd.wkind[w] = W.kind;
+    pd.dist[w].kind = W.dist.kind;
+    pd.dist[w].z_min = W.dist.z_min;
+    pd.dist[w].z_max = W.dist.z_max;
+    for (int q = 0; q < 4; ++q) pd.dist[w].p[q] = W.dist.p[q];
+    pd.dist[w].norm = 1.0;
+    // WindowFunction.__init__ (kernel.py:234-240); Convergence spans [0, z_max] (:436)
+    double zmin = (W.kind == CHOMP_WINDOW_GALAXY || W.kind == CHOMP_WINDOW_FLAT_CONVERGENCE)
+                      ? W.dist.z_min : 0.0;
+    if (zmin < c.window_precision) zmin = c.window_precision;
+    pd.w_z_min[w] = zmin;
+    pd.w_z_max[w] = W.dist.z_max;
+    pd.me_z_min[w + 1] = zmin < 0.0 ? 0.0 : zmin;
+    pd.me_z_max[w + 1] = W.dist.z_max;
+  }
+  pd.ln_kt_min = std::log(ktheta_min);
+  pd.ln_kt_max = std::log(ktheta_max);
+  pd.order = bessel_order;
+  pd.j_limit = j_limit;
+  return pd;
+}
+
 int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min,
                        double me_z_max, double ktheta_min, double ktheta_max,
                        const chomp_window* a, const chomp_window* b, int bessel_order) {
@@ -116,25 +177,8 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
   if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: bessel order must be 0 or 2");
   if (!ctx->dark_energy && has_dark_energy(cosmo->w0, cosmo->wa))
     return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup: w0/wa != -1/0 needs chomp_set_dark_energy(ctx, 1)");
-  if (!(ktheta_min > 0.0) || !(ktheta_max > ktheta_min)) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: ktheta range");
   const chomp_window* ws[2] = {a, b};
-  for (int w = 0; w < 2; ++w) {
-    if (ws[w]->kind < CHOMP_WINDOW_GALAXY || ws[w]->kind > CHOMP_WINDOW_CONVERGENCE_DELTA)
-      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup: unknown window kind");
-    const chomp_dndz& dz = ws[w]->dist;
-    if (dz.kind != CHOMP_DNDZ_MAGLIM && dz.kind != CHOMP_DNDZ_GAUSSIAN &&
-        dz.kind != CHOMP_DNDZ_BOXCAR && dz.kind != CHOMP_DNDZ_PPOLY)
-      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup: only dNdz / dNdzMagLim / dNdzGaussian / "
-                                        "dNdzInterpolation are in scope");
-    if (dz.kind == CHOMP_DNDZ_PPOLY) {
-      if (!dz.pp_breaks || !dz.pp_coef || dz.pp_n < 1 || dz.pp_n > 65536 || dz.pp_order < 0 ||
-          dz.pp_order > 5)
-        return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: dNdzInterpolation spline (pieces / order)");
-      for (int i = 0; i < dz.pp_n; ++i)
-        if (!(dz.pp_breaks[i + 1] > dz.pp_breaks[i]))
-          return fail(ctx, CHOMP_ERR_ARG, "kernel_setup: dNdzInterpolation breaks must increase");
-    }
-  }
+  { const int rcc = proj_check_args(ctx, "kernel_setup", ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
   HIPCHK(hipSetDevice(ctx->device));
   // On the side stream (SideScope): behind everything the context's stream holds now -- the
   // readers of the previous tables -- and beside whatever is queued there next (a halo set-up:
@@ -171,46 +215,22 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
     }
     P.pp_total = (size_t)P.L.total + pp_doubles[0];
   }
-  ProjDev pd;
-  std::memset(&pd, 0, sizeof(pd));
-  pd.om0 = cosmo->omega_m0; pd.ol0 = cosmo->omega_l0; pd.or0 = cosmo->omega_r0;
-  pd.H0 = 100.0 / (2.998 * 100000.0);
-  pd.growth_norm = growth_approx(pd.om0, pd.ol0, 1.0);
-  pd.me_z_min[0] = me_z_min < 0.0 ? 0.0 : me_z_min;          // cosmology.py:748-750
-  pd.me_z_max[0] = me_z_max;
+  ProjDev pd = proj_host_block(c, cosmo, me_z_min, me_z_max, ktheta_min, ktheta_max, ws, bessel_order,
+                               bessel_zero_host(bessel_order, c.kernel_bessel_limit));
   for (int w = 0; w < 2; ++w) {
     const chomp_window& W = *ws[w];
-    pd.wkind[w] = W.kind;
-    pd.dist[w].kind = W.dist.kind;
-    if (W.dist.kind == CHOMP_DNDZ_PPOLY) {
-      double* dst = P.d_tab + P.L.total + (w == 1 ? pp_doubles[0] : 0);
-      const size_t nb = (size_t)W.dist.pp_n + 1, nc = (size_t)W.dist.pp_n * (W.dist.pp_order + 1);
-      std::vector<double> blk(nb + nc);
-      std::memcpy(blk.data(), W.dist.pp_breaks, nb * sizeof(double));
-      std::memcpy(blk.data() + nb, W.dist.pp_coef, nc * sizeof(double));
-      const int rcp = upload(ctx, dst, blk.data(), (nb + nc) * sizeof(double), ctx->sh_pp[w]);
-      if (rcp) return rcp;
-      pd.dist[w].pp = dst;
-      pd.dist[w].pp_n = W.dist.pp_n;
-      pd.dist[w].pp_order = W.dist.pp_order;
-    }
-    pd.dist[w].z_min = W.dist.z_min;
-    pd.dist[w].z_max = W.dist.z_max;
-    for (int q = 0; q < 4; ++q) pd.dist[w].p[q] = W.dist.p[q];
-    pd.dist[w].norm = 1.0;
-    // WindowFunction.__init__ (kernel.py:234-240); Convergence spans [0, z_max] (:436)
-    double zmin = (W.kind == CHOMP_WINDOW_GALAXY || W.kind == CHOMP_WINDOW_FLAT_CONVERGENCE)
-                      ? W.dist.z_min : 0.0;
-    if (zmin < c.window_precision) zmin = c.window_precision;
-    pd.w_z_min[w] = zmin;
-    pd.w_z_max[w] = W.dist.z_max;
-    pd.me_z_min[w + 1] = zmin < 0.0 ? 0.0 : zmin;
-    pd.me_z_max[w + 1] = W.dist.z_max;
+    if (W.dist.kind != CHOMP_DNDZ_PPOLY) continue;
+    double* dst = P.d_tab + P.L.total + (w == 1 ? pp_doubles[0] : 0);
+    const size_t nb = (size_t)W.dist.pp_n + 1, nc = (size_t)W.dist.pp_n * (W.dist.pp_order + 1);
+    std::vector<double> blk(nb + nc);
+    std::memcpy(blk.data(), W.dist.pp_breaks, nb * sizeof(double));
+    std::memcpy(blk.data() + nb, W.dist.pp_coef, nc * sizeof(double));
+    const int rcp = upload(ctx, dst, blk.data(), (nb + nc) * sizeof(double), ctx->sh_pp[w]);
+    if (rcp) return rcp;
+    pd.dist[w].pp = dst;
+    pd.dist[w].pp_n = W.dist.pp_n;
+    pd.dist[w].pp_order = W.dist.pp_order;
   }
-  pd.ln_kt_min = std::log(ktheta_min);
-  pd.ln_kt_max = std::log(ktheta_max);
-  pd.order = bessel_order;
-  pd.j_limit = bessel_zero_host(bessel_order, c.kernel_bessel_limit);
   // (the device fills in the rest of the block -- norms, ranges, z_bar -- so every set-up starts
   //  from the block as the host prepared it: kept on the device, sent only when it changes, and
   //  copied into place on the stream -- a node of the graph under stream capture)
@@ -315,6 +335,35 @@ int chomp_me_eval(chomp_ctx* ctx, int what, const double* x, size_t n, double* o
   return st.finish();
 }
 
+// The CHOMP_KI_* scalars of one set-up's block.
+static void proj_info_out(const ProjDev& pd, double* out) {
+  out[CHOMP_KI_Z_BAR] = pd.z_bar; out[CHOMP_KI_CHI_MIN] = pd.chi_min;
+  out[CHOMP_KI_CHI_MAX] = pd.chi_max; out[CHOMP_KI_Z_MIN] = pd.z_min;
+  out[CHOMP_KI_Z_MAX] = pd.z_max; out[CHOMP_KI_D_ZBAR] = pd.D_zbar;
+  out[CHOMP_KI_NORM_A] = pd.dist[0].norm; out[CHOMP_KI_NORM_B] = pd.dist[1].norm;
+  out[CHOMP_KI_WA_CHI_MIN] = pd.w_chi_min[0]; out[CHOMP_KI_WA_CHI_MAX] = pd.w_chi_max[0];
+  out[CHOMP_KI_WB_CHI_MIN] = pd.w_chi_min[1]; out[CHOMP_KI_WB_CHI_MAX] = pd.w_chi_max[1];
+  out[CHOMP_KI_J_LIMIT] = pd.j_limit;
+}
+
+// Where table CHOMP_KTAB_* lies in a slab of the layout; false: no such table.
+static bool proj_table_span(const ProjLayout& L, int table, int* off, size_t* len) {
+  switch (table) {
+    case CHOMP_KTAB_LN_KTHETA: *off = L.k_ln; *len = L.NKT; break;
+    case CHOMP_KTAB_KERNEL: *off = L.k_arr; *len = L.NKT; break;
+    case CHOMP_KTAB_LEVELS: *off = L.k_lev; *len = L.NKT; break;
+    case CHOMP_KTAB_WA_CHI: *off = L.w_chi[0]; *len = L.NWp; break;
+    case CHOMP_KTAB_WA: *off = L.w_wf[0]; *len = L.NWp; break;
+    case CHOMP_KTAB_WB_CHI: *off = L.w_chi[1]; *len = L.NWp; break;
+    case CHOMP_KTAB_WB: *off = L.w_wf[1]; *len = L.NWp; break;
+    case CHOMP_KTAB_ME_Z: *off = L.me_z[0]; *len = L.NC; break;
+    case CHOMP_KTAB_ME_CHI: *off = L.me_chi[0]; *len = L.NC; break;
+    case CHOMP_KTAB_ME_GROWTH: *off = L.me_growth[0]; *len = L.NC; break;
+    default: return false;
+  }
+  return true;
+}
+
 int chomp_kernel_info(chomp_ctx* ctx, double* out) {
   if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "kernel_info: bad args");
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "kernel_info before kernel_setup");
@@ -323,13 +372,7 @@ int chomp_kernel_info(chomp_ctx* ctx, double* out) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ProjDev& pd = ctx->proj.host;
   HIPCHK(hipMemcpy(&pd, ctx->proj.d_pd, sizeof(pd), hipMemcpyDeviceToHost));
-  out[CHOMP_KI_Z_BAR] = pd.z_bar; out[CHOMP_KI_CHI_MIN] = pd.chi_min;
-  out[CHOMP_KI_CHI_MAX] = pd.chi_max; out[CHOMP_KI_Z_MIN] = pd.z_min;
-  out[CHOMP_KI_Z_MAX] = pd.z_max; out[CHOMP_KI_D_ZBAR] = pd.D_zbar;
-  out[CHOMP_KI_NORM_A] = pd.dist[0].norm; out[CHOMP_KI_NORM_B] = pd.dist[1].norm;
-  out[CHOMP_KI_WA_CHI_MIN] = pd.w_chi_min[0]; out[CHOMP_KI_WA_CHI_MAX] = pd.w_chi_max[0];
-  out[CHOMP_KI_WB_CHI_MIN] = pd.w_chi_min[1]; out[CHOMP_KI_WB_CHI_MAX] = pd.w_chi_max[1];
-  out[CHOMP_KI_J_LIMIT] = pd.j_limit;
+  proj_info_out(pd, out);
   return CHOMP_OK;
 }
 
@@ -339,27 +382,108 @@ int chomp_kernel_table(chomp_ctx* ctx, int table, double* out, size_t n) {
   if (!ctx->proj.ready && table != CHOMP_KTAB_ME_Z && table != CHOMP_KTAB_ME_CHI &&
       table != CHOMP_KTAB_ME_GROWTH)
     return fail(ctx, CHOMP_ERR_STATE, "kernel_table: only the MultiEpoch tables exist");
-  const ProjLayout& L = ctx->proj.L;
   int off = -1;
   size_t len = 0;
-  switch (table) {
-    case CHOMP_KTAB_LN_KTHETA: off = L.k_ln; len = L.NKT; break;
-    case CHOMP_KTAB_KERNEL: off = L.k_arr; len = L.NKT; break;
-    case CHOMP_KTAB_LEVELS: off = L.k_lev; len = L.NKT; break;
-    case CHOMP_KTAB_WA_CHI: off = L.w_chi[0]; len = L.NWp; break;
-    case CHOMP_KTAB_WA: off = L.w_wf[0]; len = L.NWp; break;
-    case CHOMP_KTAB_WB_CHI: off = L.w_chi[1]; len = L.NWp; break;
-    case CHOMP_KTAB_WB: off = L.w_wf[1]; len = L.NWp; break;
-    case CHOMP_KTAB_ME_Z: off = L.me_z[0]; len = L.NC; break;
-    case CHOMP_KTAB_ME_CHI: off = L.me_chi[0]; len = L.NC; break;
-    case CHOMP_KTAB_ME_GROWTH: off = L.me_growth[0]; len = L.NC; break;
-    default: return fail(ctx, CHOMP_ERR_ARG, "kernel_table: unknown table");
-  }
+  if (!proj_table_span(ctx->proj.L, table, &off, &len)) return fail(ctx, CHOMP_ERR_ARG, "kernel_table: unknown table");
   if (n != len) return fail(ctx, CHOMP_ERR_ARG, "kernel_table: length mismatch");
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(out, ctx->proj.d_tab + off, len * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
+// One projection set-up per cosmology (the cosmology axis of a w(theta) design or chain:
+// Kernel.set_cosmology, kernel.py:657-676, once per point of simulation_design.py:116-155): the
+// six launches of chomp_kernel_setup, once, with the set axis as the grids' z dimension
+// (chomp_proj_kernels.h, "The set axis").  On the context's stream; ctx->proj is not touched.
+int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo, double me_z_min,
+                            double me_z_max, double ktheta_min, double ktheta_max,
+                            const chomp_window* a, const chomp_window* b, int bessel_order) {
+  StageRange range_(ctx, "chomp:kernel_setup_sets");
+  if (!ctx || !cosmo || !a || !b || n_set == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bad args");
+  if (n_set > (size_t)kProjSetsMax)
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: more than " + std::to_string(kProjSetsMax) + " sets in one call");
+  if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bessel order must be 0 or 2");
+  for (size_t s = 0; s < n_set; ++s)
+    if (has_dark_energy(cosmo[s].w0, cosmo[s].wa))
+      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a w0/wa != -1/0 cosmology is set up by chomp_kernel_setup");
+  const chomp_window* ws[2] = {a, b};
+  { const int rcc = proj_check_args(ctx, "kernel_setup_sets", ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
+  for (int w = 0; w < 2; ++w)
+    if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
+      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a tabulated redshift distribution "
+                                        "(dNdzInterpolation) is set up by chomp_kernel_setup");
+  const chomp_config& c = ctx->cfg;
+  const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
+  if (L.NC > 240 || L.NWp > 360 || L.NKT > 720)          // (the spline builds are staged in 64 KB of LDS)
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: cosmo/window/kernel_npoints too large");
+  HIPCHK(hipSetDevice(ctx->device));
+  ProjSets& S = ctx->sets;
+  S.n = 0;
+  int rc = ensure(ctx, &S.d_pd, &S.cap_pd, n_set);
+  if (!rc) {
+    const ProjDev* before = S.d_pd_init;
+    rc = ensure(ctx, &S.d_pd_init, &S.cap_pd_init, n_set);
+    if (S.d_pd_init != before) ctx->sh_sets.reset();
+  }
+  if (!rc) rc = ensure(ctx, &S.d_tab, &S.cap_tab, n_set * (size_t)L.total);
+  if (rc) return rc;
+  const double j_limit = bessel_zero_host(bessel_order, c.kernel_bessel_limit);
+  std::vector<ProjDev> pd(n_set);
+  for (size_t s = 0; s < n_set; ++s)
+    pd[s] = proj_host_block(c, &cosmo[s], me_z_min, me_z_max, ktheta_min, ktheta_max, ws, bessel_order, j_limit);
+  rc = upload(ctx, S.d_pd_init, pd.data(), n_set * sizeof(ProjDev), ctx->sh_sets);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(S.d_pd, S.d_pd_init, n_set * sizeof(ProjDev), hipMemcpyDeviceToDevice, ctx->stream));
+  S.L = L;
+  S.host = pd[0];
+  const unsigned Z = (unsigned)n_set;
+  const size_t stride = (size_t)L.total;
+  hipLaunchKernelGGL(k_proj_chi_sets, dim3(L.NC, 4, Z), dim3(64), 0, ctx->stream, c, L, S.d_pd, S.d_tab, stride);
+  hipLaunchKernelGGL(k_proj_me_splines_sets, dim3(3, 1, Z), dim3(192), (size_t)(33 * L.NC) * sizeof(double),
+                     ctx->stream, c, L, S.d_pd, S.d_tab, stride);
+  hipLaunchKernelGGL(k_proj_window_sets, dim3(L.NWp, 2, Z), dim3(64),
+                     (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, S.d_pd,
+                     S.d_tab, stride);
+  hipLaunchKernelGGL(k_proj_window_splines_sets, dim3(1, 1, Z), dim3(128),
+                     (size_t)(22 * L.NWp) * sizeof(double), ctx->stream, c, L, S.d_pd, S.d_tab, stride);
+  hipLaunchKernelGGL(k_proj_kernel_knots_sets, dim3(L.NKT, 1, Z), dim3(256),
+                     (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, c, L, S.d_pd,
+                     S.d_tab, bessel_order == 0 ? ctx->d_j0 : ctx->d_j2, stride);
+  hipLaunchKernelGGL(k_proj_kernel_spline_sets, dim3(1, 1, Z), dim3(64),
+                     (size_t)(11 * L.NKT) * sizeof(double), ctx->stream, L, S.d_tab, stride);
+  HIPCHK(hipGetLastError());
+  S.n = n_set;
+  return CHOMP_OK;
+}
+
+// chomp_kernel_info of every set, [n_set][CHOMP_KI_COUNT], in one synchronising read-back.
+int chomp_kernel_info_sets(chomp_ctx* ctx, double* out) {
+  if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "kernel_info_sets: bad args");
+  const ProjSets& S = ctx->sets;
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "kernel_info_sets before kernel_setup_sets");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  std::vector<ProjDev> pd(S.n);
+  HIPCHK(hipMemcpy(pd.data(), S.d_pd, S.n * sizeof(ProjDev), hipMemcpyDeviceToHost));
+  for (size_t s = 0; s < S.n; ++s) proj_info_out(pd[s], out + s * CHOMP_KI_COUNT);
+  return CHOMP_OK;
+}
+
+// chomp_kernel_table of one set.
+int chomp_kernel_table_set(chomp_ctx* ctx, size_t set, int table, double* out, size_t n) {
+  if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "kernel_table_set: bad args");
+  const ProjSets& S = ctx->sets;
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "kernel_table_set before kernel_setup_sets");
+  if (set >= S.n) return fail(ctx, CHOMP_ERR_ARG, "kernel_table_set: set");
+  int off = -1;
+  size_t len = 0;
+  if (!proj_table_span(S.L, table, &off, &len)) return fail(ctx, CHOMP_ERR_ARG, "kernel_table_set: unknown table");
+  if (n != len) return fail(ctx, CHOMP_ERR_ARG, "kernel_table_set: length mismatch");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(out, S.d_tab + set * (size_t)S.L.total + off, len * sizeof(double), hipMemcpyDeviceToHost));
   return CHOMP_OK;
 }
 
@@ -706,6 +830,96 @@ int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch
                            ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
                            ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, D_z, din, o, ctx->d_wnodes,
                            LT, stride);
+      }
+    }
+  }
+  return st.finish();
+}
+
+// w(theta) of n_epoch epochs, epoch epoch0 + e against projection set e of the last
+// chomp_kernel_setup_sets with growth D_z[e] (a cosmology design or chain: the loop of
+// set_cosmology + correlation, correlation.py:161-171 per point): chomp_wtheta_epochs with a
+// per-row set and growth factor -- its scope, routes, chunks and work buffer.
+int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
+                      double k_max, const double* D_z, const double* theta, size_t n, double* out,
+                      int mem) {
+  StageRange range_(ctx, "chomp:wtheta_sets");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!D_z || !theta || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: bad args");
+  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: n * n_epoch too large");
+  Staging st(ctx, mem, "wtheta_sets");
+  if (st.rc) return st.rc;
+  const ProjSets& S = ctx->sets;
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "wtheta_sets before kernel_setup_sets");
+  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
+  if (ctx->precision != CHOMP_PREC_F64)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: fp64 only (the narrowed precision modes belong to chomp_wtheta)");
+  if (which & CHOMP_P_HALOFIT)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: HaloFit spectra are evaluated by chomp_wtheta");
+  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: extrapolated spectra are evaluated by chomp_wtheta");
+  if (ctx->with_bao)
+    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: the wiggle transfer function is evaluated by chomp_wtheta");
+  if (n_epoch != S.n)
+    return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: n_epoch is not the number of sets of the last kernel_setup_sets");
+  int rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  if (!(k_min > 0.0) || !(k_max > k_min)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: k range");
+  for (size_t e = 0; e < n_epoch; ++e)
+    if (!(D_z[e] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: D_z");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* din;
+  double* dout;
+  st.in(theta, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = st.place(n_epoch);         // (D_z is a host array whatever `mem` says: the scratch segment)
+  if (rc) return rc;
+  const double* dD = st.scratch;
+  HIPCHK(hipMemcpyAsync(st.scratch, D_z, n_epoch * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  // (the route and the sizes as in wtheta_impl)
+  const ProjLayout& L = S.L;
+  const size_t pstride = (size_t)L.total;
+  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
+  const int LT = ctx->cfg.divmax < kWthetaTabLevel ? ctx->cfg.divmax : kWthetaTabLevel;
+  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const double dxK = (S.host.ln_kt_max - S.host.ln_kt_min) / (double)(L.NKT - 1);
+  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
+  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
+  const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
+                    ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
+  const size_t stride = wth_epoch_stride(LT, nseg, fast);
+  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
+                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
+  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
+  if (rc) return rc;
+  double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // (of the chunk's first epoch)
+  double* segtot = rec + 4 * wth_rec_count(LT);
+  const unsigned gnodes = (unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
+  {
+    constexpr bool HF = false, BAO = false;
+    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the scratch is reused in stream order)
+      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+      const int e0 = (int)(epoch0 + c0);
+      double* o = dout + c0 * n;
+      const ProjDev* pd = S.d_pd + c0;                      // (the chunk's first set)
+      const double* ptab = S.d_tab + c0 * pstride;
+      hipLaunchKernelGGL((k_wtheta_nodes_sets<HF, BAO>), dim3(gnodes, E), dim3(256),
+                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, k_min, k_max, dD + c0, LT,
+                         ctx->d_wnodes, stride);
+      if (fast) {
+        hipLaunchKernelGGL(k_wtheta_moments_epochs, dim3((unsigned)nseg, (unsigned)LT, kWthParts * E),
+                           dim3(256), 0, ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min),
+                           std::log(k_max), rec, segtot, stride);
+        hipLaunchKernelGGL(k_wtheta_fast_sets, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
+                           ctx->cfg, L, pd, ptab, pstride, k_min, k_max, din, o, ctx->d_wnodes, rec,
+                           segtot, LT, nseg, stride);
+      } else {
+        hipLaunchKernelGGL((k_wtheta_sets<HF, BAO>), dim3((unsigned)n, E), dim3(64 * kWthetaNW), sh,
+                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                           pd, ptab, pstride, k_min, k_max, dD + c0, din, o, ctx->d_wnodes, LT,
+                           stride);
       }
     }
   }

@@ -132,6 +132,19 @@ inline void proj_free(ProjState& p) {
   p.cov_ready = false;
 }
 
+// The projection set-ups of chomp_kernel_setup_sets, beside ProjState (which they never touch):
+// n ProjDev blocks and n slabs of L.total doubles, set s at d_pd[s] and d_tab + s * L.total.
+// The buffers are kept across calls and only grow.
+struct ProjSets {
+  size_t n = 0;            // sets of the last chomp_kernel_setup_sets (0: none yet)
+  ProjLayout L;
+  ProjDev host;            // what the sets share, as the host prepared it (ln k theta range, order)
+  ProjDev* d_pd = nullptr;
+  ProjDev* d_pd_init = nullptr;   // the blocks as the host prepared them (the device fills d_pd in)
+  double* d_tab = nullptr;
+  size_t cap_pd = 0, cap_pd_init = 0, cap_tab = 0;
+};
+
 // ---------------------------------------------------------------------------
 // HaloFit
 // ---------------------------------------------------------------------------
@@ -402,10 +415,11 @@ struct DndzRaw {
 
 // grid (NC, 4), block 64.  y < 3: chi and growth of MultiEpoch y at grid point x;
 // y == 3, x < 2: normalisation of distribution x.  DE: E with the pressure spline `de`.
+// (the body of k_proj_chi and k_proj_chi_sets)
 template <bool DE>
-__global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
-                                                 ProjDev* __restrict__ pd,
-                                                 double* __restrict__ tab, DeSpline de) {
+__device__ __forceinline__ void proj_chi_body(const chomp_config& cfg, const ProjLayout& L,
+                                              ProjDev* __restrict__ pd, double* __restrict__ tab,
+                                              const DeSpline& de) {
   const int i = blockIdx.x, m = blockIdx.y;
   if (m == 3) {
     if (i >= 2) return;
@@ -432,6 +446,31 @@ __global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
     tab[L.me_chi[m] + i] = chi;
     tab[L.me_growth[m] + i] = growth_approx(pd->om0, pd->ol0, 1.0 / (1.0 + z)) / pd->growth_norm;
   }
+}
+template <bool DE>
+__global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
+                                                 ProjDev* __restrict__ pd,
+                                                 double* __restrict__ tab, DeSpline de) {
+  proj_chi_body<DE>(cfg, L, pd, tab, de);
+}
+
+// The set axis (chomp_kernel_setup_sets: one projection set-up per cosmology of a design or
+// chain, Kernel.set_cosmology of kernel.py:657-676 as one batch).  Every kernel of the set-up
+// takes its cosmology from its ProjDev block and its tables from one slab of ProjLayout::total
+// doubles, and none of their grids uses blockIdx.z: the *_sets forms run the same bodies with
+// set blockIdx.z's block pd[blockIdx.z] and its slab, `stride` doubles after the previous set's.
+// Lambda-CDM only (no pressure spline) and no tabulated redshift distribution (those ride behind
+// the single set-up's slab).  kProjSetsMax: the sets of one call -- 1024 slabs of the default
+// layout (3752 doubles) are 29 MiB; a grid's z dimension would allow 65535.
+constexpr int kProjSetsMax = CHOMP_KERNEL_SETS_MAX;   // 1024
+static_assert(kProjSetsMax <= 65535, "the set axis is a grid's z dimension");
+
+// grid (NC, 4, n_set), block 64.
+__global__ __launch_bounds__(64) void k_proj_chi_sets(chomp_config cfg, ProjLayout L,
+                                                      ProjDev* __restrict__ pd,
+                                                      double* __restrict__ tab, size_t stride) {
+  proj_chi_body<false>(cfg, L, pd + blockIdx.z, tab + stride * blockIdx.z,
+                       DeSpline{nullptr, nullptr, 0});
 }
 
 // MultiEpoch lookups with the reference's range rules (cosmology.py:873-953).
@@ -476,9 +515,10 @@ __device__ __forceinline__ void spline_build_staged(const double* x, const doubl
 
 // grid 3, block 192.  Splines of MultiEpoch m; blocks 1/2 then lay out window
 // (m-1)'s chi grid (kernel.py:298-304, 438-441).
-__global__ __launch_bounds__(192) void k_proj_me_splines(chomp_config cfg, ProjLayout L,
-                                                         ProjDev* __restrict__ pd,
-                                                         double* __restrict__ tab) {
+// (the body of k_proj_me_splines and k_proj_me_splines_sets)
+__device__ __forceinline__ void proj_me_splines_body(const chomp_config& cfg, const ProjLayout& L,
+                                                     ProjDev* __restrict__ pd,
+                                                     double* __restrict__ tab) {
   extern __shared__ __align__(16) double sm_me[];      // 3 x 11 NC doubles
   const int m = blockIdx.x, NC = L.NC;
   const int wave = threadIdx.x >> 6;
@@ -507,6 +547,18 @@ __global__ __launch_bounds__(192) void k_proj_me_splines(chomp_config cfg, ProjL
   for (int i = threadIdx.x; i < L.NWp; i += blockDim.x)
     tab[L.w_chi[w] + i] = linspace_at(lim[0], lim[1], L.NWp, i);
 }
+__global__ __launch_bounds__(192) void k_proj_me_splines(chomp_config cfg, ProjLayout L,
+                                                         ProjDev* __restrict__ pd,
+                                                         double* __restrict__ tab) {
+  proj_me_splines_body(cfg, L, pd, tab);
+}
+// ... with the set axis: grid (3, 1, n_set), block 192.
+__global__ __launch_bounds__(192) void k_proj_me_splines_sets(chomp_config cfg, ProjLayout L,
+                                                              ProjDev* __restrict__ pd,
+                                                              double* __restrict__ tab,
+                                                              size_t stride) {
+  proj_me_splines_body(cfg, L, pd + blockIdx.z, tab + stride * blockIdx.z);
+}
 
 // E0(z) of the projection's cosmology: Lambda-CDM, or (DE) with the pressure spline.
 template <bool DE>
@@ -534,10 +586,11 @@ struct LensIntegrand {
 };
 
 // grid (NWp, 2), block 64: raw window function of window y at its x-th chi knot.
+// (the body of k_proj_window and k_proj_window_sets)
 template <bool DE>
-__global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout L,
-                                                    const ProjDev* __restrict__ pd,
-                                                    double* __restrict__ tab, DeSpline de) {
+__device__ __forceinline__ void proj_window_body(const chomp_config& cfg, const ProjLayout& L,
+                                                 const ProjDev* __restrict__ pd,
+                                                 double* __restrict__ tab, const DeSpline& de) {
   extern __shared__ __align__(16) double sm[];
   __shared__ DndzDev D;
   const int i = blockIdx.x, w = blockIdx.y, m = w + 1, NC = L.NC;
@@ -575,6 +628,19 @@ __global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout
   }
   if (threadIdx.x == 0) tab[L.w_wf[w] + i] = val;
 }
+template <bool DE>
+__global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout L,
+                                                    const ProjDev* __restrict__ pd,
+                                                    double* __restrict__ tab, DeSpline de) {
+  proj_window_body<DE>(cfg, L, pd, tab, de);
+}
+// ... with the set axis: grid (NWp, 2, n_set), block 64.
+__global__ __launch_bounds__(64) void k_proj_window_sets(chomp_config cfg, ProjLayout L,
+                                                         const ProjDev* __restrict__ pd,
+                                                         double* __restrict__ tab, size_t stride) {
+  proj_window_body<false>(cfg, L, pd + blockIdx.z, tab + stride * blockIdx.z,
+                          DeSpline{nullptr, nullptr, 0});
+}
 
 // Window lookup with the range rule of kernel.py:326-340 (uniform chi knots).
 struct WindowView {
@@ -588,9 +654,11 @@ struct WindowView {
 };
 
 // grid 1, block 128: window splines, then Kernel.__init__ scalars + _find_z_bar.
-__global__ __launch_bounds__(128) void k_proj_window_splines(chomp_config cfg, ProjLayout L,
-                                                             ProjDev* __restrict__ pd,
-                                                             double* __restrict__ tab) {
+// (the body of k_proj_window_splines and k_proj_window_splines_sets)
+__device__ __forceinline__ void proj_window_splines_body(const chomp_config& cfg,
+                                                         const ProjLayout& L,
+                                                         ProjDev* __restrict__ pd,
+                                                         double* __restrict__ tab) {
   extern __shared__ __align__(16) double sm_w[];       // 2 x 11 NWp doubles
   const int wave = threadIdx.x >> 6;
   spline_build_staged(tab + L.w_chi[wave], tab + L.w_wf[wave], L.NWp, tab + L.w_pp[wave],
@@ -632,6 +700,19 @@ __global__ __launch_bounds__(128) void k_proj_window_splines(chomp_config cfg, P
   pd->chi_min = cfg.window_precision > c0 ? cfg.window_precision : c0;   // :610-612
   pd->chi_max = me.comoving_distance(z_max);
   pd->D_zbar = me.growth_factor(pd->z_bar);                        // correlation.py:94
+}
+__global__ __launch_bounds__(128) void k_proj_window_splines(chomp_config cfg, ProjLayout L,
+                                                             ProjDev* __restrict__ pd,
+                                                             double* __restrict__ tab) {
+  proj_window_splines_body(cfg, L, pd, tab);
+}
+// ... with the set axis: grid (1, 1, n_set), block 128 -- the single-block kernel of a set-up,
+// one block per set here.
+__global__ __launch_bounds__(128) void k_proj_window_splines_sets(chomp_config cfg, ProjLayout L,
+                                                                  ProjDev* __restrict__ pd,
+                                                                  double* __restrict__ tab,
+                                                                  size_t stride) {
+  proj_window_splines_body(cfg, L, pd + blockIdx.z, tab + stride * blockIdx.z);
 }
 
 // LDS-resident view of everything a projection integrand needs.
@@ -675,12 +756,13 @@ struct KernelIntegrand {
 };
 
 // grid NKT, block 256: one kernel knot per block.
-__global__ __launch_bounds__(256) void k_proj_kernel_knots(chomp_config cfg, ProjLayout L,
-                                                           const ProjDev* __restrict__ pdg,
-                                                           double* __restrict__ tab,
-                                                           const BesselTab* __restrict__ bess_g,
-                                                           const double* __restrict__ ln_in,
-                                                           double* __restrict__ out) {
+// (the body of k_proj_kernel_knots and k_proj_kernel_knots_sets)
+__device__ __forceinline__ void proj_kernel_knots_body(const chomp_config& cfg, const ProjLayout& L,
+                                                       const ProjDev* __restrict__ pdg,
+                                                       double* __restrict__ tab,
+                                                       const BesselTab* __restrict__ bess_g,
+                                                       const double* __restrict__ ln_in,
+                                                       double* __restrict__ out) {
   // ln_in == nullptr: the 50 knots of the spline table (Kernel._initialize_spline);
   // otherwise Kernel.raw_kernel at the caller's ln(k theta), results into `out`.
   extern __shared__ __align__(16) double sm[];
@@ -719,10 +801,36 @@ __global__ __launch_bounds__(256) void k_proj_kernel_knots(chomp_config cfg, Pro
     }
   }
 }
+__global__ __launch_bounds__(256) void k_proj_kernel_knots(chomp_config cfg, ProjLayout L,
+                                                           const ProjDev* __restrict__ pdg,
+                                                           double* __restrict__ tab,
+                                                           const BesselTab* __restrict__ bess_g,
+                                                           const double* __restrict__ ln_in,
+                                                           double* __restrict__ out) {
+  proj_kernel_knots_body(cfg, L, pdg, tab, bess_g, ln_in, out);
+}
+// ... with the set axis: grid (NKT, 1, n_set), block 256; the knots of the spline tables only.
+__global__ __launch_bounds__(256) void k_proj_kernel_knots_sets(chomp_config cfg, ProjLayout L,
+                                                                const ProjDev* __restrict__ pdg,
+                                                                double* __restrict__ tab,
+                                                                const BesselTab* __restrict__ bess_g,
+                                                                size_t stride) {
+  proj_kernel_knots_body(cfg, L, pdg + blockIdx.z, tab + stride * blockIdx.z, bess_g, nullptr,
+                         nullptr);
+}
 
-__global__ void k_proj_kernel_spline(ProjLayout L, double* __restrict__ tab) {
+// (the body of k_proj_kernel_spline and k_proj_kernel_spline_sets)
+__device__ __forceinline__ void proj_kernel_spline_body(const ProjLayout& L,
+                                                        double* __restrict__ tab) {
   extern __shared__ __align__(16) double sm_k[];       // 11 NKT doubles
   spline_build_staged(tab + L.k_ln, tab + L.k_arr, L.NKT, tab + L.k_pp, sm_k, threadIdx.x < 64);
+}
+__global__ void k_proj_kernel_spline(ProjLayout L, double* __restrict__ tab) {
+  proj_kernel_spline_body(L, tab);
+}
+// ... with the set axis: grid (1, 1, n_set), block 64.
+__global__ void k_proj_kernel_spline_sets(ProjLayout L, double* __restrict__ tab, size_t stride) {
+  proj_kernel_spline_body(L, tab + stride * blockIdx.z);
 }
 
 // Kernel.kernel(ln_ktheta), kernel.py:714-729 (uniform ln(k theta) knots).
@@ -846,6 +954,18 @@ __global__ __launch_bounds__(256) void k_wtheta_nodes_epochs(chomp_config cfg, T
   wth_nodes_body<HF, BAO>(cfg, HL, epochs, e0 + (int)blockIdx.y, htab, which, k_min, k_max, D_z, LT,
                           nodes + stride * blockIdx.y, blockIdx.x);
 }
+// ... with an epoch axis whose rows have their own growth factor (chomp_wtheta_sets: row
+// blockIdx.y is the epoch of one cosmology, D_z[blockIdx.y] the growth at its z_bar).
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256) void k_wtheta_nodes_sets(chomp_config cfg, TabLayout HL,
+                                                           const Epoch* __restrict__ epochs, int e0,
+                                                           const double* __restrict__ htab, int which,
+                                                           double k_min, double k_max,
+                                                           const double* __restrict__ D_z, int LT,
+                                                           double* __restrict__ nodes, size_t stride) {
+  wth_nodes_body<HF, BAO>(cfg, HL, epochs, e0 + (int)blockIdx.y, htab, which, k_min, k_max,
+                          D_z[blockIdx.y], LT, nodes + stride * blockIdx.y, blockIdx.x);
+}
 
 // correlation.py:270-275 from the node table (levels <= LT), directly beyond
 template <bool HF, bool BAO>
@@ -923,6 +1043,21 @@ __global__ __launch_bounds__(64 * kWthetaNW) void k_wtheta_epochs(
   wth_direct_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pd, ptab, k_min,
                            k_max, D_z, theta + blockIdx.x,
                            out + (size_t)blockIdx.y * gridDim.x + blockIdx.x,
+                           nodes + stride * blockIdx.y, LT);
+}
+// ... with an epoch axis whose rows have their own projection set (chomp_wtheta_sets): row
+// blockIdx.y integrates epoch e0 + blockIdx.y against pd[blockIdx.y] and its slab of tables,
+// `pstride` doubles after the previous set's, with growth D_z[blockIdx.y].
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(64 * kWthetaNW) void k_wtheta_sets(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, double k_min, double k_max,
+    const double* __restrict__ D_z, const double* __restrict__ theta, double* __restrict__ out,
+    const double* __restrict__ nodes, int LT, size_t stride) {
+  wth_direct_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pd + blockIdx.y,
+                           ptab + pstride * blockIdx.y, k_min, k_max, D_z[blockIdx.y],
+                           theta + blockIdx.x, out + (size_t)blockIdx.y * gridDim.x + blockIdx.x,
                            nodes + stride * blockIdx.y, LT);
 }
 
@@ -1311,6 +1446,19 @@ __global__ __launch_bounds__(256) void k_wtheta_fast_epochs(
   wth_fast_body(cfg, L, pd, ptab, k_min, k_max, theta + blockIdx.x,
                 out + (size_t)blockIdx.y * gridDim.x + blockIdx.x, nodes + off, rec + off,
                 segtot + off, LT, nseg);
+}
+// ... with an epoch axis whose rows have their own projection set (chomp_wtheta_sets): row
+// blockIdx.y reads the kernel spline of set blockIdx.y (pd[blockIdx.y], its slab `pstride`
+// doubles after the previous one).  The sets share the ln(k theta) range, so nseg is one number.
+__global__ __launch_bounds__(256) void k_wtheta_fast_sets(
+    chomp_config cfg, ProjLayout L, const ProjDev* __restrict__ pd, const double* __restrict__ ptab,
+    size_t pstride, double k_min, double k_max, const double* __restrict__ theta,
+    double* __restrict__ out, const double* __restrict__ nodes, const double* __restrict__ rec,
+    const double* __restrict__ segtot, int LT, int nseg, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  wth_fast_body(cfg, L, pd + blockIdx.y, ptab + pstride * blockIdx.y, k_min, k_max,
+                theta + blockIdx.x, out + (size_t)blockIdx.y * gridDim.x + blockIdx.x, nodes + off,
+                rec + off, segtot + off, LT, nseg);
 }
 
 // ---------------------------------------------------------------------------

@@ -88,17 +88,26 @@ class HaloGrid(object):
         self._z = numpy.ascontiguousarray(self.z, dtype=numpy.float64)
         self._delta_b = None          # per local epoch (power_mm_ssc); None: 0 everywhere
 
-    def set_parameters(self, cosmo=None, halo=None, hod=None, delta_b=None):
+    def set_parameters(self, cosmo=None, halo=None, hod=None, delta_b=None, z=None):
         """New parameters for this rank's epochs, taking effect at the next setup(): the step of
         an MCMC / design loop.  Each argument: None (keep), one dict, a list with one dict per
         local epoch (hod: HOD objects as well, see the class), or the packed ctypes array (Context.pack_*; cosmo also as a float64 array
         [n_local, 10]) -- packing once outside the loop keeps the host out of the step.
         delta_b: HaloSuperSampleCovariance's delta_b (power_mm_ssc), a scalar or one value per
-        local epoch; it alone needs no new set-up."""
+        local epoch; it alone needs no new set-up.
+        z: new redshifts of the local epochs (a scalar or one per local epoch), e.g. the z_bar a
+        projection finds for each point's cosmology."""
         import ctypes
         n = len(self.idx)
         if n == 0:
             return
+        if z is not None:
+            self.z = numpy.ascontiguousarray(
+                numpy.broadcast_to(numpy.asarray(z, dtype=numpy.float64), (n,))).copy()
+            self.z_all = self.z_all.copy()       # (the constructor may have kept the caller's array)
+            self.z_all[self.idx] = self.z
+            self._z = self.z
+            self._tables = 0
         if delta_b is not None:
             db = numpy.ascontiguousarray(
                 numpy.broadcast_to(numpy.asarray(delta_b, dtype=numpy.float64), (n,)))

@@ -346,6 +346,17 @@ class Kernel(object):
             self._info_ctx = ctx
         return ctx
 
+    def _setup_sets_on(self, ctx, cosmo_dicts):
+        """Stage one projection set-up of this kernel's windows, k theta range and order per
+        cosmology of `cosmo_dicts` on `ctx` (Context.kernel_setup_sets): what set_cosmology +
+        _setup_on would build point after point (kernel.py:657-676), as one batch beside the
+        context's single set-up.  This kernel's own cosmology, _done and _info are not touched."""
+        ctx.kernel_setup_sets(cosmo_dicts, self.cosmo.z_min, self.cosmo.z_max,
+                              self._ktheta[0], self._ktheta[1],
+                              self.window_function_a._struct(),
+                              self.window_function_b._struct(), self._order)
+        return ctx
+
     def _dev(self):
         if self._own is None:
             self._own = cosmology._context()

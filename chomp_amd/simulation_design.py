@@ -9,7 +9,8 @@ its spectra, the design is the native batch axis of the device library: every de
 point becomes one epoch of a HaloGrid and all of them are built and evaluated by the same
 kernel launches.  A design over HOD parameters of
 Correlation.correlation or CorrelationFourier.correlation is batched the same way, through the
-object's correlation_hods.
+object's correlation_hods; a design over cosmology parameters of Correlation.correlation through
+correlation_cosmologies, with run_design(batched="cosmology").
 """
 import copy
 import warnings
@@ -247,6 +248,55 @@ class SimulationDesign(object):
         self._warn_design_status(words, stacklevel=4)
         return pandas.DataFrame(numpy.asarray(out).T, columns=self.points.index)
 
+    def _cosmologies_design_scope(self):
+        """ChompScopeError unless this design is one Correlation.correlation_cosmologies serves:
+        exactly a Correlation, its `correlation` over an independent variable (theta), cosmology
+        parameters varying (HOD parameters may vary with them), no halo parameter, and the object
+        within correlation_cosmologies' own scope.  No device work."""
+        obj = self._input_object
+        why = None
+        if type(obj) is not correlation_mod.Correlation:
+            why = ("the object is a %s, not exactly a correlation.Correlation (C_l over cosmologies "
+                   "is not batched yet)" % type(obj).__name__)
+        elif self._method != "correlation":
+            why = "the method is %r, not 'correlation'" % (self._method,)
+        elif self._ind_var is None:
+            why = "no independent_var (theta) is given"
+        elif not self._vary_cosmology:
+            why = "no cosmology parameter varies"
+        elif self._vary_halo:
+            why = "a halo parameter varies ('alpha' names the halo profile's slope first)"
+        if why is not None:
+            raise _lib.ChompScopeError("the batched design over Correlation.correlation_cosmologies "
+                                       "does not serve this design: %s; use batched=False" % why)
+        obj._cosmologies_scope([])
+
+    def _run_batched_cosmologies(self):
+        """Every design point = one cosmology (and, when HOD parameters vary, one HOD) of one
+        correlation_cosmologies call: the loop of simulation_design.py:116-155 over
+        Correlation.set_cosmology (correlation.py:161-171) as one batch."""
+        real, rec = self._input_object, _Recorder()
+        self._cosmologies_design_scope()      # (ChompScopeError before anything is recorded)
+        cosmos, hods = [], []
+        self._input_object = rec
+        try:
+            for _, point in self.points.iterrows():
+                rec.cosmo = rec.halo = rec.hod = None
+                self._apply_point(point)
+                cosmos.append(rec.cosmo if rec.cosmo is not None
+                              else dict(real.halo.cosmo.cosmo_dict))
+                hods.append(_point_hod(real.halo.local_hod, rec.hod))
+        finally:
+            self._input_object = real
+        theta = numpy.asarray(self._ind_var, dtype=numpy.float64)
+        with warnings.catch_warnings():       # (raised below, naming the design point)
+            warnings.simplefilter("ignore", _lib.ChompAccuracyWarning)
+            warnings.simplefilter("ignore", _lib.ChompParityWarning)
+            out, words = real.correlation_cosmologies(
+                theta.ravel(), cosmos, hods=hods if self._vary_hod else None, with_status=True)
+        self._warn_design_status(words, stacklevel=4)
+        return pandas.DataFrame(numpy.asarray(out).T, columns=self.points.index)
+
     def run_design(self, batched=None, with_status=False):
         """simulation_design.py:140-155.  Returns a DataFrame with one column per design
         point holding the flattened output of the method.  batched=None picks the
@@ -261,9 +311,24 @@ class SimulationDesign(object):
         The batched path keeps the status word of every design point (chomp_get_status bits) in
         `self.design_status` (an int64 Series indexed like the design points) and raises them as
         warnings naming the point; with_status=True returns the pair (frame, design_status) --
-        the words are never mixed into the float frame, whose rows stay the method's output."""
+        the words are never mixed into the float frame, whose rows stay the method's output.
+
+        batched="cosmology" (opt-in; None and True never pick it) evaluates a design over
+        cosmology parameters -- HOD parameters optionally with them, no halo parameter -- of
+        exactly a Correlation, its `correlation` and an independent variable by ONE
+        Correlation.correlation_cosmologies call: one projection set-up and one halo epoch per
+        point.  Outside that scope it raises ChompScopeError with the reason."""
         if not self._initialized_design:
             self._init_design_points()
+        if isinstance(batched, str):
+            if batched != "cosmology":
+                raise ValueError("run_design: batched=%r (None, True, False or 'cosmology')" % (batched,))
+            self.design_status = None
+            self.design_values = self._run_batched_cosmologies()
+            self.values_frame = self.design_values
+            if with_status:
+                return self.design_values, self.design_status
+            return self.design_values
         if batched is None:
             batched = self._batched()
         self.design_status = None

@@ -678,6 +678,30 @@ int chomp_kernel_info(chomp_ctx* ctx, double* out);
 #define CHOMP_KTAB_LEVELS 9
 int chomp_kernel_table(chomp_ctx* ctx, int table, double* out, size_t n);
 
+/* The cosmology axis of the projection set-up.  A design or chain over cosmology calls
+ * Kernel.set_cosmology once per point (kernel.py:657-676, from Correlation.set_cosmology,
+ * correlation.py:161-171, in the loop of simulation_design.py:116-155): new MultiEpoch tables,
+ * windows, chi limits, z_bar and kernel knots each time.  chomp_kernel_setup_sets builds n_set
+ * such set-ups that differ in cosmology only -- windows, redshift distributions, k theta range
+ * and Bessel order are shared -- with the six launches of chomp_kernel_setup run once, on the
+ * context's stream.  The sets live beside the single set-up of chomp_kernel_setup, which (with
+ * the covariance, ssc and NG tables built on it) is left as it was; their buffers are kept
+ * across calls.  Set s holds, bit for bit, what chomp_kernel_setup(ctx, &cosmo[s], ...) builds.
+ * Validates what chomp_kernel_setup validates; in addition CHOMP_ERR_SCOPE, before anything is
+ * launched, for a CHOMP_DNDZ_PPOLY distribution and for any cosmology with w0/wa != -1/0 (both
+ * are set up by chomp_kernel_setup, one cosmology at a time), and CHOMP_ERR_ARG for n_set = 0 or
+ * n_set > CHOMP_KERNEL_SETS_MAX (callers work longer designs off in blocks of that size). */
+#define CHOMP_KERNEL_SETS_MAX 1024
+int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo /*[n_set]*/,
+                            double me_z_min, double me_z_max, double ktheta_min,
+                            double ktheta_max, const chomp_window* a, const chomp_window* b,
+                            int bessel_order);
+/* chomp_kernel_info of every set of the last chomp_kernel_setup_sets: out[s * CHOMP_KI_COUNT +
+ * CHOMP_KI_*], in ONE synchronising read-back.  CHOMP_ERR_STATE before any such set-up. */
+int chomp_kernel_info_sets(chomp_ctx* ctx, double* out /*[n_set * CHOMP_KI_COUNT]*/);
+/* chomp_kernel_table of set `set` (CHOMP_ERR_ARG beyond the last set-up's sets). */
+int chomp_kernel_table_set(chomp_ctx* ctx, size_t set, int table, double* out, size_t n);
+
 /* Kernel.raw_kernel(ln_ktheta) (kernel.py:678-704): the projection integral itself, not
  * its 50-knot spline. */
 int chomp_kernel_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n,
@@ -710,6 +734,19 @@ int chomp_wtheta(chomp_ctx* ctx, int which, size_t epoch, double k_min,
 int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
                         double k_max, double D_z, const double* theta, size_t n, double* out,
                         int mem);
+/* Correlation.correlation(theta) over cosmologies: epoch epoch0 + e of the context is integrated
+ * against projection set e of the last chomp_kernel_setup_sets with growth D_z[e] (a HOST array
+ * whatever `mem` says; the caller has moved epoch e to set e's z_bar, correlation.py:161-171):
+ * out[e * n + i] = what chomp_wtheta(ctx, which, epoch0 + e, k_min, k_max, D_z[e], theta, n, ...)
+ * returns at i after chomp_kernel_setup with cosmo[e], bit for bit -- both run the same bodies on
+ * the same inputs.  The scope, routes and chunking of chomp_wtheta_epochs (fp64 only;
+ * CHOMP_ERR_SCOPE for HaloFit codes, extrapolated halo-model spectra and the wiggle transfer
+ * function; CHOMP_TUNE_WTHETA_EPOCH_CHUNK).  n_epoch must be the number of sets
+ * (CHOMP_ERR_ARG); CHOMP_ERR_STATE before any chomp_kernel_setup_sets.  C_l has no such call yet:
+ * the chi-only node table of chomp_cell_epochs is per set. */
+int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
+                      double k_max, const double* D_z /*[n_epoch], host*/, const double* theta,
+                      size_t n, double* out, int mem);
 /* Gaussian covariance of w(theta), Covariance(corr, corr) with nongaussian_cov=False.
  *
  * chomp_covariance_table replaces Covariance._initialize_halo_splines (covariance.py:455-543,
