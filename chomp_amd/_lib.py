@@ -129,7 +129,8 @@ EXPORTS = [
     "chomp_cell", "chomp_cell_epochs",
     "chomp_kernel_setup_sets", "chomp_kernel_info_sets", "chomp_kernel_table_set",
     "chomp_wtheta_sets",
-    "chomp_set_precision", "chomp_xi3d", "chomp_spline_eval", "chomp_hod_stats",
+    "chomp_set_precision", "chomp_xi3d", "chomp_xi3d_epochs", "chomp_spline_eval",
+    "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
     "chomp_covariance_table", "chomp_covariance_gaussian",
     "chomp_covariance_cross_stage", "chomp_covariance_table_cross",
@@ -475,6 +476,7 @@ def lib():
         L.chomp_kernel_ng_eval.argtypes = [vp, vp, sz, vp]
         L.chomp_covariance_ng.argtypes = [vp, d, vp, sz, d, d, vp, sz, vp, vp, vp]
         L.chomp_xi3d.argtypes = [vp, i, sz, d, d, vp, sz, vp, i]
+        L.chomp_xi3d_epochs.argtypes = [vp, i, sz, sz, d, d, vp, sz, vp, i]
         L.chomp_spline_eval.argtypes = [vp, vp, vp, sz, vp, sz, i, vp]
         for name in EXPORTS:
             if name not in ("chomp_default_config", "chomp_ctx_destroy",
@@ -1400,6 +1402,14 @@ class Context(object):
     def xi3d(self, which, epoch, k_min, k_max, r):
         return self._run(self._L.chomp_xi3d, [r], _elementwise(
             int(which), epoch, float(k_min), float(k_max)))[0]
+
+    def xi3d_epochs(self, which, epoch0, n_epoch, k_min, k_max, r):
+        """xi(r) of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (chomp_xi3d_epochs):
+        [n_epoch, r.size], row e what xi3d(which, epoch0 + e, ...) returns, bit for bit.  Needs no
+        kernel set-up."""
+        return self._run(self._L.chomp_xi3d_epochs, [r], lambda mem, new, rr: (
+            int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), rr,
+            _numel(rr), new((int(n_epoch), _numel(rr))), mem))[0]
 
     def spline_eval(self, xk, yk, x, deriv=0):
         """Not-a-knot cubic spline through (xk, yk) at x (FITPACK k=3, s=0); deriv=1: its

@@ -196,9 +196,14 @@ class Correlation(object):
         ChompScopeError (before any launch): a halo that is not exactly halo.Halo, a
         general_profile halo, extrapolation, with_bao, a halo whose profile and mass-function
         dictionaries differ (after set_halo), an HOD of another class."""
+        return self._hods_batch(theta_rad, self._hods_scope(hods), with_status)
+
+    def _hods_batch(self, theta_rad, objs, with_status):
+        """correlation_hods behind its scope check (objs: _hods_scope's HOD objects): the kept
+        grid, the set-up, _hods_evaluate and the status words.  Correlation3d.raw_correlation_hods
+        shares it (theta_rad then being r)."""
         import warnings
         from . import grid
-        objs = self._hods_scope(hods)
         n_hod = len(objs)
         th = theta_rad if _lib._is_torch(theta_rad) else numpy.asarray(theta_rad, dtype=numpy.float64)
         flat = th.reshape(-1) if _lib._is_torch(th) else numpy.ascontiguousarray(th).ravel()
@@ -222,7 +227,7 @@ class Correlation(object):
             self._hods_grid = (key, hg)
         else:
             hg.set_parameters(hod=objs)
-        self.kernel._setup_on(hg.ctx)
+        self._hods_stage(hg.ctx)
         hg.setup(self._power_name)
         out = self._hods_evaluate(hg.ctx, h._power_code(code), n_hod, flat)
         words = hg.status()                    # (synchronises: the words belong to this result)
@@ -234,8 +239,13 @@ class Correlation(object):
                             if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
                             else _lib.ChompAccuracyWarning)
                 warnings.warn("HOD %d: %s" % (i, "; ".join(_lib.describe_status(w))), category,
-                              stacklevel=2)
+                              stacklevel=3)
         return (out, words) if with_status else out
+
+    def _hods_stage(self, ctx):
+        """What the batch needs on the grid's context besides the halo epochs: the Kernel's
+        projection tables (queued before the halo set-up, on the context's side stream)."""
+        self.kernel._setup_on(ctx)
 
     def _hods_evaluate(self, ctx, code, n_hod, flat):
         """The one call of correlation_hods that knows the observable: [n_hod, flat.size] of the
@@ -486,6 +496,127 @@ class Correlation3d(Correlation):
         out = ctx.xi3d(code, 0, self._k_lim[0], self._k_lim[1],
                        numpy.ascontiguousarray(ra).ravel())
         return float(out[0]) if ra.ndim == 0 else out.reshape(ra.shape)
+
+    # -- the batches over HODs and cosmologies -----------------------------------
+    # They are defined on raw_correlation: the reference never resets initialized_spline after
+    # set_hod, so correlation(r) in a loop keeps returning the first point's spline.
+    _hods_export = "chomp_xi3d_epochs"
+    _HODS_LOOP = "set_hod / set_hod_object + raw_correlation"
+    _COSMOLOGIES_LOOP = "fresh Correlation3d objects (+ set_hod_object) + raw_correlation"
+
+    @staticmethod
+    def _table_scope(who, loop):
+        """Context.xi3d_epochs integrates from a node table of level 20 and has no route beyond."""
+        from . import defaults
+        if defaults.default_precision["divmax"] > 20:
+            raise _lib.ChompScopeError(
+                "%s: default_precision['divmax'] = %d exceeds the node table of %s (level 20); "
+                "use the loop %s" % (who, defaults.default_precision["divmax"],
+                                     Correlation3d._hods_export, loop))
+
+    def _hods_stage(self, ctx):
+        """xi(r) needs no projection set-up."""
+
+    def _hods_evaluate(self, ctx, code, n_hod, flat):
+        return ctx.xi3d_epochs(code, 0, n_hod, self._k_lim[0], self._k_lim[1], flat)
+
+    def raw_correlation_hods(self, r, hods, with_status=False):
+        """xi(r) for many HODs in one call: the array [len(hods), r.size] whose row i is what
+        set_hod_object(<hods[i] as an object>) followed by raw_correlation(r) returns on a fresh
+        Halo, bit for bit.  hods, the kept grid.HaloGrid (one epoch per HOD at the halo's
+        redshift) and its key, the status words (`self.hods_status`, warnings naming "HOD i",
+        with_status=True) and the ChompScopeErrors are those of Correlation.correlation_hods;
+        the evaluating call is Context.xi3d_epochs: the r-independent factor of the integrand
+        once per HOD on the Romberg nodes, then one launch over (r, HOD).  A
+        default_precision['divmax'] above 20 is refused as well.  A torch cuda r returns a
+        tensor.  This object's own halo and HOD are not touched."""
+        who = "raw_correlation_hods"
+        objs = self._hods_scope(hods, who=who, loop=self._HODS_LOOP)
+        self._table_scope(who, self._HODS_LOOP)
+        if not _lib._is_torch(r) and numpy.asarray(r).size == 0:
+            self.hods_status = numpy.zeros(len(objs), dtype=numpy.uint32)
+            out = numpy.empty((len(objs), 0))
+            return (out, self.hods_status) if with_status else out
+        return self._hods_batch(r, objs, with_status)
+
+    def raw_correlation_cosmologies(self, r, cosmo_dicts, hods=None, with_status=False):
+        """xi(r) for many cosmologies in one call: the array [len(cosmo_dicts), r.size] whose row
+        i is what a fresh Correlation3d(..., redshift=z, input_halo=Halo(z, <hod>,
+        SingleEpoch(z, cosmo_dicts[i])), powSpec=...) of this object's redshift, k range, halo
+        parameters, mass function and HOD returns from raw_correlation(r), bit for bit.  With
+        `hods` (one per point, as in raw_correlation_hods) point i has hods[i].  w0-wa
+        cosmologies are in scope.
+
+        One grid.HaloGrid epoch per point at the halo's redshift (xi(r) has no projection, hence
+        no z_bar, no projection sets and no block limit) and one Context.xi3d_epochs call.  The
+        grid is kept, keyed by the number of points, the halo dictionary, the mass function and
+        the defaults a context snapshots.  The status word of every point is read with the
+        result, raised as a warning naming "cosmology i", kept in `self.cosmologies_status`
+        and returned as the second element with with_status=True.  A torch cuda r returns a
+        tensor.  This object's own halo, cosmology and HOD are not touched.
+
+        ChompScopeError (before any launch): everything raw_correlation_hods refuses.
+        ValueError: `hods` of another length than cosmo_dicts."""
+        import warnings
+        from . import defaults
+        from . import grid
+        who = "raw_correlation_cosmologies"
+        cosmo_dicts = [dict(c) for c in cosmo_dicts]
+        objs = self._hods_scope(hods, who=who, loop=self._COSMOLOGIES_LOOP)
+        self._table_scope(who, self._COSMOLOGIES_LOOP)
+        if hods is not None and len(objs) != len(cosmo_dicts):
+            raise ValueError("raw_correlation_cosmologies: %d hods for %d cosmologies"
+                             % (len(objs), len(cosmo_dicts)))
+        n_pt = len(cosmo_dicts)
+        ra = r if _lib._is_torch(r) else numpy.asarray(r, dtype=numpy.float64)
+        flat = ra.reshape(-1) if _lib._is_torch(ra) else numpy.ascontiguousarray(ra).ravel()
+        n_r = flat.numel() if _lib._is_torch(flat) else flat.size
+        self.cosmologies_status = numpy.zeros(n_pt, dtype=numpy.uint32)
+        if n_pt == 0 or n_r == 0:
+            out = flat.new_empty((n_pt, n_r)) if _lib._is_torch(flat) else numpy.empty((n_pt, n_r))
+            return (out, self.cosmologies_status) if with_status else out
+        h = self.halo
+        code, _ = _POWER[self._power_name]
+        kind = "tinker" if getattr(h.mass, "_kind", 0) else "st"
+        point_hods = list(objs) if hods is not None else h.local_hod
+        # (a context snapshots defaults.default_limits / default_precision when it is created)
+        key = (n_pt, tuple(sorted(h.mass.halo_dict.items())), kind,
+               tuple(sorted(defaults.default_limits.items())),
+               tuple(sorted(defaults.default_precision.items())))
+        kept = getattr(self, "_cosmologies_grid", (None, None))
+        hg = kept[1] if kept[0] == key else None
+        z = numpy.full(n_pt, float(h.get_redshift()))
+        if hg is None:
+            hg = grid.HaloGrid(z, cosmo_dict=cosmo_dicts, halo_dict=dict(h.mass.halo_dict),
+                               hod_dict=point_hods, mass_function=kind)
+            self._cosmologies_grid = (key, hg)
+        else:
+            hg.set_parameters(cosmo=cosmo_dicts, z=z, hod=point_hods)
+        hg.setup(self._power_name)
+        out = hg.ctx.xi3d_epochs(h._power_code(code), 0, n_pt, self._k_lim[0], self._k_lim[1], flat)
+        words = hg.status()                    # (synchronises: the words belong to this result)
+        self.cosmologies_status = words
+        for i, w in enumerate(words):
+            w = int(w)
+            if w:
+                category = (_lib.ChompParityWarning
+                            if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
+                            else _lib.ChompAccuracyWarning)
+                warnings.warn("cosmology %d: %s" % (i, "; ".join(_lib.describe_status(w))), category,
+                              stacklevel=2)
+        return (out, words) if with_status else out
+
+    def correlation_hods(self, r, hods, with_status=False):
+        """Correlation's batch of w(theta) does not apply to xi(r); ChompScopeError."""
+        raise _lib.ChompScopeError(
+            "Correlation3d.correlation_hods: xi(r) is batched on raw_correlation; use "
+            "raw_correlation_hods (or raw_correlation_cosmologies for a batch over cosmologies)")
+
+    def correlation_cosmologies(self, r, cosmo_dicts, hods=None, with_status=False):
+        """Correlation's batch of w(theta) does not apply to xi(r); ChompScopeError."""
+        raise _lib.ChompScopeError(
+            "Correlation3d.correlation_cosmologies: xi(r) is batched on raw_correlation; use "
+            "raw_correlation_cosmologies (or raw_correlation_hods for a batch over HODs)")
 
     def correlation(self, r):
         if not self.initialized_spline:

@@ -643,6 +643,61 @@ int chomp_xi3d(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_m
   return st.finish();
 }
 
+// xi(r) of n_epoch epochs that share the k range (an HOD or cosmology design or chain): the node
+// table of chomp_wtheta_epochs with D_z = 1.0 -- the r-independent factor of the integrand, once
+// per epoch -- and one Romberg launch with an epoch axis that reads it, the epochs worked off in
+// chunks of kWthEpochChunk (layout: chomp_proj_kernels.h, k_xi3d_epochs).  No projection set-up.
+int chomp_xi3d_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
+                      double k_max, const double* r, size_t n, double* out, int mem) {
+  StageRange range_(ctx, "chomp:xi3d_epochs");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!r || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "xi3d_epochs: bad args");
+  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "xi3d_epochs: n * n_epoch too large");
+  Staging st(ctx, mem, "xi3d_epochs");
+  if (st.rc) return st.rc;
+  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
+  if (ctx->precision != CHOMP_PREC_F64)
+    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: fp64 only (the narrowed precision modes belong to chomp_xi3d)");
+  if (which & CHOMP_P_HALOFIT)
+    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: HaloFit spectra are evaluated by chomp_xi3d");
+  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
+    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: extrapolated spectra are evaluated by chomp_xi3d");
+  if (ctx->with_bao)
+    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: the wiggle transfer function is evaluated by chomp_xi3d");
+  if (ctx->cfg.divmax > kWthetaTabLevel)
+    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: divmax beyond the node table (level 20) is evaluated by chomp_xi3d");
+  int rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  if (!(k_min > 0.0) || !(k_max > k_min)) return fail(ctx, CHOMP_ERR_ARG, "xi3d_epochs: k range");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* din;
+  double* dout;
+  st.in(r, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = st.place();
+  if (rc) return rc;
+  const int LT = ctx->cfg.divmax;                            // (<= kWthetaTabLevel: every level)
+  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const size_t stride = wth_epoch_stride(LT, 1, false);
+  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
+                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
+  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
+  if (rc) return rc;
+  const unsigned gnodes = (unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
+  for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {          // (the scratch is reused in stream order)
+    const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+    hipLaunchKernelGGL((k_wtheta_nodes_epochs<false, false>), dim3(gnodes, E), dim3(256),
+                       (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                       ctx->L, ctx->d_epochs, (int)(epoch0 + c0), ctx->d_tab, which, k_min, k_max,
+                       1.0, LT, ctx->d_wnodes, stride);
+    hipLaunchKernelGGL(k_xi3d_epochs, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
+                       ctx->cfg.global_precision, ctx->cfg.corr_precision, ctx->cfg.divmax,
+                       ctx->d_j0, k_min, k_max, din, dout + c0 * n, ctx->d_wnodes, stride);
+  }
+  return st.finish();
+}
+
 int chomp_spline_eval(chomp_ctx* ctx, const double* xk, const double* yk, size_t nk,
                       const double* x, size_t n, int deriv, double* out) {
   if (!ctx || !xk || !yk || !x || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "spline_eval: bad args");

@@ -1704,6 +1704,48 @@ __global__ __launch_bounds__(256) void k_xi3d(chomp_config cfg, TabLayout HL,
   if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
+// The epoch axis (chomp_xi3d_epochs: one xi(r) per HOD or cosmology of a design or chain).  Every
+// separation integrates over the same ln k range, so the r-independent factor k^2/(2 pi) P(k) of
+// the integrand is the node table of k_wtheta_nodes_epochs with D_z = 1.0 (its last factor is
+// then 1.0 / (1.0 * 1.0) = 1.0 and the product by it exact): one table per epoch at a fixed
+// stride in the context's w(theta) work buffer, the epochs worked off in chunks of
+// kWthEpochChunk.  Per node a block then only reads the table and evaluates J0(k r) -- no
+// PowerEval, no epoch record, no knot splines.  Every level lies within the table (the entry point
+// refuses divmax > kWthetaTabLevel).
+struct Xi3dTabIntegrand {
+  const double* nodes;
+  const BesselTab* B;
+  double r;
+  // ln_k: romberg_group's node (the node arithmetic wth_nodes_body tabulated with)
+  __device__ __forceinline__ void operator()(double ln_k, double (&out)[1], int lev, long j) const {
+    const long idx = lev == 0 ? j : 1 + (1L << (lev - 1)) + j;
+    const double k = exp(ln_k);
+    out[0] = nodes[idx] * bessel_j<0>(k * r, *B);
+  }
+};
+
+// grid (n_r, E), block 256: block (i, y) integrates separation r[i] of the epoch whose table is
+// row y of `nodes` into out[y * n_r + i] -- the sums of k_xi3d in its order (romberg_group<4, 1>
+// on 256 threads), so bit for bit its value.  The separation is the fast grid axis: the blocks
+// that read one table run together.  102 VGPRs, no scratch, 2 KB of LDS (tools/kernel_regs.py;
+// k_xi3d: 153): four waves per SIMD, four blocks per CU, which the second bound keeps.
+__global__ __launch_bounds__(256, 4) void k_xi3d_epochs(double tol, double rtol, int divmax,
+                                                     const BesselTab* __restrict__ bess_g,
+                                                     double k_min, double k_max,
+                                                     const double* __restrict__ r,
+                                                     double* __restrict__ out,
+                                                     const double* __restrict__ nodes,
+                                                     size_t stride) {
+  __shared__ BesselTab B;
+  __shared__ double red[romberg_scratch<4, 2>()];
+  copy_doubles(reinterpret_cast<double*>(&B), reinterpret_cast<const double*>(bess_g),
+               (int)(sizeof(BesselTab) / sizeof(double)));
+  __syncthreads();
+  Xi3dTabIntegrand f{nodes + stride * blockIdx.y, &B, r[blockIdx.x]};
+  const RombergOut<1> v = romberg_group<4, 1>(f, log(k_min), log(k_max), tol, rtol, divmax, red);
+  if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = v.value[0];
+}
+
 // Not-a-knot cubic spline through (xk, yk) evaluated at x: one block; c: 4 (nk - 1)
 // doubles, w: 2 nk doubles of scratch.
 __global__ void k_spline_eval(const double* __restrict__ xk, const double* __restrict__ yk, int nk,

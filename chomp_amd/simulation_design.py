@@ -10,7 +10,9 @@ point becomes one epoch of a HaloGrid and all of them are built and evaluated by
 kernel launches.  A design over HOD parameters of
 Correlation.correlation or CorrelationFourier.correlation is batched the same way, through the
 object's correlation_hods; a design over cosmology parameters of Correlation.correlation through
-correlation_cosmologies, with run_design(batched="cosmology").
+correlation_cosmologies, with run_design(batched="cosmology").  Designs over HOD or cosmology
+parameters of Correlation3d.raw_correlation are batched on request (batched=True / "cosmology"),
+through raw_correlation_hods / raw_correlation_cosmologies.
 """
 import copy
 import warnings
@@ -297,6 +299,62 @@ class SimulationDesign(object):
         self._warn_design_status(words, stacklevel=4)
         return pandas.DataFrame(numpy.asarray(out).T, columns=self.points.index)
 
+    def _xi_design_scope(self, cosmology):
+        """ChompScopeError unless this design is one Correlation3d.raw_correlation_hods
+        (cosmology=False: only HOD parameters vary) or raw_correlation_cosmologies
+        (cosmology=True: cosmology parameters vary, HOD parameters optionally with them) serves:
+        the method 'raw_correlation' over an independent variable (r), no halo parameter, and the
+        object within the batch's own scope.  No device work."""
+        obj = self._input_object
+        name = "raw_correlation_cosmologies" if cosmology else "raw_correlation_hods"
+        why = None
+        if self._method != "raw_correlation":
+            why = ("the method is %r, not 'raw_correlation' (the reference's spline "
+                   "correlation(r) keeps the first point's values in a loop)" % (self._method,))
+        elif self._ind_var is None:
+            why = "no independent_var (r) is given"
+        elif cosmology and not self._vary_cosmology:
+            why = "no cosmology parameter varies"
+        elif not cosmology and not self._vary_hod:
+            why = "no HOD parameter varies"
+        elif not cosmology and self._vary_cosmology:
+            why = "a cosmology parameter varies (batched='cosmology' serves that)"
+        elif self._vary_halo:
+            why = "a halo parameter varies ('alpha' names the halo profile's slope first)"
+        if why is not None:
+            raise _lib.ChompScopeError("the batched design over Correlation3d.%s does not serve "
+                                       "this design: %s; use batched=False" % (name, why))
+        obj._hods_scope(who=name, loop=obj._COSMOLOGIES_LOOP if cosmology else obj._HODS_LOOP)
+
+    def _run_batched_xi(self, cosmology):
+        """Every design point = one HOD of one Correlation3d.raw_correlation_hods call, or one
+        cosmology (and, when HOD parameters vary, one HOD) of one raw_correlation_cosmologies
+        call: the loop over the object's setters and raw_correlation(r) as one batch."""
+        real, rec = self._input_object, _Recorder()
+        self._xi_design_scope(cosmology)      # (ChompScopeError before anything is recorded)
+        cosmos, hods = [], []
+        self._input_object = rec
+        try:
+            for _, point in self.points.iterrows():
+                rec.cosmo = rec.halo = rec.hod = None
+                self._apply_point(point)
+                cosmos.append(rec.cosmo if rec.cosmo is not None
+                              else dict(real.halo.cosmo.cosmo_dict))
+                hods.append(_point_hod(real.halo.local_hod, rec.hod))
+        finally:
+            self._input_object = real
+        r = numpy.asarray(self._ind_var, dtype=numpy.float64)
+        with warnings.catch_warnings():       # (raised below, naming the design point)
+            warnings.simplefilter("ignore", _lib.ChompAccuracyWarning)
+            warnings.simplefilter("ignore", _lib.ChompParityWarning)
+            if cosmology:
+                out, words = real.raw_correlation_cosmologies(
+                    r.ravel(), cosmos, hods=hods if self._vary_hod else None, with_status=True)
+            else:
+                out, words = real.raw_correlation_hods(r.ravel(), hods, with_status=True)
+        self._warn_design_status(words, stacklevel=4)
+        return pandas.DataFrame(numpy.asarray(out).T, columns=self.points.index)
+
     def run_design(self, batched=None, with_status=False):
         """simulation_design.py:140-155.  Returns a DataFrame with one column per design
         point holding the flattened output of the method.  batched=None picks the
@@ -317,14 +375,22 @@ class SimulationDesign(object):
         cosmology parameters -- HOD parameters optionally with them, no halo parameter -- of
         exactly a Correlation, its `correlation` and an independent variable by ONE
         Correlation.correlation_cosmologies call: one projection set-up and one halo epoch per
-        point.  Outside that scope it raises ChompScopeError with the reason."""
+        point.  Outside that scope it raises ChompScopeError with the reason.
+
+        An object that is exactly a Correlation3d is batched on request only (batched=None keeps
+        its loop): with the method 'raw_correlation' and an independent variable (r),
+        batched=True evaluates a design over HOD parameters by one raw_correlation_hods call and
+        batched="cosmology" a design over cosmology (and HOD) parameters by one
+        raw_correlation_cosmologies call; ChompScopeError outside that scope."""
         if not self._initialized_design:
             self._init_design_points()
+        xi = type(self._input_object) is correlation_mod.Correlation3d
         if isinstance(batched, str):
             if batched != "cosmology":
                 raise ValueError("run_design: batched=%r (None, True, False or 'cosmology')" % (batched,))
             self.design_status = None
-            self.design_values = self._run_batched_cosmologies()
+            self.design_values = (self._run_batched_xi(True) if xi
+                                  else self._run_batched_cosmologies())
             self.values_frame = self.design_values
             if with_status:
                 return self.design_values, self.design_status
@@ -332,7 +398,9 @@ class SimulationDesign(object):
         if batched is None:
             batched = self._batched()
         self.design_status = None
-        if batched:
+        if batched and xi:
+            self.design_values = self._run_batched_xi(False)
+        elif batched:
             route = self._batched_route()
             if route is None:                  # (forced)
                 route = ("correlation" if isinstance(self._input_object, correlation_mod.Correlation)

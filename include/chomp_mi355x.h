@@ -1058,6 +1058,18 @@ int chomp_hod_stats(chomp_ctx* ctx, size_t epoch0, size_t n, double* out);
  * wavefront-group per r; P is `which` of halo epoch `epoch`. */
 int chomp_xi3d(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_max,
                const double* r, size_t n, double* out, int mem);
+/* xi(r) of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (the loop of set_hod or of fresh
+ * halos + raw_correlation over an HOD or cosmology design): out[e * n + i] is what
+ * chomp_xi3d(ctx, which, epoch0 + e, k_min, k_max, r, n, ...) returns at i, bit for bit.  The
+ * r-independent factor k^2/(2 pi) P(k) of the integrand is tabulated once per epoch on the Romberg
+ * nodes (the node table of chomp_wtheta_epochs with D_z = 1, in its work buffer: 8 MiB per epoch
+ * of a chunk at divmax = 20; CHOMP_TUNE_WTHETA_EPOCH_CHUNK sets the chunk), and one launch with
+ * an epoch axis integrates it against J0(k r).  Needs no chomp_kernel_setup.  r / out: host or
+ * device arrays (mem).  CHOMP_ERR_SCOPE (chomp_xi3d serves these): a narrowed precision mode, a
+ * HaloFit code, CHOMP_P_EXTRAPOLATE on a halo-model spectrum, a context with the wiggle
+ * transfer function, a context whose divmax exceeds 20 (the level of the node table). */
+int chomp_xi3d_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
+                      double k_max, const double* r, size_t n, double* out, int mem);
 /* scipy InterpolatedUnivariateSpline(xk, yk)(x) (k = 3, not-a-knot), host buffers: the
  * 50-knot xi(r) spline of Correlation3d.compute_correlation / correlation
  * (correlation.py:459-468, 501-510).  x outside [xk[0], xk[nk-1]] extrapolates the end
