@@ -56,7 +56,7 @@ KI = {name: i for i, name in enumerate([
     "z_bar", "chi_min", "chi_max", "z_min", "z_max", "D_zbar", "norm_a", "norm_b",
     "wa_chi_min", "wa_chi_max", "wb_chi_min", "wb_chi_max", "j_limit"])}
 KI_COUNT = 13
-KERNEL_SETS_MAX = 1024      # CHOMP_KERNEL_SETS_MAX: the sets of one chomp_kernel_setup_sets
+KERNEL_SETS_MAX = 1024      # CHOMP_KERNEL_SETS_MAX: the sets of one chomp_kernel_setup_sets / _pairs
 ME = {"chi_of_z": 0, "z_of_chi": 1, "growth_of_z": 2}
 KTAB = {"ln_ktheta": 0, "kernel": 1, "wa_chi": 2, "wa": 3, "wb_chi": 4, "wb": 5,
         "me_z": 6, "me_chi": 7, "me_growth": 8, "levels": 9}
@@ -128,7 +128,7 @@ EXPORTS = [
     "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_wtheta_epochs",
     "chomp_cell", "chomp_cell_epochs",
     "chomp_kernel_setup_sets", "chomp_kernel_info_sets", "chomp_kernel_table_set",
-    "chomp_wtheta_sets",
+    "chomp_wtheta_sets", "chomp_kernel_setup_pairs", "chomp_cell_sets",
     "chomp_set_precision", "chomp_xi3d", "chomp_xi3d_epochs", "chomp_spline_eval",
     "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
@@ -424,6 +424,9 @@ def lib():
         L.chomp_wtheta_sets.argtypes = [vp, i, sz, sz, d, d, vp, vp, sz, vp, i]
         L.chomp_cell.argtypes = [vp, i, sz, d, vp, sz, vp, i]
         L.chomp_cell_epochs.argtypes = [vp, i, sz, sz, d, vp, sz, vp, i]
+        L.chomp_kernel_setup_pairs.argtypes = [vp, sz, ctypes.POINTER(Cosmo), c_double_p, c_double_p,
+                                               d, d, ctypes.POINTER(Window), ctypes.POINTER(Window), i]
+        L.chomp_cell_sets.argtypes = [vp, i, sz, sz, vp, vp, sz, vp, i]
         L.chomp_wtheta_cell.argtypes = [vp, i, sz, d, d, d, vp, sz, vp, vp, sz, vp, i]
         L.chomp_set_precision.argtypes = [vp, i]
         L.chomp_hod_stats.argtypes = [vp, sz, sz, c_double_p]
@@ -1101,6 +1104,32 @@ class Context(object):
             ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)))
         self._n_sets = len(arr)
 
+    def kernel_setup_pairs(self, cosmo_dicts, me_z_min, me_z_max, ktheta_min, ktheta_max,
+                           windows_a, windows_b, bessel_order):
+        """One projection set-up per kernel (chomp_kernel_setup_pairs): set s is what
+        kernel_setup(cosmo_dicts[s], me_z_min[s], me_z_max[s], ktheta_min, ktheta_max,
+        windows_a[s], windows_b[s], bessel_order) builds, bit for bit.  cosmo_dicts as in
+        kernel_setup_sets; windows_a / windows_b lists of Window structs.  The sets replace those of
+        the last kernel_setup_sets / kernel_setup_pairs; the single set-up stays as it is.
+        ValueError for lists of other lengths and for more than KERNEL_SETS_MAX sets;
+        ChompScopeError, naming the set, for a w0-wa cosmology or a tabulated distribution."""
+        arr = (cosmo_dicts if isinstance(cosmo_dicts, ctypes.Array)
+               else self.pack_cosmo(cosmo_dicts, len(cosmo_dicts)))
+        n = len(arr)
+        z0 = numpy.ascontiguousarray(me_z_min, dtype=numpy.float64).ravel()
+        z1 = numpy.ascontiguousarray(me_z_max, dtype=numpy.float64).ravel()
+        if not (z0.size == z1.size == len(windows_a) == len(windows_b) == n):
+            raise ValueError("kernel_setup_pairs: one cosmology, MultiEpoch range and window pair "
+                             "per set")
+        # (the structs are copied into two contiguous arrays; a tabulated distribution's arrays
+        #  stay alive in the caller's structs for the duration of the call)
+        wa = (Window * max(n, 1))(*windows_a)
+        wb = (Window * max(n, 1))(*windows_b)
+        self._check(self._L.chomp_kernel_setup_pairs(
+            self._h, n, arr, z0.ctypes.data_as(c_double_p), z1.ctypes.data_as(c_double_p),
+            float(ktheta_min), float(ktheta_max), wa, wb, int(bessel_order)))
+        self._n_sets = n
+
     def kernel_info_sets(self):
         """kernel_info() of every set, as a dictionary of arrays [n_set]; one synchronising
         read-back."""
@@ -1133,6 +1162,18 @@ class Context(object):
         return self._run(self._L.chomp_wtheta_sets, [theta], lambda mem, new, th: (
             int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), _host_address(D), th,
             _numel(th), new((int(n_epoch), _numel(th))), mem))[0]
+
+    def cell_sets(self, which, epoch0, n_epoch, D_z, ell):
+        """C_l of the epochs epoch0 .. epoch0 + n_epoch - 1, epoch epoch0 + e against projection
+        set e with growth D_z[e] (chomp_cell_sets): [n_epoch, ell.size], row e what
+        kernel_setup(<the inputs of set e>) + cell(which, epoch0 + e, D_z[e], ell) returns, bit for
+        bit.  D_z is a host array; ell a host array or a torch cuda tensor, as in cell_epochs."""
+        D = numpy.ascontiguousarray(D_z, dtype=numpy.float64).ravel()
+        if D.size != int(n_epoch):
+            raise ValueError("cell_sets: D_z must hold one growth factor per epoch")
+        return self._run(self._L.chomp_cell_sets, [ell], lambda mem, new, el: (
+            int(which), int(epoch0), int(n_epoch), _host_address(D), el, _numel(el),
+            new((int(n_epoch), _numel(el))), mem))[0]
 
     def _run(self, fn, xs, body):
         """Call the array entry point fn on host or device arrays; returns the list of outputs.

@@ -299,56 +299,69 @@ class Correlation(object):
 
         The status word of every point is read with the result, raised as a warning naming
         "cosmology i", kept in `self.cosmologies_status` (uint32) beside
-        `self.cosmologies_z_bar` (the redshifts found) and returned as the second element with
+        `self.cosmologies_z_bar` / `self.cosmologies_D_z` (the redshifts found and D there) and returned as the second element with
         with_status=True.  A torch cuda theta returns a tensor.
 
         ChompScopeError (before any launch): everything correlation_hods refuses, a kernel with
         an assigned z_bar (after set_redshift), a dNdzInterpolation / dNdChiGaussian window, a
         w0-wa cosmology among the points.  C_l (CorrelationFourier) is not batched over
         cosmologies yet."""
+        cosmo_dicts = [dict(c) for c in cosmo_dicts]
+        objs = self._cosmologies_scope(cosmo_dicts, hods)
+        return self._sets_batch(
+            theta_rad, "cosmologies", "cosmology", len(cosmo_dicts), objs, with_status,
+            lambda b0, n: cosmo_dicts[b0:b0 + n],
+            lambda ctx, b0, n: self.kernel._setup_sets_on(ctx, cosmo_dicts[b0:b0 + n]))
+
+    def _sets_batch(self, theta_rad, name, label, n_pt, objs, with_status, cosmos_of, stage):
+        """correlation_cosmologies and correlation_kernels behind their scope checks: n_pt rows,
+        each one projection set and one grid.HaloGrid epoch at the set's z_bar, in blocks of
+        _lib.KERNEL_SETS_MAX.  cosmos_of(b0, n): the cosmologies of rows b0 .. b0 + n - 1;
+        stage(ctx, b0, n): their projection sets on the grid's context; objs: one HOD object per
+        row, or None for this halo's HOD in every row.  The grid is kept in `_<name>_grid`, keyed
+        by the rows of a block, the halo dictionary, the mass function and the defaults a context
+        snapshots; the status words are kept in `<name>_status` beside `<name>_z_bar` and
+        `<name>_D_z` and raised as warnings naming "<label> i"."""
         import warnings
         from . import defaults
         from . import grid
-        cosmo_dicts = [dict(c) for c in cosmo_dicts]
-        objs = self._cosmologies_scope(cosmo_dicts, hods)
-        n_pt = len(cosmo_dicts)
         th = theta_rad if _lib._is_torch(theta_rad) else numpy.asarray(theta_rad, dtype=numpy.float64)
         flat = th.reshape(-1) if _lib._is_torch(th) else numpy.ascontiguousarray(th).ravel()
         n_th = flat.numel() if _lib._is_torch(flat) else flat.size
-        self.cosmologies_status = numpy.zeros(n_pt, dtype=numpy.uint32)
-        self.cosmologies_z_bar = numpy.zeros(n_pt)
+        words, z_all, D_all = numpy.zeros(n_pt, dtype=numpy.uint32), numpy.zeros(n_pt), numpy.zeros(n_pt)
+        setattr(self, name + "_status", words)
+        setattr(self, name + "_z_bar", z_all)
+        setattr(self, name + "_D_z", D_all)
         if n_pt == 0 or n_th == 0:
             out = flat.new_empty((n_pt, n_th)) if _lib._is_torch(flat) else numpy.empty((n_pt, n_th))
-            return (out, self.cosmologies_status) if with_status else out
+            return (out, words) if with_status else out
         h = self.halo
         code, _ = _POWER[self._power_name]
         kind = "tinker" if getattr(h.mass, "_kind", 0) else "st"
         rows = []
         for b0 in range(0, n_pt, _lib.KERNEL_SETS_MAX):
-            cosmos = cosmo_dicts[b0:b0 + _lib.KERNEL_SETS_MAX]
-            n = len(cosmos)
-            block_hods = objs[b0:b0 + n] if objs is not None else h.local_hod
+            n = min(_lib.KERNEL_SETS_MAX, n_pt - b0)
+            cosmos = cosmos_of(b0, n)
+            block_hods = list(objs[b0:b0 + n]) if objs is not None else h.local_hod
             # (a context snapshots defaults.default_limits / default_precision when it is created)
             key = (n, tuple(sorted(h.mass.halo_dict.items())), kind,
                    tuple(sorted(defaults.default_limits.items())),
                    tuple(sorted(defaults.default_precision.items())))
-            kept = getattr(self, "_cosmologies_grid", (None, None))
+            kept = getattr(self, "_%s_grid" % name, (None, None))
             hg = kept[1] if kept[0] == key else None
             if hg is None:
                 hg = grid.HaloGrid(numpy.zeros(n), cosmo_dict=cosmos, halo_dict=dict(h.mass.halo_dict),
-                                   hod_dict=block_hods if objs is None else list(block_hods),
-                                   mass_function=kind)
-                self._cosmologies_grid = (key, hg)
-            self.kernel._setup_sets_on(hg.ctx, cosmos)
-            info = hg.ctx.kernel_info_sets()           # (synchronises: z_bar and D(z_bar) per point)
+                                   hod_dict=block_hods, mass_function=kind)
+                setattr(self, "_%s_grid" % name, (key, hg))
+            stage(hg.ctx, b0, n)
+            info = hg.ctx.kernel_info_sets()           # (synchronises: z_bar and D(z_bar) per row)
             z_bar, D_z = info["z_bar"], info["D_zbar"]
-            hg.set_parameters(cosmo=cosmos, z=z_bar,
-                              hod=block_hods if objs is None else list(block_hods))
+            hg.set_parameters(cosmo=cosmos, z=z_bar, hod=block_hods)
             hg.setup(self._power_name)
-            rows.append(hg.ctx.wtheta_sets(h._power_code(code), 0, n, self._k_lim[0], self._k_lim[1],
-                                           D_z, flat))
-            self.cosmologies_status[b0:b0 + n] = hg.status()   # (synchronises: this block's words)
-            self.cosmologies_z_bar[b0:b0 + n] = z_bar
+            rows.append(self._kernels_evaluate(hg.ctx, h._power_code(code), n, D_z, flat))
+            words[b0:b0 + n] = hg.status()             # (synchronises: this block's words)
+            z_all[b0:b0 + n] = z_bar
+            D_all[b0:b0 + n] = D_z
         if len(rows) == 1:
             out = rows[0]
         elif _lib._is_torch(flat):
@@ -356,16 +369,95 @@ class Correlation(object):
             out = torch.cat(rows)
         else:
             out = numpy.concatenate(rows)
-        words = self.cosmologies_status
         for i, w in enumerate(words):
             w = int(w)
             if w:
                 category = (_lib.ChompParityWarning
                             if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
                             else _lib.ChompAccuracyWarning)
-                warnings.warn("cosmology %d: %s" % (i, "; ".join(_lib.describe_status(w))), category,
-                              stacklevel=2)
+                warnings.warn("%s %d: %s" % (label, i, "; ".join(_lib.describe_status(w))), category,
+                              stacklevel=3)
         return (out, words) if with_status else out
+
+    # -- the batch over kernels -------------------------------------------------
+    _KERNELS_LOOP = "fresh Correlation objects, one per kernel, + correlation"
+
+    def _kernels_scope(self, kernels, hods=None):
+        """ChompScopeError unless correlation_kernels serves this object, these kernels and
+        `hods`; no device work.  Returns the HODs as objects (None without `hods`)."""
+        from . import cosmology
+        from . import kernel as kernel_mod
+        who, loop = "correlation_kernels", self._KERNELS_LOOP
+        objs = self._hods_scope(hods, who=who, loop=loop)
+
+        def refuse(why):
+            raise _lib.ChompScopeError("%s: %s; use the loop %s" % (who, why, loop))
+        mine = type(self.kernel)
+        if mine not in (kernel_mod.Kernel, kernel_mod.GalaxyGalaxyLensingKernel):
+            refuse("this object's kernel is a %s, the batch takes Kernel or "
+                   "GalaxyGalaxyLensingKernel" % mine.__name__)
+        for i, k in enumerate(kernels):
+            if type(k) is not mine:
+                refuse("kernel %d is a %s, this object's kernel a %s (one Bessel order per call)"
+                       % (i, type(k).__name__, mine.__name__))
+            if tuple(k._ktheta) != tuple(self.kernel._ktheta):
+                refuse("kernel %d has another k theta range than this object's kernel" % i)
+            if k._z_bar_override is not None:
+                refuse("kernel %d has an assigned z_bar (Correlation.set_redshift); the batch "
+                       "finds z_bar per kernel" % i)
+            for name in ("window_function_a", "window_function_b"):
+                dist = getattr(getattr(k, name, None), "_redshift_dist", None)
+                if isinstance(dist, kernel_mod.dNdzInterpolation):
+                    refuse("kernel %d: %s has a tabulated redshift distribution (%s)"
+                           % (i, name, type(dist).__name__))
+            if cosmology.has_dark_energy(k.cosmo.cosmo_dict):
+                refuse("kernel %d has a w0-wa cosmology" % i)
+        if hods is not None and len(objs) != len(kernels):
+            raise ValueError("correlation_kernels: %d hods for %d kernels" % (len(objs), len(kernels)))
+        return objs if hods is not None else None
+
+    def correlation_kernels(self, theta_rad, kernels, hods=None, with_status=False):
+        """w(theta) for many kernels in one call (on a CorrelationFourier: C_l, theta_rad being
+        l; the two classes differ in _kernels_evaluate alone): the array [len(kernels),
+        theta.size] whose row i is what a fresh object of this class, built on kernels[i] with a
+        fresh halo.Halo of kernels[i]'s cosmology, this halo's halo dictionary and mass function,
+        the HOD hods[i] (this halo's without `hods`), this object's power spectrum and (w(theta))
+        k range, returns from correlation(theta_rad) -- the window pairs of a tomographic
+        analysis (kernel.py:559-839, one Correlation each: correlation.py:33-289) as one batch.
+        As the constructor does without keep_halo_z_bar, the halo of row i is evaluated at
+        kernels[i].z_bar with D_z = D(z_bar).  This object's own kernel, halo, cosmology and HOD
+        are not touched, nor are the kernels' own read-backs.
+
+        The work: one projection set-up per kernel on the kept grid's context
+        (Kernel._setup_pairs_on: windows, MultiEpoch range and cosmology are the kernel's own),
+        ONE read-back of every row's z_bar and D(z_bar), one grid.HaloGrid epoch per row at
+        z_bar[i] with kernels[i]'s cosmology, and _kernels_evaluate (Context.wtheta_sets).  The
+        grid is kept, keyed as correlation_cosmologies' (rows, halo dictionary, mass function,
+        the defaults a context snapshots).  More kernels than _lib.KERNEL_SETS_MAX are worked
+        off in blocks of that size.
+
+        The status word of every row is read with the result, raised as a warning naming
+        "kernel i", kept in `self.kernels_status` (uint32) beside `self.kernels_z_bar` and
+        `self.kernels_D_z`, and returned as the second element with with_status=True.  A torch
+        cuda theta returns a tensor.
+
+        ChompScopeError (before any launch): everything correlation_hods refuses, a kernel whose
+        type is not exactly this object's kernel's (Kernel or GalaxyGalaxyLensingKernel), a
+        kernel with another k theta range, a kernel with an assigned z_bar, a dNdzInterpolation /
+        dNdChiGaussian window, a w0-wa cosmology.  ValueError: `hods` of another length."""
+        from . import kernel as kernel_mod
+        kernels = list(kernels)
+        objs = self._kernels_scope(kernels, hods)
+        return self._sets_batch(
+            theta_rad, "kernels", "kernel", len(kernels), objs, with_status,
+            lambda b0, n: [dict(k.cosmo.cosmo_dict) for k in kernels[b0:b0 + n]],
+            lambda ctx, b0, n: kernel_mod.Kernel._setup_pairs_on(ctx, kernels[b0:b0 + n]))
+
+    def _kernels_evaluate(self, ctx, code, n, D_z, flat):
+        """The one call of the batches over projection sets (correlation_kernels,
+        correlation_cosmologies) that knows the observable: [n, flat.size], row e the grid's
+        epoch e against the context's projection set e with growth D_z[e]."""
+        return ctx.wtheta_sets(code, 0, n, self._k_lim[0], self._k_lim[1], D_z, flat)
 
     def write(self, output_file_name):
         with open(output_file_name, "w") as f:
@@ -426,6 +518,15 @@ class CorrelationFourier(Correlation):
         tables and Romberg integrals with an epoch axis, each row bit for bit what Context.cell
         returns for that epoch."""
         return ctx.cell_epochs(code, 0, n_hod, self.D_z, flat)
+
+    def _kernels_evaluate(self, ctx, code, n, D_z, flat):
+        """correlation_kernels(l, kernels, hods=None, with_status=False) is Correlation's,
+        inherited whole, with this as its evaluating call: Context.cell_sets builds one chi-only
+        node table per row (the set's windows, growth and chi range) and runs the rows' spectrum
+        tables and Romberg integrals with a set axis, each row bit for bit what Context.cell
+        returns after Context.kernel_setup of that kernel.  A kernel carries its cosmology, so
+        this is also the batch of C_l over cosmologies."""
+        return ctx.cell_sets(code, 0, n, D_z, flat)
 
     def correlation_cosmologies(self, l, cosmo_dicts, hods=None, with_status=False):
         """C_l is not batched over cosmologies yet: the chi-only node table of
@@ -617,6 +718,12 @@ class Correlation3d(Correlation):
         raise _lib.ChompScopeError(
             "Correlation3d.correlation_cosmologies: xi(r) is batched on raw_correlation; use "
             "raw_correlation_cosmologies (or raw_correlation_hods for a batch over HODs)")
+
+    def correlation_kernels(self, r, kernels, hods=None, with_status=False):
+        """xi(r) has no projection, hence no kernels to batch over; ChompScopeError."""
+        raise _lib.ChompScopeError(
+            "Correlation3d.correlation_kernels: xi(r) has no projection kernel; use "
+            "raw_correlation_hods or raw_correlation_cosmologies for the batches of xi(r)")
 
     def correlation(self, r):
         if not self.initialized_spline:

@@ -393,31 +393,21 @@ int chomp_kernel_table(chomp_ctx* ctx, int table, double* out, size_t n) {
   return CHOMP_OK;
 }
 
-// One projection set-up per cosmology (the cosmology axis of a w(theta) design or chain:
-// Kernel.set_cosmology, kernel.py:657-676, once per point of simulation_design.py:116-155): the
-// six launches of chomp_kernel_setup, once, with the set axis as the grids' z dimension
-// (chomp_proj_kernels.h, "The set axis").  On the context's stream; ctx->proj is not touched.
-int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo, double me_z_min,
-                            double me_z_max, double ktheta_min, double ktheta_max,
-                            const chomp_window* a, const chomp_window* b, int bessel_order) {
-  StageRange range_(ctx, "chomp:kernel_setup_sets");
-  if (!ctx || !cosmo || !a || !b || n_set == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bad args");
-  if (n_set > (size_t)kProjSetsMax)
-    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: more than " + std::to_string(kProjSetsMax) + " sets in one call");
-  if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bessel order must be 0 or 2");
-  for (size_t s = 0; s < n_set; ++s)
-    if (has_dark_energy(cosmo[s].w0, cosmo[s].wa))
-      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a w0/wa != -1/0 cosmology is set up by chomp_kernel_setup");
-  const chomp_window* ws[2] = {a, b};
-  { const int rcc = proj_check_args(ctx, "kernel_setup_sets", ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
-  for (int w = 0; w < 2; ++w)
-    if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
-      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a tabulated redshift distribution "
-                                        "(dNdzInterpolation) is set up by chomp_kernel_setup");
+// n_set projection set-ups on the set axis (chomp_proj_kernels.h, "The set axis"): the six launches
+// of chomp_kernel_setup, once, with the set as the grids' z dimension.  Set s takes cosmo[s],
+// me_z_min[s * step], me_z_max[s * step], a[s * step] and b[s * step] (step 0: one range and one
+// window pair for every set; 1: arrays); the k theta range and the Bessel order are shared.  The
+// callers have validated their arguments.  On the context's stream; ctx->proj is not touched.
+// who: the caller's name.
+static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, const chomp_cosmo* cosmo,
+                              const double* me_z_min, const double* me_z_max, size_t step,
+                              double ktheta_min, double ktheta_max, const chomp_window* a,
+                              const chomp_window* b, int bessel_order) {
+  const std::string w_ = std::string(who) + ": ";
   const chomp_config& c = ctx->cfg;
   const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
   if (L.NC > 240 || L.NWp > 360 || L.NKT > 720)          // (the spline builds are staged in 64 KB of LDS)
-    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: cosmo/window/kernel_npoints too large");
+    return fail(ctx, CHOMP_ERR_ARG, w_ + "cosmo/window/kernel_npoints too large");
   HIPCHK(hipSetDevice(ctx->device));
   ProjSets& S = ctx->sets;
   S.n = 0;
@@ -431,13 +421,16 @@ int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cos
   if (rc) return rc;
   const double j_limit = bessel_zero_host(bessel_order, c.kernel_bessel_limit);
   std::vector<ProjDev> pd(n_set);
-  for (size_t s = 0; s < n_set; ++s)
-    pd[s] = proj_host_block(c, &cosmo[s], me_z_min, me_z_max, ktheta_min, ktheta_max, ws, bessel_order, j_limit);
+  for (size_t s = 0; s < n_set; ++s) {
+    const chomp_window* ws[2] = {&a[s * step], &b[s * step]};
+    pd[s] = proj_host_block(c, &cosmo[s], me_z_min[s * step], me_z_max[s * step], ktheta_min,
+                            ktheta_max, ws, bessel_order, j_limit);
+  }
   rc = upload(ctx, S.d_pd_init, pd.data(), n_set * sizeof(ProjDev), ctx->sh_sets);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(S.d_pd, S.d_pd_init, n_set * sizeof(ProjDev), hipMemcpyDeviceToDevice, ctx->stream));
   S.L = L;
-  S.host = pd[0];
+  S.host = pd[0];                   // (what the sets share: the ln k theta range and the order)
   const unsigned Z = (unsigned)n_set;
   const size_t stride = (size_t)L.total;
   hipLaunchKernelGGL(k_proj_chi_sets, dim3(L.NC, 4, Z), dim3(64), 0, ctx->stream, c, L, S.d_pd, S.d_tab, stride);
@@ -458,11 +451,65 @@ int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cos
   return CHOMP_OK;
 }
 
+// One projection set-up per cosmology (the cosmology axis of a w(theta) design or chain:
+// Kernel.set_cosmology, kernel.py:657-676, once per point of simulation_design.py:116-155):
+// kernel_sets_launch with the range and the windows of every set the same.
+int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo, double me_z_min,
+                            double me_z_max, double ktheta_min, double ktheta_max,
+                            const chomp_window* a, const chomp_window* b, int bessel_order) {
+  StageRange range_(ctx, "chomp:kernel_setup_sets");
+  if (!ctx || !cosmo || !a || !b || n_set == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bad args");
+  if (n_set > (size_t)kProjSetsMax)
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: more than " + std::to_string(kProjSetsMax) + " sets in one call");
+  if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bessel order must be 0 or 2");
+  for (size_t s = 0; s < n_set; ++s)
+    if (has_dark_energy(cosmo[s].w0, cosmo[s].wa))
+      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a w0/wa != -1/0 cosmology is set up by chomp_kernel_setup");
+  const chomp_window* ws[2] = {a, b};
+  { const int rcc = proj_check_args(ctx, "kernel_setup_sets", ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
+  for (int w = 0; w < 2; ++w)
+    if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
+      return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a tabulated redshift distribution "
+                                        "(dNdzInterpolation) is set up by chomp_kernel_setup");
+  return kernel_sets_launch(ctx, "kernel_setup_sets", n_set, cosmo, &me_z_min, &me_z_max, 0, ktheta_min,
+                            ktheta_max, a, b, bessel_order);
+}
+
+// One projection set-up per kernel (the window pairs of a tomographic analysis, each with its
+// own MultiEpoch range and cosmology: a Kernel / GalaxyGalaxyLensingKernel per set, kernel.py:
+// 559-839), on the same set axis: chomp_kernel_info_sets, chomp_kernel_table_set, chomp_wtheta_sets
+// and chomp_cell_sets serve either set-up.  Every set is validated before anything is launched,
+// and a refusal names the set.
+int chomp_kernel_setup_pairs(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo,
+                             const double* me_z_min, const double* me_z_max, double ktheta_min,
+                             double ktheta_max, const chomp_window* a, const chomp_window* b,
+                             int bessel_order) {
+  StageRange range_(ctx, "chomp:kernel_setup_pairs");
+  if (!ctx || !cosmo || !me_z_min || !me_z_max || !a || !b || n_set == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_pairs: bad args");
+  if (n_set > (size_t)kProjSetsMax)
+    return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_pairs: more than " + std::to_string(kProjSetsMax) + " sets in one call");
+  if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_pairs: bessel order must be 0 or 2");
+  for (size_t s = 0; s < n_set; ++s) {
+    const std::string ws_ = "kernel_setup_pairs: set " + std::to_string(s);
+    if (has_dark_energy(cosmo[s].w0, cosmo[s].wa))
+      return fail(ctx, CHOMP_ERR_SCOPE, ws_ + ": a w0/wa != -1/0 cosmology is set up by chomp_kernel_setup");
+    const chomp_window* ws[2] = {&a[s], &b[s]};
+    { const int rcc = proj_check_args(ctx, ws_.c_str(), ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
+    for (int w = 0; w < 2; ++w)
+      if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
+        return fail(ctx, CHOMP_ERR_SCOPE, ws_ + ": a tabulated redshift distribution "
+                                          "(dNdzInterpolation) is set up by chomp_kernel_setup");
+  }
+  return kernel_sets_launch(ctx, "kernel_setup_pairs", n_set, cosmo, me_z_min, me_z_max, 1, ktheta_min,
+                            ktheta_max, a, b, bessel_order);
+}
+
 // chomp_kernel_info of every set, [n_set][CHOMP_KI_COUNT], in one synchronising read-back.
 int chomp_kernel_info_sets(chomp_ctx* ctx, double* out) {
   if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "kernel_info_sets: bad args");
   const ProjSets& S = ctx->sets;
-  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "kernel_info_sets before kernel_setup_sets");
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "kernel_info_sets before kernel_setup_sets / kernel_setup_pairs");
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   std::vector<ProjDev> pd(S.n);
@@ -475,7 +522,7 @@ int chomp_kernel_info_sets(chomp_ctx* ctx, double* out) {
 int chomp_kernel_table_set(chomp_ctx* ctx, size_t set, int table, double* out, size_t n) {
   if (!ctx || !out) return fail(ctx, CHOMP_ERR_ARG, "kernel_table_set: bad args");
   const ProjSets& S = ctx->sets;
-  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "kernel_table_set before kernel_setup_sets");
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "kernel_table_set before kernel_setup_sets / kernel_setup_pairs");
   if (set >= S.n) return fail(ctx, CHOMP_ERR_ARG, "kernel_table_set: set");
   int off = -1;
   size_t len = 0;
@@ -891,8 +938,8 @@ int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch
   return st.finish();
 }
 
-// w(theta) of n_epoch epochs, epoch epoch0 + e against projection set e of the last
-// chomp_kernel_setup_sets with growth D_z[e] (a cosmology design or chain: the loop of
+// w(theta) of n_epoch epochs, epoch epoch0 + e against projection set e of the last set-up of
+// sets with growth D_z[e] (a cosmology design or chain: the loop of
 // set_cosmology + correlation, correlation.py:161-171 per point): chomp_wtheta_epochs with a
 // per-row set and growth factor -- its scope, routes, chunks and work buffer.
 int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
@@ -905,7 +952,7 @@ int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, 
   Staging st(ctx, mem, "wtheta_sets");
   if (st.rc) return st.rc;
   const ProjSets& S = ctx->sets;
-  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "wtheta_sets before kernel_setup_sets");
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "wtheta_sets before kernel_setup_sets / kernel_setup_pairs");
   // (what the call does not serve is said first, as in chomp_wtheta_epochs)
   if (ctx->precision != CHOMP_PREC_F64)
     return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: fp64 only (the narrowed precision modes belong to chomp_wtheta)");
@@ -916,7 +963,7 @@ int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, 
   if (ctx->with_bao)
     return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: the wiggle transfer function is evaluated by chomp_wtheta");
   if (n_epoch != S.n)
-    return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: n_epoch is not the number of sets of the last kernel_setup_sets");
+    return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: n_epoch is not the number of sets of the last kernel_setup_sets / kernel_setup_pairs");
   int rc = check_power(ctx, which, epoch0, n_epoch);
   if (rc) return rc;
   if (!(k_min > 0.0) || !(k_max > k_min)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: k range");
@@ -1077,6 +1124,106 @@ int chomp_cell_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, 
                          ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
                          ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n, o, ctx->d_cnodes, LT,
                          pk_tab, split, deep, state, stride);
+    }
+  }
+  return st.finish();
+}
+
+// C_l of n_epoch epochs, epoch epoch0 + e against projection set e of the last set-up of sets with
+// growth D_z[e] (the kernels of a tomographic analysis, or a cosmology design or chain over C_l):
+// chomp_cell_epochs with a per-row set, growth factor and chi-only node table -- its scope, routes
+// and chunks; the work buffer holds one slab per row (chomp_proj_kernels.h, "The set axis of C_l").
+int chomp_cell_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, const double* D_z,
+                    const double* ell, size_t n, double* out, int mem) {
+  StageRange range_(ctx, "chomp:cell_sets");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!D_z || !ell || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: bad args");
+  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: n * n_epoch too large");
+  Staging st(ctx, mem, "cell_sets");
+  if (st.rc) return st.rc;
+  const ProjSets& S = ctx->sets;
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "cell_sets before kernel_setup_sets / kernel_setup_pairs");
+  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
+  if (ctx->precision != CHOMP_PREC_F64)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: fp64 only (no narrowed precision mode evaluates C_l)");
+  if (which & CHOMP_P_HALOFIT)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: HaloFit spectra are evaluated by chomp_cell");
+  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: extrapolated spectra are evaluated by chomp_cell");
+  if (ctx->with_bao)
+    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: the wiggle transfer function is evaluated by chomp_cell");
+  if (n_epoch != S.n)
+    return fail(ctx, CHOMP_ERR_ARG, "cell_sets: n_epoch is not the number of sets of the last kernel_setup_sets / kernel_setup_pairs");
+  int rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  for (size_t e = 0; e < n_epoch; ++e)
+    if (!(D_z[e] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: D_z");
+  // (the sizes, the split and the route as in cell_impl)
+  const ProjLayout& L = S.L;
+  const size_t pstride = (size_t)L.total;
+  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
+  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);   // (k_cell_deep_sets)
+  constexpr int kDeepLds = 160 * 1024 - 4096;
+  if (shd > kDeepLds) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: halo_npoints too large for k_cell_deep");
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* din;
+  double* dout;
+  st.in(ell, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = st.place(n_epoch);         // (D_z is a host array whatever `mem` says: the scratch segment)
+  if (rc) return rc;
+  const double* dD = st.scratch;
+  HIPCHK(hipMemcpyAsync(st.scratch, D_z, n_epoch * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
+  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const size_t stride = cell_set_stride(n, LT);
+  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
+                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
+  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
+  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, stride * chunk);
+  if (rc) return rc;
+  double* pk_tab = ctx->d_cnodes + 3 * n_nodes;            // (of the chunk's first row)
+  double* state = pk_tab + kPTabN + 1;
+  int* deep = reinterpret_cast<int*>(state + n * kRombergDump);
+  const int split = (ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL] > 0 || ctx->cfg.divmax <= kCellSplitLevel)
+                        ? ctx->cfg.divmax : kCellSplitLevel;
+  const unsigned gdeep = (unsigned)(n < 512 ? n : 512);
+  {
+    constexpr bool HF = false, BAO = false;
+    if (split < ctx->cfg.divmax) {
+      const int rcl = lds_opt_in(ctx, &k_cell_deep_sets<HF, BAO>, kDeepLds);
+      if (rcl) return rcl;
+    }
+    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the slabs are reused in stream order)
+      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+      const int e0 = (int)(epoch0 + c0);
+      double* o = dout + c0 * n;
+      const ProjDev* pd = S.d_pd + c0;                      // (the chunk's first set)
+      const double* ptab = S.d_tab + c0 * pstride;
+      hipLaunchKernelGGL(k_cell_nodes_sets, dim3((unsigned)((n_nodes + 255) / 256), E), dim3(256),
+                         (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, L, pd, ptab,
+                         pstride, dD + c0, LT, ctx->d_cnodes, deep, stride);
+      hipLaunchKernelGGL((k_cell_ptab_epochs<HF, BAO>), dim3((kPTabN + 256) / 256, E), dim3(256),
+                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, pk_tab, (int*)nullptr, stride);
+      if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
+        hipLaunchKernelGGL((k_cell4_sets<HF, BAO>), dim3((unsigned)((n + 3) / 4), E), dim3(256), sh,
+                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                           pd, ptab, pstride, dD + c0, din, (int)n, o, ctx->d_cnodes, LT, pk_tab,
+                           split, deep, state, stride);
+      } else {
+        with_flag(split > LT, [&](auto BEYOND) {
+          hipLaunchKernelGGL((k_cell_sets<HF, BAO, BEYOND>), dim3((unsigned)n, E), dim3(256), sh,
+                             ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                             pd, ptab, pstride, dD + c0, din, o, ctx->d_cnodes, LT, pk_tab, split,
+                             deep, state, stride);
+        });
+      }
+      if (split >= ctx->cfg.divmax) continue;
+      hipLaunchKernelGGL((k_cell_deep_sets<HF, BAO>), dim3(gdeep, E), dim3(kCellDeepThreads), shd,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                         pd, ptab, pstride, dD + c0, din, (int)n, o, ctx->d_cnodes, LT, pk_tab,
+                         split, deep, state, stride);
     }
   }
   return st.finish();

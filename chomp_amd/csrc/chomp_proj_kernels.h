@@ -132,11 +132,11 @@ inline void proj_free(ProjState& p) {
   p.cov_ready = false;
 }
 
-// The projection set-ups of chomp_kernel_setup_sets, beside ProjState (which they never touch):
-// n ProjDev blocks and n slabs of L.total doubles, set s at d_pd[s] and d_tab + s * L.total.
+// The projection set-ups of chomp_kernel_setup_sets / chomp_kernel_setup_pairs, beside ProjState
+// (which they never touch): n ProjDev blocks and n slabs of L.total doubles, set s at d_pd[s] and d_tab + s * L.total.
 // The buffers are kept across calls and only grow.
 struct ProjSets {
-  size_t n = 0;            // sets of the last chomp_kernel_setup_sets (0: none yet)
+  size_t n = 0;            // sets of the last set-up of sets (0: none yet)
   ProjLayout L;
   ProjDev host;            // what the sets share, as the host prepared it (ln k theta range, order)
   ProjDev* d_pd = nullptr;
@@ -1791,17 +1791,12 @@ struct CellIntegrand {
 // grid ceil((2^LT + 1) / 256), block 256; dynamic LDS ProjLds::doubles(L).
 constexpr int kCellTabLevel = 16;       // 3 x (2^16 + 1) doubles = 1.5 MiB (the C_l integrals of
                                         // configs[3] / [4] stop at levels 7..15, a few at 14, 15)
-__global__ __launch_bounds__(256) void k_cell_nodes(ProjLayout L, const ProjDev* __restrict__ pdg,
-                                                    const double* __restrict__ ptab, double D_z,
-                                                    int LT, double* __restrict__ nodes,
-                                                    int* __restrict__ deep, int n_lists,
-                                                    size_t list_stride) {
+// (the body of k_cell_nodes and k_cell_nodes_sets)
+__device__ __forceinline__ void cell_nodes_body(const ProjLayout& L, const ProjDev* __restrict__ pdg,
+                                                const double* __restrict__ ptab, double D_z, int LT,
+                                                double* __restrict__ nodes) {
   extern __shared__ __align__(16) double sm[];
   __shared__ ProjDev pd;
-  // k_cell's lists, one per epoch of the call (chomp_cell: one): count, head
-  if (blockIdx.x == 0)
-    for (int q = threadIdx.x; q < 2 * n_lists; q += blockDim.x)
-      deep[(q >> 1) * list_stride + (q & 1)] = 0;
   copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
   __syncthreads();
   ProjLds G;
@@ -1826,6 +1821,30 @@ __global__ __launch_bounds__(256) void k_cell_nodes(ProjLayout L, const ProjDev*
   nodes[idx] = (1.0 / (D_z * D_z)) * G.wa(chi) * G.wb(chi) * D * D / (chi * chi);
   nodes[N + idx] = log(chi);
   nodes[2 * N + idx] = chi;
+}
+__global__ __launch_bounds__(256) void k_cell_nodes(ProjLayout L, const ProjDev* __restrict__ pdg,
+                                                    const double* __restrict__ ptab, double D_z,
+                                                    int LT, double* __restrict__ nodes,
+                                                    int* __restrict__ deep, int n_lists,
+                                                    size_t list_stride) {
+  // k_cell's lists, one per epoch of the call (chomp_cell: one): count, head
+  if (blockIdx.x == 0)
+    for (int q = threadIdx.x; q < 2 * n_lists; q += blockDim.x)
+      deep[(q >> 1) * list_stride + (q & 1)] = 0;
+  cell_nodes_body(L, pdg, ptab, D_z, LT, nodes);
+}
+// ... with a set axis (chomp_cell_sets, "The set axis of C_l" below): grid (as k_cell_nodes, E);
+// row blockIdx.y tabulates set pd[blockIdx.y] and its slab of projection tables, `pstride` doubles
+// after the previous set's, with growth D_z[blockIdx.y] into its own node table, `stride` doubles
+// after the previous row's, and empties its own list (deep: the first row's).
+__global__ __launch_bounds__(256) void k_cell_nodes_sets(ProjLayout L, const ProjDev* __restrict__ pd,
+                                                         const double* __restrict__ ptab,
+                                                         size_t pstride, const double* __restrict__ D_z,
+                                                         int LT, double* __restrict__ nodes,
+                                                         int* __restrict__ deep, size_t stride) {
+  if (blockIdx.x == 0 && threadIdx.x < 2) deep[2 * stride * blockIdx.y + threadIdx.x] = 0;
+  cell_nodes_body(L, pd + blockIdx.y, ptab + pstride * blockIdx.y, D_z[blockIdx.y], LT,
+                  nodes + stride * blockIdx.y);
 }
 
 // P(k) of the spectrum a C_l call integrates, on a uniform grid of kPTabN intervals in ln k
@@ -2048,6 +2067,37 @@ __global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell_epochs(
                              deep + 2 * off, state + off, blockIdx.x);
 }
 
+// The set axis of C_l (chomp_cell_sets: one C_l per kernel -- window pair, MultiEpoch range,
+// cosmology -- of a tomographic analysis or a chain over photo-z parameters).  Row y of a chunk
+// integrates epoch e0 + y against projection set y of the last set-up of sets with growth D_z[y]:
+// the chi range, the windows and the growth factor are the set's own, so the chi-only node table
+// is the row's own too.  The work buffer holds one slab per row of the chunk at a fixed stride,
+//   3 (2^LT + 1) doubles   F_j, ln chi_j, chi_j of set y   (k_cell_nodes_sets)
+//   then the slab of the epoch axis above (cell_epoch_stride: P(k), states, deep list)
+// and the *_sets kernels address row y's node table, spectrum table, states and list at y * stride
+// from the first row's.  k_cell_ptab_epochs serves unchanged (the spectrum table depends on the
+// epoch, not on the set).  A row is 1.5 MiB more than a row of the epoch axis: 34 MiB per chunk of
+// 16 at 2048 multipoles, about 0.5 GiB at the chunk maximum of 256.  Per (multipole, row) the
+// arithmetic is chomp_cell's after chomp_kernel_setup of the set's inputs: the same bodies.
+inline size_t cell_set_stride(size_t n, int LT) {
+  return 3 * (((size_t)1 << LT) + 1) + cell_epoch_stride(n);
+}
+// grid (n_ell, E), block 256: k_cell_epochs with row blockIdx.y's own set, tables, growth and nodes.
+template <bool HF, bool BAO, bool DIRECT>
+__global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell_sets(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const double* __restrict__ D_z,
+    const double* __restrict__ ell, double* __restrict__ out, const double* __restrict__ nodes,
+    int LT, const double* __restrict__ pk_tab, int split, int* __restrict__ deep,
+    double* __restrict__ state, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  cell_body<HF, BAO, DIRECT>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pd + blockIdx.y,
+                             ptab + pstride * blockIdx.y, D_z[blockIdx.y], ell,
+                             out + (size_t)blockIdx.y * gridDim.x, nodes + off, LT, pk_tab + off,
+                             split, deep + 2 * off, state + off, blockIdx.x);
+}
+
 // k_cell4: the same integrals, FOUR multipoles to a block -- one per wavefront up to level
 // kCell4Level (romberg_wave6: a multipole that stops at level 7..8, the rule, costs two to four
 // nodes per lane and no block barrier), then the block's multipoles that go on are walked by all
@@ -2189,6 +2239,21 @@ __global__ __launch_bounds__(256, 3) void k_cell4_epochs(
                       out + (size_t)blockIdx.y * n_ell, nodes, LT, pk_tab + off, split, deep + 2 * off,
                       state + off, blockIdx.x);
 }
+// ... with a set axis: grid (ceil(n_ell / 4), E), block 256; row blockIdx.y as in k_cell_sets.
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(256, 3) void k_cell4_sets(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const double* __restrict__ D_z,
+    const double* __restrict__ ell, int n_ell, double* __restrict__ out,
+    const double* __restrict__ nodes, int LT, const double* __restrict__ pk_tab, int split,
+    int* __restrict__ deep, double* __restrict__ state, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  cell4_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pd + blockIdx.y,
+                      ptab + pstride * blockIdx.y, D_z[blockIdx.y], ell, n_ell,
+                      out + (size_t)blockIdx.y * n_ell, nodes + off, LT, pk_tab + off, split,
+                      deep + 2 * off, state + off, blockIdx.x);
+}
 
 // One node by the general route (inlined: a call would put a stack -- scratch memory -- behind
 // every launch of the kernel, used or not).
@@ -2308,6 +2373,23 @@ __global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep_epochs(
   const size_t off = stride * blockIdx.y;
   cell_deep_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pdg, ptab, D_z, ell,
                           out + (size_t)blockIdx.y * n_ell, nodes, LT, pk_tab + off, split,
+                          deep + 2 * off, state + off, blockIdx.x);
+}
+// ... with a set axis: grid (min(n_ell, 512), E), block 512; the blocks of row blockIdx.y draw
+// from that row's list alone and stage its set's projection tables beside its epoch's splines and
+// spectrum table (the levels beyond the node table evaluate windows and growth from them).
+template <bool HF, bool BAO>
+__global__ __launch_bounds__(kCellDeepThreads) void k_cell_deep_sets(
+    chomp_config cfg, TabLayout HL, ProjLayout L, const Epoch* __restrict__ epochs, int e0,
+    const double* __restrict__ htab, int which, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const double* __restrict__ D_z,
+    const double* __restrict__ ell, int n_ell, double* __restrict__ out,
+    const double* __restrict__ nodes, int LT, const double* __restrict__ pk_tab, int split,
+    int* __restrict__ deep, const double* __restrict__ state, size_t stride) {
+  const size_t off = stride * blockIdx.y;
+  cell_deep_body<HF, BAO>(cfg, HL, L, epochs, e0 + (int)blockIdx.y, htab, which, pd + blockIdx.y,
+                          ptab + pstride * blockIdx.y, D_z[blockIdx.y], ell,
+                          out + (size_t)blockIdx.y * n_ell, nodes + off, LT, pk_tab + off, split,
                           deep + 2 * off, state + off, blockIdx.x);
 }
 

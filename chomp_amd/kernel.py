@@ -357,6 +357,21 @@ class Kernel(object):
                               self.window_function_b._struct(), self._order)
         return ctx
 
+    @staticmethod
+    def _setup_pairs_on(ctx, kernels):
+        """Stage one projection set-up per kernel of `kernels` on `ctx`
+        (Context.kernel_setup_pairs): set i is what kernels[i]._setup_on would build -- its
+        cosmology, MultiEpoch range and windows -- as one batch beside the context's single
+        set-up.  The kernels share the k theta range and the Bessel order of kernels[0] (the
+        caller has checked that).  The kernels' own _done and _info are not touched."""
+        first = kernels[0]
+        ctx.kernel_setup_pairs([k.cosmo.cosmo_dict for k in kernels],
+                               [k.cosmo.z_min for k in kernels], [k.cosmo.z_max for k in kernels],
+                               first._ktheta[0], first._ktheta[1],
+                               [k.window_function_a._struct() for k in kernels],
+                               [k.window_function_b._struct() for k in kernels], first._order)
+        return ctx
+
     def _dev(self):
         if self._own is None:
             self._own = cosmology._context()

@@ -696,7 +696,27 @@ int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cos
                             double me_z_min, double me_z_max, double ktheta_min,
                             double ktheta_max, const chomp_window* a, const chomp_window* b,
                             int bessel_order);
-/* chomp_kernel_info of every set of the last chomp_kernel_setup_sets: out[s * CHOMP_KI_COUNT +
+/* The kernel axis of the projection set-up.  A tomographic analysis is the opposite case: one
+ * cosmology, many window pairs (five lens bins give 15 galaxy-galaxy kernels, every lens x source
+ * pair a galaxy-galaxy-lensing one: a Kernel / GalaxyGalaxyLensingKernel each, kernel.py:559-839),
+ * and a chain over photo-z nuisance parameters rebuilds them all at every step.
+ * chomp_kernel_setup_pairs builds
+ * n_set projection set-ups that may differ in everything but the k theta range and the Bessel
+ * order: set s holds, bit for bit, what chomp_kernel_setup(ctx, &cosmo[s], me_z_min[s],
+ * me_z_max[s], ktheta_min, ktheta_max, &a[s], &b[s], bessel_order) builds.
+ * It fills the same sets as chomp_kernel_setup_sets with the same six launches (the later of the
+ * two calls holds), so chomp_kernel_info_sets, chomp_kernel_table_set, chomp_wtheta_sets and
+ * chomp_cell_sets serve either set-up.  Every set is validated before anything is launched and a
+ * refusal names the set ("set 1"): what chomp_kernel_setup_sets validates, with all four window
+ * kinds of chomp_kernel_setup; CHOMP_ERR_SCOPE for a CHOMP_DNDZ_PPOLY distribution or a w0/wa !=
+ * -1/0 cosmology in any set; CHOMP_ERR_ARG for n_set = 0, n_set > CHOMP_KERNEL_SETS_MAX and null
+ * arrays. */
+int chomp_kernel_setup_pairs(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo /*[n_set]*/,
+                             const double* me_z_min /*[n_set]*/, const double* me_z_max /*[n_set]*/,
+                             double ktheta_min, double ktheta_max,
+                             const chomp_window* a /*[n_set]*/, const chomp_window* b /*[n_set]*/,
+                             int bessel_order);
+/* chomp_kernel_info of every set of the last set-up of sets: out[s * CHOMP_KI_COUNT +
  * CHOMP_KI_*], in ONE synchronising read-back.  CHOMP_ERR_STATE before any such set-up. */
 int chomp_kernel_info_sets(chomp_ctx* ctx, double* out /*[n_set * CHOMP_KI_COUNT]*/);
 /* chomp_kernel_table of set `set` (CHOMP_ERR_ARG beyond the last set-up's sets). */
@@ -735,15 +755,15 @@ int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch
                         double k_max, double D_z, const double* theta, size_t n, double* out,
                         int mem);
 /* Correlation.correlation(theta) over cosmologies: epoch epoch0 + e of the context is integrated
- * against projection set e of the last chomp_kernel_setup_sets with growth D_z[e] (a HOST array
+ * against projection set e of the last set-up of sets with growth D_z[e] (a HOST array
  * whatever `mem` says; the caller has moved epoch e to set e's z_bar, correlation.py:161-171):
  * out[e * n + i] = what chomp_wtheta(ctx, which, epoch0 + e, k_min, k_max, D_z[e], theta, n, ...)
  * returns at i after chomp_kernel_setup with cosmo[e], bit for bit -- both run the same bodies on
  * the same inputs.  The scope, routes and chunking of chomp_wtheta_epochs (fp64 only;
  * CHOMP_ERR_SCOPE for HaloFit codes, extrapolated halo-model spectra and the wiggle transfer
  * function; CHOMP_TUNE_WTHETA_EPOCH_CHUNK).  n_epoch must be the number of sets
- * (CHOMP_ERR_ARG); CHOMP_ERR_STATE before any chomp_kernel_setup_sets.  C_l has no such call yet:
- * the chi-only node table of chomp_cell_epochs is per set. */
+ * (CHOMP_ERR_ARG); CHOMP_ERR_STATE before any set-up of sets.  chomp_cell_sets is the same call
+ * for C_l. */
 int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
                       double k_max, const double* D_z /*[n_epoch], host*/, const double* theta,
                       size_t n, double* out, int mem);
@@ -968,6 +988,19 @@ int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z,
  * time. */
 int chomp_cell_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double D_z,
                       const double* ell, size_t n, double* out, int mem);
+/* C_l of epoch epoch0 + e against projection set e with growth D_z[e] (host array whatever `mem`
+ * says, as in chomp_wtheta_sets): out[e * n + i] = what chomp_cell(ctx, which, epoch0 + e, D_z[e],
+ * ell, n, ...) returns at i after chomp_kernel_setup of set e's inputs, bit for bit.
+ * The sets are those of the last chomp_kernel_setup_sets / chomp_kernel_setup_pairs: the batch
+ * over kernels (window pairs, MultiEpoch ranges) and over cosmologies of C_l.  The chi-only node
+ * table belongs to a set, so every row of a chunk has its own (1.5 MiB at the default divmax)
+ * before its spectrum table, Romberg states and deep list; otherwise the scope, argument checks,
+ * chunking (CHOMP_TUNE_WTHETA_EPOCH_CHUNK) and routes of chomp_cell_epochs.  In addition
+ * CHOMP_ERR_STATE before any set-up of sets and CHOMP_ERR_ARG when n_epoch is not the number of
+ * sets or some D_z[e] <= 0. */
+int chomp_cell_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch,
+                    const double* D_z /*[n_epoch], host*/, const double* ell, size_t n,
+                    double* out, int mem);
 
 /* Both observables of one survey set-up -- Correlation.correlation(theta) (correlation.py:
  * 242-275) and CorrelationFourier.correlation(l) (correlation.py:360-392) on the same kernel,
