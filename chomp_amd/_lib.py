@@ -135,6 +135,7 @@ EXPORTS = [
     "chomp_covariance_table", "chomp_covariance_gaussian",
     "chomp_covariance_cross_stage", "chomp_covariance_table_cross",
     "chomp_covariance_gaussian_cross",
+    "chomp_covariance_blocks", "chomp_covariance_blocks_table",
     "chomp_set_timing", "chomp_get_timing", "chomp_get_status", "chomp_status_post",
     "chomp_status_wait", "chomp_set_tuning",
     "chomp_get_deep_stats", "chomp_stage_k", "chomp_power_plan", "chomp_get_stream",
@@ -462,6 +463,9 @@ def lib():
         L.chomp_covariance_table_cross.argtypes = [vp, d, d, c_double_p, c_double_p,
                                                    c_double_p, sz]
         L.chomp_covariance_gaussian_cross.argtypes = [vp, d, d, d, d, d, d, vp, sz, vp, i]
+        L.chomp_covariance_blocks.argtypes = [vp, i, sz, ctypes.POINTER(sz), d, d, vp, vp, sz, vp, i]
+        L.chomp_covariance_blocks_table.argtypes = [vp, sz, c_double_p, c_double_p, c_double_p,
+                                                    c_double_p, sz]
         L.chomp_kernel_ssc_setup.argtypes = [vp, d, d, d, c_double_p, c_double_p, sz, i,
                                              c_double_p, c_double_p, c_double_p]
         L.chomp_kernel_ssc_raw.argtypes = [vp, vp, sz, vp]
@@ -1290,6 +1294,43 @@ class Context(object):
                          lambda mem, new, th: (float(j0_limit), float(area), p[0], p[1], p[2],
                                                p[3], th, _numel(th) // 2,
                                                new(_numel(th) // 2), mem))[0]
+
+    def covariance_blocks(self, which, epochs, j0_limit, area, poisson, theta_a, theta_b=None):
+        """covariance_G of every block (i, j), i <= j, of len(epochs) correlations for the same
+        pairs of bin centres (chomp_covariance_blocks): [n_blocks, n_pairs], the blocks in the
+        row-major order of the upper triangle.  Correlation c is projection set c of the last
+        kernel_setup_pairs and halo epoch epochs[c]; a diagonal block is what kernel_setup +
+        covariance_table + covariance_gaussian return, a cross block what two
+        covariance_cross_stage + covariance_table_cross + covariance_gaussian_cross do, bit for
+        bit.  poisson [n_blocks, 4]: proj_power_poisson(window_pair = 0..3) of every block.
+        (theta_a, theta_b): host arrays of one length; or theta_a alone, a contiguous float64
+        torch cuda tensor holding theta_a[n] then theta_b[n], which stays on the device (so does
+        the result; the Poisson terms are sent there)."""
+        ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
+        n_blocks = ep.size * (ep.size + 1) // 2
+        p = numpy.ascontiguousarray(poisson, dtype=numpy.float64)
+        if p.shape != (n_blocks, 4):
+            raise ValueError("covariance_blocks: poisson must be [%d, 4]" % n_blocks)
+        pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
+        if _is_torch(pairs):
+            import torch
+            p = torch.as_tensor(p, device=pairs.device)
+        return self._run(self._L.chomp_covariance_blocks, [pairs, p],
+                         lambda mem, new, th, po: (
+                             int(which), ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                             float(j0_limit), float(area), po, th, _numel(th) // 2,
+                             new((n_blocks, _numel(th) // 2)), mem))[0]
+
+    def covariance_blocks_table(self, block):
+        """(ln_K [kernel_npoints], the projected spectra a, b, ab, ba [4, kernel_npoints], their
+        Romberg levels [4, kernel_npoints], scalars [8]) of one block of the last
+        covariance_blocks; a diagonal block has row 0 alone (the others are zero)."""
+        n = self.config.kernel_npoints
+        ln_K, tab, lev, sc = numpy.empty(n), numpy.empty((4, n)), numpy.empty((4, n)), numpy.empty(8)
+        self._check(self._L.chomp_covariance_blocks_table(
+            self._h, int(block), ln_K.ctypes.data_as(c_double_p), tab.ctypes.data_as(c_double_p),
+            lev.ctypes.data_as(c_double_p), sc.ctypes.data_as(c_double_p), n))
+        return ln_K, tab, lev.astype(int), sc
 
     def covariance_cross_range(self):
         """(z_min, z_max, chi_min, chi_max) of the four windows in the two staged slots."""

@@ -668,15 +668,24 @@ class Covariance(object):
         """covariance.py:297-317; the Gaussian term of all bin pairs is one launch, the
         trispectrum and super-sample terms one call each."""
         nb = len(self.annular_bins)
-        self.covar = numpy.zeros((nb, nb))
         iu = numpy.triu_indices(nb)
         centers = numpy.array([b.center for b in self.annular_bins])
+        vals = None
         if not self.poisson_noise_only and nb:
             vals = self._covariance_G_pairs(centers[iu[0]], centers[iu[1]])
             if self.nongaussian_cov:
                 vals = vals + self._covariance_NG_pairs(centers[iu[0]], centers[iu[1]])
             if self.ssc_cov:
                 vals = vals + self._covariance_ssc_pairs(centers[iu[0]], centers[iu[1]])
+        return self._fill_covar(vals)
+
+    def _fill_covar(self, vals):
+        """`covar` from the values of the bin pairs (a, b), a <= b, in numpy.triu_indices order
+        (None: no such term), and the Poisson diagonal of a matching block."""
+        nb = len(self.annular_bins)
+        self.covar = numpy.zeros((nb, nb))
+        if vals is not None:
+            iu = numpy.triu_indices(nb)
             self.covar[iu] = vals
             self.covar[(iu[1], iu[0])] = vals
         if self.matching_corrs:                              # covariance.py:312
@@ -828,9 +837,15 @@ class CovarianceMulti(Covariance):
 
     def get_covariance(self):
         """covariance.py:854-871: block (i, j) and its mirror both receive the block's covar."""
+        for row in self.covariance_list:
+            for cov in row:
+                cov.get_covariance()
+        return self._assemble()
+
+    def _assemble(self):
+        """wcovar from the blocks' covar (covariance.py:862-870)."""
         for idx1, row in enumerate(self.covariance_list):
             for idx2, cov in enumerate(row):
-                cov.get_covariance()
                 row_ndx1 = idx1 * self.theta_bins
                 row_ndx2 = row_ndx1 + self.theta_bins
                 col_ndx1 = (idx1 + idx2) * self.theta_bins
@@ -838,6 +853,156 @@ class CovarianceMulti(Covariance):
                 self.wcovar[row_ndx1:row_ndx2, col_ndx1:col_ndx2] = cov.covar
                 self.wcovar[col_ndx1:col_ndx2, row_ndx1:row_ndx2] = cov.covar
         return self.wcovar
+
+    # -- every block in one call -------------------------------------------------
+    def _batched_scope(self):
+        """ChompScopeError unless get_covariance_batched serves these blocks; no device work.
+        Returns (the correlations, the spectrum's name)."""
+        from . import cosmology
+        from . import hod as hod_mod
+
+        def refuse(why):
+            raise _lib.ChompScopeError("get_covariance_batched: %s; use get_covariance" % why)
+        blocks = [cov for row in self.covariance_list for cov in row]
+        corrs = [row[0].corr_a for row in self.covariance_list]
+        if any(cov.nongaussian_cov or cov.ssc_cov for cov in blocks):
+            refuse("the batch serves the Gaussian and Poisson terms, not the trispectrum "
+                   "(nongaussian_cov) or super-sample (ssc_cov) terms")
+        if any(cov.poisson_noise_only for cov in blocks):
+            refuse("poisson_noise_only needs no device")
+        names = set(cov.power_spec for cov in blocks)
+        if len(names) != 1:
+            refuse("the blocks' power_spec differ (%s)" % ", ".join(sorted(names)))
+        centers = [[b.center for b in cov.annular_bins] for cov in blocks]
+        if any(c != centers[0] for c in centers) or any(cov.area != blocks[0].area for cov in blocks):
+            refuse("the blocks' angular bins or survey areas differ")
+        first = corrs[0].kernel
+        for i, corr in enumerate(corrs):
+            k = corr.kernel
+            if type(k) is not kernel_mod.Kernel:
+                refuse("the kernel of correlation %d is a %s, the batch takes kernel.Kernel"
+                       % (i, type(k).__name__))
+            if k._z_bar_override is not None:
+                refuse("the kernel of correlation %d has an assigned z_bar "
+                       "(Correlation.set_redshift); the batch finds z_bar per kernel" % i)
+            for name in ("window_function_a", "window_function_b"):
+                dist = getattr(getattr(k, name, None), "_redshift_dist", None)
+                if isinstance(dist, kernel_mod.dNdzInterpolation):
+                    refuse("correlation %d: %s has a tabulated redshift distribution (%s)"
+                           % (i, name, type(dist).__name__))
+            if cosmology.has_dark_energy(k.cosmo.cosmo_dict):
+                refuse("the kernel of correlation %d has a w0-wa cosmology" % i)
+            if tuple(k._ktheta) != tuple(first._ktheta):
+                refuse("the kernel of correlation %d has another k theta range than that of "
+                       "correlation 0" % i)
+            who = "get_covariance_batched"
+            try:
+                corr._hods_scope(who=who, loop="")
+            except _lib.ChompScopeError as e:
+                why = str(e)[len(who) + 2:].rsplit("; use the loop", 1)[0]
+                refuse("correlation %d: %s" % (i, why))
+            if type(corr.halo.local_hod) not in (hod_mod.HODZheng, hod_mod.HODMandelbaum):
+                refuse("the HOD of correlation %d is a %s, not an HODZheng or HODMandelbaum"
+                       % (i, type(corr.halo.local_hod).__name__))
+        h0 = corrs[0].halo
+        for i, corr in enumerate(corrs):
+            h = corr.halo
+            if (sorted(h.mass.halo_dict.items()) != sorted(h0.mass.halo_dict.items()) or
+                    getattr(h.mass, "_kind", 0) != getattr(h0.mass, "_kind", 0)):
+                refuse("the halo of correlation %d has another halo dictionary or mass function "
+                       "than that of correlation 0 (one grid.HaloGrid takes one of each)" % i)
+            for j in range(i):
+                if corrs[j].halo is h:
+                    refuse("correlations %d and %d share one Halo object: the loop then "
+                           "evaluates both sides of their block at one redshift" % (j, i))
+        for i, ca in enumerate(corrs):
+            for cb in corrs[i + 1:]:
+                try:
+                    self._check_cross(ca, cb, False, False)
+                except _lib.ChompScopeError as e:
+                    refuse(str(e))
+        return corrs, names.pop()
+
+    def get_covariance_batched(self, with_status=False):
+        """get_covariance() with every block in one device call: the same `wcovar`, and the same
+        `covar` in every ``covariance_list[i][j - i]`` (the Poisson diagonal of the matching
+        blocks included), bit for bit what the loop over fresh correlations returns.
+
+        The work: the correlations' kernels as projection sets on one kept grid.HaloGrid's context
+        (Kernel._setup_pairs_on), ONE read-back of every kernel's z_bar -- the only
+        synchronisation besides the result and the status words --, one HaloGrid epoch per
+        correlation at its z_bar with its halo's cosmology and HOD, and Context.covariance_blocks:
+        block (i, j) reads set i, set j, epoch i and epoch j where they lie.  The grid is kept,
+        keyed as Correlation.correlation_kernels keys its own (rows, halo dictionary, mass
+        function, the defaults a context snapshots).  The correlations, their kernels and their
+        halos are not touched: unlike the loop (covariance.py:465-466) the batch does not move the
+        halos to their z_bar, and it does not fill the blocks' own tables (_halo_a_array, ...).
+
+        The status word of every correlation's epoch is read with the result, raised as a warning
+        naming "correlation i", kept in `self.blocks_status` (uint32) beside `self.blocks_z_bar`
+        and returned as the second element with with_status=True.
+
+        ChompScopeError ("get_covariance_batched: <why>; use get_covariance", before any launch):
+        nongaussian_cov, ssc_cov or poisson_noise_only; blocks whose power_spec, bins or areas
+        differ; a kernel that is not exactly kernel.Kernel, has an assigned z_bar, a tabulated
+        redshift distribution, a w0-wa cosmology or another k theta range; a halo
+        Correlation.correlation_hods would refuse, an HOD of another class, halos with different
+        halo dictionaries or mass functions, two correlations sharing one Halo object; anything
+        Covariance refuses for a cross block.  And, once z_bar is known: correlation 0's halo away
+        from its z_bar (keep_halo_z_bar), which the loop's first block would be evaluated at."""
+        import warnings
+        from . import grid
+        corrs, power_spec = self._batched_scope()
+        n = len(corrs)
+        halos = [c.halo for c in corrs]
+        h0 = halos[0]
+        kind = "tinker" if getattr(h0.mass, "_kind", 0) else "st"
+        # (a context snapshots defaults.default_limits / default_precision when it is created)
+        key = (n, tuple(sorted(h0.mass.halo_dict.items())), kind,
+               tuple(sorted(defaults.default_limits.items())),
+               tuple(sorted(defaults.default_precision.items())))
+        kept = getattr(self, "_blocks_grid", (None, None))
+        hg = kept[1] if kept[0] == key else None
+        cosmos = [dict(h.cosmo.cosmo_dict) for h in halos]
+        hods = [h.local_hod for h in halos]
+        if hg is None:
+            hg = grid.HaloGrid(numpy.zeros(n), cosmo_dict=cosmos, halo_dict=dict(h0.mass.halo_dict),
+                               hod_dict=hods, mass_function=kind)
+            self._blocks_grid = (key, hg)
+        kernel_mod.Kernel._setup_pairs_on(hg.ctx, [c.kernel for c in corrs])
+        z_bar = hg.ctx.kernel_info_sets()["z_bar"]       # (synchronises: z_bar per correlation)
+        self.blocks_z_bar = z_bar
+        if float(h0.get_redshift()) != float(z_bar[0]):
+            raise _lib.ChompScopeError(
+                "get_covariance_batched: the halo of correlation 0 is at z = %r, not at its "
+                "kernel's z_bar = %r (keep_halo_z_bar): the loop evaluates the first block there; "
+                "use get_covariance" % (float(h0.get_redshift()), float(z_bar[0])))
+        hg.set_parameters(cosmo=cosmos, z=z_bar, hod=hods)
+        hg.setup(power_spec)
+        blocks = [cov for row in self.covariance_list for cov in row]
+        first = blocks[0]
+        nb = len(first.annular_bins)
+        iu = numpy.triu_indices(nb)
+        centers = numpy.array([b.center for b in first.annular_bins])
+        code = h0._power_code(_POWER[power_spec][0])
+        vals = hg.ctx.covariance_blocks(
+            code, numpy.arange(n), first._j0_limit, first.area,
+            [[cov.proj_power_poisson(p) for p in range(4)] for cov in blocks],
+            centers[iu[0]], centers[iu[1]])
+        words = hg.status()                              # (synchronises: the words of this result)
+        self.blocks_status = words
+        for cov, v in zip(blocks, vals):
+            cov._fill_covar(v if nb else None)
+        for i, w in enumerate(words):
+            w = int(w)
+            if w:
+                category = (_lib.ChompParityWarning
+                            if w & (_lib.ST_SATURATED | _lib.ST_MASS_SEARCH_EXHAUSTED)
+                            else _lib.ChompAccuracyWarning)
+                warnings.warn("correlation %d: %s" % (i, "; ".join(_lib.describe_status(w))),
+                              category, stacklevel=2)
+        self._assemble()
+        return (self.wcovar, words) if with_status else self.wcovar
 
 
 class CovarianceFourier(object):

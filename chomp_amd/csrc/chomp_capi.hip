@@ -238,6 +238,8 @@ struct chomp_ctx {
   ProjSets sets;                // chomp_kernel_setup_sets: one projection set-up per cosmology
   CrossState cross;             // Covariance(corr_a, corr_b): the two sides' snapshots and the four tables
   FourierState fourier;         // CovarianceFourier: the four pairs' scalars, Limber tables and splines
+  BlocksState blocks;           // chomp_covariance_blocks: one table slab per block of a CovarianceMulti
+  StagedBlock sh_blocks;        // ... and its index block
   // The side stream.  The projection set-up (chomp_kernel_setup / chomp_multi_epoch_setup:
   // a chain of six small launches) depends on nothing the halo set-up produces, and C_l on
   // nothing w(theta) produces: they run here, beside the context's stream, ordered against it
@@ -710,7 +712,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
                   ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4, ctx->d_prof,
-                  ctx->sets.d_pd, ctx->sets.d_pd_init, ctx->sets.d_tab};
+                  ctx->sets.d_pd, ctx->sets.d_pd_init, ctx->sets.d_tab, ctx->blocks.d, ctx->blocks.d_index};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -718,7 +720,7 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
   for (StagedBlock* b : {&ctx->sh_cosmo, &ctx->sh_z, &ctx->sh_mass, &ctx->sh_profile, &ctx->sh_hod,
                          &ctx->sh_slot, &ctx->sh_first, &ctx->sh_delta_b, &ctx->sh_proj, &ctx->sh_pp[0],
                          &ctx->sh_pp[1], &ctx->sh_de_knots, &ctx->sh_de_slot, &ctx->de_ep.sh_par,
-                         &ctx->de_proj.sh_par, &ctx->sh_sets})
+                         &ctx->de_proj.sh_par, &ctx->sh_sets, &ctx->sh_blocks})
     b->release();
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);

@@ -1458,6 +1458,136 @@ int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area
 }
 
 // ---------------------------------------------------------------------------
+// Every Gaussian block of a CovarianceMulti in one call (chomp_proj_kernels.h, "The block axis
+// of the Gaussian covariance")
+// ---------------------------------------------------------------------------
+// Correlation c is projection set c of the last set-up of sets and P(k) epoch epoch[c] of this
+// context; block (i, j) reads both sides where they lie.  Neither ctx->proj nor ctx->cross nor
+// the single-block covariance state is touched.
+int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size_t* epoch,
+                            double j0_limit, double area, const double* poisson,
+                            const double* theta, size_t n_pairs, double* out, int mem) {
+  StageRange range_(ctx, "chomp:covariance_blocks");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!epoch || !poisson || !theta || !out || n_corr == 0 || n_pairs == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: bad args");
+  Staging st(ctx, mem, "covariance_blocks");
+  if (st.rc) return st.rc;
+  const ProjSets& S = ctx->sets;
+  if (S.n == 0)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks before kernel_setup_pairs / kernel_setup_sets");
+  if (S.n != n_corr)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks: n_corr is not the number of sets of the last "
+                                      "kernel_setup_pairs / kernel_setup_sets");
+  if (S.host.order != 0)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks: the sets are of Bessel order 2 (the covariance "
+                                      "of w(theta) takes the windows of a Kernel, order 0)");
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;     // (n_corr <= kProjSetsMax)
+  if (n_blocks > 65535)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: more than 65535 blocks (a grid's z dimension)");
+  if (n_pairs > 0x7fffffffu / n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: n_pairs * n_blocks too large");
+  for (size_t c = 0; c < n_corr; ++c) {
+    const int rcp = check_power(ctx, which, epoch[c], 1);
+    if (rcp) return fail(ctx, rcp, "covariance_blocks: correlation " + std::to_string(c) + ": " + ctx->err);
+  }
+  if (!(j0_limit > 0.0) || !(area > 0.0))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: j0_limit and area must be positive");
+  if (st.host)
+    for (size_t i = 0; i < 2 * n_pairs; ++i)
+      if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: theta must be positive");
+  const ProjLayout& L = S.L;
+  const CrossLayout C = make_blocks_layout(L.NKT);
+  const size_t sh = (size_t)cov_cross_lds_doubles(ctx->L.NK, L) * sizeof(double);
+  if (sh > 64 * 1024)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: halo/cosmo/window_npoints too large for "
+                                    "the two spectra and four windows of a cross block");
+  HIPCHK(hipSetDevice(ctx->device));
+  for (size_t c = 0; c < n_corr; ++c) {                  // (a no-op unless `which` extrapolates)
+    const int rce = prepare_extrapolation(ctx, which, epoch[c], 1);
+    if (rce) return rce;
+  }
+  BlocksState& B = ctx->blocks;
+  B.n_corr = 0;
+  int rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)C.total);
+  if (rc) return rc;
+  {
+    const int* before = B.d_index;
+    rc = ensure(ctx, &B.d_index, &B.cap_index, n_corr + 2 * n_blocks);
+    if (rc) return rc;
+    if (B.d_index != before) ctx->sh_blocks.reset();
+  }
+  std::vector<int> index(n_corr + 2 * n_blocks);
+  for (size_t c = 0; c < n_corr; ++c) index[c] = (int)epoch[c];
+  {
+    size_t b = 0;
+    for (size_t i = 0; i < n_corr; ++i)
+      for (size_t j = i; j < n_corr; ++j, ++b) {
+        index[n_corr + 2 * b] = (int)i;
+        index[n_corr + 2 * b + 1] = (int)j;
+      }
+  }
+  rc = upload(ctx, B.d_index, index.data(), index.size() * sizeof(int), ctx->sh_blocks);
+  if (rc) return rc;
+  const double *d_theta, *d_poisson;
+  double* d_out;
+  st.in(theta, 2 * n_pairs, &d_theta);
+  st.in(poisson, 4 * n_blocks, &d_poisson);
+  st.out(out, n_blocks * n_pairs, &d_out);
+  rc = st.place();
+  if (rc) return rc;
+  B.C = C;
+  const int nc = (int)n_corr;
+  const unsigned Z = (unsigned)n_blocks;
+  const size_t pstride = (size_t)L.total;
+  hipLaunchKernelGGL(k_cov_blocks_prep, dim3((Z + 63) / 64), dim3(64), 0, ctx->stream, L, C, nc,
+                     (int)n_blocks, S.d_pd, S.d_tab, pstride, B.d_index, B.d);
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_cov_blocks_knots<BAO>, dim3((unsigned)C.N, 4, Z), dim3(256), sh,
+                       ctx->stream, ctx->cfg, ctx->L, L, C, nc, ctx->d_epochs, ctx->d_tab, which,
+                       S.d_pd, S.d_tab, pstride, B.d_index, B.d);
+  });
+  hipLaunchKernelGGL(k_cov_blocks_spline, dim3(4, Z), dim3(64), 0, ctx->stream, C, nc, B.d_index, B.d);
+  const size_t shg = (size_t)(C.N + 16 * (C.N - 1)) * sizeof(double);
+  hipLaunchKernelGGL(k_cov_blocks_gaussian, dim3((unsigned)n_pairs, Z), dim3(256), shg, ctx->stream,
+                     ctx->cfg, C, nc, B.d_index, B.d, ctx->d_j0, j0_limit, area, d_poisson, d_theta,
+                     d_theta + n_pairs, d_out);
+  HIPCHK(hipGetLastError());
+  B.n_corr = n_corr;
+  return st.finish();
+}
+
+// The tables of one block of the last chomp_covariance_blocks (host arrays, any may be NULL).
+int chomp_covariance_blocks_table(chomp_ctx* ctx, size_t block, double* ln_K, double* tables,
+                                  double* levels, double* scalars, size_t n) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  const BlocksState& B = ctx->blocks;
+  if (B.n_corr == 0) return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks_table before covariance_blocks");
+  const size_t n_blocks = B.n_corr * (B.n_corr + 1) / 2;
+  if (block >= n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks_table: block");
+  const CrossLayout& C = B.C;
+  if ((ln_K || tables || levels) && n != (size_t)C.N)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks_table: length must be kernel_npoints");
+  bool diagonal = false;
+  for (size_t i = 0, b0 = 0; i < B.n_corr; b0 += B.n_corr - i, ++i) diagonal = diagonal || block == b0;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const double* ct = B.d + block * (size_t)C.total;
+  const size_t bytes = (size_t)C.N * sizeof(double);
+  if (ln_K) HIPCHK(hipMemcpy(ln_K, ct + C.ln_K, bytes, hipMemcpyDeviceToHost));
+  for (int t = 0; t < 4; ++t) {
+    if (diagonal && t > 0) {                             // (a diagonal block has table 0 alone)
+      if (tables) std::fill(tables + (size_t)t * C.N, tables + (size_t)(t + 1) * C.N, 0.0);
+      if (levels) std::fill(levels + (size_t)t * C.N, levels + (size_t)(t + 1) * C.N, 0.0);
+      continue;
+    }
+    if (tables) HIPCHK(hipMemcpy(tables + (size_t)t * C.N, ct + C.proj[t], bytes, hipMemcpyDeviceToHost));
+    if (levels) HIPCHK(hipMemcpy(levels + (size_t)t * C.N, ct + C.lev[t], bytes, hipMemcpyDeviceToHost));
+  }
+  if (scalars) HIPCHK(hipMemcpy(scalars, ct + C.scal, 8 * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Gaussian covariance of C_l: CovarianceFourier (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
 static bool fits_lds(const void* kernel, size_t dynamic_bytes);

@@ -2436,25 +2436,28 @@ struct CovProjIntegrand {
 
 // grid N (= kernel_npoints), block 256: one ln K knot of Covariance._halo_a_spline per
 // workgroup (covariance.py:455-543, the matching_corrs branch).
+// (the body of k_cov_proj_knots and of a diagonal block of k_cov_blocks_knots: the sources are
+//  the epoch record `ep` with its knot-table slab `htab`, the ProjDev block `pdg` with its
+//  projection slab `ptab`; the destination the slab `ctab` of layout C)
 template <bool BAO>
-__global__ __launch_bounds__(256) void k_cov_proj_knots(chomp_config cfg, TabLayout HL,
-                                                        ProjLayout L, CovLayout C,
-                                                        const Epoch* __restrict__ epochs, int e,
-                                                        const double* __restrict__ htab, int which,
-                                                        const ProjDev* __restrict__ pdg,
-                                                        const double* __restrict__ ptab,
-                                                        double D_z, double* __restrict__ ctab) {
+__device__ __forceinline__ void cov_proj_knots_body(const chomp_config& cfg, const TabLayout& HL,
+                                                    const ProjLayout& L, const CovLayout& C,
+                                                    const Epoch* __restrict__ ep,
+                                                    const double* __restrict__ htab, int which,
+                                                    const ProjDev* __restrict__ pdg,
+                                                    const double* __restrict__ ptab,
+                                                    double D_z, double* __restrict__ ctab) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   __shared__ ProjDev pd;
   __shared__ double red[romberg_scratch<4, 2>()];
   __shared__ double chi_peak_s;
-  copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
+  copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(ep),
                kEpochDoubles);
   copy_doubles(reinterpret_cast<double*>(&pd), reinterpret_cast<const double*>(pdg), kProjDoubles);
   __syncthreads();
   PowerEval P;
-  P.stage(cfg, HL, &E, htab + (size_t)e * HL.stride, which, sm);
+  P.stage(cfg, HL, &E, htab, which, sm);
   ProjLds G;
   G.stage(L, pd, ptab, sm + 12 * (HL.NK - 1));
   G.bess = nullptr;
@@ -2488,10 +2491,24 @@ __global__ __launch_bounds__(256) void k_cov_proj_knots(chomp_config cfg, TabLay
     }
   }
 }
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_cov_proj_knots(chomp_config cfg, TabLayout HL,
+                                                        ProjLayout L, CovLayout C,
+                                                        const Epoch* __restrict__ epochs, int e,
+                                                        const double* __restrict__ htab, int which,
+                                                        const ProjDev* __restrict__ pdg,
+                                                        const double* __restrict__ ptab,
+                                                        double D_z, double* __restrict__ ctab) {
+  cov_proj_knots_body<BAO>(cfg, HL, L, C, epochs + e, htab + (size_t)e * HL.stride, which, pdg,
+                           ptab, D_z, ctab);
+}
 
+// (the body of k_cov_spline and of a diagonal block of k_cov_blocks_spline; one thread)
+__device__ __forceinline__ void cov_spline_body(const CovLayout& C, double* __restrict__ ctab) {
+  spline_build(ctab + C.ln_K, ctab + C.proj, C.N, ctab + C.pp, ctab + C.work);
+}
 __global__ void k_cov_spline(CovLayout C, double* __restrict__ ctab) {
-  if (threadIdx.x == 0 && blockIdx.x == 0)
-    spline_build(ctab + C.ln_K, ctab + C.proj, C.N, ctab + C.pp, ctab + C.work);
+  if (threadIdx.x == 0 && blockIdx.x == 0) cov_spline_body(C, ctab);
 }
 
 // covariance.py:397-453 (_covariance_G_integrand, matching_corrs: the second two-point
@@ -2511,15 +2528,17 @@ struct CovGIntegrand {
 };
 
 // grid n pairs, block 256: Covariance.covariance_G(theta_a, theta_b) (covariance.py:361-395).
-__global__ __launch_bounds__(256) void k_cov_gaussian(chomp_config cfg, CovLayout C,
-                                                      const double* __restrict__ ctab,
-                                                      const BesselTab* __restrict__ bess_g,
-                                                      double j0_limit, double area,
-                                                      double poiss_a, double poiss_b,
-                                                      const double* __restrict__ theta_a,
-                                                      const double* __restrict__ theta_b,
-                                                      double* __restrict__ out,
-                                                      double* __restrict__ levels) {
+// (the body of k_cov_gaussian and of a diagonal block of k_cov_blocks_gaussian: pair blockIdx.x
+//  of theta_a / theta_b from the tables of the slab `ctab` into out[blockIdx.x])
+__device__ __forceinline__ void cov_gaussian_body(const chomp_config& cfg, const CovLayout& C,
+                                                  const double* __restrict__ ctab,
+                                                  const BesselTab* __restrict__ bess_g,
+                                                  double j0_limit, double area,
+                                                  double poiss_a, double poiss_b,
+                                                  const double* __restrict__ theta_a,
+                                                  const double* __restrict__ theta_b,
+                                                  double* __restrict__ out,
+                                                  double* __restrict__ levels) {
   extern __shared__ __align__(16) double sm[];
   __shared__ BesselTab B;
   __shared__ double red[romberg_scratch<4, 2>()];
@@ -2549,6 +2568,18 @@ __global__ __launch_bounds__(256) void k_cov_gaussian(chomp_config cfg, CovLayou
     out[blockIdx.x] = v;
     if (levels) levels[blockIdx.x] = (double)level;
   }
+}
+__global__ __launch_bounds__(256) void k_cov_gaussian(chomp_config cfg, CovLayout C,
+                                                      const double* __restrict__ ctab,
+                                                      const BesselTab* __restrict__ bess_g,
+                                                      double j0_limit, double area,
+                                                      double poiss_a, double poiss_b,
+                                                      const double* __restrict__ theta_a,
+                                                      const double* __restrict__ theta_b,
+                                                      double* __restrict__ out,
+                                                      double* __restrict__ levels) {
+  cov_gaussian_body(cfg, C, ctab, bess_g, j0_limit, area, poiss_a, poiss_b, theta_a, theta_b, out,
+                    levels);
 }
 
 // ---------------------------------------------------------------------------
@@ -2637,31 +2668,35 @@ struct CovCrossIntegrand {
 
 // grid (N = kernel_npoints, 4 tables), block 256: knot x of table y of
 // Covariance._initialize_halo_splines (covariance.py:455-531).  LDS: cov_cross_lds_doubles.
+// (the body of k_cov_cross_knots and of a cross block of k_cov_blocks_knots: per side the epoch
+//  record, its knot-table slab, the ProjDev block and its projection slab; the destination is
+//  the table part of the slab `ct` of layout C -- the body reads none of C's source offsets)
 template <bool BAO>
-__global__ __launch_bounds__(256) void k_cov_cross_knots(chomp_config cfg, TabLayout HL,
-                                                         ProjLayout L, CrossLayout C, int which_a,
-                                                         int which_b, double D_a, double D_b,
-                                                         double* __restrict__ ct) {
+__device__ __forceinline__ void cov_cross_knots_body(
+    const chomp_config& cfg, const TabLayout& HL, const ProjLayout& L, const CrossLayout& C,
+    const double* __restrict__ epa, const double* __restrict__ epb,
+    const double* __restrict__ hta, const double* __restrict__ htb,
+    const double* __restrict__ pdga, const double* __restrict__ pdgb,
+    const double* __restrict__ pta, const double* __restrict__ ptb, int which_a, int which_b,
+    double D_a, double D_b, double* __restrict__ ct) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch Ea, Eb;
   __shared__ ProjDev pda, pdb;
   __shared__ double red[romberg_scratch<4, 2>()];
   __shared__ double sc[4];         // chi_peak_a, chi_peak_b, chi_min_b, chi_max_b
-  copy_doubles(reinterpret_cast<double*>(&Ea), ct + C.ep[0], kEpochDoubles);
-  copy_doubles(reinterpret_cast<double*>(&Eb), ct + C.ep[1], kEpochDoubles);
-  copy_doubles(reinterpret_cast<double*>(&pda), ct + C.pd[0], kProjDoubles);
-  copy_doubles(reinterpret_cast<double*>(&pdb), ct + C.pd[1], kProjDoubles);
+  copy_doubles(reinterpret_cast<double*>(&Ea), epa, kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&Eb), epb, kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pda), pdga, kProjDoubles);
+  copy_doubles(reinterpret_cast<double*>(&pdb), pdgb, kProjDoubles);
   __syncthreads();
   PowerEval Pa, Pb;
-  Pa.stage(cfg, HL, &Ea, ct + C.htab[0], which_a, sm);
-  Pb.stage(cfg, HL, &Eb, ct + C.htab[1], which_b, sm + 12 * (HL.NK - 1));
+  Pa.stage(cfg, HL, &Ea, hta, which_a, sm);
+  Pb.stage(cfg, HL, &Eb, htb, which_b, sm + 12 * (HL.NK - 1));
   const int NC = L.NC, NW = L.NWp;
   double* chi_t = sm + 24 * (HL.NK - 1);                // [NC]
   double* pp_z = chi_t + NC;                            // [4 (NC - 1)]
   double* pp_g = pp_z + 4 * (NC - 1);
   double* wpp = pp_g + 4 * (NC - 1);                    // 4 x [4 (NW - 1)]
-  const double* pta = ct + C.ptab[0];
-  const double* ptb = ct + C.ptab[1];
   copy_doubles(chi_t, pta + L.me_chi[0], NC);
   copy_doubles(pp_z, pta + L.me_pp_z[0], 4 * (NC - 1));
   copy_doubles(pp_g, pta + L.me_pp_g[0], 4 * (NC - 1));
@@ -2725,12 +2760,25 @@ __global__ __launch_bounds__(256) void k_cov_cross_knots(chomp_config cfg, TabLa
     }
   }
 }
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_cov_cross_knots(chomp_config cfg, TabLayout HL,
+                                                         ProjLayout L, CrossLayout C, int which_a,
+                                                         int which_b, double D_a, double D_b,
+                                                         double* __restrict__ ct) {
+  cov_cross_knots_body<BAO>(cfg, HL, L, C, ct + C.ep[0], ct + C.ep[1], ct + C.htab[0],
+                            ct + C.htab[1], ct + C.pd[0], ct + C.pd[1], ct + C.ptab[0],
+                            ct + C.ptab[1], which_a, which_b, D_a, D_b, ct);
+}
 
 // grid 4, block 64: the not-a-knot spline of table blockIdx.x (covariance.py:533-541).
+// (the body of k_cov_cross_spline and of a cross block of k_cov_blocks_spline; one thread)
+__device__ __forceinline__ void cov_cross_spline_body(const CrossLayout& C,
+                                                      double* __restrict__ ct, int T) {
+  spline_build(ct + C.ln_K, ct + C.proj[T], C.N, ct + C.pp[T], ct + C.work[T]);
+}
 __global__ void k_cov_cross_spline(CrossLayout C, double* __restrict__ ct) {
   const int T = blockIdx.x;
-  if (threadIdx.x == 0 && T < 4)
-    spline_build(ct + C.ln_K, ct + C.proj[T], C.N, ct + C.pp[T], ct + C.work[T]);
+  if (threadIdx.x == 0 && T < 4) cov_cross_spline_body(C, ct, T);
 }
 
 // covariance.py:422-453 (_covariance_G_integrand, matching_corrs == False): two two-point terms
@@ -2756,16 +2804,18 @@ struct CovCrossGIntegrand {
 
 // grid n pairs, block 256: Covariance.covariance_G(theta_a, theta_b) of a cross block
 // (covariance.py:361-390).  LDS: N + 16 (N - 1) doubles.
-__global__ __launch_bounds__(256) void k_cov_cross_gaussian(chomp_config cfg, CrossLayout C,
-                                                            const double* __restrict__ ct,
-                                                            const BesselTab* __restrict__ bess_g,
-                                                            double j0_limit, double area,
-                                                            double poiss0, double poiss1,
-                                                            double poiss2, double poiss3,
-                                                            const double* __restrict__ theta_a,
-                                                            const double* __restrict__ theta_b,
-                                                            double* __restrict__ out,
-                                                            double* __restrict__ levels) {
+// (the body of k_cov_cross_gaussian and of a cross block of k_cov_blocks_gaussian)
+__device__ __forceinline__ void cov_cross_gaussian_body(const chomp_config& cfg,
+                                                        const CrossLayout& C,
+                                                        const double* __restrict__ ct,
+                                                        const BesselTab* __restrict__ bess_g,
+                                                        double j0_limit, double area,
+                                                        double poiss0, double poiss1,
+                                                        double poiss2, double poiss3,
+                                                        const double* __restrict__ theta_a,
+                                                        const double* __restrict__ theta_b,
+                                                        double* __restrict__ out,
+                                                        double* __restrict__ levels) {
   extern __shared__ __align__(16) double sm[];
   __shared__ BesselTab B;
   __shared__ double red[romberg_scratch<4, 2>()];
@@ -2798,6 +2848,156 @@ __global__ __launch_bounds__(256) void k_cov_cross_gaussian(chomp_config cfg, Cr
     out[blockIdx.x] = v;
     if (levels) levels[blockIdx.x] = (double)level;
   }
+}
+__global__ __launch_bounds__(256) void k_cov_cross_gaussian(chomp_config cfg, CrossLayout C,
+                                                            const double* __restrict__ ct,
+                                                            const BesselTab* __restrict__ bess_g,
+                                                            double j0_limit, double area,
+                                                            double poiss0, double poiss1,
+                                                            double poiss2, double poiss3,
+                                                            const double* __restrict__ theta_a,
+                                                            const double* __restrict__ theta_b,
+                                                            double* __restrict__ out,
+                                                            double* __restrict__ levels) {
+  cov_cross_gaussian_body(cfg, C, ct, bess_g, j0_limit, area, poiss0, poiss1, poiss2, poiss3,
+                          theta_a, theta_b, out, levels);
+}
+
+// ---------------------------------------------------------------------------
+// The block axis of the Gaussian covariance (chomp_covariance_blocks: every block of a
+// CovarianceMulti, covariance.py:796-871, in one call)
+// ---------------------------------------------------------------------------
+// n correlations give n (n + 1) / 2 blocks (i, j), i <= j, in the row-major order of the upper
+// triangle -- the order of CovarianceMulti.covariance_list.  With one projection set per
+// correlation on the set axis (chomp_kernel_setup_pairs) and one P(k) epoch per correlation in the
+// context, block (i, j) reads set i, set j, epoch i and epoch j where they lie: no snapshot.  The
+// kernels below run the bodies of the single-block kernels above, a diagonal block (i == j) those
+// of the matching path and a cross block those of the cross path -- the same code, so the same
+// bits -- with the block as a grid dimension; the branch is uniform in a workgroup.
+//
+// Every block owns one slab of BlocksLayout's doubles: the table part of CrossLayout (ln K knots
+// | per table the projected spectrum, its spline, its Romberg levels and spline_build's work |
+// 8 scalars).  A diagonal block uses table 0 alone and holds the scalars of CovLayout
+// {ln_K_min, ln_K_max, D_z, chi_peak}, a cross block those of CrossLayout {ln_K_min, ln_K_max,
+// D_a, D_b, chi_peak_a, chi_peak_b}; scalars 6 and 7 are D_a and D_b as k_cov_blocks_prep found
+// them (the knots kernel takes them from there, and rewrites neither).
+// The index block of a call, ints: epoch[n_corr] | (i, j)[n_blocks].
+inline CrossLayout make_blocks_layout(int N) {
+  CrossLayout C = make_cross_layout(N, 0, 0);
+  const int base = C.ln_K;         // (no snapshots in front of the tables)
+  for (int s = 0; s < 2; ++s) C.ep[s] = C.htab[s] = C.pd[s] = C.ptab[s] = -1;
+  C.ln_K -= base;
+  for (int t = 0; t < 4; ++t) {
+    C.proj[t] -= base; C.pp[t] -= base; C.lev[t] -= base; C.work[t] -= base;
+  }
+  C.scal -= base;
+  C.total = (C.scal + 8 + 7) & ~7;
+  return C;
+}
+constexpr int kBlocksScalDa = 6, kBlocksScalDb = 7;
+// The state of chomp_covariance_blocks, beside ProjState and CrossState (which it never touches).
+// The buffers are kept across calls and only grow.
+struct BlocksState {
+  double* d = nullptr;     // n_blocks slabs of C.total doubles
+  int* d_index = nullptr;  // the index block
+  size_t cap = 0, cap_index = 0;
+  CrossLayout C;
+  size_t n_corr = 0;       // correlations of the last call (0: none yet)
+};
+// Table 0 of a block's slab as the matching path's layout.
+__host__ __device__ inline CovLayout blocks_cov_layout(const CrossLayout& C) {
+  CovLayout D;
+  D.N = C.N; D.ln_K = C.ln_K; D.proj = C.proj[0]; D.pp = C.pp[0]; D.lev = C.lev[0];
+  D.scal = C.scal; D.work = C.work[0]; D.total = C.total;
+  return D;
+}
+
+// grid ceil(n_blocks / 64), block 64, a thread per block: the growth factors of block (i, j) --
+// D_a = D(z_bar_i) of set i (Correlation._growth_at_z_bar, correlation.py:94), D_b the growth
+// factor of set i's MultiEpoch 0 at set j's z_bar with MultiEpoch's range rule
+// (covariance.py:468-469: Covariance.kernel.cosmo is correlation a's) -- and the other scalars
+// cleared, so that a slab never shows what an earlier call left.
+__global__ __launch_bounds__(64) void k_cov_blocks_prep(ProjLayout L, CrossLayout C, int n_corr,
+                                                        int n_blocks,
+                                                        const ProjDev* __restrict__ pd,
+                                                        const double* __restrict__ ptab,
+                                                        size_t pstride,
+                                                        const int* __restrict__ index,
+                                                        double* __restrict__ slabs) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b >= n_blocks) return;
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  double* sc = slabs + (size_t)b * C.total + C.scal;
+  const double D_a = pd[i].D_zbar;
+  const double D_b =
+      i == j ? D_a : me_view(L, pd[i], ptab + pstride * i, 0).growth_factor(pd[j].z_bar);
+  for (int q = 0; q < 6; ++q) sc[q] = 0.0;
+  sc[kBlocksScalDa] = D_a;
+  sc[kBlocksScalDb] = D_b;
+}
+
+// grid (N = kernel_npoints, 4 tables, n_blocks), block 256: k_cov_cross_knots for a cross block
+// -- side a (epoch i, set i), side b (epoch j, set j) --, k_cov_proj_knots in the y == 0
+// workgroups of a diagonal block.  LDS: cov_cross_lds_doubles (the larger of the two).
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_cov_blocks_knots(
+    chomp_config cfg, TabLayout HL, ProjLayout L, CrossLayout C, int n_corr,
+    const Epoch* __restrict__ epochs, const double* __restrict__ htab, int which,
+    const ProjDev* __restrict__ pd, const double* __restrict__ ptab, size_t pstride,
+    const int* __restrict__ index, double* __restrict__ slabs) {
+  const int b = blockIdx.z;
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  double* ct = slabs + (size_t)b * C.total;
+  const double D_a = ct[C.scal + kBlocksScalDa], D_b = ct[C.scal + kBlocksScalDb];
+  const int ea = index[i], eb = index[j];
+  if (i == j) {
+    if (blockIdx.y != 0) return;
+    cov_proj_knots_body<BAO>(cfg, HL, L, blocks_cov_layout(C), epochs + ea,
+                             htab + (size_t)ea * HL.stride, which, pd + i, ptab + pstride * i, D_a,
+                             ct);
+    return;
+  }
+  cov_cross_knots_body<BAO>(
+      cfg, HL, L, C, reinterpret_cast<const double*>(epochs + ea),
+      reinterpret_cast<const double*>(epochs + eb), htab + (size_t)ea * HL.stride,
+      htab + (size_t)eb * HL.stride, reinterpret_cast<const double*>(pd + i),
+      reinterpret_cast<const double*>(pd + j), ptab + pstride * i, ptab + pstride * j, which,
+      which, D_a, D_b, ct);
+}
+
+// grid (4, n_blocks), block 64: the serial spline_build of table x of block y, as k_cov_spline /
+// k_cov_cross_spline run it (a diagonal block has table 0 alone).
+__global__ void k_cov_blocks_spline(CrossLayout C, int n_corr, const int* __restrict__ index,
+                                    double* __restrict__ slabs) {
+  const int T = blockIdx.x, b = blockIdx.y;
+  if (threadIdx.x != 0 || T >= 4) return;
+  double* ct = slabs + (size_t)b * C.total;
+  if (index[n_corr + 2 * b] == index[n_corr + 2 * b + 1]) {
+    if (T == 0) cov_spline_body(blocks_cov_layout(C), ct);
+    return;
+  }
+  cov_cross_spline_body(C, ct, T);
+}
+
+// grid (n_pairs, n_blocks), block 256: covariance_G of pair x of block y -- k_cov_cross_gaussian
+// for a cross block, k_cov_gaussian (with proj_power_poisson(0) and (2)) for a diagonal one.
+// poisson [n_blocks][4]; out [n_blocks][n_pairs].  LDS: N + 16 (N - 1) doubles.
+__global__ __launch_bounds__(256) void k_cov_blocks_gaussian(
+    chomp_config cfg, CrossLayout C, int n_corr, const int* __restrict__ index,
+    const double* __restrict__ slabs, const BesselTab* __restrict__ bess_g, double j0_limit,
+    double area, const double* __restrict__ poisson, const double* __restrict__ theta_a,
+    const double* __restrict__ theta_b, double* __restrict__ out) {
+  const int b = blockIdx.y;
+  const double* ct = slabs + (size_t)b * C.total;
+  const double* p = poisson + 4 * (size_t)b;
+  double* o = out + (size_t)b * gridDim.x;
+  if (index[n_corr + 2 * b] == index[n_corr + 2 * b + 1]) {
+    cov_gaussian_body(cfg, blocks_cov_layout(C), ct, bess_g, j0_limit, area, p[0], p[2], theta_a,
+                      theta_b, o, nullptr);
+    return;
+  }
+  cov_cross_gaussian_body(cfg, C, ct, bess_g, j0_limit, area, p[0], p[1], p[2], p[3], theta_a,
+                          theta_b, o, nullptr);
 }
 
 }  // namespace chomp

@@ -828,6 +828,45 @@ int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area
                                     double poisson_3, const double* theta, size_t n,
                                     double* out, int mem);
 
+/* Every Gaussian block of a CovarianceMulti (covariance.py:796-871) in one call.
+ *
+ * Correlation c (c < n_corr) is projection set c of the last chomp_kernel_setup_pairs (or
+ * chomp_kernel_setup_sets) of Bessel order 0 and P(k) epoch epoch[c] of this context, moved to
+ * that set's z_bar by the caller.  The n_blocks = n_corr (n_corr + 1) / 2 blocks (i, j), i <= j,
+ * are in the row-major order of the upper triangle -- (0,0), (0,1) ... (0,n-1), (1,1) ... --, the
+ * order of CovarianceMulti.covariance_list.  A diagonal block is what chomp_kernel_setup (kernel
+ * i) + chomp_covariance_table(which, epoch[i], D_zbar of set i) + chomp_covariance_gaussian with
+ * poisson[b][0] and poisson[b][2] return; a cross block what chomp_covariance_cross_stage of
+ * (kernel i, epoch[i]) and (kernel j, epoch[j]) + chomp_covariance_table_cross(D_a, D_b) +
+ * chomp_covariance_gaussian_cross with poisson[b][0..3] return, D_a = D_zbar of set i and D_b the
+ * growth factor of set i's MultiEpoch at set j's z_bar (:468-469): bit for bit, the blocks being
+ * a grid dimension of kernels that run the single calls' code.  Both sides of a block are read
+ * where they lie (no snapshot), and the call touches neither the context's single projection
+ * set-up nor the state of chomp_covariance_table / chomp_covariance_cross_stage.
+ *
+ * theta holds theta_a[n_pairs] then theta_b[n_pairs] (radians), the same pairs for every block;
+ * out [n_blocks][n_pairs].  theta, poisson and out are host or device arrays as `mem` says
+ * ("Memory-space convention"); epoch is a host array.  j0_limit and area as in
+ * chomp_covariance_gaussian; the transfer function and `which` as in chomp_covariance_table
+ * (an extrapolated spectrum has its constants refreshed first).
+ * CHOMP_ERR_STATE: no set-up of sets, one of another number of sets than n_corr, or of Bessel
+ * order 2.  CHOMP_ERR_ARG: an epoch out of range, more than 65535 blocks (they are a grid's z
+ * dimension), j0_limit or area not positive, a host theta not positive.
+ *
+ * chomp_covariance_blocks_table reads the tables of block `block` of the last call: ln_K [n],
+ * tables [4][n] and levels [4][n] (n = kernel_npoints; rows a, b, ab, ba -- of a diagonal block
+ * row 0 alone, the others zero) and scalars [8]: {ln_K_min, ln_K_max, D_a, D_b, chi_peak_a,
+ * chi_peak_b} of a cross block, {ln_K_min, ln_K_max, D_z, chi_peak, 0, 0} of a diagonal one, then
+ * D_a and D_b as the call's first kernel found them.  Host arrays; any may be NULL. */
+int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr,
+                            const size_t* epoch /*[n_corr]*/, double j0_limit, double area,
+                            const double* poisson /*[n_blocks][4]*/,
+                            const double* theta /*[2][n_pairs]: theta_a then theta_b*/,
+                            size_t n_pairs, double* out /*[n_blocks][n_pairs]*/, int mem);
+int chomp_covariance_blocks_table(chomp_ctx* ctx, size_t block, double* ln_K,
+                                  double* tables /*[4][N]*/, double* levels /*[4][N]*/,
+                                  double* scalars /*[8]*/, size_t n);
+
 /* Super-sample covariance of w(theta), Covariance(corr, corr, nongaussian_cov=False,
  * ssc_cov=True), with a1 = b1 = window a and a2 = b2 = window b of the context's
  * kernel_setup.  Host memory throughout.
