@@ -136,6 +136,8 @@ EXPORTS = [
     "chomp_covariance_cross_stage", "chomp_covariance_table_cross",
     "chomp_covariance_gaussian_cross",
     "chomp_covariance_blocks", "chomp_covariance_blocks_table",
+    "chomp_covariance_ssc_blocks_range", "chomp_covariance_ssc_blocks",
+    "chomp_covariance_ssc_blocks_table",
     "chomp_set_timing", "chomp_get_timing", "chomp_get_status", "chomp_status_post",
     "chomp_status_wait", "chomp_set_tuning",
     "chomp_get_deep_stats", "chomp_stage_k", "chomp_power_plan", "chomp_get_stream",
@@ -474,6 +476,11 @@ def lib():
         L.chomp_covariance_cross_range.argtypes = [vp, c_double_p]
         L.chomp_kernel_ssc_setup_cross.argtypes = L.chomp_kernel_ssc_setup.argtypes
         L.chomp_covariance_ssc_cross.argtypes = [vp, d, vp, sz, vp, vp, vp]
+        L.chomp_covariance_ssc_blocks_range.argtypes = [vp, sz, c_double_p]
+        L.chomp_covariance_ssc_blocks.argtypes = [vp, sz, ctypes.POINTER(sz), d, d, d, c_double_p,
+                                                  c_double_p, sz, d, vp, sz, vp, i]
+        L.chomp_covariance_ssc_blocks_table.argtypes = [vp, sz, c_double_p, c_double_p, c_double_p,
+                                                        c_double_p, c_double_p]
         L.chomp_covariance_fourier_zbar.argtypes = [vp, c_double_p, sz, c_double_p]
         L.chomp_covariance_fourier_table.argtypes = [vp, i, ctypes.POINTER(sz), c_double_p, sz,
                                                      c_double_p, c_double_p, c_double_p]
@@ -1393,6 +1400,68 @@ class Context(object):
         if knots:
             return outs[0], outs[1], outs[2].astype(int)
         return outs[0]
+
+    def covariance_ssc_blocks_range(self, n_corr):
+        """[n_blocks, 4] = (z_min, z_max, chi_min, chi_max) of the windows of every block (i, j),
+        i <= j, of the n_corr projection sets of the last kernel_setup_pairs, in the row-major
+        order of the upper triangle: a diagonal block's as kernel_info gives them, a cross block's
+        as covariance_cross_range does.  One launch, one read-back."""
+        n_corr = int(n_corr)
+        out = numpy.empty((n_corr * (n_corr + 1) // 2, 4))
+        self._check(self._L.chomp_covariance_ssc_blocks_range(self._h, n_corr,
+                                                              out.ctypes.data_as(c_double_p)))
+        return out
+
+    def covariance_ssc_blocks(self, epochs, ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, ln_chi,
+                              sigma2, area, theta_a, theta_b=None):
+        """covariance_ssc of every block (i, j), i <= j, of len(epochs) correlations for the same
+        pairs of bin centres (chomp_covariance_ssc_blocks): [n_blocks, n_pairs], the blocks in the
+        row-major order of the upper triangle.  Correlation c is projection set c of the last
+        kernel_setup_pairs and halo epoch epochs[c]; a diagonal block is what kernel_setup +
+        kernel_ssc_setup + covariance_ssc return, a cross block what two covariance_cross_stage +
+        kernel_ssc_setup(cross=True) + covariance_ssc_cross do, bit for bit.  ln_chi, sigma2
+        [n_blocks, corr_npoints]: every block's own sigma^2 knots (host arrays).
+        (theta_a, theta_b): host arrays of one length; or theta_a alone, a contiguous float64
+        torch cuda tensor holding theta_a[n] then theta_b[n], which stays on the device (so does
+        the result)."""
+        ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
+        n_blocks = ep.size * (ep.size + 1) // 2
+        x = numpy.ascontiguousarray(ln_chi, dtype=numpy.float64)
+        y = numpy.ascontiguousarray(sigma2, dtype=numpy.float64)
+        if x.ndim != 2 or x.shape[0] != n_blocks or y.shape != x.shape:
+            raise ValueError("covariance_ssc_blocks: ln_chi and sigma2 must be [%d, n_sigma]"
+                             % n_blocks)
+        pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
+        self._ssc_blocks_pairs = None
+        out = self._run(self._L.chomp_covariance_ssc_blocks, [pairs],
+                        lambda mem, new, th: (
+                            ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                            float(ln_ktheta_min), float(ln_ktheta_max), float(j0_ssc_limit),
+                            x.ctypes.data_as(c_double_p), y.ctypes.data_as(c_double_p),
+                            x.shape[1], float(area), th, _numel(th) // 2,
+                            new((n_blocks, _numel(th) // 2)), mem))[0]
+        self._ssc_blocks_pairs = _numel(pairs) // 2      # (what covariance_ssc_blocks_table sizes by)
+        return out
+
+    def covariance_ssc_blocks_table(self, block, knots=False):
+        """One block of the last covariance_ssc_blocks: (info[7] = z_bar_NG, chi(z_bar_NG),
+        growth_factor(z_bar_NG), z_min, z_max, chi_min, chi_max; the kernel_ssc table and its
+        Romberg levels, each [kernel_npoints, kernel_npoints]); with knots=True also (k_b knots,
+        Romberg levels), each [n_pairs, kernel_npoints]."""
+        n = self.config.kernel_npoints
+        info, tab, lev = numpy.empty(7), numpy.empty((n, n)), numpy.empty((n, n))
+        kb = kl = None
+        n_pairs = getattr(self, "_ssc_blocks_pairs", None) if knots else None
+        if knots and not n_pairs:
+            raise ChompError("covariance_ssc_blocks_table before covariance_ssc_blocks")
+        if n_pairs is not None:
+            kb, kl = numpy.empty((int(n_pairs), n)), numpy.empty((int(n_pairs), n))
+        ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
+        self._check(self._L.chomp_covariance_ssc_blocks_table(
+            self._h, int(block), ptr(info), ptr(tab), ptr(lev), ptr(kb), ptr(kl)))
+        if n_pairs is None:
+            return info, tab, lev.astype(int)
+        return info, tab, lev.astype(int), kb, kl.astype(int)
 
     def covariance_fourier_zbar(self, z):
         """_calculate_zbar of the four window pairs a1a2, b1b2, a1b2, b1a2 in the two staged slots

@@ -865,9 +865,13 @@ class CovarianceMulti(Covariance):
             raise _lib.ChompScopeError("get_covariance_batched: %s; use get_covariance" % why)
         blocks = [cov for row in self.covariance_list for cov in row]
         corrs = [row[0].corr_a for row in self.covariance_list]
-        if any(cov.nongaussian_cov or cov.ssc_cov for cov in blocks):
+        if any(cov.nongaussian_cov for cov in blocks):
             refuse("the batch serves the Gaussian and Poisson terms, not the trispectrum "
                    "(nongaussian_cov) or super-sample (ssc_cov) terms")
+        ssc = bool(blocks[0].ssc_cov)
+        if any(bool(cov.ssc_cov) != ssc for cov in blocks):
+            refuse("the blocks differ in ssc_cov: the batch adds the super-sample term to every "
+                   "block or to none")
         if any(cov.poisson_noise_only for cov in blocks):
             refuse("poisson_noise_only needs no device")
         names = set(cov.power_spec for cov in blocks)
@@ -876,6 +880,19 @@ class CovarianceMulti(Covariance):
         centers = [[b.center for b in cov.annular_bins] for cov in blocks]
         if any(c != centers[0] for c in centers) or any(cov.area != blocks[0].area for cov in blocks):
             refuse("the blocks' angular bins or survey areas differ")
+        if ssc:
+            k0 = blocks[0].kernel
+            for i, row in enumerate(self.covariance_list):
+                for j, cov in enumerate(row, i):
+                    k = cov.kernel
+                    if (k.ln_ktheta_min, k.ln_ktheta_max, k._j0_ssc_limit) != (
+                            k0.ln_ktheta_min, k0.ln_ktheta_max, k0._j0_ssc_limit):
+                        refuse("block (%d, %d): its KernelCovariance has another k theta range "
+                               "or J0 limit than that of block (0, 0)" % (i, j))
+                    if not k.z_min < k.z_max:
+                        refuse("block (%d, %d): the four windows have no redshift in common "
+                               "(z_min = %g >= z_max = %g, kernel.py:910-916)"
+                               % (i, j, k.z_min, k.z_max))
         first = corrs[0].kernel
         for i, corr in enumerate(corrs):
             k = corr.kernel
@@ -923,10 +940,48 @@ class CovarianceMulti(Covariance):
                     refuse(str(e))
         return corrs, names.pop()
 
+    @staticmethod
+    def _ssc_blocks_knots(cosmos, ranges):
+        """The sigma^2 knots of every block, (ln chi, sigma^2), each [n_blocks, corr_npoints], as
+        KernelCovariance._ssc / _ssc_four lay them (kernel.py:1208-1222): block (i, j) takes
+        logspace(log10 chi_min, log10 chi_max, corr_npoints) of its own range -- ranges
+        [n_blocks, 4] = z_min, z_max, chi_min, chi_max, the blocks in the row-major order of the
+        upper triangle -- and sigma_r(chi, 0.0)^2 of correlation i's MultiEpoch, cosmos[i]: one
+        sigma_r call per row i of blocks."""
+        n = len(cosmos)
+        npts = defaults.default_precision["corr_npoints"]
+        ranges = numpy.asarray(ranges, dtype=numpy.float64).reshape(n * (n + 1) // 2, 4)
+        ln_chi = numpy.empty((ranges.shape[0], npts))
+        sigma2 = numpy.empty((ranges.shape[0], npts))
+        b = 0
+        for i, cosmo in enumerate(cosmos):
+            rows = slice(b, b + n - i)
+            chi = numpy.stack([numpy.logspace(numpy.log10(float(r[2])), numpy.log10(float(r[3])),
+                                              npts) for r in ranges[rows]])
+            sigma = numpy.asarray(cosmo.sigma_r(chi.ravel(), 0.0),
+                                  dtype=numpy.float64).reshape(chi.shape)
+            ln_chi[rows] = numpy.log(chi)
+            sigma2[rows] = sigma * sigma
+            b += n - i
+        return ln_chi, sigma2
+
     def get_covariance_batched(self, with_status=False):
         """get_covariance() with every block in one device call: the same `wcovar`, and the same
         `covar` in every ``covariance_list[i][j - i]`` (the Poisson diagonal of the matching
         blocks included), bit for bit what the loop over fresh correlations returns.
+
+        Blocks built with ssc_cov=True (all of them; with more than one correlation that means
+        cross_terms=True) get the super-sample term as well: the epochs also carry the knot tables
+        of the response (FAM_SSC), ONE more read-back gives every block's chi range
+        (Context.covariance_ssc_blocks_range), the host lays the sigma^2 knots of every block
+        (_ssc_blocks_knots: one MultiEpoch.sigma_r call per row of blocks), and
+        Context.covariance_ssc_blocks runs kernel_ssc and covariance_ssc of every block in seven
+        launches; its values ([n_blocks, n_pairs], kept in `self.blocks_ssc`; None without the
+        term) are added to the Gaussian ones before the blocks are filled.  The
+        batch builds neither the blocks' own KernelCovariance state (z_bar_NG, _kernel_ssc_array,
+        ...) nor their HaloSuperSampleCovariance copies: it is what the loop returns for copies
+        made from halos that had built no tables yet (a copy otherwise keeps the tables its halo
+        had at construction, stale ones included; that is not reproduced).
 
         The work: the correlations' kernels as projection sets on one kept grid.HaloGrid's context
         (Kernel._setup_pairs_on), ONE read-back of every kernel's z_bar -- the only
@@ -943,9 +998,11 @@ class CovarianceMulti(Covariance):
         and returned as the second element with with_status=True.
 
         ChompScopeError ("get_covariance_batched: <why>; use get_covariance", before any launch):
-        nongaussian_cov, ssc_cov or poisson_noise_only; blocks whose power_spec, bins or areas
-        differ; a kernel that is not exactly kernel.Kernel, has an assigned z_bar, a tabulated
-        redshift distribution, a w0-wa cosmology or another k theta range; a halo
+        nongaussian_cov or poisson_noise_only; blocks that differ in ssc_cov and, with it, in the
+        k theta range of their KernelCovariance, or whose four windows have no redshift in common
+        (the block is named); blocks whose power_spec, bins or areas differ; a kernel that is not
+        exactly kernel.Kernel, has an assigned z_bar, a tabulated redshift distribution, a w0-wa
+        cosmology or another k theta range; a halo
         Correlation.correlation_hods would refuse, an HOD of another class, halos with different
         halo dictionaries or mass functions, two correlations sharing one Halo object; anything
         Covariance refuses for a cross block.  And, once z_bar is known: correlation 0's halo away
@@ -977,10 +1034,14 @@ class CovarianceMulti(Covariance):
                 "get_covariance_batched: the halo of correlation 0 is at z = %r, not at its "
                 "kernel's z_bar = %r (keep_halo_z_bar): the loop evaluates the first block there; "
                 "use get_covariance" % (float(h0.get_redshift()), float(z_bar[0])))
-        hg.set_parameters(cosmo=cosmos, z=z_bar, hod=hods)
-        hg.setup(power_spec)
         blocks = [cov for row in self.covariance_list for cov in row]
         first = blocks[0]
+        ssc = bool(first.ssc_cov)
+        hg.set_parameters(cosmo=cosmos, z=z_bar, hod=hods)
+        if ssc:      # (the response's knot tables h_m, pp_mm, I_1^2 beside the spectrum's own)
+            hg.setup(power_spec, families=_lib.FAM_SSC)
+        else:
+            hg.setup(power_spec)
         nb = len(first.annular_bins)
         iu = numpy.triu_indices(nb)
         centers = numpy.array([b.center for b in first.annular_bins])
@@ -989,6 +1050,15 @@ class CovarianceMulti(Covariance):
             code, numpy.arange(n), first._j0_limit, first.area,
             [[cov.proj_power_poisson(p) for p in range(4)] for cov in blocks],
             centers[iu[0]], centers[iu[1]])
+        self.blocks_ssc = None
+        if ssc and nb:
+            ranges = hg.ctx.covariance_ssc_blocks_range(n)   # (synchronises: chi range per block)
+            ln_chi, sigma2 = self._ssc_blocks_knots([c.kernel.cosmo for c in corrs], ranges)
+            k0 = first.kernel
+            self.blocks_ssc = hg.ctx.covariance_ssc_blocks(
+                numpy.arange(n), k0.ln_ktheta_min, k0.ln_ktheta_max, k0._j0_ssc_limit, ln_chi,
+                sigma2, first.area, centers[iu[0]], centers[iu[1]])
+            vals = vals + self.blocks_ssc                    # (the loop's order, get_covariance)
         words = hg.status()                              # (synchronises: the words of this result)
         self.blocks_status = words
         for cov, v in zip(blocks, vals):

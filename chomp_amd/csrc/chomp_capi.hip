@@ -240,6 +240,9 @@ struct chomp_ctx {
   FourierState fourier;         // CovarianceFourier: the four pairs' scalars, Limber tables and splines
   BlocksState blocks;           // chomp_covariance_blocks: one table slab per block of a CovarianceMulti
   StagedBlock sh_blocks;        // ... and its index block
+  SscBlocksState ssc_blocks;    // chomp_covariance_ssc_blocks: one kernel_ssc slab per block
+  StagedBlock sh_ssc_blocks;    // ... and its index block
+  std::vector<double> sets_z_min, sets_z_max;   // per set of `sets`: the redshifts its two windows share
   // The side stream.  The projection set-up (chomp_kernel_setup / chomp_multi_epoch_setup:
   // a chain of six small launches) depends on nothing the halo set-up produces, and C_l on
   // nothing w(theta) produces: they run here, beside the context's stream, ordered against it
@@ -712,7 +715,8 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
                   ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
                   ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
                   ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4, ctx->d_prof,
-                  ctx->sets.d_pd, ctx->sets.d_pd_init, ctx->sets.d_tab, ctx->blocks.d, ctx->blocks.d_index};
+                  ctx->sets.d_pd, ctx->sets.d_pd_init, ctx->sets.d_tab, ctx->blocks.d, ctx->blocks.d_index,
+                  ctx->ssc_blocks.d, ctx->ssc_blocks.d_kb, ctx->ssc_blocks.d_index, ctx->ssc_blocks.d_sigma};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* p : ctx->graveyard) (void)hipFree(p);
@@ -720,7 +724,8 @@ void chomp_ctx_destroy(chomp_ctx* ctx) {
   for (StagedBlock* b : {&ctx->sh_cosmo, &ctx->sh_z, &ctx->sh_mass, &ctx->sh_profile, &ctx->sh_hod,
                          &ctx->sh_slot, &ctx->sh_first, &ctx->sh_delta_b, &ctx->sh_proj, &ctx->sh_pp[0],
                          &ctx->sh_pp[1], &ctx->sh_de_knots, &ctx->sh_de_slot, &ctx->de_ep.sh_par,
-                         &ctx->de_proj.sh_par, &ctx->sh_sets, &ctx->sh_blocks})
+                         &ctx->de_proj.sh_par, &ctx->sh_sets, &ctx->sh_blocks,
+                         &ctx->sh_ssc_blocks})
     b->release();
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);

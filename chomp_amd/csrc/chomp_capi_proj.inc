@@ -431,6 +431,12 @@ static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, con
   HIPCHK(hipMemcpyAsync(S.d_pd, S.d_pd_init, n_set * sizeof(ProjDev), hipMemcpyDeviceToDevice, ctx->stream));
   S.L = L;
   S.host = pd[0];                   // (what the sets share: the ln k theta range and the order)
+  ctx->sets_z_min.resize(n_set);    // kernel.py:910-916, each set's share (as CrossState::z_min / z_max)
+  ctx->sets_z_max.resize(n_set);
+  for (size_t s = 0; s < n_set; ++s) {
+    ctx->sets_z_min[s] = std::max(pd[s].w_z_min[0], pd[s].w_z_min[1]);
+    ctx->sets_z_max[s] = std::min(pd[s].w_z_max[0], pd[s].w_z_max[1]);
+  }
   const unsigned Z = (unsigned)n_set;
   const size_t stride = (size_t)L.total;
   hipLaunchKernelGGL(k_proj_chi_sets, dim3(L.NC, 4, Z), dim3(64), 0, ctx->stream, c, L, S.d_pd, S.d_tab, stride);
@@ -1992,6 +1998,221 @@ int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta,
                      (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
                      ctx->stream, ctx->cfg, area, d_knots, d_out);
   return st.finish();
+}
+
+// ---------------------------------------------------------------------------
+// The super-sample term of every block of a CovarianceMulti in one call (chomp_cov_kernels.h,
+// "The block axis of the super-sample term")
+// ---------------------------------------------------------------------------
+// What both calls ask of the sets: a set-up of n_corr sets of order 0, at most 65535 blocks, and
+// in every block windows with a redshift in common (check_cross_windows' rule, from the host's
+// ranges: nothing is launched).
+static int ssc_blocks_check(chomp_ctx* ctx, const char* who, size_t n_corr) {
+  const std::string w = std::string(who) + ": ";
+  const ProjSets& S = ctx->sets;
+  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, std::string(who) + " before kernel_setup_pairs / kernel_setup_sets");
+  if (S.n != n_corr)
+    return fail(ctx, CHOMP_ERR_STATE, w + "n_corr is not the number of sets of the last "
+                                          "kernel_setup_pairs / kernel_setup_sets");
+  if (S.host.order != 0)
+    return fail(ctx, CHOMP_ERR_STATE, w + "the sets are of Bessel order 2 (the covariance of "
+                                          "w(theta) takes the windows of a Kernel, order 0)");
+  if (n_corr * (n_corr + 1) / 2 > 65535)                  // (n_corr <= kProjSetsMax)
+    return fail(ctx, CHOMP_ERR_ARG, w + "more than 65535 blocks (a grid's z dimension)");
+  for (size_t i = 0; i < n_corr; ++i)
+    for (size_t j = i; j < n_corr; ++j)
+      if (!(std::max(ctx->sets_z_min[i], ctx->sets_z_min[j]) <
+            std::min(ctx->sets_z_max[i], ctx->sets_z_max[j])))
+        return fail(ctx, CHOMP_ERR_SCOPE, w + "block (" + std::to_string(i) + ", " + std::to_string(j) +
+                                              "): the four windows have no redshift in common "
+                                              "(kernel.py:910-916 would give z_min >= z_max)");
+  return CHOMP_OK;
+}
+
+// The index block of n_corr correlations (chomp_cov_kernels.h): epoch | (i, j) | the diagonal
+// blocks | the cross blocks.  epoch == nullptr: epoch c for correlation c (the range call reads
+// no epoch; with these the block is most often the one the call behind it sends).
+static std::vector<int> ssc_blocks_index(size_t n_corr, const size_t* epoch) {
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  std::vector<int> index(n_corr + 3 * n_blocks);
+  for (size_t c = 0; c < n_corr; ++c) index[c] = epoch ? (int)epoch[c] : (int)c;
+  int* diag = index.data() + n_corr + 2 * n_blocks;
+  int* cross = diag + n_corr;
+  size_t b = 0;
+  for (size_t i = 0; i < n_corr; ++i)
+    for (size_t j = i; j < n_corr; ++j, ++b) {
+      index[n_corr + 2 * b] = (int)i;
+      index[n_corr + 2 * b + 1] = (int)j;
+      *(i == j ? diag : cross)++ = (int)b;
+    }
+  return index;
+}
+
+static int ssc_blocks_upload_index(chomp_ctx* ctx, size_t n_corr, const size_t* epoch) {
+  SscBlocksState& B = ctx->ssc_blocks;
+  const std::vector<int> index = ssc_blocks_index(n_corr, epoch);
+  const int* before = B.d_index;
+  const int rc = ensure(ctx, &B.d_index, &B.cap_index, index.size());
+  if (rc) return rc;
+  if (B.d_index != before) ctx->sh_ssc_blocks.reset();
+  return upload(ctx, B.d_index, index.data(), index.size() * sizeof(int), ctx->sh_ssc_blocks);
+}
+
+int chomp_covariance_ssc_blocks_range(chomp_ctx* ctx, size_t n_corr, double* info) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!info || n_corr == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks_range: bad args");
+  { const int rcc = ssc_blocks_check(ctx, "covariance_ssc_blocks_range", n_corr); if (rcc) return rcc; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const ProjSets& S = ctx->sets;
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  int rc = ssc_blocks_upload_index(ctx, n_corr, nullptr);
+  if (rc) return rc;
+  Staging st(ctx, CHOMP_HOST, "covariance_ssc_blocks_range");
+  double* d_out;
+  st.out(info, 4 * n_blocks, &d_out);
+  rc = st.place();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ssc_blocks_range, dim3((unsigned)((n_blocks + 63) / 64)), dim3(64), 0,
+                     ctx->stream, ctx->cfg, S.L, (int)n_corr, (int)n_blocks, S.d_pd, S.d_tab,
+                     (size_t)S.L.total, ctx->ssc_blocks.d_index, d_out);
+  return st.finish();
+}
+
+// Correlation c is projection set c of the last set-up of sets and halo epoch epoch[c] of this
+// context; block (i, j) reads both sides where they lie.  Neither ctx->proj (d_ssc included) nor
+// ctx->cross nor the state of chomp_covariance_blocks is touched.
+int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch,
+                                double ln_ktheta_min, double ln_ktheta_max, double j0_ssc_limit,
+                                const double* ln_chi, const double* sigma2, size_t n_sigma,
+                                double area, const double* theta, size_t n_pairs, double* out,
+                                int mem) {
+  StageRange range_(ctx, "chomp:covariance_ssc_blocks");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!epoch || !ln_chi || !sigma2 || !theta || !out || n_corr == 0 || n_pairs == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: bad args");
+  Staging st(ctx, mem, "covariance_ssc_blocks");
+  if (st.rc) return st.rc;
+  { const int rcc = ssc_blocks_check(ctx, "covariance_ssc_blocks", n_corr); if (rcc) return rcc; }
+  for (size_t c = 0; c < n_corr; ++c) {
+    const int rcp = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch[c], 1, true);
+    if (rcp) return fail(ctx, rcp, "covariance_ssc_blocks: correlation " + std::to_string(c) + ": " + ctx->err);
+  }
+  const ProjSets& S_ = ctx->sets;
+  const ProjLayout& L = S_.L;
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  if (!(ln_ktheta_max > ln_ktheta_min) || !(j0_ssc_limit > 0.0))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: ln(k theta) range / J0 limit");
+  const int N = L.NKT;
+  if (n_sigma < 4 || n_sigma > 256 || N < 4 || N > 256)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: corr_npoints and kernel_npoints must be 4..256");
+  for (size_t b = 0; b < n_blocks; ++b)
+    for (size_t q = 1; q < n_sigma; ++q)
+      if (!(ln_chi[b * n_sigma + q] > ln_chi[b * n_sigma + q - 1]))
+        return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: block " + std::to_string(b) +
+                                        ": ln chi knots must increase");
+  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: area must be positive");
+  if (n_pairs > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: at most 65535 pairs a call");
+  if (st.host)
+    for (size_t q = 0; q < 2 * n_pairs; ++q)
+      if (!(theta[q] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: theta must be positive");
+  HIPCHK(hipSetDevice(ctx->device));
+  const SscLayout S = make_ssc_layout(N, (int)n_sigma);
+  const int NK = ctx->cfg.kernel_npoints;
+  const size_t n_cross = n_blocks - n_corr;
+  const size_t sh_diag = (size_t)ssc_table_lds_doubles(L, S.NS, false) * sizeof(double);
+  const size_t sh_four = (size_t)ssc_table_lds_doubles(L, S.NS, true) * sizeof(double);
+  if (!fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_table<false>), sh_diag) ||
+      (n_cross && !fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_table<true>), sh_four)))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: cosmo/window/corr_npoints too large "
+                                    "for the windows of a block");
+  // (one kernel runs both k_b bodies: the launch takes the LDS of the larger)
+  const size_t sh_kb = (size_t)ssc_kb_cross_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
+  if (!(ctx->with_bao ? fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_kb<true>), sh_kb)
+                      : fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_kb<false>), sh_kb)))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: halo/kernel_npoints too large for the "
+                                    "two responses of a cross block");
+  SscBlocksState& B = ctx->ssc_blocks;
+  B.n_corr = 0;
+  int rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)S.total);
+  if (!rc) rc = ensure(ctx, &B.d_kb, &B.cap_kb, 2 * n_blocks * n_pairs * (size_t)NK);
+  if (!rc) rc = ensure(ctx, &B.d_sigma, &B.cap_sigma, 2 * n_blocks * n_sigma);
+  if (!rc) rc = ssc_blocks_upload_index(ctx, n_corr, epoch);
+  if (rc) return rc;
+  double* d_ln_chi = B.d_sigma;
+  double* d_sigma2 = d_ln_chi + n_blocks * n_sigma;
+  HIPCHK(hipMemcpyAsync(d_ln_chi, ln_chi, n_blocks * n_sigma * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  HIPCHK(hipMemcpyAsync(d_sigma2, sigma2, n_blocks * n_sigma * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  const double* d_theta;
+  double* d_out;
+  st.in(theta, 2 * n_pairs, &d_theta);
+  st.out(out, n_blocks * n_pairs, &d_out);
+  rc = st.place();
+  if (rc) return rc;
+  B.S = S;
+  const int nc = (int)n_corr;
+  const unsigned Z = (unsigned)n_blocks;
+  const size_t pstride = (size_t)L.total;
+  const int* d_diag = B.d_index + n_corr + 2 * n_blocks;
+  const int* d_cross = d_diag + n_corr;
+  const unsigned n_tab = (unsigned)(N * (N + 1) / 2);
+  hipLaunchKernelGGL(k_ssc_blocks_prep<false>, dim3((unsigned)n_corr), dim3(256), 0, ctx->stream,
+                     ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
+                     ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
+  if (n_cross)
+    hipLaunchKernelGGL(k_ssc_blocks_prep<true>, dim3((unsigned)n_cross), dim3(256), 0, ctx->stream,
+                       ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_cross,
+                       ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
+  hipLaunchKernelGGL(k_ssc_blocks_table<false>, dim3(n_tab, (unsigned)n_corr), dim3(256), sh_diag,
+                     ctx->stream, ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
+                     ctx->d_j0, B.d);
+  if (n_cross)
+    hipLaunchKernelGGL(k_ssc_blocks_table<true>, dim3(n_tab, (unsigned)n_cross), dim3(256), sh_four,
+                       ctx->stream, ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index,
+                       d_cross, ctx->d_j0, B.d);
+  hipLaunchKernelGGL(k_ssc_blocks_bicubic, dim3(Z), dim3(256), 0, ctx->stream, S, B.d);
+  double* d_knots = B.d_kb;
+  double* d_lev = B.d_kb + n_blocks * n_pairs * (size_t)NK;
+  with_flag(ctx->with_bao, [&](auto BAO) {
+    hipLaunchKernelGGL(k_ssc_blocks_kb<BAO>, dim3((unsigned)NK, (unsigned)n_pairs, Z), dim3(256),
+                       sh_kb, ctx->stream, ctx->cfg, ctx->L, S, nc, ctx->d_epochs, ctx->d_tab,
+                       B.d_index, B.d, d_theta, d_theta + n_pairs, d_knots, d_lev);
+  });
+  hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256),
+                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double), ctx->stream, ctx->cfg, area,
+                     d_knots, d_out);
+  HIPCHK(hipGetLastError());
+  B.n_corr = n_corr;
+  B.n_pairs = n_pairs;
+  return st.finish();
+}
+
+// One block of the last chomp_covariance_ssc_blocks (host arrays, any may be NULL).
+int chomp_covariance_ssc_blocks_table(chomp_ctx* ctx, size_t block, double* info, double* table,
+                                      double* levels, double* kb_knots, double* kb_levels) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  const SscBlocksState& B = ctx->ssc_blocks;
+  if (B.n_corr == 0)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc_blocks_table before covariance_ssc_blocks");
+  const size_t n_blocks = B.n_corr * (B.n_corr + 1) / 2;
+  if (block >= n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks_table: block");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const SscLayout& S = B.S;
+  const double* st = B.d + block * (size_t)S.total;
+  if (info) {
+    HIPCHK(hipMemcpy(info, st + S.scal + kSscZBar, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(info + 3, st + S.scal + kSscZMin, 4 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  const size_t bytes = (size_t)S.N * S.N * sizeof(double);
+  if (table) HIPCHK(hipMemcpy(table, st + S.tab, bytes, hipMemcpyDeviceToHost));
+  if (levels) HIPCHK(hipMemcpy(levels, st + S.lev, bytes, hipMemcpyDeviceToHost));
+  const size_t row = B.n_pairs * (size_t)ctx->cfg.kernel_npoints;
+  if (kb_knots) HIPCHK(hipMemcpy(kb_knots, B.d_kb + block * row, row * sizeof(double), hipMemcpyDeviceToHost));
+  if (kb_levels)
+    HIPCHK(hipMemcpy(kb_levels, B.d_kb + (n_blocks + block) * row, row * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -192,10 +192,12 @@ struct SscKernelIntegrand {
 // FOUR: the four windows of a cross block and their common range -- z_min = max, z_max = min of the
 // two sides', chi_min = max(window_precision, chi(z_min)), chi_max = chi(z_max) on slot 0's
 // MultiEpoch (kernel.py:910-931).  The range goes into the scalars in both cases.
+// (the body of k_ssc_prep and of k_ssc_blocks_prep)
 template <bool FOUR>
-__global__ __launch_bounds__(256) void k_ssc_prep(chomp_config cfg, ProjLayout L, SscLayout S,
-                                                  CovSrc src, double ln_kt_min, double ln_kt_max,
-                                                  double j0_limit, double* __restrict__ st) {
+__device__ __forceinline__ void ssc_prep_body(const chomp_config& cfg, const ProjLayout& L,
+                                              const SscLayout& S, const CovSrc& src,
+                                              double ln_kt_min, double ln_kt_max, double j0_limit,
+                                              double* __restrict__ st) {
   __shared__ double cand[256];
   __shared__ double work[2 * 256];
   const ProjDev& pd = *src.pd;
@@ -245,12 +247,18 @@ __global__ __launch_bounds__(256) void k_ssc_prep(chomp_config cfg, ProjLayout L
   st[S.scal + kSscChiMin] = chi_min;
   st[S.scal + kSscChiMax] = chi_max;
 }
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ssc_prep(chomp_config cfg, ProjLayout L, SscLayout S,
+                                                  CovSrc src, double ln_kt_min, double ln_kt_max,
+                                                  double j0_limit, double* __restrict__ st) {
+  ssc_prep_body<FOUR>(cfg, L, S, src, ln_kt_min, ln_kt_max, j0_limit, st);
+}
 
 // grid 1, block 64: out[4] = z_min, z_max, chi_min, chi_max of a cross block's four windows, as
 // k_ssc_prep<true> finds them -- what the host lays the sigma^2 knots over before that launch.
-__global__ void k_cov_cross_range(chomp_config cfg, ProjLayout L, CovSrc src,
-                                  double* __restrict__ out) {
-  if (threadIdx.x != 0) return;
+// (the body of k_cov_cross_range and of a cross block of k_ssc_blocks_range; one thread calls)
+__device__ __forceinline__ void cov_cross_range_body(const chomp_config& cfg, const ProjLayout& L,
+                                                     const CovSrc& src, double* __restrict__ out) {
   const ProjDev& pd = *src.pd;
   const ProjDev& pb = *src.pd_b;
   const MEView me = me_view(L, pd, src.ptab, 0);
@@ -262,18 +270,24 @@ __global__ void k_cov_cross_range(chomp_config cfg, ProjLayout L, CovSrc src,
   out[2] = cfg.window_precision > c0 ? cfg.window_precision : c0;
   out[3] = me.comoving_distance(z_max);
 }
+__global__ void k_cov_cross_range(chomp_config cfg, ProjLayout L, CovSrc src,
+                                  double* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  cov_cross_range_body(cfg, L, src, out);
+}
 
 // grid n integrals, block 256.  ln_a == nullptr: the knot table of _initialize_ssc_spline
 // (kernel.py:1132-1153), block b -> the b-th (i, j), i <= j, of the upper triangle, written to
 // [i][j] and [j][i] with its Romberg level; otherwise raw_kernel_ssc(ln_a[b], ln_b[b]) into out.
+// (the body of k_ssc_table and of k_ssc_blocks_table; workgroup blockIdx.x)
 template <bool FOUR>
-__global__ __launch_bounds__(256) void k_ssc_table(chomp_config cfg, ProjLayout L, SscLayout S,
-                                                   CovSrc src,
-                                                   const BesselTab* __restrict__ bess_g,
-                                                   double* __restrict__ st,
-                                                   const double* __restrict__ ln_a,
-                                                   const double* __restrict__ ln_b,
-                                                   double* __restrict__ out) {
+__device__ __forceinline__ void ssc_table_body(const chomp_config& cfg, const ProjLayout& L,
+                                               const SscLayout& S, const CovSrc& src,
+                                               const BesselTab* __restrict__ bess_g,
+                                               double* __restrict__ st,
+                                               const double* __restrict__ ln_a,
+                                               const double* __restrict__ ln_b,
+                                               double* __restrict__ out) {
   extern __shared__ __align__(16) double sm[];
   __shared__ ProjDev pd, pd_b;      // (pd_b: FOUR only)
   __shared__ BesselTab B;
@@ -336,6 +350,16 @@ __global__ __launch_bounds__(256) void k_ssc_table(chomp_config cfg, ProjLayout 
     }
   }
 }
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ssc_table(chomp_config cfg, ProjLayout L, SscLayout S,
+                                                   CovSrc src,
+                                                   const BesselTab* __restrict__ bess_g,
+                                                   double* __restrict__ st,
+                                                   const double* __restrict__ ln_a,
+                                                   const double* __restrict__ ln_b,
+                                                   double* __restrict__ out) {
+  ssc_table_body<FOUR>(cfg, L, S, src, bess_g, st, ln_a, ln_b, out);
+}
 
 // The tensor-product not-a-knot bicubic of an N x N table over the knots x in both directions
 // -- what FITPACK's regrid with s = 0 and kx = ky = 3 interpolates with (knots at x_0 x4, x_2 ..
@@ -369,8 +393,12 @@ __device__ __forceinline__ void bicubic_build(int N, const double* x, const doub
 }
 
 // grid 1, block 256: the bicubic of the kernel_ssc table.
-__global__ __launch_bounds__(256) void k_ssc_bicubic(SscLayout S, double* __restrict__ st) {
+// (the body of k_ssc_bicubic and of k_ssc_blocks_bicubic)
+__device__ __forceinline__ void ssc_bicubic_body(const SscLayout& S, double* __restrict__ st) {
   bicubic_build(S.N, st + S.kx, st + S.tab, st + S.rowt, st + S.work, st + S.bic);
+}
+__global__ __launch_bounds__(256) void k_ssc_bicubic(SscLayout S, double* __restrict__ st) {
+  ssc_bicubic_body(S, st);
 }
 
 // One cell of a bicubic of bicubic_build: sum_{p,q} c[4 p + q] da^p db^q, db innermost.
@@ -495,23 +523,25 @@ struct SscKbIntegrand {
 
 // grid (kernel_npoints, n pairs), block 256: the k_b integral at k_a knot x of pair y
 // (covariance.py:723-763).  LDS: ssc_kb_lds_doubles.
+// (the body of k_ssc_kb and of a diagonal block of k_ssc_blocks_kb; epoch: the epoch record,
+//  htab: its knot-table slab)
 template <bool BAO>
-__global__ __launch_bounds__(256) void k_ssc_kb(chomp_config cfg, TabLayout HL, SscLayout S,
-                                                const Epoch* __restrict__ epochs, int e,
-                                                const double* __restrict__ htab,
-                                                const double* __restrict__ st,
-                                                const double* __restrict__ theta_a,
-                                                const double* __restrict__ theta_b,
-                                                double* __restrict__ knots,
-                                                double* __restrict__ levels) {
+__device__ __forceinline__ void ssc_kb_body(const chomp_config& cfg, const TabLayout& HL,
+                                            const SscLayout& S, const Epoch* __restrict__ epoch,
+                                            const double* __restrict__ htab,
+                                            const double* __restrict__ st,
+                                            const double* __restrict__ theta_a,
+                                            const double* __restrict__ theta_b,
+                                            double* __restrict__ knots,
+                                            double* __restrict__ levels) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch E;
   __shared__ double red[romberg_scratch<4, 2>()];
-  copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(&epochs[e]),
+  copy_doubles(reinterpret_cast<double*>(&E), reinterpret_cast<const double*>(epoch),
                kEpochDoubles);
   __syncthreads();
   PowerEval P;
-  P.stage(cfg, HL, &E, htab + (size_t)e * HL.stride, CHOMP_P_SSC_RESPONSE, sm);
+  P.stage(cfg, HL, &E, htab, CHOMP_P_SSC_RESPONSE, sm);
   const int i = blockIdx.x, pair = blockIdx.y, NK = cfg.kernel_npoints;
   const double ln_k_min = log(cfg.k_min), ln_k_max = log(cfg.k_max);
   const double ka = exp(linspace_at(ln_k_min, ln_k_max, NK, i));
@@ -528,28 +558,45 @@ __global__ __launch_bounds__(256) void k_ssc_kb(chomp_config cfg, TabLayout HL, 
     if (levels) levels[(size_t)pair * NK + i] = (double)level;
   }
 }
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_ssc_kb(chomp_config cfg, TabLayout HL, SscLayout S,
+                                                const Epoch* __restrict__ epochs, int e,
+                                                const double* __restrict__ htab,
+                                                const double* __restrict__ st,
+                                                const double* __restrict__ theta_a,
+                                                const double* __restrict__ theta_b,
+                                                double* __restrict__ knots,
+                                                double* __restrict__ levels) {
+  ssc_kb_body<BAO>(cfg, HL, S, epochs + e, htab + (size_t)e * HL.stride, st, theta_a, theta_b,
+                   knots, levels);
+}
 
 // k_ssc_kb of a cross block: R(k_a) from slot 0's epoch (halo_a at z_bar_a) and R(k_b) from
 // slot 1's (halo_b at z_bar_b), both CHOMP_P_SSC_RESPONSE, staged side by side in LDS as
 // k_cov_cross_knots stages its two spectra.  LDS: ssc_kb_cross_lds_doubles.
+// (the body of k_ssc_kb_cross and of a cross block of k_ssc_blocks_kb; per side the epoch record
+//  as doubles and its knot-table slab)
 template <bool BAO>
-__global__ __launch_bounds__(256) void k_ssc_kb_cross(chomp_config cfg, TabLayout HL, SscLayout S,
-                                                      CrossLayout C,
-                                                      const double* __restrict__ ct,
-                                                      const double* __restrict__ st,
-                                                      const double* __restrict__ theta_a,
-                                                      const double* __restrict__ theta_b,
-                                                      double* __restrict__ knots,
-                                                      double* __restrict__ levels) {
+__device__ __forceinline__ void ssc_kb_cross_body(const chomp_config& cfg, const TabLayout& HL,
+                                                  const SscLayout& S,
+                                                  const double* __restrict__ ep_a,
+                                                  const double* __restrict__ ep_b,
+                                                  const double* __restrict__ htab_a,
+                                                  const double* __restrict__ htab_b,
+                                                  const double* __restrict__ st,
+                                                  const double* __restrict__ theta_a,
+                                                  const double* __restrict__ theta_b,
+                                                  double* __restrict__ knots,
+                                                  double* __restrict__ levels) {
   extern __shared__ __align__(16) double sm[];
   __shared__ Epoch Ea, Eb;
   __shared__ double red[romberg_scratch<4, 2>()];
-  copy_doubles(reinterpret_cast<double*>(&Ea), ct + C.ep[0], kEpochDoubles);
-  copy_doubles(reinterpret_cast<double*>(&Eb), ct + C.ep[1], kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&Ea), ep_a, kEpochDoubles);
+  copy_doubles(reinterpret_cast<double*>(&Eb), ep_b, kEpochDoubles);
   __syncthreads();
   PowerEval Pa, Pb;
-  Pa.stage(cfg, HL, &Ea, ct + C.htab[0], CHOMP_P_SSC_RESPONSE, sm);
-  Pb.stage(cfg, HL, &Eb, ct + C.htab[1], CHOMP_P_SSC_RESPONSE, sm + 12 * (HL.NK - 1));
+  Pa.stage(cfg, HL, &Ea, htab_a, CHOMP_P_SSC_RESPONSE, sm);
+  Pb.stage(cfg, HL, &Eb, htab_b, CHOMP_P_SSC_RESPONSE, sm + 12 * (HL.NK - 1));
   const int i = blockIdx.x, pair = blockIdx.y, NK = cfg.kernel_npoints;
   const double ln_k_min = log(cfg.k_min), ln_k_max = log(cfg.k_max);
   const double ka = exp(linspace_at(ln_k_min, ln_k_max, NK, i));
@@ -567,6 +614,18 @@ __global__ __launch_bounds__(256) void k_ssc_kb_cross(chomp_config cfg, TabLayou
     if (levels) levels[(size_t)pair * NK + i] = (double)level;
   }
 }
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_ssc_kb_cross(chomp_config cfg, TabLayout HL, SscLayout S,
+                                                      CrossLayout C,
+                                                      const double* __restrict__ ct,
+                                                      const double* __restrict__ st,
+                                                      const double* __restrict__ theta_a,
+                                                      const double* __restrict__ theta_b,
+                                                      double* __restrict__ knots,
+                                                      double* __restrict__ levels) {
+  ssc_kb_cross_body<BAO>(cfg, HL, S, ct + C.ep[0], ct + C.ep[1], ct + C.htab[0], ct + C.htab[1],
+                         st, theta_a, theta_b, knots, levels);
+}
 
 // covariance.py:605-622, 694-721 (covariance_NG and covariance_ssc alike): the not-a-knot spline
 // of the k_a knots, norm = 1 / spline(0), the
@@ -583,9 +642,10 @@ struct SscKaIntegrand {
 
 // grid n pairs, block 256.  LDS: ssc_outer_lds_doubles(kernel_npoints) -- the knots x and y
 // (N each), the spline pieces (4 (N - 1)) and spline_build's work (2 N).
-__global__ __launch_bounds__(256) void k_ssc_outer(chomp_config cfg, double area,
-                                                   const double* __restrict__ knots,
-                                                   double* __restrict__ out) {
+// (the body of k_ssc_outer and of k_ssc_blocks_outer; workgroup blockIdx.x)
+__device__ __forceinline__ void ssc_outer_body(const chomp_config& cfg, double area,
+                                               const double* __restrict__ knots,
+                                               double* __restrict__ out) {
   extern __shared__ __align__(16) double sm[];
   __shared__ double red[romberg_scratch<4, 2>()];
   const int N = cfg.kernel_npoints, pair = blockIdx.x;
@@ -614,6 +674,139 @@ __global__ __launch_bounds__(256) void k_ssc_outer(chomp_config cfg, double area
                     cfg.divmax, red) / (4.0 * kPi * kPi * norm * area);
   }
   if (threadIdx.x == 0) out[pair] = v;
+}
+__global__ __launch_bounds__(256) void k_ssc_outer(chomp_config cfg, double area,
+                                                   const double* __restrict__ knots,
+                                                   double* __restrict__ out) {
+  ssc_outer_body(cfg, area, knots, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The block axis of the super-sample term (chomp_covariance_ssc_blocks: the super-sample values
+// of every block of a CovarianceMulti(ssc_cov=True, cross_terms=True) in one call)
+// ---------------------------------------------------------------------------------------------
+// The blocks, their order and what they read are those of the Gaussian block axis
+// (chomp_proj_kernels.h, "The block axis of the Gaussian covariance"): block (i, j), i <= j, in
+// the row-major order of the upper triangle, reads projection set i, set j, epoch i and epoch j
+// where they lie -- no snapshot, no CrossState.  A diagonal block runs the bodies of the matching
+// path (FOUR = false, ssc_kb_body with epoch i), a cross block those of the four-window path: a1,
+// a2 and the MultiEpoch from set i, b1, b2 from set j, the response of epoch i at k_a and of epoch
+// j at k_b.  The same code, so the same bits; the branch is uniform in a workgroup.
+//
+// Every block owns one SscLayout slab.  The two template instances of the prep and table bodies
+// differ in their dynamic LDS (the four-window one stages two more windows), so each runs as a
+// launch of its own over a list of its blocks; the kernels behind the table take the block as a
+// grid dimension.  The index block of a call, ints:
+//   epoch[n_corr] | (i, j)[n_blocks] | the diagonal blocks [n_corr] | the cross blocks [n_blocks - n_corr].
+struct SscBlocksState {
+  double* d = nullptr;     // n_blocks slabs of S.total doubles
+  double* d_kb = nullptr;  // the k_b knots, then their levels: [n_blocks][n_pairs][kernel_npoints] each
+  double* d_sigma = nullptr;   // the blocks' sigma^2 knots (ln chi, then sigma^2) on their way into the slabs
+  int* d_index = nullptr;  // the index block
+  size_t cap = 0, cap_kb = 0, cap_sigma = 0, cap_index = 0;
+  SscLayout S;
+  size_t n_corr = 0;       // correlations of the last call (0: none yet)
+  size_t n_pairs = 0;      // ... and its pairs of angles
+};
+__device__ __forceinline__ CovSrc ssc_blocks_src(const ProjDev* pd, const double* ptab,
+                                                 size_t pstride, int i, int j) {
+  return CovSrc{pd + i, ptab + pstride * i, pd + j, ptab + pstride * j};
+}
+
+// grid ceil(n_blocks / 64), block 64, a thread per block: out[b] = z_min, z_max, chi_min, chi_max
+// of the block's windows -- set i's own for a diagonal block (what chomp_kernel_info returns),
+// k_cov_cross_range's for a cross block.
+__global__ __launch_bounds__(64) void k_ssc_blocks_range(chomp_config cfg, ProjLayout L, int n_corr,
+                                                         int n_blocks,
+                                                         const ProjDev* __restrict__ pd,
+                                                         const double* __restrict__ ptab,
+                                                         size_t pstride,
+                                                         const int* __restrict__ index,
+                                                         double* __restrict__ out) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b >= n_blocks) return;
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  double* o = out + 4 * (size_t)b;
+  if (i == j) {
+    o[0] = pd[i].z_min;
+    o[1] = pd[i].z_max;
+    o[2] = pd[i].chi_min;
+    o[3] = pd[i].chi_max;
+    return;
+  }
+  cov_cross_range_body(cfg, L, ssc_blocks_src(pd, ptab, pstride, i, j), o);
+}
+
+// grid n listed blocks, block 256: the block's sigma^2 knots (ln_chi, sigma2: [n_blocks][NS]) into
+// its slab, then k_ssc_prep.  (The body's barrier stands between these stores and the one thread
+// that builds the spline from them.)
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ssc_blocks_prep(
+    chomp_config cfg, ProjLayout L, SscLayout S, int n_corr, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const int* __restrict__ index,
+    const int* __restrict__ list, double ln_kt_min, double ln_kt_max, double j0_limit,
+    const double* __restrict__ ln_chi, const double* __restrict__ sigma2, double* slabs) {
+  const int b = list[blockIdx.x];
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  double* st = slabs + (size_t)b * S.total;
+  for (int q = threadIdx.x; q < S.NS; q += blockDim.x) {
+    st[S.sx + q] = ln_chi[(size_t)b * S.NS + q];
+    st[S.sy + q] = sigma2[(size_t)b * S.NS + q];
+  }
+  ssc_prep_body<FOUR>(cfg, L, S, ssc_blocks_src(pd, ptab, pstride, i, j), ln_kt_min, ln_kt_max,
+                      j0_limit, st);
+}
+
+// grid (N (N + 1) / 2, n listed blocks), block 256: the knot table of block list[y].  LDS:
+// ssc_table_lds_doubles of the instance.
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ssc_blocks_table(
+    chomp_config cfg, ProjLayout L, SscLayout S, int n_corr, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const int* __restrict__ index,
+    const int* __restrict__ list, const BesselTab* __restrict__ bess_g, double* slabs) {
+  const int b = list[blockIdx.y];
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  ssc_table_body<FOUR>(cfg, L, S, ssc_blocks_src(pd, ptab, pstride, i, j), bess_g,
+                       slabs + (size_t)b * S.total, nullptr, nullptr, nullptr);
+}
+
+// grid n_blocks, block 256: the bicubic of block x's table.
+__global__ __launch_bounds__(256) void k_ssc_blocks_bicubic(SscLayout S, double* slabs) {
+  ssc_bicubic_body(S, slabs + (size_t)blockIdx.x * S.total);
+}
+
+// grid (kernel_npoints, n_pairs, n_blocks), block 256: the k_b integral at k_a knot x of pair y of
+// block z -- k_ssc_kb with epoch i for a diagonal block, k_ssc_kb_cross with epoch i's response at
+// k_a and epoch j's at k_b for a cross block.  knots, levels: [n_blocks][n_pairs][kernel_npoints].
+// LDS: ssc_kb_cross_lds_doubles (the larger of the two).
+template <bool BAO>
+__global__ __launch_bounds__(256) void k_ssc_blocks_kb(
+    chomp_config cfg, TabLayout HL, SscLayout S, int n_corr, const Epoch* __restrict__ epochs,
+    const double* __restrict__ htab, const int* __restrict__ index,
+    const double* __restrict__ slabs, const double* __restrict__ theta_a,
+    const double* __restrict__ theta_b, double* __restrict__ knots, double* __restrict__ levels) {
+  const int b = blockIdx.z;
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  const int ea = index[i], eb = index[j];
+  const double* st = slabs + (size_t)b * S.total;
+  const size_t row = (size_t)b * gridDim.y * cfg.kernel_npoints;
+  if (i == j) {
+    ssc_kb_body<BAO>(cfg, HL, S, epochs + ea, htab + (size_t)ea * HL.stride, st, theta_a, theta_b,
+                     knots + row, levels + row);
+    return;
+  }
+  ssc_kb_cross_body<BAO>(cfg, HL, S, reinterpret_cast<const double*>(epochs + ea),
+                         reinterpret_cast<const double*>(epochs + eb),
+                         htab + (size_t)ea * HL.stride, htab + (size_t)eb * HL.stride, st, theta_a,
+                         theta_b, knots + row, levels + row);
+}
+
+// grid (n_pairs, n_blocks), block 256: k_ssc_outer of pair x of block y; out [n_blocks][n_pairs].
+__global__ __launch_bounds__(256) void k_ssc_blocks_outer(chomp_config cfg, double area,
+                                                          const double* __restrict__ knots,
+                                                          double* __restrict__ out) {
+  const size_t b = blockIdx.y;
+  ssc_outer_body(cfg, area, knots + b * gridDim.x * cfg.kernel_npoints, out + b * gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -128,9 +128,11 @@ class HaloGrid(object):
         assert len(self._c_cosmo) == n and len(self._c_halo) == n and len(self._c_hod) == n
         self._tables = 0
 
-    def setup(self, which="power_mm"):
-        """Stage K for this rank's epochs (asynchronous on the context's stream)."""
-        _, need = _WHICH[which]
+    def setup(self, which="power_mm", families=0):
+        """Stage K for this rank's epochs (asynchronous on the context's stream).  families:
+        further _lib.FAM_* families to build beside those of `which` (e.g. _lib.FAM_SSC, the knot
+        tables of the super-sample response, beside a spectrum's own)."""
+        need = _WHICH[which][1] | int(families)
         if len(self.idx) == 0:
             return
         self.ctx.epochs_set(self._c_cosmo, self._z, **cosmology._de_kw(self._c_cosmo))

@@ -932,6 +932,55 @@ int chomp_kernel_ssc_setup_cross(chomp_ctx* ctx, double ln_ktheta_min, double ln
 int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta, size_t n,
                                double* out, double* kb_knots, double* kb_levels);
 
+/* The super-sample term of every block of a CovarianceMulti(ssc_cov=True, cross_terms=True) in
+ * one call, beside chomp_covariance_blocks: the same correlations (projection set c of the last
+ * chomp_kernel_setup_pairs of Bessel order 0, halo epoch epoch[c] of this context at that set's
+ * z_bar, holding the families h_m, pp_mm and i_1_2), the same n_blocks = n_corr (n_corr + 1) / 2
+ * blocks (i, j), i <= j, in the row-major order of the upper triangle.  A diagonal block is what
+ * chomp_kernel_setup (kernel i) + chomp_kernel_ssc_setup + chomp_covariance_ssc(epoch[i]) return;
+ * a cross block what chomp_covariance_cross_stage of (kernel i, epoch[i]) and (kernel j, epoch[j])
+ * + chomp_kernel_ssc_setup_cross + chomp_covariance_ssc_cross return -- a1, a2 and the MultiEpoch
+ * from set i, b1, b2 from set j, the response of epoch[i] at k_a and of epoch[j] at k_b, so the
+ * order of the two angles matters: bit for bit, the blocks being a grid dimension of kernels that
+ * run the single calls' code.  Both sides of a block are read where they lie (no snapshot); the
+ * call keeps a state of its own and touches neither the context's kernel_ssc state, nor the two
+ * slots of chomp_covariance_cross_stage, nor the state of chomp_covariance_blocks.
+ *
+ * chomp_covariance_ssc_blocks_range gives info[n_blocks][4] = z_min, z_max, chi_min, chi_max of
+ * every block's windows -- a diagonal block's as chomp_kernel_info returns them, a cross block's
+ * as chomp_covariance_cross_range does -- in one launch and one read-back: the ranges the caller
+ * lays the blocks' sigma^2 knots over.  A block whose windows have no redshift in common is
+ * CHOMP_ERR_SCOPE naming the block, here and in chomp_covariance_ssc_blocks, before anything is
+ * launched.
+ *
+ * chomp_covariance_ssc_blocks: ln_ktheta_min, ln_ktheta_max, j0_ssc_limit and n_sigma as in
+ * chomp_kernel_ssc_setup; ln_chi and sigma2 (host, [n_blocks][n_sigma]) hold every block's own
+ * sigma^2 knots; area and theta (theta_a[n_pairs] then theta_b[n_pairs], the same pairs for every
+ * block) as in chomp_covariance_ssc; out [n_blocks][n_pairs].  theta and out are host or device
+ * arrays as `mem` says ("Memory-space convention"); epoch, ln_chi and sigma2 are host arrays.
+ * CHOMP_ERR_STATE: no set-up of sets, one of another number of sets than n_corr or of Bessel
+ * order 2, an epoch without the response's knot tables.  CHOMP_ERR_ARG: an epoch out of range,
+ * more than 65535 blocks or pairs, what chomp_kernel_ssc_setup refuses (per block for the knots),
+ * area or a host theta not positive, a configuration whose windows or responses do not fit a
+ * workgroup's LDS.
+ *
+ * chomp_covariance_ssc_blocks_table reads block `block` of the last call: info[7] = z_bar_NG,
+ * chi(z_bar_NG), growth_factor(z_bar_NG), z_min, z_max, chi_min, chi_max; table and levels
+ * [kernel_npoints^2]; kb_knots and kb_levels [n_pairs * kernel_npoints].  Host arrays; any may
+ * be NULL. */
+int chomp_covariance_ssc_blocks_range(chomp_ctx* ctx, size_t n_corr,
+                                      double* info /*[n_blocks][4]*/);
+int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch /*[n_corr]*/,
+                                double ln_ktheta_min, double ln_ktheta_max, double j0_ssc_limit,
+                                const double* ln_chi /*[n_blocks][n_sigma]*/,
+                                const double* sigma2 /*[n_blocks][n_sigma]*/, size_t n_sigma,
+                                double area,
+                                const double* theta /*[2][n_pairs]: theta_a then theta_b*/,
+                                size_t n_pairs, double* out /*[n_blocks][n_pairs]*/, int mem);
+int chomp_covariance_ssc_blocks_table(chomp_ctx* ctx, size_t block, double* info /*[7]*/,
+                                      double* table, double* levels, double* kb_knots,
+                                      double* kb_levels);
+
 /* Gaussian covariance of C_l, covariance.CovarianceFourier (covariance.py:874-1083): four Limber
  * tables over ln l, one per window pair X = a1a2, b1b2, a1b2, b1a2 (that order throughout), each
  * from the P_mm of a halo epoch at that pair's z_bar.

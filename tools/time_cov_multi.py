@@ -10,7 +10,13 @@ pairs) -- two ways:
     batch   CovarianceMulti.get_covariance_batched(): chomp_kernel_setup_pairs, ONE read-back of
             z_bar, the grid set-up of 15 epochs, chomp_covariance_blocks; keeps no tables
 
-    python tools/time_cov_multi.py [--rounds 5] [--modes loop,batch] [--out FILE.json]
+    python tools/time_cov_multi.py [--rounds 5] [--modes loop,batch] [--ssc] [--out FILE.json]
+
+--ssc: the same analysis with the super-sample term, CovarianceMulti(ssc_cov=True,
+cross_terms=True): per cross block the loop adds kernel_ssc (a read-back of the chi range, a host
+sigma_r call, the 1275 integrals of the table, its bicubic) and covariance_ssc; the batch adds one
+read-back of every block's range, one sigma_r call per row of blocks and
+chomp_covariance_ssc_blocks.
 
 Timed, host clock around calls that end with their result on the host (so synchronised):
     loop_first / batch_first   the first call on fresh objects (contexts, buffers, code objects)
@@ -56,6 +62,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--modes", default="loop,batch")
+    ap.add_argument("--ssc", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
     import torch
@@ -67,8 +74,9 @@ def main():
 
     def build():
         corrs = correlations()
+        kws = dict(ssc_cov=True, cross_terms=True) if args.ssc else {}
         return corrs, covariance.CovarianceMulti(corrs, bins_per_decade=5, nongaussian_cov=False,
-                                                 survey_area_deg2=25.0)
+                                                 survey_area_deg2=25.0, **kws)
 
     def move(corrs, which):
         """A new HOD on the correlations `which`."""
@@ -86,7 +94,8 @@ def main():
         return (time.perf_counter() - t0) * 1e3, out    # milliseconds
 
     result = {"what": "milliseconds per covariance matrix (host clock, result on the host), 15 "
-                      "correlations, 120 blocks, 10 angular bins, power_mm",
+                      "correlations, 120 blocks, 10 angular bins, power_mm"
+                      + (", Gaussian + super-sample terms (ssc_cov, cross_terms)" if args.ssc else ""),
               "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "modes": modes}
     state, warm = {}, {}
     if "loop" in modes:
