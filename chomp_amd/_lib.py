@@ -577,6 +577,21 @@ def _elementwise(*pre, shape=None):
     return lambda mem, new, x: pre + (x, _numel(x), new(x.shape if shape is None else shape), mem)
 
 
+def _rows(n_epoch, *pre):
+    """Context._run's body of a batched entry point fn(handle, *pre, x, n, out, mem): out
+    [n_epoch, x.size], a row per epoch."""
+    n_epoch = int(n_epoch)
+    return lambda mem, new, x: pre + (x, _numel(x), new((n_epoch, _numel(x))), mem)
+
+
+def _row_growth(who, D_z, n_epoch):
+    """The per-row growth factors of `who` (a *_sets call): a host array, one per epoch."""
+    D = numpy.ascontiguousarray(D_z, dtype=numpy.float64).ravel()
+    if D.size != int(n_epoch):
+        raise ValueError("%s: D_z must hold one growth factor per epoch" % who)
+    return D
+
+
 def _pairs(a, b):
     """The pairs of the covariance calls: two host arrays of one length, one after the other."""
     a = numpy.ascontiguousarray(a, dtype=numpy.float64).ravel()
@@ -1167,24 +1182,19 @@ class Context(object):
         kernel_setup(<cosmology e>) + wtheta(which, epoch0 + e, ..., D_z[e], theta) returns, bit
         for bit.  D_z is a host array; theta a host array or a torch cuda tensor, as in
         wtheta_epochs."""
-        D = numpy.ascontiguousarray(D_z, dtype=numpy.float64).ravel()
-        if D.size != int(n_epoch):
-            raise ValueError("wtheta_sets: D_z must hold one growth factor per epoch")
-        return self._run(self._L.chomp_wtheta_sets, [theta], lambda mem, new, th: (
-            int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), _host_address(D), th,
-            _numel(th), new((int(n_epoch), _numel(th))), mem))[0]
+        D = _row_growth("wtheta_sets", D_z, n_epoch)
+        return self._run(self._L.chomp_wtheta_sets, [theta], _rows(
+            n_epoch, int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max),
+            _host_address(D)))[0]
 
     def cell_sets(self, which, epoch0, n_epoch, D_z, ell):
         """C_l of the epochs epoch0 .. epoch0 + n_epoch - 1, epoch epoch0 + e against projection
         set e with growth D_z[e] (chomp_cell_sets): [n_epoch, ell.size], row e what
         kernel_setup(<the inputs of set e>) + cell(which, epoch0 + e, D_z[e], ell) returns, bit for
         bit.  D_z is a host array; ell a host array or a torch cuda tensor, as in cell_epochs."""
-        D = numpy.ascontiguousarray(D_z, dtype=numpy.float64).ravel()
-        if D.size != int(n_epoch):
-            raise ValueError("cell_sets: D_z must hold one growth factor per epoch")
-        return self._run(self._L.chomp_cell_sets, [ell], lambda mem, new, el: (
-            int(which), int(epoch0), int(n_epoch), _host_address(D), el, _numel(el),
-            new((int(n_epoch), _numel(el))), mem))[0]
+        D = _row_growth("cell_sets", D_z, n_epoch)
+        return self._run(self._L.chomp_cell_sets, [ell], _rows(
+            n_epoch, int(which), int(epoch0), int(n_epoch), _host_address(D)))[0]
 
     def _run(self, fn, xs, body):
         """Call the array entry point fn on host or device arrays; returns the list of outputs.
@@ -1234,9 +1244,9 @@ class Context(object):
     def wtheta_epochs(self, which, epoch0, n_epoch, k_min, k_max, D_z, theta):
         """w(theta) of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (chomp_wtheta_epochs):
         [n_epoch, theta.size], row e what wtheta(which, epoch0 + e, ...) returns, bit for bit."""
-        return self._run(self._L.chomp_wtheta_epochs, [theta], lambda mem, new, th: (
-            int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), float(D_z), th,
-            _numel(th), new((int(n_epoch), _numel(th))), mem))[0]
+        return self._run(self._L.chomp_wtheta_epochs, [theta], _rows(
+            n_epoch, int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max),
+            float(D_z)))[0]
 
     def wtheta_cell(self, which, epoch, k_min, k_max, D_z, theta, ell):
         """(w(theta), C_l) of one set-up in one call (chomp_wtheta_cell): with torch cuda
@@ -1558,9 +1568,8 @@ class Context(object):
         """xi(r) of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (chomp_xi3d_epochs):
         [n_epoch, r.size], row e what xi3d(which, epoch0 + e, ...) returns, bit for bit.  Needs no
         kernel set-up."""
-        return self._run(self._L.chomp_xi3d_epochs, [r], lambda mem, new, rr: (
-            int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max), rr,
-            _numel(rr), new((int(n_epoch), _numel(rr))), mem))[0]
+        return self._run(self._L.chomp_xi3d_epochs, [r], _rows(
+            n_epoch, int(which), int(epoch0), int(n_epoch), float(k_min), float(k_max)))[0]
 
     def spline_eval(self, xk, yk, x, deriv=0):
         """Not-a-knot cubic spline through (xk, yk) at x (FITPACK k=3, s=0); deriv=1: its
@@ -1581,6 +1590,5 @@ class Context(object):
     def cell_epochs(self, which, epoch0, n_epoch, D_z, ell):
         """C_l of the epochs epoch0 .. epoch0 + n_epoch - 1 in one call (chomp_cell_epochs):
         [n_epoch, ell.size], row e what cell(which, epoch0 + e, D_z, ell) returns, bit for bit."""
-        return self._run(self._L.chomp_cell_epochs, [ell], lambda mem, new, el: (
-            int(which), int(epoch0), int(n_epoch), float(D_z), el, _numel(el),
-            new((int(n_epoch), _numel(el))), mem))[0]
+        return self._run(self._L.chomp_cell_epochs, [ell], _rows(
+            n_epoch, int(which), int(epoch0), int(n_epoch), float(D_z)))[0]

@@ -618,12 +618,12 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
   rc = st.place();
   if (rc) return rc;
   const ProjLayout& L = ctx->proj.L;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
-  const int LT = ctx->cfg.divmax < kWthetaTabLevel ? ctx->cfg.divmax : kWthetaTabLevel;
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
+  const WthPlan P = wth_plan(ctx->cfg.divmax, ctx->L.NK, L, ctx->proj.host.ln_kt_min,
+                             ctx->proj.host.ln_kt_max, k_min, k_max, ctx->tune[CHOMP_TUNE_WTHETA_DIRECT]);
+  const int LT = P.LT, nseg = P.nseg;
   if (ctx->precision != CHOMP_PREC_F64) {
     auto mixed = [&](auto PREC) {
-      hipLaunchKernelGGL(k_wtheta_mixed<PREC>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
+      hipLaunchKernelGGL(k_wtheta_mixed<PREC>, dim3((unsigned)n), dim3(256), P.sh, ctx->stream, ctx->cfg,
                          ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd,
                          ctx->proj.d_tab, k_min, k_max, D_z, din, dout);
     };
@@ -635,26 +635,17 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
     return st.finish();
   }
   // fp64: the theta-independent factor of the integrand on the Romberg nodes first, then the
-  // moment route (k_wtheta_moments + k_wtheta_fast: every level within the node table, segments
-  // about as wide as -- never narrower than -- a piece of the kernel spline) or k_wtheta
-  const double dxK = (ctx->proj.host.ln_kt_max - ctx->proj.host.ln_kt_min) / (double)(L.NKT - 1);
-  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
-  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
-  const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
-                    ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
-  // node table, then (fast route) the moment records and the segments' totals
-  const size_t n_rec = 4 * wth_rec_count(LT), n_tot = 4 * (size_t)(LT + 1) * (size_t)nseg;
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, n_nodes + 1 + (fast ? n_rec + n_tot + 2 : 0));
+  // moment route (k_wtheta_moments + k_wtheta_fast) or k_wtheta, as the plan says (WthPlan: the
+  // node table, then the moment records and the segments' totals -- one epoch's scratch)
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, P.stride);
   if (rc) return rc;
-  double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // 16-byte aligned records
-  double* segtot = rec + n_rec;
+  double* rec = ctx->d_wnodes + P.rec_at;
+  double* segtot = ctx->d_wnodes + P.tot_at;
   with_flag(which & CHOMP_P_HALOFIT, ctx->with_bao, [&](auto HF, auto BAO) {
-    hipLaunchKernelGGL((k_wtheta_nodes<HF, BAO>),
-                       dim3((unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread))),
-                       dim3(256), (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
-                       ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, k_min, k_max, D_z, LT,
-                       ctx->d_wnodes);
-    if (fast) {
+    hipLaunchKernelGGL((k_wtheta_nodes<HF, BAO>), dim3(P.gnodes), dim3(256), P.sh_nodes, ctx->stream,
+                       ctx->cfg, ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, k_min, k_max,
+                       D_z, LT, ctx->d_wnodes);
+    if (P.fast) {
       hipLaunchKernelGGL(k_wtheta_moments, dim3((unsigned)nseg, (unsigned)LT, kWthParts), dim3(256), 0,
                          ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min), std::log(k_max), rec,
                          segtot);
@@ -662,7 +653,7 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
                          ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, din, dout, ctx->d_wnodes, rec,
                          segtot, LT, nseg);
     } else {
-      hipLaunchKernelGGL((k_wtheta<HF, BAO>), dim3((unsigned)n), dim3(64 * kWthetaNW), sh, ctx->stream,
+      hipLaunchKernelGGL((k_wtheta<HF, BAO>), dim3((unsigned)n), dim3(64 * kWthetaNW), P.sh, ctx->stream,
                          ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, ctx->proj.d_pd,
                          ctx->proj.d_tab, k_min, k_max, D_z, din, dout, ctx->d_wnodes, LT);
     }
@@ -696,30 +687,60 @@ int chomp_xi3d(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k_m
   return st.finish();
 }
 
+// -- the batched calls: w(theta), xi(r) and C_l of many epochs ---------------------------------
+// What they share is written once: the plans of the scratch and the launches (WthPlan, CellPlan:
+// chomp_proj_kernels.h), the chunk rule, the refusals, and per observable one chunked driver
+// (wtheta_rows, cell_rows).  In messages a call names itself (`who`) and the single-epoch call
+// that serves what it does not (`single`).
+
+// The epochs of one chunk: kWthEpochChunk unless CHOMP_TUNE_WTHETA_EPOCH_CHUNK says otherwise.
+static size_t epoch_chunk(const chomp_ctx* ctx, size_t n_epoch) {
+  const long long tuned = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK];
+  const size_t chunk = tuned > 0 ? (size_t)tuned : (size_t)kWthEpochChunk;
+  return std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
+}
+
+// arrays: every array argument is there
+static int batch_args(chomp_ctx* ctx, const char* who, bool arrays, size_t n, size_t n_epoch) {
+  if (!arrays || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": bad args");
+  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": n * n_epoch too large");
+  return CHOMP_OK;
+}
+
+// What the batched calls do not serve is said before the spectrum is looked at: a HaloFit code on
+// epochs without a HaloFit set-up is out of scope here, not a state to repair.  fp64_note: why,
+// where the single call has no narrowed precision mode either.
+static int batch_scope(chomp_ctx* ctx, const char* who, const char* single, int which,
+                       const char* fp64_note = nullptr) {
+  if (ctx->precision != CHOMP_PREC_F64) {
+    const std::string why = fp64_note ? fp64_note : std::string("the narrowed precision modes belong to ") + single;
+    return fail(ctx, CHOMP_ERR_SCOPE, std::string(who) + ": fp64 only (" + why + ")");
+  }
+  const char* what = nullptr;
+  if (which & CHOMP_P_HALOFIT) what = ": HaloFit spectra are";
+  else if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN) what = ": extrapolated spectra are";
+  else if (ctx->with_bao) what = ": the wiggle transfer function is";
+  if (!what) return CHOMP_OK;
+  return fail(ctx, CHOMP_ERR_SCOPE, std::string(who) + what + " evaluated by " + single);
+}
+
 // xi(r) of n_epoch epochs that share the k range (an HOD or cosmology design or chain): the node
 // table of chomp_wtheta_epochs with D_z = 1.0 -- the r-independent factor of the integrand, once
 // per epoch -- and one Romberg launch with an epoch axis that reads it, the epochs worked off in
-// chunks of kWthEpochChunk (layout: chomp_proj_kernels.h, k_xi3d_epochs).  No projection set-up.
+// chunks (layout: chomp_proj_kernels.h, k_xi3d_epochs).  No projection set-up.
 int chomp_xi3d_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
                       double k_max, const double* r, size_t n, double* out, int mem) {
   StageRange range_(ctx, "chomp:xi3d_epochs");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!r || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "xi3d_epochs: bad args");
-  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "xi3d_epochs: n * n_epoch too large");
+  int rc = batch_args(ctx, "xi3d_epochs", r && out, n, n_epoch);
+  if (rc) return rc;
   Staging st(ctx, mem, "xi3d_epochs");
   if (st.rc) return st.rc;
-  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
-  if (ctx->precision != CHOMP_PREC_F64)
-    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: fp64 only (the narrowed precision modes belong to chomp_xi3d)");
-  if (which & CHOMP_P_HALOFIT)
-    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: HaloFit spectra are evaluated by chomp_xi3d");
-  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
-    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: extrapolated spectra are evaluated by chomp_xi3d");
-  if (ctx->with_bao)
-    return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: the wiggle transfer function is evaluated by chomp_xi3d");
+  rc = batch_scope(ctx, "xi3d_epochs", "chomp_xi3d", which);
+  if (rc) return rc;
   if (ctx->cfg.divmax > kWthetaTabLevel)
     return fail(ctx, CHOMP_ERR_SCOPE, "xi3d_epochs: divmax beyond the node table (level 20) is evaluated by chomp_xi3d");
-  int rc = check_power(ctx, which, epoch0, n_epoch);
+  rc = check_power(ctx, which, epoch0, n_epoch);
   if (rc) return rc;
   if (!(k_min > 0.0) || !(k_max > k_min)) return fail(ctx, CHOMP_ERR_ARG, "xi3d_epochs: k range");
   HIPCHK(hipSetDevice(ctx->device));
@@ -729,24 +750,19 @@ int chomp_xi3d_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, 
   st.out(out, n * n_epoch, &dout);
   rc = st.place();
   if (rc) return rc;
-  const int LT = ctx->cfg.divmax;                            // (<= kWthetaTabLevel: every level)
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
-  const size_t stride = wth_epoch_stride(LT, 1, false);
-  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
-                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
-  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
+  // (the node-table part of the w(theta) plan: every level, divmax <= kWthetaTabLevel)
+  const WthPlan P = wth_plan_of(ctx->cfg.divmax, 1, false, ctx->L.NK);
+  const size_t chunk = epoch_chunk(ctx, n_epoch);
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, P.stride * chunk);
   if (rc) return rc;
-  const unsigned gnodes = (unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
   for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {          // (the scratch is reused in stream order)
     const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
-    hipLaunchKernelGGL((k_wtheta_nodes_epochs<false, false>), dim3(gnodes, E), dim3(256),
-                       (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
-                       ctx->L, ctx->d_epochs, (int)(epoch0 + c0), ctx->d_tab, which, k_min, k_max,
-                       1.0, LT, ctx->d_wnodes, stride);
+    hipLaunchKernelGGL((k_wtheta_nodes_epochs<false, false>), dim3(P.gnodes, E), dim3(256), P.sh_nodes,
+                       ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, (int)(epoch0 + c0), ctx->d_tab,
+                       which, k_min, k_max, 1.0, P.LT, ctx->d_wnodes, P.stride);
     hipLaunchKernelGGL(k_xi3d_epochs, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
                        ctx->cfg.global_precision, ctx->cfg.corr_precision, ctx->cfg.divmax,
-                       ctx->d_j0, k_min, k_max, din, dout + c0 * n, ctx->d_wnodes, stride);
+                       ctx->d_j0, k_min, k_max, din, dout + c0 * n, ctx->d_wnodes, P.stride);
   }
   return st.finish();
 }
@@ -791,10 +807,9 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   if (rc) return rc;
   if (!(D_z > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "cell: D_z");
   const ProjLayout& L = ctx->proj.L;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
-  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);   // (k_cell_deep)
-  constexpr int kDeepLds = 160 * 1024 - 4096;
-  if (shd > kDeepLds) return fail(ctx, CHOMP_ERR_ARG, "cell: halo_npoints too large for k_cell_deep");
+  const CellPlan P = cell_plan(ctx->cfg.divmax, ctx->L.NK, L, n, ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL],
+                               false);
+  if (!P.deep_fits) return fail(ctx, CHOMP_ERR_ARG, "cell: halo_npoints too large for k_cell_deep");
   HIPCHK(hipSetDevice(ctx->device));
   rc = prepare_extrapolation(ctx, which, epoch, 1);
   if (rc) return rc;
@@ -804,31 +819,25 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   st.out(out, n, &dout);
   rc = st.place();
   if (rc) return rc;
-  // the chi-only factors of the integrand on the Romberg nodes first
-  const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
-  // (+ the hand-over of k_cell to k_cell_deep: Romberg states, then the list as ints)
-  const size_t off_state = 3 * n_nodes + (size_t)kPTabN + 1;
-  const size_t off_list = off_state + n * kRombergDump;
-  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, off_list + (n + 3) / 2 + 1);
+  // the chi-only factors of the integrand on the Romberg nodes first (CellPlan: the node table,
+  // then one slab -- the spectrum table and the hand-over of k_cell to k_cell_deep)
+  const int LT = P.LT, split = P.split;
+  const size_t sh = P.sh;
+  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, P.doubles(1));
   if (rc) return rc;
-  double* state = ctx->d_cnodes + off_state;
-  int* deep = reinterpret_cast<int*>(ctx->d_cnodes + off_list);
-  hipLaunchKernelGGL(k_cell_nodes, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256),
-                     (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, L, ctx->proj.d_pd,
-                     ctx->proj.d_tab, D_z, LT, ctx->d_cnodes, deep, 1, (size_t)0);
-  // ... and the spectrum itself on a uniform ln k grid (no-wiggle spectra)
-  double* pk_tab = ctx->with_bao ? nullptr : ctx->d_cnodes + 3 * n_nodes;
-  // levels beyond kCellSplitLevel by k_cell_deep (CHOMP_TUNE_CELL_ONE_KERNEL: all in k_cell)
-  const int split = (ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL] > 0 || ctx->cfg.divmax <= kCellSplitLevel)
-                        ? ctx->cfg.divmax : kCellSplitLevel;
-  const unsigned gdeep = (unsigned)(n < 512 ? n : 512);
+  double* state = ctx->d_cnodes + P.state_at;
+  int* deep = reinterpret_cast<int*>(ctx->d_cnodes + P.deep_at);
+  hipLaunchKernelGGL(k_cell_nodes, dim3(P.gnodes), dim3(256), P.sh_nodes, ctx->stream, L,
+                     ctx->proj.d_pd, ctx->proj.d_tab, D_z, LT, ctx->d_cnodes, deep, 1, (size_t)0);
+  // ... and the spectrum itself on a uniform ln k grid (no-wiggle spectra); levels beyond
+  // kCellSplitLevel by k_cell_deep (CHOMP_TUNE_CELL_ONE_KERNEL: all in k_cell)
+  double* pk_tab = ctx->with_bao ? nullptr : ctx->d_cnodes + P.pk_at;
   rc = with_flag(which & CHOMP_P_HALOFIT, ctx->with_bao, [&](auto HF, auto BAO) {
     if (pk_tab)
       hipLaunchKernelGGL((k_cell_ptab<HF, BAO>), dim3((kPTabN + 256) / 256), dim3(256),
                          (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
                          ctx->L, ctx->d_epochs, (int)epoch, ctx->d_tab, which, pk_tab);
-    if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
+    if (P.four) {   // (four multipoles to a block)
       hipLaunchKernelGGL((k_cell4<HF, BAO>), dim3((unsigned)((n + 3) / 4)), dim3(256), sh,
                          ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,
                          ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n,
@@ -842,9 +851,9 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
       });
     }
     if (split >= ctx->cfg.divmax) return CHOMP_OK;
-    const int rcl = lds_opt_in(ctx, &k_cell_deep<HF, BAO>, kDeepLds);
+    const int rcl = lds_opt_in(ctx, &k_cell_deep<HF, BAO>, P.deep_lds);
     if (rcl) return rcl;
-    hipLaunchKernelGGL((k_cell_deep<HF, BAO>), dim3(gdeep), dim3(kCellDeepThreads), shd,
+    hipLaunchKernelGGL((k_cell_deep<HF, BAO>), dim3(P.gdeep), dim3(kCellDeepThreads), P.shd,
                        ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, (int)epoch,
                        ctx->d_tab, which, ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, dout,
                        ctx->d_cnodes, LT, pk_tab, split, deep, state);
@@ -863,85 +872,137 @@ int chomp_wtheta(chomp_ctx* ctx, int which, size_t epoch, double k_min, double k
   return wtheta_impl(ctx, which, epoch, k_min, k_max, D_z, theta, n, out, mem);
 }
 
+// The rows of a batched projection.  sets == nullptr (chomp_*_epochs): every epoch against the
+// context's projection set-up with the one growth factor D_z.  Otherwise (chomp_*_sets): epoch
+// epoch0 + e against set e of the last set-up of sets with growth D_zs[e], a host array.
+struct ProjRows {
+  const char *who, *single;
+  const ProjSets* sets;
+  double D_z;
+  const double* D_zs;
+};
+
+// The set-up the rows need, then the scope, then (sets) a row per set.
+static int rows_check(chomp_ctx* ctx, const ProjRows& R, int which, size_t n_epoch,
+                      const char* fp64_note = nullptr) {
+  if (R.sets ? R.sets->n == 0 : !ctx->proj.ready)
+    return fail(ctx, CHOMP_ERR_STATE, std::string(R.who) + (R.sets ? " before kernel_setup_sets / kernel_setup_pairs"
+                                                                    : " before kernel_setup"));
+  const int rc = batch_scope(ctx, R.who, R.single, which, fp64_note);
+  if (rc) return rc;
+  if (R.sets && n_epoch != R.sets->n)
+    return fail(ctx, CHOMP_ERR_ARG, std::string(R.who) + ": n_epoch is not the number of sets of the last "
+                                                         "kernel_setup_sets / kernel_setup_pairs");
+  return CHOMP_OK;
+}
+
+static bool rows_growth_ok(const ProjRows& R, size_t n_epoch) {
+  if (!R.sets) return R.D_z > 0.0;
+  for (size_t e = 0; e < n_epoch; ++e)
+    if (!(R.D_zs[e] > 0.0)) return false;
+  return true;
+}
+
+// st.place() with (sets) the per-row growth factors behind it on the device: D_zs is a host array
+// whatever `mem` says, so it goes through the scratch segment.  *dD: null without sets.
+static int rows_place(chomp_ctx* ctx, Staging& st, const ProjRows& R, size_t n_epoch, const double** dD) {
+  *dD = nullptr;
+  const int rc = st.place(R.sets ? n_epoch : 0);
+  if (rc || !R.sets) return rc;
+  *dD = st.scratch;
+  HIPCHK(hipMemcpyAsync(st.scratch, R.D_zs, n_epoch * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  return CHOMP_OK;
+}
+
+// The chunked driver of chomp_wtheta_epochs and chomp_wtheta_sets: the three launches of
+// wtheta_impl with an epoch axis -- the _epochs kernels, or the _sets kernels with the chunk's
+// first set and growth factor -- the epochs worked off in chunks that reuse one work buffer
+// (layout: chomp_proj_kernels.h, "The epoch axis"; the sizes and the route: WthPlan).
+static int wtheta_rows(chomp_ctx* ctx, const ProjRows& R, int which, size_t epoch0, size_t n_epoch,
+                       double k_min, double k_max, const double* theta, size_t n, double* out, int mem) {
+  int rc = batch_args(ctx, R.who, theta && out && (!R.sets || R.D_zs), n, n_epoch);
+  if (rc) return rc;
+  Staging st(ctx, mem, R.who);
+  if (st.rc) return st.rc;
+  rc = rows_check(ctx, R, which, n_epoch);
+  if (rc) return rc;
+  rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  const bool range_ok = k_min > 0.0 && k_max > k_min;
+  if (!R.sets) {
+    if (!range_ok || !rows_growth_ok(R, n_epoch)) return fail(ctx, CHOMP_ERR_ARG, std::string(R.who) + ": k range / D_z");
+  } else {
+    if (!range_ok) return fail(ctx, CHOMP_ERR_ARG, std::string(R.who) + ": k range");
+    if (!rows_growth_ok(R, n_epoch)) return fail(ctx, CHOMP_ERR_ARG, std::string(R.who) + ": D_z");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!R.sets) { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  const double *din, *dD;
+  double* dout;
+  st.in(theta, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = rows_place(ctx, st, R, n_epoch, &dD);
+  if (rc) return rc;
+  const ProjLayout& L = R.sets ? R.sets->L : ctx->proj.L;
+  const ProjDev& host = R.sets ? R.sets->host : ctx->proj.host;
+  const WthPlan P = wth_plan(ctx->cfg.divmax, ctx->L.NK, L, host.ln_kt_min, host.ln_kt_max, k_min,
+                             k_max, ctx->tune[CHOMP_TUNE_WTHETA_DIRECT]);
+  const int LT = P.LT, nseg = P.nseg;
+  const size_t stride = P.stride, pstride = (size_t)L.total;
+  const size_t chunk = epoch_chunk(ctx, n_epoch);
+  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
+  if (rc) return rc;
+  double* rec = ctx->d_wnodes + P.rec_at;                   // (of the chunk's first epoch)
+  double* segtot = ctx->d_wnodes + P.tot_at;
+  constexpr bool HF = false, BAO = false;
+  for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {          // (the scratch is reused in stream order)
+    const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+    const int e0 = (int)(epoch0 + c0);
+    double* o = dout + c0 * n;
+    const ProjDev* pd = R.sets ? R.sets->d_pd + c0 : ctx->proj.d_pd;   // (sets: the chunk's first set)
+    const double* ptab = R.sets ? R.sets->d_tab + c0 * pstride : ctx->proj.d_tab;
+    if (R.sets)
+      hipLaunchKernelGGL((k_wtheta_nodes_sets<HF, BAO>), dim3(P.gnodes, E), dim3(256), P.sh_nodes,
+                         ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, k_min,
+                         k_max, dD + c0, LT, ctx->d_wnodes, stride);
+    else
+      hipLaunchKernelGGL((k_wtheta_nodes_epochs<HF, BAO>), dim3(P.gnodes, E), dim3(256), P.sh_nodes,
+                         ctx->stream, ctx->cfg, ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, k_min,
+                         k_max, R.D_z, LT, ctx->d_wnodes, stride);
+    if (P.fast) {
+      hipLaunchKernelGGL(k_wtheta_moments_epochs, dim3((unsigned)nseg, (unsigned)LT, kWthParts * E),
+                         dim3(256), 0, ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min),
+                         std::log(k_max), rec, segtot, stride);
+      if (R.sets)
+        hipLaunchKernelGGL(k_wtheta_fast_sets, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
+                           ctx->cfg, L, pd, ptab, pstride, k_min, k_max, din, o, ctx->d_wnodes, rec,
+                           segtot, LT, nseg, stride);
+      else
+        hipLaunchKernelGGL(k_wtheta_fast_epochs, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
+                           ctx->cfg, L, pd, ptab, k_min, k_max, din, o, ctx->d_wnodes, rec, segtot,
+                           LT, nseg, stride);
+    } else if (R.sets) {
+      hipLaunchKernelGGL((k_wtheta_sets<HF, BAO>), dim3((unsigned)n, E), dim3(64 * kWthetaNW), P.sh,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which, pd,
+                         ptab, pstride, k_min, k_max, dD + c0, din, o, ctx->d_wnodes, LT, stride);
+    } else {
+      hipLaunchKernelGGL((k_wtheta_epochs<HF, BAO>), dim3((unsigned)n, E), dim3(64 * kWthetaNW), P.sh,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which, pd,
+                         ptab, k_min, k_max, R.D_z, din, o, ctx->d_wnodes, LT, stride);
+    }
+  }
+  return st.finish();
+}
+
 // w(theta) of n_epoch epochs that share the projection set-up, the k range and D_z (an HOD design
-// or chain at one cosmology): the three launches of wtheta_impl with an epoch axis, the epochs
-// worked off in chunks of kWthEpochChunk (layout: chomp_proj_kernels.h, "The epoch axis").
+// or chain at one cosmology).
 int chomp_wtheta_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double k_min,
                         double k_max, double D_z, const double* theta, size_t n, double* out,
                         int mem) {
   StageRange range_(ctx, "chomp:wtheta_epochs");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!theta || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "wtheta_epochs: bad args");
-  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "wtheta_epochs: n * n_epoch too large");
-  Staging st(ctx, mem, "wtheta_epochs");
-  if (st.rc) return st.rc;
-  if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "wtheta_epochs before kernel_setup");
-  // (what the call does not serve is said first: a HaloFit code on epochs without a HaloFit
-  //  set-up is out of scope here, not a state to repair)
-  if (ctx->precision != CHOMP_PREC_F64)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: fp64 only (the narrowed precision modes belong to chomp_wtheta)");
-  if (which & CHOMP_P_HALOFIT)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: HaloFit spectra are evaluated by chomp_wtheta");
-  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: extrapolated spectra are evaluated by chomp_wtheta");
-  if (ctx->with_bao)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_epochs: the wiggle transfer function is evaluated by chomp_wtheta");
-  int rc = check_power(ctx, which, epoch0, n_epoch);
-  if (rc) return rc;
-  if (!(k_min > 0.0) || !(k_max > k_min) || !(D_z > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_epochs: k range / D_z");
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  const double* din;
-  double* dout;
-  st.in(theta, n, &din);
-  st.out(out, n * n_epoch, &dout);
-  rc = st.place();
-  if (rc) return rc;
-  // (the route and the sizes as in wtheta_impl)
-  const ProjLayout& L = ctx->proj.L;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
-  const int LT = ctx->cfg.divmax < kWthetaTabLevel ? ctx->cfg.divmax : kWthetaTabLevel;
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
-  const double dxK = (ctx->proj.host.ln_kt_max - ctx->proj.host.ln_kt_min) / (double)(L.NKT - 1);
-  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
-  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
-  const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
-                    ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
-  const size_t stride = wth_epoch_stride(LT, nseg, fast);
-  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
-                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
-  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
-  if (rc) return rc;
-  double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // (of the chunk's first epoch)
-  double* segtot = rec + 4 * wth_rec_count(LT);
-  const unsigned gnodes = (unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
-  {
-    constexpr bool HF = false, BAO = false;
-    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the scratch is reused in stream order)
-      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
-      const int e0 = (int)(epoch0 + c0);
-      double* o = dout + c0 * n;
-      hipLaunchKernelGGL((k_wtheta_nodes_epochs<HF, BAO>), dim3(gnodes, E), dim3(256),
-                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
-                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, k_min, k_max, D_z, LT,
-                         ctx->d_wnodes, stride);
-      if (fast) {
-        hipLaunchKernelGGL(k_wtheta_moments_epochs, dim3((unsigned)nseg, (unsigned)LT, kWthParts * E),
-                           dim3(256), 0, ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min),
-                           std::log(k_max), rec, segtot, stride);
-        hipLaunchKernelGGL(k_wtheta_fast_epochs, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
-                           ctx->cfg, L, ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, din, o,
-                           ctx->d_wnodes, rec, segtot, LT, nseg, stride);
-      } else {
-        hipLaunchKernelGGL((k_wtheta_epochs<HF, BAO>), dim3((unsigned)n, E), dim3(64 * kWthetaNW), sh,
-                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                           ctx->proj.d_pd, ctx->proj.d_tab, k_min, k_max, D_z, din, o, ctx->d_wnodes,
-                           LT, stride);
-      }
-    }
-  }
-  return st.finish();
+  const ProjRows R = {"wtheta_epochs", "chomp_wtheta", nullptr, D_z, nullptr};
+  return wtheta_rows(ctx, R, which, epoch0, n_epoch, k_min, k_max, theta, n, out, mem);
 }
 
 // w(theta) of n_epoch epochs, epoch epoch0 + e against projection set e of the last set-up of
@@ -953,85 +1014,8 @@ int chomp_wtheta_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, 
                       int mem) {
   StageRange range_(ctx, "chomp:wtheta_sets");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!D_z || !theta || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: bad args");
-  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: n * n_epoch too large");
-  Staging st(ctx, mem, "wtheta_sets");
-  if (st.rc) return st.rc;
-  const ProjSets& S = ctx->sets;
-  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "wtheta_sets before kernel_setup_sets / kernel_setup_pairs");
-  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
-  if (ctx->precision != CHOMP_PREC_F64)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: fp64 only (the narrowed precision modes belong to chomp_wtheta)");
-  if (which & CHOMP_P_HALOFIT)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: HaloFit spectra are evaluated by chomp_wtheta");
-  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: extrapolated spectra are evaluated by chomp_wtheta");
-  if (ctx->with_bao)
-    return fail(ctx, CHOMP_ERR_SCOPE, "wtheta_sets: the wiggle transfer function is evaluated by chomp_wtheta");
-  if (n_epoch != S.n)
-    return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: n_epoch is not the number of sets of the last kernel_setup_sets / kernel_setup_pairs");
-  int rc = check_power(ctx, which, epoch0, n_epoch);
-  if (rc) return rc;
-  if (!(k_min > 0.0) || !(k_max > k_min)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: k range");
-  for (size_t e = 0; e < n_epoch; ++e)
-    if (!(D_z[e] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "wtheta_sets: D_z");
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* din;
-  double* dout;
-  st.in(theta, n, &din);
-  st.out(out, n * n_epoch, &dout);
-  rc = st.place(n_epoch);         // (D_z is a host array whatever `mem` says: the scratch segment)
-  if (rc) return rc;
-  const double* dD = st.scratch;
-  HIPCHK(hipMemcpyAsync(st.scratch, D_z, n_epoch * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  // (the route and the sizes as in wtheta_impl)
-  const ProjLayout& L = S.L;
-  const size_t pstride = (size_t)L.total;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + 4 * (L.NKT - 1)) * sizeof(double);
-  const int LT = ctx->cfg.divmax < kWthetaTabLevel ? ctx->cfg.divmax : kWthetaTabLevel;
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
-  const double dxK = (S.host.ln_kt_max - S.host.ln_kt_min) / (double)(L.NKT - 1);
-  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
-  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
-  const bool fast = ctx->tune[CHOMP_TUNE_WTHETA_DIRECT] <= 0 &&
-                    ctx->cfg.divmax <= kWthetaTabLevel && L.NKT <= 63;
-  const size_t stride = wth_epoch_stride(LT, nseg, fast);
-  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
-                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
-  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
-  if (rc) return rc;
-  double* rec = ctx->d_wnodes + n_nodes + (n_nodes & 1);   // (of the chunk's first epoch)
-  double* segtot = rec + 4 * wth_rec_count(LT);
-  const unsigned gnodes = (unsigned)((n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
-  {
-    constexpr bool HF = false, BAO = false;
-    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the scratch is reused in stream order)
-      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
-      const int e0 = (int)(epoch0 + c0);
-      double* o = dout + c0 * n;
-      const ProjDev* pd = S.d_pd + c0;                      // (the chunk's first set)
-      const double* ptab = S.d_tab + c0 * pstride;
-      hipLaunchKernelGGL((k_wtheta_nodes_sets<HF, BAO>), dim3(gnodes, E), dim3(256),
-                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
-                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, k_min, k_max, dD + c0, LT,
-                         ctx->d_wnodes, stride);
-      if (fast) {
-        hipLaunchKernelGGL(k_wtheta_moments_epochs, dim3((unsigned)nseg, (unsigned)LT, kWthParts * E),
-                           dim3(256), 0, ctx->stream, ctx->d_wnodes, LT, nseg, std::log(k_min),
-                           std::log(k_max), rec, segtot, stride);
-        hipLaunchKernelGGL(k_wtheta_fast_sets, dim3((unsigned)n, E), dim3(256), 0, ctx->stream,
-                           ctx->cfg, L, pd, ptab, pstride, k_min, k_max, din, o, ctx->d_wnodes, rec,
-                           segtot, LT, nseg, stride);
-      } else {
-        hipLaunchKernelGGL((k_wtheta_sets<HF, BAO>), dim3((unsigned)n, E), dim3(64 * kWthetaNW), sh,
-                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                           pd, ptab, pstride, k_min, k_max, dD + c0, din, o, ctx->d_wnodes, LT,
-                           stride);
-      }
-    }
-  }
-  return st.finish();
+  const ProjRows R = {"wtheta_sets", "chomp_wtheta", &ctx->sets, 0.0, D_z};
+  return wtheta_rows(ctx, R, which, epoch0, n_epoch, k_min, k_max, theta, n, out, mem);
 }
 
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z, const double* ell, size_t n,
@@ -1043,196 +1027,125 @@ int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z, const double
   return cell_impl(ctx, which, epoch, D_z, ell, n, out, mem);
 }
 
+// The chunked driver of chomp_cell_epochs and chomp_cell_sets: the launches of cell_impl with an
+// epoch axis, the epochs worked off in chunks that reuse the slabs of one work buffer (the sizes,
+// the split and the route: CellPlan).  Without sets ONE chi-only node table serves the call
+// (chomp_proj_kernels.h, "The epoch axis" of C_l); with sets every row has its own, built with the
+// chunk ("The set axis of C_l").
+static int cell_rows(chomp_ctx* ctx, const ProjRows& R, int which, size_t epoch0, size_t n_epoch,
+                     const double* ell, size_t n, double* out, int mem) {
+  int rc = batch_args(ctx, R.who, ell && out && (!R.sets || R.D_zs), n, n_epoch);
+  if (rc) return rc;
+  Staging st(ctx, mem, R.who);
+  if (st.rc) return st.rc;
+  rc = rows_check(ctx, R, which, n_epoch, "no narrowed precision mode evaluates C_l");
+  if (rc) return rc;
+  rc = check_power(ctx, which, epoch0, n_epoch);
+  if (rc) return rc;
+  if (!rows_growth_ok(R, n_epoch)) return fail(ctx, CHOMP_ERR_ARG, std::string(R.who) + ": D_z");
+  const ProjLayout& L = R.sets ? R.sets->L : ctx->proj.L;
+  const CellPlan P = cell_plan(ctx->cfg.divmax, ctx->L.NK, L, n, ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL],
+                               R.sets != nullptr);
+  if (!P.deep_fits) return fail(ctx, CHOMP_ERR_ARG, std::string(R.who) + ": halo_npoints too large for k_cell_deep");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!R.sets) { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  const double *din, *dD;
+  double* dout;
+  st.in(ell, n, &din);
+  st.out(out, n * n_epoch, &dout);
+  rc = rows_place(ctx, st, R, n_epoch, &dD);
+  if (rc) return rc;
+  const int LT = P.LT, split = P.split;
+  const size_t stride = P.stride, pstride = (size_t)L.total;
+  const size_t chunk = epoch_chunk(ctx, n_epoch);
+  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, P.doubles(chunk));
+  if (rc) return rc;
+  double* pk_tab = ctx->d_cnodes + P.pk_at;                 // (of the chunk's first row)
+  double* state = ctx->d_cnodes + P.state_at;
+  int* deep = reinterpret_cast<int*>(ctx->d_cnodes + P.deep_at);
+  constexpr bool HF = false, BAO = false;
+  if (!R.sets)                      // (also empties the deep lists of the first chunk)
+    hipLaunchKernelGGL(k_cell_nodes, dim3(P.gnodes), dim3(256), P.sh_nodes, ctx->stream, L,
+                       ctx->proj.d_pd, ctx->proj.d_tab, R.D_z, LT, ctx->d_cnodes, deep, (int)chunk,
+                       2 * stride);
+  if (split < ctx->cfg.divmax) {
+    rc = R.sets ? lds_opt_in(ctx, &k_cell_deep_sets<HF, BAO>, P.deep_lds)
+                : lds_opt_in(ctx, &k_cell_deep_epochs<HF, BAO>, P.deep_lds);
+    if (rc) return rc;
+  }
+  for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {          // (the slabs are reused in stream order)
+    const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
+    const int e0 = (int)(epoch0 + c0);
+    double* o = dout + c0 * n;
+    const ProjDev* pd = R.sets ? R.sets->d_pd + c0 : ctx->proj.d_pd;   // (sets: the chunk's first set)
+    const double* ptab = R.sets ? R.sets->d_tab + c0 * pstride : ctx->proj.d_tab;
+    if (R.sets)                     // (... and empties the rows' deep lists)
+      hipLaunchKernelGGL(k_cell_nodes_sets, dim3(P.gnodes, E), dim3(256), P.sh_nodes, ctx->stream, L,
+                         pd, ptab, pstride, dD + c0, LT, ctx->d_cnodes, deep, stride);
+    hipLaunchKernelGGL((k_cell_ptab_epochs<HF, BAO>), dim3((kPTabN + 256) / 256, E), dim3(256),
+                       (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
+                       ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, pk_tab,
+                       !R.sets && c0 ? deep : (int*)nullptr, stride);
+    if (P.four) {                   // (four multipoles to a block)
+      if (R.sets)
+        hipLaunchKernelGGL((k_cell4_sets<HF, BAO>), dim3((unsigned)((n + 3) / 4), E), dim3(256), P.sh,
+                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                           pd, ptab, pstride, dD + c0, din, (int)n, o, ctx->d_cnodes, LT, pk_tab,
+                           split, deep, state, stride);
+      else
+        hipLaunchKernelGGL((k_cell4_epochs<HF, BAO>), dim3((unsigned)((n + 3) / 4), E), dim3(256), P.sh,
+                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                           pd, ptab, R.D_z, din, (int)n, o, ctx->d_cnodes, LT, pk_tab, split, deep,
+                           state, stride);
+    } else {
+      with_flag(split > LT, [&](auto BEYOND) {
+        if (R.sets)
+          hipLaunchKernelGGL((k_cell_sets<HF, BAO, BEYOND>), dim3((unsigned)n, E), dim3(256), P.sh,
+                             ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                             pd, ptab, pstride, dD + c0, din, o, ctx->d_cnodes, LT, pk_tab, split,
+                             deep, state, stride);
+        else
+          hipLaunchKernelGGL((k_cell_epochs<HF, BAO, BEYOND>), dim3((unsigned)n, E), dim3(256), P.sh,
+                             ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                             pd, ptab, R.D_z, din, o, ctx->d_cnodes, LT, pk_tab, split, deep, state,
+                             stride);
+      });
+    }
+    if (split >= ctx->cfg.divmax) continue;
+    if (R.sets)
+      hipLaunchKernelGGL((k_cell_deep_sets<HF, BAO>), dim3(P.gdeep, E), dim3(kCellDeepThreads), P.shd,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                         pd, ptab, pstride, dD + c0, din, (int)n, o, ctx->d_cnodes, LT, pk_tab,
+                         split, deep, state, stride);
+    else
+      hipLaunchKernelGGL((k_cell_deep_epochs<HF, BAO>), dim3(P.gdeep, E), dim3(kCellDeepThreads), P.shd,
+                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
+                         pd, ptab, R.D_z, din, (int)n, o, ctx->d_cnodes, LT, pk_tab, split, deep,
+                         state, stride);
+  }
+  return st.finish();
+}
+
 // C_l of n_epoch epochs that share the projection set-up and D_z (an HOD design or chain at one
-// cosmology): the launches of cell_impl with an epoch axis behind ONE node table, the epochs worked
-// off in chunks of kWthEpochChunk (layout: chomp_proj_kernels.h, "The epoch axis" of C_l).
+// cosmology).
 int chomp_cell_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, double D_z,
                       const double* ell, size_t n, double* out, int mem) {
   StageRange range_(ctx, "chomp:cell_epochs");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!ell || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: bad args");
-  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: n * n_epoch too large");
-  Staging st(ctx, mem, "cell_epochs");
-  if (st.rc) return st.rc;
-  if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "cell_epochs before kernel_setup");
-  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
-  if (ctx->precision != CHOMP_PREC_F64)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: fp64 only (no narrowed precision mode evaluates C_l)");
-  if (which & CHOMP_P_HALOFIT)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: HaloFit spectra are evaluated by chomp_cell");
-  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: extrapolated spectra are evaluated by chomp_cell");
-  if (ctx->with_bao)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_epochs: the wiggle transfer function is evaluated by chomp_cell");
-  int rc = check_power(ctx, which, epoch0, n_epoch);
-  if (rc) return rc;
-  if (!(D_z > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: D_z");
-  // (the sizes, the split and the route as in cell_impl)
-  const ProjLayout& L = ctx->proj.L;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
-  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);   // (k_cell_deep_epochs)
-  constexpr int kDeepLds = 160 * 1024 - 4096;
-  if (shd > kDeepLds) return fail(ctx, CHOMP_ERR_ARG, "cell_epochs: halo_npoints too large for k_cell_deep");
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  const double* din;
-  double* dout;
-  st.in(ell, n, &din);
-  st.out(out, n * n_epoch, &dout);
-  rc = st.place();
-  if (rc) return rc;
-  const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
-  const size_t stride = cell_epoch_stride(n);
-  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
-                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
-  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
-  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, 3 * n_nodes + stride * chunk);
-  if (rc) return rc;
-  double* pk_tab = ctx->d_cnodes + 3 * n_nodes;            // (of the chunk's first epoch)
-  double* state = pk_tab + kPTabN + 1;
-  int* deep = reinterpret_cast<int*>(state + n * kRombergDump);
-  hipLaunchKernelGGL(k_cell_nodes, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256),
-                     (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, L, ctx->proj.d_pd,
-                     ctx->proj.d_tab, D_z, LT, ctx->d_cnodes, deep, (int)chunk, 2 * stride);
-  const int split = (ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL] > 0 || ctx->cfg.divmax <= kCellSplitLevel)
-                        ? ctx->cfg.divmax : kCellSplitLevel;
-  const unsigned gdeep = (unsigned)(n < 512 ? n : 512);
-  {
-    constexpr bool HF = false, BAO = false;
-    if (split < ctx->cfg.divmax) {
-      const int rcl = lds_opt_in(ctx, &k_cell_deep_epochs<HF, BAO>, kDeepLds);
-      if (rcl) return rcl;
-    }
-    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the slabs are reused in stream order)
-      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
-      const int e0 = (int)(epoch0 + c0);
-      double* o = dout + c0 * n;
-      hipLaunchKernelGGL((k_cell_ptab_epochs<HF, BAO>), dim3((kPTabN + 256) / 256, E), dim3(256),
-                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
-                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, pk_tab,
-                         c0 ? deep : (int*)nullptr, stride);
-      if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
-        hipLaunchKernelGGL((k_cell4_epochs<HF, BAO>), dim3((unsigned)((n + 3) / 4), E), dim3(256), sh,
-                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                           ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n, o, ctx->d_cnodes, LT,
-                           pk_tab, split, deep, state, stride);
-      } else {
-        with_flag(split > LT, [&](auto BEYOND) {
-          hipLaunchKernelGGL((k_cell_epochs<HF, BAO, BEYOND>), dim3((unsigned)n, E), dim3(256), sh,
-                             ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                             ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, o, ctx->d_cnodes, LT, pk_tab,
-                             split, deep, state, stride);
-        });
-      }
-      if (split >= ctx->cfg.divmax) continue;
-      hipLaunchKernelGGL((k_cell_deep_epochs<HF, BAO>), dim3(gdeep, E), dim3(kCellDeepThreads), shd,
-                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                         ctx->proj.d_pd, ctx->proj.d_tab, D_z, din, (int)n, o, ctx->d_cnodes, LT,
-                         pk_tab, split, deep, state, stride);
-    }
-  }
-  return st.finish();
+  const ProjRows R = {"cell_epochs", "chomp_cell", nullptr, D_z, nullptr};
+  return cell_rows(ctx, R, which, epoch0, n_epoch, ell, n, out, mem);
 }
 
 // C_l of n_epoch epochs, epoch epoch0 + e against projection set e of the last set-up of sets with
 // growth D_z[e] (the kernels of a tomographic analysis, or a cosmology design or chain over C_l):
 // chomp_cell_epochs with a per-row set, growth factor and chi-only node table -- its scope, routes
-// and chunks; the work buffer holds one slab per row (chomp_proj_kernels.h, "The set axis of C_l").
+// and chunks.
 int chomp_cell_sets(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, const double* D_z,
                     const double* ell, size_t n, double* out, int mem) {
   StageRange range_(ctx, "chomp:cell_sets");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!D_z || !ell || !out || n == 0 || n_epoch == 0) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: bad args");
-  if (n > 0x7fffffffu / n_epoch) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: n * n_epoch too large");
-  Staging st(ctx, mem, "cell_sets");
-  if (st.rc) return st.rc;
-  const ProjSets& S = ctx->sets;
-  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, "cell_sets before kernel_setup_sets / kernel_setup_pairs");
-  // (what the call does not serve is said first, as in chomp_wtheta_epochs)
-  if (ctx->precision != CHOMP_PREC_F64)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: fp64 only (no narrowed precision mode evaluates C_l)");
-  if (which & CHOMP_P_HALOFIT)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: HaloFit spectra are evaluated by chomp_cell");
-  if ((which & CHOMP_P_EXTRAPOLATE) && (which & 15) != CHOMP_P_LIN)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: extrapolated spectra are evaluated by chomp_cell");
-  if (ctx->with_bao)
-    return fail(ctx, CHOMP_ERR_SCOPE, "cell_sets: the wiggle transfer function is evaluated by chomp_cell");
-  if (n_epoch != S.n)
-    return fail(ctx, CHOMP_ERR_ARG, "cell_sets: n_epoch is not the number of sets of the last kernel_setup_sets / kernel_setup_pairs");
-  int rc = check_power(ctx, which, epoch0, n_epoch);
-  if (rc) return rc;
-  for (size_t e = 0; e < n_epoch; ++e)
-    if (!(D_z[e] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: D_z");
-  // (the sizes, the split and the route as in cell_impl)
-  const ProjLayout& L = S.L;
-  const size_t pstride = (size_t)L.total;
-  const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
-  const size_t shd = sh + (size_t)(kPTabN + 1) * sizeof(double);   // (k_cell_deep_sets)
-  constexpr int kDeepLds = 160 * 1024 - 4096;
-  if (shd > kDeepLds) return fail(ctx, CHOMP_ERR_ARG, "cell_sets: halo_npoints too large for k_cell_deep");
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* din;
-  double* dout;
-  st.in(ell, n, &din);
-  st.out(out, n * n_epoch, &dout);
-  rc = st.place(n_epoch);         // (D_z is a host array whatever `mem` says: the scratch segment)
-  if (rc) return rc;
-  const double* dD = st.scratch;
-  HIPCHK(hipMemcpyAsync(st.scratch, D_z, n_epoch * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const int LT = ctx->cfg.divmax < kCellTabLevel ? ctx->cfg.divmax : kCellTabLevel;
-  const size_t n_nodes = ((size_t)1 << LT) + 1;
-  const size_t stride = cell_set_stride(n, LT);
-  size_t chunk = ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] > 0
-                     ? (size_t)ctx->tune[CHOMP_TUNE_WTHETA_EPOCH_CHUNK] : (size_t)kWthEpochChunk;
-  chunk = std::min(std::min(chunk, (size_t)kWthEpochChunkMax), n_epoch);
-  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, stride * chunk);
-  if (rc) return rc;
-  double* pk_tab = ctx->d_cnodes + 3 * n_nodes;            // (of the chunk's first row)
-  double* state = pk_tab + kPTabN + 1;
-  int* deep = reinterpret_cast<int*>(state + n * kRombergDump);
-  const int split = (ctx->tune[CHOMP_TUNE_CELL_ONE_KERNEL] > 0 || ctx->cfg.divmax <= kCellSplitLevel)
-                        ? ctx->cfg.divmax : kCellSplitLevel;
-  const unsigned gdeep = (unsigned)(n < 512 ? n : 512);
-  {
-    constexpr bool HF = false, BAO = false;
-    if (split < ctx->cfg.divmax) {
-      const int rcl = lds_opt_in(ctx, &k_cell_deep_sets<HF, BAO>, kDeepLds);
-      if (rcl) return rcl;
-    }
-    for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {        // (the slabs are reused in stream order)
-      const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
-      const int e0 = (int)(epoch0 + c0);
-      double* o = dout + c0 * n;
-      const ProjDev* pd = S.d_pd + c0;                      // (the chunk's first set)
-      const double* ptab = S.d_tab + c0 * pstride;
-      hipLaunchKernelGGL(k_cell_nodes_sets, dim3((unsigned)((n_nodes + 255) / 256), E), dim3(256),
-                         (size_t)ProjLds::doubles(L) * sizeof(double), ctx->stream, L, pd, ptab,
-                         pstride, dD + c0, LT, ctx->d_cnodes, deep, stride);
-      hipLaunchKernelGGL((k_cell_ptab_epochs<HF, BAO>), dim3((kPTabN + 256) / 256, E), dim3(256),
-                         (size_t)(12 * (ctx->L.NK - 1)) * sizeof(double), ctx->stream, ctx->cfg,
-                         ctx->L, ctx->d_epochs, e0, ctx->d_tab, which, pk_tab, (int*)nullptr, stride);
-      if (split <= LT && split >= 6 && n >= 16) {   // (four multipoles to a block)
-        hipLaunchKernelGGL((k_cell4_sets<HF, BAO>), dim3((unsigned)((n + 3) / 4), E), dim3(256), sh,
-                           ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                           pd, ptab, pstride, dD + c0, din, (int)n, o, ctx->d_cnodes, LT, pk_tab,
-                           split, deep, state, stride);
-      } else {
-        with_flag(split > LT, [&](auto BEYOND) {
-          hipLaunchKernelGGL((k_cell_sets<HF, BAO, BEYOND>), dim3((unsigned)n, E), dim3(256), sh,
-                             ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                             pd, ptab, pstride, dD + c0, din, o, ctx->d_cnodes, LT, pk_tab, split,
-                             deep, state, stride);
-        });
-      }
-      if (split >= ctx->cfg.divmax) continue;
-      hipLaunchKernelGGL((k_cell_deep_sets<HF, BAO>), dim3(gdeep, E), dim3(kCellDeepThreads), shd,
-                         ctx->stream, ctx->cfg, ctx->L, L, ctx->d_epochs, e0, ctx->d_tab, which,
-                         pd, ptab, pstride, dD + c0, din, (int)n, o, ctx->d_cnodes, LT, pk_tab,
-                         split, deep, state, stride);
-    }
-  }
-  return st.finish();
+  const ProjRows R = {"cell_sets", "chomp_cell", &ctx->sets, 0.0, D_z};
+  return cell_rows(ctx, R, which, epoch0, n_epoch, ell, n, out, mem);
 }
 
 // w(theta) and C_l of one set-up in one call (configs[3], [4]: both observables of a survey).

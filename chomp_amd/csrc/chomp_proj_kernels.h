@@ -1139,6 +1139,44 @@ inline size_t wth_epoch_stride(int LT, int nseg, bool fast) {
   return (n + 1) & ~(size_t)1;
 }
 
+// The host's plan of the w(theta) scratch and launches -- what chomp_wtheta, chomp_wtheta_epochs,
+// chomp_wtheta_sets and (its node-table part) chomp_xi3d_epochs size, place and launch by.  One
+// epoch's scratch is wth_epoch_stride doubles: the node table, then from rec_at the moment
+// records and from tot_at the segments' totals; a chunk keeps one such scratch per epoch.
+struct WthPlan {
+  int LT, nseg;                     // levels within the node table; segments of the moment route
+  bool fast;                        // the moment route (k_wtheta_moments + k_wtheta_fast)
+  size_t n_nodes, stride, rec_at, tot_at;
+  size_t sh_nodes, sh;              // dynamic LDS of k_wtheta_nodes, of k_wtheta
+  unsigned gnodes;                  // blocks of k_wtheta_nodes
+};
+
+// (the scratch of given LT, nseg and route; NK, NKT: the knots of P(k) and of the kernel spline)
+inline WthPlan wth_plan_of(int LT, int nseg, bool fast, int NK = 1, int NKT = 1) {
+  WthPlan P;
+  P.LT = LT; P.nseg = nseg; P.fast = fast;
+  P.n_nodes = ((size_t)1 << LT) + 1;
+  P.stride = wth_epoch_stride(LT, nseg, fast);
+  P.rec_at = P.n_nodes + (P.n_nodes & 1);   // 16-byte aligned records
+  P.tot_at = P.rec_at + 4 * wth_rec_count(LT);
+  P.sh_nodes = (size_t)(12 * (NK - 1)) * sizeof(double);
+  P.sh = (size_t)(12 * (NK - 1) + 4 * (NKT - 1)) * sizeof(double);
+  P.gnodes = (unsigned)((P.n_nodes + 256 * kWthNodesPerThread - 1) / (256 * kWthNodesPerThread));
+  return P;
+}
+
+// The plan of a call: every level within the node table by the moment route (segments about as
+// wide as -- never narrower than -- a piece of the kernel spline) unless `direct`
+// (CHOMP_TUNE_WTHETA_DIRECT), a divmax beyond the table or a long kernel spline rule it out.
+inline WthPlan wth_plan(int divmax, int NK, const ProjLayout& L, double ln_kt_min, double ln_kt_max,
+                        double k_min, double k_max, long long direct) {
+  const double dxK = (ln_kt_max - ln_kt_min) / (double)(L.NKT - 1);
+  int nseg = dxK > 0.0 ? (int)std::floor((std::log(k_max) - std::log(k_min)) / dxK) : 1;
+  nseg = nseg < 1 ? 1 : (nseg > 65535 ? 65535 : nseg);
+  const bool fast = direct <= 0 && divmax <= kWthetaTabLevel && L.NKT <= 63;
+  return wth_plan_of(divmax < kWthetaTabLevel ? divmax : kWthetaTabLevel, nseg, fast, NK, L.NKT);
+}
+
 // (the body of k_wtheta_moments and k_wtheta_moments_epochs; part: the block's part of its segment)
 __device__ __forceinline__ void wth_moments_body(const double* __restrict__ nodes, int LT, int nseg,
                                                  double a, double b, double* __restrict__ rec,
@@ -2081,6 +2119,51 @@ __global__ __launch_bounds__(256, DIRECT ? 2 : 3) void k_cell_epochs(
 // arithmetic is chomp_cell's after chomp_kernel_setup of the set's inputs: the same bodies.
 inline size_t cell_set_stride(size_t n, int LT) {
   return 3 * (((size_t)1 << LT) + 1) + cell_epoch_stride(n);
+}
+
+// The host's plan of the C_l work buffer and launches -- what chomp_cell, chomp_cell_epochs and
+// chomp_cell_sets size, place and launch by.  The first row's spectrum table, Romberg states and
+// deep list (the hand-over of k_cell to k_cell_deep) sit at pk_at, state_at and deep_at in all
+// three forms; they differ in what a further row of a chunk adds (`stride`):
+//   single   the node table, then one slab            (doubles(1))
+//   epochs   one node table, then a slab per epoch    (stride = cell_epoch_stride)
+//   sets     a node table and a slab per row          (stride = cell_set_stride)
+constexpr int kDeepLds = 160 * 1024 - 4096;   // dynamic LDS k_cell_deep is opted in to
+struct CellPlan {
+  size_t sh_nodes, sh, shd;         // dynamic LDS of k_cell_nodes, of k_cell / k_cell4, of k_cell_deep
+  int deep_lds;                     // what k_cell_deep is opted in to (kDeepLds)
+  bool deep_fits;                   // ... holds shd
+  int LT, split;                    // levels within the node table; levels beyond `split` by k_cell_deep
+  bool four;                        // k_cell4 (four multipoles to a block), not k_cell
+  size_t n_nodes, stride, pk_at, state_at, deep_at;
+  unsigned gnodes, gdeep;           // blocks of k_cell_nodes, of k_cell_deep
+  bool per_row_nodes;
+  // the doubles of the work buffer for a chunk of `rows`
+  size_t doubles(size_t rows) const { return (per_row_nodes ? 0 : 3 * n_nodes) + stride * rows; }
+};
+
+// n: multipoles; one_kernel: CHOMP_TUNE_CELL_ONE_KERNEL (every level in k_cell); per_row_nodes:
+// the sets form
+inline CellPlan cell_plan(int divmax, int NK, const ProjLayout& L, size_t n, long long one_kernel,
+                          bool per_row_nodes) {
+  CellPlan P;
+  P.sh_nodes = (size_t)ProjLds::doubles(L) * sizeof(double);
+  P.sh = (size_t)(12 * (NK - 1)) * sizeof(double) + P.sh_nodes;
+  P.shd = P.sh + (size_t)(kPTabN + 1) * sizeof(double);
+  P.deep_lds = kDeepLds;
+  P.deep_fits = P.shd <= (size_t)kDeepLds;
+  P.LT = divmax < kCellTabLevel ? divmax : kCellTabLevel;
+  P.split = (one_kernel > 0 || divmax <= kCellSplitLevel) ? divmax : kCellSplitLevel;
+  P.four = P.split <= P.LT && P.split >= 6 && n >= 16;
+  P.n_nodes = ((size_t)1 << P.LT) + 1;
+  P.per_row_nodes = per_row_nodes;
+  P.stride = per_row_nodes ? cell_set_stride(n, P.LT) : cell_epoch_stride(n);
+  P.pk_at = 3 * P.n_nodes;
+  P.state_at = P.pk_at + (size_t)kPTabN + 1;
+  P.deep_at = P.state_at + n * kRombergDump;
+  P.gnodes = (unsigned)((P.n_nodes + 255) / 256);
+  P.gdeep = (unsigned)(n < 512 ? n : 512);
+  return P;
 }
 // grid (n_ell, E), block 256: k_cell_epochs with row blockIdx.y's own set, tables, growth and nodes.
 template <bool HF, bool BAO, bool DIRECT>

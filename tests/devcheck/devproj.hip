@@ -92,19 +92,10 @@ __global__ void k_logs(double k_min, double k_max, const double* theta, int n, d
   if (i < n) out[2 + i] = log(theta[i]);
 }
 
-// The sizes of chomp_wtheta (one epoch: E = 0) and chomp_wtheta_epochs (E >= 1).
-struct WthSizes {
-  size_t n_nodes, n_rec, n_tot, stride, total, rec_at, tot_at;
-  WthSizes(int LT, int nseg, int E) {
-    n_nodes = ((size_t)1 << LT) + 1;
-    n_rec = 4 * chomp::wth_rec_count(LT);
-    n_tot = 4 * (size_t)(LT + 1) * (size_t)nseg;
-    stride = E > 0 ? chomp::wth_epoch_stride(LT, nseg, true) : 0;
-    total = E > 0 ? stride * (size_t)E : n_nodes + 1 + n_rec + n_tot + 2;
-    rec_at = n_nodes + (n_nodes & 1);
-    tot_at = rec_at + n_rec;
-  }
-};
+// The product's plan of the moment route's scratch, and the doubles of the work buffer by it:
+// chomp_wtheta (E = 0) keeps one epoch's scratch, chomp_wtheta_epochs (E >= 1) one per epoch.
+chomp::WthPlan wth_plan(int LT, int nseg) { return chomp::wth_plan_of(LT, nseg, true); }
+size_t wth_total(const chomp::WthPlan& Z, int E) { return Z.stride * (size_t)(E > 0 ? E : 1); }
 
 bool wth_args_ok(int LT, int nseg, int E) {
   return LT >= 1 && LT <= chomp::kWthetaTabLevel && nseg >= 1 && nseg <= 65535 && E >= 0 &&
@@ -112,7 +103,7 @@ bool wth_args_ok(int LT, int nseg, int E) {
 }
 
 // NaN bytes everywhere, then every epoch's node table; the moment kernel of the form asked for.
-int wth_moments(Dev& d_w, const WthSizes& Z, const double* nodes, int LT, int nseg, double k_min,
+int wth_moments(Dev& d_w, const chomp::WthPlan& Z, const double* nodes, int LT, int nseg, double k_min,
                 double k_max, int E) {
   DJ_TRY(d_w.nan_fill());
   for (int e = 0; e < (E > 0 ? E : 1); ++e)
@@ -175,9 +166,9 @@ int dj_wth_parts() { return chomp::kWthParts; }
 // first epoch start in it (E = 0: the single-epoch call); out: total, rec, segtot, stride
 int dj_wth_sizes(int LT, int nseg, int E, double* out) {
   if (!wth_args_ok(LT, nseg, E)) return -1;
-  const WthSizes Z(LT, nseg, E);
-  out[0] = (double)Z.total; out[1] = (double)Z.rec_at; out[2] = (double)Z.tot_at;
-  out[3] = (double)Z.stride;
+  const chomp::WthPlan Z = wth_plan(LT, nseg);
+  out[0] = (double)wth_total(Z, E); out[1] = (double)Z.rec_at; out[2] = (double)Z.tot_at;
+  out[3] = E > 0 ? (double)Z.stride : 0.0;
   return 0;
 }
 
@@ -186,11 +177,11 @@ int dj_wth_sizes(int LT, int nseg, int E, double* out) {
 int dj_moments(const double* nodes, int LT, int nseg, double k_min, double k_max, int E,
                double* work_out) {
   if (!wth_args_ok(LT, nseg, E)) return -1;
-  const WthSizes Z(LT, nseg, E);
-  Dev d_w(Z.total, nullptr);
+  const chomp::WthPlan Z = wth_plan(LT, nseg);
+  Dev d_w(wth_total(Z, E), nullptr);
   DJ_TRY(d_w.err);
   if (const int rc = wth_moments(d_w, Z, nodes, LT, nseg, k_min, k_max, E)) return rc;
-  DJ_TRY(d_w.back(work_out, Z.total));
+  DJ_TRY(d_w.back(work_out, wth_total(Z, E)));
   return 0;
 }
 
@@ -207,10 +198,10 @@ int dj_wtheta(const double* nodes, int LT, int nseg, double k_min, double k_max,
   if (E > 0 && (n_run != 1 || lt_run[0] != LT)) return -1;
   for (int r = 0; r < n_run; ++r)
     if (lt_run[r] < 1 || lt_run[r] > LT) return -1;
-  const WthSizes Z(LT, nseg, E);
+  const chomp::WthPlan Z = wth_plan(LT, nseg);
   const KernelTab T(NKT, k_pp, ln_kt_min, ln_kt_max);
   const size_t n_out = (size_t)n_theta * (size_t)(E > 0 ? E : n_run);
-  Dev d_w(Z.total, nullptr), d_tab(T.tab.size(), T.tab.data()),
+  Dev d_w(wth_total(Z, E), nullptr), d_tab(T.tab.size(), T.tab.data()),
       d_pd(chomp::kProjDoubles, reinterpret_cast<const double*>(&T.pd)), d_th(n_theta, theta),
       d_o(n_out, nullptr), d_l((size_t)2 + n_theta, nullptr);
   DJ_TRY(d_w.err); DJ_TRY(d_tab.err); DJ_TRY(d_pd.err); DJ_TRY(d_th.err); DJ_TRY(d_o.err);
@@ -239,7 +230,7 @@ int dj_wtheta(const double* nodes, int LT, int nseg, double k_min, double k_max,
   DJ_SYNC();
   DJ_TRY(d_o.back(out, n_out));
   DJ_TRY(d_l.back(logs_out, (size_t)2 + n_theta));
-  if (work_out != nullptr) DJ_TRY(d_w.back(work_out, Z.total));
+  if (work_out != nullptr) DJ_TRY(d_w.back(work_out, wth_total(Z, E)));
   return 0;
 }
 
