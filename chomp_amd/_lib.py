@@ -600,6 +600,11 @@ def _pairs(a, b):
     return numpy.concatenate([a, b])
 
 
+def _ptr(a):
+    """A host array as a double pointer argument; None stays None (the C calls' optional outputs)."""
+    return a.ctypes.data_as(c_double_p) if a is not None else None
+
+
 def _torch_current_stream(device):
     """torch's current HIP stream on `device`, if torch is in use in this process (never
     imports torch or initialises the GPU through it by itself)."""
@@ -1367,49 +1372,48 @@ class Context(object):
         assert x.size == y.size
         info = numpy.empty(3)
         tab, lev = (numpy.empty((n, n)), numpy.empty((n, n))) if with_table else (None, None)
-        ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
         fn = self._L.chomp_kernel_ssc_setup_cross if cross else self._L.chomp_kernel_ssc_setup
         self._check(fn(
             self._h, float(ln_ktheta_min), float(ln_ktheta_max), float(j0_ssc_limit),
-            x.ctypes.data_as(c_double_p), y.ctypes.data_as(c_double_p), x.size,
-            int(bool(with_table)), ptr(info), ptr(tab), ptr(lev)))
+            _ptr(x), _ptr(y), x.size, int(bool(with_table)), _ptr(info), _ptr(tab), _ptr(lev)))
         return info, tab, (lev.astype(int) if with_table else None)
 
+    def _pair_eval(self, fn, a, b):
+        """One value per pair (a[i], b[i]) of ln(k theta): the four kernel_{ssc,ng}_{raw,eval}."""
+        return self._run(fn, [_pairs(a, b)], lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+
+    def _pair_knots(self, fn, pre, theta_a, theta_b, knots):
+        """fn(handle, *pre, theta, n, out, k_b knots, levels) of covariance_ssc, _ssc_cross and
+        _ng: the value per pair; with `knots` also (k_b knots, Romberg levels), each
+        [n, kernel_npoints] (without, the C call gets no array for them)."""
+        nk = self.config.kernel_npoints
+
+        def body(mem, new, th):
+            n = th.size // 2
+            return pre + (th, n, new(n), new((n, nk)) if knots else None,
+                          new((n, nk)) if knots else None)
+        outs = self._run(fn, [_pairs(theta_a, theta_b)], body)
+        if knots:
+            return outs[0], outs[1], outs[2].astype(int)
+        return outs[0]
+
     def kernel_ssc_raw(self, ln_ktheta_a, ln_ktheta_b):
-        return self._run(self._L.chomp_kernel_ssc_raw, [_pairs(ln_ktheta_a, ln_ktheta_b)],
-                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+        return self._pair_eval(self._L.chomp_kernel_ssc_raw, ln_ktheta_a, ln_ktheta_b)
 
     def kernel_ssc_eval(self, ln_ktheta_a, ln_ktheta_b):
-        return self._run(self._L.chomp_kernel_ssc_eval, [_pairs(ln_ktheta_a, ln_ktheta_b)],
-                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+        return self._pair_eval(self._L.chomp_kernel_ssc_eval, ln_ktheta_a, ln_ktheta_b)
 
     def covariance_ssc(self, epoch, area, theta_a, theta_b, knots=False):
         """covariance_ssc for each pair; with knots=True also (k_b knots, Romberg levels),
         each [n, kernel_npoints]."""
-        nk = self.config.kernel_npoints
-
-        def body(mem, new, th):
-            n = th.size // 2
-            return (epoch, float(area), th, n, new(n), new((n, nk)) if knots else None,
-                    new((n, nk)) if knots else None)
-        outs = self._run(self._L.chomp_covariance_ssc, [_pairs(theta_a, theta_b)], body)
-        if knots:
-            return outs[0], outs[1], outs[2].astype(int)
-        return outs[0]
+        return self._pair_knots(self._L.chomp_covariance_ssc, (epoch, float(area)), theta_a, theta_b,
+                                knots)
 
     def covariance_ssc_cross(self, area, theta_a, theta_b, knots=False):
         """covariance_ssc of a cross block for each pair (halo_a's response at k_a, halo_b's at
         k_b, from the staged slots); with knots=True also (k_b knots, Romberg levels)."""
-        nk = self.config.kernel_npoints
-
-        def body(mem, new, th):
-            n = th.size // 2
-            return (float(area), th, n, new(n), new((n, nk)) if knots else None,
-                    new((n, nk)) if knots else None)
-        outs = self._run(self._L.chomp_covariance_ssc_cross, [_pairs(theta_a, theta_b)], body)
-        if knots:
-            return outs[0], outs[1], outs[2].astype(int)
-        return outs[0]
+        return self._pair_knots(self._L.chomp_covariance_ssc_cross, (float(area),), theta_a, theta_b,
+                                knots)
 
     def covariance_ssc_blocks_range(self, n_corr):
         """[n_blocks, 4] = (z_min, z_max, chi_min, chi_max) of the windows of every block (i, j),
@@ -1466,9 +1470,8 @@ class Context(object):
             raise ChompError("covariance_ssc_blocks_table before covariance_ssc_blocks")
         if n_pairs is not None:
             kb, kl = numpy.empty((int(n_pairs), n)), numpy.empty((int(n_pairs), n))
-        ptr = (lambda a: a.ctypes.data_as(c_double_p) if a is not None else None)
         self._check(self._L.chomp_covariance_ssc_blocks_table(
-            self._h, int(block), ptr(info), ptr(tab), ptr(lev), ptr(kb), ptr(kl)))
+            self._h, int(block), _ptr(info), _ptr(tab), _ptr(lev), _ptr(kb), _ptr(kl)))
         if n_pairs is None:
             return info, tab, lev.astype(int)
         return info, tab, lev.astype(int), kb, kl.astype(int)
@@ -1527,31 +1530,22 @@ class Context(object):
                           ChompAccuracyWarning, stacklevel=stacklevel)
 
     def kernel_ng_raw(self, ln_ktheta_a, ln_ktheta_b):
-        return self._run(self._L.chomp_kernel_ng_raw, [_pairs(ln_ktheta_a, ln_ktheta_b)],
-                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+        return self._pair_eval(self._L.chomp_kernel_ng_raw, ln_ktheta_a, ln_ktheta_b)
 
     def kernel_ng_eval(self, ln_ktheta_a, ln_ktheta_b):
-        return self._run(self._L.chomp_kernel_ng_eval, [_pairs(ln_ktheta_a, ln_ktheta_b)],
-                         lambda mem, new, x: (x, x.size // 2, new(x.size // 2)))[0]
+        return self._pair_eval(self._L.chomp_kernel_ng_eval, ln_ktheta_a, ln_ktheta_b)
 
     def covariance_ng(self, area, tri_table, tri_k_min, tri_k_max, theta_a, theta_b,
                       knots=False):
         """covariance_NG for each pair with the I_0^4 table tri_table [N, N] over
         linspace(ln tri_k_min, ln tri_k_max, N); with knots=True also (k_b knots, Romberg
         levels), each [n, kernel_npoints]."""
-        nk = self.config.kernel_npoints
         tri = numpy.ascontiguousarray(tri_table, dtype=numpy.float64)
         if tri.ndim != 2 or tri.shape[0] != tri.shape[1]:
             raise ValueError("covariance_ng: the I_0^4 table must be square")
-
-        def body(mem, new, th):
-            n = th.size // 2
-            return (float(area), tri, tri.shape[0], float(tri_k_min), float(tri_k_max), th, n,
-                    new(n), new((n, nk)) if knots else None, new((n, nk)) if knots else None)
-        outs = self._run(self._L.chomp_covariance_ng, [_pairs(theta_a, theta_b)], body)
-        if knots:
-            return outs[0], outs[1], outs[2].astype(int)
-        return outs[0]
+        return self._pair_knots(self._L.chomp_covariance_ng,
+                                (float(area), tri, tri.shape[0], float(tri_k_min), float(tri_k_max)),
+                                theta_a, theta_b, knots)
 
     def hod_stats(self, epoch0=0, n=None):
         """[n, 3]: effective bias, effective halo mass, satellite fraction."""

@@ -1180,6 +1180,211 @@ int chomp_wtheta_cell(chomp_ctx* ctx, int which, size_t epoch, double k_min, dou
   return rcw;
 }
 
+// ---------------------------------------------------------------------------
+// What the covariance calls share (DESIGN.md, "One set of checks, plans and tails behind the
+// covariance calls").  Every message is composed from the call's name on the failure path only.
+// (templates have C++ linkage: extern "C++" inside this file's extern "C")
+// ---------------------------------------------------------------------------
+// The dynamic LDS of a launch beside the kernel's static LDS fits the 64 kB a workgroup may use.
+extern "C++" template <class Kernel>
+static bool fits_lds(Kernel* kernel, size_t dynamic_bytes) {
+  hipFuncAttributes attr;
+  if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel)) != hipSuccess) return false;
+  return dynamic_bytes + attr.sharedSizeBytes <= 64 * 1024;
+}
+// ... of the instance of a kernel template that `flag` selects.
+extern "C++" template <class Kernel>
+static bool fits_lds(bool flag, Kernel* on, Kernel* off, size_t dynamic_bytes) {
+  return flag ? fits_lds(on, dynamic_bytes) : fits_lds(off, dynamic_bytes);
+}
+
+// One kind of table (or run of scalars) of a slab on its way back to the host: `count` tables
+// of n doubles, the t-th from base + at[t] to out + t * n (out == nullptr: not asked for).
+struct SlabRows {
+  double* out;
+  const int* at;
+  int count;
+  size_t n;
+};
+// Synchronise (unless the caller has), then copy the rows back in the order given; nothing at
+// all when nothing is asked for.
+static int slab_read(chomp_ctx* ctx, const double* base, std::initializer_list<SlabRows> rows,
+                     bool synced = false) {
+  bool any = false;
+  for (const SlabRows& r : rows) any = any || r.out;
+  if (!any) return CHOMP_OK;
+  if (!synced) HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (const SlabRows& r : rows)
+    for (int t = 0; r.out && t < r.count; ++t)
+      HIPCHK(hipMemcpy(r.out + (size_t)t * r.n, base + r.at[t], r.n * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
+// The windows behind a kernel_ssc / kernel_NG / CovarianceFourier state: the context's own
+// kernel_setup, or (four) the two slots of its cross block.
+static CovSrc cov_src(const chomp_ctx* ctx, bool four) {
+  const ProjState& P = ctx->proj;
+  if (!four) return CovSrc{P.d_pd, P.d_tab, nullptr, nullptr};
+  const CrossState& X = ctx->cross;
+  return CovSrc{reinterpret_cast<const ProjDev*>(X.d + X.C.pd[0]), X.d + X.C.ptab[0],
+                reinterpret_cast<const ProjDev*>(X.d + X.C.pd[1]), X.d + X.C.ptab[1]};
+}
+
+// A cross block's slots are staged and of the configuration of L; with `overlap`, their four
+// windows have a redshift in common as well.
+static int check_cross_slots(chomp_ctx* ctx, const ProjLayout& L, const char* what, bool overlap) {
+  const CrossState& X = ctx->cross;
+  if (!X.staged[0] || !X.staged[1])
+    return fail(ctx, CHOMP_ERR_STATE, std::string(what) + " before covariance_cross_stage of both slots");
+  if (X.C.pd[0] - X.C.htab[0] != ctx->L.stride || X.C.N != L.NKT ||
+      X.C.ptab[1] - X.C.ptab[0] < L.total)
+    return fail(ctx, CHOMP_ERR_STATE, std::string(what) + ": the snapshots are of another configuration");
+  if (overlap && !(std::max(X.z_min[0], X.z_min[1]) < std::min(X.z_max[0], X.z_max[1])))
+    return fail(ctx, CHOMP_ERR_SCOPE, std::string(what) + ": the four windows have no redshift in common "
+                                                          "(kernel.py:910-916 would give z_min >= z_max)");
+  return CHOMP_OK;
+}
+
+// *sh: the dynamic LDS of the knots of a cross block (k_cov_cross_knots, k_cov_blocks_knots), in
+// bytes; refused beyond 64 kB.
+static int cross_lds_bytes(chomp_ctx* ctx, const ProjLayout& L, const char* who, size_t* sh) {
+  *sh = (size_t)cov_cross_lds_doubles(ctx->L.NK, L) * sizeof(double);
+  if (*sh > 64 * 1024)
+    return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": halo/cosmo/window_npoints too large for "
+                                                       "the two spectra and four windows of a cross block");
+  return CHOMP_OK;
+}
+
+// The dynamic LDS of the Gaussian term's launches: ln K and the splines of `tables` tables.
+static size_t gaussian_lds_bytes(int N, int tables) {
+  return (size_t)(N + 4 * tables * (N - 1)) * sizeof(double);
+}
+// What the three Gaussian calls ask of (j0_limit, area) and of host angles theta[2 n]; each call
+// keeps what it does between the two.
+static int gaussian_scalars(chomp_ctx* ctx, const char* who, double j0_limit, double area) {
+  if (!(j0_limit > 0.0) || !(area > 0.0))
+    return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": j0_limit and area must be positive");
+  return CHOMP_OK;
+}
+static int gaussian_theta(chomp_ctx* ctx, const char* who, bool host, const double* theta, size_t n) {
+  for (size_t i = 0; host && i < 2 * n; ++i)
+    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": theta must be positive");
+  return CHOMP_OK;
+}
+
+// What the block-axis calls ask of the sets: a set-up of n_corr sets of order 0 and at most 65535
+// blocks; with `overlap` (the super-sample calls), in every block windows with a redshift in
+// common as well (check_cross_slots' rule, from the host's ranges: nothing is launched).
+static int blocks_check(chomp_ctx* ctx, const char* who, size_t n_corr, bool overlap) {
+  const ProjSets& S = ctx->sets;
+  const auto refuse = [&](int code, const std::string& text) { return fail(ctx, code, std::string(who) + text); };
+  if (S.n == 0) return refuse(CHOMP_ERR_STATE, " before kernel_setup_pairs / kernel_setup_sets");
+  if (S.n != n_corr)
+    return refuse(CHOMP_ERR_STATE, ": n_corr is not the number of sets of the last "
+                                   "kernel_setup_pairs / kernel_setup_sets");
+  if (S.host.order != 0)
+    return refuse(CHOMP_ERR_STATE, ": the sets are of Bessel order 2 (the covariance of "
+                                   "w(theta) takes the windows of a Kernel, order 0)");
+  if (n_corr * (n_corr + 1) / 2 > 65535)                  // (n_corr <= kProjSetsMax)
+    return refuse(CHOMP_ERR_ARG, ": more than 65535 blocks (a grid's z dimension)");
+  for (size_t i = 0; overlap && i < n_corr; ++i)
+    for (size_t j = i; j < n_corr; ++j)
+      if (!(std::max(ctx->sets_z_min[i], ctx->sets_z_min[j]) <
+            std::min(ctx->sets_z_max[i], ctx->sets_z_max[j])))
+        return refuse(CHOMP_ERR_SCOPE, ": block (" + std::to_string(i) + ", " + std::to_string(j) +
+                                       "): the four windows have no redshift in common "
+                                       "(kernel.py:910-916 would give z_min >= z_max)");
+  return CHOMP_OK;
+}
+
+// The index block of n_corr correlations (chomp_proj_kernels.h, chomp_cov_kernels.h): epoch |
+// (i, j) and, with `lists`, | the diagonal blocks | the cross blocks.  epoch == nullptr: epoch c
+// for correlation c (the range call reads no epoch; with these the block is most often the one
+// the call behind it sends).
+static std::vector<int> blocks_index(size_t n_corr, const size_t* epoch, bool lists) {
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  std::vector<int> index(n_corr + (lists ? 3 : 2) * n_blocks);
+  for (size_t c = 0; c < n_corr; ++c) index[c] = epoch ? (int)epoch[c] : (int)c;
+  int* diag = lists ? index.data() + n_corr + 2 * n_blocks : nullptr;
+  int* cross = lists ? diag + n_corr : nullptr;
+  size_t b = 0;
+  for (size_t i = 0; i < n_corr; ++i)
+    for (size_t j = i; j < n_corr; ++j, ++b) {
+      index[n_corr + 2 * b] = (int)i;
+      index[n_corr + 2 * b + 1] = (int)j;
+      if (lists) *(i == j ? diag : cross)++ = (int)b;
+    }
+  return index;
+}
+// ... in a state's device buffer (grown if need be), through the state's staging block.
+static int blocks_index_upload(chomp_ctx* ctx, int** d_index, size_t* cap_index, StagedBlock& sh,
+                               const std::vector<int>& index) {
+  const int* before = *d_index;
+  const int rc = ensure(ctx, d_index, cap_index, index.size());
+  if (rc) return rc;
+  if (*d_index != before) sh.reset();
+  return upload(ctx, *d_index, index.data(), index.size() * sizeof(int), sh);
+}
+
+// The pairs of angles of chomp_covariance_ssc, _ssc_cross and _ng: what they refuse ...
+static int pairs_check(chomp_ctx* ctx, const char* who, double area, size_t n) {
+  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": area must be positive");
+  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": at most 65535 pairs a call");
+  return CHOMP_OK;
+}
+static int pairs_positive(chomp_ctx* ctx, const char* who, const double* theta, size_t n) {
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": arguments must be positive");
+  return CHOMP_OK;
+}
+// ... their arrays on the device: theta[2 n], out[n], the k_b knots and their levels [n * NK]
+// (k_ssc_outer reads the knots: staged even when not copied back) ...
+struct PairArrays {
+  const double* theta;
+  double *out, *knots, *lev;
+  void stage(Staging& st, const double* theta_, size_t n, int NK, double* out_, double* kb_knots,
+             double* kb_levels) {
+    st.in(theta_, 2 * n, &theta);
+    st.out(out_, n, &out);
+    st.out(kb_knots, n * NK, &knots);
+    st.out(kb_levels, n * NK, &lev);
+  }
+};
+// ... and the outer integral over the knots the call's own launches left, and the way back.
+static int pairs_finish(chomp_ctx* ctx, Staging& st, const PairArrays& d, size_t n, size_t sh_outer,
+                        double area) {
+  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256), sh_outer, ctx->stream, ctx->cfg, area,
+                     d.knots, d.out);
+  return st.finish();
+}
+
+// The four evaluators of ln(k theta) pairs, chomp_kernel_{ssc,ng}_{raw,eval}: out[n] from
+// ln_ktheta[2 n].  `ready`: the flag of ctx->proj the call needs, set by `setup`; max_n: the most
+// points of a call (0: no bound); finite: the values are checked; launch(d_in, d_out) queues the
+// kernel.
+extern "C++" template <class Launch>
+static int pair_eval(chomp_ctx* ctx, const char* who, const char* setup, bool ProjState::*ready,
+                     size_t max_n, bool finite, const double* ln_ktheta, size_t n, double* out,
+                     Launch launch) {
+  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": bad args");
+  if (!ctx->proj.ready || !(ctx->proj.*ready))
+    return fail(ctx, CHOMP_ERR_STATE, std::string(who) + " before " + setup);
+  if (max_n && n > max_n) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": too many points");
+  for (size_t i = 0; finite && i < 2 * n; ++i)
+    if (!std::isfinite(ln_ktheta[i])) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": ln(k theta) must be finite");
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  Staging st(ctx, CHOMP_HOST, who);
+  const double* d_in;
+  double* d_out;
+  st.in(ln_ktheta, 2 * n, &d_in);
+  st.out(out, n, &d_out);
+  const int rc = st.place();
+  if (rc) return rc;
+  launch(d_in, d_out);
+  return st.finish();
+}
+
 int chomp_covariance_table(chomp_ctx* ctx, int which, size_t epoch, double D_z, double* ln_K,
                            double* proj, double* levels, size_t n) {
   if (!ctx) return CHOMP_ERR_ARG;
@@ -1207,14 +1412,8 @@ int chomp_covariance_table(chomp_ctx* ctx, int which, size_t epoch, double D_z, 
   hipLaunchKernelGGL(k_cov_spline, dim3(1), dim3(64), 0, ctx->stream, C, P.d_cov);
   HIPCHK(hipGetLastError());
   P.cov_ready = true;
-  if (ln_K || proj || levels) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const size_t b = (size_t)C.N * sizeof(double);
-    if (ln_K) HIPCHK(hipMemcpy(ln_K, P.d_cov + C.ln_K, b, hipMemcpyDeviceToHost));
-    if (proj) HIPCHK(hipMemcpy(proj, P.d_cov + C.proj, b, hipMemcpyDeviceToHost));
-    if (levels) HIPCHK(hipMemcpy(levels, P.d_cov + C.lev, b, hipMemcpyDeviceToHost));
-  }
-  return CHOMP_OK;
+  const size_t N = (size_t)C.N;
+  return slab_read(ctx, P.d_cov, {{ln_K, &C.ln_K, 1, N}, {proj, &C.proj, 1, N}, {levels, &C.lev, 1, N}});
 }
 
 int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area, double poisson_a,
@@ -1226,21 +1425,20 @@ int chomp_covariance_gaussian(chomp_ctx* ctx, double j0_limit, double area, doub
   if (st.rc) return st.rc;
   if (!ctx->proj.cov_ready)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_gaussian before covariance_table");
-  if (!(j0_limit > 0.0) || !(area > 0.0))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian: j0_limit and area must be positive");
+  int rc = gaussian_scalars(ctx, "covariance_gaussian", j0_limit, area);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  if (st.host)
-    for (size_t i = 0; i < 2 * n; ++i)
-      if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian: theta must be positive");
+  rc = gaussian_theta(ctx, "covariance_gaussian", st.host, theta, n);
+  if (rc) return rc;
   const double* d_theta;
   double* d_out;
   st.in(theta, 2 * n, &d_theta);
   st.out(out, n, &d_out);
-  const int rc = st.place();
+  rc = st.place();
   if (rc) return rc;
   const CovLayout C = make_cov_layout(ctx->proj.L.NKT);
-  const size_t sh = (size_t)(C.N + 4 * (C.N - 1)) * sizeof(double);
+  const size_t sh = gaussian_lds_bytes(C.N, 1);
   hipLaunchKernelGGL(k_cov_gaussian, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg, C,
                      ctx->proj.d_cov, ctx->d_j0, j0_limit, area, poisson_a, poisson_b, d_theta,
                      d_theta + n, d_out, (double*)nullptr);
@@ -1323,10 +1521,8 @@ int chomp_covariance_table_cross(chomp_ctx* ctx, double D_a, double D_b, double*
     return fail(ctx, CHOMP_ERR_ARG, "covariance_table_cross: length must be kernel_npoints");
   HIPCHK(hipSetDevice(ctx->device));
   X.ready = false;
-  const size_t sh = (size_t)cov_cross_lds_doubles(ctx->L.NK, L) * sizeof(double);
-  if (sh > 64 * 1024)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_table_cross: halo/cosmo/window_npoints too large for "
-                                    "the two spectra and four windows of a cross block");
+  size_t sh;
+  { const int rcl = cross_lds_bytes(ctx, L, "covariance_table_cross", &sh); if (rcl) return rcl; }
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_cov_cross_knots<BAO>, dim3((unsigned)C.N, 4), dim3(256), sh, ctx->stream,
                        c, ctx->L, L, C, X.which[0], X.which[1], D_a, D_b, X.d);
@@ -1334,16 +1530,8 @@ int chomp_covariance_table_cross(chomp_ctx* ctx, double D_a, double D_b, double*
   hipLaunchKernelGGL(k_cov_cross_spline, dim3(4), dim3(64), 0, ctx->stream, C, X.d);
   HIPCHK(hipGetLastError());
   X.ready = true;
-  if (ln_K || tables || levels) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const size_t b = (size_t)C.N * sizeof(double);
-    if (ln_K) HIPCHK(hipMemcpy(ln_K, X.d + C.ln_K, b, hipMemcpyDeviceToHost));
-    for (int t = 0; t < 4; ++t) {
-      if (tables) HIPCHK(hipMemcpy(tables + (size_t)t * C.N, X.d + C.proj[t], b, hipMemcpyDeviceToHost));
-      if (levels) HIPCHK(hipMemcpy(levels + (size_t)t * C.N, X.d + C.lev[t], b, hipMemcpyDeviceToHost));
-    }
-  }
-  return CHOMP_OK;
+  const size_t N = (size_t)C.N;
+  return slab_read(ctx, X.d, {{ln_K, &C.ln_K, 1, N}, {tables, C.proj, 4, N}, {levels, C.lev, 4, N}});
 }
 
 int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area,
@@ -1356,20 +1544,19 @@ int chomp_covariance_gaussian_cross(chomp_ctx* ctx, double j0_limit, double area
   if (st.rc) return st.rc;
   if (!ctx->cross.ready)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_gaussian_cross before covariance_table_cross");
-  if (!(j0_limit > 0.0) || !(area > 0.0))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian_cross: j0_limit and area must be positive");
+  int rc = gaussian_scalars(ctx, "covariance_gaussian_cross", j0_limit, area);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
-  if (st.host)
-    for (size_t i = 0; i < 2 * n; ++i)
-      if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_gaussian_cross: theta must be positive");
+  rc = gaussian_theta(ctx, "covariance_gaussian_cross", st.host, theta, n);
+  if (rc) return rc;
   const double* d_theta;
   double* d_out;
   st.in(theta, 2 * n, &d_theta);
   st.out(out, n, &d_out);
-  const int rc = st.place();
+  rc = st.place();
   if (rc) return rc;
   const CrossLayout& C = ctx->cross.C;
-  const size_t sh = (size_t)(C.N + 16 * (C.N - 1)) * sizeof(double);
+  const size_t sh = gaussian_lds_bytes(C.N, 4);
   hipLaunchKernelGGL(k_cov_cross_gaussian, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
                      C, ctx->cross.d, ctx->d_j0, j0_limit, area, poisson_0, poisson_1, poisson_2,
                      poisson_3, d_theta, d_theta + n, d_out, (double*)nullptr);
@@ -1392,34 +1579,23 @@ int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size
     return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: bad args");
   Staging st(ctx, mem, "covariance_blocks");
   if (st.rc) return st.rc;
+  int rc = blocks_check(ctx, "covariance_blocks", n_corr, false);
+  if (rc) return rc;
   const ProjSets& S = ctx->sets;
-  if (S.n == 0)
-    return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks before kernel_setup_pairs / kernel_setup_sets");
-  if (S.n != n_corr)
-    return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks: n_corr is not the number of sets of the last "
-                                      "kernel_setup_pairs / kernel_setup_sets");
-  if (S.host.order != 0)
-    return fail(ctx, CHOMP_ERR_STATE, "covariance_blocks: the sets are of Bessel order 2 (the covariance "
-                                      "of w(theta) takes the windows of a Kernel, order 0)");
-  const size_t n_blocks = n_corr * (n_corr + 1) / 2;     // (n_corr <= kProjSetsMax)
-  if (n_blocks > 65535)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: more than 65535 blocks (a grid's z dimension)");
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
   if (n_pairs > 0x7fffffffu / n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: n_pairs * n_blocks too large");
   for (size_t c = 0; c < n_corr; ++c) {
     const int rcp = check_power(ctx, which, epoch[c], 1);
     if (rcp) return fail(ctx, rcp, "covariance_blocks: correlation " + std::to_string(c) + ": " + ctx->err);
   }
-  if (!(j0_limit > 0.0) || !(area > 0.0))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: j0_limit and area must be positive");
-  if (st.host)
-    for (size_t i = 0; i < 2 * n_pairs; ++i)
-      if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: theta must be positive");
+  rc = gaussian_scalars(ctx, "covariance_blocks", j0_limit, area);
+  if (!rc) rc = gaussian_theta(ctx, "covariance_blocks", st.host, theta, n_pairs);
+  if (rc) return rc;
   const ProjLayout& L = S.L;
   const CrossLayout C = make_blocks_layout(L.NKT);
-  const size_t sh = (size_t)cov_cross_lds_doubles(ctx->L.NK, L) * sizeof(double);
-  if (sh > 64 * 1024)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: halo/cosmo/window_npoints too large for "
-                                    "the two spectra and four windows of a cross block");
+  size_t sh;
+  rc = cross_lds_bytes(ctx, L, "covariance_blocks", &sh);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   for (size_t c = 0; c < n_corr; ++c) {                  // (a no-op unless `which` extrapolates)
     const int rce = prepare_extrapolation(ctx, which, epoch[c], 1);
@@ -1427,25 +1603,9 @@ int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size
   }
   BlocksState& B = ctx->blocks;
   B.n_corr = 0;
-  int rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)C.total);
-  if (rc) return rc;
-  {
-    const int* before = B.d_index;
-    rc = ensure(ctx, &B.d_index, &B.cap_index, n_corr + 2 * n_blocks);
-    if (rc) return rc;
-    if (B.d_index != before) ctx->sh_blocks.reset();
-  }
-  std::vector<int> index(n_corr + 2 * n_blocks);
-  for (size_t c = 0; c < n_corr; ++c) index[c] = (int)epoch[c];
-  {
-    size_t b = 0;
-    for (size_t i = 0; i < n_corr; ++i)
-      for (size_t j = i; j < n_corr; ++j, ++b) {
-        index[n_corr + 2 * b] = (int)i;
-        index[n_corr + 2 * b + 1] = (int)j;
-      }
-  }
-  rc = upload(ctx, B.d_index, index.data(), index.size() * sizeof(int), ctx->sh_blocks);
+  rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)C.total);
+  if (!rc) rc = blocks_index_upload(ctx, &B.d_index, &B.cap_index, ctx->sh_blocks,
+                                    blocks_index(n_corr, epoch, false));
   if (rc) return rc;
   const double *d_theta, *d_poisson;
   double* d_out;
@@ -1466,7 +1626,7 @@ int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size
                        S.d_pd, S.d_tab, pstride, B.d_index, B.d);
   });
   hipLaunchKernelGGL(k_cov_blocks_spline, dim3(4, Z), dim3(64), 0, ctx->stream, C, nc, B.d_index, B.d);
-  const size_t shg = (size_t)(C.N + 16 * (C.N - 1)) * sizeof(double);
+  const size_t shg = gaussian_lds_bytes(C.N, 4);
   hipLaunchKernelGGL(k_cov_blocks_gaussian, dim3((unsigned)n_pairs, Z), dim3(256), shg, ctx->stream,
                      ctx->cfg, C, nc, B.d_index, B.d, ctx->d_j0, j0_limit, area, d_poisson, d_theta,
                      d_theta + n_pairs, d_out);
@@ -1490,45 +1650,18 @@ int chomp_covariance_blocks_table(chomp_ctx* ctx, size_t block, double* ln_K, do
   for (size_t i = 0, b0 = 0; i < B.n_corr; b0 += B.n_corr - i, ++i) diagonal = diagonal || block == b0;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const double* ct = B.d + block * (size_t)C.total;
-  const size_t bytes = (size_t)C.N * sizeof(double);
-  if (ln_K) HIPCHK(hipMemcpy(ln_K, ct + C.ln_K, bytes, hipMemcpyDeviceToHost));
-  for (int t = 0; t < 4; ++t) {
-    if (diagonal && t > 0) {                             // (a diagonal block has table 0 alone)
-      if (tables) std::fill(tables + (size_t)t * C.N, tables + (size_t)(t + 1) * C.N, 0.0);
-      if (levels) std::fill(levels + (size_t)t * C.N, levels + (size_t)(t + 1) * C.N, 0.0);
-      continue;
-    }
-    if (tables) HIPCHK(hipMemcpy(tables + (size_t)t * C.N, ct + C.proj[t], bytes, hipMemcpyDeviceToHost));
-    if (levels) HIPCHK(hipMemcpy(levels + (size_t)t * C.N, ct + C.lev[t], bytes, hipMemcpyDeviceToHost));
-  }
-  if (scalars) HIPCHK(hipMemcpy(scalars, ct + C.scal, 8 * sizeof(double), hipMemcpyDeviceToHost));
-  return CHOMP_OK;
+  const int rows = diagonal ? 1 : 4;                       // (a diagonal block has table 0 alone)
+  for (double* t : {tables, levels})
+    if (t) std::fill(t + (size_t)rows * C.N, t + (size_t)4 * C.N, 0.0);
+  const size_t N = (size_t)C.N;
+  return slab_read(ctx, B.d + block * (size_t)C.total,
+                   {{ln_K, &C.ln_K, 1, N}, {tables, C.proj, rows, N}, {levels, C.lev, rows, N},
+                    {scalars, &C.scal, 1, 8}}, true);
 }
 
 // ---------------------------------------------------------------------------
 // Gaussian covariance of C_l: CovarianceFourier (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
-static bool fits_lds(const void* kernel, size_t dynamic_bytes);
-
-// The two slots hold windows of this context's configuration.
-static int check_fourier_slots(chomp_ctx* ctx, const ProjLayout& L, const char* what) {
-  const CrossState& X = ctx->cross;
-  const std::string w(what);
-  if (!X.staged[0] || !X.staged[1])
-    return fail(ctx, CHOMP_ERR_STATE, w + " before covariance_cross_stage of both slots");
-  if (X.C.pd[0] - X.C.htab[0] != ctx->L.stride || X.C.N != L.NKT ||
-      X.C.ptab[1] - X.C.ptab[0] < L.total)
-    return fail(ctx, CHOMP_ERR_STATE, w + ": the snapshots are of another configuration");
-  return CHOMP_OK;
-}
-
-static CovSrc fourier_src(const chomp_ctx* ctx) {
-  const CrossState& X = ctx->cross;
-  return CovSrc{reinterpret_cast<const ProjDev*>(X.d + X.C.pd[0]), X.d + X.C.ptab[0],
-                reinterpret_cast<const ProjDev*>(X.d + X.C.pd[1]), X.d + X.C.ptab[1]};
-}
-
 int chomp_covariance_fourier_zbar(chomp_ctx* ctx, const double* z, size_t n_z, double* info) {
   if (!ctx || !z) return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_zbar: bad args");
   if (n_z < 1 || n_z > 256)
@@ -1537,7 +1670,7 @@ int chomp_covariance_fourier_zbar(chomp_ctx* ctx, const double* z, size_t n_z, d
   if (c.corr_npoints < 4)
     return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_zbar: corr_npoints must be at least 4");
   const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
-  { const int rcs = check_fourier_slots(ctx, L, "covariance_fourier_zbar"); if (rcs) return rcs; }
+  { const int rcs = check_cross_slots(ctx, L, "covariance_fourier_zbar", false); if (rcs) return rcs; }
   HIPCHK(hipSetDevice(ctx->device));
   FourierState& S = ctx->fourier;
   S.zbar = S.ready = false;
@@ -1564,7 +1697,7 @@ int chomp_covariance_fourier_zbar(chomp_ctx* ctx, const double* z, size_t n_z, d
   st.in(z, n_z, &d_z);
   const int rc = st.place();
   if (rc) return rc;
-  hipLaunchKernelGGL(k_covf_zbar, dim3(4), dim3(256), 0, ctx->stream, L, F, fourier_src(ctx), d_z,
+  hipLaunchKernelGGL(k_covf_zbar, dim3(4), dim3(256), 0, ctx->stream, L, F, cov_src(ctx, true), d_z,
                      (int)n_z, S.d);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1599,11 +1732,10 @@ int chomp_covariance_fourier_table(chomp_ctx* ctx, int which, const size_t epoch
     if (!(ln_l[i] > ln_l[i - 1]))
       return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_table: ln l knots must increase");
   const ProjLayout L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
-  { const int rcs = check_fourier_slots(ctx, L, "covariance_fourier_table"); if (rcs) return rcs; }
+  { const int rcs = check_cross_slots(ctx, L, "covariance_fourier_table", false); if (rcs) return rcs; }
   HIPCHK(hipSetDevice(ctx->device));
   const size_t sh = (size_t)covf_lds_doubles(ctx->L.NK, L) * sizeof(double);
-  if (!(ctx->with_bao ? fits_lds(reinterpret_cast<const void*>(&k_covf_knots<true>), sh)
-                      : fits_lds(reinterpret_cast<const void*>(&k_covf_knots<false>), sh)))
+  if (!fits_lds(ctx->with_bao, &k_covf_knots<true>, &k_covf_knots<false>, sh))
     return fail(ctx, CHOMP_ERR_ARG, "covariance_fourier_table: halo/cosmo/window_npoints too large "
                                     "for the spectrum and the windows of a pair");
   S.ready = false;
@@ -1617,7 +1749,7 @@ int chomp_covariance_fourier_table(chomp_ctx* ctx, int which, const size_t epoch
   HIPCHK(hipMemcpyAsync(S.d + F.ln_l, ln_l, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_covf_knots<BAO>, dim3((unsigned)F.N, 4), dim3(256), sh, ctx->stream, c,
-                       ctx->L, L, F, fourier_src(ctx), ctx->d_epochs, ctx->d_tab, which,
+                       ctx->L, L, F, cov_src(ctx, true), ctx->d_epochs, ctx->d_tab, which,
                        (int)epoch[0], (int)epoch[1], (int)epoch[2], (int)epoch[3], S.d);
   });
   hipLaunchKernelGGL(k_covf_spline, dim3(4), dim3(64), 0, ctx->stream, F, S.d);
@@ -1660,36 +1792,9 @@ int chomp_covariance_fourier_gaussian(chomp_ctx* ctx, const double* l, size_t n,
 // ---------------------------------------------------------------------------
 // Super-sample covariance of w(theta) (chomp_cov_kernels.h)
 // ---------------------------------------------------------------------------
-// The windows behind the context's kernel_ssc / kernel_NG state: its own kernel_setup, or the two
-// slots of its cross block.
-static CovSrc cov_src(chomp_ctx* ctx, bool four) {
-  ProjState& P = ctx->proj;
-  if (!four) return CovSrc{P.d_pd, P.d_tab, nullptr, nullptr};
-  const CrossState& X = ctx->cross;
-  return CovSrc{reinterpret_cast<const ProjDev*>(X.d + X.C.pd[0]), X.d + X.C.ptab[0],
-                reinterpret_cast<const ProjDev*>(X.d + X.C.pd[1]), X.d + X.C.ptab[1]};
-}
-
-// The dynamic LDS of a launch beside the kernel's static LDS fits the 64 kB a workgroup may use.
-static bool fits_lds(const void* kernel, size_t dynamic_bytes) {
-  hipFuncAttributes attr;
-  if (hipFuncGetAttributes(&attr, kernel) != hipSuccess) return false;
-  return dynamic_bytes + attr.sharedSizeBytes <= 64 * 1024;
-}
-
-// A cross block's slots are staged, of this configuration, and their windows overlap.
-static int check_cross_windows(chomp_ctx* ctx, const char* what) {
-  const CrossState& X = ctx->cross;
-  const std::string w(what);
-  if (!X.staged[0] || !X.staged[1])
-    return fail(ctx, CHOMP_ERR_STATE, w + " before covariance_cross_stage of both slots");
-  if (X.C.pd[0] - X.C.htab[0] != ctx->L.stride || X.C.N != ctx->proj.L.NKT ||
-      X.C.ptab[1] - X.C.ptab[0] < ctx->proj.L.total)
-    return fail(ctx, CHOMP_ERR_STATE, w + ": the snapshots are of another configuration");
-  if (!(std::max(X.z_min[0], X.z_min[1]) < std::min(X.z_max[0], X.z_max[1])))
-    return fail(ctx, CHOMP_ERR_SCOPE, w + ": the four windows have no redshift in common "
-                                          "(kernel.py:910-916 would give z_min >= z_max)");
-  return CHOMP_OK;
+// The plan of the context's kernel_ssc state (set by kernel_ssc_setup).
+static SscPlan ssc_plan_of(const chomp_ctx* ctx) {
+  return ssc_plan(ctx->cfg, ctx->L.NK, ctx->proj.L, ctx->proj.ssc_ns);
 }
 
 static int kernel_ssc_setup(chomp_ctx* ctx, bool four, double ln_ktheta_min, double ln_ktheta_max,
@@ -1709,14 +1814,15 @@ static int kernel_ssc_setup(chomp_ctx* ctx, bool four, double ln_ktheta_min, dou
   for (size_t i = 1; i < n_sigma; ++i)
     if (!(ln_chi[i] > ln_chi[i - 1]))
       return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup: ln chi knots must increase");
-  if (four) { const int rcx = check_cross_windows(ctx, "kernel_ssc_setup_cross"); if (rcx) return rcx; }
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   ProjState& P = ctx->proj;
   const ProjLayout& L = P.L;
-  const SscLayout S = make_ssc_layout(N, (int)n_sigma);
-  const size_t sh = (size_t)ssc_table_lds_doubles(L, S.NS, four) * sizeof(double);
-  if (four && !fits_lds(reinterpret_cast<const void*>(&k_ssc_table<true>), sh))
+  if (four) { const int rcx = check_cross_slots(ctx, L, "kernel_ssc_setup_cross", true); if (rcx) return rcx; }
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
+  const SscPlan plan = ssc_plan(ctx->cfg, ctx->L.NK, L, (int)n_sigma);
+  const SscLayout& S = plan.S;
+  const size_t sh = plan.sh_table[four];
+  if (four && !fits_lds(&k_ssc_table<true>, sh))
     return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_setup_cross: cosmo/window/corr_npoints too large "
                                     "for the four windows of a cross block");
   P.ssc_ready = false;
@@ -1731,7 +1837,7 @@ static int kernel_ssc_setup(chomp_ctx* ctx, bool four, double ln_ktheta_min, dou
     hipLaunchKernelGGL(k_ssc_prep<FOUR>, dim3(1), dim3(256), 0, ctx->stream, ctx->cfg, L, S, src,
                        ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, P.d_ssc);
     if (with_table)
-      hipLaunchKernelGGL(k_ssc_table<FOUR>, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh,
+      hipLaunchKernelGGL(k_ssc_table<FOUR>, dim3(plan.n_tab), dim3(256), sh,
                          ctx->stream, ctx->cfg, L, S, src, ctx->d_j0, P.d_ssc,
                          (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
   });
@@ -1742,14 +1848,8 @@ static int kernel_ssc_setup(chomp_ctx* ctx, bool four, double ln_ktheta_min, dou
   P.ssc_four = four;
   P.ssc_prep = true;
   P.ssc_ready = with_table != 0;
-  if (info || table || levels) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (info) HIPCHK(hipMemcpy(info, P.d_ssc + S.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
-    const size_t b = (size_t)N * N * sizeof(double);
-    if (table) HIPCHK(hipMemcpy(table, P.d_ssc + S.tab, b, hipMemcpyDeviceToHost));
-    if (levels) HIPCHK(hipMemcpy(levels, P.d_ssc + S.lev, b, hipMemcpyDeviceToHost));
-  }
-  return CHOMP_OK;
+  const size_t NN = (size_t)N * N;
+  return slab_read(ctx, P.d_ssc, {{info, &S.scal, 1, 3}, {table, &S.tab, 1, NN}, {levels, &S.lev, 1, NN}});
 }
 
 int chomp_kernel_ssc_setup(chomp_ctx* ctx, double ln_ktheta_min, double ln_ktheta_max,
@@ -1771,7 +1871,7 @@ int chomp_kernel_ssc_setup_cross(chomp_ctx* ctx, double ln_ktheta_min, double ln
 int chomp_covariance_cross_range(chomp_ctx* ctx, double* info) {
   if (!ctx || !info) return fail(ctx, CHOMP_ERR_ARG, "covariance_cross_range: bad args");
   if (!ctx->proj.ready) return fail(ctx, CHOMP_ERR_STATE, "covariance_cross_range before kernel_setup");
-  { const int rcx = check_cross_windows(ctx, "covariance_cross_range"); if (rcx) return rcx; }
+  { const int rcx = check_cross_slots(ctx, ctx->proj.L, "covariance_cross_range", true); if (rcx) return rcx; }
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   Staging st(ctx, CHOMP_HOST, "covariance_cross_range");
@@ -1785,49 +1885,26 @@ int chomp_covariance_cross_range(chomp_ctx* ctx, double* info) {
 }
 
 int chomp_kernel_ssc_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
-  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_raw: bad args");
-  if (!ctx->proj.ready || !ctx->proj.ssc_prep)
-    return fail(ctx, CHOMP_ERR_STATE, "kernel_ssc_raw before kernel_ssc_setup");
-  for (size_t i = 0; i < 2 * n; ++i)
-    if (!std::isfinite(ln_ktheta[i])) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_raw: ln(k theta) must be finite");
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  ProjState& P = ctx->proj;
-  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
-  Staging st(ctx, CHOMP_HOST, "kernel_ssc_raw");
-  const double* d_in;
-  double* d_out;
-  st.in(ln_ktheta, 2 * n, &d_in);
-  st.out(out, n, &d_out);
-  const int rc = st.place();
-  if (rc) return rc;
-  const size_t sh = (size_t)ssc_table_lds_doubles(P.L, S.NS, P.ssc_four) * sizeof(double);
-  const CovSrc src = cov_src(ctx, P.ssc_four);
-  with_flag(P.ssc_four, [&](auto FOUR) {
-    hipLaunchKernelGGL(k_ssc_table<FOUR>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
-                       P.L, S, src, ctx->d_j0, P.d_ssc, d_in, d_in + n, d_out);
+  return pair_eval(ctx, "kernel_ssc_raw", "kernel_ssc_setup", &ProjState::ssc_prep, 0, true, ln_ktheta,
+                   n, out, [&](const double* d_in, double* d_out) {
+    const ProjState& P = ctx->proj;
+    const SscPlan plan = ssc_plan_of(ctx);
+    const CovSrc src = cov_src(ctx, P.ssc_four);
+    with_flag(P.ssc_four, [&](auto FOUR) {
+      hipLaunchKernelGGL(k_ssc_table<FOUR>, dim3((unsigned)n), dim3(256), plan.sh_table[P.ssc_four],
+                         ctx->stream, ctx->cfg, P.L, plan.S, src, ctx->d_j0, P.d_ssc, d_in, d_in + n,
+                         d_out);
+    });
   });
-  return st.finish();
 }
 
 int chomp_kernel_ssc_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
-  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ssc_eval: bad args");
-  if (!ctx->proj.ready || !ctx->proj.ssc_ready)
-    return fail(ctx, CHOMP_ERR_STATE, "kernel_ssc_eval before kernel_ssc_setup");
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  ProjState& P = ctx->proj;
-  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
-  Staging st(ctx, CHOMP_HOST, "kernel_ssc_eval");
-  const double* d_in;
-  double* d_out;
-  st.in(ln_ktheta, 2 * n, &d_in);
-  st.out(out, n, &d_out);
-  const int rc = st.place();
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ssc_eval, grid_1d(n), dim3(256), 0, ctx->stream, S, P.d_ssc, d_in, d_in + n,
-                     (int)n, d_out);
-  return st.finish();
+  return pair_eval(ctx, "kernel_ssc_eval", "kernel_ssc_setup", &ProjState::ssc_ready, 0, false,
+                   ln_ktheta, n, out, [&](const double* d_in, double* d_out) {
+    const ProjState& P = ctx->proj;
+    hipLaunchKernelGGL(k_ssc_eval, grid_1d(n), dim3(256), 0, ctx->stream,
+                       make_ssc_layout(P.L.NKT, P.ssc_ns), P.d_ssc, d_in, d_in + n, (int)n, d_out);
+  });
 }
 
 int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double* theta,
@@ -1838,36 +1915,26 @@ int chomp_covariance_ssc(chomp_ctx* ctx, size_t epoch, double area, const double
   if (ctx->proj.ssc_four)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc: the kernel_ssc table is a cross block's "
                                       "(chomp_covariance_ssc_cross serves it)");
-  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: area must be positive");
-  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: at most 65535 pairs a call");
-  int rc = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch, 1, true);
+  int rc = pairs_check(ctx, "covariance_ssc", area, n);
+  if (!rc) rc = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch, 1, true);
   if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  ProjState& P = ctx->proj;
-  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
-  const int NK = ctx->cfg.kernel_npoints;
-  for (size_t i = 0; i < 2 * n; ++i)
-    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc: arguments must be positive");
+  const ProjState& P = ctx->proj;
+  const SscPlan plan = ssc_plan_of(ctx);
+  rc = pairs_positive(ctx, "covariance_ssc", theta, n);
+  if (rc) return rc;
   Staging st(ctx, CHOMP_HOST, "covariance_ssc");
-  const double* d_theta;
-  double *d_out, *d_knots, *d_lev;   // (k_ssc_outer reads the knots: staged even when not copied back)
-  st.in(theta, 2 * n, &d_theta);
-  st.out(out, n, &d_out);
-  st.out(kb_knots, n * NK, &d_knots);
-  st.out(kb_levels, n * NK, &d_lev);
+  PairArrays d;
+  d.stage(st, theta, n, plan.NK, out, kb_knots, kb_levels);
   rc = st.place();
   if (rc) return rc;
-  const size_t sh = (size_t)ssc_kb_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
   with_flag(ctx->with_bao, [&](auto BAO) {
-    hipLaunchKernelGGL(k_ssc_kb<BAO>, dim3((unsigned)NK, (unsigned)n), dim3(256), sh, ctx->stream,
-                       ctx->cfg, ctx->L, S, ctx->d_epochs, (int)epoch, ctx->d_tab, P.d_ssc,
-                       d_theta, d_theta + n, d_knots, d_lev);
+    hipLaunchKernelGGL(k_ssc_kb<BAO>, dim3((unsigned)plan.NK, (unsigned)n), dim3(256), plan.sh_kb[0],
+                       ctx->stream, ctx->cfg, ctx->L, plan.S, ctx->d_epochs, (int)epoch, ctx->d_tab,
+                       P.d_ssc, d.theta, d.theta + n, d.knots, d.lev);
   });
-  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
-                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
-                     ctx->stream, ctx->cfg, area, d_knots, d_out);
-  return st.finish();
+  return pairs_finish(ctx, st, d, n, plan.sh_outer, area);
 }
 
 int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta, size_t n,
@@ -1875,110 +1942,54 @@ int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta,
   if (!ctx || !theta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: bad args");
   if (!ctx->proj.ready || !ctx->proj.ssc_ready || !ctx->proj.ssc_four)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc_cross before kernel_ssc_setup_cross");
-  { const int rcx = check_cross_windows(ctx, "covariance_ssc_cross"); if (rcx) return rcx; }
+  const ProjState& P = ctx->proj;
+  { const int rcx = check_cross_slots(ctx, P.L, "covariance_ssc_cross", true); if (rcx) return rcx; }
   const CrossState& X = ctx->cross;
   if (!X.response[0] || !X.response[1])
     return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc_cross: the staged epochs do not hold the "
                                       "knot tables of the super-sample response (h_m, pp_mm, i_1_2)");
-  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: area must be positive");
-  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: at most 65535 pairs a call");
-  for (size_t i = 0; i < 2 * n; ++i)
-    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: arguments must be positive");
+  int rc = pairs_check(ctx, "covariance_ssc_cross", area, n);
+  if (!rc) rc = pairs_positive(ctx, "covariance_ssc_cross", theta, n);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  ProjState& P = ctx->proj;
-  const SscLayout S = make_ssc_layout(P.L.NKT, P.ssc_ns);
-  const int NK = ctx->cfg.kernel_npoints;
-  const size_t sh = (size_t)ssc_kb_cross_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
-  if (!(ctx->with_bao ? fits_lds(reinterpret_cast<const void*>(&k_ssc_kb_cross<true>), sh) : fits_lds(reinterpret_cast<const void*>(&k_ssc_kb_cross<false>), sh)))
+  const SscPlan plan = ssc_plan_of(ctx);
+  if (!fits_lds(ctx->with_bao, &k_ssc_kb_cross<true>, &k_ssc_kb_cross<false>, plan.sh_kb[1]))
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_cross: halo/kernel_npoints too large for the "
                                     "two responses of a cross block");
   Staging st(ctx, CHOMP_HOST, "covariance_ssc_cross");
-  const double* d_theta;
-  double *d_out, *d_knots, *d_lev;   // (k_ssc_outer reads the knots: staged even when not copied back)
-  st.in(theta, 2 * n, &d_theta);
-  st.out(out, n, &d_out);
-  st.out(kb_knots, n * NK, &d_knots);
-  st.out(kb_levels, n * NK, &d_lev);
-  const int rc = st.place();
+  PairArrays d;
+  d.stage(st, theta, n, plan.NK, out, kb_knots, kb_levels);
+  rc = st.place();
   if (rc) return rc;
   with_flag(ctx->with_bao, [&](auto BAO) {
-    hipLaunchKernelGGL(k_ssc_kb_cross<BAO>, dim3((unsigned)NK, (unsigned)n), dim3(256), sh,
-                       ctx->stream, ctx->cfg, ctx->L, S, X.C, X.d, P.d_ssc, d_theta, d_theta + n,
-                       d_knots, d_lev);
+    hipLaunchKernelGGL(k_ssc_kb_cross<BAO>, dim3((unsigned)plan.NK, (unsigned)n), dim3(256),
+                       plan.sh_kb[1], ctx->stream, ctx->cfg, ctx->L, plan.S, X.C, X.d, P.d_ssc,
+                       d.theta, d.theta + n, d.knots, d.lev);
   });
-  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
-                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
-                     ctx->stream, ctx->cfg, area, d_knots, d_out);
-  return st.finish();
+  return pairs_finish(ctx, st, d, n, plan.sh_outer, area);
 }
 
 // ---------------------------------------------------------------------------
 // The super-sample term of every block of a CovarianceMulti in one call (chomp_cov_kernels.h,
 // "The block axis of the super-sample term")
 // ---------------------------------------------------------------------------
-// What both calls ask of the sets: a set-up of n_corr sets of order 0, at most 65535 blocks, and
-// in every block windows with a redshift in common (check_cross_windows' rule, from the host's
-// ranges: nothing is launched).
-static int ssc_blocks_check(chomp_ctx* ctx, const char* who, size_t n_corr) {
-  const std::string w = std::string(who) + ": ";
-  const ProjSets& S = ctx->sets;
-  if (S.n == 0) return fail(ctx, CHOMP_ERR_STATE, std::string(who) + " before kernel_setup_pairs / kernel_setup_sets");
-  if (S.n != n_corr)
-    return fail(ctx, CHOMP_ERR_STATE, w + "n_corr is not the number of sets of the last "
-                                          "kernel_setup_pairs / kernel_setup_sets");
-  if (S.host.order != 0)
-    return fail(ctx, CHOMP_ERR_STATE, w + "the sets are of Bessel order 2 (the covariance of "
-                                          "w(theta) takes the windows of a Kernel, order 0)");
-  if (n_corr * (n_corr + 1) / 2 > 65535)                  // (n_corr <= kProjSetsMax)
-    return fail(ctx, CHOMP_ERR_ARG, w + "more than 65535 blocks (a grid's z dimension)");
-  for (size_t i = 0; i < n_corr; ++i)
-    for (size_t j = i; j < n_corr; ++j)
-      if (!(std::max(ctx->sets_z_min[i], ctx->sets_z_min[j]) <
-            std::min(ctx->sets_z_max[i], ctx->sets_z_max[j])))
-        return fail(ctx, CHOMP_ERR_SCOPE, w + "block (" + std::to_string(i) + ", " + std::to_string(j) +
-                                              "): the four windows have no redshift in common "
-                                              "(kernel.py:910-916 would give z_min >= z_max)");
-  return CHOMP_OK;
-}
-
-// The index block of n_corr correlations (chomp_cov_kernels.h): epoch | (i, j) | the diagonal
-// blocks | the cross blocks.  epoch == nullptr: epoch c for correlation c (the range call reads
-// no epoch; with these the block is most often the one the call behind it sends).
-static std::vector<int> ssc_blocks_index(size_t n_corr, const size_t* epoch) {
-  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
-  std::vector<int> index(n_corr + 3 * n_blocks);
-  for (size_t c = 0; c < n_corr; ++c) index[c] = epoch ? (int)epoch[c] : (int)c;
-  int* diag = index.data() + n_corr + 2 * n_blocks;
-  int* cross = diag + n_corr;
-  size_t b = 0;
-  for (size_t i = 0; i < n_corr; ++i)
-    for (size_t j = i; j < n_corr; ++j, ++b) {
-      index[n_corr + 2 * b] = (int)i;
-      index[n_corr + 2 * b + 1] = (int)j;
-      *(i == j ? diag : cross)++ = (int)b;
-    }
-  return index;
-}
-
+// The index block of the super-sample calls (with the lists) in their state's buffer.
 static int ssc_blocks_upload_index(chomp_ctx* ctx, size_t n_corr, const size_t* epoch) {
   SscBlocksState& B = ctx->ssc_blocks;
-  const std::vector<int> index = ssc_blocks_index(n_corr, epoch);
-  const int* before = B.d_index;
-  const int rc = ensure(ctx, &B.d_index, &B.cap_index, index.size());
-  if (rc) return rc;
-  if (B.d_index != before) ctx->sh_ssc_blocks.reset();
-  return upload(ctx, B.d_index, index.data(), index.size() * sizeof(int), ctx->sh_ssc_blocks);
+  return blocks_index_upload(ctx, &B.d_index, &B.cap_index, ctx->sh_ssc_blocks,
+                             blocks_index(n_corr, epoch, true));
 }
 
 int chomp_covariance_ssc_blocks_range(chomp_ctx* ctx, size_t n_corr, double* info) {
   if (!ctx) return CHOMP_ERR_ARG;
   if (!info || n_corr == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks_range: bad args");
-  { const int rcc = ssc_blocks_check(ctx, "covariance_ssc_blocks_range", n_corr); if (rcc) return rcc; }
+  int rc = blocks_check(ctx, "covariance_ssc_blocks_range", n_corr, true);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   const ProjSets& S = ctx->sets;
   const size_t n_blocks = n_corr * (n_corr + 1) / 2;
-  int rc = ssc_blocks_upload_index(ctx, n_corr, nullptr);
+  rc = ssc_blocks_upload_index(ctx, n_corr, nullptr);
   if (rc) return rc;
   Staging st(ctx, CHOMP_HOST, "covariance_ssc_blocks_range");
   double* d_out;
@@ -2005,7 +2016,8 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: bad args");
   Staging st(ctx, mem, "covariance_ssc_blocks");
   if (st.rc) return st.rc;
-  { const int rcc = ssc_blocks_check(ctx, "covariance_ssc_blocks", n_corr); if (rcc) return rcc; }
+  int rc = blocks_check(ctx, "covariance_ssc_blocks", n_corr, true);
+  if (rc) return rc;
   for (size_t c = 0; c < n_corr; ++c) {
     const int rcp = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch[c], 1, true);
     if (rcp) return fail(ctx, rcp, "covariance_ssc_blocks: correlation " + std::to_string(c) + ": " + ctx->err);
@@ -2023,30 +2035,27 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
       if (!(ln_chi[b * n_sigma + q] > ln_chi[b * n_sigma + q - 1]))
         return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: block " + std::to_string(b) +
                                         ": ln chi knots must increase");
-  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: area must be positive");
-  if (n_pairs > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: at most 65535 pairs a call");
+  rc = pairs_check(ctx, "covariance_ssc_blocks", area, n_pairs);
+  if (rc) return rc;
   if (st.host)
     for (size_t q = 0; q < 2 * n_pairs; ++q)
       if (!(theta[q] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: theta must be positive");
   HIPCHK(hipSetDevice(ctx->device));
-  const SscLayout S = make_ssc_layout(N, (int)n_sigma);
-  const int NK = ctx->cfg.kernel_npoints;
+  const SscPlan plan = ssc_plan(ctx->cfg, ctx->L.NK, L, (int)n_sigma);
+  const SscLayout& S = plan.S;
+  const int NK = plan.NK;
   const size_t n_cross = n_blocks - n_corr;
-  const size_t sh_diag = (size_t)ssc_table_lds_doubles(L, S.NS, false) * sizeof(double);
-  const size_t sh_four = (size_t)ssc_table_lds_doubles(L, S.NS, true) * sizeof(double);
-  if (!fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_table<false>), sh_diag) ||
-      (n_cross && !fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_table<true>), sh_four)))
+  if (!fits_lds(&k_ssc_blocks_table<false>, plan.sh_table[0]) ||
+      (n_cross && !fits_lds(&k_ssc_blocks_table<true>, plan.sh_table[1])))
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: cosmo/window/corr_npoints too large "
                                     "for the windows of a block");
   // (one kernel runs both k_b bodies: the launch takes the LDS of the larger)
-  const size_t sh_kb = (size_t)ssc_kb_cross_lds_doubles(ctx->L.NK, S.N) * sizeof(double);
-  if (!(ctx->with_bao ? fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_kb<true>), sh_kb)
-                      : fits_lds(reinterpret_cast<const void*>(&k_ssc_blocks_kb<false>), sh_kb)))
+  if (!fits_lds(ctx->with_bao, &k_ssc_blocks_kb<true>, &k_ssc_blocks_kb<false>, plan.sh_kb[1]))
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: halo/kernel_npoints too large for the "
                                     "two responses of a cross block");
   SscBlocksState& B = ctx->ssc_blocks;
   B.n_corr = 0;
-  int rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)S.total);
+  rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)S.total);
   if (!rc) rc = ensure(ctx, &B.d_kb, &B.cap_kb, 2 * n_blocks * n_pairs * (size_t)NK);
   if (!rc) rc = ensure(ctx, &B.d_sigma, &B.cap_sigma, 2 * n_blocks * n_sigma);
   if (!rc) rc = ssc_blocks_upload_index(ctx, n_corr, epoch);
@@ -2069,7 +2078,6 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
   const size_t pstride = (size_t)L.total;
   const int* d_diag = B.d_index + n_corr + 2 * n_blocks;
   const int* d_cross = d_diag + n_corr;
-  const unsigned n_tab = (unsigned)(N * (N + 1) / 2);
   hipLaunchKernelGGL(k_ssc_blocks_prep<false>, dim3((unsigned)n_corr), dim3(256), 0, ctx->stream,
                      ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
                      ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
@@ -2077,11 +2085,11 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
     hipLaunchKernelGGL(k_ssc_blocks_prep<true>, dim3((unsigned)n_cross), dim3(256), 0, ctx->stream,
                        ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_cross,
                        ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
-  hipLaunchKernelGGL(k_ssc_blocks_table<false>, dim3(n_tab, (unsigned)n_corr), dim3(256), sh_diag,
+  hipLaunchKernelGGL(k_ssc_blocks_table<false>, dim3(plan.n_tab, (unsigned)n_corr), dim3(256), plan.sh_table[0],
                      ctx->stream, ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
                      ctx->d_j0, B.d);
   if (n_cross)
-    hipLaunchKernelGGL(k_ssc_blocks_table<true>, dim3(n_tab, (unsigned)n_cross), dim3(256), sh_four,
+    hipLaunchKernelGGL(k_ssc_blocks_table<true>, dim3(plan.n_tab, (unsigned)n_cross), dim3(256), plan.sh_table[1],
                        ctx->stream, ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index,
                        d_cross, ctx->d_j0, B.d);
   hipLaunchKernelGGL(k_ssc_blocks_bicubic, dim3(Z), dim3(256), 0, ctx->stream, S, B.d);
@@ -2089,12 +2097,11 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
   double* d_lev = B.d_kb + n_blocks * n_pairs * (size_t)NK;
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_ssc_blocks_kb<BAO>, dim3((unsigned)NK, (unsigned)n_pairs, Z), dim3(256),
-                       sh_kb, ctx->stream, ctx->cfg, ctx->L, S, nc, ctx->d_epochs, ctx->d_tab,
+                       plan.sh_kb[1], ctx->stream, ctx->cfg, ctx->L, S, nc, ctx->d_epochs, ctx->d_tab,
                        B.d_index, B.d, d_theta, d_theta + n_pairs, d_knots, d_lev);
   });
-  hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256),
-                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double), ctx->stream, ctx->cfg, area,
-                     d_knots, d_out);
+  hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256), plan.sh_outer,
+                     ctx->stream, ctx->cfg, area, d_knots, d_out);
   HIPCHK(hipGetLastError());
   B.n_corr = n_corr;
   B.n_pairs = n_pairs;
@@ -2114,13 +2121,11 @@ int chomp_covariance_ssc_blocks_table(chomp_ctx* ctx, size_t block, double* info
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const SscLayout& S = B.S;
   const double* st = B.d + block * (size_t)S.total;
-  if (info) {
-    HIPCHK(hipMemcpy(info, st + S.scal + kSscZBar, 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(info + 3, st + S.scal + kSscZMin, 4 * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  const size_t bytes = (size_t)S.N * S.N * sizeof(double);
-  if (table) HIPCHK(hipMemcpy(table, st + S.tab, bytes, hipMemcpyDeviceToHost));
-  if (levels) HIPCHK(hipMemcpy(levels, st + S.lev, bytes, hipMemcpyDeviceToHost));
+  const int z_bar = S.scal + kSscZBar, z_min = S.scal + kSscZMin;
+  const size_t NN = (size_t)S.N * S.N;
+  const int rc = slab_read(ctx, st, {{info, &z_bar, 1, 3}, {info ? info + 3 : nullptr, &z_min, 1, 4},
+                                     {table, &S.tab, 1, NN}, {levels, &S.lev, 1, NN}}, true);
+  if (rc) return rc;
   const size_t row = B.n_pairs * (size_t)ctx->cfg.kernel_npoints;
   if (kb_knots) HIPCHK(hipMemcpy(kb_knots, B.d_kb + block * row, row * sizeof(double), hipMemcpyDeviceToHost));
   if (kb_levels)
@@ -2148,14 +2153,14 @@ int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, doubl
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   ProjState& P = ctx->proj;
   const ProjLayout& L = P.L;
-  const int N = L.NKT;
-  const SscLayout S = make_ssc_layout(N, P.ssc_ns);
-  const NgLayout G = make_ng_layout(N);
+  const SscLayout S = make_ssc_layout(L.NKT, P.ssc_ns);
+  const NgPlan plan = ng_plan(ctx->cfg, L);
+  const NgLayout& G = plan.G;
   // (the windows are those of the kernel_ssc state: a cross block's four, or the context's two)
   const bool four = P.ssc_four;
-  if (four) { const int rcx = check_cross_windows(ctx, "kernel_ng_setup"); if (rcx) return rcx; }
-  const size_t sh = (size_t)ng_table_lds_doubles(L, four) * sizeof(double);
-  if (four && !fits_lds(reinterpret_cast<const void*>(&k_ng_table<true>), sh))
+  if (four) { const int rcx = check_cross_slots(ctx, L, "kernel_ng_setup", true); if (rcx) return rcx; }
+  const size_t sh = plan.sh_table[four];
+  if (four && !fits_lds(&k_ng_table<true>, sh))
     return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_setup: cosmo/window_npoints too large for the four "
                                     "windows of a cross block");
   P.ng_ready = false;
@@ -2166,7 +2171,7 @@ int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, doubl
   if (with_table) {
     const CovSrc src = cov_src(ctx, four);
     with_flag(four, [&](auto FOUR) {
-      hipLaunchKernelGGL(k_ng_table<FOUR>, dim3((unsigned)(N * (N + 1) / 2)), dim3(256), sh,
+      hipLaunchKernelGGL(k_ng_table<FOUR>, dim3(plan.n_tab), dim3(256), sh,
                          ctx->stream, ctx->cfg, L, G, src, ctx->d_j0, P.d_ng,
                          (const double*)nullptr, (const double*)nullptr, (double*)nullptr,
                          ng_status(ctx));
@@ -2177,63 +2182,32 @@ int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, doubl
   P.ng_four = four;
   P.ng_prep = true;
   P.ng_ready = with_table != 0;
-  if (table || levels || table_min) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const size_t b = (size_t)N * N * sizeof(double);
-    if (table) HIPCHK(hipMemcpy(table, P.d_ng + G.tab, b, hipMemcpyDeviceToHost));
-    if (levels) HIPCHK(hipMemcpy(levels, P.d_ng + G.lev, b, hipMemcpyDeviceToHost));
-    if (table_min)
-      HIPCHK(hipMemcpy(table_min, P.d_ng + G.scal + kNgMin, sizeof(double), hipMemcpyDeviceToHost));
-  }
-  return CHOMP_OK;
+  const int at_min = G.scal + kNgMin;
+  const size_t NN = (size_t)G.N * G.N;
+  return slab_read(ctx, P.d_ng, {{table, &G.tab, 1, NN}, {levels, &G.lev, 1, NN}, {table_min, &at_min, 1, 1}});
 }
 
 int chomp_kernel_ng_raw(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
-  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_raw: bad args");
-  if (!ctx->proj.ready || !ctx->proj.ng_prep)
-    return fail(ctx, CHOMP_ERR_STATE, "kernel_ng_raw before kernel_ng_setup");
-  if (n > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_raw: too many points");
-  for (size_t i = 0; i < 2 * n; ++i)
-    if (!std::isfinite(ln_ktheta[i])) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_raw: ln(k theta) must be finite");
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  ProjState& P = ctx->proj;
-  const NgLayout G = make_ng_layout(P.L.NKT);
-  Staging st(ctx, CHOMP_HOST, "kernel_ng_raw");
-  const double* d_in;
-  double* d_out;
-  st.in(ln_ktheta, 2 * n, &d_in);
-  st.out(out, n, &d_out);
-  const int rc = st.place();
-  if (rc) return rc;
-  const size_t sh = (size_t)ng_table_lds_doubles(P.L, P.ng_four) * sizeof(double);
-  const CovSrc src = cov_src(ctx, P.ng_four);
-  with_flag(P.ng_four, [&](auto FOUR) {
-    hipLaunchKernelGGL(k_ng_table<FOUR>, dim3((unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
-                       P.L, G, src, ctx->d_j0, P.d_ng, d_in, d_in + n, d_out, ng_status(ctx));
+  return pair_eval(ctx, "kernel_ng_raw", "kernel_ng_setup", &ProjState::ng_prep, (size_t)INT32_MAX, true,
+                   ln_ktheta, n, out, [&](const double* d_in, double* d_out) {
+    const ProjState& P = ctx->proj;
+    const NgPlan plan = ng_plan(ctx->cfg, P.L);
+    const CovSrc src = cov_src(ctx, P.ng_four);
+    with_flag(P.ng_four, [&](auto FOUR) {
+      hipLaunchKernelGGL(k_ng_table<FOUR>, dim3((unsigned)n), dim3(256), plan.sh_table[P.ng_four],
+                         ctx->stream, ctx->cfg, P.L, plan.G, src, ctx->d_j0, P.d_ng, d_in, d_in + n,
+                         d_out, ng_status(ctx));
+    });
   });
-  return st.finish();
 }
 
 int chomp_kernel_ng_eval(chomp_ctx* ctx, const double* ln_ktheta, size_t n, double* out) {
-  if (!ctx || !ln_ktheta || !out || n == 0) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_eval: bad args");
-  if (!ctx->proj.ready || !ctx->proj.ng_ready)
-    return fail(ctx, CHOMP_ERR_STATE, "kernel_ng_eval before kernel_ng_setup");
-  if (n > (size_t)INT32_MAX) return fail(ctx, CHOMP_ERR_ARG, "kernel_ng_eval: too many points");
-  HIPCHK(hipSetDevice(ctx->device));
-  { const int rcj = proj_join(ctx); if (rcj) return rcj; }
-  ProjState& P = ctx->proj;
-  const NgLayout G = make_ng_layout(P.L.NKT);
-  Staging st(ctx, CHOMP_HOST, "kernel_ng_eval");
-  const double* d_in;
-  double* d_out;
-  st.in(ln_ktheta, 2 * n, &d_in);
-  st.out(out, n, &d_out);
-  const int rc = st.place();
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ng_eval, grid_1d(n), dim3(256), 0, ctx->stream, G, P.d_ng, d_in, d_in + n,
-                     (int)n, d_out);
-  return st.finish();
+  return pair_eval(ctx, "kernel_ng_eval", "kernel_ng_setup", &ProjState::ng_ready, (size_t)INT32_MAX,
+                   false, ln_ktheta, n, out, [&](const double* d_in, double* d_out) {
+    const ProjState& P = ctx->proj;
+    hipLaunchKernelGGL(k_ng_eval, grid_1d(n), dim3(256), 0, ctx->stream, make_ng_layout(P.L.NKT),
+                       P.d_ng, d_in, d_in + n, (int)n, d_out);
+  });
 }
 
 int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, size_t n_tri,
@@ -2243,41 +2217,35 @@ int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, si
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: bad args");
   if (!ctx->proj.ready || !ctx->proj.ng_ready)
     return fail(ctx, CHOMP_ERR_STATE, "covariance_ng before kernel_ng_setup");
-  if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: area must be positive");
-  if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: at most 65535 pairs a call");
+  int rc = pairs_check(ctx, "covariance_ng", area, n);
+  if (rc) return rc;
   if (n_tri < 4 || n_tri > 64)
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: the I_0^4 table must be 4..64 knots a side");
   if (!(tri_k_min > 0.0) || !(tri_k_max > tri_k_min))
     return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: the I_0^4 table's k range");
-  for (size_t i = 0; i < 2 * n; ++i)
-    if (!(theta[i] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng: arguments must be positive");
+  rc = pairs_positive(ctx, "covariance_ng", theta, n);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   { const int rcj = proj_join(ctx); if (rcj) return rcj; }
   ProjState& P = ctx->proj;
-  const NgLayout G = make_ng_layout(P.L.NKT);
+  const NgPlan plan = ng_plan(ctx->cfg, P.L);
+  const NgLayout& G = plan.G;
   const NgTriLayout T = make_ng_tri_layout((int)n_tri);
-  const int NK = ctx->cfg.kernel_npoints;
   { const int rce = ensure(ctx, &P.d_ng_tri, &P.cap_ng_tri, (size_t)T.total); if (rce) return rce; }
   Staging st(ctx, CHOMP_HOST, "covariance_ng");
-  const double *d_theta, *d_tri_in;
-  double *d_out, *d_knots, *d_lev;   // (k_ssc_outer reads the knots: staged even when not copied back)
-  st.in(theta, 2 * n, &d_theta);
+  PairArrays d;
+  const double* d_tri_in;
+  d.stage(st, theta, n, plan.NK, out, kb_knots, kb_levels);
   st.in(tri_table, n_tri * n_tri, &d_tri_in);
-  st.out(out, n, &d_out);
-  st.out(kb_knots, n * NK, &d_knots);
-  st.out(kb_levels, n * NK, &d_lev);
-  const int rc = st.place();
+  rc = st.place();
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(P.d_ng_tri + T.tab, d_tri_in, n_tri * n_tri * sizeof(double),
                         hipMemcpyDeviceToDevice, ctx->stream));
   hipLaunchKernelGGL(k_ng_tri, dim3(1), dim3(256), 0, ctx->stream, T, tri_k_min, tri_k_max,
                      P.d_ng_tri);
   const size_t sh = (size_t)ng_kb_lds_doubles(G.N, T.N) * sizeof(double);
-  hipLaunchKernelGGL(k_ng_kb, dim3((unsigned)NK, (unsigned)n), dim3(256), sh, ctx->stream, ctx->cfg,
-                     G, T, P.d_ng, P.d_ng_tri, tri_k_min, tri_k_max, d_theta, d_theta + n, d_knots,
-                     d_lev, ng_status(ctx));
-  hipLaunchKernelGGL(k_ssc_outer, dim3((unsigned)n), dim3(256),
-                     (size_t)ssc_outer_lds_doubles(NK) * sizeof(double),
-                     ctx->stream, ctx->cfg, area, d_knots, d_out);
-  return st.finish();
+  hipLaunchKernelGGL(k_ng_kb, dim3((unsigned)plan.NK, (unsigned)n), dim3(256), sh, ctx->stream,
+                     ctx->cfg, G, T, P.d_ng, P.d_ng_tri, tri_k_min, tri_k_max, d.theta, d.theta + n,
+                     d.knots, d.lev, ng_status(ctx));
+  return pairs_finish(ctx, st, d, n, plan.sh_outer, area);
 }

@@ -147,6 +147,31 @@ inline int ng_table_lds_doubles(const ProjLayout& L, bool four) {
   return four ? CovWindows<true>::doubles(L) : CovWindows<false>::doubles(L);
 }
 
+// The host's plan of the super-sample launches -- what kernel_ssc_setup, chomp_kernel_ssc_raw,
+// chomp_covariance_ssc, _ssc_cross and _ssc_blocks size and launch by.  Indexed by `four`: the two
+// windows of a matching block, or the four of a cross block (and with them its two responses).
+struct SscPlan {
+  SscLayout S;
+  int NK;                           // the k_b knots of a pair of angles (kernel_npoints)
+  size_t sh_table[2];               // dynamic LDS of k_ssc_table / k_ssc_blocks_table
+  size_t sh_kb[2];                  // ... of k_ssc_kb, of k_ssc_kb_cross / k_ssc_blocks_kb
+  size_t sh_outer;                  // ... of k_ssc_outer / k_ssc_blocks_outer
+  unsigned n_tab;                   // blocks of a table launch: the upper triangle of N x N
+};
+// (NK_halo: the knots of P(k); NS: the sigma^2 knots)
+inline SscPlan ssc_plan(const chomp_config& cfg, int NK_halo, const ProjLayout& L, int NS) {
+  SscPlan P;
+  P.S = make_ssc_layout(L.NKT, NS);
+  P.NK = cfg.kernel_npoints;
+  for (int four = 0; four < 2; ++four)
+    P.sh_table[four] = (size_t)ssc_table_lds_doubles(L, NS, four != 0) * sizeof(double);
+  P.sh_kb[0] = (size_t)ssc_kb_lds_doubles(NK_halo, P.S.N) * sizeof(double);
+  P.sh_kb[1] = (size_t)ssc_kb_cross_lds_doubles(NK_halo, P.S.N) * sizeof(double);
+  P.sh_outer = (size_t)ssc_outer_lds_doubles(P.NK) * sizeof(double);
+  P.n_tab = (unsigned)(P.S.N * (P.S.N + 1) / 2);
+  return P;
+}
+
 // kernel.py:1103-1111 (_kernel_NG_integrand): a1 a2 b1 b2 D^4 / chi^2 J0 J0 in the reference's
 // order of operations (norm = 1 multiplies exactly); with a1 = b1, a2 = b2 of a matching block
 // that is wa wb wa wb.
@@ -856,6 +881,26 @@ inline NgTriLayout make_ng_tri_layout(int N) {
 }
 // Dynamic LDS of k_ng_kb, in doubles: the kernel_NG row (SscRow) and the trispectrum row.
 inline int ng_kb_lds_doubles(int N, int NT) { return 5 * N - 4 + NT + 16 * (NT - 1); }
+
+// The host's plan of the kernel_NG launches, as SscPlan is of the super-sample ones: what
+// chomp_kernel_ng_setup, _ng_raw, _ng_eval and chomp_covariance_ng size and launch by.
+struct NgPlan {
+  NgLayout G;
+  int NK;                           // the k_b knots of a pair of angles (kernel_npoints)
+  size_t sh_table[2];               // dynamic LDS of k_ng_table: two windows, four
+  size_t sh_outer;                  // ... of k_ssc_outer
+  unsigned n_tab;                   // blocks of the table launch: the upper triangle of N x N
+};
+inline NgPlan ng_plan(const chomp_config& cfg, const ProjLayout& L) {
+  NgPlan P;
+  P.G = make_ng_layout(L.NKT);
+  P.NK = cfg.kernel_npoints;
+  for (int four = 0; four < 2; ++four)
+    P.sh_table[four] = (size_t)ng_table_lds_doubles(L, four != 0) * sizeof(double);
+  P.sh_outer = (size_t)ssc_outer_lds_doubles(P.NK) * sizeof(double);
+  P.n_tab = (unsigned)(P.G.N * (P.G.N + 1) / 2);
+  return P;
+}
 
 // grid 1, block 256: z_bar_NG, chi(z_bar_NG), D(z_bar_NG) and the ln k theta knots from the
 // kernel_ssc block (k_ssc_prep has run), _j0_limit, and the status bit cleared.
