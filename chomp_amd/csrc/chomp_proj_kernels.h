@@ -1996,7 +1996,9 @@ struct CellTabIntegrand {
                      q2 * (ab * d * ef) * (-1.0 / 12.0) + q3 * (ab * t * ef) * (1.0 / 12.0) +
                      q4 * (ab * cd * f) * (-1.0 / 24.0) + q5 * (ab * cd * e) * (1.0 / 120.0);
     *ok = in || zero_out;
-    return in ? v : 0.0;
+    // (at the table's last point the weights are 0 .. 0 1 only up to the rounding of
+    //  q5 * 120 * (1 / 120): the spectrum at k_max is the last entry itself)
+    return in ? (u == (double)kPTabN ? q5 : v) : 0.0;
   }
   __device__ __forceinline__ void operator()(double chi, double (&out)[1], int lev, long j) const {
     if (lev <= LT) {

@@ -3,7 +3,9 @@ of tests/hostcheck: libdevcheck.so (devcheck.hip: the fp64 primitives of chomp_m
 wavefront Romberg of chomp_romberg.h), libdevphys.so (devphys.hip: the halo-model physics of
 chomp_math.h, through the product's whole header chain from chomp_cov_kernels.h down) and
 libdevproj.so (devproj.hip: the moment route of w(theta), the bicubic tables and HaloFit's
-quintic derivatives of chomp_proj_kernels.h / chomp_cov_kernels.h).  Each harness is
+quintic derivatives of chomp_proj_kernels.h / chomp_cov_kernels.h) and libdevpower.so
+(devpower.hip: the spectrum evaluator and the Stage E launch shapes of chomp_power_kernels.h,
+the spectrum table and its stencil of chomp_proj_kernels.h).  Each harness is
 compiled with the product's compiler flags (imported from chomp_amd._lib, never copied) and
 rebuilt only when the content of what IT is compiled from changes, as _lib.py does for the
 product library: its own source, .so and content hash, the hash over every product header it
@@ -51,7 +53,7 @@ class Harness:
 
 
 HARNESSES = {"devcheck": Harness("devcheck"), "devphys": Harness("devphys"),
-             "devproj": Harness("devproj")}
+             "devproj": Harness("devproj"), "devpower": Harness("devpower")}
 # the first harness under its earlier names
 SRC = HARNESSES["devcheck"].src
 SO = HARNESSES["devcheck"].so
@@ -109,8 +111,24 @@ PROJ_ENTRY_POINTS = {
     "dj_quintic_grid": [_i, _p],
     "dj_quintic": [_p, _i, _p, _i, _p],
 }
+# ... and for the fourth (devpower.hip); _S: the set-up every entry point starts with (n_epoch,
+# ein, tab, NK, k_min, k_max)
+_S = [_i, _p, _p, _i, _d, _d]
+POWER_ENTRY_POINTS = {
+    "dw_ptab_n": [], "dw_sizeof_epoch": [], "dw_epoch_inputs": [], "dw_wave_bits": [_ip],
+    "dw_layout": [_i, _ip],
+    "dw_logs": [_d, _d, _p],
+    "dw_epochs": _S + [_v, _p],
+    "dw_eval": _S + [_p, _i, _i, _p, _i, _p],
+    "dw_at_ln": _S + [_p, _i, _i, _i, _p, _i, _p],
+    "dw_grid": _S + [_p, _i, _i, _i, _i, _p, _i, _p],
+    "dw_stream": _S + [_p, _i, _i, _i, _i, _p, _i, _i, _p, _ip, _ip],
+    "dw_extrap": _S + [_i, _i, _p],
+    "dw_ptab": _S[1:] + [_i, _p],
+    "dw_stencil": _S[1:] + [_i, _p, _p, _p, _i, _p],
+}
 ALL_ENTRY_POINTS = {"devcheck": ENTRY_POINTS, "devphys": PHYS_ENTRY_POINTS,
-                    "devproj": PROJ_ENTRY_POINTS}
+                    "devproj": PROJ_ENTRY_POINTS, "devpower": POWER_ENTRY_POINTS}
 # dc_quad shapes
 SHAPE = {"group1": 0, "group2": 1, "group4": 2, "group8": 3, "group16": 4,
          "group1_nf2": 5, "group4_nf2": 6, "group4_unroll4": 7, "group4_fast4": 8,
@@ -160,7 +178,7 @@ def build(force=False, harness="devcheck"):
 
 
 VOID = {"devcheck": ("dc_fma_k_constants", "dc_gl16"), "devphys": ("dp_epoch_offsets",),
-        "devproj": ("dj_quintic_grid",)}
+        "devproj": ("dj_quintic_grid",), "devpower": ("dw_wave_bits",)}
 
 
 def load(harness="devcheck"):

@@ -1,8 +1,10 @@
 """The device harnesses (tests/devcheck: devcheck.hip, the fp64 primitives and the wavefront
 Romberg; devphys.hip, the halo-model physics; devproj.hip, the moment route of w(theta), the
-bicubic tables and the quintic derivatives) compile for
+bicubic tables and the quintic derivatives; devpower.hip, the spectrum evaluator and the Stage E
+launch shapes) compile for
 gfx950 against the current headers and export every entry point the GPU tests
-(test_gpu_devmath.py, test_gpu_romberg.py; test_gpu_devphys.py; test_gpu_devproj.py) use.  No GPU is needed: hipcc cross-compiles.  This
+(test_gpu_devmath.py, test_gpu_romberg.py; test_gpu_devphys.py; test_gpu_devproj.py;
+test_gpu_devpower.py) use.  No GPU is needed: hipcc cross-compiles.  This
 keeps the harness from rotting when a header's signature changes in a change developed without
 a GPU."""
 import ctypes
@@ -115,6 +117,70 @@ def test_devproj_compiles_and_exports():
     assert x[0] == math.log(0.1) and x[6] == math.log(10.0) and list(x) == sorted(x)
 
 
+@pytest.mark.skipif(not devcheck_build.have_hipcc(), reason="hipcc is not installed")
+def test_devpower_compiles_and_exports():
+    H = devcheck_build.HARNESSES["devpower"]
+    others = [devcheck_build.HARNESSES[n] for n in ("devcheck", "devphys", "devproj")]
+    for o in others:
+        devcheck_build.build(harness=o.name)
+    stamps = [os.stat(o.so).st_mtime_ns for o in others]
+    path = devcheck_build.build(harness="devpower")
+    assert path == H.so and all(path != o.so for o in others)
+    stamp = os.stat(path).st_mtime_ns
+    assert devcheck_build.build(harness="devpower") == path
+    assert os.stat(path).st_mtime_ns == stamp                 # (second call: nothing to do)
+    assert [os.stat(o.so).st_mtime_ns for o in others] == stamps   # (the others: left alone)
+    with open(H.hash) as f:
+        assert f.read().strip() == devcheck_build.source_hash("devpower")
+    L = ctypes.CDLL(path)
+    for name in devcheck_build.POWER_ENTRY_POINTS:
+        assert hasattr(L, name), name
+    assert set(devcheck_build.VOID["devpower"]) <= set(devcheck_build.POWER_ENTRY_POINTS)
+    assert devcheck_build.ALL_ENTRY_POINTS["devpower"] is devcheck_build.POWER_ENTRY_POINTS
+    assert all(n.startswith("dw_") for n in devcheck_build.POWER_ENTRY_POINTS)
+    # every entry point the GPU test names is declared (and so exported, above)
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "test_gpu_devpower.py")) as f:
+        named = set(re.findall(r"\b(dw_[a-z0-9_]+)\b", f.read()))
+    assert named and named <= set(devcheck_build.POWER_ENTRY_POINTS), named
+    # the package never loads it
+    from chomp_amd import _lib
+    assert not any("devpower" in src for src, _ in _lib.UNITS)
+    # its hash covers the header chain and the epoch filler it shares with devphys.hip
+    for name in ("devpower", "devphys"):
+        base = [os.path.basename(p) for p in devcheck_build.HARNESSES[name].headers]
+        assert "epoch_fill.h" in base, name
+    base = [os.path.basename(p) for p in H.headers]
+    for need in ("chomp_cov_kernels.h", "chomp_proj_kernels.h", "chomp_power_kernels.h",
+                 "chomp_halo_kernels.h", "chomp_mass_kernels.h", "chomp_romberg.h",
+                 "chomp_math.h", "special_tables.h", "chomp_mi355x.h"):
+        assert need in base, need
+    # the getters run on the host: the constants of the headers
+    with open(os.path.join(_lib.CSRC, "chomp_proj_kernels.h")) as f:
+        n_tab = int(re.search(r"constexpr int kPTabN = (\d+);", f.read()).group(1))
+    with open(os.path.join(_lib.CSRC, "chomp_power_kernels.h")) as f:
+        m = re.search(r"kWaveIdxMask = (\w+), kWaveSlow = 1 << (\d+), kWaveTwo = 1 << (\d+);", f.read())
+    assert L.dw_ptab_n() == n_tab == 8192
+    bits = (ctypes.c_int * 3)()
+    L.dw_wave_bits(bits)
+    assert list(bits) == [int(m.group(1), 0), 1 << int(m.group(2)), 1 << int(m.group(3))]
+    P = devcheck_build.HARNESSES["devphys"]
+    Lp = ctypes.CDLL(P.so)
+    assert L.dw_sizeof_epoch() == Lp.dp_sizeof_epoch() and L.dw_sizeof_epoch() % 16 == 0
+    assert L.dw_epoch_inputs() == Lp.dp_epoch_inputs() + 12
+    lay = (ctypes.c_int * 14)()
+    assert L.dw_layout(7, lay) == -1 and L.dw_layout(65, lay) == -1      # (k_power_extrap reads knots NK - 7 ..)
+    for NK in (8, 11, 64):
+        assert L.dw_layout(NK, lay) == 0
+        v = list(lay)
+        # make_layout(NM, NK): six knot tables of NK, then six coefficient tables of 4 (NK - 1),
+        # the levels (6 NK), HaloFit's ln sigma^2 (NK), misc (8); the stride a multiple of 8
+        assert [b - a for a, b in zip(v[0:5], v[1:6])] == [NK] * 5 and v[6] == v[5] + NK
+        assert [b - a for a, b in zip(v[6:11], v[7:12])] == [4 * (NK - 1)] * 5
+        assert v[12] == v[11] + 4 * (NK - 1) + 7 * NK
+        assert v[13] % 8 == 0 and 0 <= v[13] - (v[12] + 8) < 8
+
+
 def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
     """Each harness's hash covers the product headers it includes, transitively: devphys.hip
     and devproj.hip reach chomp_math.h through chomp_cov_kernels.h, and a change in any header of
@@ -136,6 +202,7 @@ def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
     os.makedirs(root / "tests" / "devcheck")
     for H in devcheck_build.HARNESSES.values():
         shutil.copy(H.src, root / "tests" / "devcheck")
+    shutil.copy(os.path.join(devcheck_build.DIR, "epoch_fill.h"), root / "tests" / "devcheck")
     copies = {n: devcheck_build.Harness(n) for n in devcheck_build.HARNESSES}
     for H in copies.values():
         H.src = str(root / "tests" / "devcheck" / (H.name + ".hip"))
@@ -151,9 +218,17 @@ def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
     last = {n: devcheck_build.source_hash(n) for n in copies}
     assert last["devphys"] != after["devphys"] and last["devcheck"] != after["devcheck"]
     assert last["devproj"] != after["devproj"]
+    assert after["devpower"] != before["devpower"] and last["devpower"] != after["devpower"]
     # a harness's own source changes its hash alone
     with open(copies["devproj"].src, "a") as f:
         f.write("// changed\n")
     own = {n: devcheck_build.source_hash(n) for n in copies}
     assert own["devproj"] != last["devproj"]
     assert own["devphys"] == last["devphys"] and own["devcheck"] == last["devcheck"]
+    assert own["devpower"] == last["devpower"]
+    # the shared epoch filler changes the two harnesses that include it, and only them
+    with open(root / "tests" / "devcheck" / "epoch_fill.h", "a") as f:
+        f.write("// changed\n")
+    fill = {n: devcheck_build.source_hash(n) for n in copies}
+    assert fill["devpower"] != own["devpower"] and fill["devphys"] != own["devphys"]
+    assert fill["devproj"] == own["devproj"] and fill["devcheck"] == own["devcheck"]
