@@ -324,6 +324,67 @@ __device__ __forceinline__ void sigma8_from_parts(const chomp_config& cfg, const
   if (threadIdx.x == 0) n[kSigmaOffI8] = i8;
 }
 
+// One ln S integral of the aiming table by a block of 256 threads in ONE round: the whole level-L
+// Romberg grid (L <= kLnsLevel = 10: 1024 intervals, thread t holds the points t + 256 r,
+// r = 0..3 -- four independent evaluations issued back to back -- and the last thread the upper
+// end point), the per-level sums, and the last Romberg row from them: the construction of
+// sigma8_from_parts.  An adaptive walk to the same cap is a first round to level 7 and up to
+// three more dependent levels, each a barrier and an LDS hand-over; its 1e-5 stopping rule
+// bought nothing the table needs (the value only aims the search), so the row returned is
+// simply row L, at least as accurate as any earlier one the rule would have stopped at.
+// The points of thread t != 0 differ by multiples of 256, so all four lie on one level,
+// L - ctz(t): a lane sums its four values, and a wavefront's lanes 1..63 hold six levels
+// (ctz 0..5): six masked wave sums.  Lane 0 of a wavefront (t a multiple of 64) adds its points
+// to their levels one by one.  Whole block; one barrier.
+constexpr int kLnsLevel = 10;
+template <class F>
+__device__ __forceinline__ double lns_one_pass(const F& f, double a, double b, int L) {
+  static_assert(kLnsLevel == 10, "four points per thread of 256");
+  __shared__ double lsum[4][kLnsLevel + 1];     // per wavefront: sums of levels 1..L
+  __shared__ double ends[2];                    // f(a), f(b)
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int N = 1 << L;
+  const double range = b - a;
+  const double crow = CHOMP_ROMBERG_C[L][lane & 31];   // (in flight behind the nodes)
+  double v[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int p = (int)threadIdx.x + 256 * r;
+    v[r] = p < N ? f(a + ldexp(range * (double)p, -L)) : 0.0;
+  }
+  if (threadIdx.x == 255) ends[1] = f(b);
+  if (threadIdx.x == 0) {
+    ends[0] = v[0];
+    v[0] = 0.0;                                 // (an end point, not an interior node)
+  }
+  if (lane <= kLnsLevel) lsum[wv][lane] = 0.0;  // (same wavefront as the writes below: in order)
+  const double mine = (v[0] + v[1]) + (v[2] + v[3]);
+  const int tz = lane == 0 ? -1 : __builtin_ctz((unsigned)lane);
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const double s = wave_sum(tz == c ? mine : 0.0);
+    if (lane == 0 && L - c >= 1) lsum[wv][L - c] = s;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int p = (int)threadIdx.x + 256 * r;
+      if (p > 0 && p < N) lsum[wv][L - __builtin_ctz((unsigned)p)] += v[r];
+    }
+  }
+  __syncthreads();
+  // lane m <= L of every wavefront: the trapezoid estimate T_m from the level sums; row L is
+  // sum_m C[L][m] T_m (one multiply and one butterfly)
+  double T = 0.0;
+  if (lane <= L) {
+    double ordsum = 0.5 * (ends[0] + ends[1]);
+    for (int l = 1; l <= lane; ++l)
+      ordsum += ((lsum[0][l] + lsum[1][l]) + lsum[2][l]) + lsum[3][l];
+    T = ldexp(range * ordsum, -lane);
+  }
+  return wave_sum32(crow * T);
+}
+
 // NPT: table nodes per thread.  1: most blocks, shortest launch (a (k, z) grid has ONE cosmology
 // and the launch is a link of its latency chain).  4: a batch of many cosmologies (a design, an
 // MCMC population) -- a quarter of the blocks, each paying the serial head (the transfer-function
@@ -429,16 +490,15 @@ __global__ __launch_bounds__(256) void k_sigma_nodes(chomp_config cfg,
     return;
   }
   if ((int)blockIdx.x >= nb) {
-    // ln S point (the ln S points only aim the search: 1e-5 and at most 2^10 panels are plenty
-    // -- only R > 100 Mpc/h would go on to 2^11, where the cap costs ~1e-4 of an estimate that
+    // ln S point (the ln S points only aim the search: 2^10 panels are plenty -- only
+    // R > 100 Mpc/h would go on to 2^11 at 1e-5, where the cap costs ~1e-4 of an estimate that
     // the probes certify anyway)
     const int i = (int)blockIdx.x - nb;
     const double R = exp(make_sgrid(cfg.k_min, cfg.k_max).ln_r(i));
     double lo, hi;
     sigma_limits(E, R, &lo, &hi);
     SigmaIntegrandT<BAO> f{&E, R};              // sigma_norm = 1: amp * integral
-    const double s2 = romberg1<4>(f, lo, hi, cfg.global_precision, 1e-5,
-                                  cfg.divmax < 10 ? cfg.divmax : 10, red);
+    const double s2 = lns_one_pass(f, lo, hi, cfg.divmax < kLnsLevel ? cfg.divmax : kLnsLevel);
     if (threadIdx.x == 0) n[kSigmaOffLnS + i] = log(s2);
     return;
   }
@@ -927,22 +987,63 @@ __device__ __forceinline__ double ln_s_estimate(const SGrid& G, const double* ln
 
 // Where the estimate says the walk of `side` stops: dir (0: the starting mass already
 // passes), and the first index j of the candidate table whose estimate passes.  ok = false
-// when the estimate cannot be trusted to within one candidate.  The whole block calls it
-// (every candidate is tried at once); sh: one int of LDS.
+// when the estimate cannot be trusted to within one candidate.  The whole block calls it with
+// block-uniform arguments; sh: one int of LDS (the search below).
+//
+// The index is the root of a smooth monotone function on a 48-point table, so it is first
+// SOLVED for (INVERSE: crossing_index, every thread the same few estimates, no barrier) and the
+// integer checked with the walk's own predicate: passes(j) and not passes(j - 1) -- candidate 0
+// fails by the margin.  The predicate is monotone, so a j that checks is the j the search finds.
+// Where it does not check (a kink between two segments, a walk that leaves the table, NaN) the
+// two-round SEARCH over all candidates decides as before (searched = true).
 struct SidePlan {
   bool ok;
   int dir, j;
   double nu_start;              // estimate at the starting mass
   bool at_edge;                 // the starting mass sits on a band edge: dir is a guess, the
                                 // probes are candidates 0..3 (j = 2) and 0 decides exactly
+  bool searched;                // the two-round search ran
 };
+
+// Real-valued index at which ln S(x0 + dir j step) crosses `target`, by inverse interpolation:
+// the table interval that brackets the target (a point per lane; of several, the first along the
+// walk), the chord across it, one more chord of the bracket after an estimate there and a secant
+// step through the two estimates.  On a 0.35-wide interval of ln S (|S''/S'| ~ 0.15) the three
+// guesses are off by ~5e-3, ~2e-4 and ~2e-7 of ln R against a candidate spacing of 1.6e-2.
+// NaN where no interval brackets it.  Wave-level only: any block shape.
+__device__ __forceinline__ double crossing_index(const SGrid& G, const double* lns, double x0,
+                                                 int dir, double step, double target) {
+  if (!G.valid) return NAN;
+  const int lane = threadIdx.x & 63;
+  bool brackets = false;
+  if (lane < kSGrid - 1 && lane != 7 && lane != 21 && lane != 39) {   // (not across a kink)
+    // ln S falls with R; the interval must lie (partly) on the walk's side of the start
+    const double xl = G.ln_r(lane), xr = G.ln_r(lane + 1);
+    brackets = lns[lane] >= target && lns[lane + 1] < target && (dir < 0 ? xl < x0 : xr > x0);
+  }
+  const unsigned long long m = __ballot(brackets);
+  if (m == 0ull) return NAN;
+  const int ib = dir < 0 ? 63 - __builtin_clzll(m) : __builtin_ctzll(m);
+  double xa = G.ln_r(ib), xb = G.ln_r(ib + 1);
+  double ga = lns[ib] - target, gb = lns[ib + 1] - target;           // ga >= 0 > gb
+  const double x1 = xa + (xb - xa) * (ga / (ga - gb));
+  const double g1 = ln_s_estimate(G, lns, x1) - target;
+  if (g1 >= 0.0) { xa = x1; ga = g1; } else { xb = x1; gb = g1; }
+  const double x2 = xa + (xb - xa) * (ga / (ga - gb));
+  const double g2 = ln_s_estimate(G, lns, x2) - target;
+  double x3 = x2;
+  if (g2 != g1) x3 = x2 - g2 * ((x2 - x1) / (g2 - g1));
+  return (x3 - x0) / ((double)dir * step);
+}
+
+template <bool INVERSE = true>
 __device__ __forceinline__ SidePlan plan_side(const Epoch& E, const double* lns, int side,
                                               const double* cand, int* sh) {
   const SideThresholds T = side_thresholds(side, cand);
   const SGrid G = make_sgrid(E.k_min, E.k_max);
   const double margin = 1e-2;             // estimate error ~1e-4; candidates are >= 0.4 % apart
   const double ln_margin = 0.00995033085; // ln(1 + margin)
-  SidePlan P{false, 0, 0, 0.0, false};
+  SidePlan P{false, 0, 0, 0.0, false, false};
   // ln nu = ln_nu_c - ln S(ln R); the candidates are M_0 * 1.05^(-+j), so ln R moves by
   // ln(1.05) / 3 per step (to the estimate's accuracy).  The four logarithms this needs are
   // one call with a different argument in each of four lanes.
@@ -973,12 +1074,29 @@ __device__ __forceinline__ SidePlan plan_side(const Epoch& E, const double* lns,
   const double ln_thr = P.dir < 0 ? ln_hi : ln_lo;
   // nu is monotone along the table, so the first passing index is the minimum over the
   // passing ones; a candidate outside the ln S table counts as passing, and is rejected
-  // below if it turns out to be the first.  Two rounds: every (kSearchJ / 256)-th candidate,
-  // then the candidates between the last failing and the first passing one of those.
+  // below if it turns out to be the first.
   auto passes = [&](int j) {
     const double ln_nu = ln_nu_c - ln_s_estimate(G, lns, x0 + (double)(P.dir * j) * step);
     return !(ln_nu == ln_nu) || (P.dir < 0 ? !(ln_thr < ln_nu) : !(ln_thr > ln_nu));
   };
+  if constexpr (INVERSE) {
+    // ln nu = ln_thr where ln S = ln_nu_c - ln_thr; the first integer on the passing side
+    const double jr = ceil(crossing_index(G, lns, x0, P.dir, step, ln_nu_c - ln_thr));
+    if (jr >= 1.0 && jr <= (double)(kSearchJ - 1)) {      // (false for NaN)
+      const int j = (int)jr;
+      const double lsj = ln_s_estimate(G, lns, x0 + (double)(P.dir * j) * step);
+      const double ln_nu = ln_nu_c - lsj;
+      const bool pass_j = lsj == lsj && (P.dir < 0 ? !(ln_thr < ln_nu) : !(ln_thr > ln_nu));
+      if (pass_j && (j == 1 || !passes(j - 1))) {
+        P.j = j;
+        P.ok = true;
+        return P;
+      }
+    }
+  }
+  // Two rounds: every (kSearchJ / 256)-th candidate, then the candidates between the last
+  // failing and the first passing one of those.
+  P.searched = true;
   constexpr int kStride = kSearchJ / 256;
   __syncthreads();
   if (threadIdx.x == 0) *sh = kSearchJ;
