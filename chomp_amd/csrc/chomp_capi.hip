@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/chomp_mi355x.h"
+#include "chomp_buffers.h"
 #include "chomp_power_kernels.h"
 #include "chomp_proj_kernels.h"
 #include "chomp_cov_kernels.h"
@@ -31,29 +32,6 @@
 #include "chomp_profile_kernels.h"
 
 using namespace chomp;
-
-// A parameter block of the epoch batch on its way to the device: the host shadow says what
-// the device holds (an unchanged block is not uploaded again -- MCMC-style loops re-run the
-// set-up with mostly identical inputs); a changed block goes through one of two pinned
-// staging buffers, each guarded by an event, so the copy is a true asynchronous DMA and the
-// host never drains the stream (SimulationDesign / MCMC loops change a block on every call).
-struct StagedBlock {
-  std::vector<char> shadow;
-  void* pin[2] = {nullptr, nullptr};
-  hipEvent_t done[2] = {nullptr, nullptr};
-  bool used[2] = {false, false};
-  size_t cap = 0;
-  int turn = 0;
-  void reset() { shadow.clear(); }
-  void release() {
-    for (int i = 0; i < 2; ++i) {
-      if (pin[i]) (void)hipHostFree(pin[i]);
-      if (done[i]) (void)hipEventDestroy(done[i]);
-      pin[i] = nullptr; done[i] = nullptr; used[i] = false;
-    }
-    cap = 0;
-  }
-};
 
 // roctx ranges around the stages (chomp_set_tuning CHOMP_TUNE_ROCTX; rocprofv3 --marker-trace):
 // the marker library is looked up at run time, so nothing links against a profiler.
@@ -78,11 +56,9 @@ struct RoctxApi {
 // distinct (w0, wa), in the order `keys` lists them, valid while the keys stay the same.
 struct DeTables {
   std::vector<DePar> keys;
-  double* d_tab = nullptr;
-  DePar* d_par = nullptr;
-  size_t cap_tab = 0, cap_par = 0;
+  DeviceBuffer<double> d_tab;
+  StagedBuffer<DePar> d_par;
   bool valid = false;
-  StagedBlock sh_par;
 };
 
 struct chomp_ctx {
@@ -94,34 +70,39 @@ struct chomp_ctx {
   TabLayout L;
   std::string err;
 
+  // Buffers a captured HIP graph may still reference are never freed before the context
+  // is destroyed (mem.graph_seen: a call of this context has been captured at least once).
+  BufferHome mem;
+
   // constant tables
-  SiCiTab* d_sici = nullptr;
-  BesselTab* d_j0 = nullptr;
-  BesselTab* d_j2 = nullptr;
-  TinkerTab* d_tinker = nullptr;
-  double* d_gl16 = nullptr;
-  double* d_cand = nullptr;
+  DeviceBuffer<SiCiTab> d_sici;
+  DeviceBuffer<BesselTab> d_j0;
+  DeviceBuffer<BesselTab> d_j2;
+  DeviceBuffer<TinkerTab> d_tinker;
+  DeviceBuffer<double> d_gl16;
+  DeviceBuffer<double> d_cand;
 
   // epoch batch
   size_t n_epoch = 0, cap_epoch = 0;
-  chomp_cosmo* d_cosmo = nullptr;
-  double* d_z = nullptr;
-  Epoch* d_epochs = nullptr;
-  double* d_search = nullptr;
-  double* d_probe = nullptr;       // k_epoch_init: certifying probes of the mass-limit search
-  int* d_count = nullptr;          // k_epoch_init: arrivals per epoch (reset by the kernel)
-  int* d_pending = nullptr;        // work list of k_halo_knots_deep (cleared by k_halo_finalize)
-  double* d_tab = nullptr;
-  chomp_halo_par* d_mass_par = nullptr;
-  chomp_halo_par* d_profile = nullptr;
-  HodDev* d_hod = nullptr;
-  double* d_nodes = nullptr;       // node tables of the halo integrals
-  double* d_snodes = nullptr;      // node tables of the sigma(R) integrals (per cosmology slot)
-  int* d_slot = nullptr;           // epoch -> cosmology slot
-  int* d_first = nullptr;          // slot -> an epoch with that cosmology
-  unsigned* d_status = nullptr;    // per-epoch status word (chomp_get_status)
-  double* d_endp = nullptr;        // integrand pairs of the knots at the upper end point
-  int* d_npend = nullptr;          // per epoch: listed knots + 1 token (k_halo_knots_fast)
+  // (the parameter blocks travel with their shadows: see upload)
+  StagedBuffer<chomp_cosmo> d_cosmo;
+  StagedBuffer<double> d_z;
+  DeviceBuffer<Epoch> d_epochs;
+  DeviceBuffer<double> d_search;
+  DeviceBuffer<double> d_probe;    // k_epoch_init: certifying probes of the mass-limit search
+  DeviceBuffer<int> d_count;       // k_epoch_init: arrivals per epoch (reset by the kernel)
+  DeviceBuffer<int> d_pending;     // work list of k_halo_knots_deep (cleared by k_halo_finalize)
+  DeviceBuffer<double> d_tab;
+  StagedBuffer<chomp_halo_par> d_mass_par;
+  StagedBuffer<chomp_halo_par> d_profile;
+  StagedBuffer<HodDev> d_hod;
+  DeviceBuffer<double> d_nodes;    // node tables of the halo integrals
+  DeviceBuffer<double> d_snodes;   // node tables of the sigma(R) integrals (per cosmology slot)
+  StagedBuffer<int> d_slot;        // epoch -> cosmology slot
+  StagedBuffer<int> d_first;       // slot -> an epoch with that cosmology
+  DeviceBuffer<unsigned> d_status; // per-epoch status word (chomp_get_status)
+  DeviceBuffer<double> d_endp;     // integrand pairs of the knots at the upper end point
+  DeviceBuffer<int> d_npend;       // per epoch: listed knots + 1 token (k_halo_knots_fast)
   long long tune[CHOMP_TUNE_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // chomp_set_tuning
   bool have_epochs = false, have_mass = false, have_halo = false;
   unsigned fam_mask = 0;          // families (F_* bits) with valid splines in every epoch (set-ups)
@@ -129,48 +110,34 @@ struct chomp_ctx {
   // HaloSuperSampleCovariance._delta_b per epoch (chomp_set_delta_b), read by CHOMP_P_MM_SSC.
   // chomp_epochs_set only raises delta_b_zero: the buffer is cleared when something next needs
   // it, so that a batch that never asks for the super-sample codes queues nothing for them.
-  double* d_delta_b = nullptr;
-  size_t cap_delta_b = 0;
+  DeviceBuffer<double> d_delta_b;
   StagedBlock sh_delta_b;
   bool delta_b_zero = true;
   std::vector<char> have_halofit;
-  StagedBlock sh_cosmo, sh_z, sh_mass, sh_profile, sh_hod, sh_slot, sh_first;
   StagedBlock sh_proj, sh_pp[2];   // projection scalars, tabulated redshift distributions
-  StagedBlock sh_sets;             // the ProjDev blocks of chomp_kernel_setup_sets
   // pinned host mirrors of the staging buffers of host-pointer calls (chomp_power)
-  unsigned* h_status = nullptr;    // chomp_status_post: pinned copy of d_status ...
-  size_t cap_hstatus = 0, n_hstatus = 0;
+  PinnedBuffer<unsigned> h_status; // chomp_status_post: pinned copy of d_status ...
+  size_t n_hstatus = 0;
   hipEvent_t ev_status = nullptr;  // ... complete when this event is
-  double* h_stage_in = nullptr;
-  double* h_stage_out = nullptr;
-  size_t cap_hin = 0, cap_hout = 0;
-  // Buffers a captured HIP graph may still reference are never freed before the context
-  // is destroyed (graph_seen: a call of this context has been captured at least once).
-  bool graph_seen = false;
-  std::vector<void*> graveyard;
-  std::vector<void*> host_graveyard;   // (pinned words a graph's kernels or copies may write)
+  PinnedBuffer<double> h_stage_in;
+  PinnedBuffer<double> h_stage_out;
 
   // staging for host-pointer calls
-  double* d_stage_in = nullptr;
-  double* d_kcache = nullptr;      // device copy of the last host k grid of chomp_power
-  const double* kcache_ptr = nullptr;   // (== d_kcache while kcache_shadow describes its contents)
-  size_t cap_kcache = 0;
-  std::vector<double> kcache_shadow;
-  double* d_stage_out = nullptr;
-  int* d_slow = nullptr;           // Stage E: 2 counters + list of k groups for the per-lane pass
-  int* d_winfo = nullptr;          // Stage E: per k group knot interval / flags (k_power_prep)
-  double* d_ktab = nullptr;        // Stage E: per-k (offset, shape) table (k_power_prep)
-  double* d_wnodes = nullptr;      // w(theta): theta-independent integrand factor on the Romberg nodes
-  double* d_cnodes = nullptr;      // C_l: chi-only factors on the Romberg nodes
-  size_t cap_cnodes = 0;
-  double* d_samples = nullptr;     // coarse samples of the listed knots, a slot each (k_halo_knots_samples -> _fast)
-  double* d_psum = nullptr;        // ... and their per-level sums
-  size_t cap_samples = 0, cap_psum = 0, cap_plan = 0;
-  char* d_plan = nullptr;          // per (epoch, group): the break-point plan (DeepPlan; k_halo_knots -> _fast)
-  double* d_deepw = nullptr;       // k_halo_knots_fast: level weights (deep_weights_host)
-  double* d_hf_ainv = nullptr;     // k_halofit_finalize: inverse collocation matrix of the ln R grid
-  int* d_deepstat = nullptr;       // k_halo_knots_fast: knots done by the fast / literal path
-  size_t cap_slow = 0, cap_winfo = 0, cap_ktab = 0, cap_wnodes = 0;
+  DeviceBuffer<double> d_stage_in;
+  DeviceBuffer<double> d_kcache;   // device copy of the last host k grid of chomp_power
+  std::vector<double> kcache_shadow;   // ... which is this one (empty: the buffer holds none)
+  DeviceBuffer<double> d_stage_out;
+  DeviceBuffer<int> d_slow;        // Stage E: 2 counters + list of k groups for the per-lane pass
+  DeviceBuffer<int> d_winfo;       // Stage E: per k group knot interval / flags (k_power_prep)
+  DeviceBuffer<double> d_ktab;     // Stage E: per-k (offset, shape) table (k_power_prep)
+  DeviceBuffer<double> d_wnodes;   // w(theta): theta-independent integrand factor on the Romberg nodes
+  DeviceBuffer<double> d_cnodes;   // C_l: chi-only factors on the Romberg nodes
+  DeviceBuffer<double> d_samples;  // coarse samples of the listed knots, a slot each (k_halo_knots_samples -> _fast)
+  DeviceBuffer<double> d_psum;     // ... and their per-level sums
+  DeviceBuffer<DeepPlan> d_plan;   // per (epoch, group): the break-point plan (k_halo_knots -> _fast)
+  DeviceBuffer<double> d_deepw;    // k_halo_knots_fast: level weights (deep_weights_host)
+  DeviceBuffer<double> d_hf_ainv;  // k_halofit_finalize: inverse collocation matrix of the ln R grid
+  DeviceBuffer<int> d_deepstat;    // k_halo_knots_fast: knots done by the fast / literal path
   // chomp_power_plan: the k-only table of a registered k grid, kept across chomp_power calls
   struct PowerPlan {
     bool valid = false;
@@ -189,41 +156,33 @@ struct chomp_ctx {
   // w0-wa dark energy (chomp_set_dark_energy): the switch, the knots (ln a_i, then z_i; host-made,
   // sent once), the epochs' and the projection's tables, and per epoch its table (-1: none)
   int dark_energy = 0;
-  double* d_de_knots = nullptr;
-  size_t cap_de_knots = 0;
-  StagedBlock sh_de_knots;
+  StagedBuffer<double> d_de_knots;
   DeTables de_ep, de_proj;
   std::vector<int> de_slot;
-  int* d_de_slot = nullptr;
-  size_t cap_de_slot = 0;
-  StagedBlock sh_de_slot;
+  StagedBuffer<int> d_de_slot;
   // MassFunctionSecondOrder (chomp_set_second_order): the switch, and per epoch the sigma knots,
   // the sigma(nu) spline and bias_2_norm (B2Layout); have_b2: the last mass set-up made them
   int second_order = 0;
   bool have_b2 = false;
   B2Layout B2;
-  double* d_b2 = nullptr;
-  size_t cap_b2 = 0;
+  DeviceBuffer<double> d_b2;
   // HaloTrispectrumOneHalo (chomp_tri1h_setup): per epoch the I_0^4 table, its levels and its
   // bicubic (TriLayout); tri_built: the epoch has one since chomp_epochs_set
   TriLayout T3;
-  double* d_tri = nullptr;
-  size_t cap_tri = 0;
+  DeviceBuffer<double> d_tri;
   std::vector<char> tri_built;
   int tri_moment = -1;             // the moment of the I_0^4 tables in d_tri (the last chomp_tri1h_setup)
   // HaloTrispectrum (chomp_tri_setup): per epoch the I_1^2, I_1^3, I_2^2 and I_2^1 tables with
   // their levels and splines (TriTabLayout); tri4_built as tri_built
   TriTabLayout Q4;
-  double* d_tri4 = nullptr;
-  size_t cap_tri4 = 0;
+  DeviceBuffer<double> d_tri4;
   std::vector<char> tri4_built;
   // General-slope halo profiles (chomp_set_general_profile): the switch, per epoch the y(k, M)
   // table with its levels and splines (ProfLayout), and which epochs of the last halo set-up have
   // one (prof_general: alpha != -1 in a set-up that took the general path)
   int general_profile = 0;
   ProfLayout PL;
-  double* d_prof = nullptr;
-  size_t cap_prof = 0;
+  DeviceBuffer<double> d_prof;
   std::vector<char> prof_general;
   bool prof_built = false;         // ... and that set-up built knot tables (some family asked for)
   int timing = 0;                  // chomp_set_timing: HIP events around the Stage E launches
@@ -231,7 +190,6 @@ struct chomp_ctx {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<int> slot;           // host copy: epoch -> cosmology slot
   size_t n_slots = 1;              // distinct cosmologies of the batch
-  size_t cap_in = 0, cap_out = 0;
 
   // projection
   ProjState proj;
@@ -239,9 +197,7 @@ struct chomp_ctx {
   CrossState cross;             // Covariance(corr_a, corr_b): the two sides' snapshots and the four tables
   FourierState fourier;         // CovarianceFourier: the four pairs' scalars, Limber tables and splines
   BlocksState blocks;           // chomp_covariance_blocks: one table slab per block of a CovarianceMulti
-  StagedBlock sh_blocks;        // ... and its index block
   SscBlocksState ssc_blocks;    // chomp_covariance_ssc_blocks: one kernel_ssc slab per block
-  StagedBlock sh_ssc_blocks;    // ... and its index block
   std::vector<double> sets_z_min, sets_z_max;   // per set of `sets`: the redshifts its two windows share
   // The side stream.  The projection set-up (chomp_kernel_setup / chomp_multi_epoch_setup:
   // a chain of six small launches) depends on nothing the halo set-up produces, and C_l on
@@ -259,7 +215,7 @@ struct chomp_ctx {
   bool status_mirrored = false;    // the last set-up ended with a halo set-up: its finalising blocks
                                    // wrote the status words to the pinned host words themselves
   // (see ensure_hstatus / mirror_next / chomp_status_post)
-  unsigned long long* h_mirror = nullptr;
+  PinnedBuffer<unsigned long long> h_mirror;
   unsigned setup_seq = 0, posted_seq = 0;
   int mirror_half = 0, mirror_region = 0, posted_half = 0;
   int posted_kind = 0;             // 0 none, 1 the mirror, 2 the copy, 3 collected into posted_saved
@@ -293,17 +249,11 @@ int fail(chomp_ctx* c, int code, const std::string& msg) {
 
 bool capturing(chomp_ctx* ctx) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  ctx->mem.capture = false;
   if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess) return false;
-  if (st == hipStreamCaptureStatusActive) ctx->graph_seen = true;
-  return st == hipStreamCaptureStatusActive;
-}
-
-// Free a device buffer, unless a captured graph may still hold its address.
-int release_device(chomp_ctx* ctx, void* p) {
-  if (!p) return CHOMP_OK;
-  if (ctx->graph_seen) { ctx->graveyard.push_back(p); return CHOMP_OK; }
-  HIPCHK(hipFree(p));
-  return CHOMP_OK;
+  ctx->mem.capture = st == hipStreamCaptureStatusActive;
+  if (ctx->mem.capture) ctx->mem.graph_seen = true;
+  return ctx->mem.capture;
 }
 
 // Upload `bytes` from `src` to `dst` unless the shadow says the device already holds
@@ -340,6 +290,10 @@ int upload(chomp_ctx* ctx, void* dst, const void* src, size_t bytes, StagedBlock
   b.turn = t ^ 1;
   b.shadow.assign(static_cast<const char*>(src), static_cast<const char*>(src) + bytes);
   return CHOMP_OK;
+}
+template <class T>
+int upload(chomp_ctx* ctx, StagedBuffer<T>& b, const void* src, size_t bytes) {
+  return upload(ctx, b.dev.get(), src, bytes, b.sh);
 }
 
 // -- the side stream ------------------------------------------------------------------
@@ -407,18 +361,28 @@ int proj_join(chomp_ctx* ctx) {
   return CHOMP_OK;
 }
 
-template <class T>
-int ensure(chomp_ctx* ctx, T** p, size_t* cap, size_t n) {
-  if (n <= *cap && *p) return CHOMP_OK;
-  if (capturing(ctx))
+// What a growth of one of the context's buffers came to, as a return code.
+int grown(chomp_ctx* ctx, BufferGrowth g) {
+  if (g == BufferGrowth::refused)
     return fail(ctx, CHOMP_ERR_STATE,
                 "a work buffer would have to grow while the context's stream is being captured: "
                 "run the call once at this size before capturing");
-  if (*p) { const int rc = release_device(ctx, *p); if (rc) return rc; }
-  *p = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  *cap = n;
+  if (g == BufferGrowth::failed)
+    return fail(ctx, CHOMP_ERR_HIP, std::string("a buffer of the context: ") +
+                                        hipGetErrorString((hipError_t)ctx->mem.error));
   return CHOMP_OK;
+}
+
+// Room for n elements in `b` (a DeviceBuffer, PinnedBuffer or StagedBuffer); contents are not
+// kept.  *moved: the block is a new one, and holds nothing.
+template <class B>
+int ensure(chomp_ctx* ctx, B& b, size_t n, bool* moved = nullptr) {
+  if (moved) *moved = false;
+  if (b.fits(n)) return CHOMP_OK;
+  (void)capturing(ctx);
+  const BufferGrowth g = b.ensure(ctx->mem, n);
+  if (moved) *moved = g == BufferGrowth::moved;
+  return grown(ctx, g);
 }
 
 // Before a launch with more than 64 KiB of dynamic LDS: opt `kernel` in to `bytes`, once per
@@ -430,16 +394,6 @@ int lds_opt_in(chomp_ctx* ctx, Kernel* kernel, int bytes) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   have = bytes;
-  return CHOMP_OK;
-}
-
-// Pinned host mirror of a staging buffer (host-pointer calls).
-int ensure_host(chomp_ctx* ctx, double** p, size_t* cap, size_t n) {
-  if (n <= *cap && *p) return CHOMP_OK;
-  if (*p) HIPCHK(hipHostFree(*p));
-  *p = nullptr;
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(p), n * sizeof(double), hipHostMallocDefault));
-  *cap = n;
   return CHOMP_OK;
 }
 
@@ -487,8 +441,8 @@ struct Staging {
   int place(size_t n_scratch = 0) {
     if (rc) return rc;             // (an unknown mem never takes either path)
     const size_t off_scratch = take(&n_in, n_scratch);
-    if (n_in) { const int e = ensure(ctx, &ctx->d_stage_in, &ctx->cap_in, n_in); if (e) return e; }
-    if (n_out) { const int e = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, n_out); if (e) return e; }
+    if (n_in) { const int e = ensure(ctx, ctx->d_stage_in, n_in); if (e) return e; }
+    if (n_out) { const int e = ensure(ctx, ctx->d_stage_out, n_out); if (e) return e; }
     for (const Seg<const double>& s : ins) {
       *s.dev = ctx->d_stage_in + s.off;
       HIPCHK(hipMemcpyAsync(ctx->d_stage_in + s.off, s.host, s.n * sizeof(double),
@@ -536,18 +490,27 @@ double erfinv_host(double y) {
   return x;
 }
 
+// A constant table: allocated once, n elements, and filled from `src`.
+template <class T>
+int constant(chomp_ctx* ctx, DeviceBuffer<T>& b, const T* src, size_t n) {
+  HIPCHK((hipError_t)b.once(n));
+  HIPCHK(hipMemcpy(b, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return CHOMP_OK;
+}
+
 int setup_constants(chomp_ctx* ctx) {
   SiCiTab s;
   BesselTab j0, j2;
   fill_tables(&s, &j0, &j2);
-  HIPCHK(hipMalloc(&ctx->d_sici, sizeof(SiCiTab)));
-  HIPCHK(hipMalloc(&ctx->d_j0, sizeof(BesselTab)));
-  HIPCHK(hipMalloc(&ctx->d_j2, sizeof(BesselTab)));
-  HIPCHK(hipMemcpy(ctx->d_sici, &s, sizeof(s), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_j0, &j0, sizeof(j0), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_j2, &j2, sizeof(j2), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&ctx->d_gl16, 32 * sizeof(double)));
-  HIPCHK(hipMemcpy(ctx->d_gl16, CHOMP_GL16, 32 * sizeof(double), hipMemcpyHostToDevice));
+  // (the three blocks first, then their contents: the order the context has always made them in)
+  HIPCHK((hipError_t)ctx->d_sici.once(1));
+  HIPCHK((hipError_t)ctx->d_j0.once(1));
+  HIPCHK((hipError_t)ctx->d_j2.once(1));
+  int rc = constant(ctx, ctx->d_sici, &s, 1);
+  if (!rc) rc = constant(ctx, ctx->d_j0, &j0, 1);
+  if (!rc) rc = constant(ctx, ctx->d_j2, &j2, 1);
+  if (!rc) rc = constant(ctx, ctx->d_gl16, CHOMP_GL16, 32);
+  if (rc) return rc;
   // Tinker et al. 2010 parameter table (mass_function.py:450-459), splined in
   // ln(Delta) exactly as the reference does (:461-470).
   static const double delta[9] = {200, 300, 400, 600, 800, 1200, 1600, 2400, 3200};
@@ -561,8 +524,8 @@ int setup_constants(chomp_ctx* ctx) {
   double work[18];
   for (int i = 0; i < 9; ++i) tt.x[i] = std::log(delta[i]);
   for (int q = 0; q < 5; ++q) spline_build(tt.x, par[q], 9, tt.c[q], work);
-  HIPCHK(hipMalloc(&ctx->d_tinker, sizeof(TinkerTab)));
-  HIPCHK(hipMemcpy(ctx->d_tinker, &tt, sizeof(tt), hipMemcpyHostToDevice));
+  rc = constant(ctx, ctx->d_tinker, &tt, 1);
+  if (rc) return rc;
   // Candidate masses of the 5 % walk (mass_function.py:161-193), generated by the
   // same repeated multiply/divide so every candidate is bit-identical to the value
   // the reference's loop would hold after j steps.
@@ -580,22 +543,19 @@ int setup_constants(chomp_ctx* ctx) {
     const int top = ctx->cfg.divmax;
     std::vector<double> w((size_t)(top > kDeepCoarse ? top - kDeepCoarse : 1) * kDeepWStride, 0.0);
     if (top > kDeepCoarse) deep_weights_host(kDeepCoarse, top, w.data());
-    HIPCHK(hipMalloc(&ctx->d_deepw, w.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(ctx->d_deepw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&ctx->d_deepstat, 8 * sizeof(int)));
+    rc = constant(ctx, ctx->d_deepw, w.data(), w.size());
+    if (rc) return rc;
+    HIPCHK((hipError_t)ctx->d_deepstat.once(8));
     HIPCHK(hipMemset(ctx->d_deepstat, 0, 8 * sizeof(int)));
   }
   if (ctx->cfg.halo_npoints >= 12) {   // (fewer points: the serial quintic solve of k_halofit_finalize)
     const int nk = ctx->cfg.halo_npoints;
     std::vector<double> ai((size_t)nk * nk);
     halofit_collocation_inverse_host(nk, ai.data());
-    HIPCHK(hipMalloc(&ctx->d_hf_ainv, ai.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(ctx->d_hf_ainv, ai.data(), ai.size() * sizeof(double), hipMemcpyHostToDevice));
+    rc = constant(ctx, ctx->d_hf_ainv, ai.data(), ai.size());
+    if (rc) return rc;
   }
-  HIPCHK(hipMalloc(&ctx->d_cand, cand.size() * sizeof(double)));
-  HIPCHK(hipMemcpy(ctx->d_cand, cand.data(), cand.size() * sizeof(double),
-                   hipMemcpyHostToDevice));
-  return CHOMP_OK;
+  return constant(ctx, ctx->d_cand, cand.data(), cand.size());
 }
 
 int alloc_epochs(chomp_ctx* ctx, size_t n) {
@@ -603,42 +563,42 @@ int alloc_epochs(chomp_ctx* ctx, size_t n) {
   if (capturing(ctx))
     return fail(ctx, CHOMP_ERR_STATE,
                 "the epoch batch would have to grow while the context's stream is being captured");
-  void* old[] = {ctx->d_cosmo, ctx->d_z, ctx->d_epochs, ctx->d_search, ctx->d_probe, ctx->d_count, ctx->d_pending, ctx->d_tab,
-                 ctx->d_mass_par, ctx->d_profile, ctx->d_hod, ctx->d_nodes, ctx->d_snodes,
-                 ctx->d_slot, ctx->d_first, ctx->d_status, ctx->d_endp, ctx->d_npend};
-  for (void* p : old) {
-    const int rc = release_device(ctx, p);
-    if (rc) return rc;
-  }
-  HIPCHK(hipMalloc(&ctx->d_cosmo, n * sizeof(chomp_cosmo)));
-  HIPCHK(hipMalloc(&ctx->d_z, n * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_epochs, n * sizeof(Epoch)));
-  HIPCHK(hipMalloc(&ctx->d_search, n * 4 * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_probe, n * kProbeStride * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_count, n * sizeof(int)));
+  // (every block of the batch is a new one of exactly its size; a parameter block's shadow
+  //  goes with the block it described)
+  auto fresh = [&](auto& b, size_t count) { return grown(ctx, b.renew(ctx->mem, count)); };
+  int rc = fresh(ctx->d_cosmo, n);
+  if (!rc) rc = fresh(ctx->d_z, n);
+  if (!rc) rc = fresh(ctx->d_epochs, n);
+  if (!rc) rc = fresh(ctx->d_search, n * 4);
+  if (!rc) rc = fresh(ctx->d_probe, n * kProbeStride);
+  if (!rc) rc = fresh(ctx->d_count, n);
+  if (rc) return rc;
   HIPCHK(hipMemsetAsync(ctx->d_count, 0, n * sizeof(int), ctx->stream));
-  HIPCHK(hipMalloc(&ctx->d_pending, pending_ints(n, ctx->L.NK) * sizeof(int)));
+  rc = fresh(ctx->d_pending, pending_ints(n, ctx->L.NK));
+  if (rc) return rc;
   HIPCHK(hipMemsetAsync(ctx->d_pending, 0, kPendingHead * sizeof(int), ctx->stream));
-  HIPCHK(hipMalloc(&ctx->d_endp, n * kGroups * 2 * (size_t)ctx->L.NK * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_npend, n * sizeof(int)));
+  rc = fresh(ctx->d_endp, n * kGroups * 2 * (size_t)ctx->L.NK);
+  if (!rc) rc = fresh(ctx->d_npend, n);
+  if (rc) return rc;
   HIPCHK(hipMemsetAsync(ctx->d_npend, 0, n * sizeof(int), ctx->stream));
-  HIPCHK(hipMalloc(&ctx->d_tab, n * (size_t)ctx->L.stride * sizeof(double)));
+  rc = fresh(ctx->d_tab, n * (size_t)ctx->L.stride);
+  if (rc) return rc;
   // (rows of the levels table and knot tables no set-up has written read back as 0, not as
   //  whatever the allocation held: the same for every context)
   HIPCHK(hipMemsetAsync(ctx->d_tab, 0, n * (size_t)ctx->L.stride * sizeof(double), ctx->stream));
-  HIPCHK(hipMalloc(&ctx->d_mass_par, n * sizeof(chomp_halo_par)));
-  HIPCHK(hipMalloc(&ctx->d_profile, n * sizeof(chomp_halo_par)));
-  HIPCHK(hipMalloc(&ctx->d_hod, n * sizeof(HodDev)));
-  HIPCHK(hipMalloc(&ctx->d_nodes, n * kGroups * (size_t)kNodeStride * sizeof(double)));
-  HIPCHK(hipMalloc(&ctx->d_snodes, n * (size_t)kSigmaStride * sizeof(double)));
+  rc = fresh(ctx->d_mass_par, n);
+  if (!rc) rc = fresh(ctx->d_profile, n);
+  if (!rc) rc = fresh(ctx->d_hod, n);
+  if (!rc) rc = fresh(ctx->d_nodes, n * kGroups * (size_t)kNodeStride);
+  if (!rc) rc = fresh(ctx->d_snodes, n * (size_t)kSigmaStride);
+  if (rc) return rc;
   // (holds the arrival counters of k_sigma_nodes: zero once, the kernel resets them)
   HIPCHK(hipMemsetAsync(ctx->d_snodes, 0, n * (size_t)kSigmaStride * sizeof(double), ctx->stream));
-  HIPCHK(hipMalloc(&ctx->d_slot, n * sizeof(int)));
-  HIPCHK(hipMalloc(&ctx->d_first, n * sizeof(int)));
-  HIPCHK(hipMalloc(&ctx->d_status, n * sizeof(unsigned)));
+  rc = fresh(ctx->d_slot, n);
+  if (!rc) rc = fresh(ctx->d_first, n);
+  if (!rc) rc = fresh(ctx->d_status, n);
+  if (rc) return rc;
   ctx->cap_epoch = n;
-  ctx->sh_cosmo.reset(); ctx->sh_z.reset(); ctx->sh_mass.reset();
-  ctx->sh_profile.reset(); ctx->sh_hod.reset(); ctx->sh_slot.reset(); ctx->sh_first.reset();
   return CHOMP_OK;
 }
 
@@ -664,10 +624,15 @@ int chomp_ctx_create(const chomp_config* cfg, int device, void* hip_stream,
   chomp_ctx* ctx = new chomp_ctx();
   if (cfg) ctx->cfg = *cfg; else chomp_default_config(&ctx->cfg);
   const chomp_config& c = ctx->cfg;
+  // (every way out that is not success: through chomp_ctx_destroy once there is a stream, so
+  //  that it and the constants go too; before that the context owns nothing on the device)
+  auto leave = [&](int code) {
+    if (ctx->stream) chomp_ctx_destroy(ctx); else delete ctx;
+    return code;
+  };
   auto bad = [&](const char* m) {
-    delete ctx;
     fprintf(stderr, "chomp_ctx_create: %s\n", m);
-    return CHOMP_ERR_ARG;
+    return leave(CHOMP_ERR_ARG);
   };
   if (c.mass_npoints < 8 || c.mass_npoints > 256) return bad("mass_npoints out of [8,256]");
   if (c.halo_npoints < 6 || c.halo_npoints > 256) return bad("halo_npoints out of [6,256]");
@@ -681,60 +646,36 @@ int chomp_ctx_create(const chomp_config* cfg, int device, void* hip_stream,
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    delete ctx;
     fprintf(stderr, "chomp_ctx_create: no usable HIP device %d (%s) -- this library has "
                     "no CPU fallback\n", device, hipGetErrorString(e));
-    return CHOMP_ERR_HIP;
+    return leave(CHOMP_ERR_HIP);
   }
-  if (hipSetDevice(device) != hipSuccess) { delete ctx; return CHOMP_ERR_HIP; }
+  if (hipSetDevice(device) != hipSuccess) return leave(CHOMP_ERR_HIP);
   if (hip_stream) {
     ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
   } else {
-    if (hipStreamCreate(&ctx->stream) != hipSuccess) { delete ctx; return CHOMP_ERR_HIP; }
+    if (hipStreamCreate(&ctx->stream) != hipSuccess) return leave(CHOMP_ERR_HIP);
     ctx->owns_stream = true;
   }
   int rc = setup_constants(ctx);
   if (rc != CHOMP_OK) {
     fprintf(stderr, "chomp_ctx_create: %s\n", ctx->err.c_str());
-    delete ctx;
-    return rc;
+    return leave(rc);
   }
   *out = ctx;
   return CHOMP_OK;
 }
 
+// Nothing of the context is in flight once its two streams have drained (every call queues on
+// one of them), so the buffers -- which free themselves with the context, after the streams it
+// owns are gone -- are freed idle; hipFree does not need the stream.  A caller's stream
+// (owns_stream false) is drained the same and left alone.
 void chomp_ctx_destroy(chomp_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->side) (void)hipStreamSynchronize(ctx->side);
   (void)hipStreamSynchronize(ctx->stream);
-  void* ptrs[] = {ctx->d_sici, ctx->d_j0, ctx->d_j2, ctx->d_tinker, ctx->d_gl16,
-                  ctx->d_cand, ctx->d_cosmo, ctx->d_z, ctx->d_epochs, ctx->d_search, ctx->d_probe, ctx->d_count, ctx->d_pending,
-                  ctx->d_tab, ctx->d_mass_par, ctx->d_profile, ctx->d_hod, ctx->d_nodes, ctx->d_snodes, ctx->d_slot, ctx->d_first, ctx->d_status, ctx->d_endp, ctx->d_npend,
-                  ctx->d_stage_in, ctx->d_kcache, ctx->d_stage_out, ctx->d_slow, ctx->d_wnodes, ctx->d_cnodes, ctx->d_deepw, ctx->d_deepstat,
-                  ctx->d_winfo, ctx->d_ktab, ctx->d_samples, ctx->d_psum, ctx->d_plan, ctx->d_hf_ainv, ctx->d_delta_b,
-                  ctx->d_de_knots, ctx->d_de_slot, ctx->de_ep.d_tab, ctx->de_ep.d_par, ctx->de_proj.d_tab,
-                  ctx->de_proj.d_par, ctx->d_b2, ctx->d_tri, ctx->d_tri4, ctx->d_prof,
-                  ctx->sets.d_pd, ctx->sets.d_pd_init, ctx->sets.d_tab, ctx->blocks.d, ctx->blocks.d_index,
-                  ctx->ssc_blocks.d, ctx->ssc_blocks.d_kb, ctx->ssc_blocks.d_index, ctx->ssc_blocks.d_sigma};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (void* p : ctx->graveyard) (void)hipFree(p);
-  for (void* p : ctx->host_graveyard) (void)hipHostFree(p);
-  for (StagedBlock* b : {&ctx->sh_cosmo, &ctx->sh_z, &ctx->sh_mass, &ctx->sh_profile, &ctx->sh_hod,
-                         &ctx->sh_slot, &ctx->sh_first, &ctx->sh_delta_b, &ctx->sh_proj, &ctx->sh_pp[0],
-                         &ctx->sh_pp[1], &ctx->sh_de_knots, &ctx->sh_de_slot, &ctx->de_ep.sh_par,
-                         &ctx->de_proj.sh_par, &ctx->sh_sets, &ctx->sh_blocks,
-                         &ctx->sh_ssc_blocks})
-    b->release();
-  if (ctx->h_status) (void)hipHostFree(ctx->h_status);
-  if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);
   if (ctx->ev_status) (void)hipEventDestroy(ctx->ev_status);
-  if (ctx->h_stage_in) (void)hipHostFree(ctx->h_stage_in);
-  if (ctx->h_stage_out) (void)hipHostFree(ctx->h_stage_out);
-  proj_free(ctx->proj);
-  if (ctx->cross.d) (void)hipFree(ctx->cross.d);
-  if (ctx->fourier.d) (void)hipFree(ctx->fourier.d);
   for (hipEvent_t e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {ctx->ev_side_go, ctx->ev_proj_ready, ctx->ev_side_done})
@@ -834,7 +775,7 @@ int chomp_get_status(chomp_ctx* ctx, size_t epoch0, size_t n, unsigned* out) {
 static int mirror_collect(chomp_ctx* ctx, int half, unsigned seq, size_t epoch0, size_t n,
                           unsigned* out);
 static int ensure_hstatus(chomp_ctx* ctx) {
-  if (ctx->n_epoch <= ctx->cap_hstatus && ctx->h_status && ctx->h_mirror) return CHOMP_OK;
+  if (ctx->h_status.fits(ctx->n_epoch) && ctx->h_mirror) return CHOMP_OK;
   if (capturing(ctx)) return CHOMP_OK;
   HIPCHK(hipStreamSynchronize(ctx->stream));       // (a copy or a kernel's mirror may be in flight)
   // (a post nobody has waited for yet survives the reallocation: its words are there now)
@@ -852,25 +793,14 @@ static int ensure_hstatus(chomp_ctx* ctx) {
   }
   const int kept_kind = ctx->posted_kind;
   const size_t kept_n = ctx->n_hstatus;
-  if (ctx->graph_seen) {
-    if (ctx->h_status) ctx->host_graveyard.push_back(ctx->h_status);
-    if (ctx->h_mirror) ctx->host_graveyard.push_back(ctx->h_mirror);
-  } else {
-    if (ctx->h_status) HIPCHK(hipHostFree(ctx->h_status));
-    if (ctx->h_mirror) HIPCHK(hipHostFree(ctx->h_mirror));
-  }
-  ctx->h_status = nullptr;
-  ctx->h_mirror = nullptr;
   ctx->L.h_status = nullptr;
-  ctx->cap_hstatus = 0;
   ctx->posted_kind = kept_kind == 3 ? 3 : 0;
   ctx->n_hstatus = kept_kind == 3 ? kept_n : 0;
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_status), ctx->n_epoch * sizeof(unsigned),
-                       hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_mirror),
-                       3 * ctx->n_epoch * sizeof(unsigned long long), hipHostMallocDefault));
+  // (a graph may still write the old words: the buffers park them then)
+  int rc = grown(ctx, ctx->h_status.renew(ctx->mem, ctx->n_epoch));
+  if (!rc) rc = grown(ctx, ctx->h_mirror.renew(ctx->mem, 3 * ctx->n_epoch));
+  if (rc) return rc;
   std::memset(ctx->h_mirror, 0, 3 * ctx->n_epoch * sizeof(unsigned long long));
-  ctx->cap_hstatus = ctx->n_epoch;
   ctx->mirror_half = 0;
   ctx->mirror_region = 0;
   ctx->L.h_status = ctx->h_mirror;
@@ -883,7 +813,7 @@ static int ensure_hstatus(chomp_ctx* ctx) {
 // an error when the stream has drained and they still do not (a set-up that failed).
 static int mirror_collect(chomp_ctx* ctx, int half, unsigned seq, size_t epoch0, size_t n,
                           unsigned* out) {
-  const volatile unsigned long long* w = ctx->h_mirror + (size_t)half * ctx->cap_hstatus + epoch0;
+  const volatile unsigned long long* w = ctx->h_mirror + (size_t)half * ctx->h_status.cap() + epoch0;
   for (size_t i = 0; i < n; ++i) {
     bool drained = false;
     for (;;) {
@@ -916,7 +846,7 @@ static int mirror_next(chomp_ctx* ctx) {
     ctx->posted_kind = 3;
   }
   ctx->mirror_region = next;
-  ctx->L.h_status = ctx->h_mirror + (size_t)next * ctx->cap_hstatus;
+  ctx->L.h_status = ctx->h_mirror + (size_t)next * ctx->h_status.cap();
   ctx->L.h_seq = ++ctx->setup_seq;
   return CHOMP_OK;
 }
@@ -926,7 +856,7 @@ int chomp_status_post(chomp_ctx* ctx) {
   if (!ctx->have_epochs) return fail(ctx, CHOMP_ERR_STATE, "status_post before epochs_set");
   HIPCHK(hipSetDevice(ctx->device));
   const bool cap = capturing(ctx);
-  if (cap && (ctx->n_epoch > ctx->cap_hstatus || !ctx->h_status))
+  if (cap && (ctx->n_epoch > ctx->h_status.cap() || !ctx->h_status))
     return fail(ctx, CHOMP_ERR_STATE,
                 "status_post during stream capture before any eager set-up of this size (the "
                 "pinned words would have to be allocated)");
@@ -985,11 +915,9 @@ static int de_knots(chomp_ctx* ctx) {
   const int n = ctx->cfg.cosmo_npoints;
   std::vector<double> k(2 * (size_t)n);
   for (int i = 0; i < n; ++i) de_knot(ctx->cfg.cosmo_precision, n, i, &k[i], &k[n + i]);
-  const double* before = ctx->d_de_knots;
-  const int rc = ensure(ctx, &ctx->d_de_knots, &ctx->cap_de_knots, k.size());
+  const int rc = ensure(ctx, ctx->d_de_knots, k.size());
   if (rc) return rc;
-  if (ctx->d_de_knots != before) ctx->sh_de_knots.reset();
-  return upload(ctx, ctx->d_de_knots, k.data(), k.size() * sizeof(double), ctx->sh_de_knots);
+  return upload(ctx, ctx->d_de_knots, k.data(), k.size() * sizeof(double));
 }
 
 // The tables of the distinct (w0, wa) of `keys`, queued on the context's stream -- or nothing,
@@ -1005,13 +933,11 @@ static int de_build(chomp_ctx* ctx, DeTables& T, const std::vector<DePar>& keys)
   T.valid = false;
   int rc = de_knots(ctx);
   if (rc) return rc;
-  const DePar* before = T.d_par;
-  rc = ensure(ctx, &T.d_par, &T.cap_par, nk);
+  rc = ensure(ctx, T.d_par, nk);
   if (rc) return rc;
-  if (T.d_par != before) T.sh_par.reset();
-  rc = ensure(ctx, &T.d_tab, &T.cap_tab, nk * (size_t)de_stride(n));
+  rc = ensure(ctx, T.d_tab, nk * (size_t)de_stride(n));
   if (rc) return rc;
-  rc = upload(ctx, T.d_par, keys.data(), nk * sizeof(DePar), T.sh_par);
+  rc = upload(ctx, T.d_par, keys.data(), nk * sizeof(DePar));
   if (rc) return rc;
   hipLaunchKernelGGL(k_de_table, dim3((unsigned)n, (unsigned)nk), dim3(64 * kDeNW), 0, ctx->stream,
                      ctx->cfg, T.d_par, ctx->d_de_knots, T.d_tab);
@@ -1095,9 +1021,9 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   ctx->tri_built.assign(n_epoch, 0);
   ctx->tri4_built.assign(n_epoch, 0);
   ctx->prof_general.assign(n_epoch, 0);
-  rc = upload(ctx, ctx->d_cosmo, cosmo, n_epoch * sizeof(chomp_cosmo), ctx->sh_cosmo);
+  rc = upload(ctx, ctx->d_cosmo, cosmo, n_epoch * sizeof(chomp_cosmo));
   if (rc) return rc;
-  rc = upload(ctx, ctx->d_z, z, n_epoch * sizeof(double), ctx->sh_z);
+  rc = upload(ctx, ctx->d_z, z, n_epoch * sizeof(double));
   if (rc) return rc;
   // cosmology-only work (sigma node table, sigma_8 integral) is shared by the epochs of
   // one cosmology: slot = index of the first epoch with identical parameters
@@ -1129,9 +1055,9 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   ctx->n_slots = n_slots;
   ctx->slot = slot;
   first.resize(n_epoch, 0);
-  rc = upload(ctx, ctx->d_slot, slot.data(), n_epoch * sizeof(int), ctx->sh_slot);
+  rc = upload(ctx, ctx->d_slot, slot.data(), n_epoch * sizeof(int));
   if (rc) return rc;
-  rc = upload(ctx, ctx->d_first, first.data(), n_epoch * sizeof(int), ctx->sh_first);
+  rc = upload(ctx, ctx->d_first, first.data(), n_epoch * sizeof(int));
   if (rc) return rc;
   // w0-wa dark energy: one pressure table per distinct (w0, wa), epoch -> table (-1: none).  A
   // batch without dark energy queues nothing here.
@@ -1150,11 +1076,9 @@ int chomp_epochs_set(chomp_ctx* ctx, size_t n_epoch, const chomp_cosmo* cosmo,
   if (any_de) {
     rc = de_build(ctx, ctx->de_ep, de_keys);
     if (rc) return rc;
-    const int* before = ctx->d_de_slot;
-    rc = ensure(ctx, &ctx->d_de_slot, &ctx->cap_de_slot, n_epoch);
+    rc = ensure(ctx, ctx->d_de_slot, n_epoch);
     if (rc) return rc;
-    if (ctx->d_de_slot != before) ctx->sh_de_slot.reset();
-    rc = upload(ctx, ctx->d_de_slot, ctx->de_slot.data(), n_epoch * sizeof(int), ctx->sh_de_slot);
+    rc = upload(ctx, ctx->d_de_slot, ctx->de_slot.data(), n_epoch * sizeof(int));
     if (rc) return rc;
   }
   // (one cosmology or a few: most blocks, shortest launch; a batch of many: four nodes per
@@ -1294,9 +1218,9 @@ static int halo_prepare(chomp_ctx* ctx, const chomp_halo_par* profile, const cho
     d.safe_norm = std::pow(10.0, h.log_M_min + 1.0 * h.sigma);
     if (h.alpha != 1.0) P->eval = true;
   }
-  int rcu = upload(ctx, ctx->d_profile, profile, n * sizeof(chomp_halo_par), ctx->sh_profile);
+  int rcu = upload(ctx, ctx->d_profile, profile, n * sizeof(chomp_halo_par));
   if (rcu) return rcu;
-  rcu = upload(ctx, ctx->d_hod, hd.data(), n * sizeof(HodDev), ctx->sh_hod);
+  rcu = upload(ctx, ctx->d_hod, hd.data(), n * sizeof(HodDev));
   if (rcu) return rcu;
   // header bits CHOMP_T_* are (1 << F_*) by construction
   P->fam = tables & ((1u << kFamilies) - 1u);
@@ -1325,7 +1249,7 @@ static int launch_nu_mass(chomp_ctx* ctx, int mf_kind, const HaloPlan* plan) {
   ctx->have_b2 = false;
   if (ctx->second_order) {
     ctx->B2 = make_b2_layout(L.NM);
-    const int rcb = ensure(ctx, &ctx->d_b2, &ctx->cap_b2, n * (size_t)ctx->B2.stride);
+    const int rcb = ensure(ctx, ctx->d_b2, n * (size_t)ctx->B2.stride);
     if (rcb) return rcb;
   }
   with_flag(ctx->with_bao, (size_t)L.NM * n <= 512, [&](auto BAO, auto FEW) {
@@ -1387,7 +1311,7 @@ extern "C++" struct KnotsFast {
                        P.groups[1], P.groups[2], P.groups[3], P.kmask, (int)ctx->n_epoch, ctx->d_pending, ctx->d_npend,
                        ctx->d_epochs, P.fam, ctx->d_status, ctx->d_deepw, all_literal, deep_tol, max_rough,
                        max_fine, ctx->d_deepstat, ctx->d_samples, ctx->d_psum, parts, round, lo, hi,
-                       from_eval, reinterpret_cast<const DeepPlan*>(ctx->d_plan), ctx->d_profile, ctx->d_hod);
+                       from_eval, ctx->d_plan, ctx->d_profile, ctx->d_hod);
     return CHOMP_OK;
   }
 };
@@ -1424,9 +1348,9 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
     if ((worst + slots - 1) / slots > (size_t)kPendingRounds)
       slots = (worst + kPendingRounds - 1) / kPendingRounds;
     rounds = (int)((worst + slots - 1) / slots);
-    int rck = ensure(ctx, &ctx->d_samples, &ctx->cap_samples, slots * (size_t)kDeepSlot);
+    int rck = ensure(ctx, ctx->d_samples, slots * (size_t)kDeepSlot);
     if (rck) return rck;
-    rck = ensure(ctx, &ctx->d_psum, &ctx->cap_psum, slots * (size_t)(kDeepChunks * kDeepPsum));
+    rck = ensure(ctx, ctx->d_psum, slots * (size_t)(kDeepChunks * kDeepPsum));
     if (rck) return rck;
   }
   // (a set-up of one or a few epochs -- every launch lasts as long as its slowest unit -- leaves
@@ -1449,7 +1373,7 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
   // (the break-point plans of the (epoch, group)s: an extra block row of k_halo_knots)
   const int want_plan = deep_route ? 1 : 0;
   if (want_plan) {
-    const int rcp = ensure(ctx, &ctx->d_plan, &ctx->cap_plan, n * kGroups * sizeof(DeepPlan));
+    const int rcp = ensure(ctx, ctx->d_plan, n * kGroups);
     if (rcp) return rcp;
   }
   auto knots = [&](auto KNW) {
@@ -1458,7 +1382,7 @@ static int launch_halo_knots(chomp_ctx* ctx, const HaloPlan& P) {
                        ctx->d_profile, ctx->d_hod, ctx->d_sici, ctx->d_nodes, ctx->d_endp,
                        P.groups[0], P.groups[1], P.groups[2], P.groups[3], P.kmask, P.want_nbar, ctx->d_pending,
                        ctx->d_npend, ctx->d_status, hod_cap, want_plan, max_rough, max_fine,
-                       reinterpret_cast<DeepPlan*>(ctx->d_plan));
+                       ctx->d_plan);
   };
   if (wide) knots(int_c<4>{}); else if (lone) knots(int_c<0>{}); else knots(int_c<1>{});
   // blocks 0..n-1 take the epochs' tokens; with integrands that can run beyond the node
@@ -1541,7 +1465,7 @@ static int launch_halo_general(chomp_ctx* ctx, const HaloPlan& P, const chomp_ha
   if (n > 65535) return fail(ctx, CHOMP_ERR_ARG, "halo_setup: at most 65535 epochs with a general profile");
   ctx->PL = make_prof_layout(L.NM, L.NK);
   const ProfLayout& PL = ctx->PL;
-  int rc = ensure(ctx, &ctx->d_prof, &ctx->cap_prof, n * (size_t)PL.stride);
+  int rc = ensure(ctx, ctx->d_prof, n * (size_t)PL.stride);
   if (rc) return rc;
   if (P.fam) {                      // (a set-up for n_bar alone integrates no y)
     hipLaunchKernelGGL(k_y_general_table, dim3((unsigned)L.NM, (unsigned)L.NK, (unsigned)n), dim3(64), 0,
@@ -1584,7 +1508,7 @@ int chomp_mass_setup(chomp_ctx* ctx, const chomp_halo_par* par, int mf_kind) {
   if (mf_kind != CHOMP_MF_ST && mf_kind != CHOMP_MF_TINKER)
     return fail(ctx, CHOMP_ERR_ARG, "mass_setup: unknown mass function kind");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = upload(ctx, ctx->d_mass_par, par, ctx->n_epoch * sizeof(chomp_halo_par), ctx->sh_mass);
+  int rc = upload(ctx, ctx->d_mass_par, par, ctx->n_epoch * sizeof(chomp_halo_par));
   if (rc) return rc;
   rc = launch_nu_mass(ctx, mf_kind, nullptr);
   if (rc) return rc;
@@ -1633,7 +1557,7 @@ int chomp_stage_k_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, int mf_kin
   if (mf_kind != CHOMP_MF_ST && mf_kind != CHOMP_MF_TINKER)
     return fail(ctx, CHOMP_ERR_ARG, "stage_k: unknown mass function kind");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = upload(ctx, ctx->d_mass_par, mass_par, ctx->n_epoch * sizeof(chomp_halo_par), ctx->sh_mass);
+  int rc = upload(ctx, ctx->d_mass_par, mass_par, ctx->n_epoch * sizeof(chomp_halo_par));
   if (rc) return rc;
   HaloPlan P;
   rc = halo_prepare(ctx, profile, hod, tables, &P);
@@ -1686,7 +1610,7 @@ int chomp_hod_stats(chomp_ctx* ctx, size_t epoch0, size_t n, double* out) {
   if (!ctx->have_halo) return fail(ctx, CHOMP_ERR_STATE, "hod_stats before halo_setup");
   if (epoch0 + n > ctx->n_epoch) return fail(ctx, CHOMP_ERR_ARG, "hod_stats: epoch range");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, 3 * n);
+  int rc = ensure(ctx, ctx->d_stage_out, 3 * n);
   if (rc) return rc;
   const TabLayout& L = ctx->L;
   const size_t sh = (size_t)(L.NM + 8 * (L.NM - 1) + kKnotScratch) * sizeof(double);
@@ -1759,10 +1683,10 @@ static int stage_e_prep(chomp_ctx* ctx, size_t epoch0, int w, const double* dk, 
   // and clears the other for the next streaming call).  A call captured into a HIP graph
   // would replay ONE parity for ever and run its counter past the list, so under capture
   // the call clears both counters itself (a memset node) and keeps the bit still.
-  const size_t had = ctx->cap_slow;
-  int rc = ensure(ctx, &ctx->d_slow, &ctx->cap_slow, groups + 2);
+  bool fresh = false;
+  int rc = ensure(ctx, ctx->d_slow, groups + 2, &fresh);
   if (rc) return rc;
-  if (ctx->cap_slow != had)                      // fresh buffer: clear both counters
+  if (fresh)                                     // fresh buffer: clear both counters
     HIPCHK(hipMemsetAsync(ctx->d_slow, 0, 2 * sizeof(int), ctx->stream));
   *parity = ctx->slow_parity;
   if (capturing(ctx)) ctx->slow_by_memset = true;
@@ -1773,9 +1697,9 @@ static int stage_e_prep(chomp_ctx* ctx, size_t epoch0, int w, const double* dk, 
     ctx->slow_parity ^= 1;
   }
   const unsigned gx8 = (gx + 7) / 8 * 8;
-  rc = ensure(ctx, &ctx->d_winfo, &ctx->cap_winfo, (size_t)gx8 * 4);
+  rc = ensure(ctx, ctx->d_winfo, (size_t)gx8 * 4);
   if (rc) return rc;
-  rc = ensure(ctx, &ctx->d_ktab, &ctx->cap_ktab, (size_t)gx8 * 1024);
+  rc = ensure(ctx, ctx->d_ktab, (size_t)gx8 * 1024);
   if (rc) return rc;
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_power_prep<BAO>, dim3(gx8), dim3(256), 0, ctx->stream, ctx->cfg, L,
@@ -1789,11 +1713,11 @@ static int stage_e_prep(chomp_ctx* ctx, size_t epoch0, int w, const double* dk, 
 // The per-epoch delta_b buffer, cleared if chomp_epochs_set has been called since it was last
 // written.
 static int ensure_delta_b(chomp_ctx* ctx) {
-  const size_t had = ctx->cap_delta_b;
-  const int rc = ensure(ctx, &ctx->d_delta_b, &ctx->cap_delta_b, ctx->n_epoch);
+  bool fresh = false;
+  const int rc = ensure(ctx, ctx->d_delta_b, ctx->n_epoch, &fresh);
   if (rc) return rc;
-  if (ctx->delta_b_zero || ctx->cap_delta_b != had) {
-    HIPCHK(hipMemsetAsync(ctx->d_delta_b, 0, ctx->cap_delta_b * sizeof(double), ctx->stream));
+  if (ctx->delta_b_zero || fresh) {
+    HIPCHK(hipMemsetAsync(ctx->d_delta_b, 0, ctx->d_delta_b.cap() * sizeof(double), ctx->stream));
     ctx->delta_b_zero = false;
   }
   return CHOMP_OK;
@@ -1824,8 +1748,8 @@ int chomp_set_delta_b(chomp_ctx* ctx, size_t epoch0, size_t n, const double* del
 static bool plan_matches(chomp_ctx* ctx, size_t epoch0, const double* dk, size_t nk) {
   const chomp_ctx::PowerPlan& P = ctx->plan;
   if (!P.valid || P.k != dk || P.nk != nk || P.bao != ctx->with_bao) return false;
-  if (ctx->sh_cosmo.shadow.size() < (epoch0 + 1) * sizeof(chomp_cosmo)) return false;
-  return std::memcmp(&P.cosmo, ctx->sh_cosmo.shadow.data() + epoch0 * sizeof(chomp_cosmo),
+  if (ctx->d_cosmo.sh.shadow.size() < (epoch0 + 1) * sizeof(chomp_cosmo)) return false;
+  return std::memcmp(&P.cosmo, ctx->d_cosmo.sh.shadow.data() + epoch0 * sizeof(chomp_cosmo),
                      sizeof(chomp_cosmo)) == 0;
 }
 
@@ -1844,7 +1768,7 @@ int chomp_power_plan(chomp_ctx* ctx, size_t epoch0, const double* k, size_t nk) 
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->plan.k = k;
   ctx->plan.nk = nk;
-  std::memcpy(&ctx->plan.cosmo, ctx->sh_cosmo.shadow.data() + epoch0 * sizeof(chomp_cosmo),
+  std::memcpy(&ctx->plan.cosmo, ctx->d_cosmo.sh.shadow.data() + epoch0 * sizeof(chomp_cosmo),
               sizeof(chomp_cosmo));
   ctx->plan.bao = ctx->with_bao;
   ctx->plan.parity = parity;
@@ -1873,20 +1797,22 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
   const double* dk = k;
   double* dout = out;
   if (mem == CHOMP_HOST) {
-    rc = ensure(ctx, &ctx->d_stage_out, &ctx->cap_out, nk * n);
+    rc = ensure(ctx, ctx->d_stage_out, nk * n);
     if (rc) return rc;
     // through pinned mirrors: a pageable buffer would be staged by the runtime in small
-    // synchronous pieces
-    rc = ensure_host(ctx, &ctx->h_stage_in, &ctx->cap_hin, nk);
+    // synchronous pieces (no refusal of their own under capture: d_stage_out has made it)
+    if (!ctx->h_stage_in.fits(nk)) rc = grown(ctx, ctx->h_stage_in.renew(ctx->mem, nk));
     if (rc) return rc;
-    rc = ensure_host(ctx, &ctx->h_stage_out, &ctx->cap_hout, nk * n);
+    if (!ctx->h_stage_out.fits(nk * n)) rc = grown(ctx, ctx->h_stage_out.renew(ctx->mem, nk * n));
     if (rc) return rc;
     // The reference-shaped loop asks for the same k array at every redshift: the device copy of
     // the last host k grid is kept (a buffer of its own; 32 KB compared in ~1 us) and the upload
     // -- which would sit behind the set-up on the stream, in front of the evaluation -- skipped.
-    rc = ensure(ctx, &ctx->d_kcache, &ctx->cap_kcache, nk);
+    bool moved = false;
+    rc = ensure(ctx, ctx->d_kcache, nk, &moved);
     if (rc) return rc;
-    if (ctx->kcache_ptr != ctx->d_kcache || ctx->kcache_shadow.size() != nk ||
+    if (moved) ctx->kcache_shadow.clear();
+    if (ctx->kcache_shadow.size() != nk ||
         std::memcmp(ctx->kcache_shadow.data(), k, nk * sizeof(double)) != 0) {
       if (capturing(ctx))
         return fail(ctx, CHOMP_ERR_STATE, "power: a new host k grid while the stream is being captured");
@@ -1894,7 +1820,6 @@ int chomp_power_range(chomp_ctx* ctx, int which, size_t epoch0, size_t n, const 
       HIPCHK(hipMemcpyAsync(ctx->d_kcache, ctx->h_stage_in, nk * sizeof(double),
                             hipMemcpyHostToDevice, ctx->stream));
       ctx->kcache_shadow.assign(k, k + nk);
-      ctx->kcache_ptr = ctx->d_kcache;
     }
     dk = ctx->d_kcache;
     dout = ctx->d_stage_out;
@@ -2023,7 +1948,7 @@ int chomp_y_nfw(chomp_ctx* ctx, size_t epoch, const double* ln_k, const double* 
 // it; an NFW-only one has not).
 static int ensure_prof(chomp_ctx* ctx) {
   ctx->PL = make_prof_layout(ctx->L.NM, ctx->L.NK);
-  return ensure(ctx, &ctx->d_prof, &ctx->cap_prof, ctx->n_epoch * (size_t)ctx->PL.stride);
+  return ensure(ctx, ctx->d_prof, ctx->n_epoch * (size_t)ctx->PL.stride);
 }
 
 int chomp_y_general(chomp_ctx* ctx, size_t epoch, double ln_k, const double* mass, size_t n,
@@ -2229,11 +2154,9 @@ int chomp_tri1h_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, int moment,
   ctx->T3 = make_tri_layout(N);
   const TriLayout& T = ctx->T3;
   const size_t need = ctx->n_epoch * (size_t)T.total;
-  if (need > ctx->cap_tri) {          // (a grown buffer holds no epoch's table)
-    const int rc = ensure(ctx, &ctx->d_tri, &ctx->cap_tri, need);
-    if (rc) return rc;
-    ctx->tri_built.assign(ctx->n_epoch, 0);
-  }
+  bool moved = false;
+  { const int rc = ensure(ctx, ctx->d_tri, need, &moved); if (rc) return rc; }
+  if (moved) ctx->tri_built.assign(ctx->n_epoch, 0);   // (a grown buffer holds no epoch's table)
   const int lds = tri_table_lds_doubles(ctx->L.NM, N) * (int)sizeof(double);
   { const int rc = lds_opt_in(ctx, &k_tri1h_table, lds); if (rc) return rc; }
   hipLaunchKernelGGL(k_tri1h_table, dim3((unsigned)T.nchunk, (unsigned)n_epoch), dim3(kTriThreads),
@@ -2337,11 +2260,9 @@ int chomp_tri_setup(chomp_ctx* ctx, size_t epoch0, size_t n_epoch, double* table
   ctx->Q4 = make_tri_tab_layout(N);
   const TriTabLayout& Q = ctx->Q4;
   const size_t need = ctx->n_epoch * (size_t)Q.total;
-  if (need > ctx->cap_tri4 || ctx->tri4_built.size() != ctx->n_epoch) {
-    const int rc = ensure(ctx, &ctx->d_tri4, &ctx->cap_tri4, need);
-    if (rc) return rc;
-    ctx->tri4_built.assign(ctx->n_epoch, 0);
-  }
+  bool moved = false;
+  { const int rc = ensure(ctx, ctx->d_tri4, need, &moved); if (rc) return rc; }
+  if (moved || ctx->tri4_built.size() != ctx->n_epoch) ctx->tri4_built.assign(ctx->n_epoch, 0);
   const int lds = tri_tab_lds_doubles(ctx->L.NM, N) * (int)sizeof(double);
   { const int rc = lds_opt_in(ctx, &k_tri_table, lds); if (rc) return rc; }
   hipLaunchKernelGGL(k_tri_table, dim3((unsigned)Q.T.nchunk, (unsigned)n_epoch, 4u),

@@ -52,7 +52,7 @@ int chomp_stage_k_halofit_hod(chomp_ctx* ctx, const chomp_halo_par* mass_par, in
   if (mf_kind != CHOMP_MF_ST && mf_kind != CHOMP_MF_TINKER)
     return fail(ctx, CHOMP_ERR_ARG, "stage_k_halofit: unknown mass function kind");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = upload(ctx, ctx->d_mass_par, mass_par, ctx->n_epoch * sizeof(chomp_halo_par), ctx->sh_mass);
+  int rc = upload(ctx, ctx->d_mass_par, mass_par, ctx->n_epoch * sizeof(chomp_halo_par));
   if (rc) return rc;
   HaloPlan P;
   rc = halo_prepare(ctx, profile, hod, tables, &P);
@@ -201,15 +201,15 @@ int chomp_kernel_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double me_z_min
   for (int w = 0; w < 2; ++w)
     if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
       pp_doubles[w] = (size_t)ws[w]->dist.pp_n * (ws[w]->dist.pp_order + 2) + 1;
-  if (!P.d_pd) HIPCHK(hipMalloc(&P.d_pd, sizeof(ProjDev)));
-  if (!P.d_pd_init) HIPCHK(hipMalloc(&P.d_pd_init, sizeof(ProjDev)));
+  HIPCHK((hipError_t)P.d_pd.once(1));
+  HIPCHK((hipError_t)P.d_pd_init.once(1));
   {   // (kept across calls: a free / malloc pair would drain the device on every set-up)
-    const double* before = P.d_tab;
-    const int rce = ensure(ctx, &P.d_tab, &P.cap_tab, (size_t)P.L.total + pp_doubles[0] + pp_doubles[1]);
+    bool moved = false;
+    const int rce = ensure(ctx, P.d_tab, (size_t)P.L.total + pp_doubles[0] + pp_doubles[1], &moved);
     if (rce) return rce;
     // (the tabulated distributions' place behind the tables moves with the buffer and the
     //  layout: only then do they have to be sent again)
-    if (P.d_tab != before || P.pp_total != (size_t)P.L.total + pp_doubles[0]) {
+    if (moved || P.pp_total != (size_t)P.L.total + pp_doubles[0]) {
       ctx->sh_pp[0].reset();
       ctx->sh_pp[1].reset();
     }
@@ -290,9 +290,9 @@ int chomp_multi_epoch_setup(chomp_ctx* ctx, const chomp_cosmo* cosmo, double z_m
   P.ng_ready = false;
   P.ng_prep = false;
   P.L = make_proj_layout(c.cosmo_npoints, c.window_npoints, c.kernel_npoints);
-  if (!P.d_pd) HIPCHK(hipMalloc(&P.d_pd, sizeof(ProjDev)));
-  if (!P.d_pd_init) HIPCHK(hipMalloc(&P.d_pd_init, sizeof(ProjDev)));
-  { const int rce = ensure(ctx, &P.d_tab, &P.cap_tab, (size_t)P.L.total); if (rce) return rce; }
+  HIPCHK((hipError_t)P.d_pd.once(1));
+  HIPCHK((hipError_t)P.d_pd_init.once(1));
+  { const int rce = ensure(ctx, P.d_tab, (size_t)P.L.total); if (rce) return rce; }
   ProjDev pd;
   std::memset(&pd, 0, sizeof(pd));
   pd.om0 = cosmo->omega_m0; pd.ol0 = cosmo->omega_l0; pd.or0 = cosmo->omega_r0;
@@ -411,13 +411,9 @@ static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, con
   HIPCHK(hipSetDevice(ctx->device));
   ProjSets& S = ctx->sets;
   S.n = 0;
-  int rc = ensure(ctx, &S.d_pd, &S.cap_pd, n_set);
-  if (!rc) {
-    const ProjDev* before = S.d_pd_init;
-    rc = ensure(ctx, &S.d_pd_init, &S.cap_pd_init, n_set);
-    if (S.d_pd_init != before) ctx->sh_sets.reset();
-  }
-  if (!rc) rc = ensure(ctx, &S.d_tab, &S.cap_tab, n_set * (size_t)L.total);
+  int rc = ensure(ctx, S.d_pd, n_set);
+  if (!rc) rc = ensure(ctx, S.d_pd_init, n_set);
+  if (!rc) rc = ensure(ctx, S.d_tab, n_set * (size_t)L.total);
   if (rc) return rc;
   const double j_limit = bessel_zero_host(bessel_order, c.kernel_bessel_limit);
   std::vector<ProjDev> pd(n_set);
@@ -426,7 +422,7 @@ static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, con
     pd[s] = proj_host_block(c, &cosmo[s], me_z_min[s * step], me_z_max[s * step], ktheta_min,
                             ktheta_max, ws, bessel_order, j_limit);
   }
-  rc = upload(ctx, S.d_pd_init, pd.data(), n_set * sizeof(ProjDev), ctx->sh_sets);
+  rc = upload(ctx, S.d_pd_init, pd.data(), n_set * sizeof(ProjDev));
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(S.d_pd, S.d_pd_init, n_set * sizeof(ProjDev), hipMemcpyDeviceToDevice, ctx->stream));
   S.L = L;
@@ -637,7 +633,7 @@ static int wtheta_impl(chomp_ctx* ctx, int which, size_t epoch, double k_min, do
   // fp64: the theta-independent factor of the integrand on the Romberg nodes first, then the
   // moment route (k_wtheta_moments + k_wtheta_fast) or k_wtheta, as the plan says (WthPlan: the
   // node table, then the moment records and the segments' totals -- one epoch's scratch)
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, P.stride);
+  rc = ensure(ctx, ctx->d_wnodes, P.stride);
   if (rc) return rc;
   double* rec = ctx->d_wnodes + P.rec_at;
   double* segtot = ctx->d_wnodes + P.tot_at;
@@ -753,7 +749,7 @@ int chomp_xi3d_epochs(chomp_ctx* ctx, int which, size_t epoch0, size_t n_epoch, 
   // (the node-table part of the w(theta) plan: every level, divmax <= kWthetaTabLevel)
   const WthPlan P = wth_plan_of(ctx->cfg.divmax, 1, false, ctx->L.NK);
   const size_t chunk = epoch_chunk(ctx, n_epoch);
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, P.stride * chunk);
+  rc = ensure(ctx, ctx->d_wnodes, P.stride * chunk);
   if (rc) return rc;
   for (size_t c0 = 0; c0 < n_epoch; c0 += chunk) {          // (the scratch is reused in stream order)
     const unsigned E = (unsigned)std::min(chunk, n_epoch - c0);
@@ -823,7 +819,7 @@ static int cell_impl(chomp_ctx* ctx, int which, size_t epoch, double D_z, const 
   // then one slab -- the spectrum table and the hand-over of k_cell to k_cell_deep)
   const int LT = P.LT, split = P.split;
   const size_t sh = P.sh;
-  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, P.doubles(1));
+  rc = ensure(ctx, ctx->d_cnodes, P.doubles(1));
   if (rc) return rc;
   double* state = ctx->d_cnodes + P.state_at;
   int* deep = reinterpret_cast<int*>(ctx->d_cnodes + P.deep_at);
@@ -950,7 +946,7 @@ static int wtheta_rows(chomp_ctx* ctx, const ProjRows& R, int which, size_t epoc
   const int LT = P.LT, nseg = P.nseg;
   const size_t stride = P.stride, pstride = (size_t)L.total;
   const size_t chunk = epoch_chunk(ctx, n_epoch);
-  rc = ensure(ctx, &ctx->d_wnodes, &ctx->cap_wnodes, stride * chunk);
+  rc = ensure(ctx, ctx->d_wnodes, stride * chunk);
   if (rc) return rc;
   double* rec = ctx->d_wnodes + P.rec_at;                   // (of the chunk's first epoch)
   double* segtot = ctx->d_wnodes + P.tot_at;
@@ -1058,7 +1054,7 @@ static int cell_rows(chomp_ctx* ctx, const ProjRows& R, int which, size_t epoch0
   const int LT = P.LT, split = P.split;
   const size_t stride = P.stride, pstride = (size_t)L.total;
   const size_t chunk = epoch_chunk(ctx, n_epoch);
-  rc = ensure(ctx, &ctx->d_cnodes, &ctx->cap_cnodes, P.doubles(chunk));
+  rc = ensure(ctx, ctx->d_cnodes, P.doubles(chunk));
   if (rc) return rc;
   double* pk_tab = ctx->d_cnodes + P.pk_at;                 // (of the chunk's first row)
   double* state = ctx->d_cnodes + P.state_at;
@@ -1316,14 +1312,11 @@ static std::vector<int> blocks_index(size_t n_corr, const size_t* epoch, bool li
     }
   return index;
 }
-// ... in a state's device buffer (grown if need be), through the state's staging block.
-static int blocks_index_upload(chomp_ctx* ctx, int** d_index, size_t* cap_index, StagedBlock& sh,
-                               const std::vector<int>& index) {
-  const int* before = *d_index;
-  const int rc = ensure(ctx, d_index, cap_index, index.size());
+// ... in a state's device buffer (grown if need be), through its staging block.
+static int blocks_index_upload(chomp_ctx* ctx, StagedBuffer<int>& d_index, const std::vector<int>& index) {
+  const int rc = ensure(ctx, d_index, index.size());
   if (rc) return rc;
-  if (*d_index != before) sh.reset();
-  return upload(ctx, *d_index, index.data(), index.size() * sizeof(int), sh);
+  return upload(ctx, d_index, index.data(), index.size() * sizeof(int));
 }
 
 // The pairs of angles of chomp_covariance_ssc, _ssc_cross and _ng: what they refuse ...
@@ -1402,7 +1395,7 @@ int chomp_covariance_table(chomp_ctx* ctx, int which, size_t epoch, double D_z, 
   if (rc) return rc;
   ProjState& P = ctx->proj;
   P.cov_ready = false;
-  if (!P.d_cov) HIPCHK(hipMalloc(&P.d_cov, (size_t)C.total * sizeof(double)));
+  HIPCHK((hipError_t)P.d_cov.once((size_t)C.total));
   const size_t sh = (size_t)(12 * (ctx->L.NK - 1) + ProjLds::doubles(L)) * sizeof(double);
   with_flag(ctx->with_bao, [&](auto BAO) {
     hipLaunchKernelGGL(k_cov_proj_knots<BAO>, dim3((unsigned)C.N), dim3(256), sh, ctx->stream,
@@ -1472,9 +1465,9 @@ int chomp_covariance_cross_stage(chomp_ctx* ctx, int slot, chomp_ctx* src, int w
   const CrossLayout C = make_cross_layout(L.NKT, src->L.stride, L.total);
   if (!X.d || X.C.total != C.total || X.C.htab[1] != C.htab[1] || X.C.ln_K != C.ln_K)
     X.staged[0] = X.staged[1] = false;                   // (another layout: both sides again)
-  { const double* before = X.d;
-    const int rce = ensure(ctx, &X.d, &X.cap, (size_t)C.total); if (rce) return rce;
-    if (X.d != before) X.staged[0] = X.staged[1] = false; }
+  { bool moved = false;
+    const int rce = ensure(ctx, X.d, (size_t)C.total, &moved); if (rce) return rce;
+    if (moved) X.staged[0] = X.staged[1] = false; }
   X.C = C;
   X.ready = false;
   X.staged[slot] = false;
@@ -1603,9 +1596,8 @@ int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size
   }
   BlocksState& B = ctx->blocks;
   B.n_corr = 0;
-  rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)C.total);
-  if (!rc) rc = blocks_index_upload(ctx, &B.d_index, &B.cap_index, ctx->sh_blocks,
-                                    blocks_index(n_corr, epoch, false));
+  rc = ensure(ctx, B.d, n_blocks * (size_t)C.total);
+  if (!rc) rc = blocks_index_upload(ctx, B.d_index, blocks_index(n_corr, epoch, false));
   if (rc) return rc;
   const double *d_theta, *d_poisson;
   double* d_out;
@@ -1690,7 +1682,7 @@ int chomp_covariance_fourier_zbar(chomp_ctx* ctx, const double* z, size_t n_z, d
     }
   }
   const FourierLayout F = make_fourier_layout(c.corr_npoints);
-  { const int rce = ensure(ctx, &S.d, &S.cap, (size_t)F.total); if (rce) return rce; }
+  { const int rce = ensure(ctx, S.d, (size_t)F.total); if (rce) return rce; }
   S.F = F;
   Staging st(ctx, CHOMP_HOST, "covariance_fourier_zbar");
   const double* d_z;
@@ -1827,7 +1819,7 @@ static int kernel_ssc_setup(chomp_ctx* ctx, bool four, double ln_ktheta_min, dou
                                     "for the four windows of a cross block");
   P.ssc_ready = false;
   P.ssc_prep = false;
-  { const int rce = ensure(ctx, &P.d_ssc, &P.cap_ssc, (size_t)S.total); if (rce) return rce; }
+  { const int rce = ensure(ctx, P.d_ssc, (size_t)S.total); if (rce) return rce; }
   HIPCHK(hipMemcpyAsync(P.d_ssc + S.sx, ln_chi, n_sigma * sizeof(double), hipMemcpyHostToDevice,
                         ctx->stream));
   HIPCHK(hipMemcpyAsync(P.d_ssc + S.sy, sigma2, n_sigma * sizeof(double), hipMemcpyHostToDevice,
@@ -1977,8 +1969,7 @@ int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta,
 // The index block of the super-sample calls (with the lists) in their state's buffer.
 static int ssc_blocks_upload_index(chomp_ctx* ctx, size_t n_corr, const size_t* epoch) {
   SscBlocksState& B = ctx->ssc_blocks;
-  return blocks_index_upload(ctx, &B.d_index, &B.cap_index, ctx->sh_ssc_blocks,
-                             blocks_index(n_corr, epoch, true));
+  return blocks_index_upload(ctx, B.d_index, blocks_index(n_corr, epoch, true));
 }
 
 int chomp_covariance_ssc_blocks_range(chomp_ctx* ctx, size_t n_corr, double* info) {
@@ -2055,9 +2046,9 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
                                     "two responses of a cross block");
   SscBlocksState& B = ctx->ssc_blocks;
   B.n_corr = 0;
-  rc = ensure(ctx, &B.d, &B.cap, n_blocks * (size_t)S.total);
-  if (!rc) rc = ensure(ctx, &B.d_kb, &B.cap_kb, 2 * n_blocks * n_pairs * (size_t)NK);
-  if (!rc) rc = ensure(ctx, &B.d_sigma, &B.cap_sigma, 2 * n_blocks * n_sigma);
+  rc = ensure(ctx, B.d, n_blocks * (size_t)S.total);
+  if (!rc) rc = ensure(ctx, B.d_kb, 2 * n_blocks * n_pairs * (size_t)NK);
+  if (!rc) rc = ensure(ctx, B.d_sigma, 2 * n_blocks * n_sigma);
   if (!rc) rc = ssc_blocks_upload_index(ctx, n_corr, epoch);
   if (rc) return rc;
   double* d_ln_chi = B.d_sigma;
@@ -2165,7 +2156,7 @@ int chomp_kernel_ng_setup(chomp_ctx* ctx, double j0_limit, int with_table, doubl
                                     "windows of a cross block");
   P.ng_ready = false;
   P.ng_prep = false;
-  { const int rce = ensure(ctx, &P.d_ng, &P.cap_ng, (size_t)G.total); if (rce) return rce; }
+  { const int rce = ensure(ctx, P.d_ng, (size_t)G.total); if (rce) return rce; }
   hipLaunchKernelGGL(k_ng_prep, dim3(1), dim3(256), 0, ctx->stream, S, G, P.d_ssc, j0_limit,
                      P.d_ng, ng_status(ctx));
   if (with_table) {
@@ -2231,7 +2222,7 @@ int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, si
   const NgPlan plan = ng_plan(ctx->cfg, P.L);
   const NgLayout& G = plan.G;
   const NgTriLayout T = make_ng_tri_layout((int)n_tri);
-  { const int rce = ensure(ctx, &P.d_ng_tri, &P.cap_ng_tri, (size_t)T.total); if (rce) return rce; }
+  { const int rce = ensure(ctx, P.d_ng_tri, (size_t)T.total); if (rce) return rce; }
   Staging st(ctx, CHOMP_HOST, "covariance_ng");
   PairArrays d;
   const double* d_tri_in;

@@ -724,11 +724,10 @@ __global__ __launch_bounds__(256) void k_ssc_outer(chomp_config cfg, double area
 // grid dimension.  The index block of a call, ints:
 //   epoch[n_corr] | (i, j)[n_blocks] | the diagonal blocks [n_corr] | the cross blocks [n_blocks - n_corr].
 struct SscBlocksState {
-  double* d = nullptr;     // n_blocks slabs of S.total doubles
-  double* d_kb = nullptr;  // the k_b knots, then their levels: [n_blocks][n_pairs][kernel_npoints] each
-  double* d_sigma = nullptr;   // the blocks' sigma^2 knots (ln chi, then sigma^2) on their way into the slabs
-  int* d_index = nullptr;  // the index block
-  size_t cap = 0, cap_kb = 0, cap_sigma = 0, cap_index = 0;
+  DeviceBuffer<double> d;  // n_blocks slabs of S.total doubles
+  DeviceBuffer<double> d_kb;   // the k_b knots, then their levels: [n_blocks][n_pairs][kernel_npoints] each
+  DeviceBuffer<double> d_sigma;   // the blocks' sigma^2 knots (ln chi, then sigma^2) on their way into the slabs
+  StagedBuffer<int> d_index;   // the index block
   SscLayout S;
   size_t n_corr = 0;       // correlations of the last call (0: none yet)
   size_t n_pairs = 0;      // ... and its pairs of angles
@@ -1201,8 +1200,7 @@ inline FourierLayout make_fourier_layout(int N) {
   return F;
 }
 struct FourierState {
-  double* d = nullptr;     // the block of FourierLayout
-  size_t cap = 0;          // doubles allocated at d
+  DeviceBuffer<double> d;  // the block of FourierLayout
   FourierLayout F;
   bool zbar = false;       // the scalars of the four pairs (chomp_covariance_fourier_zbar) valid
   bool ready = false;      // ... and the four tables with their splines (chomp_covariance_fourier_table)

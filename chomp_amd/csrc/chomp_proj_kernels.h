@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "chomp_buffers.h"
 #include "chomp_power_kernels.h"
 
 namespace chomp {
@@ -86,51 +87,23 @@ struct ProjState {
   bool de = false;         // the set-up's cosmology has w0-wa dark energy (its table: chomp_ctx::de_proj)
   ProjLayout L;
   ProjDev host;            // host copy of the scalars (refreshed by kernel_info)
-  ProjDev* d_pd = nullptr;
-  ProjDev* d_pd_init = nullptr;   // the block as the host prepared it (the device fills d_pd in)
-  double* d_tab = nullptr;
-  size_t cap_tab = 0;      // doubles allocated at d_tab
+  DeviceBuffer<ProjDev> d_pd;
+  DeviceBuffer<ProjDev> d_pd_init;   // the block as the host prepared it (the device fills d_pd in)
+  DeviceBuffer<double> d_tab;
   size_t pp_total = 0;     // doubles of tabulated redshift distributions behind the tables
   bool cov_ready = false;  // covariance table (chomp_covariance_table) valid
-  double* d_cov = nullptr;
+  DeviceBuffer<double> d_cov;
   bool ssc_prep = false;   // sigma^2 spline and z_bar_NG (chomp_kernel_ssc_setup) valid
   bool ssc_ready = false;  // ... and the kernel_ssc table with its bicubic
   int ssc_ns = 0;          // sigma^2 knots of that set-up
-  double* d_ssc = nullptr;
-  size_t cap_ssc = 0;      // doubles allocated at d_ssc
+  DeviceBuffer<double> d_ssc;
   bool ssc_four = false;   // that state is of the four windows of a cross block (chomp_kernel_ssc_setup_cross)
   bool ng_four = false;    // ... and so is the kernel_NG state built from it
   bool ng_prep = false;    // kernel_NG scalars and knots (chomp_kernel_ng_setup) valid
   bool ng_ready = false;   // ... and the kernel_NG table with its log-offset bicubic
-  double* d_ng = nullptr;
-  size_t cap_ng = 0;       // doubles allocated at d_ng
-  double* d_ng_tri = nullptr;   // the I_0^4 table of the last chomp_covariance_ng and its bicubic
-  size_t cap_ng_tri = 0;
+  DeviceBuffer<double> d_ng;
+  DeviceBuffer<double> d_ng_tri;   // the I_0^4 table of the last chomp_covariance_ng and its bicubic
 };
-inline void proj_free(ProjState& p) {
-  if (p.d_pd) (void)hipFree(p.d_pd);
-  if (p.d_pd_init) (void)hipFree(p.d_pd_init);
-  if (p.d_tab) (void)hipFree(p.d_tab);
-  if (p.d_cov) (void)hipFree(p.d_cov);
-  if (p.d_ssc) (void)hipFree(p.d_ssc);
-  p.d_ssc = nullptr;
-  p.cap_ssc = 0;
-  p.ssc_ready = false;
-  p.ssc_prep = false;
-  if (p.d_ng) (void)hipFree(p.d_ng);
-  if (p.d_ng_tri) (void)hipFree(p.d_ng_tri);
-  p.d_ng = p.d_ng_tri = nullptr;
-  p.cap_ng = p.cap_ng_tri = 0;
-  p.ng_ready = false;
-  p.ng_prep = false;
-  p.d_pd = nullptr;
-  p.d_pd_init = nullptr;
-  p.d_tab = nullptr;
-  p.d_cov = nullptr;
-  p.ready = false;
-  p.me_ready = false;
-  p.cov_ready = false;
-}
 
 // The projection set-ups of chomp_kernel_setup_sets / chomp_kernel_setup_pairs, beside ProjState
 // (which they never touch): n ProjDev blocks and n slabs of L.total doubles, set s at d_pd[s] and d_tab + s * L.total.
@@ -139,10 +112,9 @@ struct ProjSets {
   size_t n = 0;            // sets of the last set-up of sets (0: none yet)
   ProjLayout L;
   ProjDev host;            // what the sets share, as the host prepared it (ln k theta range, order)
-  ProjDev* d_pd = nullptr;
-  ProjDev* d_pd_init = nullptr;   // the blocks as the host prepared them (the device fills d_pd in)
-  double* d_tab = nullptr;
-  size_t cap_pd = 0, cap_pd_init = 0, cap_tab = 0;
+  DeviceBuffer<ProjDev> d_pd;
+  StagedBuffer<ProjDev> d_pd_init;   // the blocks as the host prepared them (the device fills d_pd in)
+  DeviceBuffer<double> d_tab;
 };
 
 // ---------------------------------------------------------------------------
@@ -2706,8 +2678,7 @@ inline CrossLayout make_cross_layout(int N, int h_stride, int p_total) {
   return C;
 }
 struct CrossState {
-  double* d = nullptr;     // the block of CrossLayout
-  size_t cap = 0;          // doubles allocated at d
+  DeviceBuffer<double> d;  // the block of CrossLayout
   CrossLayout C;
   bool staged[2] = {false, false};   // slot holds a snapshot (chomp_covariance_cross_stage)
   int which[2] = {0, 0};   // ... of this spectrum
@@ -2983,9 +2954,8 @@ constexpr int kBlocksScalDa = 6, kBlocksScalDb = 7;
 // The state of chomp_covariance_blocks, beside ProjState and CrossState (which it never touches).
 // The buffers are kept across calls and only grow.
 struct BlocksState {
-  double* d = nullptr;     // n_blocks slabs of C.total doubles
-  int* d_index = nullptr;  // the index block
-  size_t cap = 0, cap_index = 0;
+  DeviceBuffer<double> d;  // n_blocks slabs of C.total doubles
+  StagedBuffer<int> d_index;   // the index block
   CrossLayout C;
   size_t n_corr = 0;       // correlations of the last call (0: none yet)
 };
