@@ -5,7 +5,10 @@ chomp_math.h, through the product's whole header chain from chomp_cov_kernels.h 
 libdevproj.so (devproj.hip: the moment route of w(theta), the bicubic tables and HaloFit's
 quintic derivatives of chomp_proj_kernels.h / chomp_cov_kernels.h) and libdevpower.so
 (devpower.hip: the spectrum evaluator and the Stage E launch shapes of chomp_power_kernels.h,
-the spectrum table and its stencil of chomp_proj_kernels.h).  Each harness is
+the spectrum table and its stencil of chomp_proj_kernels.h) and libdevcell.so (devcell.hip: the
+C_l route -- the node table, k_cell, k_cell4, the hand-over, k_cell_deep and their _epochs / _sets
+forms with the Romberg levels as arguments -- the plan of its work buffer, and the parallel
+not-a-knot spline build in the block shapes the product calls it in).  Each harness is
 compiled with the product's compiler flags (imported from chomp_amd._lib, never copied) and
 rebuilt only when the content of what IT is compiled from changes, as _lib.py does for the
 product library: its own source, .so and content hash, the hash over every product header it
@@ -53,7 +56,8 @@ class Harness:
 
 
 HARNESSES = {"devcheck": Harness("devcheck"), "devphys": Harness("devphys"),
-             "devproj": Harness("devproj"), "devpower": Harness("devpower")}
+             "devproj": Harness("devproj"), "devpower": Harness("devpower"),
+             "devcell": Harness("devcell")}
 # the first harness under its earlier names
 SRC = HARNESSES["devcheck"].src
 SO = HARNESSES["devcheck"].so
@@ -127,8 +131,22 @@ POWER_ENTRY_POINTS = {
     "dw_ptab": _S[1:] + [_i, _p],
     "dw_stencil": _S[1:] + [_i, _p, _p, _p, _i, _p],
 }
+# ... and for the sixth (devcell.hip; the fifth, devaim.hip, is registered by its test module)
+_ll, _llp, _u = ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong), ctypes.c_uint
+CELL_ENTRY_POINTS = {
+    "dl_romberg_dump": [], "dl_ptab_n": [], "dl_pd_inputs": [], "dl_constants": [_ip],
+    "dl_proj_layout": [_i, _i, _i, _ip],
+    "dl_plan": [_i, _i, _i, _i, _i, _ll, _ll, _i, _llp],
+    "dl_nodes": [_i, _i, _p, _p, _d, _i, _i, _ll, _i, _p, _ip],
+    "dl_nodes_sets": [_i, _i, _i, _p, _p, _p, _i, _i, _p],
+    "dl_spline": [_i, _p, _p, _i, _i, _u, _i, _p],
+    "dl_logs": [_p, _i, _p],
+    "dl_cell": _S + [_i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _d, _d, _i, _i, _i, _i, _i, _i, _i, _i,
+                     _p, _p, _p, _p],
+}
 ALL_ENTRY_POINTS = {"devcheck": ENTRY_POINTS, "devphys": PHYS_ENTRY_POINTS,
-                    "devproj": PROJ_ENTRY_POINTS, "devpower": POWER_ENTRY_POINTS}
+                    "devproj": PROJ_ENTRY_POINTS, "devpower": POWER_ENTRY_POINTS,
+                    "devcell": CELL_ENTRY_POINTS}
 # dc_quad shapes
 SHAPE = {"group1": 0, "group2": 1, "group4": 2, "group8": 3, "group16": 4,
          "group1_nf2": 5, "group4_nf2": 6, "group4_unroll4": 7, "group4_fast4": 8,
@@ -178,7 +196,8 @@ def build(force=False, harness="devcheck"):
 
 
 VOID = {"devcheck": ("dc_fma_k_constants", "dc_gl16"), "devphys": ("dp_epoch_offsets",),
-        "devproj": ("dj_quintic_grid",), "devpower": ("dw_wave_bits",)}
+        "devproj": ("dj_quintic_grid",), "devpower": ("dw_wave_bits",),
+        "devcell": ("dl_constants",)}
 
 
 def load(harness="devcheck"):

@@ -1,10 +1,10 @@
 """The device harnesses (tests/devcheck: devcheck.hip, the fp64 primitives and the wavefront
 Romberg; devphys.hip, the halo-model physics; devproj.hip, the moment route of w(theta), the
 bicubic tables and the quintic derivatives; devpower.hip, the spectrum evaluator and the Stage E
-launch shapes) compile for
+launch shapes; devcell.hip, the C_l route and the parallel spline build) compile for
 gfx950 against the current headers and export every entry point the GPU tests
 (test_gpu_devmath.py, test_gpu_romberg.py; test_gpu_devphys.py; test_gpu_devproj.py;
-test_gpu_devpower.py) use.  No GPU is needed: hipcc cross-compiles.  This
+test_gpu_devpower.py; test_gpu_devcell.py) use.  No GPU is needed: hipcc cross-compiles.  This
 keeps the harness from rotting when a header's signature changes in a change developed without
 a GPU."""
 import ctypes
@@ -181,6 +181,58 @@ def test_devpower_compiles_and_exports():
         assert v[13] % 8 == 0 and 0 <= v[13] - (v[12] + 8) < 8
 
 
+@pytest.mark.skipif(not devcheck_build.have_hipcc(), reason="hipcc is not installed")
+def test_devcell_compiles_and_exports():
+    H = devcheck_build.HARNESSES["devcell"]
+    others = [devcheck_build.HARNESSES[n] for n in ("devcheck", "devphys", "devproj", "devpower")]
+    for o in others:
+        devcheck_build.build(harness=o.name)
+    stamps = [os.stat(o.so).st_mtime_ns for o in others]
+    path = devcheck_build.build(harness="devcell")
+    assert path == H.so and all(path != o.so for o in others)
+    stamp = os.stat(path).st_mtime_ns
+    assert devcheck_build.build(harness="devcell") == path
+    assert os.stat(path).st_mtime_ns == stamp                 # (second call: nothing to do)
+    assert [os.stat(o.so).st_mtime_ns for o in others] == stamps   # (the others: left alone)
+    with open(H.hash) as f:
+        assert f.read().strip() == devcheck_build.source_hash("devcell")
+    L = ctypes.CDLL(path)
+    for name in devcheck_build.CELL_ENTRY_POINTS:
+        assert hasattr(L, name), name
+    assert set(devcheck_build.VOID["devcell"]) <= set(devcheck_build.CELL_ENTRY_POINTS)
+    assert devcheck_build.ALL_ENTRY_POINTS["devcell"] is devcheck_build.CELL_ENTRY_POINTS
+    assert all(n.startswith("dl_") for n in devcheck_build.CELL_ENTRY_POINTS)
+    # every entry point the tests name is declared (and so exported, above)
+    here = os.path.dirname(os.path.abspath(__file__))
+    for test in ("test_gpu_devcell.py", "test_devcell_cpu.py"):
+        with open(os.path.join(here, test)) as f:
+            named = set(re.findall(r"\b(dl_[a-z0-9_]+)\b", f.read()))
+        assert named and named <= set(devcheck_build.CELL_ENTRY_POINTS), (test, named)
+    # the package never loads it
+    from chomp_amd import _lib
+    assert not any("devcell" in src for src, _ in _lib.UNITS)
+    # its hash covers the header chain and the plumbing it shares with devpower.hip
+    for name in ("devcell", "devpower"):
+        base = [os.path.basename(p) for p in devcheck_build.HARNESSES[name].headers]
+        assert "power_setup.h" in base and "epoch_fill.h" in base, name
+    base = [os.path.basename(p) for p in H.headers]
+    for need in ("chomp_cov_kernels.h", "chomp_proj_kernels.h", "chomp_power_kernels.h",
+                 "chomp_halo_kernels.h", "chomp_mass_kernels.h", "chomp_romberg.h",
+                 "chomp_math.h", "special_tables.h", "chomp_mi355x.h"):
+        assert need in base, need
+    # the getters run on the host: the constants of the headers
+    with open(os.path.join(_lib.CSRC, "chomp_proj_kernels.h")) as f:
+        text = f.read()
+    k = (ctypes.c_int * 5)()
+    L.dl_constants(k)
+    for i, name in enumerate(("kCellTabLevel", "kCellSplitLevel", "kCell4Level", "kCellDeepThreads")):
+        assert k[i] == int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1)), name
+    assert k[4] == 160 * 1024 - 4096
+    with open(os.path.join(_lib.CSRC, "chomp_romberg.h")) as f:
+        assert L.dl_romberg_dump() == int(re.search(r"constexpr int kRombergDump = (\d+);", f.read()).group(1))
+    assert L.dl_ptab_n() == 8192 and L.dl_pd_inputs() == 8
+
+
 def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
     """Each harness's hash covers the product headers it includes, transitively: devphys.hip
     and devproj.hip reach chomp_math.h through chomp_cov_kernels.h, and a change in any header of
@@ -202,7 +254,8 @@ def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
     os.makedirs(root / "tests" / "devcheck")
     for H in devcheck_build.HARNESSES.values():
         shutil.copy(H.src, root / "tests" / "devcheck")
-    shutil.copy(os.path.join(devcheck_build.DIR, "epoch_fill.h"), root / "tests" / "devcheck")
+    for shared in ("epoch_fill.h", "power_setup.h"):
+        shutil.copy(os.path.join(devcheck_build.DIR, shared), root / "tests" / "devcheck")
     copies = {n: devcheck_build.Harness(n) for n in devcheck_build.HARNESSES}
     for H in copies.values():
         H.src = str(root / "tests" / "devcheck" / (H.name + ".hip"))
@@ -226,9 +279,16 @@ def test_harness_hash_covers_every_product_header(tmp_path, monkeypatch):
     assert own["devproj"] != last["devproj"]
     assert own["devphys"] == last["devphys"] and own["devcheck"] == last["devcheck"]
     assert own["devpower"] == last["devpower"]
-    # the shared epoch filler changes the two harnesses that include it, and only them
+    # the shared epoch filler changes the harnesses that include it, and only them
     with open(root / "tests" / "devcheck" / "epoch_fill.h", "a") as f:
         f.write("// changed\n")
     fill = {n: devcheck_build.source_hash(n) for n in copies}
     assert fill["devpower"] != own["devpower"] and fill["devphys"] != own["devphys"]
+    assert fill["devcell"] != own["devcell"]
     assert fill["devproj"] == own["devproj"] and fill["devcheck"] == own["devcheck"]
+    # ... and the plumbing devpower.hip and devcell.hip share those two
+    with open(root / "tests" / "devcheck" / "power_setup.h", "a") as f:
+        f.write("// changed\n")
+    plumb = {n: devcheck_build.source_hash(n) for n in copies}
+    assert plumb["devpower"] != fill["devpower"] and plumb["devcell"] != fill["devcell"]
+    assert all(plumb[n] == fill[n] for n in ("devphys", "devproj", "devcheck"))
