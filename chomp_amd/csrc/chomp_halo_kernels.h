@@ -496,7 +496,9 @@ __global__ __launch_bounds__(256) void k_mass_nodes(
   if (do_nodes)
     copy_doubles(reinterpret_cast<double*>(&S), reinterpret_cast<const double*>(sici_g),
                  (int)(sizeof(SiCiTab) / sizeof(double)));
-  __syncthreads();
+  // (no barrier here: mass_setup_block stages the nu table and the ln M grid, which depend on
+  //  nothing in E, and then has the block's first one -- the record, the Si/Ci tables and the
+  //  two tables arrive in one round trip instead of two)
   MassLds M;
   M.carve(sm, L.NM);
   const int n_search = (int)(search[(e * 2 + 0) * 2 + 1] + search[(e * 2 + 1) * 2 + 1]);
@@ -572,31 +574,83 @@ __device__ __forceinline__ int group_fb(int group) {
 __host__ __device__ inline int finalize_lds_doubles(int NK) { return (1 + kFamilies + 36) * NK; }
 // through: the knot values were (in part) written by other blocks of this launch, with agent
 // scope: they are read with agent-scope loads, and the caller needs no fence in front.
+// FinalizeEarly: everything the block reads from global memory on the way, fetched by
+// finalize_fetch in ONE round of loads -- by a caller that can issue them beside loads it waits
+// for anyway, and only where no other block of the launch writes any of it (nothing listed).
+struct FinalizeEarly {
+  double nbr, rho_bar;     // n_bar / rho_bar, rho_bar
+  double knot;             // knot `lane` of the family this wavefront builds in round 0
+  double amp2, same;       // thread 0: the Stage-E record
+  unsigned word;           // thread 0: the epoch's status word
+};
+__device__ __forceinline__ FinalizeEarly finalize_fetch(const TabLayout& L,
+                                                        const Epoch* epochs, const double* tab,
+                                                        int e, unsigned fam_mask,
+                                                        const unsigned* status) {
+  const double* t = tab + (size_t)e * L.stride;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  FinalizeEarly r;
+  r.nbr = t[L.off_misc];
+  r.rho_bar = epochs[e].rho_bar;
+  r.knot = 0.0;
+  if (wave < 4 && ((fam_mask >> wave) & 1u) && lane < L.NK) r.knot = t[L.off_knot[wave] + lane];
+  r.amp2 = r.same = 0.0;
+  r.word = 0u;
+  if (threadIdx.x == 0) {
+    const Epoch& E = epochs[e];
+    r.amp2 = E.amp * E.sigma_norm * E.sigma_norm;
+    r.same = (e > 0 && same_cosmology(E, epochs[e - 1])) ? 1.0 : 0.0;
+    r.word = __hip_atomic_load(&status[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return r;
+}
+// FAST: the finalisation the headline chain ends with (k_halo_knots_fast's instance without HOD
+// integrands, nothing listed): the early values, the early word for the host and the
+// one-wavefront builds.  Every other caller compiles the routine as it was -- the instances that
+// evaluate listed knots run at their register cap, and the lean one took 64 more bytes of scratch
+// per lane, 4 us of its 65, with the two builders and the early values inlined.
+template <bool FAST = false>
 __device__ __forceinline__ void halo_finalize_block(const chomp_config& cfg, const TabLayout& L,
                                                     Epoch* __restrict__ epochs,
                                                     double* __restrict__ tab, int e,
                                                     unsigned fam_mask,
                                                     unsigned* __restrict__ status, double* sm,
-                                                    bool through = false) {
+                                                    bool through = false,
+                                                    const FinalizeEarly* early = nullptr) {
   const int NK = L.NK;
+  if (!FAST) early = nullptr;
   double* xk = sm;                      // [NK]
   double* yk = xk + NK;                 // [kFamilies][NK]
   double* work = yk + kFamilies * NK;   // [4][9 NK]
   double* t = tab + (size_t)e * L.stride;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const double nbr = t[L.off_misc];                    // n_bar / rho_bar
-  const double rho_bar = epochs[e].rho_bar;
+  const double nbr = early ? early->nbr : t[L.off_misc];                    // n_bar / rho_bar
+  const double rho_bar = early ? early->rho_bar : epochs[e].rho_bar;
   for (int i = threadIdx.x; i < NK; i += blockDim.x)
     xk[i] = linspace_at(log(cfg.k_min), log(cfg.k_max), NK, i);
   if (threadIdx.x == 0) {
     // Stage-E record: amplitude of Delta^2 and "same cosmology as the previous epoch"
-    const Epoch& E = epochs[e];
-    t[L.off_misc + 1] = E.amp * E.sigma_norm * E.sigma_norm;
-    t[L.off_misc + 2] = (e > 0 && same_cosmology(E, epochs[e - 1])) ? 1.0 : 0.0;
+    if (early) {
+      t[L.off_misc + 1] = early->amp2;
+      t[L.off_misc + 2] = early->same;
+    } else {
+      const Epoch& E = epochs[e];
+      t[L.off_misc + 1] = E.amp * E.sigma_norm * E.sigma_norm;
+      t[L.off_misc + 2] = (e > 0 && same_cosmology(E, epochs[e - 1])) ? 1.0 : 0.0;
+    }
     epochs[e].n_bar_over_rho_bar = nbr;                // halo.py:692-700
     epochs[e].n_bar = nbr * rho_bar;
   }
   const int rounds = (fam_mask >> 4) ? 2 : 1;          // (families 4, 5 = pp_gg, I_1^2: round 1)
+  // With NK <= 64 a family's build takes its wavefront and no block barrier between its steps
+  // (spline_build_pcr_wave): one barrier in front of a round's builds, one behind them.
+  const bool wave_build = FAST && NK <= kSplineWaveMax;
+  // With the early word and one round, the word for the host is known once the families are
+  // normalised: early->word | this block's own non-finite bit -- nobody else writes the epoch's
+  // word during such a launch.  Posted there, its way to the host runs under the builds and not
+  // at the launch's end.
+  const bool post_early = early != nullptr && rounds == 1 && L.h_status != nullptr;
+  __shared__ unsigned bad_sh[4];
   for (int round = 0; round < rounds; ++round) {
     const int f = wave + 4 * round;                      // (wavefronts beyond the fourth only keep
     const bool active = wave < 4 && f < kFamilies && ((fam_mask >> f) & 1u);   //  the barriers company)
@@ -611,19 +665,37 @@ __device__ __forceinline__ void halo_finalize_block(const chomp_config& cfg, con
       for (int i = lane; i < NK; i += 64) {
         const double raw = through ? __hip_atomic_load(&t[L.off_knot[f] + i], __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_AGENT)
-                                   : t[L.off_knot[f] + i];
+                                   : (early && round == 0 && i == lane ? early->knot
+                                                                       : t[L.off_knot[f] + i]);
         const double v = raw * scale;
         yk[f * NK + i] = v;
         t[L.off_knot[f] + i] = v;
         bad = bad || !(fabs(v) <= 1.79769313486231570815e308);   // NaN or infinity
       }
-      if (__any(bad) && lane == 0) atomicOr(&status[e], kStNonfinite);
+      bad = __any(bad);
+      if (bad && lane == 0) atomicOr(&status[e], kStNonfinite);
+      if (post_early && lane == 0) bad_sh[wave] = bad ? kStNonfinite : 0u;
+    } else if (post_early && wave < 4 && lane == 0) {
+      bad_sh[wave] = 0u;
     }
-    __syncthreads();
+    __syncthreads();                     // (xk stands; bad_sh)
+    if (post_early && threadIdx.x == 0) {
+      const unsigned w = early->word | bad_sh[0] | bad_sh[1] | bad_sh[2] | bad_sh[3];
+      __hip_atomic_store(&L.h_status[e], ((unsigned long long)L.h_seq << 32) | (unsigned long long)w,
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     const int fs = active ? f : 0;
-    spline_build_pcr(xk, yk + fs * NK, NK, t + L.off_kpp[fs], work + (wave & 3) * 9 * NK, lane, 64,
-                     active);
+    if (wave_build) {
+      if (active)
+        spline_build_pcr_wave(xk, yk + fs * NK, NK, t + L.off_kpp[fs], work + (wave & 3) * 9 * NK, lane);
+      // (whoever goes on in this block may use the LDS again; round 1 writes yk and work anew)
+      __syncthreads();
+    } else {
+      spline_build_pcr(xk, yk + fs * NK, NK, t + L.off_kpp[fs], work + (wave & 3) * 9 * NK, lane, 64,
+                       active);
+    }
   }
+  if (post_early) return;
   // The epoch's status word is final here (every kernel of the set-up has had its say, this
   // block its own behind the barriers above): mirrored into the pinned host words, so that a
   // status post behind the set-up puts NOTHING on the stream: the word arrives with the
@@ -1641,16 +1713,26 @@ __device__ __forceinline__ void deep_fast_body(
   const int NK = L.NK;
   const int tid = threadIdx.x;
   const int wv = tid >> 6, ln = tid & 63;
+  // (what the finalisation of epoch blockIdx.x reads, in the same round of loads as the list's
+  //  counts: with an empty list -- the headline chain -- it is all final, and the block goes from
+  //  one round trip straight into the builds; with knots listed the values are dropped, the
+  //  finalising block reads them once the knots are in)
+  //  (SELF only: see halo_finalize_block)
+  const bool finalizes = round == 0 && !from_eval && (int)blockIdx.x < n_epoch;
+  FinalizeEarly early = {};
+  if constexpr (SELF)
+    if (finalizes) early = finalize_fetch(L, epochs_rw, tab, (int)blockIdx.x, fam_mask, status);
   const int count_front = pending[0], count = count_front + pending[2];
   // (with an empty list no block of this launch writes a knot: every value the finalisation
   //  reads comes from the previous launch, and no fence is needed)
   const bool fences = count != 0;
-  if (round == 0 && !from_eval && (int)blockIdx.x < n_epoch) {
+  if (finalizes) {
     if (count == 0) {
       // (nothing listed anywhere: every epoch's counter stands at its token, and block e
       //  finalises epoch e without the atomic's round trip -- the headline chain's last launch
       //  is nothing but this)
-      halo_finalize_block(cfg, L, epochs_rw, tab, (int)blockIdx.x, fam_mask, status, sm, false);
+      halo_finalize_block<SELF>(cfg, L, epochs_rw, tab, (int)blockIdx.x, fam_mask, status, sm, false,
+                                &early);
     } else {
       deep_arrive(cfg, L, epochs_rw, tab, (int)blockIdx.x, fam_mask, status, npend, fences, &last_sh, sm,
                   kArriveNothing);

@@ -804,6 +804,42 @@ __device__ __forceinline__ void spline_build_pcr(const double* x, const double* 
   __syncthreads();
 }
 
+// The same build by ONE wavefront, n <= 64: row `lane` per lane, the same spline_row /
+// pcr_step / spline_coef calls on the same arguments in the same order, hence the same
+// coefficients bit for bit -- and no block barrier: a wavefront's LDS accesses are carried out
+// in program order, so between two steps it only has to keep the compiler from moving them
+// (wave_lds_order).  Wavefronts of a block may each build a system of their own side by side, or
+// do something else meanwhile; the caller orders the result against the OTHER wavefronts.
+// w: 9 n doubles of LDS.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+constexpr int kSplineWaveMax = 64;
+__device__ __forceinline__ void spline_build_pcr_wave(const double* x, const double* y, int n,
+                                                      double* c, double* w, int lane) {
+  double *a0 = w, *b0 = w + n, *c0 = w + 2 * n, *d0 = w + 3 * n;
+  double *a1 = w + 4 * n, *b1 = w + 5 * n, *c1 = w + 6 * n, *d1 = w + 7 * n;
+  double* sl = w + 8 * n;
+  const bool row = lane < n;
+  wave_lds_order();                        // (x, y: written by this wavefront, or ordered by the caller)
+  if (row) spline_row(x, y, n, lane, &a0[lane], &b0[lane], &c0[lane], &d0[lane]);
+  wave_lds_order();
+  for (int s = 1; s < n; s *= 2) {
+    if (row) pcr_step(n, lane, s, a0, b0, c0, d0, a1, b1, c1, d1);
+    wave_lds_order();
+    double* t;
+    t = a0; a0 = a1; a1 = t;
+    t = b0; b0 = b1; b1 = t;
+    t = c0; c0 = c1; c1 = t;
+    t = d0; d0 = d1; d1 = t;
+  }
+  if (row) sl[lane] = d0[lane] / b0[lane];
+  wave_lds_order();
+  if (lane < n - 1) spline_coef(x, y, sl, lane, c);
+  wave_lds_order();
+}
+
 // nu(M) = (delta_c / sigma(R(M)))^2, cosmology.py:662-699.
 template <int NW, int UNROLL = 1, bool BAO = false>
 __device__ __forceinline__ double nu_of_mass_block(const Epoch& E, const double* snode,
@@ -1296,17 +1332,27 @@ __device__ __forceinline__ void mass_setup_block(
   copy_doubles(M.y_nu, t + L.off_nu, NM);
   copy_doubles(M.gl, gl16, 32);
   __syncthreads();
-  {   // nu(ln M) on threads 0..127, ln M(nu) on threads 128..255, in lockstep
+  // The record's fields other than m_star need no spline: with NM <= 64 the two builds take one
+  // wavefront each and no block barrier (spline_build_pcr_wave), and the block's third wavefront
+  // fills those fields in beside them; m_star follows behind the one barrier that ends the builds.
+  const bool wave_build = NM <= kSplineWaveMax;
+  const int par_wave = wave_build ? 2 : 0;
+  if (wave_build) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave < 2)     // nu(ln M) on wavefront 0, ln M(nu) on wavefront 1
+      spline_build_pcr_wave(wave == 0 ? M.x_lnm : M.y_nu, wave == 0 ? M.y_nu : M.x_lnm, NM,
+                            wave == 0 ? M.c_nu : M.c_lnm, M.work + wave * 9 * NM, lane);
+  } else {   // nu(ln M) on threads 0..127, ln M(nu) on threads 128..255, in lockstep
     const int sys = threadIdx.x >> 7, tid = threadIdx.x & 127;
     spline_build_pcr(sys == 0 ? M.x_lnm : M.y_nu, sys == 0 ? M.y_nu : M.x_lnm, NM,
                      sys == 0 ? M.c_nu : M.c_lnm, M.work + sys * 9 * NM, tid, 128, true);
   }
-  if (threadIdx.x < 64) {
+  if ((int)(threadIdx.x >> 6) == par_wave) {
     // (one wavefront: the five Tinker parameters -- a look-up in the 9-row table from global
-    //  memory and a power of 1 + z each, mass_function.py:547-564 -- in five lanes at once, m_star
-    //  in a sixth: done one after the other by thread 0 they were 6.7 us of every block's chain
-    //  on a Tinker set-up (per-block time stamps).  Same calls on the same arguments.)
-    const int lane = (int)threadIdx.x;
+    //  memory and a power of 1 + z each, mass_function.py:547-564 -- in five lanes at once:
+    //  done one after the other by thread 0 they were, with m_star, 6.7 us of every block's
+    //  chain on a Tinker set-up (per-block time stamps).  Same calls on the same arguments.)
+    const int lane = (int)(threadIdx.x & 63);
     const double mf_delta_v = (hp.delta_v == -1.0) ? E.delta_v : hp.delta_v;
     double mine = 0.0;
     if (mf_kind == CHOMP_MF_TINKER && lane < 5) {
@@ -1316,17 +1362,15 @@ __device__ __forceinline__ void mass_setup_block(
       const double ex = lane == 1 ? 0.20 : (lane == 2 ? -0.01 : (lane == 3 ? -0.08 : 0.27));
       if (lane > 0) mine *= pow(opz, ex);
     }
-    if (lane == 5) mine = exp(spline_eval(M.y_nu, M.c_lnm, NM, 1.0));   // :223
     const double t_alpha = readlane_d(mine, 0), t_beta = readlane_d(mine, 1);
     const double t_gamma = readlane_d(mine, 2), t_phi = readlane_d(mine, 3);
-    const double t_eta = readlane_d(mine, 4), m_star = readlane_d(mine, 5);
+    const double t_eta = readlane_d(mine, 4);
     if (lane == 0) {
       E.ln_mass_min = ln_mass_min;
       E.ln_mass_max = ln_mass_max;
       E.n_search = n_search;
       E.nu_min = 1.001 * M.y_nu[0];                       // mass_function.py:212-213
       E.nu_max = 0.999 * M.y_nu[NM - 1];
-      E.m_star = m_star;
       E.stq = hp.stq;
       E.st_a = hp.st_little_a;
       E.mf_delta_v = mf_delta_v;
@@ -1346,6 +1390,8 @@ __device__ __forceinline__ void mass_setup_block(
       }
     }
   }
+  if (wave_build) __syncthreads();        // (the splines stand: spline_build_pcr ends with one)
+  if (threadIdx.x == 0) E.m_star = exp(spline_eval(M.y_nu, M.c_lnm, NM, 1.0));   // :223
   __syncthreads();
   // Normalisations (mass_function.py:225-241; Tinker: bias only, :532-545).  The
   // reference integrates in linear nu with Romberg to rtol 1.48e-8 (8193 nodes);
