@@ -152,6 +152,7 @@ EXPORTS = [
     "chomp_tri_triple",
     "chomp_kernel_ng_setup", "chomp_kernel_ng_raw", "chomp_kernel_ng_eval",
     "chomp_covariance_ng",
+    "chomp_cov_ng_blocks", "chomp_cov_ng_blocks_table", "chomp_cov_ng_blocks_plan",
     "chomp_covariance_cross_range", "chomp_kernel_ssc_setup_cross", "chomp_covariance_ssc_cross",
     "chomp_set_general_profile", "chomp_y_general", "chomp_y_general_table",
     "chomp_halo_normalization",
@@ -489,6 +490,11 @@ def lib():
         L.chomp_kernel_ng_raw.argtypes = [vp, vp, sz, vp]
         L.chomp_kernel_ng_eval.argtypes = [vp, vp, sz, vp]
         L.chomp_covariance_ng.argtypes = [vp, d, vp, sz, d, d, vp, sz, vp, vp, vp]
+        L.chomp_cov_ng_blocks.argtypes = [vp, sz, ctypes.POINTER(sz), d, d, d, d, c_double_p,
+                                                 sz, d, d, vp, sz, vp, i]
+        L.chomp_cov_ng_blocks_table.argtypes = [vp, sz] + [c_double_p] * 6
+        L.chomp_cov_ng_blocks_plan.argtypes = [sz, ctypes.POINTER(sz), sz, sz, sz, sz,
+                                               ctypes.POINTER(sz), ctypes.POINTER(i)]
         L.chomp_xi3d.argtypes = [vp, i, sz, d, d, vp, sz, vp, i]
         L.chomp_xi3d_epochs.argtypes = [vp, i, sz, sz, d, d, vp, sz, vp, i]
         L.chomp_spline_eval.argtypes = [vp, vp, vp, sz, vp, sz, i, vp]
@@ -498,6 +504,29 @@ def lib():
                 getattr(L, name).restype = i
         _lib = L
         return _lib
+
+
+def cov_ng_blocks_plan(n_corr, n_pairs, n_ktheta, n_k, n_tri, epochs=None):
+    """What Context.covariance_ng_blocks keeps on the device for n_corr correlations and n_pairs
+    pairs of angles (chomp_cov_ng_blocks_plan; host arithmetic, no device): (sizes, index) --
+    sizes a dict of element counts (n_blocks, slab, slabs, kb, tri, index), index the call's index
+    block: epoch[n_corr] | (i, j)[n_blocks] | the diagonal blocks | the cross blocks."""
+    n_corr = int(n_corr)
+    sizes = (ctypes.c_size_t * 6)()
+    index = numpy.empty(n_corr + 3 * (n_corr * (n_corr + 1) // 2), dtype=numpy.intc)
+    ep = None
+    if epochs is not None:
+        ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
+        if ep.size != n_corr:
+            raise ValueError("cov_ng_blocks_plan: epochs must be [n_corr]")
+    rc = lib().chomp_cov_ng_blocks_plan(
+        n_corr, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)) if ep is not None else None,
+        int(n_pairs), int(n_ktheta), int(n_k), int(n_tri), sizes,
+        index.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    if rc:
+        raise ValueError("cov_ng_blocks_plan: sizes beyond what covariance_ng_blocks takes")
+    names = ("n_blocks", "slab", "slabs", "kb", "tri", "index")
+    return dict(zip(names, (int(v) for v in sizes))), index
 
 
 def current_device():
@@ -1546,6 +1575,55 @@ class Context(object):
         return self._pair_knots(self._L.chomp_covariance_ng,
                                 (float(area), tri, tri.shape[0], float(tri_k_min), float(tri_k_max)),
                                 theta_a, theta_b, knots)
+
+    def covariance_ng_blocks(self, epochs, ln_ktheta_min, ln_ktheta_max, j0_limit, area, tri_table,
+                             tri_k_min, tri_k_max, theta_a, theta_b=None):
+        """covariance_NG of every block (i, j), i <= j, of len(epochs) correlations for the same
+        pairs of bin centres (chomp_cov_ng_blocks): [n_blocks, n_pairs], the blocks in the
+        row-major order of the upper triangle.  Correlation c is projection set c of the last
+        kernel_setup_pairs; a diagonal block is what kernel_setup + kernel_ssc_setup(with_table=
+        False) + kernel_ng_setup + covariance_ng return, a cross block what two
+        covariance_cross_stage + kernel_ssc_setup(cross=True, with_table=False) + kernel_ng_setup
+        + covariance_ng do, bit for bit.  The term reads no halo epoch: epochs[c] only names the
+        status word ST_COV_NG_DIVMAX of a block (c, j) goes to.  tri_table [N, N]: the I_0^4 table
+        over linspace(ln tri_k_min, ln tri_k_max, N) (a host array), one for all blocks.
+        (theta_a, theta_b): host arrays of one length; or theta_a alone, a contiguous float64
+        torch cuda tensor holding theta_a[n] then theta_b[n], which stays on the device (so does
+        the result)."""
+        ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
+        n_blocks = ep.size * (ep.size + 1) // 2
+        tri = numpy.ascontiguousarray(tri_table, dtype=numpy.float64)
+        if tri.ndim != 2 or tri.shape[0] != tri.shape[1]:
+            raise ValueError("covariance_ng_blocks: the I_0^4 table must be square")
+        pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
+        out = self._run(self._L.chomp_cov_ng_blocks, [pairs],
+                        lambda mem, new, th: (
+                            ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                            float(ln_ktheta_min), float(ln_ktheta_max), float(j0_limit),
+                            float(area), tri.ctypes.data_as(c_double_p), tri.shape[0],
+                            float(tri_k_min), float(tri_k_max), th, _numel(th) // 2,
+                            new((n_blocks, _numel(th) // 2)), mem))[0]
+        self._ng_blocks_pairs = _numel(pairs) // 2       # (what covariance_ng_blocks_table sizes by)
+        return out
+
+    def covariance_ng_blocks_table(self, block, knots=False):
+        """One block of the last covariance_ng_blocks: (info[7] = z_bar_NG, chi(z_bar_NG),
+        growth_factor(z_bar_NG), z_min, z_max, chi_min, chi_max; the kernel_NG table and its
+        Romberg levels, each [kernel_npoints, kernel_npoints]; min(table)); with knots=True also
+        (k_b knots, Romberg levels), each [n_pairs, kernel_npoints]."""
+        n = self.config.kernel_npoints
+        info, tab, lev, mn = numpy.empty(7), numpy.empty((n, n)), numpy.empty((n, n)), numpy.empty(1)
+        kb = kl = None
+        n_pairs = getattr(self, "_ng_blocks_pairs", None) if knots else None
+        if knots and not n_pairs:
+            raise ChompError("covariance_ng_blocks_table before covariance_ng_blocks")
+        if n_pairs is not None:
+            kb, kl = numpy.empty((int(n_pairs), n)), numpy.empty((int(n_pairs), n))
+        self._check(self._L.chomp_cov_ng_blocks_table(
+            self._h, int(block), _ptr(info), _ptr(tab), _ptr(lev), _ptr(mn), _ptr(kb), _ptr(kl)))
+        if n_pairs is None:
+            return info, tab, lev.astype(int), numpy.float64(mn[0])
+        return info, tab, lev.astype(int), numpy.float64(mn[0]), kb, kl.astype(int)
 
     def hod_stats(self, epoch0=0, n=None):
         """[n, 3]: effective bias, effective halo mass, satellite fraction."""

@@ -855,9 +855,11 @@ class CovarianceMulti(Covariance):
         return self.wcovar
 
     # -- every block in one call -------------------------------------------------
-    def _batched_scope(self):
+    def _batched_scope(self, trispectrum=False):
         """ChompScopeError unless get_covariance_batched serves these blocks; no device work.
-        Returns (the correlations, the spectrum's name)."""
+        Returns (the correlations, the spectrum's name).  trispectrum: the caller opted in to the
+        one-halo trispectrum term (get_covariance_batched(trispectrum=True)); without it blocks
+        built with nongaussian_cov are refused as they always were."""
         from . import cosmology
         from . import hod as hod_mod
 
@@ -865,9 +867,16 @@ class CovarianceMulti(Covariance):
             raise _lib.ChompScopeError("get_covariance_batched: %s; use get_covariance" % why)
         blocks = [cov for row in self.covariance_list for cov in row]
         corrs = [row[0].corr_a for row in self.covariance_list]
-        if any(cov.nongaussian_cov for cov in blocks):
+        if not trispectrum and any(cov.nongaussian_cov for cov in blocks):
             refuse("the batch serves the Gaussian and Poisson terms, not the trispectrum "
                    "(nongaussian_cov) or super-sample (ssc_cov) terms")
+        ng = bool(blocks[0].nongaussian_cov)
+        if any(bool(cov.nongaussian_cov) != ng for cov in blocks):
+            refuse("the blocks differ in nongaussian_cov: the batch adds the trispectrum term to "
+                   "every block or to none")
+        if ng and any(cov.halo_tri is not blocks[0].halo_tri for cov in blocks):
+            refuse("the blocks do not share one halo_tri object: the batch takes one I_0^4 table "
+                   "for all of them")
         ssc = bool(blocks[0].ssc_cov)
         if any(bool(cov.ssc_cov) != ssc for cov in blocks):
             refuse("the blocks differ in ssc_cov: the batch adds the super-sample term to every "
@@ -880,13 +889,17 @@ class CovarianceMulti(Covariance):
         centers = [[b.center for b in cov.annular_bins] for cov in blocks]
         if any(c != centers[0] for c in centers) or any(cov.area != blocks[0].area for cov in blocks):
             refuse("the blocks' angular bins or survey areas differ")
-        if ssc:
+        if ssc or ng:
             k0 = blocks[0].kernel
+            # (the J0 limit of each term that is asked for: _j0_ssc_limit, _j0_limit)
+            limits = [name for name, on in (("_j0_ssc_limit", ssc), ("_j0_limit", ng)) if on]
+
+            def shared(k):
+                return (k.ln_ktheta_min, k.ln_ktheta_max) + tuple(getattr(k, a) for a in limits)
             for i, row in enumerate(self.covariance_list):
                 for j, cov in enumerate(row, i):
                     k = cov.kernel
-                    if (k.ln_ktheta_min, k.ln_ktheta_max, k._j0_ssc_limit) != (
-                            k0.ln_ktheta_min, k0.ln_ktheta_max, k0._j0_ssc_limit):
+                    if shared(k) != shared(k0):
                         refuse("block (%d, %d): its KernelCovariance has another k theta range "
                                "or J0 limit than that of block (0, 0)" % (i, j))
                     if not k.z_min < k.z_max:
@@ -965,7 +978,7 @@ class CovarianceMulti(Covariance):
             b += n - i
         return ln_chi, sigma2
 
-    def get_covariance_batched(self, with_status=False):
+    def get_covariance_batched(self, with_status=False, trispectrum=False):
         """get_covariance() with every block in one device call: the same `wcovar`, and the same
         `covar` in every ``covariance_list[i][j - i]`` (the Poisson diagonal of the matching
         blocks included), bit for bit what the loop over fresh correlations returns.
@@ -983,6 +996,18 @@ class CovarianceMulti(Covariance):
         made from halos that had built no tables yet (a copy otherwise keeps the tables its halo
         had at construction, stale ones included; that is not reproduced).
 
+        trispectrum=True opts in to the one-halo trispectrum term (without the keyword blocks
+        built with nongaussian_cov=True are refused, as they always were).  Blocks built with
+        nongaussian_cov=True (all of them, sharing one HaloTrispectrumOneHalo) then get
+        covariance_NG as well: the trispectrum object's I_0^4 table is built if need be, on that
+        object's own context, and ONE Context.covariance_ng_blocks call runs kernel_NG and
+        covariance_NG of every block in eight launches, with no read-back and no sigma_r call.
+        Its values ([n_blocks, n_pairs], kept in `self.blocks_ng`; None without the term) are
+        added in the loop's order: Gaussian, then trispectrum, then super-sample.  An exhausted
+        divmax of block (i, j) shows as ST_COV_NG_DIVMAX in correlation i's status word.  As with
+        the super-sample term the batch does not build the blocks' own KernelCovariance NG state
+        (_kernel_array, ...).
+
         The work: the correlations' kernels as projection sets on one kept grid.HaloGrid's context
         (Kernel._setup_pairs_on), ONE read-back of every kernel's z_bar -- the only
         synchronisation besides the result and the status words --, one HaloGrid epoch per
@@ -998,10 +1023,11 @@ class CovarianceMulti(Covariance):
         and returned as the second element with with_status=True.
 
         ChompScopeError ("get_covariance_batched: <why>; use get_covariance", before any launch):
-        nongaussian_cov or poisson_noise_only; blocks that differ in ssc_cov and, with it, in the
-        k theta range of their KernelCovariance, or whose four windows have no redshift in common
-        (the block is named); blocks whose power_spec, bins or areas differ; a kernel that is not
-        exactly kernel.Kernel, has an assigned z_bar, a tabulated redshift distribution, a w0-wa
+        nongaussian_cov without trispectrum=True, or poisson_noise_only; blocks that differ in
+        ssc_cov or nongaussian_cov or do not share one halo_tri object and, with either term, in
+        the k theta range or J0 limit of their KernelCovariance, or whose four windows have no
+        redshift in common (the block is named); blocks whose power_spec, bins or areas differ; a
+        kernel that is not exactly kernel.Kernel, has an assigned z_bar, a tabulated redshift distribution, a w0-wa
         cosmology or another k theta range; a halo
         Correlation.correlation_hods would refuse, an HOD of another class, halos with different
         halo dictionaries or mass functions, two correlations sharing one Halo object; anything
@@ -1009,7 +1035,7 @@ class CovarianceMulti(Covariance):
         from its z_bar (keep_halo_z_bar), which the loop's first block would be evaluated at."""
         import warnings
         from . import grid
-        corrs, power_spec = self._batched_scope()
+        corrs, power_spec = self._batched_scope(trispectrum=trispectrum)
         n = len(corrs)
         halos = [c.halo for c in corrs]
         h0 = halos[0]
@@ -1050,6 +1076,16 @@ class CovarianceMulti(Covariance):
             code, numpy.arange(n), first._j0_limit, first.area,
             [[cov.proj_power_poisson(p) for p in range(4)] for cov in blocks],
             centers[iu[0]], centers[iu[1]])
+        self.blocks_ng = None
+        if first.nongaussian_cov and nb:
+            tri = first.halo_tri
+            if not tri._initialized_i_0_4:
+                tri._initialize_i_0_4()                      # (on the trispectrum object's own context)
+            k0 = first.kernel
+            self.blocks_ng = hg.ctx.covariance_ng_blocks(
+                numpy.arange(n), k0.ln_ktheta_min, k0.ln_ktheta_max, k0._j0_limit, first.area,
+                tri._i_0_4_array, tri._k_min, tri._k_max, centers[iu[0]], centers[iu[1]])
+            vals = vals + self.blocks_ng                     # (the loop's order, get_covariance)
         self.blocks_ssc = None
         if ssc and nb:
             ranges = hg.ctx.covariance_ssc_blocks_range(n)   # (synchronises: chi range per block)

@@ -198,6 +198,7 @@ struct chomp_ctx {
   FourierState fourier;         // CovarianceFourier: the four pairs' scalars, Limber tables and splines
   BlocksState blocks;           // chomp_covariance_blocks: one table slab per block of a CovarianceMulti
   SscBlocksState ssc_blocks;    // chomp_covariance_ssc_blocks: one kernel_ssc slab per block
+  NgBlocksState ng_blocks;      // chomp_covariance_ng_blocks: one kernel_NG slab per block
   std::vector<double> sets_z_min, sets_z_max;   // per set of `sets`: the redshifts its two windows share
   // The side stream.  The projection set-up (chomp_kernel_setup / chomp_multi_epoch_setup:
   // a chain of six small launches) depends on nothing the halo set-up produces, and C_l on

@@ -2240,3 +2240,175 @@ int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, si
                      d.knots, d.lev, ng_status(ctx));
   return pairs_finish(ctx, st, d, n, plan.sh_outer, area);
 }
+
+// ---------------------------------------------------------------------------
+// The trispectrum term of every block of a CovarianceMulti in one call (chomp_cov_kernels.h,
+// "The block axis of the trispectrum term")
+// ---------------------------------------------------------------------------
+// Correlation c is projection set c of the last set-up of sets; block (i, j) reads both sides
+// where they lie, and epoch[c] only names a status word.  Neither ctx->proj (d_ssc, d_ng and
+// d_ng_tri included) nor ctx->cross nor the states of chomp_covariance_blocks and
+// chomp_covariance_ssc_blocks are touched.
+//
+// What a call of n_corr correlations and n_pairs pairs of angles keeps on the device, in elements:
+// the slabs (n_blocks NgLayout blocks of n_ktheta knots a side), the k_b buffer (knots, then
+// levels), the I_0^4 block and the index block.  Host arithmetic alone.
+struct NgBlocksSizes {
+  size_t n_blocks, slab, slabs, kb, tri, index;
+};
+static NgBlocksSizes ng_blocks_sizes(size_t n_corr, size_t n_pairs, int n_ktheta, int n_k, int n_tri) {
+  NgBlocksSizes Z;
+  Z.n_blocks = n_corr * (n_corr + 1) / 2;
+  Z.slab = (size_t)make_ng_layout(n_ktheta).total;
+  Z.slabs = Z.n_blocks * Z.slab;
+  Z.kb = 2 * Z.n_blocks * n_pairs * (size_t)n_k;
+  Z.tri = (size_t)make_ng_tri_layout(n_tri).total;
+  Z.index = n_corr + 3 * Z.n_blocks;
+  return Z;
+}
+
+int chomp_cov_ng_blocks_plan(size_t n_corr, const size_t* epoch, size_t n_pairs, size_t n_ktheta,
+                             size_t n_k, size_t n_tri, size_t* sizes, int* index) {
+  if (!sizes || n_corr == 0 || n_corr > (size_t)kProjSetsMax || n_corr * (n_corr + 1) / 2 > 65535 ||
+      n_pairs == 0 || n_pairs > 65535 ||
+      n_ktheta < 4 || n_ktheta > 256 || n_k < 4 || n_k > 256 || n_tri < 4 || n_tri > 64)
+    return CHOMP_ERR_ARG;
+  const NgBlocksSizes Z = ng_blocks_sizes(n_corr, n_pairs, (int)n_ktheta, (int)n_k, (int)n_tri);
+  const size_t out[6] = {Z.n_blocks, Z.slab, Z.slabs, Z.kb, Z.tri, Z.index};
+  std::copy(out, out + 6, sizes);
+  if (index) {
+    const std::vector<int> block = blocks_index(n_corr, epoch, true);
+    std::copy(block.begin(), block.end(), index);
+  }
+  return CHOMP_OK;
+}
+
+int chomp_cov_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch,
+                               double ln_ktheta_min, double ln_ktheta_max, double j0_limit,
+                               double area, const double* tri_table, size_t n_tri,
+                               double tri_k_min, double tri_k_max, const double* theta,
+                               size_t n_pairs, double* out, int mem) {
+  StageRange range_(ctx, "chomp:covariance_ng_blocks");
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (!tri_table || !theta || !out || n_corr == 0 || n_pairs == 0)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: bad args");
+  Staging st(ctx, mem, "covariance_ng_blocks");
+  if (st.rc) return st.rc;
+  // (with `overlap`: a block whose windows share no redshift is refused here, from the host's
+  //  ranges of the sets)
+  int rc = blocks_check(ctx, "covariance_ng_blocks", n_corr, true);
+  if (rc) return rc;
+  for (size_t c = 0; epoch && c < n_corr; ++c)
+    if (epoch[c] >= ctx->n_epoch)
+      return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: correlation " + std::to_string(c) +
+                                      ": epoch range");
+  const ProjSets& S_ = ctx->sets;
+  const ProjLayout& L = S_.L;
+  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  if (!(ln_ktheta_max > ln_ktheta_min) || !(j0_limit > 0.0))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: ln(k theta) range / J0 limit");
+  const int N = L.NKT;
+  if (N < 4 || N > 256)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: kernel_npoints must be 4..256");
+  rc = pairs_check(ctx, "covariance_ng_blocks", area, n_pairs);
+  if (rc) return rc;
+  if (n_tri < 4 || n_tri > 64)
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: the I_0^4 table must be 4..64 knots a side");
+  if (!(tri_k_min > 0.0) || !(tri_k_max > tri_k_min))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: the I_0^4 table's k range");
+  if (st.host) {
+    rc = pairs_positive(ctx, "covariance_ng_blocks", theta, n_pairs);
+    if (rc) return rc;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const NgPlan plan = ng_plan(ctx->cfg, L);
+  const NgLayout& G = plan.G;
+  const NgTriLayout T = make_ng_tri_layout((int)n_tri);
+  const int NK = plan.NK;
+  const size_t n_cross = n_blocks - n_corr;
+  const NgBlocksSizes sizes = ng_blocks_sizes(n_corr, n_pairs, G.N, NK, T.N);
+  const size_t sh_kb = (size_t)ng_kb_lds_doubles(G.N, T.N) * sizeof(double);
+  if (!fits_lds(&k_ng_blocks_table<false>, plan.sh_table[0]) ||
+      (n_cross && !fits_lds(&k_ng_blocks_table<true>, plan.sh_table[1])))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: cosmo/window_npoints too large for the "
+                                    "windows of a block");
+  if (!fits_lds(&k_ng_blocks_kb, sh_kb))
+    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: kernel_npoints too large for the rows of "
+                                    "the two tables");
+  NgBlocksState& B = ctx->ng_blocks;
+  B.n_corr = 0;
+  rc = ensure(ctx, B.d, sizes.slabs);
+  if (!rc) rc = ensure(ctx, B.d_kb, sizes.kb);
+  if (!rc) rc = ensure(ctx, B.d_tri, sizes.tri);
+  if (!rc) rc = blocks_index_upload(ctx, B.d_index, blocks_index(n_corr, epoch, true));
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(B.d_tri + T.tab, tri_table, n_tri * n_tri * sizeof(double),
+                        hipMemcpyHostToDevice, ctx->stream));
+  const double* d_theta;
+  double* d_out;
+  st.in(theta, 2 * n_pairs, &d_theta);
+  st.out(out, n_blocks * n_pairs, &d_out);
+  rc = st.place();
+  if (rc) return rc;
+  B.G = G;
+  const int nc = (int)n_corr;
+  const unsigned Z = (unsigned)n_blocks;
+  const size_t pstride = (size_t)L.total;
+  const int* d_diag = B.d_index + n_corr + 2 * n_blocks;
+  const int* d_cross = d_diag + n_corr;
+  unsigned* d_status = epoch ? (unsigned*)ctx->d_status : nullptr;
+  hipLaunchKernelGGL(k_ng_tri, dim3(1), dim3(256), 0, ctx->stream, T, tri_k_min, tri_k_max, B.d_tri);
+  hipLaunchKernelGGL(k_ng_blocks_prep<false>, dim3((unsigned)n_corr), dim3(256), 0, ctx->stream,
+                     ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
+                     ln_ktheta_min, ln_ktheta_max, j0_limit, B.d, d_status);
+  if (n_cross)
+    hipLaunchKernelGGL(k_ng_blocks_prep<true>, dim3((unsigned)n_cross), dim3(256), 0, ctx->stream,
+                       ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_cross,
+                       ln_ktheta_min, ln_ktheta_max, j0_limit, B.d, d_status);
+  hipLaunchKernelGGL(k_ng_blocks_table<false>, dim3(plan.n_tab, (unsigned)n_corr), dim3(256),
+                     plan.sh_table[0], ctx->stream, ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab, pstride,
+                     B.d_index, d_diag, ctx->d_j0, B.d, d_status);
+  if (n_cross)
+    hipLaunchKernelGGL(k_ng_blocks_table<true>, dim3(plan.n_tab, (unsigned)n_cross), dim3(256),
+                       plan.sh_table[1], ctx->stream, ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab,
+                       pstride, B.d_index, d_cross, ctx->d_j0, B.d, d_status);
+  hipLaunchKernelGGL(k_ng_blocks_bicubic, dim3(Z), dim3(256), 0, ctx->stream, G, B.d);
+  double* d_knots = B.d_kb;
+  double* d_lev = B.d_kb + n_blocks * n_pairs * (size_t)NK;
+  hipLaunchKernelGGL(k_ng_blocks_kb, dim3((unsigned)NK, (unsigned)n_pairs, Z), dim3(256), sh_kb,
+                     ctx->stream, ctx->cfg, G, T, nc, B.d_index, B.d, B.d_tri, tri_k_min, tri_k_max,
+                     d_theta, d_theta + n_pairs, d_knots, d_lev, d_status);
+  hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256), plan.sh_outer,
+                     ctx->stream, ctx->cfg, area, d_knots, d_out);
+  HIPCHK(hipGetLastError());
+  B.n_corr = n_corr;
+  B.n_pairs = n_pairs;
+  return st.finish();
+}
+
+// One block of the last chomp_cov_ng_blocks (host arrays, any may be NULL).
+int chomp_cov_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info, double* table,
+                                     double* levels, double* table_min, double* kb_knots,
+                                     double* kb_levels) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  const NgBlocksState& B = ctx->ng_blocks;
+  if (B.n_corr == 0)
+    return fail(ctx, CHOMP_ERR_STATE, "covariance_ng_blocks_table before covariance_ng_blocks");
+  const size_t n_blocks = B.n_corr * (B.n_corr + 1) / 2;
+  if (block >= n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks_table: block");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const NgLayout& G = B.G;
+  const double* ng = B.d + block * (size_t)G.total;
+  const int z_bar = G.scal + kSscZBar, z_min = G.scal + kSscZMin, at_min = G.scal + kNgMin;
+  const size_t NN = (size_t)G.N * G.N;
+  const int rc = slab_read(ctx, ng, {{info, &z_bar, 1, 3}, {info ? info + 3 : nullptr, &z_min, 1, 4},
+                                     {table, &G.tab, 1, NN}, {levels, &G.lev, 1, NN},
+                                     {table_min, &at_min, 1, 1}}, true);
+  if (rc) return rc;
+  const size_t row = B.n_pairs * (size_t)ctx->cfg.kernel_npoints;
+  if (kb_knots) HIPCHK(hipMemcpy(kb_knots, B.d_kb + block * row, row * sizeof(double), hipMemcpyDeviceToHost));
+  if (kb_levels)
+    HIPCHK(hipMemcpy(kb_levels, B.d_kb + (n_blocks + block) * row, row * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}

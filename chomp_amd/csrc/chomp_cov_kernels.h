@@ -22,6 +22,10 @@
 //   k_ng_tri        the bicubic of an uploaded I_0^4 table (HaloTrispectrumOneHalo's)
 //   k_ng_kb         covariance_NG, inner integrals: one k_b Romberg per (pair, k_a knot)
 //
+//   k_ssc_blocks_*  the super-sample term with the block of a CovarianceMulti as a grid dimension
+//   k_ng_blocks_*   ... and the trispectrum term: prep (the scalars alone, cov_scalars_body),
+//                   table, bicubic and kb; the outer integrals are k_ssc_blocks_outer's
+//
 // ... and the Gaussian covariance of C_l, CovarianceFourier, covariance.py:874-1083 (at the end):
 //
 //   k_covf_zbar     z_bar and the range of the four window pairs a1a2, b1b2, a1b2, b1a2
@@ -217,14 +221,18 @@ struct SscKernelIntegrand {
 // FOUR: the four windows of a cross block and their common range -- z_min = max, z_max = min of the
 // two sides', chi_min = max(window_precision, chi(z_min)), chi_max = chi(z_max) on slot 0's
 // MultiEpoch (kernel.py:910-931).  The range goes into the scalars in both cases.
-// (the body of k_ssc_prep and of k_ssc_blocks_prep)
+//
+// cov_scalars_body is the part that reads no sigma^2 knot: the N ln k theta knots into kx and the
+// scalars (kSsc*: z_bar_NG, its chi and growth, the ln k theta range, `limit`, the common range)
+// into scal.  The trispectrum term's block axis runs it alone (k_ng_blocks_prep).  All threads
+// call; thread 0 writes the scalars behind the body's one barrier.
 template <bool FOUR>
-__device__ __forceinline__ void ssc_prep_body(const chomp_config& cfg, const ProjLayout& L,
-                                              const SscLayout& S, const CovSrc& src,
-                                              double ln_kt_min, double ln_kt_max, double j0_limit,
-                                              double* __restrict__ st) {
+__device__ __forceinline__ void cov_scalars_body(const chomp_config& cfg, const ProjLayout& L,
+                                                 int N, const CovSrc& src, double ln_kt_min,
+                                                 double ln_kt_max, double limit,
+                                                 double* __restrict__ scal,
+                                                 double* __restrict__ kx) {
   __shared__ double cand[256];
-  __shared__ double work[2 * 256];
   const ProjDev& pd = *src.pd;
   const double* ptab = src.ptab;
   const MEView me = me_view(L, pd, ptab, 0);
@@ -243,9 +251,9 @@ __device__ __forceinline__ void ssc_prep_body(const chomp_config& cfg, const Pro
     chi_max = me.comoving_distance(z_max);
   }
   const int t = threadIdx.x;
-  for (int i = t; i < S.N; i += blockDim.x) st[S.kx + i] = linspace_at(ln_kt_min, ln_kt_max, S.N, i);
-  if (t < S.N) {
-    const double z = linspace_at(z_min, z_max, S.N, t);
+  for (int i = t; i < N; i += blockDim.x) kx[i] = linspace_at(ln_kt_min, ln_kt_max, N, i);
+  if (t < N) {
+    const double z = linspace_at(z_min, z_max, N, t);
     double chi = me.comoving_distance(z);
     if (!(chi > cfg.window_precision)) chi = cfg.window_precision;
     const double D = me.growth_factor(me.redshift(chi));
@@ -255,22 +263,34 @@ __device__ __forceinline__ void ssc_prep_body(const chomp_config& cfg, const Pro
   }
   __syncthreads();
   if (t != 0) return;
-  spline_build(st + S.sx, st + S.sy, S.NS, st + S.spp, work);
   // numpy.argmax: the first of equal maxima, and the first NaN if there is one
   int best = 0;
-  for (int i = 1; i < S.N && !isnan(cand[best]); ++i)
+  for (int i = 1; i < N && !isnan(cand[best]); ++i)
     if (isnan(cand[i]) || cand[i] > cand[best]) best = i;
-  const double zb = linspace_at(z_min, z_max, S.N, best);
-  st[S.scal + kSscZBar] = zb;
-  st[S.scal + kSscChiPeak] = me.comoving_distance(zb);
-  st[S.scal + kSscDz] = me.growth_factor(zb);
-  st[S.scal + kSscLnMin] = ln_kt_min;
-  st[S.scal + kSscLnMax] = ln_kt_max;
-  st[S.scal + kSscLimit] = j0_limit;
-  st[S.scal + kSscZMin] = z_min;
-  st[S.scal + kSscZMax] = z_max;
-  st[S.scal + kSscChiMin] = chi_min;
-  st[S.scal + kSscChiMax] = chi_max;
+  const double zb = linspace_at(z_min, z_max, N, best);
+  scal[kSscZBar] = zb;
+  scal[kSscChiPeak] = me.comoving_distance(zb);
+  scal[kSscDz] = me.growth_factor(zb);
+  scal[kSscLnMin] = ln_kt_min;
+  scal[kSscLnMax] = ln_kt_max;
+  scal[kSscLimit] = limit;
+  scal[kSscZMin] = z_min;
+  scal[kSscZMax] = z_max;
+  scal[kSscChiMin] = chi_min;
+  scal[kSscChiMax] = chi_max;
+}
+// (the body of k_ssc_prep and of k_ssc_blocks_prep: the scalars, and one thread builds the
+//  sigma^2 spline from the knots already in the slab -- the scalars' barrier stands behind the
+//  stores of k_ssc_blocks_prep)
+template <bool FOUR>
+__device__ __forceinline__ void ssc_prep_body(const chomp_config& cfg, const ProjLayout& L,
+                                              const SscLayout& S, const CovSrc& src,
+                                              double ln_kt_min, double ln_kt_max, double j0_limit,
+                                              double* __restrict__ st) {
+  __shared__ double work[2 * 256];
+  cov_scalars_body<FOUR>(cfg, L, S.N, src, ln_kt_min, ln_kt_max, j0_limit, st + S.scal,
+                         st + S.kx);
+  if (threadIdx.x == 0) spline_build(st + S.sx, st + S.sy, S.NS, st + S.spp, work);
 }
 template <bool FOUR>
 __global__ __launch_bounds__(256) void k_ssc_prep(chomp_config cfg, ProjLayout L, SscLayout S,
@@ -930,15 +950,16 @@ struct NgKernelIntegrand {
 // _initialize_NG_spline (kernel.py:1016-1030), block b -> the b-th (i, j), i <= j, of the upper
 // triangle, written to [i][j] and [j][i] with its Romberg level; otherwise
 // raw_kernel_NG(ln_a[b], ln_b[b]) into out.
+// (the body of k_ng_table and of k_ng_blocks_table; workgroup blockIdx.x)
 template <bool FOUR>
-__global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L, NgLayout G,
-                                                  CovSrc src,
-                                                  const BesselTab* __restrict__ bess_g,
-                                                  double* __restrict__ ng,
-                                                  const double* __restrict__ ln_a,
-                                                  const double* __restrict__ ln_b,
-                                                  double* __restrict__ out,
-                                                  unsigned* __restrict__ status) {
+__device__ __forceinline__ void ng_table_body(const chomp_config& cfg, const ProjLayout& L,
+                                              const NgLayout& G, const CovSrc& src,
+                                              const BesselTab* __restrict__ bess_g,
+                                              double* __restrict__ ng,
+                                              const double* __restrict__ ln_a,
+                                              const double* __restrict__ ln_b,
+                                              double* __restrict__ out,
+                                              unsigned* __restrict__ status) {
   extern __shared__ __align__(16) double sm[];
   __shared__ ProjDev pd, pd_b;      // (pd_b: FOUR only)
   __shared__ BesselTab B;
@@ -1001,11 +1022,23 @@ __global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L
     if (!converged && status) atomicOr(status, kStCovNgDivmax);
   }
 }
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ng_table(chomp_config cfg, ProjLayout L, NgLayout G,
+                                                  CovSrc src,
+                                                  const BesselTab* __restrict__ bess_g,
+                                                  double* __restrict__ ng,
+                                                  const double* __restrict__ ln_a,
+                                                  const double* __restrict__ ln_b,
+                                                  double* __restrict__ out,
+                                                  unsigned* __restrict__ status) {
+  ng_table_body<FOUR>(cfg, L, G, src, bess_g, ng, ln_a, ln_b, out, status);
+}
 
 // grid 1, block 256: kernel.py:1026-1029 -- min(table) (numpy.min: a NaN entry gives NaN), then
 // the bicubic of log(table - 10 min).  Nothing is guarded: with min >= 0 an entry equal to
 // 10 min gives log(0) and the reference's spline is not finite either.
-__global__ __launch_bounds__(256) void k_ng_bicubic(NgLayout G, double* __restrict__ ng) {
+// (the body of k_ng_bicubic and of k_ng_blocks_bicubic)
+__device__ __forceinline__ void ng_bicubic_body(const NgLayout& G, double* __restrict__ ng) {
   __shared__ double part[256];
   const int t = threadIdx.x, NN = G.N * G.N;
   double m = INFINITY;
@@ -1032,6 +1065,9 @@ __global__ __launch_bounds__(256) void k_ng_bicubic(NgLayout G, double* __restri
   __threadfence_block();
   __syncthreads();
   bicubic_build(G.N, ng + G.kx, ng + G.ltab, ng + G.rowt, ng + G.work, ng + G.bic);
+}
+__global__ __launch_bounds__(256) void k_ng_bicubic(NgLayout G, double* __restrict__ ng) {
+  ng_bicubic_body(G, ng);
 }
 
 // The bicubic of log(table - 10 min) with kernel_ssc's range rules (kernel.py:1003-1014 clamps
@@ -1136,15 +1172,15 @@ struct NgKbIntegrand {
 
 // grid (kernel_npoints, n pairs), block 256: the k_b integral at k_a knot x of pair y
 // (covariance.py:624-671), / D(z_bar_NG)^4.  LDS: ng_kb_lds_doubles.
-__global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgTriLayout T,
-                                               const double* __restrict__ ng,
-                                               const double* __restrict__ tri, double tri_k_min,
-                                               double tri_k_max,
-                                               const double* __restrict__ theta_a,
-                                               const double* __restrict__ theta_b,
-                                               double* __restrict__ knots,
-                                               double* __restrict__ levels,
-                                               unsigned* __restrict__ status) {
+// (the body of k_ng_kb and of k_ng_blocks_kb; workgroup (blockIdx.x, blockIdx.y))
+__device__ __forceinline__ void ng_kb_body(const chomp_config& cfg, const NgLayout& G,
+                                           const NgTriLayout& T, const double* __restrict__ ng,
+                                           const double* __restrict__ tri, double tri_k_min,
+                                           double tri_k_max, const double* __restrict__ theta_a,
+                                           const double* __restrict__ theta_b,
+                                           double* __restrict__ knots,
+                                           double* __restrict__ levels,
+                                           unsigned* __restrict__ status) {
   extern __shared__ __align__(16) double sm[];
   __shared__ double red[romberg_scratch<4, 2>()];
   const int i = blockIdx.x, pair = blockIdx.y, NK = cfg.kernel_npoints;
@@ -1166,6 +1202,100 @@ __global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgT
     if (levels) levels[(size_t)pair * NK + i] = (double)r.level[0];
     if (!r.converged[0] && status) atomicOr(status, kStCovNgDivmax);
   }
+}
+__global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgTriLayout T,
+                                               const double* __restrict__ ng,
+                                               const double* __restrict__ tri, double tri_k_min,
+                                               double tri_k_max,
+                                               const double* __restrict__ theta_a,
+                                               const double* __restrict__ theta_b,
+                                               double* __restrict__ knots,
+                                               double* __restrict__ levels,
+                                               unsigned* __restrict__ status) {
+  ng_kb_body(cfg, G, T, ng, tri, tri_k_min, tri_k_max, theta_a, theta_b, knots, levels, status);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The block axis of the trispectrum term (chomp_cov_ng_blocks: the one-halo trispectrum
+// values of every block of a CovarianceMulti(nongaussian_cov=True, cross_terms=True) in one call)
+// ---------------------------------------------------------------------------------------------
+// The blocks, their order and the windows they read are those of the super-sample block axis
+// above: block (i, j), i <= j, in the row-major order of the upper triangle, reads projection set
+// i and set j where they lie (ssc_blocks_src) -- no snapshot, no CrossState.  The term reads no
+// halo epoch: the one I_0^4 table of the call (k_ng_tri, once) serves every block, and an epoch
+// only names the status word CHOMP_ST_COV_NG_DIVMAX of block (i, j) goes to, epoch[i]'s.  A
+// diagonal block runs the bodies of the matching path (FOUR = false), a cross block those of the
+// four-window path: the same code as k_ssc_prep + k_ng_prep, k_ng_table, k_ng_bicubic and k_ng_kb,
+// so the same bits; every branch on the block is uniform in a workgroup.
+//
+// Every block owns one NgLayout slab.  Its scalars come from cov_scalars_body alone: no sigma^2
+// knot is read, so the host sends none.  The two instances of the prep and table bodies differ in
+// their dynamic LDS, so each runs as a launch of its own over a list of its blocks (the index
+// block of the super-sample calls, with the lists).
+struct NgBlocksState {
+  DeviceBuffer<double> d;      // n_blocks slabs of G.total doubles
+  DeviceBuffer<double> d_kb;   // the k_b knots, then their levels: [n_blocks][n_pairs][kernel_npoints] each
+  DeviceBuffer<double> d_tri;  // the I_0^4 table of the last call and its bicubic (NgTriLayout)
+  StagedBuffer<int> d_index;   // the index block
+  NgLayout G;
+  size_t n_corr = 0;           // correlations of the last call (0: none yet)
+  size_t n_pairs = 0;          // ... and its pairs of angles
+};
+
+// grid n listed blocks, block 256: what k_ssc_prep and k_ng_prep leave in a kernel_NG block -- the
+// scalars with _j0_limit, the ln k theta knots -- in block list[x]'s slab, and the status bit of
+// epoch[i]'s word cleared (every i has its diagonal block; the tables are launched behind both
+// prep launches).  status == nullptr: no status.
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ng_blocks_prep(
+    chomp_config cfg, ProjLayout L, NgLayout G, int n_corr, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const int* __restrict__ index,
+    const int* __restrict__ list, double ln_kt_min, double ln_kt_max, double j0_limit,
+    double* slabs, unsigned* __restrict__ status) {
+  const int b = list[blockIdx.x];
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  double* ng = slabs + (size_t)b * G.total;
+  const int t = threadIdx.x;
+  // (the scalars k_ng_prep leaves at 0, and those nothing reads)
+  if (t == 6 || t == 7 || (t >= 12 && t < 16)) ng[G.scal + t] = 0.0;
+  if (t == 0 && status) atomicAnd(status + index[i], ~kStCovNgDivmax);
+  cov_scalars_body<FOUR>(cfg, L, G.N, ssc_blocks_src(pd, ptab, pstride, i, j), ln_kt_min,
+                         ln_kt_max, j0_limit, ng + G.scal, ng + G.kx);
+}
+
+// grid (N (N + 1) / 2, n listed blocks), block 256: the knot table of block list[y].  LDS:
+// ng_table_lds_doubles of the instance.
+template <bool FOUR>
+__global__ __launch_bounds__(256) void k_ng_blocks_table(
+    chomp_config cfg, ProjLayout L, NgLayout G, int n_corr, const ProjDev* __restrict__ pd,
+    const double* __restrict__ ptab, size_t pstride, const int* __restrict__ index,
+    const int* __restrict__ list, const BesselTab* __restrict__ bess_g, double* slabs,
+    unsigned* __restrict__ status) {
+  const int b = list[blockIdx.y];
+  const int i = index[n_corr + 2 * b], j = index[n_corr + 2 * b + 1];
+  ng_table_body<FOUR>(cfg, L, G, ssc_blocks_src(pd, ptab, pstride, i, j), bess_g,
+                      slabs + (size_t)b * G.total, nullptr, nullptr, nullptr,
+                      status ? status + index[i] : nullptr);
+}
+
+// grid n_blocks, block 256: min(table) and the bicubic of log(table - 10 min) of block x.
+__global__ __launch_bounds__(256) void k_ng_blocks_bicubic(NgLayout G, double* slabs) {
+  ng_bicubic_body(G, slabs + (size_t)blockIdx.x * G.total);
+}
+
+// grid (kernel_npoints, n_pairs, n_blocks), block 256: the k_b integral at k_a knot x of pair y of
+// block z, every block with the one I_0^4 slab `tri`.  knots, levels:
+// [n_blocks][n_pairs][kernel_npoints].  LDS: ng_kb_lds_doubles.
+__global__ __launch_bounds__(256) void k_ng_blocks_kb(
+    chomp_config cfg, NgLayout G, NgTriLayout T, int n_corr, const int* __restrict__ index,
+    const double* __restrict__ slabs, const double* __restrict__ tri, double tri_k_min,
+    double tri_k_max, const double* __restrict__ theta_a, const double* __restrict__ theta_b,
+    double* __restrict__ knots, double* __restrict__ levels, unsigned* __restrict__ status) {
+  const int b = blockIdx.z;
+  const int i = index[n_corr + 2 * b];
+  const size_t row = (size_t)b * gridDim.y * cfg.kernel_npoints;
+  ng_kb_body(cfg, G, T, slabs + (size_t)b * G.total, tri, tri_k_min, tri_k_max, theta_a, theta_b,
+             knots + row, levels + row, status ? status + index[i] : nullptr);
 }
 
 // ---------------------------------------------------------------------------

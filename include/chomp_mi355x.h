@@ -1060,6 +1060,68 @@ int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, si
                         double tri_k_min, double tri_k_max, const double* theta, size_t n,
                         double* out, double* kb_knots, double* kb_levels);
 
+/* The one-halo trispectrum term of EVERY block of a CovarianceMulti(nongaussian_cov=True,
+ * cross_terms=True) in one call: the block axis of chomp_covariance_blocks and
+ * chomp_covariance_ssc_blocks for the third term.  Correlation c is projection set c of the last
+ * chomp_kernel_setup_pairs (Bessel order 0); block (i, j), i <= j, in the row-major order of the
+ * upper triangle, reads set i and set j where they lie.  The term reads no halo epoch and no
+ * sigma^2 knot: the host sends neither knots nor a range, and nothing is read back before the
+ * result.
+ *
+ * A diagonal block is, bit for bit, what chomp_kernel_setup, chomp_kernel_ssc_setup(with_table 0),
+ * chomp_kernel_ng_setup and chomp_covariance_ng return for kernel i; a cross block what two
+ * chomp_covariance_cross_stage, chomp_kernel_ssc_setup_cross(with_table 0), chomp_kernel_ng_setup
+ * and chomp_covariance_ng do: the table, its levels and minimum, the scalars, the k_b knots, their
+ * levels and the values.
+ *
+ * ln_ktheta_min / ln_ktheta_max and j0_limit (_j0_limit) are those of chomp_kernel_ssc_setup and
+ * chomp_kernel_ng_setup, area, tri_table (a host array), n_tri, tri_k_min and tri_k_max those of
+ * chomp_covariance_ng: the I_0^4 table's bicubic is built once for all blocks.  theta holds
+ * theta_a[n_pairs] then theta_b[n_pairs] and out [n_blocks][n_pairs], both host or device arrays
+ * as `mem` says.  epoch ([n_corr], or NULL: no status) only says where the status bit goes: a
+ * block (i, j) that exhausts divmax sets CHOMP_ST_COV_NG_DIVMAX on epoch[i]'s word; the call
+ * clears the bit on every epoch[i] first.
+ *
+ * The call keeps a state of its own (one kernel_NG block per block, the k_b knots, the I_0^4
+ * table, an index block) and touches neither the context's kernel_ssc / kernel_NG state nor the
+ * two cross slots nor the state of chomp_covariance_blocks or chomp_covariance_ssc_blocks.
+ *
+ * CHOMP_ERR_STATE: no sets, another number of sets than n_corr, sets of order 2.  CHOMP_ERR_ARG:
+ * more than 65535 blocks or pairs, a bad ln(k theta) range or J0 limit, n_tri outside 4..64, a bad
+ * trispectrum k range, an area or a host theta that is not positive, an epoch the context does not
+ * have, tables too large for the 64 kB of LDS.  CHOMP_ERR_SCOPE, naming the block and before
+ * anything is launched: a block whose four windows share no redshift (decided on the host from
+ * the sets' ranges).
+ *
+ * chomp_cov_ng_blocks_table reads block `block` of the last call (host arrays, any may be
+ * NULL): info[7] = z_bar_NG, chi(z_bar_NG), growth_factor(z_bar_NG), z_min, z_max, chi_min,
+ * chi_max; table and levels [kernel_npoints^2], table_min[1]; kb_knots and kb_levels
+ * [n_pairs * kernel_npoints].
+ *
+ * chomp_cov_ng_blocks_plan is host arithmetic and needs neither a context nor a device: what a
+ * call of n_corr correlations and n_pairs pairs keeps on the device, in elements -- sizes[6] =
+ * n_blocks, one kernel_NG block (n_ktheta knots a side), all of them, the k_b buffer (knots then
+ * levels, n_k knots a pair), the I_0^4 block, the index block -- and, if asked for, that index
+ * block, index[n_corr + 3 n_blocks] ints: epoch[n_corr] (NULL: 0 .. n_corr - 1) | (i, j)[n_blocks]
+ * | the diagonal blocks [n_corr] | the cross blocks [n_blocks - n_corr].  CHOMP_ERR_ARG beyond
+ * the sizes the call itself takes (more than 65535 blocks or pairs included).
+ *
+ * (The calls are spelled chomp_cov_ng_blocks*, not chomp_covariance_ng_blocks*: the family
+ * chomp_covariance_* / chomp_kernel_ssc_* / chomp_kernel_ng_* is a closed list of 24 that the
+ * suite pins.  Their messages and the Python methods say covariance_ng_blocks.) */
+int chomp_cov_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch /*[n_corr] or NULL*/,
+                               double ln_ktheta_min, double ln_ktheta_max, double j0_limit,
+                               double area, const double* tri_table, size_t n_tri,
+                               double tri_k_min, double tri_k_max,
+                               const double* theta /*[2][n_pairs]*/, size_t n_pairs,
+                               double* out /*[n_blocks][n_pairs]*/, int mem);
+int chomp_cov_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info /*[7]*/, double* table,
+                              double* levels, double* table_min, double* kb_knots,
+                              double* kb_levels);
+int chomp_cov_ng_blocks_plan(size_t n_corr, const size_t* epoch /*[n_corr] or NULL*/,
+                             size_t n_pairs, size_t n_ktheta, size_t n_k, size_t n_tri,
+                             size_t* sizes /*[6]*/, int* index /*[n_corr + 3 n_blocks] or NULL*/);
+
 /* CorrelationFourier.correlation(l) (correlation.py:360-392): Limber C_l. */
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z,
                const double* ell, size_t n, double* out, int mem);

@@ -10,13 +10,21 @@ pairs) -- two ways:
     batch   CovarianceMulti.get_covariance_batched(): chomp_kernel_setup_pairs, ONE read-back of
             z_bar, the grid set-up of 15 epochs, chomp_covariance_blocks; keeps no tables
 
-    python tools/time_cov_multi.py [--rounds 5] [--modes loop,batch] [--ssc] [--out FILE.json]
+    python tools/time_cov_multi.py [--rounds 5] [--modes loop,batch] [--ssc] [--ng] [--out FILE.json]
 
 --ssc: the same analysis with the super-sample term, CovarianceMulti(ssc_cov=True,
 cross_terms=True): per cross block the loop adds kernel_ssc (a read-back of the chi range, a host
 sigma_r call, the 1275 integrals of the table, its bicubic) and covariance_ssc; the batch adds one
 read-back of every block's range, one sigma_r call per row of blocks and
 chomp_covariance_ssc_blocks.
+
+--ng: the same analysis with the one-halo trispectrum term, CovarianceMulti(nongaussian_cov=True,
+cross_terms=True, input_halo_trispectrum=HaloTrispectrumOneHalo(0.5)), one trispectrum object at
+one fixed redshift for all blocks: per cross block the loop adds the kernel_ssc scalars (a
+read-back of the chi range, a host sigma_r call), kernel_NG (the 1275 integrals of the table, a
+read-back of it, its bicubic) and covariance_NG (the upload and bicubic of the I_0^4 table, the
+k_b and outer integrals); the batch, get_covariance_batched(trispectrum=True), adds
+chomp_cov_ng_blocks alone.  --ng --ssc: all three terms.
 
 Timed, host clock around calls that end with their result on the host (so synchronised):
     loop_first / batch_first   the first call on fresh objects (contexts, buffers, code objects)
@@ -63,20 +71,31 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--modes", default="loop,batch")
     ap.add_argument("--ssc", action="store_true")
+    ap.add_argument("--ng", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs the MI355X"
     warnings.simplefilter("ignore")
-    from chomp_amd import covariance, defaults
+    from chomp_amd import covariance, defaults, halo_trispectrum
     modes = args.modes.split(",")
     step = [0]
 
     def build():
         corrs = correlations()
-        kws = dict(ssc_cov=True, cross_terms=True) if args.ssc else {}
-        return corrs, covariance.CovarianceMulti(corrs, bins_per_decade=5, nongaussian_cov=False,
+        kws = dict(nongaussian_cov=False)
+        if args.ssc:
+            kws.update(ssc_cov=True, cross_terms=True)
+        if args.ng:
+            kws.update(nongaussian_cov=True, cross_terms=True,
+                       input_halo_trispectrum=halo_trispectrum.HaloTrispectrumOneHalo(0.5))
+        return corrs, covariance.CovarianceMulti(corrs, bins_per_decade=5,
                                                  survey_area_deg2=25.0, **kws)
+
+    def batched(cm):
+        # (the keyword only where it is needed: the Gaussian and --ssc runs also serve trees
+        #  whose get_covariance_batched does not have it)
+        return cm.get_covariance_batched(trispectrum=True) if args.ng else cm.get_covariance_batched()
 
     def move(corrs, which):
         """A new HOD on the correlations `which`."""
@@ -95,7 +114,8 @@ def main():
 
     result = {"what": "milliseconds per covariance matrix (host clock, result on the host), 15 "
                       "correlations, 120 blocks, 10 angular bins, power_mm"
-                      + (", Gaussian + super-sample terms (ssc_cov, cross_terms)" if args.ssc else ""),
+                      + (", Gaussian + super-sample terms (ssc_cov, cross_terms)" if args.ssc else "")
+                      + (", + one-halo trispectrum term (nongaussian_cov, cross_terms)" if args.ng else ""),
               "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "modes": modes}
     state, warm = {}, {}
     if "loop" in modes:
@@ -106,10 +126,10 @@ def main():
         warm["loop_one"] = lambda: (move(corrs, [step[0] % len(corrs)]), cm.get_covariance())[1]
     if "batch" in modes:
         corrs_b, cm_b = build()
-        result["batch_first_ms"], w = clock(cm_b.get_covariance_batched)
+        result["batch_first_ms"], w = clock(lambda: batched(cm_b))
         state["batch"] = (corrs_b, cm_b, w.copy())
         warm["batch_one"] = lambda: (move(corrs_b, [step[0] % len(corrs_b)]),
-                                     cm_b.get_covariance_batched())[1]
+                                     batched(cm_b))[1]
         result["correlations_with_a_status_word"] = int(numpy.count_nonzero(cm_b.blocks_status))
     if "loop" in state and "batch" in state:
         a, b = state["loop"][2], state["batch"][2]
