@@ -57,6 +57,8 @@ KI = {name: i for i, name in enumerate([
     "wa_chi_min", "wa_chi_max", "wb_chi_min", "wb_chi_max", "j_limit"])}
 KI_COUNT = 13
 KERNEL_SETS_MAX = 1024      # CHOMP_KERNEL_SETS_MAX: the sets of one chomp_kernel_setup_sets / _pairs
+SETS_TABULATED = 1          # CHOMP_SETS_*: what chomp_set_sets_scope lets into those two calls
+SETS_DARK_ENERGY = 2
 ME = {"chi_of_z": 0, "z_of_chi": 1, "growth_of_z": 2}
 KTAB = {"ln_ktheta": 0, "kernel": 1, "wa_chi": 2, "wa": 3, "wb_chi": 4, "wb": 5,
         "me_z": 6, "me_chi": 7, "me_growth": 8, "levels": 9}
@@ -128,7 +130,7 @@ EXPORTS = [
     "chomp_kernel_eval", "chomp_window_eval", "chomp_wtheta", "chomp_wtheta_epochs",
     "chomp_cell", "chomp_cell_epochs",
     "chomp_kernel_setup_sets", "chomp_kernel_info_sets", "chomp_kernel_table_set",
-    "chomp_wtheta_sets", "chomp_kernel_setup_pairs", "chomp_cell_sets",
+    "chomp_wtheta_sets", "chomp_kernel_setup_pairs", "chomp_cell_sets", "chomp_set_sets_scope",
     "chomp_set_precision", "chomp_xi3d", "chomp_xi3d_epochs", "chomp_spline_eval",
     "chomp_hod_stats",
     "chomp_set_transfer", "chomp_kernel_raw",
@@ -436,6 +438,7 @@ def lib():
         L.chomp_hod_stats.argtypes = [vp, sz, sz, c_double_p]
         L.chomp_set_transfer.argtypes = [vp, i]
         L.chomp_set_dark_energy.argtypes = [vp, i]
+        L.chomp_set_sets_scope.argtypes = [vp, ctypes.c_uint]
         L.chomp_set_general_profile.argtypes = [vp, i]
         L.chomp_y_general.argtypes = [vp, sz, d, vp, sz, vp]
         L.chomp_y_general_table.argtypes = [vp, sz, vp, vp]
@@ -1150,29 +1153,47 @@ class Context(object):
         return out
 
     # -- the cosmology axis of the projection set-up --------------------------
+    def _sets_call(self, call, args, tabulated, dark_energy):
+        """One of the two set-ups of sets.  With an opt-in, chomp_set_sets_scope goes before the
+        call and is taken back after it, also when it raised: the opt-in never sticks to the
+        context.  Without one there is no call but the set-up's own."""
+        flags = (SETS_TABULATED if tabulated else 0) | (SETS_DARK_ENERGY if dark_energy else 0)
+        if not flags:
+            self._check(call(*args))
+            return
+        self._check(self._L.chomp_set_sets_scope(self._h, flags))
+        try:
+            self._check(call(*args))
+        finally:
+            self._L.chomp_set_sets_scope(self._h, 0)
+
     def kernel_setup_sets(self, cosmo_dicts, me_z_min, me_z_max, ktheta_min, ktheta_max,
-                          wa, wb, bessel_order):
+                          wa, wb, bessel_order, tabulated=False, dark_energy=False):
         """One projection set-up per cosmology (chomp_kernel_setup_sets): cosmo_dicts a list of
         dictionaries, a float64 array [n, 10] or the packed ctypes array (pack_cosmo).  The sets
         live beside the single set-up of kernel_setup, which stays as it is.  At most
-        KERNEL_SETS_MAX sets per call (ValueError); ChompScopeError for a w0-wa cosmology or a
-        tabulated redshift distribution."""
+        KERNEL_SETS_MAX sets per call (ValueError); ChompScopeError for a w0-wa cosmology unless
+        dark_energy=True, and for a tabulated redshift distribution unless tabulated=True (the
+        opt-ins hold for this call only: chomp_set_sets_scope)."""
         arr = (cosmo_dicts if isinstance(cosmo_dicts, ctypes.Array)
                else self.pack_cosmo(cosmo_dicts, len(cosmo_dicts)))
-        self._check(self._L.chomp_kernel_setup_sets(
-            self._h, len(arr), arr, me_z_min, me_z_max, ktheta_min, ktheta_max,
-            ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)))
+        self._sets_call(self._L.chomp_kernel_setup_sets,
+                        (self._h, len(arr), arr, me_z_min, me_z_max, ktheta_min, ktheta_max,
+                         ctypes.byref(wa), ctypes.byref(wb), int(bessel_order)),
+                        tabulated, dark_energy)
         self._n_sets = len(arr)
 
     def kernel_setup_pairs(self, cosmo_dicts, me_z_min, me_z_max, ktheta_min, ktheta_max,
-                           windows_a, windows_b, bessel_order):
+                           windows_a, windows_b, bessel_order, tabulated=False, dark_energy=False):
         """One projection set-up per kernel (chomp_kernel_setup_pairs): set s is what
         kernel_setup(cosmo_dicts[s], me_z_min[s], me_z_max[s], ktheta_min, ktheta_max,
         windows_a[s], windows_b[s], bessel_order) builds, bit for bit.  cosmo_dicts as in
         kernel_setup_sets; windows_a / windows_b lists of Window structs.  The sets replace those of
         the last kernel_setup_sets / kernel_setup_pairs; the single set-up stays as it is.
         ValueError for lists of other lengths and for more than KERNEL_SETS_MAX sets;
-        ChompScopeError, naming the set, for a w0-wa cosmology or a tabulated distribution."""
+        ChompScopeError, naming the set, for a w0-wa cosmology unless dark_energy=True and for a
+        tabulated distribution unless tabulated=True (as in kernel_setup_sets; equal tables are
+        sent to the device once)."""
         arr = (cosmo_dicts if isinstance(cosmo_dicts, ctypes.Array)
                else self.pack_cosmo(cosmo_dicts, len(cosmo_dicts)))
         n = len(arr)
@@ -1185,9 +1206,10 @@ class Context(object):
         #  stay alive in the caller's structs for the duration of the call)
         wa = (Window * max(n, 1))(*windows_a)
         wb = (Window * max(n, 1))(*windows_b)
-        self._check(self._L.chomp_kernel_setup_pairs(
-            self._h, n, arr, z0.ctypes.data_as(c_double_p), z1.ctypes.data_as(c_double_p),
-            float(ktheta_min), float(ktheta_max), wa, wb, int(bessel_order)))
+        self._sets_call(self._L.chomp_kernel_setup_pairs,
+                        (self._h, n, arr, z0.ctypes.data_as(c_double_p), z1.ctypes.data_as(c_double_p),
+                         float(ktheta_min), float(ktheta_max), wa, wb, int(bessel_order)),
+                        tabulated, dark_energy)
         self._n_sets = n
 
     def kernel_info_sets(self):

@@ -253,9 +253,11 @@ class Correlation(object):
         return ctx.wtheta_epochs(code, 0, n_hod, self._k_lim[0], self._k_lim[1], self.D_z, flat)
 
     # -- the batch over cosmologies --------------------------------------------
-    def _cosmologies_scope(self, cosmo_dicts, hods=None):
+    def _cosmologies_scope(self, cosmo_dicts, hods=None, tabulated=False, dark_energy=False):
         """ChompScopeError unless correlation_cosmologies serves this object, these cosmologies
-        and `hods`; no device work.  Returns the HODs as objects (None without `hods`)."""
+        and `hods`; no device work.  tabulated / dark_energy: the caller's opt-ins, which let
+        tabulated redshift distributions / w0-wa cosmologies through.  Returns the HODs as
+        objects (None without `hods`)."""
         from . import cosmology
         from . import kernel as kernel_mod
         who, loop = "correlation_cosmologies", "set_cosmology (+ set_hod_object) + correlation"
@@ -268,17 +270,18 @@ class Correlation(object):
                    "z_bar per cosmology, as set_cosmology does")
         for name in ("window_function_a", "window_function_b"):
             dist = getattr(getattr(self.kernel, name, None), "_redshift_dist", None)
-            if isinstance(dist, kernel_mod.dNdzInterpolation):
+            if not tabulated and isinstance(dist, kernel_mod.dNdzInterpolation):
                 refuse("%s has a tabulated redshift distribution (%s)" % (name, type(dist).__name__))
         for i, c in enumerate(cosmo_dicts):
-            if cosmology.has_dark_energy(c):
+            if not dark_energy and cosmology.has_dark_energy(c):
                 refuse("cosmology %d has w0-wa dark energy" % i)
         if hods is not None and len(objs) != len(cosmo_dicts):
             raise ValueError("correlation_cosmologies: %d hods for %d cosmologies"
                              % (len(objs), len(cosmo_dicts)))
         return objs if hods is not None else None
 
-    def correlation_cosmologies(self, theta_rad, cosmo_dicts, hods=None, with_status=False):
+    def correlation_cosmologies(self, theta_rad, cosmo_dicts, hods=None, with_status=False,
+                                tabulated=False, dark_energy=False):
         """w(theta) for many cosmologies in one call: the array [len(cosmo_dicts), theta.size]
         whose row i is what set_cosmology(cosmo_dicts[i]) followed by correlation(theta_rad)
         returns on a fresh Correlation of the same kernel, halo parameters and HOD -- the loop
@@ -302,12 +305,18 @@ class Correlation(object):
         `self.cosmologies_z_bar` / `self.cosmologies_D_z` (the redshifts found and D there) and returned as the second element with
         with_status=True.  A torch cuda theta returns a tensor.
 
+        tabulated=True takes dNdzInterpolation / dNdChiGaussian windows (a dNdChiGaussian keeps
+        the table it was built with in every row, as in the loop), dark_energy=True takes w0-wa
+        cosmologies among the points (Lambda-CDM points beside them compute what they compute
+        in a Lambda-CDM batch).  Both are opt-ins of this call alone.
+
         ChompScopeError (before any launch): everything correlation_hods refuses, a kernel with
-        an assigned z_bar (after set_redshift), a dNdzInterpolation / dNdChiGaussian window, a
-        w0-wa cosmology among the points.  C_l (CorrelationFourier) is not batched over
-        cosmologies yet."""
+        an assigned z_bar (after set_redshift), without tabulated=True a dNdzInterpolation /
+        dNdChiGaussian window, without dark_energy=True a w0-wa cosmology among the points.
+        C_l (CorrelationFourier) is not batched over cosmologies yet."""
         cosmo_dicts = [dict(c) for c in cosmo_dicts]
-        objs = self._cosmologies_scope(cosmo_dicts, hods)
+        objs = self._cosmologies_scope(cosmo_dicts, hods, tabulated=tabulated,
+                                       dark_energy=dark_energy)
         return self._sets_batch(
             theta_rad, "cosmologies", "cosmology", len(cosmo_dicts), objs, with_status,
             lambda b0, n: cosmo_dicts[b0:b0 + n],
@@ -382,9 +391,11 @@ class Correlation(object):
     # -- the batch over kernels -------------------------------------------------
     _KERNELS_LOOP = "fresh Correlation objects, one per kernel, + correlation"
 
-    def _kernels_scope(self, kernels, hods=None):
+    def _kernels_scope(self, kernels, hods=None, tabulated=False, dark_energy=False):
         """ChompScopeError unless correlation_kernels serves this object, these kernels and
-        `hods`; no device work.  Returns the HODs as objects (None without `hods`)."""
+        `hods`; no device work.  tabulated / dark_energy: the caller's opt-ins, which let
+        tabulated redshift distributions / w0-wa cosmologies through.  Returns the HODs as
+        objects (None without `hods`)."""
         from . import cosmology
         from . import kernel as kernel_mod
         who, loop = "correlation_kernels", self._KERNELS_LOOP
@@ -407,16 +418,17 @@ class Correlation(object):
                        "finds z_bar per kernel" % i)
             for name in ("window_function_a", "window_function_b"):
                 dist = getattr(getattr(k, name, None), "_redshift_dist", None)
-                if isinstance(dist, kernel_mod.dNdzInterpolation):
+                if not tabulated and isinstance(dist, kernel_mod.dNdzInterpolation):
                     refuse("kernel %d: %s has a tabulated redshift distribution (%s)"
                            % (i, name, type(dist).__name__))
-            if cosmology.has_dark_energy(k.cosmo.cosmo_dict):
+            if not dark_energy and cosmology.has_dark_energy(k.cosmo.cosmo_dict):
                 refuse("kernel %d has a w0-wa cosmology" % i)
         if hods is not None and len(objs) != len(kernels):
             raise ValueError("correlation_kernels: %d hods for %d kernels" % (len(objs), len(kernels)))
         return objs if hods is not None else None
 
-    def correlation_kernels(self, theta_rad, kernels, hods=None, with_status=False):
+    def correlation_kernels(self, theta_rad, kernels, hods=None, with_status=False,
+                            tabulated=False, dark_energy=False):
         """w(theta) for many kernels in one call (on a CorrelationFourier: C_l, theta_rad being
         l; the two classes differ in _kernels_evaluate alone): the array [len(kernels),
         theta.size] whose row i is what a fresh object of this class, built on kernels[i] with a
@@ -441,13 +453,18 @@ class Correlation(object):
         `self.kernels_D_z`, and returned as the second element with with_status=True.  A torch
         cuda theta returns a tensor.
 
+        tabulated=True takes kernels with dNdzInterpolation / dNdChiGaussian windows -- the
+        photometric bins of a survey; a bin shared by several kernels is sent to the device once
+        --, dark_energy=True kernels with a w0-wa cosmology.  Both are opt-ins of this call alone.
+
         ChompScopeError (before any launch): everything correlation_hods refuses, a kernel whose
         type is not exactly this object's kernel's (Kernel or GalaxyGalaxyLensingKernel), a
-        kernel with another k theta range, a kernel with an assigned z_bar, a dNdzInterpolation /
-        dNdChiGaussian window, a w0-wa cosmology.  ValueError: `hods` of another length."""
+        kernel with another k theta range, a kernel with an assigned z_bar, without
+        tabulated=True a dNdzInterpolation / dNdChiGaussian window, without dark_energy=True a
+        w0-wa cosmology.  ValueError: `hods` of another length."""
         from . import kernel as kernel_mod
         kernels = list(kernels)
-        objs = self._kernels_scope(kernels, hods)
+        objs = self._kernels_scope(kernels, hods, tabulated=tabulated, dark_energy=dark_energy)
         return self._sets_batch(
             theta_rad, "kernels", "kernel", len(kernels), objs, with_status,
             lambda b0, n: [dict(k.cosmo.cosmo_dict) for k in kernels[b0:b0 + n]],
@@ -520,7 +537,8 @@ class CorrelationFourier(Correlation):
         return ctx.cell_epochs(code, 0, n_hod, self.D_z, flat)
 
     def _kernels_evaluate(self, ctx, code, n, D_z, flat):
-        """correlation_kernels(l, kernels, hods=None, with_status=False) is Correlation's,
+        """correlation_kernels(l, kernels, hods=None, with_status=False, tabulated=False,
+        dark_energy=False) is Correlation's,
         inherited whole, with this as its evaluating call: Context.cell_sets builds one chi-only
         node table per row (the set's windows, growth and chi range) and runs the rows' spectrum
         tables and Romberg integrals with a set axis, each row bit for bit what Context.cell

@@ -855,11 +855,12 @@ class CovarianceMulti(Covariance):
         return self.wcovar
 
     # -- every block in one call -------------------------------------------------
-    def _batched_scope(self, trispectrum=False):
+    def _batched_scope(self, trispectrum=False, tabulated=False):
         """ChompScopeError unless get_covariance_batched serves these blocks; no device work.
         Returns (the correlations, the spectrum's name).  trispectrum: the caller opted in to the
         one-halo trispectrum term (get_covariance_batched(trispectrum=True)); without it blocks
-        built with nongaussian_cov are refused as they always were."""
+        built with nongaussian_cov are refused as they always were.  tabulated: the caller opted
+        in to tabulated redshift distributions, refused without it as they always were."""
         from . import cosmology
         from . import hod as hod_mod
 
@@ -917,7 +918,7 @@ class CovarianceMulti(Covariance):
                        "(Correlation.set_redshift); the batch finds z_bar per kernel" % i)
             for name in ("window_function_a", "window_function_b"):
                 dist = getattr(getattr(k, name, None), "_redshift_dist", None)
-                if isinstance(dist, kernel_mod.dNdzInterpolation):
+                if not tabulated and isinstance(dist, kernel_mod.dNdzInterpolation):
                     refuse("correlation %d: %s has a tabulated redshift distribution (%s)"
                            % (i, name, type(dist).__name__))
             if cosmology.has_dark_energy(k.cosmo.cosmo_dict):
@@ -978,7 +979,7 @@ class CovarianceMulti(Covariance):
             b += n - i
         return ln_chi, sigma2
 
-    def get_covariance_batched(self, with_status=False, trispectrum=False):
+    def get_covariance_batched(self, with_status=False, trispectrum=False, tabulated=False):
         """get_covariance() with every block in one device call: the same `wcovar`, and the same
         `covar` in every ``covariance_list[i][j - i]`` (the Poisson diagonal of the matching
         blocks included), bit for bit what the loop over fresh correlations returns.
@@ -1008,6 +1009,12 @@ class CovarianceMulti(Covariance):
         the super-sample term the batch does not build the blocks' own KernelCovariance NG state
         (_kernel_array, ...).
 
+        tabulated=True opts in to kernels with tabulated redshift distributions (dNdzInterpolation,
+        dNdChiGaussian: the photometric bins of a survey; without the keyword they are refused, as
+        they always were).  The block kernels read the projection sets' tables only, so nothing
+        but the set-up of the sets knows of it: a bin shared by several kernels is sent to the
+        device once.
+
         The work: the correlations' kernels as projection sets on one kept grid.HaloGrid's context
         (Kernel._setup_pairs_on), ONE read-back of every kernel's z_bar -- the only
         synchronisation besides the result and the status words --, one HaloGrid epoch per
@@ -1027,15 +1034,15 @@ class CovarianceMulti(Covariance):
         ssc_cov or nongaussian_cov or do not share one halo_tri object and, with either term, in
         the k theta range or J0 limit of their KernelCovariance, or whose four windows have no
         redshift in common (the block is named); blocks whose power_spec, bins or areas differ; a
-        kernel that is not exactly kernel.Kernel, has an assigned z_bar, a tabulated redshift distribution, a w0-wa
-        cosmology or another k theta range; a halo
+        kernel that is not exactly kernel.Kernel, has an assigned z_bar, a tabulated redshift
+        distribution without tabulated=True, a w0-wa cosmology or another k theta range; a halo
         Correlation.correlation_hods would refuse, an HOD of another class, halos with different
         halo dictionaries or mass functions, two correlations sharing one Halo object; anything
         Covariance refuses for a cross block.  And, once z_bar is known: correlation 0's halo away
         from its z_bar (keep_halo_z_bar), which the loop's first block would be evaluated at."""
         import warnings
         from . import grid
-        corrs, power_spec = self._batched_scope(trispectrum=trispectrum)
+        corrs, power_spec = self._batched_scope(trispectrum=trispectrum, tabulated=tabulated)
         n = len(corrs)
         halos = [c.halo for c in corrs]
         h0 = halos[0]

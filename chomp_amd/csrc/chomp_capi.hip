@@ -30,6 +30,7 @@
 #include "chomp_pt_kernels.h"
 #include "chomp_tri_kernels.h"
 #include "chomp_profile_kernels.h"
+#include "chomp_pp_plan.h"
 
 using namespace chomp;
 
@@ -50,15 +51,6 @@ struct RoctxApi {
     }
     return false;
   }
-};
-
-// Dark-energy pressure tables of one kind of set-up (the epochs' or the projection's): one per
-// distinct (w0, wa), in the order `keys` lists them, valid while the keys stay the same.
-struct DeTables {
-  std::vector<DePar> keys;
-  DeviceBuffer<double> d_tab;
-  StagedBuffer<DePar> d_par;
-  bool valid = false;
 };
 
 struct chomp_ctx {
@@ -160,6 +152,9 @@ struct chomp_ctx {
   DeTables de_ep, de_proj;
   std::vector<int> de_slot;
   StagedBuffer<int> d_de_slot;
+  // What chomp_kernel_setup_sets / _pairs take beyond analytic windows in Lambda-CDM
+  // (chomp_set_sets_scope: CHOMP_SETS_* bits)
+  unsigned sets_scope = 0;
   // MassFunctionSecondOrder (chomp_set_second_order): the switch, and per epoch the sigma knots,
   // the sigma(nu) spline and bias_2_norm (B2Layout); have_b2: the last mass set-up made them
   int second_order = 0;
@@ -953,6 +948,14 @@ static int de_build(chomp_ctx* ctx, DeTables& T, const std::vector<DePar>& keys)
 int chomp_set_dark_energy(chomp_ctx* ctx, int on) {
   if (!ctx) return CHOMP_ERR_ARG;
   ctx->dark_energy = on != 0;
+  return CHOMP_OK;
+}
+
+int chomp_set_sets_scope(chomp_ctx* ctx, unsigned flags) {
+  if (!ctx) return CHOMP_ERR_ARG;
+  if (flags & ~(unsigned)(CHOMP_SETS_TABULATED | CHOMP_SETS_DARK_ENERGY))
+    return fail(ctx, CHOMP_ERR_ARG, "set_sets_scope: unknown flag");
+  ctx->sets_scope = flags;
   return CHOMP_OK;
 }
 

@@ -398,6 +398,9 @@ int chomp_kernel_table(chomp_ctx* ctx, int table, double* out, size_t n) {
 // me_z_min[s * step], me_z_max[s * step], a[s * step] and b[s * step] (step 0: one range and one
 // window pair for every set; 1: arrays); the k theta range and the Bessel order are shared.  The
 // callers have validated their arguments.  On the context's stream; ctx->proj is not touched.
+// Tabulated redshift distributions go to the sets' arena (chomp_pp_plan.h: equal tables share a
+// place) ahead of the launches; with a w0-wa cosmology among the sets, the distinct (w0, wa) get
+// their pressure tables in S.de and the two kernels that evaluate E(z) run their <true> forms.
 // who: the caller's name.
 static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, const chomp_cosmo* cosmo,
                               const double* me_z_min, const double* me_z_max, size_t step,
@@ -415,12 +418,60 @@ static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, con
   if (!rc) rc = ensure(ctx, S.d_pd_init, n_set);
   if (!rc) rc = ensure(ctx, S.d_tab, n_set * (size_t)L.total);
   if (rc) return rc;
+  // the tables of the windows (step 0: of the one pair), window w of set s at [2 s + w]
+  const size_t n_pair = step ? n_set : 1;
+  std::vector<PpTable> tables(2 * n_pair, PpTable{nullptr, nullptr, 0, 0});
+  bool tabulated = false;
+  for (size_t s = 0; s < n_pair; ++s)
+    for (int w = 0; w < 2; ++w) {
+      const chomp_dndz& dz = (w == 0 ? a : b)[s].dist;
+      if (dz.kind != CHOMP_DNDZ_PPOLY) continue;
+      tables[2 * s + w] = PpTable{dz.pp_breaks, dz.pp_coef, dz.pp_n, dz.pp_order};
+      tabulated = true;
+    }
+  PpPlan plan;
+  if (tabulated) {
+    if (!pp_plan(tables.data(), tables.size(), &plan))
+      return fail(ctx, CHOMP_ERR_ARG, w_ + "the distinct tabulated redshift distributions of one call "
+                                           "exceed " + std::to_string(kPpArenaMax) + " doubles");
+    rc = ensure(ctx, S.d_pp, plan.total);
+    if (rc) return rc;
+    std::vector<double> arena(plan.total);
+    pp_pack(tables.data(), plan, arena.data());
+    rc = upload(ctx, S.d_pp, arena.data(), plan.total * sizeof(double));
+    if (rc) return rc;
+  }
+  // the pressure tables of the distinct (w0, wa), and every set's
+  std::vector<DePar> de_keys;
+  std::vector<int> de_slot(n_set, -1);
+  for (size_t s = 0; s < n_set; ++s) {
+    if (!has_dark_energy(cosmo[s].w0, cosmo[s].wa)) continue;
+    size_t q = 0;
+    while (q < de_keys.size() && !(de_keys[q].w0 == cosmo[s].w0 && de_keys[q].wa == cosmo[s].wa)) ++q;
+    if (q == de_keys.size()) de_keys.push_back(DePar{cosmo[s].w0, cosmo[s].wa});
+    de_slot[s] = (int)q;
+  }
+  DeSets de{nullptr, nullptr, 0, 0};
+  if (!de_keys.empty()) {
+    rc = de_build(ctx, S.de, de_keys);
+    if (!rc) rc = ensure(ctx, S.d_de_slot, n_set);
+    if (!rc) rc = upload(ctx, S.d_de_slot, de_slot.data(), n_set * sizeof(int));
+    if (rc) return rc;
+    de = DeSets{S.de.d_tab, S.d_de_slot, de_stride(c.cosmo_npoints), c.cosmo_npoints};
+  }
   const double j_limit = bessel_zero_host(bessel_order, c.kernel_bessel_limit);
   std::vector<ProjDev> pd(n_set);
   for (size_t s = 0; s < n_set; ++s) {
     const chomp_window* ws[2] = {&a[s * step], &b[s * step]};
     pd[s] = proj_host_block(c, &cosmo[s], me_z_min[s * step], me_z_max[s * step], ktheta_min,
                             ktheta_max, ws, bessel_order, j_limit);
+    for (int w = 0; w < 2 && tabulated; ++w) {
+      const long long at = plan.offset[2 * (s * step) + w];
+      if (at < 0) continue;
+      pd[s].dist[w].pp = S.d_pp + at;
+      pd[s].dist[w].pp_n = ws[w]->dist.pp_n;
+      pd[s].dist[w].pp_order = ws[w]->dist.pp_order;
+    }
   }
   rc = upload(ctx, S.d_pd_init, pd.data(), n_set * sizeof(ProjDev));
   if (rc) return rc;
@@ -435,12 +486,20 @@ static int kernel_sets_launch(chomp_ctx* ctx, const char* who, size_t n_set, con
   }
   const unsigned Z = (unsigned)n_set;
   const size_t stride = (size_t)L.total;
-  hipLaunchKernelGGL(k_proj_chi_sets, dim3(L.NC, 4, Z), dim3(64), 0, ctx->stream, c, L, S.d_pd, S.d_tab, stride);
+  if (de.tab)
+    hipLaunchKernelGGL(k_proj_chi_sets<true>, dim3(L.NC, 4, Z), dim3(64), 0, ctx->stream, c, L, S.d_pd, S.d_tab, stride, de);
+  else
+    hipLaunchKernelGGL(k_proj_chi_sets<false>, dim3(L.NC, 4, Z), dim3(64), 0, ctx->stream, c, L, S.d_pd, S.d_tab, stride, de);
   hipLaunchKernelGGL(k_proj_me_splines_sets, dim3(3, 1, Z), dim3(192), (size_t)(33 * L.NC) * sizeof(double),
                      ctx->stream, c, L, S.d_pd, S.d_tab, stride);
-  hipLaunchKernelGGL(k_proj_window_sets, dim3(L.NWp, 2, Z), dim3(64),
-                     (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, S.d_pd,
-                     S.d_tab, stride);
+  if (de.tab)
+    hipLaunchKernelGGL(k_proj_window_sets<true>, dim3(L.NWp, 2, Z), dim3(64),
+                       (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, S.d_pd,
+                       S.d_tab, stride, de);
+  else
+    hipLaunchKernelGGL(k_proj_window_sets<false>, dim3(L.NWp, 2, Z), dim3(64),
+                       (size_t)(L.NC + 4 * (L.NC - 1)) * sizeof(double), ctx->stream, c, L, S.d_pd,
+                       S.d_tab, stride, de);
   hipLaunchKernelGGL(k_proj_window_splines_sets, dim3(1, 1, Z), dim3(128),
                      (size_t)(22 * L.NWp) * sizeof(double), ctx->stream, c, L, S.d_pd, S.d_tab, stride);
   hipLaunchKernelGGL(k_proj_kernel_knots_sets, dim3(L.NKT, 1, Z), dim3(256),
@@ -464,12 +523,12 @@ int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cos
   if (n_set > (size_t)kProjSetsMax)
     return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: more than " + std::to_string(kProjSetsMax) + " sets in one call");
   if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_sets: bessel order must be 0 or 2");
-  for (size_t s = 0; s < n_set; ++s)
+  for (size_t s = 0; s < n_set && !(ctx->sets_scope & CHOMP_SETS_DARK_ENERGY); ++s)
     if (has_dark_energy(cosmo[s].w0, cosmo[s].wa))
       return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a w0/wa != -1/0 cosmology is set up by chomp_kernel_setup");
   const chomp_window* ws[2] = {a, b};
   { const int rcc = proj_check_args(ctx, "kernel_setup_sets", ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
-  for (int w = 0; w < 2; ++w)
+  for (int w = 0; w < 2 && !(ctx->sets_scope & CHOMP_SETS_TABULATED); ++w)
     if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
       return fail(ctx, CHOMP_ERR_SCOPE, "kernel_setup_sets: a tabulated redshift distribution "
                                         "(dNdzInterpolation) is set up by chomp_kernel_setup");
@@ -494,11 +553,11 @@ int chomp_kernel_setup_pairs(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* co
   if (bessel_order != 0 && bessel_order != 2) return fail(ctx, CHOMP_ERR_ARG, "kernel_setup_pairs: bessel order must be 0 or 2");
   for (size_t s = 0; s < n_set; ++s) {
     const std::string ws_ = "kernel_setup_pairs: set " + std::to_string(s);
-    if (has_dark_energy(cosmo[s].w0, cosmo[s].wa))
+    if (!(ctx->sets_scope & CHOMP_SETS_DARK_ENERGY) && has_dark_energy(cosmo[s].w0, cosmo[s].wa))
       return fail(ctx, CHOMP_ERR_SCOPE, ws_ + ": a w0/wa != -1/0 cosmology is set up by chomp_kernel_setup");
     const chomp_window* ws[2] = {&a[s], &b[s]};
     { const int rcc = proj_check_args(ctx, ws_.c_str(), ktheta_min, ktheta_max, ws); if (rcc) return rcc; }
-    for (int w = 0; w < 2; ++w)
+    for (int w = 0; w < 2 && !(ctx->sets_scope & CHOMP_SETS_TABULATED); ++w)
       if (ws[w]->dist.kind == CHOMP_DNDZ_PPOLY)
         return fail(ctx, CHOMP_ERR_SCOPE, ws_ + ": a tabulated redshift distribution "
                                           "(dNdzInterpolation) is set up by chomp_kernel_setup");

@@ -13,6 +13,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
+#include "chomp_buffers.h"
 #include "chomp_mass_kernels.h"
 
 namespace chomp {
@@ -22,6 +25,16 @@ constexpr unsigned kStDeDivmax = CHOMP_ST_DE_DIVMAX;
 // One (w0, wa) pair per table.
 struct DePar {
   double w0, wa;
+};
+
+// Dark-energy pressure tables of one kind of set-up (the epochs', the projection's or the
+// projection sets'): one per distinct (w0, wa), in the order `keys` lists them, valid while the
+// keys stay the same.
+struct DeTables {
+  std::vector<DePar> keys;
+  DeviceBuffer<double> d_tab;
+  StagedBuffer<DePar> d_par;
+  bool valid = false;
 };
 
 // Knots in the order the reference lists them: a ascending, so z_i descending and knot 0 the

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chomp_buffers.h"
+#include "chomp_de_kernels.h"
 #include "chomp_power_kernels.h"
 
 namespace chomp {
@@ -107,7 +108,11 @@ struct ProjState {
 
 // The projection set-ups of chomp_kernel_setup_sets / chomp_kernel_setup_pairs, beside ProjState
 // (which they never touch): n ProjDev blocks and n slabs of L.total doubles, set s at d_pd[s] and d_tab + s * L.total.
-// The buffers are kept across calls and only grow.
+// The buffers are kept across calls and only grow.  The sets have their own arena of tabulated
+// redshift distributions (d_pp: the distinct tables of the last call, placed by chomp_pp_plan.h;
+// the blocks' dist[w].pp point into it and are rebuilt every call, so a moved arena is harmless)
+// and their own pressure tables (de, with every set's table in d_de_slot, -1 for Lambda-CDM):
+// the single set-up's tables (behind ProjState::d_tab, chomp_ctx::de_proj) are not touched.
 struct ProjSets {
   size_t n = 0;            // sets of the last set-up of sets (0: none yet)
   ProjLayout L;
@@ -115,6 +120,9 @@ struct ProjSets {
   DeviceBuffer<ProjDev> d_pd;
   StagedBuffer<ProjDev> d_pd_init;   // the blocks as the host prepared them (the device fills d_pd in)
   DeviceBuffer<double> d_tab;
+  StagedBuffer<double> d_pp;
+  DeTables de;
+  StagedBuffer<int> d_de_slot;
 };
 
 // ---------------------------------------------------------------------------
@@ -387,23 +395,24 @@ struct DndzRaw {
 
 // grid (NC, 4), block 64.  y < 3: chi and growth of MultiEpoch y at grid point x;
 // y == 3, x < 2: normalisation of distribution x.  DE: E with the pressure spline `de`.
-// (the body of k_proj_chi and k_proj_chi_sets)
+// (the body of k_proj_chi and k_proj_chi_sets, in its two parts: the normalising blocks, which
+//  hold the body's only barrier and never look at E, and the grid points)
+__device__ __forceinline__ void proj_chi_norm(const chomp_config& cfg, ProjDev* __restrict__ pd) {
+  const int i = blockIdx.x;
+  if (i >= 2) return;
+  __shared__ DndzDev D;
+  if (threadIdx.x == 0) D = pd->dist[i];
+  __syncthreads();
+  DndzRaw f{&D};
+  const double norm = romberg1<1>(f, D.z_min, D.z_max, cfg.global_precision,
+                                  cfg.dNdz_precision, cfg.divmax, nullptr);
+  if (threadIdx.x == 0) pd->dist[i].norm = 1.0 / norm;
+}
 template <bool DE>
-__device__ __forceinline__ void proj_chi_body(const chomp_config& cfg, const ProjLayout& L,
-                                              ProjDev* __restrict__ pd, double* __restrict__ tab,
-                                              const DeSpline& de) {
+__device__ __forceinline__ void proj_chi_point(const chomp_config& cfg, const ProjLayout& L,
+                                               ProjDev* __restrict__ pd, double* __restrict__ tab,
+                                               const DeSpline& de) {
   const int i = blockIdx.x, m = blockIdx.y;
-  if (m == 3) {
-    if (i >= 2) return;
-    __shared__ DndzDev D;
-    if (threadIdx.x == 0) D = pd->dist[i];
-    __syncthreads();
-    DndzRaw f{&D};
-    const double norm = romberg1<1>(f, D.z_min, D.z_max, cfg.global_precision,
-                                    cfg.dNdz_precision, cfg.divmax, nullptr);
-    if (threadIdx.x == 0) pd->dist[i].norm = 1.0 / norm;
-    return;
-  }
   const double z = linspace_at(pd->me_z_min[m], pd->me_z_max[m], L.NC, i);
   double chi;
   if constexpr (DE) {
@@ -420,6 +429,13 @@ __device__ __forceinline__ void proj_chi_body(const chomp_config& cfg, const Pro
   }
 }
 template <bool DE>
+__device__ __forceinline__ void proj_chi_body(const chomp_config& cfg, const ProjLayout& L,
+                                              ProjDev* __restrict__ pd, double* __restrict__ tab,
+                                              const DeSpline& de) {
+  if (blockIdx.y == 3) { proj_chi_norm(cfg, pd); return; }
+  proj_chi_point<DE>(cfg, L, pd, tab, de);
+}
+template <bool DE>
 __global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
                                                  ProjDev* __restrict__ pd,
                                                  double* __restrict__ tab, DeSpline de) {
@@ -431,18 +447,43 @@ __global__ __launch_bounds__(64) void k_proj_chi(chomp_config cfg, ProjLayout L,
 // takes its cosmology from its ProjDev block and its tables from one slab of ProjLayout::total
 // doubles, and none of their grids uses blockIdx.z: the *_sets forms run the same bodies with
 // set blockIdx.z's block pd[blockIdx.z] and its slab, `stride` doubles after the previous set's.
-// Lambda-CDM only (no pressure spline) and no tabulated redshift distribution (those ride behind
-// the single set-up's slab).  kProjSetsMax: the sets of one call -- 1024 slabs of the default
-// layout (3752 doubles) are 29 MiB; a grid's z dimension would allow 65535.
+// A tabulated redshift distribution of a set is read where its block's dist[w].pp points: into
+// the sets' own arena of tables (ProjSets::d_pp, laid out by chomp_pp_plan.h), never behind the
+// single set-up's slab.  Dark energy: a batch with a w0-wa cosmology runs the <true> forms of the
+// two kernels that evaluate E(z) (k_proj_chi_sets, k_proj_window_sets) with DeSets, the sets'
+// pressure tables and a slot per set; a batch without one runs the <false> forms, which are the
+// kernels of a Lambda-CDM batch and ignore it.  kProjSetsMax: the sets of one call -- 1024 slabs
+// of the default layout (3752 doubles) are 29 MiB; a grid's z dimension would allow 65535.
 constexpr int kProjSetsMax = CHOMP_KERNEL_SETS_MAX;   // 1024
 static_assert(kProjSetsMax <= 65535, "the set axis is a grid's z dimension");
 
+// The pressure tables of a batch of sets: table t at tab + t * stride (de_stride(n) doubles, n =
+// cosmo_npoints), and per set its table, or -1 for a Lambda-CDM set -- which then runs the
+// arithmetic it runs in a pure Lambda-CDM batch.  The choice is uniform over a block.
+struct DeSets {
+  const double* tab;
+  const int* slot;
+  int stride, n;
+};
+
 // grid (NC, 4, n_set), block 64.
+template <bool DE>
 __global__ __launch_bounds__(64) void k_proj_chi_sets(chomp_config cfg, ProjLayout L,
                                                       ProjDev* __restrict__ pd,
-                                                      double* __restrict__ tab, size_t stride) {
-  proj_chi_body<false>(cfg, L, pd + blockIdx.z, tab + stride * blockIdx.z,
-                       DeSpline{nullptr, nullptr, 0});
+                                                      double* __restrict__ tab, size_t stride,
+                                                      DeSets de) {
+  ProjDev* p = pd + blockIdx.z;
+  double* t = tab + stride * blockIdx.z;
+  if constexpr (DE) {
+    if (blockIdx.y == 3) { proj_chi_norm(cfg, p); return; }
+    const int slot = de.slot[blockIdx.z];
+    if (slot >= 0)            // (no barrier on either side)
+      proj_chi_point<true>(cfg, L, p, t, de_spline(de.tab + (size_t)slot * de.stride, de.n));
+    else
+      proj_chi_point<false>(cfg, L, p, t, DeSpline{nullptr, nullptr, 0});
+  } else {
+    proj_chi_body<false>(cfg, L, p, t, DeSpline{nullptr, nullptr, 0});
+  }
 }
 
 // MultiEpoch lookups with the reference's range rules (cosmology.py:873-953).
@@ -558,20 +599,29 @@ struct LensIntegrand {
 };
 
 // grid (NWp, 2), block 64: raw window function of window y at its x-th chi knot.
-// (the body of k_proj_window and k_proj_window_sets)
-template <bool DE>
-__device__ __forceinline__ void proj_window_body(const chomp_config& cfg, const ProjLayout& L,
-                                                 const ProjDev* __restrict__ pd,
-                                                 double* __restrict__ tab, const DeSpline& de) {
-  extern __shared__ __align__(16) double sm[];
+// (the body of k_proj_window and k_proj_window_sets, in its two parts: the staging of the
+//  MultiEpoch's chi knots and z(chi) spline in `sm` and of the distribution in LDS, with the
+//  body's only barrier, and the value, which alone looks at E)
+__device__ __forceinline__ const DndzDev* proj_window_stage(const ProjLayout& L,
+                                                            const ProjDev* __restrict__ pd,
+                                                            const double* __restrict__ tab,
+                                                            double* sm) {
   __shared__ DndzDev D;
-  const int i = blockIdx.x, w = blockIdx.y, m = w + 1, NC = L.NC;
-  double* chi_knots = sm;
-  double* pp_z = sm + NC;
-  copy_doubles(chi_knots, tab + L.me_chi[m], NC);
-  copy_doubles(pp_z, tab + L.me_pp_z[m], 4 * (NC - 1));
+  const int w = blockIdx.y, m = w + 1, NC = L.NC;
+  copy_doubles(sm, tab + L.me_chi[m], NC);
+  copy_doubles(sm + NC, tab + L.me_pp_z[m], 4 * (NC - 1));
   if (threadIdx.x == 0) D = pd->dist[w];
   __syncthreads();
+  return &D;
+}
+template <bool DE>
+__device__ __forceinline__ void proj_window_value(const chomp_config& cfg, const ProjLayout& L,
+                                                  const ProjDev* __restrict__ pd,
+                                                  double* __restrict__ tab, const DeSpline& de,
+                                                  const double* sm, const DndzDev& D) {
+  const int i = blockIdx.x, w = blockIdx.y, NC = L.NC;
+  const double* chi_knots = sm;
+  const double* pp_z = sm + NC;
   const double chi = tab[L.w_chi[w] + i];
   const double z = spline_eval(chi_knots, pp_z, NC, chi);
   double val;
@@ -601,17 +651,38 @@ __device__ __forceinline__ void proj_window_body(const chomp_config& cfg, const 
   if (threadIdx.x == 0) tab[L.w_wf[w] + i] = val;
 }
 template <bool DE>
+__device__ __forceinline__ void proj_window_body(const chomp_config& cfg, const ProjLayout& L,
+                                                 const ProjDev* __restrict__ pd,
+                                                 double* __restrict__ tab, const DeSpline& de) {
+  extern __shared__ __align__(16) double sm[];
+  const DndzDev* D = proj_window_stage(L, pd, tab, sm);
+  proj_window_value<DE>(cfg, L, pd, tab, de, sm, *D);
+}
+template <bool DE>
 __global__ __launch_bounds__(64) void k_proj_window(chomp_config cfg, ProjLayout L,
                                                     const ProjDev* __restrict__ pd,
                                                     double* __restrict__ tab, DeSpline de) {
   proj_window_body<DE>(cfg, L, pd, tab, de);
 }
-// ... with the set axis: grid (NWp, 2, n_set), block 64.
+// ... with the set axis: grid (NWp, 2, n_set), block 64.  DE: as k_proj_chi_sets.
+template <bool DE>
 __global__ __launch_bounds__(64) void k_proj_window_sets(chomp_config cfg, ProjLayout L,
                                                          const ProjDev* __restrict__ pd,
-                                                         double* __restrict__ tab, size_t stride) {
-  proj_window_body<false>(cfg, L, pd + blockIdx.z, tab + stride * blockIdx.z,
-                          DeSpline{nullptr, nullptr, 0});
+                                                         double* __restrict__ tab, size_t stride,
+                                                         DeSets de) {
+  const ProjDev* p = pd + blockIdx.z;
+  double* t = tab + stride * blockIdx.z;
+  if constexpr (DE) {
+    extern __shared__ __align__(16) double sm[];
+    const DndzDev* D = proj_window_stage(L, p, t, sm);
+    const int slot = de.slot[blockIdx.z];
+    if (slot >= 0)            // (no barrier on either side)
+      proj_window_value<true>(cfg, L, p, t, de_spline(de.tab + (size_t)slot * de.stride, de.n), sm, *D);
+    else
+      proj_window_value<false>(cfg, L, p, t, DeSpline{nullptr, nullptr, 0}, sm, *D);
+  } else {
+    proj_window_body<false>(cfg, L, p, t, DeSpline{nullptr, nullptr, 0});
+  }
 }
 
 // Window lookup with the range rule of kernel.py:326-340 (uniform chi knots).

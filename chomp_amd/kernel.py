@@ -296,6 +296,24 @@ class WindowFunctionConvergenceDelta(WindowFunction):
         self._redshift_dist = dNdz(0.0, redshift)              # (carries the limits only)
 
 
+def _is_tabulated(window):
+    """The window's redshift distribution is a table (dNdzInterpolation, dNdChiGaussian)."""
+    return getattr(getattr(window, "_redshift_dist", None), "_kind", None) == _lib.DNDZ_PPOLY
+
+
+def _sets_kw(kernels, cosmos):
+    """The opt-ins of Context.kernel_setup_sets / kernel_setup_pairs that `kernels` over
+    `cosmos` (as cosmology._de_kw takes them) need: tabulated=True when some window's
+    distribution is a table, dark_energy=True when some cosmology has w0-wa dark energy, and
+    nothing otherwise, so that a set-up of analytic windows in Lambda-CDM is called as it always
+    was."""
+    kw = dict(cosmology._de_kw(cosmos))
+    if any(_is_tabulated(w) for k in kernels
+           for w in (k.window_function_a, k.window_function_b)):
+        kw["tabulated"] = True
+    return kw
+
+
 class Kernel(object):
     """K(k theta) = int dchi W_a W_b D^2 J0(k theta chi) (kernel.py:559-781)."""
     _order = 0
@@ -354,7 +372,8 @@ class Kernel(object):
         ctx.kernel_setup_sets(cosmo_dicts, self.cosmo.z_min, self.cosmo.z_max,
                               self._ktheta[0], self._ktheta[1],
                               self.window_function_a._struct(),
-                              self.window_function_b._struct(), self._order)
+                              self.window_function_b._struct(), self._order,
+                              **_sets_kw([self], cosmo_dicts))
         return ctx
 
     @staticmethod
@@ -369,7 +388,8 @@ class Kernel(object):
                                [k.cosmo.z_min for k in kernels], [k.cosmo.z_max for k in kernels],
                                first._ktheta[0], first._ktheta[1],
                                [k.window_function_a._struct() for k in kernels],
-                               [k.window_function_b._struct() for k in kernels], first._order)
+                               [k.window_function_b._struct() for k in kernels], first._order,
+                               **_sets_kw(kernels, [k.cosmo.cosmo_dict for k in kernels]))
         return ctx
 
     def _dev(self):

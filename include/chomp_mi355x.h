@@ -689,8 +689,9 @@ int chomp_kernel_table(chomp_ctx* ctx, int table, double* out, size_t n);
  * across calls.  Set s holds, bit for bit, what chomp_kernel_setup(ctx, &cosmo[s], ...) builds.
  * Validates what chomp_kernel_setup validates; in addition CHOMP_ERR_SCOPE, before anything is
  * launched, for a CHOMP_DNDZ_PPOLY distribution and for any cosmology with w0/wa != -1/0 (both
- * are set up by chomp_kernel_setup, one cosmology at a time), and CHOMP_ERR_ARG for n_set = 0 or
- * n_set > CHOMP_KERNEL_SETS_MAX (callers work longer designs off in blocks of that size). */
+ * are set up by chomp_kernel_setup, one cosmology at a time) unless chomp_set_sets_scope, below,
+ * has let them in, and CHOMP_ERR_ARG for n_set = 0 or n_set > CHOMP_KERNEL_SETS_MAX (callers
+ * work longer designs off in blocks of that size). */
 #define CHOMP_KERNEL_SETS_MAX 1024
 int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo /*[n_set]*/,
                             double me_z_min, double me_z_max, double ktheta_min,
@@ -709,13 +710,32 @@ int chomp_kernel_setup_sets(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cos
  * chomp_cell_sets serve either set-up.  Every set is validated before anything is launched and a
  * refusal names the set ("set 1"): what chomp_kernel_setup_sets validates, with all four window
  * kinds of chomp_kernel_setup; CHOMP_ERR_SCOPE for a CHOMP_DNDZ_PPOLY distribution or a w0/wa !=
- * -1/0 cosmology in any set; CHOMP_ERR_ARG for n_set = 0, n_set > CHOMP_KERNEL_SETS_MAX and null
- * arrays. */
+ * -1/0 cosmology in any set (unless chomp_set_sets_scope has let them in); CHOMP_ERR_ARG for
+ * n_set = 0, n_set > CHOMP_KERNEL_SETS_MAX and null arrays. */
 int chomp_kernel_setup_pairs(chomp_ctx* ctx, size_t n_set, const chomp_cosmo* cosmo /*[n_set]*/,
                              const double* me_z_min /*[n_set]*/, const double* me_z_max /*[n_set]*/,
                              double ktheta_min, double ktheta_max,
                              const chomp_window* a /*[n_set]*/, const chomp_window* b /*[n_set]*/,
                              int bessel_order);
+/* What the two calls above take beyond analytic distributions in Lambda-CDM, opt-in (flags: an
+ * OR of CHOMP_SETS_*, 0 at creation; CHOMP_ERR_ARG for an unknown bit).  With a flag off, the
+ * calls refuse that input as they always did, with the same text; nothing else reads the flags.
+ *   CHOMP_SETS_TABULATED    CHOMP_DNDZ_PPOLY distributions.  The distinct tables of a call -- equal
+ *     in pp_n, pp_order and bytes, whatever their addresses: five bins behind 15 kernels are five
+ *     tables -- are copied, during the call, into an arena of the sets' own, which is kept across
+ *     calls and only grows.  CHOMP_ERR_ARG when they exceed 2^22 doubles (32 MiB: nine tables of
+ *     65536 pieces of order 5); nothing is allocated or copied then.
+ *   CHOMP_SETS_DARK_ENERGY  cosmologies with w0/wa != -1/0, whatever chomp_set_dark_energy says.
+ *     The distinct (w0, wa) of a call get pressure tables of the sets' own (as chomp_set_dark_energy
+ *     describes them), and the two launches that evaluate E(z) run in a form that looks its set's
+ *     table up; a Lambda-CDM set beside them does the arithmetic of a Lambda-CDM batch, and a
+ *     batch without a w0-wa cosmology makes the launches it makes with the flag off.
+ * Either way set s holds, bit for bit, what chomp_kernel_setup builds for it (with
+ * chomp_set_dark_energy(ctx, 1) where its cosmology needs that), and the single set-up, its
+ * tables behind it and its pressure table stay as they are. */
+#define CHOMP_SETS_TABULATED 1u
+#define CHOMP_SETS_DARK_ENERGY 2u
+int chomp_set_sets_scope(chomp_ctx* ctx, unsigned flags);
 /* chomp_kernel_info of every set of the last set-up of sets: out[s * CHOMP_KI_COUNT +
  * CHOMP_KI_*], in ONE synchronising read-back.  CHOMP_ERR_STATE before any such set-up. */
 int chomp_kernel_info_sets(chomp_ctx* ctx, double* out /*[n_set * CHOMP_KI_COUNT]*/);
