@@ -153,8 +153,8 @@ EXPORTS = [
     "chomp_tri_setup", "chomp_tri_table_eval", "chomp_tri_terms", "chomp_tri_proj",
     "chomp_tri_triple",
     "chomp_kernel_ng_setup", "chomp_kernel_ng_raw", "chomp_kernel_ng_eval",
-    "chomp_covariance_ng",
-    "chomp_cov_ng_blocks", "chomp_cov_ng_blocks_table", "chomp_cov_ng_blocks_plan",
+    "chomp_covariance_ng", "chomp_covariance_ng_blocks", "chomp_covariance_ng_blocks_table",
+    "chomp_covariance_ng_blocks_plan",
     "chomp_covariance_cross_range", "chomp_kernel_ssc_setup_cross", "chomp_covariance_ssc_cross",
     "chomp_set_general_profile", "chomp_y_general", "chomp_y_general_table",
     "chomp_halo_normalization",
@@ -493,11 +493,11 @@ def lib():
         L.chomp_kernel_ng_raw.argtypes = [vp, vp, sz, vp]
         L.chomp_kernel_ng_eval.argtypes = [vp, vp, sz, vp]
         L.chomp_covariance_ng.argtypes = [vp, d, vp, sz, d, d, vp, sz, vp, vp, vp]
-        L.chomp_cov_ng_blocks.argtypes = [vp, sz, ctypes.POINTER(sz), d, d, d, d, c_double_p,
+        L.chomp_covariance_ng_blocks.argtypes = [vp, sz, ctypes.POINTER(sz), d, d, d, d, c_double_p,
                                                  sz, d, d, vp, sz, vp, i]
-        L.chomp_cov_ng_blocks_table.argtypes = [vp, sz] + [c_double_p] * 6
-        L.chomp_cov_ng_blocks_plan.argtypes = [sz, ctypes.POINTER(sz), sz, sz, sz, sz,
-                                               ctypes.POINTER(sz), ctypes.POINTER(i)]
+        L.chomp_covariance_ng_blocks_table.argtypes = [vp, sz] + [c_double_p] * 6
+        L.chomp_covariance_ng_blocks_plan.argtypes = [sz, ctypes.POINTER(sz), sz, sz, sz, sz,
+                                                      ctypes.POINTER(sz), ctypes.POINTER(i)]
         L.chomp_xi3d.argtypes = [vp, i, sz, d, d, vp, sz, vp, i]
         L.chomp_xi3d_epochs.argtypes = [vp, i, sz, sz, d, d, vp, sz, vp, i]
         L.chomp_spline_eval.argtypes = [vp, vp, vp, sz, vp, sz, i, vp]
@@ -509,9 +509,9 @@ def lib():
         return _lib
 
 
-def cov_ng_blocks_plan(n_corr, n_pairs, n_ktheta, n_k, n_tri, epochs=None):
+def covariance_ng_blocks_plan(n_corr, n_pairs, n_ktheta, n_k, n_tri, epochs=None):
     """What Context.covariance_ng_blocks keeps on the device for n_corr correlations and n_pairs
-    pairs of angles (chomp_cov_ng_blocks_plan; host arithmetic, no device): (sizes, index) --
+    pairs of angles (chomp_covariance_ng_blocks_plan; host arithmetic, no device): (sizes, index) --
     sizes a dict of element counts (n_blocks, slab, slabs, kb, tri, index), index the call's index
     block: epoch[n_corr] | (i, j)[n_blocks] | the diagonal blocks | the cross blocks."""
     n_corr = int(n_corr)
@@ -521,13 +521,13 @@ def cov_ng_blocks_plan(n_corr, n_pairs, n_ktheta, n_k, n_tri, epochs=None):
     if epochs is not None:
         ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
         if ep.size != n_corr:
-            raise ValueError("cov_ng_blocks_plan: epochs must be [n_corr]")
-    rc = lib().chomp_cov_ng_blocks_plan(
+            raise ValueError("covariance_ng_blocks_plan: epochs must be [n_corr]")
+    rc = lib().chomp_covariance_ng_blocks_plan(
         n_corr, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)) if ep is not None else None,
         int(n_pairs), int(n_ktheta), int(n_k), int(n_tri), sizes,
         index.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
     if rc:
-        raise ValueError("cov_ng_blocks_plan: sizes beyond what covariance_ng_blocks takes")
+        raise ValueError("covariance_ng_blocks_plan: sizes beyond what covariance_ng_blocks takes")
     names = ("n_blocks", "slab", "slabs", "kb", "tri", "index")
     return dict(zip(names, (int(v) for v in sizes))), index
 
@@ -1379,20 +1379,51 @@ class Context(object):
         (theta_a, theta_b): host arrays of one length; or theta_a alone, a contiguous float64
         torch cuda tensor holding theta_a[n] then theta_b[n], which stays on the device (so does
         the result; the Poisson terms are sent there)."""
+        def args(n_blocks):
+            p = numpy.ascontiguousarray(poisson, dtype=numpy.float64)
+            if p.shape != (n_blocks, 4):
+                raise ValueError("covariance_blocks: poisson must be [%d, 4]" % n_blocks)
+            return (int(which),), (float(j0_limit), float(area)), [p]
+        return self._blocks(self._L.chomp_covariance_blocks, epochs, theta_a, theta_b, args)
+
+    def _blocks(self, fn, epochs, theta_a, theta_b, args, term=None):
+        """A covariance_*_blocks call, fn(handle, *head, n_corr, epochs, *middle, *sent, pairs,
+        n_pairs, out, mem): out [n_blocks, n_pairs].  args(n_blocks) checks the call's own arrays
+        and returns (head, middle, sent), `sent` the host arrays that go where the pairs are.
+        term: the pair count covariance_<term>_blocks_table sizes the k_b knots by, remembered
+        after a successful call only -- a refused call leaves the last result readable, its k_b
+        knots included (the C call gives its state up behind its last refusal only)."""
         ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
         n_blocks = ep.size * (ep.size + 1) // 2
-        p = numpy.ascontiguousarray(poisson, dtype=numpy.float64)
-        if p.shape != (n_blocks, 4):
-            raise ValueError("covariance_blocks: poisson must be [%d, 4]" % n_blocks)
+        head, middle, sent = args(n_blocks)
         pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
-        if _is_torch(pairs):
+        if sent and _is_torch(pairs):
             import torch
-            p = torch.as_tensor(p, device=pairs.device)
-        return self._run(self._L.chomp_covariance_blocks, [pairs, p],
-                         lambda mem, new, th, po: (
-                             int(which), ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
-                             float(j0_limit), float(area), po, th, _numel(th) // 2,
-                             new((n_blocks, _numel(th) // 2)), mem))[0]
+            sent = [torch.as_tensor(x, device=pairs.device) for x in sent]
+        out = self._run(fn, [pairs] + sent, lambda mem, new, th, *on: head + (
+            ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))) + middle + on + (
+                th, _numel(th) // 2, new((n_blocks, _numel(th) // 2)), mem))[0]
+        if term:
+            setattr(self, "_%s_blocks_pairs" % term, _numel(pairs) // 2)
+        return out
+
+    def _blocks_table(self, fn, term, block, knots, minimum=False):
+        """One block of the last covariance_<term>_blocks, fn(handle, block, info, table, levels,
+        [table_min,] kb_knots, kb_levels): (info [7], table and Romberg levels [kernel_npoints,
+        kernel_npoints] [, min(table)]); with `knots` also (k_b knots, Romberg levels), each
+        [n_pairs, kernel_npoints]."""
+        n = self.config.kernel_npoints
+        info, tab, lev, mn = numpy.empty(7), numpy.empty((n, n)), numpy.empty((n, n)), numpy.empty(1)
+        kb = kl = None
+        if knots:
+            n_pairs = getattr(self, "_%s_blocks_pairs" % term, None)
+            if not n_pairs:
+                raise ChompError("covariance_%s_blocks_table before covariance_%s_blocks" % (term, term))
+            kb, kl = numpy.empty((int(n_pairs), n)), numpy.empty((int(n_pairs), n))
+        self._check(fn(self._h, int(block), _ptr(info), _ptr(tab), _ptr(lev),
+                       *([_ptr(mn)] if minimum else []), _ptr(kb), _ptr(kl)))
+        out = (info, tab, lev.astype(int)) + ((numpy.float64(mn[0]),) if minimum else ())
+        return out + (kb, kl.astype(int)) if knots else out
 
     def covariance_blocks_table(self, block):
         """(ln_K [kernel_npoints], the projected spectra a, b, ab, ba [4, kernel_npoints], their
@@ -1489,43 +1520,22 @@ class Context(object):
         (theta_a, theta_b): host arrays of one length; or theta_a alone, a contiguous float64
         torch cuda tensor holding theta_a[n] then theta_b[n], which stays on the device (so does
         the result)."""
-        ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
-        n_blocks = ep.size * (ep.size + 1) // 2
-        x = numpy.ascontiguousarray(ln_chi, dtype=numpy.float64)
-        y = numpy.ascontiguousarray(sigma2, dtype=numpy.float64)
-        if x.ndim != 2 or x.shape[0] != n_blocks or y.shape != x.shape:
-            raise ValueError("covariance_ssc_blocks: ln_chi and sigma2 must be [%d, n_sigma]"
-                             % n_blocks)
-        pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
-        self._ssc_blocks_pairs = None
-        out = self._run(self._L.chomp_covariance_ssc_blocks, [pairs],
-                        lambda mem, new, th: (
-                            ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
-                            float(ln_ktheta_min), float(ln_ktheta_max), float(j0_ssc_limit),
-                            x.ctypes.data_as(c_double_p), y.ctypes.data_as(c_double_p),
-                            x.shape[1], float(area), th, _numel(th) // 2,
-                            new((n_blocks, _numel(th) // 2)), mem))[0]
-        self._ssc_blocks_pairs = _numel(pairs) // 2      # (what covariance_ssc_blocks_table sizes by)
-        return out
+        def args(n_blocks):
+            x = numpy.ascontiguousarray(ln_chi, dtype=numpy.float64)
+            y = numpy.ascontiguousarray(sigma2, dtype=numpy.float64)
+            if x.ndim != 2 or x.shape[0] != n_blocks or y.shape != x.shape:
+                raise ValueError("covariance_ssc_blocks: ln_chi and sigma2 must be [%d, n_sigma]"
+                                 % n_blocks)
+            return (), (float(ln_ktheta_min), float(ln_ktheta_max), float(j0_ssc_limit), _ptr(x),
+                        _ptr(y), x.shape[1], float(area)), []
+        return self._blocks(self._L.chomp_covariance_ssc_blocks, epochs, theta_a, theta_b, args, "ssc")
 
     def covariance_ssc_blocks_table(self, block, knots=False):
         """One block of the last covariance_ssc_blocks: (info[7] = z_bar_NG, chi(z_bar_NG),
         growth_factor(z_bar_NG), z_min, z_max, chi_min, chi_max; the kernel_ssc table and its
         Romberg levels, each [kernel_npoints, kernel_npoints]); with knots=True also (k_b knots,
         Romberg levels), each [n_pairs, kernel_npoints]."""
-        n = self.config.kernel_npoints
-        info, tab, lev = numpy.empty(7), numpy.empty((n, n)), numpy.empty((n, n))
-        kb = kl = None
-        n_pairs = getattr(self, "_ssc_blocks_pairs", None) if knots else None
-        if knots and not n_pairs:
-            raise ChompError("covariance_ssc_blocks_table before covariance_ssc_blocks")
-        if n_pairs is not None:
-            kb, kl = numpy.empty((int(n_pairs), n)), numpy.empty((int(n_pairs), n))
-        self._check(self._L.chomp_covariance_ssc_blocks_table(
-            self._h, int(block), _ptr(info), _ptr(tab), _ptr(lev), _ptr(kb), _ptr(kl)))
-        if n_pairs is None:
-            return info, tab, lev.astype(int)
-        return info, tab, lev.astype(int), kb, kl.astype(int)
+        return self._blocks_table(self._L.chomp_covariance_ssc_blocks_table, "ssc", block, knots)
 
     def covariance_fourier_zbar(self, z):
         """_calculate_zbar of the four window pairs a1a2, b1b2, a1b2, b1a2 in the two staged slots
@@ -1601,7 +1611,7 @@ class Context(object):
     def covariance_ng_blocks(self, epochs, ln_ktheta_min, ln_ktheta_max, j0_limit, area, tri_table,
                              tri_k_min, tri_k_max, theta_a, theta_b=None):
         """covariance_NG of every block (i, j), i <= j, of len(epochs) correlations for the same
-        pairs of bin centres (chomp_cov_ng_blocks): [n_blocks, n_pairs], the blocks in the
+        pairs of bin centres (chomp_covariance_ng_blocks): [n_blocks, n_pairs], the blocks in the
         row-major order of the upper triangle.  Correlation c is projection set c of the last
         kernel_setup_pairs; a diagonal block is what kernel_setup + kernel_ssc_setup(with_table=
         False) + kernel_ng_setup + covariance_ng return, a cross block what two
@@ -1612,40 +1622,20 @@ class Context(object):
         (theta_a, theta_b): host arrays of one length; or theta_a alone, a contiguous float64
         torch cuda tensor holding theta_a[n] then theta_b[n], which stays on the device (so does
         the result)."""
-        ep = numpy.ascontiguousarray(epochs, dtype=numpy.uintp).ravel()
-        n_blocks = ep.size * (ep.size + 1) // 2
-        tri = numpy.ascontiguousarray(tri_table, dtype=numpy.float64)
-        if tri.ndim != 2 or tri.shape[0] != tri.shape[1]:
-            raise ValueError("covariance_ng_blocks: the I_0^4 table must be square")
-        pairs = theta_a if theta_b is None else _pairs(theta_a, theta_b)
-        out = self._run(self._L.chomp_cov_ng_blocks, [pairs],
-                        lambda mem, new, th: (
-                            ep.size, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
-                            float(ln_ktheta_min), float(ln_ktheta_max), float(j0_limit),
-                            float(area), tri.ctypes.data_as(c_double_p), tri.shape[0],
-                            float(tri_k_min), float(tri_k_max), th, _numel(th) // 2,
-                            new((n_blocks, _numel(th) // 2)), mem))[0]
-        self._ng_blocks_pairs = _numel(pairs) // 2       # (what covariance_ng_blocks_table sizes by)
-        return out
+        def args(n_blocks):
+            tri = numpy.ascontiguousarray(tri_table, dtype=numpy.float64)
+            if tri.ndim != 2 or tri.shape[0] != tri.shape[1]:
+                raise ValueError("covariance_ng_blocks: the I_0^4 table must be square")
+            return (), (float(ln_ktheta_min), float(ln_ktheta_max), float(j0_limit), float(area),
+                        _ptr(tri), tri.shape[0], float(tri_k_min), float(tri_k_max)), []
+        return self._blocks(self._L.chomp_covariance_ng_blocks, epochs, theta_a, theta_b, args, "ng")
 
     def covariance_ng_blocks_table(self, block, knots=False):
         """One block of the last covariance_ng_blocks: (info[7] = z_bar_NG, chi(z_bar_NG),
         growth_factor(z_bar_NG), z_min, z_max, chi_min, chi_max; the kernel_NG table and its
         Romberg levels, each [kernel_npoints, kernel_npoints]; min(table)); with knots=True also
         (k_b knots, Romberg levels), each [n_pairs, kernel_npoints]."""
-        n = self.config.kernel_npoints
-        info, tab, lev, mn = numpy.empty(7), numpy.empty((n, n)), numpy.empty((n, n)), numpy.empty(1)
-        kb = kl = None
-        n_pairs = getattr(self, "_ng_blocks_pairs", None) if knots else None
-        if knots and not n_pairs:
-            raise ChompError("covariance_ng_blocks_table before covariance_ng_blocks")
-        if n_pairs is not None:
-            kb, kl = numpy.empty((int(n_pairs), n)), numpy.empty((int(n_pairs), n))
-        self._check(self._L.chomp_cov_ng_blocks_table(
-            self._h, int(block), _ptr(info), _ptr(tab), _ptr(lev), _ptr(mn), _ptr(kb), _ptr(kl)))
-        if n_pairs is None:
-            return info, tab, lev.astype(int), numpy.float64(mn[0])
-        return info, tab, lev.astype(int), numpy.float64(mn[0]), kb, kl.astype(int)
+        return self._blocks_table(self._L.chomp_covariance_ng_blocks_table, "ng", block, knots, True)
 
     def hod_stats(self, epoch0=0, n=None):
         """[n, 3]: effective bias, effective halo mass, satellite fraction."""

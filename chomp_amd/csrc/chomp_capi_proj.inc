@@ -1378,6 +1378,118 @@ static int blocks_index_upload(chomp_ctx* ctx, StagedBuffer<int>& d_index, const
   return upload(ctx, d_index, index.data(), index.size() * sizeof(int));
 }
 
+// One call on the block axis (chomp_covariance_blocks, _ssc_blocks, _ng_blocks): its staged
+// arrays, the sizes n_corr gives and where the sets of the last set-up lie.  The steps are made
+// in the order written here; a call makes its own refusals and launches between them.
+// (member templates need C++ linkage too)
+extern "C++" struct BlocksCall {
+  chomp_ctx* ctx;
+  const char* who;
+  Staging st;
+  const ProjSets& S;
+  const ProjLayout& L;                   // the sets'
+  const size_t n_corr, n_pairs, n_blocks, n_cross, pstride;
+  const int nc;
+  const unsigned Z;                      // n_blocks, as a grid's extent
+  const int *d_index = nullptr, *d_diag = nullptr, *d_cross = nullptr;   // (begin)
+  double *d_knots = nullptr, *d_lev = nullptr;
+  const double* d_theta = nullptr;       // (place)
+  double* d_out = nullptr;
+
+  BlocksCall(chomp_ctx* c, const char* w, int mem, size_t n, size_t pairs)
+      : ctx(c), who(w), st(c, mem, w), S(c->sets), L(S.L), n_corr(n), n_pairs(pairs),
+        n_blocks(n * (n + 1) / 2), n_cross(n_blocks - n), pstride((size_t)L.total), nc((int)n),
+        Z((unsigned)n_blocks) {}
+  int refuse(int code, const std::string& text) const { return fail(ctx, code, std::string(who) + text); }
+  // What every call refuses first (the null context aside): "bad args" (`args`: its arrays are
+  // there), a `mem` that Staging does not know, blocks_check.
+  int head(bool args, bool overlap) {
+    if (!args || n_corr == 0 || n_pairs == 0) return refuse(CHOMP_ERR_ARG, ": bad args");
+    if (st.rc) return st.rc;
+    return blocks_check(ctx, who, n_corr, overlap);
+  }
+  // check(c): the term's refusal of correlation c's epoch, its text in ctx->err.
+  template <class Check>
+  int epochs(Check&& check) {
+    for (size_t c = 0; c < n_corr; ++c) {
+      const int rc = check(c);
+      if (rc) return refuse(rc, ": correlation " + std::to_string(c) + ": " + ctx->err);
+    }
+    return CHOMP_OK;
+  }
+  // Behind the last refusal: the state's last result is given up, its buffers grown to `slabs`
+  // doubles of slabs and `kb` of k_b knots and levels, the index block (with the lists) sent.
+  int begin(TermBlocksState& B, size_t slabs, size_t kb, const size_t* epoch) {
+    B.n_corr = 0;
+    int rc = ensure(ctx, B.d, slabs);
+    if (!rc) rc = ensure(ctx, B.d_kb, kb);
+    if (!rc) rc = blocks_index_upload(ctx, B.d_index, blocks_index(n_corr, epoch, true));
+    if (rc) return rc;
+    d_index = B.d_index;
+    d_diag = d_index + n_corr + 2 * n_blocks;
+    d_cross = d_diag + n_corr;
+    d_knots = B.d_kb;
+    d_lev = d_knots + kb / 2;
+    return CHOMP_OK;
+  }
+  // theta[2 n_pairs] in, out[n_blocks][n_pairs] out.
+  int place(const double* theta, double* out) {
+    st.in(theta, 2 * n_pairs, &d_theta);
+    st.out(out, n_blocks * n_pairs, &d_out);
+    return st.place();
+  }
+  // The two instances of a term's prep or table kernel over slabs of layout T: <false> over the
+  // list of diagonal blocks, then <true> over that of the cross blocks, if there are any.  Grid
+  // (x, listed blocks), or (listed blocks) for x == 0; sh: the dynamic LDS of each; `more`: the
+  // arguments behind the list.
+  template <class Diag, class Cross, class Layout, class... More>
+  void lists(Diag* diag, Cross* cross, unsigned x, const size_t (&sh)[2], const Layout& T,
+             const More&... more) const {
+    const auto grid = [x](size_t n) { return x ? dim3(x, (unsigned)n) : dim3((unsigned)n); };
+    hipLaunchKernelGGL(diag, grid(n_corr), dim3(256), sh[0], ctx->stream, ctx->cfg, L, T, nc, S.d_pd,
+                       S.d_tab, pstride, d_index, d_diag, more...);
+    if (n_cross)
+      hipLaunchKernelGGL(cross, grid(n_cross), dim3(256), sh[1], ctx->stream, ctx->cfg, L, T, nc,
+                         S.d_pd, S.d_tab, pstride, d_index, d_cross, more...);
+  }
+  // The tail: every block's pairs from their k_b knots, and the state readable again.
+  int finish(TermBlocksState& B, size_t sh_outer, double area) {
+    hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256), sh_outer,
+                       ctx->stream, ctx->cfg, area, d_knots, d_out);
+    HIPCHK(hipGetLastError());
+    B.n_corr = n_corr;
+    B.n_pairs = n_pairs;
+    return st.finish();
+  }
+};
+
+// One block of the last call of a term on the block axis, for chomp_covariance_<who>_table (host
+// arrays, any may be NULL): info[7], the table and its levels [N, N] of layout T, scalar
+// `extra_at` of the slab, and the block's k_b knots and levels.
+extern "C++" template <class Layout>
+static int term_blocks_table(chomp_ctx* ctx, const char* who, const TermBlocksState& B,
+                             const Layout& T, size_t block, double* info, double* table,
+                             double* levels, double* extra, int extra_at, double* kb_knots,
+                             double* kb_levels) {
+  if (B.n_corr == 0)
+    return fail(ctx, CHOMP_ERR_STATE, std::string(who) + "_table before " + who);
+  const size_t n_blocks = B.n_corr * (B.n_corr + 1) / 2;
+  if (block >= n_blocks) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + "_table: block");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int z_bar = T.scal + kSscZBar, z_min = T.scal + kSscZMin, at = T.scal + extra_at;
+  const size_t NN = (size_t)T.N * T.N;
+  const int rc = slab_read(ctx, B.d + block * (size_t)T.total,
+                           {{info, &z_bar, 1, 3}, {info ? info + 3 : nullptr, &z_min, 1, 4},
+                            {table, &T.tab, 1, NN}, {levels, &T.lev, 1, NN}, {extra, &at, 1, 1}}, true);
+  if (rc) return rc;
+  const size_t row = B.n_pairs * (size_t)ctx->cfg.kernel_npoints;
+  if (kb_knots) HIPCHK(hipMemcpy(kb_knots, B.d_kb + block * row, row * sizeof(double), hipMemcpyDeviceToHost));
+  if (kb_levels)
+    HIPCHK(hipMemcpy(kb_levels, B.d_kb + (n_blocks + block) * row, row * sizeof(double), hipMemcpyDeviceToHost));
+  return CHOMP_OK;
+}
+
 // The pairs of angles of chomp_covariance_ssc, _ssc_cross and _ng: what they refuse ...
 static int pairs_check(chomp_ctx* ctx, const char* who, double area, size_t n) {
   if (!(area > 0.0)) return fail(ctx, CHOMP_ERR_ARG, std::string(who) + ": area must be positive");
@@ -1627,26 +1739,21 @@ int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size
                             const double* theta, size_t n_pairs, double* out, int mem) {
   StageRange range_(ctx, "chomp:covariance_blocks");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!epoch || !poisson || !theta || !out || n_corr == 0 || n_pairs == 0)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: bad args");
-  Staging st(ctx, mem, "covariance_blocks");
-  if (st.rc) return st.rc;
-  int rc = blocks_check(ctx, "covariance_blocks", n_corr, false);
+  BlocksCall A(ctx, "covariance_blocks", mem, n_corr, n_pairs);
+  int rc = A.head(epoch && poisson && theta && out, false);
   if (rc) return rc;
-  const ProjSets& S = ctx->sets;
-  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
-  if (n_pairs > 0x7fffffffu / n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_blocks: n_pairs * n_blocks too large");
-  for (size_t c = 0; c < n_corr; ++c) {
-    const int rcp = check_power(ctx, which, epoch[c], 1);
-    if (rcp) return fail(ctx, rcp, "covariance_blocks: correlation " + std::to_string(c) + ": " + ctx->err);
-  }
-  rc = gaussian_scalars(ctx, "covariance_blocks", j0_limit, area);
-  if (!rc) rc = gaussian_theta(ctx, "covariance_blocks", st.host, theta, n_pairs);
+  Staging& st = A.st;
+  const ProjSets& S = A.S;
+  const size_t n_blocks = A.n_blocks;
+  if (n_pairs > 0x7fffffffu / n_blocks) return A.refuse(CHOMP_ERR_ARG, ": n_pairs * n_blocks too large");
+  rc = A.epochs([&](size_t c) { return check_power(ctx, which, epoch[c], 1); });
+  if (!rc) rc = gaussian_scalars(ctx, A.who, j0_limit, area);
+  if (!rc) rc = gaussian_theta(ctx, A.who, st.host, theta, n_pairs);
   if (rc) return rc;
-  const ProjLayout& L = S.L;
+  const ProjLayout& L = A.L;
   const CrossLayout C = make_blocks_layout(L.NKT);
   size_t sh;
-  rc = cross_lds_bytes(ctx, L, "covariance_blocks", &sh);
+  rc = cross_lds_bytes(ctx, L, A.who, &sh);
   if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   for (size_t c = 0; c < n_corr; ++c) {                  // (a no-op unless `which` extrapolates)
@@ -1666,9 +1773,9 @@ int chomp_covariance_blocks(chomp_ctx* ctx, int which, size_t n_corr, const size
   rc = st.place();
   if (rc) return rc;
   B.C = C;
-  const int nc = (int)n_corr;
-  const unsigned Z = (unsigned)n_blocks;
-  const size_t pstride = (size_t)L.total;
+  const int nc = A.nc;
+  const unsigned Z = A.Z;
+  const size_t pstride = A.pstride;
   hipLaunchKernelGGL(k_cov_blocks_prep, dim3((Z + 63) / 64), dim3(64), 0, ctx->stream, L, C, nc,
                      (int)n_blocks, S.d_pd, S.d_tab, pstride, B.d_index, B.d);
   with_flag(ctx->with_bao, [&](auto BAO) {
@@ -2025,12 +2132,6 @@ int chomp_covariance_ssc_cross(chomp_ctx* ctx, double area, const double* theta,
 // The super-sample term of every block of a CovarianceMulti in one call (chomp_cov_kernels.h,
 // "The block axis of the super-sample term")
 // ---------------------------------------------------------------------------
-// The index block of the super-sample calls (with the lists) in their state's buffer.
-static int ssc_blocks_upload_index(chomp_ctx* ctx, size_t n_corr, const size_t* epoch) {
-  SscBlocksState& B = ctx->ssc_blocks;
-  return blocks_index_upload(ctx, B.d_index, blocks_index(n_corr, epoch, true));
-}
-
 int chomp_covariance_ssc_blocks_range(chomp_ctx* ctx, size_t n_corr, double* info) {
   if (!ctx) return CHOMP_ERR_ARG;
   if (!info || n_corr == 0) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks_range: bad args");
@@ -2039,7 +2140,8 @@ int chomp_covariance_ssc_blocks_range(chomp_ctx* ctx, size_t n_corr, double* inf
   HIPCHK(hipSetDevice(ctx->device));
   const ProjSets& S = ctx->sets;
   const size_t n_blocks = n_corr * (n_corr + 1) / 2;
-  rc = ssc_blocks_upload_index(ctx, n_corr, nullptr);
+  // (the index block of the super-sample calls, in their state's buffer)
+  rc = blocks_index_upload(ctx, ctx->ssc_blocks.d_index, blocks_index(n_corr, nullptr, true));
   if (rc) return rc;
   Staging st(ctx, CHOMP_HOST, "covariance_ssc_blocks_range");
   double* d_out;
@@ -2062,53 +2164,36 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
                                 int mem) {
   StageRange range_(ctx, "chomp:covariance_ssc_blocks");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!epoch || !ln_chi || !sigma2 || !theta || !out || n_corr == 0 || n_pairs == 0)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: bad args");
-  Staging st(ctx, mem, "covariance_ssc_blocks");
-  if (st.rc) return st.rc;
-  int rc = blocks_check(ctx, "covariance_ssc_blocks", n_corr, true);
+  BlocksCall A(ctx, "covariance_ssc_blocks", mem, n_corr, n_pairs);
+  int rc = A.head(epoch && ln_chi && sigma2 && theta && out, true);
+  if (!rc) rc = A.epochs([&](size_t c) { return check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch[c], 1, true); });
   if (rc) return rc;
-  for (size_t c = 0; c < n_corr; ++c) {
-    const int rcp = check_power(ctx, CHOMP_P_SSC_RESPONSE, epoch[c], 1, true);
-    if (rcp) return fail(ctx, rcp, "covariance_ssc_blocks: correlation " + std::to_string(c) + ": " + ctx->err);
-  }
-  const ProjSets& S_ = ctx->sets;
-  const ProjLayout& L = S_.L;
-  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  const ProjLayout& L = A.L;
+  const size_t n_blocks = A.n_blocks;
   if (!(ln_ktheta_max > ln_ktheta_min) || !(j0_ssc_limit > 0.0))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: ln(k theta) range / J0 limit");
-  const int N = L.NKT;
-  if (n_sigma < 4 || n_sigma > 256 || N < 4 || N > 256)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: corr_npoints and kernel_npoints must be 4..256");
+    return A.refuse(CHOMP_ERR_ARG, ": ln(k theta) range / J0 limit");
+  if (n_sigma < 4 || n_sigma > 256 || L.NKT < 4 || L.NKT > 256)
+    return A.refuse(CHOMP_ERR_ARG, ": corr_npoints and kernel_npoints must be 4..256");
   for (size_t b = 0; b < n_blocks; ++b)
     for (size_t q = 1; q < n_sigma; ++q)
       if (!(ln_chi[b * n_sigma + q] > ln_chi[b * n_sigma + q - 1]))
-        return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: block " + std::to_string(b) +
-                                        ": ln chi knots must increase");
-  rc = pairs_check(ctx, "covariance_ssc_blocks", area, n_pairs);
+        return A.refuse(CHOMP_ERR_ARG, ": block " + std::to_string(b) + ": ln chi knots must increase");
+  rc = pairs_check(ctx, A.who, area, n_pairs);
+  if (!rc) rc = gaussian_theta(ctx, A.who, A.st.host, theta, n_pairs);
   if (rc) return rc;
-  if (st.host)
-    for (size_t q = 0; q < 2 * n_pairs; ++q)
-      if (!(theta[q] > 0.0)) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: theta must be positive");
   HIPCHK(hipSetDevice(ctx->device));
   const SscPlan plan = ssc_plan(ctx->cfg, ctx->L.NK, L, (int)n_sigma);
   const SscLayout& S = plan.S;
   const int NK = plan.NK;
-  const size_t n_cross = n_blocks - n_corr;
   if (!fits_lds(&k_ssc_blocks_table<false>, plan.sh_table[0]) ||
-      (n_cross && !fits_lds(&k_ssc_blocks_table<true>, plan.sh_table[1])))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: cosmo/window/corr_npoints too large "
-                                    "for the windows of a block");
+      (A.n_cross && !fits_lds(&k_ssc_blocks_table<true>, plan.sh_table[1])))
+    return A.refuse(CHOMP_ERR_ARG, ": cosmo/window/corr_npoints too large for the windows of a block");
   // (one kernel runs both k_b bodies: the launch takes the LDS of the larger)
   if (!fits_lds(ctx->with_bao, &k_ssc_blocks_kb<true>, &k_ssc_blocks_kb<false>, plan.sh_kb[1]))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks: halo/kernel_npoints too large for the "
-                                    "two responses of a cross block");
+    return A.refuse(CHOMP_ERR_ARG, ": halo/kernel_npoints too large for the two responses of a cross block");
   SscBlocksState& B = ctx->ssc_blocks;
-  B.n_corr = 0;
-  rc = ensure(ctx, B.d, n_blocks * (size_t)S.total);
-  if (!rc) rc = ensure(ctx, B.d_kb, 2 * n_blocks * n_pairs * (size_t)NK);
+  rc = A.begin(B, n_blocks * (size_t)S.total, 2 * n_blocks * n_pairs * (size_t)NK, epoch);
   if (!rc) rc = ensure(ctx, B.d_sigma, 2 * n_blocks * n_sigma);
-  if (!rc) rc = ssc_blocks_upload_index(ctx, n_corr, epoch);
   if (rc) return rc;
   double* d_ln_chi = B.d_sigma;
   double* d_sigma2 = d_ln_chi + n_blocks * n_sigma;
@@ -2116,46 +2201,20 @@ int chomp_covariance_ssc_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epo
                         ctx->stream));
   HIPCHK(hipMemcpyAsync(d_sigma2, sigma2, n_blocks * n_sigma * sizeof(double), hipMemcpyHostToDevice,
                         ctx->stream));
-  const double* d_theta;
-  double* d_out;
-  st.in(theta, 2 * n_pairs, &d_theta);
-  st.out(out, n_blocks * n_pairs, &d_out);
-  rc = st.place();
+  rc = A.place(theta, out);
   if (rc) return rc;
   B.S = S;
-  const int nc = (int)n_corr;
-  const unsigned Z = (unsigned)n_blocks;
-  const size_t pstride = (size_t)L.total;
-  const int* d_diag = B.d_index + n_corr + 2 * n_blocks;
-  const int* d_cross = d_diag + n_corr;
-  hipLaunchKernelGGL(k_ssc_blocks_prep<false>, dim3((unsigned)n_corr), dim3(256), 0, ctx->stream,
-                     ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
-                     ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
-  if (n_cross)
-    hipLaunchKernelGGL(k_ssc_blocks_prep<true>, dim3((unsigned)n_cross), dim3(256), 0, ctx->stream,
-                       ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_cross,
-                       ln_ktheta_min, ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
-  hipLaunchKernelGGL(k_ssc_blocks_table<false>, dim3(plan.n_tab, (unsigned)n_corr), dim3(256), plan.sh_table[0],
-                     ctx->stream, ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
-                     ctx->d_j0, B.d);
-  if (n_cross)
-    hipLaunchKernelGGL(k_ssc_blocks_table<true>, dim3(plan.n_tab, (unsigned)n_cross), dim3(256), plan.sh_table[1],
-                       ctx->stream, ctx->cfg, L, S, nc, S_.d_pd, S_.d_tab, pstride, B.d_index,
-                       d_cross, ctx->d_j0, B.d);
-  hipLaunchKernelGGL(k_ssc_blocks_bicubic, dim3(Z), dim3(256), 0, ctx->stream, S, B.d);
-  double* d_knots = B.d_kb;
-  double* d_lev = B.d_kb + n_blocks * n_pairs * (size_t)NK;
+  A.lists(&k_ssc_blocks_prep<false>, &k_ssc_blocks_prep<true>, 0, {0, 0}, S, ln_ktheta_min,
+          ln_ktheta_max, j0_ssc_limit, d_ln_chi, d_sigma2, B.d);
+  A.lists(&k_ssc_blocks_table<false>, &k_ssc_blocks_table<true>, plan.n_tab, plan.sh_table, S,
+          ctx->d_j0, B.d);
+  hipLaunchKernelGGL(k_ssc_blocks_bicubic, dim3(A.Z), dim3(256), 0, ctx->stream, S, B.d);
   with_flag(ctx->with_bao, [&](auto BAO) {
-    hipLaunchKernelGGL(k_ssc_blocks_kb<BAO>, dim3((unsigned)NK, (unsigned)n_pairs, Z), dim3(256),
-                       plan.sh_kb[1], ctx->stream, ctx->cfg, ctx->L, S, nc, ctx->d_epochs, ctx->d_tab,
-                       B.d_index, B.d, d_theta, d_theta + n_pairs, d_knots, d_lev);
+    hipLaunchKernelGGL(k_ssc_blocks_kb<BAO>, dim3((unsigned)NK, (unsigned)n_pairs, A.Z), dim3(256),
+                       plan.sh_kb[1], ctx->stream, ctx->cfg, ctx->L, S, A.nc, ctx->d_epochs, ctx->d_tab,
+                       A.d_index, B.d, A.d_theta, A.d_theta + n_pairs, A.d_knots, A.d_lev);
   });
-  hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256), plan.sh_outer,
-                     ctx->stream, ctx->cfg, area, d_knots, d_out);
-  HIPCHK(hipGetLastError());
-  B.n_corr = n_corr;
-  B.n_pairs = n_pairs;
-  return st.finish();
+  return A.finish(B, plan.sh_outer, area);
 }
 
 // One block of the last chomp_covariance_ssc_blocks (host arrays, any may be NULL).
@@ -2163,24 +2222,8 @@ int chomp_covariance_ssc_blocks_table(chomp_ctx* ctx, size_t block, double* info
                                       double* levels, double* kb_knots, double* kb_levels) {
   if (!ctx) return CHOMP_ERR_ARG;
   const SscBlocksState& B = ctx->ssc_blocks;
-  if (B.n_corr == 0)
-    return fail(ctx, CHOMP_ERR_STATE, "covariance_ssc_blocks_table before covariance_ssc_blocks");
-  const size_t n_blocks = B.n_corr * (B.n_corr + 1) / 2;
-  if (block >= n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_ssc_blocks_table: block");
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const SscLayout& S = B.S;
-  const double* st = B.d + block * (size_t)S.total;
-  const int z_bar = S.scal + kSscZBar, z_min = S.scal + kSscZMin;
-  const size_t NN = (size_t)S.N * S.N;
-  const int rc = slab_read(ctx, st, {{info, &z_bar, 1, 3}, {info ? info + 3 : nullptr, &z_min, 1, 4},
-                                     {table, &S.tab, 1, NN}, {levels, &S.lev, 1, NN}}, true);
-  if (rc) return rc;
-  const size_t row = B.n_pairs * (size_t)ctx->cfg.kernel_npoints;
-  if (kb_knots) HIPCHK(hipMemcpy(kb_knots, B.d_kb + block * row, row * sizeof(double), hipMemcpyDeviceToHost));
-  if (kb_levels)
-    HIPCHK(hipMemcpy(kb_levels, B.d_kb + (n_blocks + block) * row, row * sizeof(double), hipMemcpyDeviceToHost));
-  return CHOMP_OK;
+  return term_blocks_table(ctx, "covariance_ssc_blocks", B, B.S, block, info, table, levels, nullptr,
+                           0, kb_knots, kb_levels);
 }
 
 // ---------------------------------------------------------------------------
@@ -2326,8 +2369,9 @@ static NgBlocksSizes ng_blocks_sizes(size_t n_corr, size_t n_pairs, int n_ktheta
   return Z;
 }
 
-int chomp_cov_ng_blocks_plan(size_t n_corr, const size_t* epoch, size_t n_pairs, size_t n_ktheta,
-                             size_t n_k, size_t n_tri, size_t* sizes, int* index) {
+int chomp_covariance_ng_blocks_plan(size_t n_corr, const size_t* epoch, size_t n_pairs,
+                                    size_t n_ktheta, size_t n_k, size_t n_tri, size_t* sizes,
+                                    int* index) {
   if (!sizes || n_corr == 0 || n_corr > (size_t)kProjSetsMax || n_corr * (n_corr + 1) / 2 > 65535 ||
       n_pairs == 0 || n_pairs > 65535 ||
       n_ktheta < 4 || n_ktheta > 256 || n_k < 4 || n_k > 256 || n_tri < 4 || n_tri > 64)
@@ -2342,41 +2386,34 @@ int chomp_cov_ng_blocks_plan(size_t n_corr, const size_t* epoch, size_t n_pairs,
   return CHOMP_OK;
 }
 
-int chomp_cov_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch,
+int chomp_covariance_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch,
                                double ln_ktheta_min, double ln_ktheta_max, double j0_limit,
                                double area, const double* tri_table, size_t n_tri,
                                double tri_k_min, double tri_k_max, const double* theta,
                                size_t n_pairs, double* out, int mem) {
   StageRange range_(ctx, "chomp:covariance_ng_blocks");
   if (!ctx) return CHOMP_ERR_ARG;
-  if (!tri_table || !theta || !out || n_corr == 0 || n_pairs == 0)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: bad args");
-  Staging st(ctx, mem, "covariance_ng_blocks");
-  if (st.rc) return st.rc;
+  BlocksCall A(ctx, "covariance_ng_blocks", mem, n_corr, n_pairs);
   // (with `overlap`: a block whose windows share no redshift is refused here, from the host's
   //  ranges of the sets)
-  int rc = blocks_check(ctx, "covariance_ng_blocks", n_corr, true);
+  int rc = A.head(tri_table && theta && out, true);
+  if (!rc && epoch)
+    rc = A.epochs([&](size_t c) {
+      return epoch[c] >= ctx->n_epoch ? fail(ctx, CHOMP_ERR_ARG, "epoch range") : CHOMP_OK;
+    });
   if (rc) return rc;
-  for (size_t c = 0; epoch && c < n_corr; ++c)
-    if (epoch[c] >= ctx->n_epoch)
-      return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: correlation " + std::to_string(c) +
-                                      ": epoch range");
-  const ProjSets& S_ = ctx->sets;
-  const ProjLayout& L = S_.L;
-  const size_t n_blocks = n_corr * (n_corr + 1) / 2;
+  const ProjLayout& L = A.L;
   if (!(ln_ktheta_max > ln_ktheta_min) || !(j0_limit > 0.0))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: ln(k theta) range / J0 limit");
-  const int N = L.NKT;
-  if (N < 4 || N > 256)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: kernel_npoints must be 4..256");
-  rc = pairs_check(ctx, "covariance_ng_blocks", area, n_pairs);
+    return A.refuse(CHOMP_ERR_ARG, ": ln(k theta) range / J0 limit");
+  if (L.NKT < 4 || L.NKT > 256) return A.refuse(CHOMP_ERR_ARG, ": kernel_npoints must be 4..256");
+  rc = pairs_check(ctx, A.who, area, n_pairs);
   if (rc) return rc;
   if (n_tri < 4 || n_tri > 64)
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: the I_0^4 table must be 4..64 knots a side");
+    return A.refuse(CHOMP_ERR_ARG, ": the I_0^4 table must be 4..64 knots a side");
   if (!(tri_k_min > 0.0) || !(tri_k_max > tri_k_min))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: the I_0^4 table's k range");
-  if (st.host) {
-    rc = pairs_positive(ctx, "covariance_ng_blocks", theta, n_pairs);
+    return A.refuse(CHOMP_ERR_ARG, ": the I_0^4 table's k range");
+  if (A.st.host) {
+    rc = pairs_positive(ctx, A.who, theta, n_pairs);
     if (rc) return rc;
   }
   HIPCHK(hipSetDevice(ctx->device));
@@ -2384,90 +2421,41 @@ int chomp_cov_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch,
   const NgLayout& G = plan.G;
   const NgTriLayout T = make_ng_tri_layout((int)n_tri);
   const int NK = plan.NK;
-  const size_t n_cross = n_blocks - n_corr;
   const NgBlocksSizes sizes = ng_blocks_sizes(n_corr, n_pairs, G.N, NK, T.N);
   const size_t sh_kb = (size_t)ng_kb_lds_doubles(G.N, T.N) * sizeof(double);
   if (!fits_lds(&k_ng_blocks_table<false>, plan.sh_table[0]) ||
-      (n_cross && !fits_lds(&k_ng_blocks_table<true>, plan.sh_table[1])))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: cosmo/window_npoints too large for the "
-                                    "windows of a block");
+      (A.n_cross && !fits_lds(&k_ng_blocks_table<true>, plan.sh_table[1])))
+    return A.refuse(CHOMP_ERR_ARG, ": cosmo/window_npoints too large for the windows of a block");
   if (!fits_lds(&k_ng_blocks_kb, sh_kb))
-    return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks: kernel_npoints too large for the rows of "
-                                    "the two tables");
+    return A.refuse(CHOMP_ERR_ARG, ": kernel_npoints too large for the rows of the two tables");
   NgBlocksState& B = ctx->ng_blocks;
-  B.n_corr = 0;
-  rc = ensure(ctx, B.d, sizes.slabs);
-  if (!rc) rc = ensure(ctx, B.d_kb, sizes.kb);
+  rc = A.begin(B, sizes.slabs, sizes.kb, epoch);
   if (!rc) rc = ensure(ctx, B.d_tri, sizes.tri);
-  if (!rc) rc = blocks_index_upload(ctx, B.d_index, blocks_index(n_corr, epoch, true));
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(B.d_tri + T.tab, tri_table, n_tri * n_tri * sizeof(double),
                         hipMemcpyHostToDevice, ctx->stream));
-  const double* d_theta;
-  double* d_out;
-  st.in(theta, 2 * n_pairs, &d_theta);
-  st.out(out, n_blocks * n_pairs, &d_out);
-  rc = st.place();
+  rc = A.place(theta, out);
   if (rc) return rc;
   B.G = G;
-  const int nc = (int)n_corr;
-  const unsigned Z = (unsigned)n_blocks;
-  const size_t pstride = (size_t)L.total;
-  const int* d_diag = B.d_index + n_corr + 2 * n_blocks;
-  const int* d_cross = d_diag + n_corr;
   unsigned* d_status = epoch ? (unsigned*)ctx->d_status : nullptr;
   hipLaunchKernelGGL(k_ng_tri, dim3(1), dim3(256), 0, ctx->stream, T, tri_k_min, tri_k_max, B.d_tri);
-  hipLaunchKernelGGL(k_ng_blocks_prep<false>, dim3((unsigned)n_corr), dim3(256), 0, ctx->stream,
-                     ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_diag,
-                     ln_ktheta_min, ln_ktheta_max, j0_limit, B.d, d_status);
-  if (n_cross)
-    hipLaunchKernelGGL(k_ng_blocks_prep<true>, dim3((unsigned)n_cross), dim3(256), 0, ctx->stream,
-                       ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab, pstride, B.d_index, d_cross,
-                       ln_ktheta_min, ln_ktheta_max, j0_limit, B.d, d_status);
-  hipLaunchKernelGGL(k_ng_blocks_table<false>, dim3(plan.n_tab, (unsigned)n_corr), dim3(256),
-                     plan.sh_table[0], ctx->stream, ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab, pstride,
-                     B.d_index, d_diag, ctx->d_j0, B.d, d_status);
-  if (n_cross)
-    hipLaunchKernelGGL(k_ng_blocks_table<true>, dim3(plan.n_tab, (unsigned)n_cross), dim3(256),
-                       plan.sh_table[1], ctx->stream, ctx->cfg, L, G, nc, S_.d_pd, S_.d_tab,
-                       pstride, B.d_index, d_cross, ctx->d_j0, B.d, d_status);
-  hipLaunchKernelGGL(k_ng_blocks_bicubic, dim3(Z), dim3(256), 0, ctx->stream, G, B.d);
-  double* d_knots = B.d_kb;
-  double* d_lev = B.d_kb + n_blocks * n_pairs * (size_t)NK;
-  hipLaunchKernelGGL(k_ng_blocks_kb, dim3((unsigned)NK, (unsigned)n_pairs, Z), dim3(256), sh_kb,
-                     ctx->stream, ctx->cfg, G, T, nc, B.d_index, B.d, B.d_tri, tri_k_min, tri_k_max,
-                     d_theta, d_theta + n_pairs, d_knots, d_lev, d_status);
-  hipLaunchKernelGGL(k_ssc_blocks_outer, dim3((unsigned)n_pairs, Z), dim3(256), plan.sh_outer,
-                     ctx->stream, ctx->cfg, area, d_knots, d_out);
-  HIPCHK(hipGetLastError());
-  B.n_corr = n_corr;
-  B.n_pairs = n_pairs;
-  return st.finish();
+  A.lists(&k_ng_blocks_prep<false>, &k_ng_blocks_prep<true>, 0, {0, 0}, G, ln_ktheta_min,
+          ln_ktheta_max, j0_limit, B.d, d_status);
+  A.lists(&k_ng_blocks_table<false>, &k_ng_blocks_table<true>, plan.n_tab, plan.sh_table, G,
+          ctx->d_j0, B.d, d_status);
+  hipLaunchKernelGGL(k_ng_blocks_bicubic, dim3(A.Z), dim3(256), 0, ctx->stream, G, B.d);
+  hipLaunchKernelGGL(k_ng_blocks_kb, dim3((unsigned)NK, (unsigned)n_pairs, A.Z), dim3(256), sh_kb,
+                     ctx->stream, ctx->cfg, G, T, A.nc, A.d_index, B.d, B.d_tri, tri_k_min,
+                     tri_k_max, A.d_theta, A.d_theta + n_pairs, A.d_knots, A.d_lev, d_status);
+  return A.finish(B, plan.sh_outer, area);
 }
 
-// One block of the last chomp_cov_ng_blocks (host arrays, any may be NULL).
-int chomp_cov_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info, double* table,
+// One block of the last chomp_covariance_ng_blocks (host arrays, any may be NULL).
+int chomp_covariance_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info, double* table,
                                      double* levels, double* table_min, double* kb_knots,
                                      double* kb_levels) {
   if (!ctx) return CHOMP_ERR_ARG;
   const NgBlocksState& B = ctx->ng_blocks;
-  if (B.n_corr == 0)
-    return fail(ctx, CHOMP_ERR_STATE, "covariance_ng_blocks_table before covariance_ng_blocks");
-  const size_t n_blocks = B.n_corr * (B.n_corr + 1) / 2;
-  if (block >= n_blocks) return fail(ctx, CHOMP_ERR_ARG, "covariance_ng_blocks_table: block");
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const NgLayout& G = B.G;
-  const double* ng = B.d + block * (size_t)G.total;
-  const int z_bar = G.scal + kSscZBar, z_min = G.scal + kSscZMin, at_min = G.scal + kNgMin;
-  const size_t NN = (size_t)G.N * G.N;
-  const int rc = slab_read(ctx, ng, {{info, &z_bar, 1, 3}, {info ? info + 3 : nullptr, &z_min, 1, 4},
-                                     {table, &G.tab, 1, NN}, {levels, &G.lev, 1, NN},
-                                     {table_min, &at_min, 1, 1}}, true);
-  if (rc) return rc;
-  const size_t row = B.n_pairs * (size_t)ctx->cfg.kernel_npoints;
-  if (kb_knots) HIPCHK(hipMemcpy(kb_knots, B.d_kb + block * row, row * sizeof(double), hipMemcpyDeviceToHost));
-  if (kb_levels)
-    HIPCHK(hipMemcpy(kb_levels, B.d_kb + (n_blocks + block) * row, row * sizeof(double), hipMemcpyDeviceToHost));
-  return CHOMP_OK;
+  return term_blocks_table(ctx, "covariance_ng_blocks", B, B.G, block, info, table, levels, table_min,
+                           kNgMin, kb_knots, kb_levels);
 }

@@ -743,14 +743,19 @@ __global__ __launch_bounds__(256) void k_ssc_outer(chomp_config cfg, double area
 // launch of its own over a list of its blocks; the kernels behind the table take the block as a
 // grid dimension.  The index block of a call, ints:
 //   epoch[n_corr] | (i, j)[n_blocks] | the diagonal blocks [n_corr] | the cross blocks [n_blocks - n_corr].
-struct SscBlocksState {
-  DeviceBuffer<double> d;  // n_blocks slabs of S.total doubles
+//
+// What the state of a term on the block axis holds whatever the term (this one and the
+// trispectrum's below); a term adds its slab layout and the buffer of what its host sends.
+struct TermBlocksState {
+  DeviceBuffer<double> d;      // n_blocks slabs of the term's layout
   DeviceBuffer<double> d_kb;   // the k_b knots, then their levels: [n_blocks][n_pairs][kernel_npoints] each
-  DeviceBuffer<double> d_sigma;   // the blocks' sigma^2 knots (ln chi, then sigma^2) on their way into the slabs
   StagedBuffer<int> d_index;   // the index block
+  size_t n_corr = 0;           // correlations of the last call (0: none yet)
+  size_t n_pairs = 0;          // ... and its pairs of angles
+};
+struct SscBlocksState : TermBlocksState {
+  DeviceBuffer<double> d_sigma;   // the blocks' sigma^2 knots (ln chi, then sigma^2) on their way into the slabs
   SscLayout S;
-  size_t n_corr = 0;       // correlations of the last call (0: none yet)
-  size_t n_pairs = 0;      // ... and its pairs of angles
 };
 __device__ __forceinline__ CovSrc ssc_blocks_src(const ProjDev* pd, const double* ptab,
                                                  size_t pstride, int i, int j) {
@@ -1216,7 +1221,7 @@ __global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgT
 }
 
 // ---------------------------------------------------------------------------------------------
-// The block axis of the trispectrum term (chomp_cov_ng_blocks: the one-halo trispectrum
+// The block axis of the trispectrum term (chomp_covariance_ng_blocks: the one-halo trispectrum
 // values of every block of a CovarianceMulti(nongaussian_cov=True, cross_terms=True) in one call)
 // ---------------------------------------------------------------------------------------------
 // The blocks, their order and the windows they read are those of the super-sample block axis
@@ -1232,14 +1237,9 @@ __global__ __launch_bounds__(256) void k_ng_kb(chomp_config cfg, NgLayout G, NgT
 // knot is read, so the host sends none.  The two instances of the prep and table bodies differ in
 // their dynamic LDS, so each runs as a launch of its own over a list of its blocks (the index
 // block of the super-sample calls, with the lists).
-struct NgBlocksState {
-  DeviceBuffer<double> d;      // n_blocks slabs of G.total doubles
-  DeviceBuffer<double> d_kb;   // the k_b knots, then their levels: [n_blocks][n_pairs][kernel_npoints] each
+struct NgBlocksState : TermBlocksState {
   DeviceBuffer<double> d_tri;  // the I_0^4 table of the last call and its bicubic (NgTriLayout)
-  StagedBuffer<int> d_index;   // the index block
   NgLayout G;
-  size_t n_corr = 0;           // correlations of the last call (0: none yet)
-  size_t n_pairs = 0;          // ... and its pairs of angles
 };
 
 // grid n listed blocks, block 256: what k_ssc_prep and k_ng_prep leave in a kernel_NG block -- the

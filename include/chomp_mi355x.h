@@ -1113,34 +1113,32 @@ int chomp_covariance_ng(chomp_ctx* ctx, double area, const double* tri_table, si
  * anything is launched: a block whose four windows share no redshift (decided on the host from
  * the sets' ranges).
  *
- * chomp_cov_ng_blocks_table reads block `block` of the last call (host arrays, any may be
+ * chomp_covariance_ng_blocks_table reads block `block` of the last call (host arrays, any may be
  * NULL): info[7] = z_bar_NG, chi(z_bar_NG), growth_factor(z_bar_NG), z_min, z_max, chi_min,
  * chi_max; table and levels [kernel_npoints^2], table_min[1]; kb_knots and kb_levels
  * [n_pairs * kernel_npoints].
  *
- * chomp_cov_ng_blocks_plan is host arithmetic and needs neither a context nor a device: what a
- * call of n_corr correlations and n_pairs pairs keeps on the device, in elements -- sizes[6] =
- * n_blocks, one kernel_NG block (n_ktheta knots a side), all of them, the k_b buffer (knots then
- * levels, n_k knots a pair), the I_0^4 block, the index block -- and, if asked for, that index
- * block, index[n_corr + 3 n_blocks] ints: epoch[n_corr] (NULL: 0 .. n_corr - 1) | (i, j)[n_blocks]
- * | the diagonal blocks [n_corr] | the cross blocks [n_blocks - n_corr].  CHOMP_ERR_ARG beyond
- * the sizes the call itself takes (more than 65535 blocks or pairs included).
- *
- * (The calls are spelled chomp_cov_ng_blocks*, not chomp_covariance_ng_blocks*: the family
- * chomp_covariance_* / chomp_kernel_ssc_* / chomp_kernel_ng_* is a closed list of 24 that the
- * suite pins.  Their messages and the Python methods say covariance_ng_blocks.) */
-int chomp_cov_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch /*[n_corr] or NULL*/,
+ * chomp_covariance_ng_blocks_plan is host arithmetic and needs neither a context nor a device:
+ * what a call of n_corr correlations and n_pairs pairs keeps on the device, in elements --
+ * sizes[6] = n_blocks, one kernel_NG block (n_ktheta knots a side), all of them, the k_b buffer
+ * (knots then levels, n_k knots a pair), the I_0^4 block, the index block -- and, if asked for,
+ * that index block, index[n_corr + 3 n_blocks] ints: epoch[n_corr] (NULL: 0 .. n_corr - 1) |
+ * (i, j)[n_blocks] | the diagonal blocks [n_corr] | the cross blocks [n_blocks - n_corr].
+ * CHOMP_ERR_ARG beyond the sizes the call itself takes (more than 65535 blocks or pairs
+ * included). */
+int chomp_covariance_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch /*[n_corr] or NULL*/,
                                double ln_ktheta_min, double ln_ktheta_max, double j0_limit,
                                double area, const double* tri_table, size_t n_tri,
                                double tri_k_min, double tri_k_max,
                                const double* theta /*[2][n_pairs]*/, size_t n_pairs,
                                double* out /*[n_blocks][n_pairs]*/, int mem);
-int chomp_cov_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info /*[7]*/, double* table,
-                              double* levels, double* table_min, double* kb_knots,
-                              double* kb_levels);
-int chomp_cov_ng_blocks_plan(size_t n_corr, const size_t* epoch /*[n_corr] or NULL*/,
-                             size_t n_pairs, size_t n_ktheta, size_t n_k, size_t n_tri,
-                             size_t* sizes /*[6]*/, int* index /*[n_corr + 3 n_blocks] or NULL*/);
+int chomp_covariance_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info /*[7]*/,
+                                     double* table, double* levels, double* table_min,
+                                     double* kb_knots, double* kb_levels);
+int chomp_covariance_ng_blocks_plan(size_t n_corr, const size_t* epoch /*[n_corr] or NULL*/,
+                                    size_t n_pairs, size_t n_ktheta, size_t n_k, size_t n_tri,
+                                    size_t* sizes /*[6]*/,
+                                    int* index /*[n_corr + 3 n_blocks] or NULL*/);
 
 /* CorrelationFourier.correlation(l) (correlation.py:360-392): Limber C_l. */
 int chomp_cell(chomp_ctx* ctx, int which, size_t epoch, double D_z,

@@ -1,5 +1,5 @@
 """Host side of the trispectrum term in CovarianceMulti.get_covariance_batched(trispectrum=True) /
-chomp_cov_ng_blocks: the C declarations and their bindings, what the batch's scope serves with the
+chomp_covariance_ng_blocks: the C declarations and their bindings, what the batch's scope serves with the
 keyword and what it refuses with and without it (before any device context exists), the plan of
 the call -- its index block and the sizes of what it keeps on the device -- and the route of the
 call on a stubbed grid and context.  No device."""
@@ -41,17 +41,17 @@ def test_header_declares_the_entry_points_and_the_bindings_match():
         header = f.read()
     flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
     decls = {
-        "chomp_cov_ng_blocks":
-            "int chomp_cov_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch , "
+        "chomp_covariance_ng_blocks":
+            "int chomp_covariance_ng_blocks(chomp_ctx* ctx, size_t n_corr, const size_t* epoch , "
             "double ln_ktheta_min, double ln_ktheta_max, double j0_limit, double area, "
             "const double* tri_table, size_t n_tri, double tri_k_min, double tri_k_max, "
             "const double* theta , size_t n_pairs, double* out , int mem);",
-        "chomp_cov_ng_blocks_table":
-            "int chomp_cov_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info , "
+        "chomp_covariance_ng_blocks_table":
+            "int chomp_covariance_ng_blocks_table(chomp_ctx* ctx, size_t block, double* info , "
             "double* table, double* levels, double* table_min, double* kb_knots, "
             "double* kb_levels);",
-        "chomp_cov_ng_blocks_plan":
-            "int chomp_cov_ng_blocks_plan(size_t n_corr, const size_t* epoch , size_t n_pairs, "
+        "chomp_covariance_ng_blocks_plan":
+            "int chomp_covariance_ng_blocks_plan(size_t n_corr, const size_t* epoch , size_t n_pairs, "
             "size_t n_ktheta, size_t n_k, size_t n_tri, size_t* sizes , int* index );"}
     for decl in decls.values():
         assert decl in flat, decl
@@ -76,14 +76,14 @@ def test_header_declares_the_entry_points_and_the_bindings_match():
         for t, g in zip(types, got):
             assert g in kinds[t], (name, t, g)
         assert getattr(L, name).restype is ctypes.c_int
-    at = L.chomp_cov_ng_blocks.argtypes
+    at = L.chomp_covariance_ng_blocks.argtypes
     assert at[7] == dp                                  # tri_table: host only
     assert at[11] == vp and at[13] == vp                # theta, out: host or device
-    assert L.chomp_cov_ng_blocks_table.argtypes[2:] == [dp] * 6
+    assert L.chomp_covariance_ng_blocks_table.argtypes[2:] == [dp] * 6
     for name in ("covariance_ng_blocks", "covariance_ng_blocks_table"):
         assert callable(getattr(_lib.Context, name))
     # a null context is CHOMP_ERR_ARG, with no message to write
-    for name in ("chomp_cov_ng_blocks", "chomp_cov_ng_blocks_table"):
+    for name in ("chomp_covariance_ng_blocks", "chomp_covariance_ng_blocks_table"):
         fn = getattr(L, name)
         args = [0.0 if t is ctypes.c_double else 0 if t in (ctypes.c_int, sz) else None
                 for t in fn.argtypes]
@@ -108,7 +108,7 @@ def _tri(N):
 def test_plan_index_block_and_sizes(n_corr, n_pairs):
     from chomp_amd import _lib
     n_blocks = n_corr * (n_corr + 1) // 2
-    sizes, index = _lib.cov_ng_blocks_plan(n_corr, n_pairs, 50, 50, 50)
+    sizes, index = _lib.covariance_ng_blocks_plan(n_corr, n_pairs, 50, 50, 50)
     assert sizes == dict(n_blocks=n_blocks, slab=_slab(50), slabs=n_blocks * _slab(50),
                          kb=2 * n_blocks * n_pairs * 50, tri=_tri(50), index=n_corr + 3 * n_blocks)
     assert _slab(50) == 114584 and index.size == sizes["index"] and index.dtype == numpy.intc
@@ -126,7 +126,7 @@ def test_plan_index_block_and_sizes(n_corr, n_pairs):
     assert (2 * n_blocks - 1) * n_pairs * 50 + n_pairs * 50 <= sizes["kb"]
     # the caller's epochs, and other sizes
     ep = numpy.arange(n_corr)[::-1] + 2
-    sizes2, index2 = _lib.cov_ng_blocks_plan(n_corr, 3, 20, 30, 8, epochs=ep)
+    sizes2, index2 = _lib.covariance_ng_blocks_plan(n_corr, 3, 20, 30, 8, epochs=ep)
     assert list(index2[:n_corr]) == list(ep) and numpy.array_equal(index2[n_corr:], index[n_corr:])
     assert sizes2 == dict(n_blocks=n_blocks, slab=_slab(20), slabs=n_blocks * _slab(20),
                           kb=2 * n_blocks * 3 * 30, tri=_tri(8), index=index.size)
@@ -137,11 +137,11 @@ def test_plan_refuses_what_the_call_refuses():
     for args in ((0, 10, 50, 50, 50), (3, 0, 50, 50, 50), (3, 65536, 50, 50, 50), (3, 10, 3, 50, 50),
                  (3, 10, 50, 257, 50), (3, 10, 50, 50, 3), (3, 10, 50, 50, 65), (1025, 10, 50, 50, 50),
                  (362, 10, 50, 50, 50)):                  # (362 * 363 / 2 = 65703 blocks)
-        with pytest.raises(ValueError, match="cov_ng_blocks_plan"):
-            _lib.cov_ng_blocks_plan(*args)
-    assert _lib.cov_ng_blocks_plan(361, 10, 50, 50, 50)[0]["n_blocks"] == 65341
+        with pytest.raises(ValueError, match="covariance_ng_blocks_plan"):
+            _lib.covariance_ng_blocks_plan(*args)
+    assert _lib.covariance_ng_blocks_plan(361, 10, 50, 50, 50)[0]["n_blocks"] == 65341
     with pytest.raises(ValueError, match=r"epochs must be \[n_corr\]"):
-        _lib.cov_ng_blocks_plan(3, 10, 50, 50, 50, epochs=[0, 1])
+        _lib.covariance_ng_blocks_plan(3, 10, 50, 50, 50, epochs=[0, 1])
 
 
 def test_scope_serves_the_trispectrum_blocks_with_the_keyword(no_device):  # noqa: F811

@@ -272,3 +272,26 @@ def test_halo_grid_setup_asks_for_further_families(monkeypatch):
     hg.setup("power_gg", families=_lib.FAM_SSC)
     assert seen == [_lib.FAM_MM, _lib.FAM_MM | _lib.FAM_SSC, _lib.FAM_GG | _lib.FAM_SSC]
     assert hg._tables == _lib.FAM_GG | _lib.FAM_SSC
+
+
+def test_the_knots_of_a_table_need_a_call_that_succeeded():
+    """covariance_ssc_blocks_table and covariance_ng_blocks_table share one rule: the k_b knots are
+    sized by the pairs of the last successful call, so knots=True before one raises, and the
+    library is not called."""
+    from chomp_amd import _lib
+
+    def called(*args):
+        raise AssertionError("the library was called")
+
+    class L(object):
+        chomp_covariance_ssc_blocks_table = chomp_covariance_ng_blocks_table = staticmethod(called)
+    ctx = _lib.Context.__new__(_lib.Context)
+    ctx._L, ctx._h = L, None
+    ctx.config = type("Config", (object,), {"kernel_npoints": 4})
+    for term in ("ssc", "ng"):
+        table = getattr(ctx, "covariance_%s_blocks_table" % term)
+        with pytest.raises(_lib.ChompError) as e:
+            table(0, knots=True)
+        assert str(e.value) == "covariance_%s_blocks_table before covariance_%s_blocks" % (term, term)
+        with pytest.raises(AssertionError, match="the library was called"):
+            table(0)                                 # (without knots the C state decides)

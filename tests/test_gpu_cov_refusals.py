@@ -248,12 +248,13 @@ def _lib_names():
 
 
 def test_null_context():
-    """Every covariance call returns CHOMP_ERR_ARG for a null context (there is no message)."""
+    """Every covariance call returns CHOMP_ERR_ARG for a null context (there is no message); so
+    does chomp_covariance_ng_blocks_plan, which takes no context, for its all-zero arguments."""
     _lib = _lib_names()[0]
     L = _lib.lib()
     names = [n for n in _lib.EXPORTS if n.startswith(("chomp_covariance_", "chomp_kernel_ssc_",
                                                       "chomp_kernel_ng_"))]
-    assert len(names) == 24, names
+    assert len(names) == 27, names
     for name in names:
         fn = getattr(L, name)
         args = [0.0 if t is ctypes.c_double else 0 if t in (ctypes.c_int, ctypes.c_size_t) else None

@@ -1,5 +1,5 @@
 """The one-halo trispectrum term of every block of a CovarianceMulti in one call:
-Context.covariance_ng_blocks (chomp_cov_ng_blocks) against the single-block calls on the same
+Context.covariance_ng_blocks (chomp_covariance_ng_blocks) against the single-block calls on the same
 context (bit for bit), CovarianceMulti.get_covariance_batched(trispectrum=True) against the loop
 get_covariance() on fresh objects and against the reference's numbers (G30), the seams of the call
 and its refusals.
@@ -47,7 +47,7 @@ class Staged(object):
     """One context with the three kernels as projection sets and the three epochs of a HaloGrid
     at their z_bar (with the response's families, for the super-sample batch of the seams), and
     the I_0^4 table of the trispectrum object: what get_covariance_batched(trispectrum=True)
-    hands chomp_cov_ng_blocks."""
+    hands chomp_covariance_ng_blocks."""
 
     def __init__(self):
         from chomp_amd import _lib, correlation, grid, kernel
@@ -382,7 +382,7 @@ def test_null_epochs_give_the_same_values(staged):
     assert numpy.array_equal(S.hg.status() & _ng_bit(), S.words)
     out = numpy.empty((6, 10))
     th = numpy.concatenate([S.ta, S.tb])
-    S.ctx._check(S.ctx._L.chomp_cov_ng_blocks(
+    S.ctx._check(S.ctx._L.chomp_covariance_ng_blocks(
         S.ctx._h, 3, None, S.kt[0], S.kt[1], S.kt[2], S.area, S.table.ctypes.data_as(_lib.c_double_p),
         S.table.shape[0], S.k_range[0], S.k_range[1], th.ctypes.data, 10, out.ctypes.data, _lib.HOST))
     assert numpy.array_equal(out, S.first)

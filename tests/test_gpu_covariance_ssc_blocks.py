@@ -359,6 +359,9 @@ def test_refusals(staged):
         ctx.covariance_ssc_blocks_range(2)
     with pytest.raises(ValueError, match="covariance_ssc_blocks_table: block"):
         ctx.covariance_ssc_blocks_table(6)
+    # a refused call leaves the last result readable, its k_b knots included
+    assert all(numpy.array_equal(x, y) for x, y in
+               zip(ctx.covariance_ssc_blocks_table(1, knots=True), S.tables[1]))
     # a context without sets; epochs without the response's tables; sets of Bessel order 2
     hg = grid.HaloGrid(numpy.zeros(3))
     hg.setup("power_mm")

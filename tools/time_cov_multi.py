@@ -24,7 +24,7 @@ one fixed redshift for all blocks: per cross block the loop adds the kernel_ssc 
 read-back of the chi range, a host sigma_r call), kernel_NG (the 1275 integrals of the table, a
 read-back of it, its bicubic) and covariance_NG (the upload and bicubic of the I_0^4 table, the
 k_b and outer integrals); the batch, get_covariance_batched(trispectrum=True), adds
-chomp_cov_ng_blocks alone.  --ng --ssc: all three terms.
+chomp_covariance_ng_blocks alone.  --ng --ssc: all three terms.
 
 Timed, host clock around calls that end with their result on the host (so synchronised):
     loop_first / batch_first   the first call on fresh objects (contexts, buffers, code objects)
